@@ -19,6 +19,9 @@ batch shards by index range with no collective on the data path (weak scaling: e
 own 2^26 points), the only communication being a barrier + device synchronise either side of the K timed steps and the
 max over ranks of each rank's own elapsed time (taken after its synchronise, before the closing barrier).
 
+`--dump-outputs DIR` writes what the headline's last timed step computed as DIR/<name>.npy (rank 0's shard; a seeded sample
+of the points where the planes exceed 48 MiB), so that two builds can be compared output for output.
+
 `roofline`: algorithmic bytes per launch / average kernel duration (HIP events on the launch
 stream) against the 8 TB/s HBM3E peak.  `cpu_baseline`: the CPU oracle (a port of the reference's
 scalar closure code) timed on this host's cores on a bounded sample of the same workload.
@@ -65,6 +68,13 @@ from bench_workloads import (DISNEY_UNIFORM, PLANES, SEED, SKIN_UNIFORM, S_KS, S
 
 # BASELINE.json configs -> (workload, log2 of the points ONE GPU holds): config 4 is 2^28 points over 8 GPUs, config 5 2^30
 CONFIG_PRESETS = {2: ("ggx_reflect_refract", 26), 3: ("disney_integrate", 26), 4: ("sss_probe", 25), 5: ("skin", 27)}
+
+# --dump-outputs: at most this many bytes of output planes (the .npy headers fit in what is left of 64 MB), and the seed of
+# the sample of points that larger batches are written at
+DUMP_BUDGET_BYTES = 48 << 20
+DUMP_SEED = 20260101
+# names of the planes of workloads whose `outputs` is a tuple (dict outputs are named by their keys)
+OUTPUT_NAMES = {"ggx_reflect_refract": ("wi", "f", "pdf", "fresnel", "wt", "weight")}
 
 # the `workloads` block of the default line: (workload, log2 points per GPU, timed steps)
 BLOCK_ALL = [("ggx_reflect_refract_uniform", 26, 40), ("ggx_reflect", 26, 40), ("ggx_eval", 26, 40), ("ggx_pdf", 26, 40),
@@ -124,11 +134,18 @@ def parse_args():
                     help="after the timed region: the order-independent 64-bit checksum (rls_checksum) of every output plane "
                          "of this rank's shard, gathered over the ranks; the shard sums of a G-rank run add up (mod 2^64) "
                          "to the sum of one process over the same G * n points (validation, BASELINE configs 2-5 only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region: the output planes of the headline's last timed step as DIR/<name>.npy "
+                         "(float32; rank 0's shard), for comparing two builds output for output.  A batch whose outputs exceed "
+                         f"{DUMP_BUDGET_BYTES >> 20} MiB is written at a fixed, seeded sample of its points (BASELINE "
+                         "configurations 2-5 only)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target seconds of CPU-baseline work (headline)")
     ap.add_argument("--block-cpu-seconds", type=float, default=2.5, help="the same for each record of the workloads block")
     ap.add_argument("--block-log2-points", type=int, default=None,
                     help="every record of the workloads block at 2^this points per GPU instead of its configuration's size (tests)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.host_resident:
         a.workload = "ggx_reflect_refract_host"
         if a.log2_points is None:
@@ -537,12 +554,55 @@ def roofline_record(wl, n: int, kernel_ms: float, math: str, clock: dict | None 
 STAMPED = ("ggx_reflect_refract", "disney_integrate", "sss_probe", "skin")      # workloads whose kernel has a stamped instantiation
 
 
+def dump_sample(n: int, rows: int):
+    """The points --dump-outputs writes of an n-point batch with `rows` output planes: None (all of them) when they fit in
+    DUMP_BUDGET_BYTES, else a sorted, seeded sample of distinct indices -- the same for every run with the same n and rows."""
+    import numpy as np
+    k = n
+    while k > 1 and k * rows * 4 > DUMP_BUDGET_BYTES:
+        k //= 2
+    if k == n:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(wl, n: int, directory: str) -> dict:
+    """Write the output planes of the last launch of `wl` (what a caller of the verb receives) to directory/<name>.npy:
+    [3, k] for vectors and colours, [k] for scalars, k = n or the dump_sample of n.  -> a record of what was written."""
+    import numpy as np
+    import torch
+    outs = getattr(wl, "outputs", None)
+    if outs is None:
+        raise SystemExit(f"bench.py: --dump-outputs covers the BASELINE configurations, not {wl.name}")
+    if isinstance(outs, dict):
+        planes = dict(outs)
+    else:
+        names = OUTPUT_NAMES.get(wl.name) or tuple(f"out{i}" for i in range(len(outs)))
+        planes = dict(zip(names, outs))
+    rows = sum(1 if t.dim() == 1 else t.shape[0] for t in planes.values())
+    sample = dump_sample(n, rows)
+    out_dir = Path(directory)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    files = {}
+    for name, t in planes.items():
+        if sample is not None:
+            t = t.index_select(t.dim() - 1, torch.from_numpy(sample).to(t.device))
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(out_dir / f"{name}.npy", a)
+        files[name] = list(a.shape)
+    return {"dir": str(out_dir), "points": n if sample is None else len(sample), "of_points": n,
+            "sample_seed": None if sample is None else DUMP_SEED, "files": files}
+
+
 def measure(R, ctx, ranks, torch, name: str, log2n: int, steps: int, warmup: int, math: str, candidates: int,
-            chunk_log2: int, other_mode: bool, depth: int = 3, clock: bool = True, sustain: float = 0.0):
+            chunk_log2: int, other_mode: bool, depth: int = 3, clock: bool = True, sustain: float = 0.0, capture=None):
     """Build one workload on this rank's shard, warm it up, time `steps` passes between barriers.
     -> dict: wl, n, elapsed [s, max over ranks of each rank's own K steps], wall [s, rank 0's clock from the opening barrier's
     exit to the closing barrier's exit: last end - first start], kernel_ms [per step, max over ranks], my_kernel_ms,
-    other_ms [kernel ms per step in the other arithmetic mode or None], clock [dict or None]"""
+    other_ms [kernel ms per step in the other arithmetic mode or None], clock [dict or None], captured [what capture(wl, n)
+    returned, called right after the timed steps and before anything launches again; or None]"""
     from rlshaders_amd.sharding import shard_range
     world, rank = ranks.world, ranks.rank
     n = 1 << log2n
@@ -575,6 +635,7 @@ def measure(R, ctx, ranks, torch, name: str, log2n: int, steps: int, warmup: int
     if wl.bound == "pcie":                 # the pipeline runs on its own streams and returns when the batch is back in host
         my_kernel_ms = elapsed / max(steps, 1) * 1e3      # memory: the pass is timed on the host clock
     elapsed, kernel_ms = ranks.max_over_ranks([elapsed, my_kernel_ms])
+    captured = capture(wl, n) if capture is not None else None
     clock_rec = None
     if clock and name in STAMPED and wl.launches_per_step == 1:
         # the clock the kernel ran at: the same K launches again, right behind the timed ones, as the stamped instantiation
@@ -608,7 +669,7 @@ def measure(R, ctx, ranks, torch, name: str, log2n: int, steps: int, warmup: int
         other_ms = ranks.max_over_ranks([ctx.timer_elapsed_ms() / 5])[0]
         ctx.set_math_mode(math == "fast")
     return {"wl": wl, "n": n, "elapsed": elapsed, "wall": wall, "kernel_ms": kernel_ms, "my_kernel_ms": my_kernel_ms,
-            "other_ms": other_ms, "clock": clock_rec}
+            "other_ms": other_ms, "clock": clock_rec, "captured": captured}
 
 
 # what tests/test_gpu_fast_mode.py holds RLS_MATH_FAST to (the measurement: profiles/r04_fast_conditioning.json)
@@ -870,7 +931,8 @@ def run_rank(args, world: int):
 
     m = measure(R, ctx, ranks, torch, args.workload, args.log2_points, args.steps, args.warmup, args.math, args.arena_candidates,
                 args.chunk_log2, not (args.checksum or args.no_other_mode),       # (the other mode would overwrite the outputs)
-                args.pipeline_depth, clock=not args.no_clock, sustain=args.sustain_seconds)
+                args.pipeline_depth, clock=not args.no_clock, sustain=args.sustain_seconds,
+                capture=(lambda w, n_: dump_outputs(w, n_, args.dump_outputs)) if args.dump_outputs and rank == 0 else None)
     wl, n, elapsed, kernel_ms, my_ms, other_ms = m["wl"], m["n"], m["elapsed"], m["kernel_ms"], m["my_kernel_ms"], m["other_ms"]
     per_rank_ms = ranks.gather_objects(round(my_ms, 5))
     shard_sums = None
@@ -933,6 +995,8 @@ def run_rank(args, world: int):
                                          "parity": FAST_PARITY if other == "fast" else "bit-exact against the CPU oracle"}
         if cpu_records.get("headline"):
             detail["cpu_baseline"] = cpu_records["headline"]
+        if m["captured"] is not None:
+            detail["outputs_dump"] = m["captured"]
     del wl, m
     torch.cuda.empty_cache()
 

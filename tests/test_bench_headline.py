@@ -217,3 +217,23 @@ def test_a_rank_that_hangs_gives_up_at_the_deadline():
     assert p.returncode == 1 and took < 30, (p.returncode, took)
     errs = _error_lines(p.stdout)
     assert len(errs) == 1 and "deadline" in errs[0]["error"] and errs[0]["rank"] == 0
+
+
+def test_steps_must_be_at_least_one():
+    """--steps is the number of timed steps ms_per_step divides by: zero or fewer is a usage error before anything runs"""
+    p, took = _run_bench(["--steps", "0"])
+    assert p.returncode == 2 and "--steps" in p.stderr and took < 60, (p.returncode, p.stderr[-2000:])
+
+
+def test_dump_sample_is_seeded_and_within_64_mb():
+    """--dump-outputs: a batch whose output planes fit the budget is written whole; a larger one at a sorted sample of distinct
+    points that is the same in every run, so that the files of two builds compare point for point"""
+    b = _bench()
+    assert b.dump_sample(1 << 16, 12) is None
+    s = b.dump_sample(1 << 26, 12)                          # config 2: wi3 f3 pdf fresnel wt3 weight
+    assert len(s) == 1 << 20 and s.dtype.kind == "i" and s[0] >= 0 and s[-1] < 1 << 26
+    assert (s[1:] > s[:-1]).all()                           # sorted, no index twice
+    assert (s == b.dump_sample(1 << 26, 12)).all()
+    for n, rows in ((1 << 26, 12), (1 << 27, 24), (1 << 25, 12), (1 << 26, 8), (3 << 20, 24)):
+        k = n if b.dump_sample(n, rows) is None else len(b.dump_sample(n, rows))
+        assert k * rows * 4 <= b.DUMP_BUDGET_BYTES and k * rows * 4 + 24 * 128 < 64_000_000

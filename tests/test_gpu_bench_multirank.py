@@ -27,6 +27,16 @@ def _bench(world, extra=(), cpu_baseline=False):
     return _parse(p.stdout)
 
 
+def _need_gpus(k):
+    """the 8-rank runs take one GPU per rank (eight processes on one device are more than a shared node should carry);
+    checked before anything is launched"""
+    import torch
+    have = torch.cuda.device_count()
+    if have < k:
+        pytest.skip(f"needs {k} GPUs (one rank each), found {have}")
+    return have
+
+
 def _parse(stdout):
     """the compact headline is the LAST line of stdout, parses on its own and fits a 2000-character tail; the long records
     come before it, one JSON line each, and are attached here under `_records` for the assertions below"""
@@ -125,9 +135,10 @@ def test_rccl_control_path_on_one_gpu():
 @pytest.mark.gpu
 @pytest.mark.parametrize("config", [4, 5])
 def test_eight_rank_dress_rehearsal(config):
-    """BASELINE configs 4 and 5 are 8-GPU jobs.  Eight ranks (gloo, sharing this box's one GPU) at 2^20 points each: the
+    """BASELINE configs 4 and 5 are 8-GPU jobs.  Eight ranks (gloo, one per GPU) at 2^20 points each: the
     shards tile [0, 8 * 2^20), their output checksums add up (mod 2^64) to one process's checksum over the same 2^23 points,
     and the last line is the compact headline with ranks_seen == 8 -- so the driver's 8-GPU run yields a parsed record."""
+    _need_gpus(8)
     eight = _bench(8, ("--config", str(config), "--checksum"))          # _bench passes --log2-points 20
     n = 1 << 20
     assert eight["n_gpus"] == 8 and eight["ranks"]["ranks_seen"] == 8 and eight["ranks"]["world_size"] == 8
@@ -151,18 +162,19 @@ def test_multi_rank_line_is_self_sufficient():
     """an N > 1 line carries `roofline` AND `cpu_baseline` (rank 0 times the CPU leg after the closing
     barrier, outside the timed region, while the other ranks wait), `ranks` keeps distinct_devices, and both clocks of the
     timed region are there: the slowest rank's own K steps (ms_per_step, what `value` is quoted on) and rank 0's
-    barrier-to-barrier wall (ms_per_step_wall).  Eight ranks over gloo on this box's one GPU."""
-    eight = _bench(8, cpu_baseline=True)
-    assert eight["n_gpus"] == 8 and eight["ranks"]["ranks_seen"] == 8
-    assert eight["ranks"]["distinct_devices"] == 1 and eight["ranks"]["world_size"] == 8
-    rf, cb = eight["roofline"], eight["cpu_baseline"]
+    barrier-to-barrier wall (ms_per_step_wall).  Four ranks over gloo on one GPU: with the test process, five processes
+    hold the device."""
+    four = _bench(4, cpu_baseline=True)
+    assert four["n_gpus"] == 4 and four["ranks"]["ranks_seen"] == 4
+    assert four["ranks"]["distinct_devices"] == 1 and four["ranks"]["world_size"] == 4
+    rf, cb = four["roofline"], four["cpu_baseline"]
     assert rf["bound"] == "hbm" and rf["kernel_ms"] > 0 and 0 < rf["frac"] < 1
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["sample"]
     assert cb["with_alloc"]["kind"] == "port+alloc" and 0 < cb["with_alloc"]["value"] <= cb["value"] * 1.25
-    assert eight["_detail"]["cpu_baseline"]["ranks_waiting"] == 7
+    assert four["_detail"]["cpu_baseline"]["ranks_waiting"] == 3
     # rank 0's wall clock between the barriers contains the slowest rank's own time up to the skew of the barrier exits
-    assert eight["ms_per_step_wall"] > 0 and eight["ms_per_step_wall"] >= 0.5 * eight["ms_per_step"]
-    # rank 0 measured the clock its kernel ran at (eight ranks share the GPU here: no statement about its value)
+    assert four["ms_per_step_wall"] > 0 and four["ms_per_step_wall"] >= 0.5 * four["ms_per_step"]
+    # rank 0 measured the clock its kernel ran at (four ranks share the GPU here: no statement about its value)
     assert 0.5 < rf["effective_clock_ghz"] <= 2.45 and rf.get("issue_slot_frac_at_clock") is not None
     one = _bench(1, cpu_baseline=True)
     assert "ranks_waiting" not in one["_detail"]["cpu_baseline"] and one["cpu_baseline"]["with_alloc"]["value"] > 0
@@ -275,3 +287,47 @@ def test_default_shape_with_cpu_baseline():
     assert all(r["cpu_baseline"]["value"] > 0 for r in line["workloads"])
     saved = json.loads((ROOT / "gpurun_out" / "bench_workloads.json").read_text())
     assert [r["record"] for r in saved] == ["headline_detail", "workload", "workload", "workload"]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_what_the_timed_steps_computed(tmp_path):
+    """--dump-outputs DIR: the output planes of the last timed step as DIR/<name>.npy.  A batch that fits the budget is
+    written whole and equals the CPU oracle on the same seeded inputs; the same arguments give the same files byte for byte;
+    a larger batch is written at a seeded sample of its points, under 64 MB in all.  --steps is the count of timed steps."""
+    import numpy as np
+
+    import cases
+    import oracle_lib as O
+    from gpu_util import ggx_oracle
+
+    def run(log2n, d, steps):
+        p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--log2-points", str(log2n), "--steps", str(steps),
+                            "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True,
+                           timeout=600, cwd=str(ROOT))
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = _parse(p.stdout)
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        return line
+
+    names = ("wi", "f", "pdf", "fresnel", "wt", "weight")
+    n = 1 << 16
+    small = run(16, tmp_path / "a", 3)
+    assert sorted(f.stem for f in (tmp_path / "a").glob("*.npy")) == sorted(names)
+    rec = small["_detail"]["outputs_dump"]
+    assert rec["points"] == n and rec["of_points"] == n and rec["sample_seed"] is None
+    got = [np.load(tmp_path / "a" / f"{k}.npy") for k in names]
+    assert [a.shape for a in got] == [(3, n), (3, n), (n,), (n,), (3, n), (n,)] and all(a.dtype == np.float32 for a in got)
+    c = cases.ggx_mixed(1234, n)                       # bench.py's inputs: the seeded generator, seed 1234, from index 0
+    x = cases.xi(1234, n, 4)
+    ref = ggx_oracle(O, c).reflect_refract(x[0], x[1], x[2], x[3])
+    for k, a, b in zip(names, got, ref):
+        st = cases.summarize(cases.rel_err(a, b))
+        assert st["nonfinite"] == 0 and st["max"] <= 1e-5, (k, st)
+    run(16, tmp_path / "b", 5)
+    for k in names:
+        assert (tmp_path / "a" / f"{k}.npy").read_bytes() == (tmp_path / "b" / f"{k}.npy").read_bytes(), k
+    big = run(22, tmp_path / "c", 2)
+    rec = big["_detail"]["outputs_dump"]
+    assert rec["of_points"] == 1 << 22 and rec["points"] == 1 << 20 and rec["sample_seed"] is not None
+    assert sum(f.stat().st_size for f in (tmp_path / "c").glob("*.npy")) < 64_000_000
+    assert np.load(tmp_path / "c" / "wi.npy").shape == (3, 1 << 20)
