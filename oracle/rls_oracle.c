@@ -111,7 +111,7 @@ orc_v2 orc_concentric_disk_sample(float rx, float ry)
         phi = AI_PIOVER2 * 0.5f * ry / rx;
     } else {
         r = ry;
-        phi = AI_PIOVER2 * (1.0f - 0.5f * rx / ry);
+        phi = AI_PIOVER2 * (1.0f - (0.5f * rx) / ry);
     }
     result.x = r * cosf(phi);
     result.y = r * sinf(phi);
@@ -181,7 +181,7 @@ orc_v2 orc_vndf_sample_slope(float theta, float rx, float ry)
     }
     float B = tanf(theta);
     float B2 = SQRf(B);
-    float G1 = 2.0f / (1.0f + sqrtf(1.0f + B2));
+    float G1 = 2.0f / (1.0f + sqrtf(B2 + 1.0f));
 
     float A = 2.0f * rx / G1 - 1.0f;
     float A2 = SQRf(A);
@@ -192,7 +192,7 @@ orc_v2 orc_vndf_sample_slope(float theta, float rx, float ry)
     float D = sqrtf(MAXf(0.0f, B2 * SQRf(tmp) - (A2 - B2) * tmp));
     float slopeX1 = B * tmp - D;
     float slopeX2 = B * tmp + D;
-    slope.x = (A < 0.0f || slopeX2 > 1.0f / B) ? slopeX1 : slopeX2;
+    slope.x = (A < 0.0f || slopeX2 > (1.0f / B)) ? slopeX1 : slopeX2;
 
     float sign = 1.0f;
     if (ry > 0.5f) {
@@ -464,7 +464,7 @@ static float D_GTR1(const orc_disney *d, float MdotN2)
     float alpha = LERPf(d->clearcoatGloss, 0.1f, 0.001f);
     float a2 = SQRf(alpha);
     float denominator = logf(a2) * (1.0f + (a2 - 1.0f) * MdotN2);
-    return (a2 - 1.0f) * AI_ONEOVERPI / denominator;
+    return ((a2 - 1.0f) * AI_ONEOVERPI) / denominator;
 }
 
 /* src/rlDisney.cpp:561-568 */
@@ -501,13 +501,13 @@ orc_rgb orc_disney_eval_diffuse(const orc_disney *d, orc_v3 L)
 {
     float LdotN = v3dot(L, d->axisN);
     float VdotN = v3dot(d->viewDir, d->axisN);
-    if (LdotN < AI_EPSILON || VdotN < AI_EPSILON) {
+    if ((LdotN < AI_EPSILON) || (VdotN < AI_EPSILON)) {
         return RGB_BLACK;
     }
     orc_v3 H = v3normalize(v3add(L, d->viewDir));
     float LdotH = v3dot(L, H);
     float NdotH = v3dot(d->viewDir, H);     /* named NdotH in the reference, is V.H (line 210) */
-    if (NdotH < AI_EPSILON || LdotH < AI_EPSILON) {
+    if ((NdotH < AI_EPSILON) || (LdotH < AI_EPSILON)) {
         return RGB_BLACK;
     }
     float LdotH2 = SQRf(LdotH);
@@ -519,7 +519,7 @@ orc_rgb orc_disney_eval_diffuse(const orc_disney *d, orc_v3 L)
 
     float Fss90 = d->roughness * LdotH2;
     float Fss = LERPf(FL, 1.0f, Fss90) * LERPf(FV, 1.0f, Fss90);
-    float ssFactor = 1.25f * (Fss * (1.0f / (LdotN + VdotN) - 0.5f) + 0.5f);
+    float ssFactor = 1.25f * ((Fss * (1.0f / (LdotN + VdotN) - 0.5f)) + 0.5f);
 
     float mix = LERPf(d->subsurface, diffuseFactor, ssFactor);
     float om = 1.0f - d->metallic;
@@ -533,13 +533,13 @@ orc_rgb orc_disney_eval_specular(const orc_disney *d, orc_v3 L)
 {
     float LdotN = v3dot(L, d->axisN);
     float VdotN = v3dot(d->viewDir, d->axisN);
-    if (LdotN < AI_EPSILON || VdotN < AI_EPSILON) {
+    if ((LdotN < AI_EPSILON) || (VdotN < AI_EPSILON)) {
         return RGB_BLACK;
     }
     orc_v3 M = v3normalize(v3add(L, d->viewDir));
     float LdotM = v3dot(L, M);
     float NdotM = v3dot(d->axisN, M);
-    if (NdotM < AI_EPSILON || LdotM < AI_EPSILON) {
+    if ((NdotM < AI_EPSILON) || (LdotM < AI_EPSILON)) {
         return RGB_BLACK;
     }
     float NdotM2 = SQRf(v3dot(d->axisN, M));
@@ -553,7 +553,8 @@ orc_rgb orc_disney_eval_specular(const orc_disney *d, orc_v3 L)
     const float clearcoatRoughness = 0.25f;
     float Dr = D_GTR1(d, NdotM2);
     float Fr = LERPf(FH, clearcoatF0, 1.0f);
-    float Gr = smithG_GGX(LdotN, clearcoatRoughness) * smithG_GGX(VdotN, clearcoatRoughness);
+    float Gr = smithG_GGX(LdotN, clearcoatRoughness)
+             * smithG_GGX(VdotN, clearcoatRoughness);
 
     float om = 1.0f - d->metallic;
     orc_rgb Fsheen = rgb(FH * d->sheenColor.r * om, FH * d->sheenColor.g * om, FH * d->sheenColor.b * om);
@@ -624,7 +625,8 @@ orc_v3 orc_disney_sample_specular(const orc_disney *d, float rx, float ry)
             ? vndf_microfacet(d->viewDir, d->axisU, d->axisV, d->axisN, d->alphaX, d->alphaY, rx, ry)
             : orc_disney_sample_gtr2_aniso(d, rx, ry);
     } else {
-        rx = (rx - gtr2Weight) / (1.0f - gtr2Weight);
+        float gtr1Weight = 1.0f - gtr2Weight;
+        rx = (rx - gtr2Weight) / gtr1Weight;
         M = disney_sample_gtr1(d, rx, ry);
     }
     if (v3dot(d->axisN, M) < 0.0f) {

@@ -69,7 +69,7 @@ static orc_v3 microfacet_variant(const orc_ggx *g, float rx, float ry, int bits,
             const float D = sqrtf(MAXf(0.0f, B2 * SQRf(tmp) - (A2 - B2) * tmp));
             const float slopeX1 = B * tmp - D;
             const float slopeX2 = B * tmp + D;
-            slope.x = (A < 0.0f || slopeX2 > 1.0f / B) ? slopeX1 : slopeX2;
+            slope.x = (A < 0.0f || slopeX2 > (1.0f / B)) ? slopeX1 : slopeX2;
             float sign = 1.0f, u = ry;
             if (u > 0.5f) {
                 u = 2.0f * (u - 0.5f);
