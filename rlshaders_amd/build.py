@@ -103,6 +103,64 @@ def build_library(force: bool = False, verbose: bool = False, variant: str = "",
     return lib
 
 
+# The caller-traced integrators (include/rlshaders_amd_trace.h): a companion library beside the product, so that the product's
+# device code -- frozen, tests/test_profile_binding.py -- stays what it is.  Same flags, the same two flavours per unit (EXACT
+# with the C ABI, FAST behind hidden symbols), fixed -cuid per unit; linked against librlshaders_amd.so (context, errors) and
+# found next to it ($ORIGIN).  A name no build_library(variant=...) output can take.
+TRACE_CSRC = PKG / "csrc_trace"
+TRACE_SOURCES = ["trace.hip"]
+TRACE_LIB = LIBDIR / "librls_trace.so"
+TRACE_HEADERS = [TRACE_CSRC / "rls_trace_device.hpp", PKG.parent / "include" / "rlshaders_amd_trace.h"]
+
+
+def build_trace_library(force: bool = False, verbose: bool = False) -> Path:
+    """Compile csrc_trace/ for gfx950 and link librls_trace.so against the product library.  Returns its path."""
+    hipcc = _hipcc()
+    main = build_library(verbose=verbose)
+    objdir = OBJDIR / "trace"
+    objdir.mkdir(parents=True, exist_ok=True)
+    jobs, objs = [], []
+    for name in TRACE_SOURCES:
+        src = TRACE_CSRC / name
+        for suffix, flag in (("", "RLS_FAST=0"), ("_fast", "RLS_FAST=1")):
+            obj = objdir / (src.stem + suffix + ".o")
+            objs.append(obj)
+            if force or _stale(obj, [src, *HEADERS, *TRACE_HEADERS, Path(__file__)]):
+                jobs.append([hipcc, *HIPCC_FLAGS, f"-cuid=rls_trace.{src.stem}{suffix}", f"-D{flag}", "-c", str(src),
+                             "-o", str(obj)])
+
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
+
+    if jobs:
+        with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
+            list(ex.map(run, jobs))
+    if force or jobs or _stale(TRACE_LIB, [*objs, main]):
+        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(TRACE_LIB), *map(str, objs),
+             f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"])
+    return TRACE_LIB
+
+
+def build_trace_example(verbose: bool = False) -> Path:
+    """host/example_trace.cpp against both libraries (emit -> a host-side \"tracer\" -> resolve)."""
+    OBJDIR.mkdir(exist_ok=True)
+    lib = build_trace_library(verbose=verbose)
+    src, out = PKG / "host" / "example_trace.cpp", OBJDIR / "example_trace"
+    if _stale(out, [src, PKG / "host" / "rls_trace.hpp", lib, LIB, *HEADERS, *TRACE_HEADERS]):
+        cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{PKG / 'host'}", str(src), "-o", str(out),
+               f"-L{LIBDIR}", "-lrls_trace", "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"host example example_trace failed to build:\n{p.stdout}\n{p.stderr}")
+    return out
+
+
 def build_host_examples(verbose: bool = False) -> Path:
     """Compile-check the C++ host mirror (header-only) and its example against the C ABI."""
     OBJDIR.mkdir(exist_ok=True)

@@ -1,0 +1,113 @@
+// rls_trace_device.hpp -- device helpers of the caller-traced integrators (trace.hip): the launch descriptors, a sample's
+// rank among the kept samples of its point, and the int64 scan of the per-point ray counts.
+#pragma once
+#include "../csrc/rls_loops.hpp"
+#include "../../include/rlshaders_amd_trace.h"
+
+namespace {
+
+constexpr uint16_t kDropped = 0xFFFF;        // staging tag of a sample that is not queued (else rank | kind << 8)
+
+// emit: one G-lane group per point writes slot s * n + i of the staging planes for every sample, and the point's count
+// of kept samples into offsets[i] (scanned in place afterwards)
+struct TraceEmitIO {
+    rls_ggx_closure c;
+    float *dir[3];
+    float *w[3];             // glossy: 3 planes; refraction: w[0]
+    uint16_t *tag;
+    int64_t *count;          // = the queue's offsets
+    float *side;             // avg_reflect_weight / tir_fraction, NULL-able
+    int64_t n;
+    int spp;
+    uint32_t seed;
+    uint64_t first;
+};
+
+struct TraceCompactIO {
+    const float *sdir[3];
+    const float *sw[3];
+    const uint16_t *tag;
+    const int64_t *offsets;
+    rls_ray_queue q;
+    int64_t n;
+    int spp;
+    int tile_points;         // points per compaction tile: min(kCompactMaxPoints, kCompactSlots / spp)
+};
+constexpr int kCompactSlots = 4096;          // samples per compaction tile (LDS: 4 B each for the position and one plane)
+constexpr int kCompactMaxPoints = 256;       // (a point's local index in a tile is 8 bits)
+
+struct TraceResolveIO {
+    const int64_t *offsets;
+    const float *w[3];
+    rls_crgb L;
+    rls_rgb out;
+    float scale;             // refraction: 1 / spp (applied after the sum); glossy: unused
+    int64_t n;
+};
+
+// Rank of this lane's sample among the kept samples of its point, in sample order.  The G lanes of a group hold G
+// consecutive samples (lane `sub` the sub-th); `run` counts the kept samples of the group's earlier rounds and is advanced
+// past this round.  Every lane of the wavefront calls it (ballot).
+template <int G>
+__device__ __forceinline__ int group_rank(bool keep, int sub, int &run)
+{
+    const uint64_t m = __builtin_amdgcn_ballot_w64(keep);
+    const int base = (int)(threadIdx.x & 63u) & ~(G - 1);
+    uint64_t gm = m;
+    if constexpr (G < 64) gm = (m >> base) & ((1ull << G) - 1ull);
+    const int rank = run + __builtin_popcountll(gm & ((1ull << sub) - 1ull));
+    run += __builtin_popcountll(gm);
+    return rank;
+}
+
+// exclusive scan of one value per thread over the workgroup; `total` = the workgroup's sum
+__device__ __forceinline__ int64_t block_excl_scan(int64_t v, int64_t &total)
+{
+    __shared__ int64_t wsum[rlsh::kBlock / 64];
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    int64_t x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int64_t y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();
+    int64_t before = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < rlsh::kBlock / 64; w++) {
+        if (w < wave) before += wsum[w];
+        tot += wsum[w];
+    }
+    __syncthreads();         // wsum is reused by the next call
+    total = tot;
+    return before + x - v;
+}
+
+constexpr int kScanPer = 8;                               // values per thread of a scan tile
+constexpr int64_t kScanTile = (int64_t)rlsh::kBlock * kScanPer;
+
+// exclusive scan of v[0, count) (count <= kScanTile) in place, plus `carry`; returns the tile's sum.  Loads and stores are
+// coalesced through LDS; each thread scans kScanPer consecutive values.
+__device__ __forceinline__ int64_t scan_tile(int64_t *v, int64_t count, int64_t carry)
+{
+    __shared__ int64_t t[kScanTile];
+    for (int k = threadIdx.x; k < kScanTile; k += rlsh::kBlock) t[k] = k < count ? v[k] : 0;
+    __syncthreads();
+    int64_t loc[kScanPer], sum = 0;
+#pragma unroll
+    for (int k = 0; k < kScanPer; k++) {
+        loc[k] = sum;
+        sum += t[threadIdx.x * kScanPer + k];
+    }
+    int64_t total;
+    const int64_t pre = carry + block_excl_scan(sum, total);
+#pragma unroll
+    for (int k = 0; k < kScanPer; k++) t[threadIdx.x * kScanPer + k] = pre + loc[k];
+    __syncthreads();
+    for (int k = threadIdx.x; k < count; k += rlsh::kBlock) v[k] = t[k];
+    __syncthreads();         // t is reused by the next call
+    return total;
+}
+
+} // namespace

@@ -1,0 +1,480 @@
+// trace.hip -- caller-traced rlGgx integrators (include/rlshaders_amd_trace.h): integrateGlossy and integrateRefract's
+// traced branch (src/rlGgx.h:172-184, 228-244) cut where the reference traces, into an emit of every sample ray and a
+// resolve of the radiance the caller traced for them.
+//
+// Emit, three steps on the context's stream:
+//   1. ggx_{glossy,refract}_emit_kernel: the sample loop of rls_ggx_integrate / rls_ggx_integrate_refract (one G-lane
+//      group per point, the same packed VNDF sampling), each sample computed ONCE: its record goes to a fixed staging slot
+//      s * n + i (sample-major: the lanes of a wavefront store to consecutive words) with a tag (its rank among the
+//      point's kept samples, or "dropped"), the point's kept count to offsets[i].  A count pass and a write pass would run
+//      the sample arithmetic twice.
+//   2. trace_scan_{block,totals,add}_kernel: offsets[0, n) scanned in place (exclusive), offsets[n] = the ray count.  A
+//      multi-kernel scan (tiles, then the tile sums in one workgroup, then the add-back): no workgroup waits on another.
+//   3. trace_compact_kernel: per tile of points, the kept records move from their staging slots to offsets[i] + rank,
+//      transposed through LDS (staging rows in, the tile's contiguous queue range out).
+// Every position is a function of the inputs: no atomics anywhere.
+//
+// Resolve (trace_resolve_kernel): per point the sequential sum over its rays in queue order; the products
+// radiance x weight of a tile of rays are formed with coalesced loads into LDS, then each lane adds its point's ones.
+//
+// Built twice like the closure units of librlshaders_amd.so (rlshaders_amd/build.py, build_trace_library): RLS_FAST=0
+// carries the C ABI, the EXACT emit kernels and the mode-free scan / compact / resolve kernels; RLS_FAST=1 the FAST emit
+// kernels behind hidden symbols.
+#include "rls_trace_device.hpp"
+
+namespace {
+
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_glossy_emit_kernel(TraceEmitIO a)
+{
+    constexpr int K = RLS_SPEC_BLOCK;
+    __shared__ uint32_t tab[2][kMaxSpp];
+    __shared__ SlowLds<K> slow;
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    const int sub = threadIdx.x % G;
+    const int64_t groups_per_block = rlsh::kBlock / G;
+    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
+    const int64_t rounds = (a.n + stride - 1) / stride;
+    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
+    for (int64_t it = 0; it < rounds; it++, i += stride) {
+        const bool live = i < a.n;
+        const int64_t ii = live ? i : a.n - 1;
+        const rls_ggx_closure &c = a.c;
+        const PIndex<int64_t> pk = pindex(c.materials, ii);
+        V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
+        float kr, kg, kb;
+        ldrgb(c.KsColor, pk, kr, kg, kb);
+        bool exiting = c.exiting ? (c.exiting[ii] != 0) : false;
+        Ggx g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp(c.ior, pk), ldp(c.specularRoughness, pk),
+                         ldp(c.anisotropic, pk));
+        VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
+        const uint32_t sx = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream);
+        const uint32_t sy = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + 1);
+
+        // ggx_glossy_loop (rls_loops.hpp) with the per-sample terms stored instead of summed; the Fresnel sum is folded in
+        // sample order exactly as there
+        float accF = 0.0f;
+        int run = 0;
+        for (int s0 = sub; s0 - sub < a.spp; s0 += K * G) {
+            int cnt = 0;
+#pragma unroll 1
+            for (int k = 0; k < K; k++) {
+                const int s = s0 + k * G;
+                const int sc = s < a.spp ? s : 0;
+                ggx_vndf_push<K>(slow, k, cnt, s < a.spp, w, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
+            }
+            slow_run<K>(slow, cnt);
+#pragma unroll 1
+            for (int k = 0; k < K; k++) {
+                const int s = s0 + k * G;
+                float tR = 0.0f, tG = 0.0f, tB = 0.0f, tF = 0.0f;
+                V3 L = mk(0.0f, 0.0f, 0.0f);
+                if (s < a.spp) {
+                    V3 M = ggx_vndf_pop<K>(slow, k, w, g.fr);
+                    L = reflect_direction(g.view, M);
+                    tF = ggx_fresnel(g, L, M);                      // mReflectWeight, src/rlGgx.h:103
+                    float fr, fg, fb, pdf;
+                    ggx_eval_pdf<true, true>(g, L, fr, fg, fb, pdf);
+                    tR = fr / pdf; tG = fg / pdf; tB = fb / pdf;
+                }
+                fold<G>(accF, tF);
+                const bool keep = s < a.spp && !(tR == 0.0f && tG == 0.0f && tB == 0.0f);
+                const int rank = group_rank<G>(keep, sub, run);
+                if (live && s < a.spp) {
+                    const int64_t slot = (int64_t)s * a.n + i;
+                    if (keep) {
+                        a.dir[0][slot] = L.x; a.dir[1][slot] = L.y; a.dir[2][slot] = L.z;
+                        a.w[0][slot] = tR; a.w[1][slot] = tG; a.w[2][slot] = tB;
+                    }
+                    a.tag[slot] = keep ? (uint16_t)rank : kDropped;
+                }
+            }
+        }
+        if (live && sub == 0) {
+            a.count[i] = run;
+            if (a.side) stg(a.side, i, accF / (float)a.spp);       // getAvgReflectWeight, src/rlGgx.h:181-184
+        }
+    }
+}
+
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_refract_emit_kernel(TraceEmitIO a)
+{
+    constexpr int K = RLS_SPEC_BLOCK;
+    __shared__ uint32_t tab[2][kMaxSpp];
+    __shared__ SlowLds<K> slow;
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    const int sub = threadIdx.x % G;
+    const int64_t groups_per_block = rlsh::kBlock / G;
+    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
+    const int64_t rounds = (a.n + stride - 1) / stride;
+    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
+    for (int64_t it = 0; it < rounds; it++, i += stride) {
+        const bool live = i < a.n;
+        const int64_t ii = live ? i : a.n - 1;
+        const rls_ggx_closure &c = a.c;
+        const PIndex<int64_t> pk = pindex(c.materials, ii);
+        V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
+        float kr, kg, kb;
+        ldrgb(c.KsColor, pk, kr, kg, kb);
+        bool exiting = c.exiting ? (c.exiting[ii] != 0) : false;
+        Ggx g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp(c.ior, pk), ldp(c.specularRoughness, pk),
+                         ldp(c.anisotropic, pk));
+        VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
+        const uint32_t sx = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream);
+        const uint32_t sy = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + 1);
+
+        // ggx_refract_loop (rls_loops.hpp) with the per-sample direction and weight stored instead of summed
+        float tir = 0.0f;
+        int run = 0;
+        for (int s0 = sub; s0 - sub < a.spp; s0 += K * G) {
+            int cnt = 0;
+#pragma unroll 1
+            for (int k = 0; k < K; k++) {
+                const int s = s0 + k * G;
+                const int sc = s < a.spp ? s : 0;
+                ggx_vndf_push<K>(slow, k, cnt, s < a.spp, w, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
+            }
+            slow_run<K>(slow, cnt);
+#pragma unroll 1
+            for (int k = 0; k < K; k++) {
+                const int s = s0 + k * G;
+                float t = 0.0f;
+                bool mirror = false;
+                V3 dir = mk(0.0f, 0.0f, 0.0f);
+                if (s < a.spp) {
+                    V3 M = ggx_vndf_pop<K>(slow, k, w, g.fr);
+                    mirror = !ggx_refract(g, M, dir);
+                    if (mirror) tir += 1.0f;
+                    t = ggx_sample_weight(g, g.view, dir, M);        // src/rlGgx.h:241
+                }
+                const bool keep = s < a.spp && !(t == 0.0f);
+                const int rank = group_rank<G>(keep, sub, run);
+                if (live && s < a.spp) {
+                    const int64_t slot = (int64_t)s * a.n + i;
+                    if (keep) {
+                        a.dir[0][slot] = dir.x; a.dir[1][slot] = dir.y; a.dir[2][slot] = dir.z;
+                        a.w[0][slot] = t;
+                    }
+                    a.tag[slot] = keep ? (uint16_t)(rank | (mirror ? RLS_RAY_TIR_MIRROR << 8 : 0)) : kDropped;
+                }
+            }
+        }
+        if (G > 1) tir = group_sum<G>(tir);                         // a count: integers, any order
+        if (live && sub == 0) {
+            a.count[i] = run;
+            if (a.side) stg(a.side, i, tir * (1.0f / (float)a.spp));   // as ggx_refract_loop: tir *= inv
+        }
+    }
+}
+
+#if !RLS_FAST
+// exclusive scan of offsets[0, n): each workgroup one tile, its sum to totals[tile]
+__global__ __launch_bounds__(rlsh::kBlock) void trace_scan_block_kernel(int64_t *v, int64_t n, int64_t *totals)
+{
+    const int64_t base = (int64_t)blockIdx.x * kScanTile;
+    const int64_t count = n - base < kScanTile ? n - base : kScanTile;
+    const int64_t total = scan_tile(v + base, count, 0);
+    if (threadIdx.x == 0) totals[blockIdx.x] = total;
+}
+
+// one workgroup: exclusive scan of the tile sums, tile by tile with a carry; the grand total is the ray count, offsets[n]
+__global__ __launch_bounds__(rlsh::kBlock) void trace_scan_totals_kernel(int64_t *totals, int64_t tiles, int64_t *ray_count)
+{
+    int64_t carry = 0;
+    for (int64_t b = 0; b < tiles; b += kScanTile) {
+        const int64_t count = tiles - b < kScanTile ? tiles - b : kScanTile;
+        carry += scan_tile(totals + b, count, carry);
+    }
+    if (threadIdx.x == 0) *ray_count = carry;
+}
+
+__global__ __launch_bounds__(rlsh::kBlock) void trace_scan_add_kernel(int64_t *v, int64_t n, const int64_t *totals)
+{
+    for (int64_t j = (int64_t)blockIdx.x * rlsh::kBlock + threadIdx.x; j < n; j += (int64_t)gridDim.x * rlsh::kBlock)
+        v[j] += totals[j / kScanTile];
+}
+
+// A tile of P consecutive points (P * spp <= kCompactSlots): sample (i, s) moves from staging slot s * n + i to queue position
+// offsets[i] + rank.  Through LDS, one plane at a time, so that both sides are coalesced: the staging is read in rows (one
+// sample of P consecutive points), the tile's rays are one contiguous range of the queue and are written in order.
+template <int NW>
+__global__ __launch_bounds__(rlsh::kBlock) void trace_compact_kernel(TraceCompactIO a)
+{
+    constexpr int kPer = kCompactSlots / rlsh::kBlock;         // slots per thread: their loads are issued together
+    __shared__ float buf[kCompactSlots];         // one plane of the tile's rays, in queue order
+    __shared__ int64_t off[kCompactMaxPoints + 1];
+    const rls_ray_queue &q = a.q;
+    const int P = a.tile_points;
+    const int64_t tiles = (a.n + P - 1) / P;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t p0 = tile * P;
+        const int pc = a.n - p0 < P ? (int)(a.n - p0) : P;
+        const int slots = pc * a.spp;
+        __syncthreads();                                         // the previous tile is written out
+        for (int p = threadIdx.x; p <= pc; p += rlsh::kBlock) off[p] = a.offsets[p0 + p];
+        __syncthreads();
+        const int64_t base = off[0];
+        const int rays = (int)(off[pc] - base);
+        // slot t = threadIdx.x + u * kBlock = s * pc + p: its staging index and position in the tile's range (-1: dropped)
+        int64_t src_at[kPer];
+        uint16_t tag[kPer];
+#pragma unroll
+        for (int u = 0; u < kPer; u++) {
+            const int t = (int)threadIdx.x + u * rlsh::kBlock, s = t / pc, p = t - s * pc;
+            src_at[u] = (int64_t)s * a.n + p0 + p;
+            tag[u] = t < slots ? a.tag[src_at[u]] : kDropped;
+        }
+        int pos[kPer];
+#pragma unroll
+        for (int u = 0; u < kPer; u++) {
+            const int t = (int)threadIdx.x + u * rlsh::kBlock, s = t / pc, p = t - s * pc;
+            pos[u] = tag[u] == kDropped ? -1 : (int)(off[p] - base) + (tag[u] & 0xFF);
+        }
+        for (int plane = 0; plane < 3 + NW; plane++) {
+            const float *src = plane < 3 ? a.sdir[plane] : a.sw[plane - 3];
+            float *out = plane == 0 ? q.dir.x : plane == 1 ? q.dir.y : plane == 2 ? q.dir.z
+                       : plane == 3 ? q.weight.r : plane == 4 ? q.weight.g : q.weight.b;
+            float v[kPer];
+#pragma unroll
+            for (int u = 0; u < kPer; u++) v[u] = pos[u] >= 0 ? src[src_at[u]] : 0.0f;
+#pragma unroll
+            for (int u = 0; u < kPer; u++) if (pos[u] >= 0) buf[pos[u]] = v[u];
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < kPer; u++) {
+                const int k = (int)threadIdx.x + u * rlsh::kBlock;
+                if (k < rays) out[base + k] = buf[k];
+            }
+            __syncthreads();
+        }
+        if (q.point || q.sample || q.kind) {
+            uint32_t *ib = (uint32_t *)buf;
+#pragma unroll
+            for (int u = 0; u < kPer; u++) {
+                const int t = (int)threadIdx.x + u * rlsh::kBlock, s = t / pc, p = t - s * pc;
+                if (pos[u] >= 0) ib[pos[u]] = (uint32_t)p | (uint32_t)s << 8 | (uint32_t)(tag[u] >> 8) << 16;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < kPer; u++) {
+                const int k = (int)threadIdx.x + u * rlsh::kBlock;
+                if (k >= rays) continue;
+                const uint32_t v = ib[k];
+                if (q.point) q.point[base + k] = (uint32_t)(p0 + (v & 0xFF));
+                if (q.sample) q.sample[base + k] = (uint8_t)(v >> 8);
+                if (NW == 1 && q.kind) q.kind[base + k] = (uint8_t)(v >> 16);
+            }
+        }
+    }
+}
+
+// per point the sum over its rays [offsets[i], offsets[i+1]) in queue order.  A workgroup takes kBlock consecutive points,
+// i.e. one contiguous range of rays, in tiles of kResolveTile rays: coalesced loads form the products L x weight in LDS,
+// then lane i adds those of its own rays, in order.
+constexpr int kResolveTile = 1024;
+template <int NW>
+__global__ __launch_bounds__(rlsh::kBlock) void trace_resolve_kernel(TraceResolveIO a)
+{
+    __shared__ float prod[3][kResolveTile];
+    for (int64_t p0 = (int64_t)blockIdx.x * rlsh::kBlock; p0 < a.n; p0 += (int64_t)gridDim.x * rlsh::kBlock) {
+        const int64_t i = p0 + threadIdx.x;
+        const bool live = i < a.n;
+        const int64_t pend = a.n - p0 < rlsh::kBlock ? a.n : p0 + rlsh::kBlock;
+        const int64_t r0 = a.offsets[p0], r1 = a.offsets[pend];
+        const int64_t lo = live ? a.offsets[i] : 0, hi = live ? a.offsets[i + 1] : 0;
+        float aR = 0.0f, aG = 0.0f, aB = 0.0f;
+        for (int64_t t0 = r0; t0 < r1; t0 += kResolveTile) {
+            const int tn = r1 - t0 < kResolveTile ? (int)(r1 - t0) : kResolveTile;
+            __syncthreads();                                     // the previous tile's products are consumed
+            for (int k = threadIdx.x; k < tn; k += rlsh::kBlock) {
+                const int64_t q = t0 + k;
+                if (NW == 3) {
+                    prod[0][k] = a.L.r[q] * a.w[0][q]; prod[1][k] = a.L.g[q] * a.w[1][q]; prod[2][k] = a.L.b[q] * a.w[2][q];
+                } else {
+                    const float wq = a.w[0][q];
+                    prod[0][k] = a.L.r[q] * wq; prod[1][k] = a.L.g[q] * wq; prod[2][k] = a.L.b[q] * wq;
+                }
+            }
+            __syncthreads();
+            const int64_t b = lo > t0 ? lo : t0, e = hi < t0 + tn ? hi : t0 + tn;
+            for (int64_t q = b; q < e; q++) {
+                aR += prod[0][q - t0]; aG += prod[1][q - t0]; aB += prod[2][q - t0];
+            }
+        }
+        if (live) {
+            if (NW == 1) { aR *= a.scale; aG *= a.scale; aB *= a.scale; }
+            a.out.r[i] = aR; a.out.g[i] = aG; a.out.b[i] = aB;
+        }
+    }
+}
+#endif
+
+} // namespace
+
+#if RLS_FAST
+RLS_HIDDEN rls_status rls_trace_fast_glossy_emit(rls_context *ctx, int g, const TraceEmitIO *io)
+{
+    return launch_g(ctx, ggx_glossy_emit_kernel<1>, ggx_glossy_emit_kernel<4>, ggx_glossy_emit_kernel<16>,
+                    ggx_glossy_emit_kernel<64>, g, *io, "rls_trace_ggx_glossy_emit[fast]");
+}
+RLS_HIDDEN rls_status rls_trace_fast_refract_emit(rls_context *ctx, int g, const TraceEmitIO *io)
+{
+    return launch_g(ctx, ggx_refract_emit_kernel<1>, ggx_refract_emit_kernel<4>, ggx_refract_emit_kernel<16>,
+                    ggx_refract_emit_kernel<64>, g, *io, "rls_trace_ggx_refract_emit[fast]");
+}
+#else
+RLS_HIDDEN rls_status rls_trace_fast_glossy_emit(rls_context *ctx, int g, const TraceEmitIO *io);
+RLS_HIDDEN rls_status rls_trace_fast_refract_emit(rls_context *ctx, int g, const TraceEmitIO *io);
+
+namespace {
+
+// the staging planes of an emit inside the caller's scratch, each 256-byte aligned
+struct Staging {
+    float *dir[3];
+    float *w[3];
+    uint16_t *tag;
+    int64_t *totals;
+    int64_t tiles;
+    size_t bytes;
+};
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline Staging staging(void *base, int64_t n, int spp)
+{
+    Staging s = {};
+    const size_t slots = (size_t)n * (size_t)spp;
+    char *p = (char *)base;
+    size_t off = 0;
+    for (int k = 0; k < 3; k++) { s.dir[k] = (float *)(p + off); off += align256(slots * sizeof(float)); }
+    for (int k = 0; k < 3; k++) { s.w[k] = (float *)(p + off); off += align256(slots * sizeof(float)); }
+    s.tag = (uint16_t *)(p + off); off += align256(slots * sizeof(uint16_t));
+    s.tiles = (n + kScanTile - 1) / kScanTile;
+    s.totals = (int64_t *)(p + off); off += align256((size_t)(s.tiles > 0 ? s.tiles : 1) * sizeof(int64_t));
+    s.bytes = off;
+    return s;
+}
+
+rls_status emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed, uint64_t first_index,
+                const rls_ray_queue *q, float *side, bool refract)
+{
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE(n >= 0, "n < 0");
+    RLS_REQUIRE(n <= (int64_t)UINT32_MAX, "n > 2^32 - 1 (the queue's point index is 32-bit)");
+    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
+    RLS_REQUIRE(q != nullptr && q->offsets != nullptr, "queue or queue.offsets is NULL");
+    const int spp = spp_n * spp_n;
+    if (n == 0) {                                        // an empty queue: offsets[0] = 0
+        hipLaunchKernelGGL(trace_scan_totals_kernel, dim3(1), dim3(rlsh::kBlock), 0, ctx->stream, q->offsets, (int64_t)0,
+                           q->offsets);
+        return rlsh::check_launch(refract ? "rls_trace_ggx_refract_emit" : "rls_trace_ggx_glossy_emit");
+    }
+    RLS_REQUIRE(c != nullptr, "closure is NULL");
+    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T), "wo/N/T plane is NULL");
+    RLS_REQUIRE(rlsh::ok_rgb(c->KsColor), "KsColor planes must be all set or all NULL");
+    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    RLS_REQUIRE(rlsh::has3(q->dir), "queue.dir plane is NULL");
+    RLS_REQUIRE(refract ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
+    RLS_REQUIRE(q->capacity >= n * spp, "queue.capacity < n * spp_n^2");
+    const Staging st = staging(q->scratch, n, spp);
+    RLS_REQUIRE(q->scratch != nullptr && q->scratch_bytes >= st.bytes, "queue.scratch is NULL or smaller than rls_trace_scratch_bytes");
+
+    TraceEmitIO io = {};
+    io.c = *c;
+    for (int k = 0; k < 3; k++) { io.dir[k] = st.dir[k]; io.w[k] = st.w[k]; }
+    io.tag = st.tag; io.count = q->offsets; io.side = side;
+    io.n = n; io.spp = spp; io.seed = seed; io.first = first_index;
+    const int g = pick_group(ctx, n, spp);
+    rls_status s;
+    if (refract)
+        s = ctx->fast ? rls_trace_fast_refract_emit(ctx, g, &io)
+                      : launch_g(ctx, ggx_refract_emit_kernel<1>, ggx_refract_emit_kernel<4>, ggx_refract_emit_kernel<16>,
+                                 ggx_refract_emit_kernel<64>, g, io, "rls_trace_ggx_refract_emit");
+    else
+        s = ctx->fast ? rls_trace_fast_glossy_emit(ctx, g, &io)
+                      : launch_g(ctx, ggx_glossy_emit_kernel<1>, ggx_glossy_emit_kernel<4>, ggx_glossy_emit_kernel<16>,
+                                 ggx_glossy_emit_kernel<64>, g, io, "rls_trace_ggx_glossy_emit");
+    if (s != RLS_OK) return s;
+
+    // offsets: the counts scanned in place
+    hipLaunchKernelGGL(trace_scan_block_kernel, dim3((unsigned)st.tiles), dim3(rlsh::kBlock), 0, ctx->stream, q->offsets, n,
+                       st.totals);
+    if ((s = rlsh::check_launch("trace_scan_block_kernel")) != RLS_OK) return s;
+    hipLaunchKernelGGL(trace_scan_totals_kernel, dim3(1), dim3(rlsh::kBlock), 0, ctx->stream, st.totals, st.tiles,
+                       q->offsets + n);
+    if ((s = rlsh::check_launch("trace_scan_totals_kernel")) != RLS_OK) return s;
+    hipLaunchKernelGGL(trace_scan_add_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, q->offsets, n,
+                       (const int64_t *)st.totals);
+    if ((s = rlsh::check_launch("trace_scan_add_kernel")) != RLS_OK) return s;
+
+    TraceCompactIO cio = {};
+    for (int k = 0; k < 3; k++) { cio.sdir[k] = st.dir[k]; cio.sw[k] = st.w[k]; }
+    cio.tag = st.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp;
+    cio.tile_points = kCompactSlots / spp < kCompactMaxPoints ? kCompactSlots / spp : kCompactMaxPoints;
+    const dim3 cgrid = rlsh::grid_for(ctx, n, cio.tile_points);
+    if (refract) hipLaunchKernelGGL(trace_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    else hipLaunchKernelGGL(trace_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    return rlsh::check_launch("trace_compact_kernel");
+}
+
+rls_status resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, int spp_n, rls_crgb radiance, rls_rgb out, bool refract)
+{
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE(n >= 0, "n < 0");
+    RLS_REQUIRE(!refract || (spp_n >= 1 && spp_n * spp_n <= kMaxSpp), "spp_n must be in [1, 16]");
+    if (n == 0) return RLS_OK;
+    RLS_REQUIRE(q != nullptr && q->offsets != nullptr, "queue or queue.offsets is NULL");
+    RLS_REQUIRE(refract ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
+    RLS_REQUIRE(radiance.r && radiance.g && radiance.b, "radiance plane is NULL");
+    RLS_REQUIRE(rlsh::has3(out), "NULL output plane");
+    TraceResolveIO io = {};
+    io.offsets = q->offsets;
+    io.w[0] = q->weight.r; io.w[1] = q->weight.g; io.w[2] = q->weight.b;
+    io.L = radiance; io.out = out; io.n = n;
+    io.scale = refract ? 1.0f / (float)(spp_n * spp_n) : 1.0f;     // AiSamplerGetSampleInvCount, src/rlGgx.h:244
+    const dim3 grid = rlsh::grid_for(ctx, n);
+    if (refract) hipLaunchKernelGGL(trace_resolve_kernel<1>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
+    else hipLaunchKernelGGL(trace_resolve_kernel<3>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(refract ? "rls_trace_ggx_refract_resolve" : "rls_trace_ggx_glossy_resolve");
+}
+
+} // namespace
+
+extern "C" {
+
+rls_status rls_trace_scratch_bytes(int64_t n, int spp_n, size_t *bytes)
+{
+    RLS_REQUIRE(bytes != nullptr, "bytes is NULL");
+    RLS_REQUIRE(n >= 0, "n < 0");
+    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
+    *bytes = staging(nullptr, n, spp_n * spp_n).bytes;
+    return RLS_OK;
+}
+
+rls_status rls_trace_ggx_glossy_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed,
+                                     uint64_t first_index, const rls_ray_queue *q, float *avg_reflect_weight)
+{
+    return emit(ctx, n, c, spp_n, seed, first_index, q, avg_reflect_weight, false);
+}
+
+rls_status rls_trace_ggx_refract_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed,
+                                      uint64_t first_index, const rls_ray_queue *q, float *tir_fraction)
+{
+    return emit(ctx, n, c, spp_n, seed, first_index, q, tir_fraction, true);
+}
+
+rls_status rls_trace_ggx_glossy_resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, rls_crgb radiance, rls_rgb sum)
+{
+    return resolve(ctx, n, q, 1, radiance, sum, false);
+}
+
+rls_status rls_trace_ggx_refract_resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, int spp_n, rls_crgb radiance,
+                                         rls_rgb result)
+{
+    return resolve(ctx, n, q, spp_n, radiance, result, true);
+}
+
+} // extern "C"
+
+#endif // !RLS_FAST

@@ -1,0 +1,85 @@
+// example_trace.cpp -- the caller-traced rlGgx integrators from C++ (rls_trace.hpp): emit integrateGlossy's and
+// integrateRefract's sample rays, "trace" them against an analytic sky on the host, resolve.
+//
+//   example_trace [points] [spp_n]
+// prints one JSON line: the ray counts and a checksum (FNV-1a over the bits of the resolved planes) per integrator, which
+// tests/test_gpu_trace_host_cpp.py compares with the Python path (rlshaders_amd/trace.py) on the same inputs.
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "rls_trace.hpp"
+
+namespace {
+constexpr uint32_t kSeed = 1234;
+
+// the renderer's tracer, in a few lines: every ray escapes to a sky brighter towards +z, warm-tinted.  dz: the rays'
+// z components; L: 3 planes of cap floats
+void sky(const std::vector<float> &dz, int64_t cap, std::vector<float> &L)
+{
+    for (size_t k = 0; k < dz.size(); k++) {
+        const float up = 0.25f + 0.75f * std::max(dz[k], 0.0f);
+        L[k] = up;
+        L[(size_t)cap + k] = up * 0.875f;
+        L[(size_t)(2 * cap) + k] = up * 0.75f;
+    }
+}
+
+uint64_t fnv(const std::vector<float> &v)
+{
+    uint64_t h = 1469598103934665603ull;
+    for (float f : v) {
+        uint32_t b;
+        std::memcpy(&b, &f, 4);
+        for (int k = 0; k < 4; k++) { h ^= (b >> (8 * k)) & 0xFFu; h *= 1099511628211ull; }
+    }
+    return h;
+}
+} // namespace
+
+int main(int argc, char **argv)
+{
+    const int64_t n = argc > 1 ? std::atoll(argv[1]) : 4096;
+    const int spp_n = argc > 2 ? std::atoi(argv[2]) : 4;
+    const int64_t cap = n * spp_n * spp_n;
+    try {
+        rlsb::Device dev(0);
+        rlsb::Planes frame(dev, n, 9);
+        rlsb::check(rls_gen_frame(dev.ctx(), kSeed, 0, n, frame.vec3(0), frame.vec3(3), frame.vec3(6)));
+        rls_ggx_closure c = {};
+        c.wo = frame.cvec3(0); c.N = frame.cvec3(3); c.T = frame.cvec3(6);
+        c.KsColor = rlsb::ParamRGB(0.9f, 0.6f, 0.3f).c();
+        c.specularRoughness = rls_param{nullptr, 0.4f};
+        c.ior = rls_param{nullptr, 1.6f};
+        c.anisotropic = rls_param{nullptr, 0.5f};
+
+        std::printf("{");
+        const rlsb::RayQueue::Kind kinds[2] = {rlsb::RayQueue::Glossy, rlsb::RayQueue::Refract};
+        for (int j = 0; j < 2; j++) {
+            rlsb::RayQueue q(dev, n, spp_n, kinds[j]);
+            rlsb::Planes side(dev, n, 1), out(dev, n, 3), radiance(dev, cap, 3);
+            if (j == 0) rlsb::emitGlossy(dev, c, n, spp_n, kSeed, q, side.plane(0));
+            else rlsb::emitRefract(dev, c, n, spp_n, kSeed, q, side.plane(0));
+            const int64_t count = q.count();
+            std::vector<float> dz((size_t)count), L((size_t)(3 * cap), 0.0f);
+            rlsb::check(rls_copy_to_host(dev.ctx(), dz.data(), q.c().dir.z, sizeof(float) * dz.size()));
+            sky(dz, cap, L);
+            radiance.upload(L);
+            if (j == 0) rlsb::resolveGlossy(dev, q, radiance, out);
+            else rlsb::resolveRefract(dev, q, radiance, out);
+            std::vector<float> res = out.download();
+            double mean = 0.0;
+            for (float v : res) mean += v;
+            std::printf("%s\"%s\": {\"rays\": %lld, \"checksum\": \"%016llx\", \"mean\": %.9g}", j ? ", " : "",
+                        j == 0 ? "glossy" : "refract", (long long)count, (unsigned long long)fnv(res), mean / (double)res.size());
+        }
+        std::printf(", \"points\": %lld, \"spp_n\": %d}\n", (long long)n, spp_n);
+    } catch (const rlsb::Error &e) {
+        std::fprintf(stderr, "example_trace: %s (status %d)\n", e.what(), (int)e.status);
+        return 1;
+    }
+    return 0;
+}

@@ -1,0 +1,119 @@
+// rls_trace.hpp -- C++14 host-side mirror of the caller-traced rlGgx integrators (include/rlshaders_amd_trace.h,
+// librls_trace.so).  Header-only, in the style of rls_batch.hpp, whose Device / Planes / check it uses.
+//
+// Where the reference traces inside integrateGlossy / integrateRefract (AiBRDFIntegrate, src/rlGgx.h:172-179; AiTrace,
+// src/rlGgx.h:228-244), a renderer's bucket flush does three steps:
+//     rlsb::RayQueue q(dev, n, spp_n, rlsb::RayQueue::Glossy);
+//     rlsb::emitGlossy(dev, closure, n, spp_n, seed, q, avgReflectWeight);   // every sample ray, compacted
+//     ... trace q.dir() [q.count() rays] with the renderer's tracer, one radiance per ray -> radiance (3 planes) ...
+//     rlsb::resolveGlossy(dev, q, radiance, sum);                           // sum of radiance x f/pdf per point
+// Nothing here synchronises the host except RayQueue::count() (it reads offsets[n]).
+#pragma once
+
+#include <cstdint>
+
+#include "rls_batch.hpp"
+#include "rlshaders_amd_trace.h"
+
+namespace rlsb {
+
+// The device buffers of one emit: per-ray planes for n * spp_n^2 rays, offsets [n + 1] and the emit's scratch.
+class RayQueue {
+public:
+    enum Kind { Glossy, Refract };
+
+    RayQueue(const Device &d, int64_t n, int spp_n, Kind kind) : dev_(&d), n_(n), spp_n_(spp_n), kind_(kind)
+    {
+        const int64_t cap = n * spp_n * spp_n;
+        size_t scratch = 0;
+        check(rls_trace_scratch_bytes(n, spp_n, &scratch));
+        try {
+            allocate(cap, scratch);
+        } catch (...) {
+            release();
+            throw;
+        }
+    }
+    ~RayQueue() { release(); }
+    RayQueue(const RayQueue &) = delete;
+    RayQueue &operator=(const RayQueue &) = delete;
+
+    const rls_ray_queue &c() const { return q_; }
+    int64_t points() const { return n_; }
+    int sppN() const { return spp_n_; }
+    Kind kind() const { return kind_; }
+    // offsets[n]: the number of rays (synchronises)
+    int64_t count() const
+    {
+        int64_t c = 0;
+        check(rls_copy_to_host(dev_->ctx(), &c, q_.offsets + n_, sizeof(c)));
+        return c;
+    }
+
+private:
+    void allocate(int64_t cap, size_t scratch)
+    {
+        q_.capacity = cap;
+        q_.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(n_ + 1)));
+        q_.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
+        q_.weight.r = falloc(cap);
+        if (kind_ == Glossy) { q_.weight.g = falloc(cap); q_.weight.b = falloc(cap); }
+        q_.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
+        q_.sample = static_cast<uint8_t *>(alloc((size_t)cap));
+        if (kind_ == Refract) q_.kind = static_cast<uint8_t *>(alloc((size_t)cap));
+        q_.scratch = alloc(scratch);
+        q_.scratch_bytes = scratch;
+    }
+    void release()
+    {
+        for (int k = 0; k < nbufs_; k++) rls_device_free(dev_->ctx(), bufs_[k]);
+        nbufs_ = 0;
+    }
+    void *alloc(size_t bytes)
+    {
+        void *p = nullptr;
+        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
+        bufs_[nbufs_++] = p;
+        return p;
+    }
+    float *falloc(int64_t count) { return static_cast<float *>(alloc(sizeof(float) * (size_t)count)); }
+
+    const Device *dev_;
+    int64_t n_;
+    int spp_n_;
+    Kind kind_;
+    rls_ray_queue q_{};
+    void *bufs_[12] = {};
+    int nbufs_ = 0;
+};
+
+// integrateGlossy's sample rays (src/rlGgx.h:172-179); avgReflectWeight: n floats (getAvgReflectWeight, :181-184) or nullptr
+inline void emitGlossy(const Device &d, const rls_ggx_closure &c, int64_t n, int spp_n, uint32_t seed, RayQueue &q,
+                       float *avgReflectWeight = nullptr, uint64_t first_index = 0)
+{
+    if (q.kind() != RayQueue::Glossy) throw Error(RLS_ERR_INVALID_ARGUMENT, "emitGlossy: a refraction queue");
+    check(rls_trace_ggx_glossy_emit(d.ctx(), n, &c, spp_n, seed, first_index, &q.c(), avgReflectWeight));
+}
+
+// integrateRefract's sample rays (src/rlGgx.h:228-241); tirFraction: n floats or nullptr
+inline void emitRefract(const Device &d, const rls_ggx_closure &c, int64_t n, int spp_n, uint32_t seed, RayQueue &q,
+                        float *tirFraction = nullptr, uint64_t first_index = 0)
+{
+    if (q.kind() != RayQueue::Refract) throw Error(RLS_ERR_INVALID_ARGUMENT, "emitRefract: a glossy queue");
+    check(rls_trace_ggx_refract_emit(d.ctx(), n, &c, spp_n, seed, first_index, &q.c(), tirFraction));
+}
+
+// radiance: 3 planes of >= q.count() floats, one per ray; out: 3 planes of n floats
+inline void resolveGlossy(const Device &d, const RayQueue &q, const Planes &radiance, Planes &sum)
+{
+    check(rls_trace_ggx_glossy_resolve(d.ctx(), q.points(), &q.c(),
+                                       rls_crgb{radiance.plane(0), radiance.plane(1), radiance.plane(2)}, sum.rgb()));
+}
+
+inline void resolveRefract(const Device &d, const RayQueue &q, const Planes &radiance, Planes &result)
+{
+    check(rls_trace_ggx_refract_resolve(d.ctx(), q.points(), &q.c(), q.sppN(),
+                                        rls_crgb{radiance.plane(0), radiance.plane(1), radiance.plane(2)}, result.rgb()));
+}
+
+} // namespace rlsb

@@ -1,0 +1,187 @@
+"""Caller-traced rlGgx integrators: emit the sample rays of integrateGlossy / integrateRefract, trace them with your own
+tracer, resolve the radiance (include/rlshaders_amd_trace.h, companion library ``librls_trace.so``).
+
+    q = trace.glossy_rays(sampler, spp_n=4, seed=7)          # RayQueue: q.dir [3, count], q.weight [3, count], ...
+    L = my_tracer(origins[q.point], q.dir)                   # [3, count] radiance, one per ray
+    s = q.resolve(L)                                         # [3, n]: sum of L x f/pdf per point (rls_ggx_integrate's sum)
+
+``count`` is read from the device once (it synchronises); everything else stays asynchronous on the context's stream, so
+``glossy_rays(..., queue=q)`` / ``q.resolve(L, out=...)`` with preallocated tensors can be recorded by ``ctx.capture()``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from pathlib import Path
+from typing import Optional
+
+import torch
+
+from . import _capi as capi
+from ._capi import check
+from .closures import GgxSampler, plane, rgb
+
+TRACE_LIB_PATH = capi._PKG / "lib" / "librls_trace.so"
+
+RLS_RAY_TRANSMITTED = 0
+RLS_RAY_TIR_MIRROR = 1
+
+
+class RayQueue_(C.Structure):
+    """rls_ray_queue"""
+    _fields_ = [("capacity", C.c_int64), ("offsets", C.c_void_p), ("dir", capi.Vec3), ("weight", capi.Rgb),
+                ("point", C.c_void_p), ("sample", C.c_void_p), ("kind", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+_ctx, _i64, _vp = C.c_void_p, C.c_int64, C.c_void_p
+_q = C.POINTER(RayQueue_)
+PROTOTYPES = {
+    "rls_trace_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
+    "rls_trace_ggx_glossy_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
+    "rls_trace_ggx_refract_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
+    "rls_trace_ggx_glossy_resolve": (C.c_int, [_ctx, _i64, _q, capi.CRgb, capi.Rgb]),
+    "rls_trace_ggx_refract_resolve": (C.c_int, [_ctx, _i64, _q, C.c_int, capi.CRgb, capi.Rgb]),
+}
+
+_lib = None
+
+
+def load() -> C.CDLL:
+    """Load (once) and prototype the companion library; RLSHADERS_AMD_TRACE_LIB overrides its path.  The product library is
+    loaded first (the companion takes its contexts and error state from it)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    capi.load()
+    path = Path(os.environ.get("RLSHADERS_AMD_TRACE_LIB", str(TRACE_LIB_PATH)))
+    if not path.exists():
+        raise RuntimeError(f"rlshaders_amd.trace: {path} not found. Build it with "
+                           f"`python -c 'from rlshaders_amd import build; build.build_trace_library()'` (needs hipcc).")
+    lib = C.CDLL(str(path), mode=C.RTLD_GLOBAL)
+    missing = [n for n in PROTOTYPES if not hasattr(lib, n)]
+    if missing:
+        raise RuntimeError(f"rlshaders_amd.trace: {path} lacks C-ABI symbols: {missing}")
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    _lib = lib
+    return lib
+
+
+def scratch_bytes(n: int, spp_n: int) -> int:
+    b = C.c_size_t()
+    check(load().rls_trace_scratch_bytes(int(n), int(spp_n), C.byref(b)))
+    return int(b.value)
+
+
+class RayQueue:
+    """The sample rays of one emit over n points at spp_n^2 samples, point-major (CSR: point i's rays are
+    [offsets[i], offsets[i+1])).  Planes are allocated for the full capacity n * spp_n^2; the properties below view the
+    first ``count`` rays."""
+
+    def __init__(self, ctx, n: int, spp_n: int, refract: bool, want_kind: bool = True):
+        self.ctx, self.n, self.spp_n, self.refract = ctx, int(n), int(spp_n), bool(refract)
+        dev = ctx.torch_device
+        cap = self.n * self.spp_n * self.spp_n
+        self.capacity = cap
+        self.offsets = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
+        self._dir = torch.empty(3, cap, dtype=torch.float32, device=dev)
+        self._weight = torch.empty(1 if refract else 3, cap, dtype=torch.float32, device=dev)
+        self._point = torch.empty(cap, dtype=torch.int32, device=dev)          # uint32 on the device; n < 2^31 here
+        self._sample = torch.empty(cap, dtype=torch.uint8, device=dev)
+        self._kind = torch.empty(cap, dtype=torch.uint8, device=dev) if refract and want_kind else None
+        self._scratch = torch.empty(max(scratch_bytes(self.n, self.spp_n), 1), dtype=torch.uint8, device=dev)
+        # per point: getAvgReflectWeight (glossy) / the fraction of totally internally reflected samples (refraction)
+        self.side = torch.empty(self.n, dtype=torch.float32, device=dev)
+        w = self._weight
+        q = RayQueue_()
+        q.capacity = cap
+        q.offsets = self.offsets.data_ptr()
+        q.dir = capi.Vec3(*[self._dir[k].data_ptr() for k in range(3)])
+        q.weight = capi.Rgb(w[0].data_ptr(), None if refract else w[1].data_ptr(), None if refract else w[2].data_ptr())
+        q.point, q.sample = self._point.data_ptr(), self._sample.data_ptr()
+        q.kind = self._kind.data_ptr() if self._kind is not None else None
+        q.scratch, q.scratch_bytes = self._scratch.data_ptr(), self._scratch.numel()
+        self.q = q
+
+    @property
+    def count(self) -> int:
+        """offsets[n]: the number of rays (reads the device: synchronises)"""
+        return int(self.offsets[self.n].item())
+
+    @property
+    def dir(self) -> torch.Tensor:
+        return self._dir[:, :self.count]
+
+    @property
+    def weight(self) -> torch.Tensor:
+        """[3, count] f/pdf (glossy) or [1, count] getSampleWeight (refraction)"""
+        return self._weight[:, :self.count]
+
+    @property
+    def point(self) -> torch.Tensor:
+        return self._point[:self.count]
+
+    @property
+    def sample(self) -> torch.Tensor:
+        return self._sample[:self.count]
+
+    @property
+    def kind(self) -> Optional[torch.Tensor]:
+        return None if self._kind is None else self._kind[:self.count]
+
+    @property
+    def avg_reflect_weight(self) -> torch.Tensor:
+        if self.refract:
+            raise AttributeError("a refraction queue has tir_fraction, not avg_reflect_weight")
+        return self.side
+
+    @property
+    def tir_fraction(self) -> torch.Tensor:
+        if not self.refract:
+            raise AttributeError("a glossy queue has avg_reflect_weight, not tir_fraction")
+        return self.side
+
+    def resolve(self, radiance: torch.Tensor, out: Optional[torch.Tensor] = None, count: Optional[int] = None) -> torch.Tensor:
+        """radiance [3, >= count] float32, one per ray -> [3, n]: glossy the sum of radiance x f/pdf per point (the
+        convention of rls_ggx_integrate's sum), refraction the mean of radiance x weight over the spp_n^2 samples.
+        ``count``: the ray count when the caller knows it (skips the read of offsets[n], e.g. while recording a graph)."""
+        ctx, n = self.ctx, self.n
+        count = self.count if count is None else int(count)
+        if not isinstance(radiance, torch.Tensor) or radiance.dtype != torch.float32 or not radiance.is_cuda or \
+                radiance.dim() != 2 or radiance.shape[0] != 3 or radiance.shape[1] < count or radiance.stride(1) != 1:
+            raise ValueError(f"radiance: expected a float32 CUDA tensor [3, >= {count}] with unit inner stride")
+        res = ctx.empty(3, n) if out is None else out
+        L = capi.CRgb(radiance[0].data_ptr(), radiance[1].data_ptr(), radiance[2].data_ptr())
+        lib = load()
+        if self.refract:
+            check(lib.rls_trace_ggx_refract_resolve(ctx.handle, n, C.byref(self.q), self.spp_n, L, rgb(res, n, "result")))
+        else:
+            check(lib.rls_trace_ggx_glossy_resolve(ctx.handle, n, C.byref(self.q), L, rgb(res, n, "sum")))
+        return res
+
+
+def _emit(sampler: GgxSampler, spp_n: int, seed: int, first_index: int, queue: Optional[RayQueue], refract: bool) -> RayQueue:
+    ctx, n = sampler.ctx, sampler.n
+    q = RayQueue(ctx, n, spp_n, refract) if queue is None else queue
+    if q.n != n or q.spp_n != int(spp_n) or q.refract != refract:
+        raise ValueError("queue: allocated for another batch size, spp_n or integrator")
+    lib = load()
+    fn = lib.rls_trace_ggx_refract_emit if refract else lib.rls_trace_ggx_glossy_emit
+    check(fn(ctx.handle, n, C.byref(sampler.c), int(spp_n), int(seed) & 0xFFFFFFFF, int(first_index), C.byref(q.q),
+             plane(q.side, n, "side") if n > 0 else None))
+    return q
+
+
+def glossy_rays(sampler: GgxSampler, spp_n: int, seed: int, first_index: int = 0, queue: Optional[RayQueue] = None) -> RayQueue:
+    """integrateGlossy's sample rays (src/rlGgx.h:172-179): the samples rls_ggx_integrate draws, those with f/pdf != 0 queued
+    with their direction and f/pdf; ``queue.avg_reflect_weight`` as rls_ggx_integrate writes it."""
+    return _emit(sampler, spp_n, seed, first_index, queue, False)
+
+
+def refract_rays(sampler: GgxSampler, spp_n: int, seed: int, first_index: int = 0, queue: Optional[RayQueue] = None) -> RayQueue:
+    """integrateRefract's sample rays (src/rlGgx.h:228-241): the samples rls_ggx_integrate_refract(traced=1) draws, those with
+    a non-zero weight queued with their direction, weight and kind (RLS_RAY_TRANSMITTED / RLS_RAY_TIR_MIRROR);
+    ``queue.tir_fraction`` as rls_ggx_integrate_refract writes it."""
+    return _emit(sampler, spp_n, seed, first_index, queue, True)

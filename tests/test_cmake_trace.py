@@ -1,0 +1,64 @@
+"""CPU: the CMake build carries the companion library of the caller-traced integrators (librls_trace.so,
+include/rlshaders_amd_trace.h): it builds for gfx950 beside librlshaders_amd.so, exports exactly the rls_trace_* symbols its
+header declares, installs with its header and the C++ mirror, and an outside project links rlshaders_amd::trace."""
+import os
+import shutil
+import subprocess
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+BUILD = ROOT / "rlshaders_amd" / "build" / "cmake"          # the tree tests/test_cmake_build.py builds (incremental)
+PREFIX = ROOT / "rlshaders_amd" / "build" / "cmake_trace_prefix"
+
+CONSUMER = """cmake_minimum_required(VERSION 3.21)
+project(rls_trace_consumer LANGUAGES CXX)
+find_package(rlshaders_amd REQUIRED)
+add_executable(consumer ${RLS_EXAMPLE_SOURCE})
+set_target_properties(consumer PROPERTIES CXX_STANDARD 14 CXX_STANDARD_REQUIRED ON)
+target_link_libraries(consumer PRIVATE rlshaders_amd::trace)
+"""
+
+
+def _run(cmd, **kw):
+    p = subprocess.run(cmd, capture_output=True, text=True, **kw)
+    assert p.returncode == 0, f"{' '.join(map(str, cmd))}\n{p.stdout[-3000:]}\n{p.stderr[-3000:]}"
+    return p.stdout
+
+
+@pytest.fixture(scope="module")
+def built():
+    if shutil.which("cmake") is None:
+        pytest.skip("cmake is not installed")
+    gen = ["-G", "Ninja"] if shutil.which("ninja") else []
+    _run(["cmake", "-S", str(ROOT), "-B", str(BUILD), *gen])
+    _run(["cmake", "--build", str(BUILD), "-j", str(min(6, os.cpu_count() or 2))])
+    shutil.rmtree(PREFIX, ignore_errors=True)
+    _run(["cmake", "--install", str(BUILD), "--prefix", str(PREFIX)])
+    return BUILD
+
+
+def test_companion_builds_and_exports_its_header(built):
+    from test_trace_abi import declared_trace_symbols, exported_trace_symbols
+    lib = built / "librls_trace.so"
+    assert lib.exists()
+    assert exported_trace_symbols(lib) == declared_trace_symbols()
+    assert "librlshaders_amd.so" in _run(["readelf", "-d", str(lib)])
+    assert (built / "example_trace").exists()
+
+
+def test_install_and_outside_consumer(built, tmp_path):
+    for rel in ("include/rlshaders_amd_trace.h", "include/rls_trace.hpp", "lib/librls_trace.so", "lib/librlshaders_amd.so"):
+        assert (PREFIX / rel).exists(), rel
+    src = tmp_path / "src"
+    src.mkdir()
+    (src / "CMakeLists.txt").write_text(CONSUMER)
+    gen = ["-G", "Ninja"] if shutil.which("ninja") else []
+    _run(["cmake", "-S", str(src), "-B", str(tmp_path / "b"), *gen, f"-DCMAKE_PREFIX_PATH={PREFIX}",
+          f"-DRLS_EXAMPLE_SOURCE={ROOT / 'rlshaders_amd' / 'host' / 'example_trace.cpp'}"])
+    _run(["cmake", "--build", str(tmp_path / "b")])
+    exe = tmp_path / "b" / "consumer"
+    assert exe.exists()
+    needed = _run(["readelf", "-d", str(exe)])
+    assert "librls_trace.so" in needed and "librlshaders_amd.so" in needed
