@@ -84,10 +84,10 @@ template <int OP>
 rls_status launch_kernel(rls_context *ctx, const AltIO &io, const char *name)
 {
     hipLaunchKernelGGL(alt_kernel<OP>, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
-    return rlsh::check_launch(name);
+    return rlsh::check_launch(name, RLS_FAST);
 }
 
-rls_status dispatch(rls_context *ctx, int op, const AltIO &io, const char *name)
+rls_status launch_alt(rls_context *ctx, int op, const AltIO &io, const char *name)
 {
     switch (op) {
     case AOP_GTR2_ANISO: return launch_kernel<AOP_GTR2_ANISO>(ctx, io, name);
@@ -101,30 +101,9 @@ rls_status dispatch(rls_context *ctx, int op, const AltIO &io, const char *name)
 
 } // namespace
 
-#if RLS_FAST
-RLS_HIDDEN rls_status rls_fast_alt(rls_context *ctx, int op, const rlsh::AltIO *io) { return dispatch(ctx, op, *io, "alternates[fast]"); }
-#else
-RLS_HIDDEN rls_status rls_fast_alt(rls_context *ctx, int op, const rlsh::AltIO *io);
+RLS_FLAVOURS(alt, rlsh::AltIO)
 
-namespace {
-rls_status run(rls_context *ctx, int op, const AltIO &io, const char *name)
-{
-    return ctx->fast ? rls_fast_alt(ctx, op, &io) : dispatch(ctx, op, io, name);
-}
-rls_status check_closure(const rls_disney_closure *c)
-{
-    RLS_REQUIRE(c != nullptr, "closure is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T), "wo/N/T plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->base_color), "base_color planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
-    return RLS_OK;
-}
-} // namespace
-
-#define RLS_PROLOGUE()                                   \
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");          \
-    RLS_REQUIRE(n >= 0, "n < 0");                        \
-    if (n == 0) return RLS_OK;
+#if !RLS_FAST
 
 extern "C" {
 
@@ -132,32 +111,32 @@ rls_status rls_disney_alt_sample(rls_context *ctx, int64_t n, const rls_disney_c
                                  const float *rx, const float *ry, rls_vec3 m)
 {
     RLS_PROLOGUE();
-    { rls_status s = check_closure(c); if (s != RLS_OK) return s; }
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(kind == RLS_DISNEY_ALT_GTR2_ANISO || kind == RLS_DISNEY_ALT_GTR2, "unknown alternate sampler");
     RLS_REQUIRE(rx && ry && rlsh::has3(m), "NULL plane");
     AltIO io = {};
     io.c = *c; io.rx = rx; io.ry = ry; io.out3 = m; io.n = n;
-    return run(ctx, kind == RLS_DISNEY_ALT_GTR2_ANISO ? AOP_GTR2_ANISO : AOP_GTR2, io, "rls_disney_alt_sample");
+    return dispatch_alt(ctx, kind == RLS_DISNEY_ALT_GTR2_ANISO ? AOP_GTR2_ANISO : AOP_GTR2, io, "rls_disney_alt_sample");
 }
 
 rls_status rls_disney_alt_pdf(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 wi, float *pdf)
 {
     RLS_PROLOGUE();
-    { rls_status s = check_closure(c); if (s != RLS_OK) return s; }
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(wi) && pdf, "NULL plane");
     AltIO io = {};
     io.c = *c; io.v = wi; io.out1 = pdf; io.n = n;
-    return run(ctx, AOP_NDF_PDF, io, "rls_disney_alt_pdf");
+    return dispatch_alt(ctx, AOP_NDF_PDF, io, "rls_disney_alt_pdf");
 }
 
 rls_status rls_disney_d_gtr2(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 m, float *d)
 {
     RLS_PROLOGUE();
-    { rls_status s = check_closure(c); if (s != RLS_OK) return s; }
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(m) && d, "NULL plane");
     AltIO io = {};
     io.c = *c; io.v = m; io.out1 = d; io.n = n;
-    return run(ctx, AOP_D_GTR2, io, "rls_disney_d_gtr2");
+    return dispatch_alt(ctx, AOP_D_GTR2, io, "rls_disney_d_gtr2");
 }
 
 rls_status rls_gaussian_sample(rls_context *ctx, int64_t n, rls_param dist_x, const float *rx,
@@ -167,7 +146,7 @@ rls_status rls_gaussian_sample(rls_context *ctx, int64_t n, rls_param dist_x, co
     RLS_REQUIRE(rx && r && pdf && profile, "NULL plane");
     AltIO io = {};
     io.dist_x = dist_x; io.rx = rx; io.r = r; io.pdf = pdf; io.profile = profile; io.n = n;
-    return run(ctx, AOP_GAUSS, io, "rls_gaussian_sample");
+    return dispatch_alt(ctx, AOP_GAUSS, io, "rls_gaussian_sample");
 }
 
 rls_status rls_libm_eval(rls_context *ctx, int fn, int64_t n, const float *x, const float *y, float *out)
@@ -178,7 +157,7 @@ rls_status rls_libm_eval(rls_context *ctx, int fn, int64_t n, const float *x, co
     RLS_REQUIRE(x && out && (!binary || y), "NULL plane");
     AltIO io = {};
     io.rx = x; io.ry = binary ? y : nullptr; io.out1 = out; io.fn = fn; io.n = n;
-    return run(ctx, AOP_LIBM, io, "rls_libm_eval");
+    return dispatch_alt(ctx, AOP_LIBM, io, "rls_libm_eval");
 }
 
 } // extern "C"

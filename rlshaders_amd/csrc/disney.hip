@@ -119,16 +119,6 @@ __global__ RLS_DISNEY_ATTR void disney_kernel(DisneyIO a0)
     }
 }
 
-rls_status check_closure(const rls_disney_closure *c, int lobe)
-{
-    RLS_REQUIRE(c != nullptr, "closure is NULL");
-    RLS_REQUIRE(lobe == RLS_RAY_DIFFUSE || lobe == RLS_RAY_GLOSSY, "lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T), "wo/N/T plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->base_color), "base_color planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
-    return RLS_OK;
-}
-
 template <int OP>
 rls_status launch_kernel(rls_context *ctx, int lobe, const DisneyIO &io, const char *name)
 {
@@ -153,37 +143,26 @@ rls_status launch_kernel(rls_context *ctx, int lobe, const DisneyIO &io, const c
         else if (colour_map) hipLaunchKernelGGL((disney_kernel<OP, false, RLS_FAST, UNIFORM_SCALARS>), grid, block, 0, ctx->stream, io);
         else hipLaunchKernelGGL((disney_kernel<OP, false, RLS_FAST, MIXED>), grid, block, 0, ctx->stream, io);
     }
-    return rlsh::check_launch(name);
+    return rlsh::check_launch(name, RLS_FAST);
 }
 
-} // namespace
-
-#if RLS_FAST
-RLS_HIDDEN rls_status rls_fast_disney(rls_context *ctx, int op, int lobe, const rlsh::DisneyIO *io)
+// sel: the op | the lobe (RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY, bits above the op's)
+rls_status launch_disney(rls_context *ctx, int sel, const DisneyIO &io, const char *name)
 {
-    switch (op) {
-    case OP_SAMPLE: return launch_kernel<OP_SAMPLE>(ctx, lobe, *io, "rls_disney_sample[fast]");
-    case OP_EVAL: return launch_kernel<OP_EVAL>(ctx, lobe, *io, "rls_disney_eval[fast]");
-    case OP_PDF: return launch_kernel<OP_PDF>(ctx, lobe, *io, "rls_disney_pdf[fast]");
-    default: return launch_kernel<OP_FUSED>(ctx, lobe, *io, "rls_disney_sample_eval_pdf[fast]");
+    const int lobe = sel & ~7;
+    switch (sel & 7) {
+    case OP_SAMPLE: return launch_kernel<OP_SAMPLE>(ctx, lobe, io, name);
+    case OP_EVAL: return launch_kernel<OP_EVAL>(ctx, lobe, io, name);
+    case OP_PDF: return launch_kernel<OP_PDF>(ctx, lobe, io, name);
+    default: return launch_kernel<OP_FUSED>(ctx, lobe, io, name);
     }
 }
-#else
-RLS_HIDDEN rls_status rls_fast_disney(rls_context *ctx, int op, int lobe, const rlsh::DisneyIO *io);
 
-namespace {
-template <int OP>
-rls_status launch(rls_context *ctx, int lobe, const DisneyIO &io, const char *name)
-{
-    return ctx->fast ? rls_fast_disney(ctx, OP, lobe, &io) : launch_kernel<OP>(ctx, lobe, io, name);
-}
 } // namespace
 
-#define RLS_PROLOGUE()                                   \
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");          \
-    RLS_REQUIRE(n >= 0, "n < 0");                        \
-    if (n == 0) return RLS_OK;                           \
-    { rls_status _s = check_closure(c, lobe); if (_s != RLS_OK) return _s; }
+RLS_FLAVOURS(disney, rlsh::DisneyIO)
+
+#if !RLS_FAST
 
 extern "C" {
 
@@ -191,31 +170,40 @@ rls_status rls_disney_sample(rls_context *ctx, int64_t n, const rls_disney_closu
                              const float *rx, const float *ry, rls_vec3 wi)
 {
     RLS_PROLOGUE();
+    RLS_REQUIRE(c != nullptr, "closure is NULL");
+    RLS_REQUIRE(lobe == RLS_RAY_DIFFUSE || lobe == RLS_RAY_GLOSSY, "lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY");
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rx && ry, "rx/ry is NULL");
     RLS_REQUIRE(rlsh::has3(wi), "wi plane is NULL");
     DisneyIO io = {};
     io.c = *c; io.rx = rx; io.ry = ry; io.wi = wi; io.n = n;
-    return launch<OP_SAMPLE>(ctx, lobe, io, "rls_disney_sample");
+    return dispatch_disney(ctx, OP_SAMPLE | lobe, io, "rls_disney_sample");
 }
 
 rls_status rls_disney_eval(rls_context *ctx, int64_t n, const rls_disney_closure *c, int lobe,
                            rls_cvec3 wi, rls_rgb f)
 {
     RLS_PROLOGUE();
+    RLS_REQUIRE(c != nullptr, "closure is NULL");
+    RLS_REQUIRE(lobe == RLS_RAY_DIFFUSE || lobe == RLS_RAY_GLOSSY, "lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY");
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(wi) && rlsh::has3(f), "wi/f plane is NULL");
     DisneyIO io = {};
     io.c = *c; io.cwi = wi; io.f = f; io.n = n;
-    return launch<OP_EVAL>(ctx, lobe, io, "rls_disney_eval");
+    return dispatch_disney(ctx, OP_EVAL | lobe, io, "rls_disney_eval");
 }
 
 rls_status rls_disney_pdf(rls_context *ctx, int64_t n, const rls_disney_closure *c, int lobe,
                           rls_cvec3 wi, float *pdf)
 {
     RLS_PROLOGUE();
+    RLS_REQUIRE(c != nullptr, "closure is NULL");
+    RLS_REQUIRE(lobe == RLS_RAY_DIFFUSE || lobe == RLS_RAY_GLOSSY, "lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY");
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(wi) && pdf, "wi/pdf is NULL");
     DisneyIO io = {};
     io.c = *c; io.cwi = wi; io.pdf = pdf; io.n = n;
-    return launch<OP_PDF>(ctx, lobe, io, "rls_disney_pdf");
+    return dispatch_disney(ctx, OP_PDF | lobe, io, "rls_disney_pdf");
 }
 
 rls_status rls_disney_sample_eval_pdf(rls_context *ctx, int64_t n, const rls_disney_closure *c, int lobe,
@@ -223,11 +211,14 @@ rls_status rls_disney_sample_eval_pdf(rls_context *ctx, int64_t n, const rls_dis
                                       rls_vec3 wi, rls_rgb f, float *pdf)
 {
     RLS_PROLOGUE();
+    RLS_REQUIRE(c != nullptr, "closure is NULL");
+    RLS_REQUIRE(lobe == RLS_RAY_DIFFUSE || lobe == RLS_RAY_GLOSSY, "lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY");
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rx && ry, "rx/ry is NULL");
     RLS_REQUIRE(rlsh::has3(wi) && rlsh::has3(f) && pdf, "wi/f/pdf is NULL");
     DisneyIO io = {};
     io.c = *c; io.rx = rx; io.ry = ry; io.wi = wi; io.f = f; io.pdf = pdf; io.n = n;
-    return launch<OP_FUSED>(ctx, lobe, io, "rls_disney_sample_eval_pdf");
+    return dispatch_disney(ctx, OP_FUSED | lobe, io, "rls_disney_sample_eval_pdf");
 }
 
 } // extern "C"

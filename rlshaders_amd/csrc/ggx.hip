@@ -152,71 +152,43 @@ __global__ RLS_GGX_ATTR(OP) void ggx_kernel_stamped(GgxIO a0, unsigned long long
 }
 #endif
 
-rls_status check_closure(const rls_ggx_closure *c)
-{
-    RLS_REQUIRE(c != nullptr, "closure is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T), "wo/N/T plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->KsColor), "KsColor planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
-    return RLS_OK;
-}
-
 template <int OP>
 rls_status launch_kernel(rls_context *ctx, const GgxIO &io, const char *name)
 {
     const rls_ggx_closure &c = io.c;
     const bool streamed = !c.materials.id && c.KsColor.r && c.specularRoughness.v && c.ior.v && c.anisotropic.v;
     const bool uniform = !c.materials.id && !c.specularRoughness.v && !c.ior.v && !c.anisotropic.v;       // specColor: either
-#if RLS_DIAGNOSTICS
-    if constexpr (OP == OP_REFLECT_REFRACT) {      // BASELINE config 2 under rls_diag_clock_stamps_begin: the stamped instantiation
-        if (unsigned long long *stamps = streamed ? rlsh::stamps_for_launch(ctx) : nullptr) {
-            hipLaunchKernelGGL((ggx_kernel_stamped<OP, RLS_FAST, STREAMED_ALL>), rlsh::grid_for(ctx, io.n, rlsh::kBlock, RLS_CAP_MULT),
-                               dim3(rlsh::kBlock), 0, ctx->stream, io, stamps);
-            return rlsh::check_launch(name);
-        }
-    }
-#endif
+    if constexpr (OP == OP_REFLECT_REFRACT)        // BASELINE config 2 under rls_diag_clock_stamps_begin
+        RLS_STAMPED_LAUNCH(streamed, (ggx_kernel_stamped<OP, RLS_FAST, STREAMED_ALL>),
+                           rlsh::grid_for(ctx, io.n, rlsh::kBlock, RLS_CAP_MULT), io, name);
     if (streamed)
         hipLaunchKernelGGL((ggx_kernel<OP, RLS_FAST, STREAMED_ALL>), rlsh::grid_for(ctx, io.n, rlsh::kBlock, RLS_CAP_MULT), dim3(rlsh::kBlock), 0, ctx->stream, io);
     else if (uniform)   // a thread that hoists wants many tiles to spread the hoisted work over (grid_for_hoisting)
         hipLaunchKernelGGL((ggx_kernel<OP, RLS_FAST, UNIFORM_MATERIAL>), rlsh::grid_for_hoisting(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
     else
         hipLaunchKernelGGL((ggx_kernel<OP, RLS_FAST, MIXED>), rlsh::grid_for(ctx, io.n, rlsh::kBlock, RLS_CAP_MULT), dim3(rlsh::kBlock), 0, ctx->stream, io);
-    return rlsh::check_launch(name);
+    return rlsh::check_launch(name, RLS_FAST);
 }
 
-} // namespace
-
-#if RLS_FAST
-RLS_HIDDEN rls_status rls_fast_ggx(rls_context *ctx, int op, const rlsh::GgxIO *io)
+rls_status launch_ggx(rls_context *ctx, int op, const GgxIO &io, const char *name)
 {
     switch (op) {
-    case OP_SAMPLE: return launch_kernel<OP_SAMPLE>(ctx, *io, "rls_ggx_sample[fast]");
-    case OP_EVAL: return launch_kernel<OP_EVAL>(ctx, *io, "rls_ggx_eval[fast]");
-    case OP_PDF: return launch_kernel<OP_PDF>(ctx, *io, "rls_ggx_pdf[fast]");
-    case OP_FUSED: return launch_kernel<OP_FUSED>(ctx, *io, "rls_ggx_sample_eval_pdf[fast]");
-    case OP_REFRACT: return launch_kernel<OP_REFRACT>(ctx, *io, "rls_ggx_refract_sample[fast]");
-    case OP_REFLECT_REFRACT: return launch_kernel<OP_REFLECT_REFRACT>(ctx, *io, "rls_ggx_reflect_refract[fast]");
-    case OP_MICROFACET: return launch_kernel<OP_MICROFACET>(ctx, *io, "rls_ggx_microfacet[fast]");
-    default: return launch_kernel<OP_NDF_PDF>(ctx, *io, "rls_ggx_ndf_pdf[fast]");
+    case OP_SAMPLE: return launch_kernel<OP_SAMPLE>(ctx, io, name);
+    case OP_EVAL: return launch_kernel<OP_EVAL>(ctx, io, name);
+    case OP_PDF: return launch_kernel<OP_PDF>(ctx, io, name);
+    case OP_FUSED: return launch_kernel<OP_FUSED>(ctx, io, name);
+    case OP_REFRACT: return launch_kernel<OP_REFRACT>(ctx, io, name);
+    case OP_REFLECT_REFRACT: return launch_kernel<OP_REFLECT_REFRACT>(ctx, io, name);
+    case OP_MICROFACET: return launch_kernel<OP_MICROFACET>(ctx, io, name);
+    default: return launch_kernel<OP_NDF_PDF>(ctx, io, name);
     }
 }
-#else
-RLS_HIDDEN rls_status rls_fast_ggx(rls_context *ctx, int op, const rlsh::GgxIO *io);
 
-namespace {
-template <int OP>
-rls_status launch(rls_context *ctx, const GgxIO &io, const char *name)
-{
-    return ctx->fast ? rls_fast_ggx(ctx, OP, &io) : launch_kernel<OP>(ctx, io, name);
-}
 } // namespace
 
-#define RLS_PROLOGUE()                                   \
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");          \
-    RLS_REQUIRE(n >= 0, "n < 0");                        \
-    if (n == 0) return RLS_OK;                           \
-    { rls_status _s = check_closure(c); if (_s != RLS_OK) return _s; }
+RLS_FLAVOURS(ggx, rlsh::GgxIO)
+
+#if !RLS_FAST
 
 extern "C" {
 
@@ -224,29 +196,32 @@ rls_status rls_ggx_sample(rls_context *ctx, int64_t n, const rls_ggx_closure *c,
                           const float *rx, const float *ry, rls_vec3 wi, float *fresnel)
 {
     RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rx && ry, "rx/ry is NULL");
     RLS_REQUIRE(rlsh::has3(wi), "wi plane is NULL");
     GgxIO io = {};
     io.c = *c; io.rx = rx; io.ry = ry; io.wi = wi; io.fresnel = fresnel; io.n = n;
-    return launch<OP_SAMPLE>(ctx, io, "rls_ggx_sample");
+    return dispatch_ggx(ctx, OP_SAMPLE, io, "rls_ggx_sample");
 }
 
 rls_status rls_ggx_eval(rls_context *ctx, int64_t n, const rls_ggx_closure *c, rls_cvec3 wi, rls_rgb f)
 {
     RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(wi) && rlsh::has3(f), "wi/f plane is NULL");
     GgxIO io = {};
     io.c = *c; io.cwi = wi; io.f = f; io.n = n;
-    return launch<OP_EVAL>(ctx, io, "rls_ggx_eval");
+    return dispatch_ggx(ctx, OP_EVAL, io, "rls_ggx_eval");
 }
 
 rls_status rls_ggx_pdf(rls_context *ctx, int64_t n, const rls_ggx_closure *c, rls_cvec3 wi, float *pdf)
 {
     RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(wi) && pdf, "wi/pdf is NULL");
     GgxIO io = {};
     io.c = *c; io.cwi = wi; io.pdf = pdf; io.n = n;
-    return launch<OP_PDF>(ctx, io, "rls_ggx_pdf");
+    return dispatch_ggx(ctx, OP_PDF, io, "rls_ggx_pdf");
 }
 
 rls_status rls_ggx_sample_eval_pdf(rls_context *ctx, int64_t n, const rls_ggx_closure *c,
@@ -254,11 +229,12 @@ rls_status rls_ggx_sample_eval_pdf(rls_context *ctx, int64_t n, const rls_ggx_cl
                                    rls_vec3 wi, rls_rgb f, float *pdf, float *fresnel)
 {
     RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rx && ry, "rx/ry is NULL");
     RLS_REQUIRE(rlsh::has3(wi) && rlsh::has3(f) && pdf, "wi/f/pdf is NULL");
     GgxIO io = {};
     io.c = *c; io.rx = rx; io.ry = ry; io.wi = wi; io.f = f; io.pdf = pdf; io.fresnel = fresnel; io.n = n;
-    return launch<OP_FUSED>(ctx, io, "rls_ggx_sample_eval_pdf");
+    return dispatch_ggx(ctx, OP_FUSED, io, "rls_ggx_sample_eval_pdf");
 }
 
 rls_status rls_ggx_refract_sample(rls_context *ctx, int64_t n, const rls_ggx_closure *c,
@@ -266,11 +242,12 @@ rls_status rls_ggx_refract_sample(rls_context *ctx, int64_t n, const rls_ggx_clo
                                   rls_vec3 wt, float *weight, uint8_t *refracted)
 {
     RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rx && ry, "rx/ry is NULL");
     RLS_REQUIRE(rlsh::has3(wt) && weight, "wt/weight is NULL");
     GgxIO io = {};
     io.c = *c; io.rx = rx; io.ry = ry; io.wt = wt; io.weight = weight; io.refracted = refracted; io.n = n;
-    return launch<OP_REFRACT>(ctx, io, "rls_ggx_refract_sample");
+    return dispatch_ggx(ctx, OP_REFRACT, io, "rls_ggx_refract_sample");
 }
 
 rls_status rls_ggx_reflect_refract(rls_context *ctx, int64_t n, const rls_ggx_closure *c,
@@ -279,34 +256,37 @@ rls_status rls_ggx_reflect_refract(rls_context *ctx, int64_t n, const rls_ggx_cl
                                    rls_vec3 wt, float *weight)
 {
     RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rx && ry && rx2 && ry2, "random-number plane is NULL");
     RLS_REQUIRE(rlsh::has3(wi) && rlsh::has3(f) && pdf, "wi/f/pdf is NULL");
     RLS_REQUIRE(rlsh::has3(wt) && weight, "wt/weight is NULL");
     GgxIO io = {};
     io.c = *c; io.rx = rx; io.ry = ry; io.rx2 = rx2; io.ry2 = ry2;
     io.wi = wi; io.f = f; io.pdf = pdf; io.fresnel = fresnel; io.wt = wt; io.weight = weight; io.n = n;
-    return launch<OP_REFLECT_REFRACT>(ctx, io, "rls_ggx_reflect_refract");
+    return dispatch_ggx(ctx, OP_REFLECT_REFRACT, io, "rls_ggx_reflect_refract");
 }
 
 rls_status rls_ggx_microfacet(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int kernel,
                               const float *rx, const float *ry, rls_vec3 m)
 {
     RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(kernel == RLS_KERNEL_VNDF || kernel == RLS_KERNEL_NDF, "unknown sampling kernel");
     RLS_REQUIRE(rx && ry, "rx/ry is NULL");
     RLS_REQUIRE(rlsh::has3(m), "m plane is NULL");
     GgxIO io = {};
     io.c = *c; io.rx = rx; io.ry = ry; io.wi = m; io.kernel = kernel; io.n = n;
-    return launch<OP_MICROFACET>(ctx, io, "rls_ggx_microfacet");
+    return dispatch_ggx(ctx, OP_MICROFACET, io, "rls_ggx_microfacet");
 }
 
 rls_status rls_ggx_ndf_pdf(rls_context *ctx, int64_t n, const rls_ggx_closure *c, rls_cvec3 wi, float *pdf)
 {
     RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(wi) && pdf, "wi/pdf is NULL");
     GgxIO io = {};
     io.c = *c; io.cwi = wi; io.pdf = pdf; io.n = n;
-    return launch<OP_NDF_PDF>(ctx, io, "rls_ggx_ndf_pdf");
+    return dispatch_ggx(ctx, OP_NDF_PDF, io, "rls_ggx_ndf_pdf");
 }
 
 } // extern "C"

@@ -225,7 +225,7 @@ inline rls_status launch_disney_stamped(rls_context *ctx, const rlsh::DisneyIntI
 {
     hipLaunchKernelGGL(disney_integrate_kernel_stamped<1>, rlsh::grid_for(ctx, io.n, rlsh::kBlock), dim3(rlsh::kBlock), 0, ctx->stream,
                        io, stamps);
-    return rlsh::check_launch(name);
+    return rlsh::check_launch(name, RLS_FAST);
 }
 #endif
 
@@ -234,22 +234,19 @@ inline rls_status launch_disney_stamped(rls_context *ctx, const rlsh::DisneyIntI
 #if RLS_FAST
 RLS_HIDDEN rls_status rls_fast_ggx_integrate(rls_context *ctx, int g, const rlsh::GgxIntIO *io)
 {
-    return launch_g(ctx, ggx_integrate_kernel<1>, ggx_integrate_kernel<4>, ggx_integrate_kernel<16>,
-                    ggx_integrate_kernel<64>, g, *io, "rls_ggx_integrate[fast]");
+    return launch_g(ctx, RLS_G_FAMILY(ggx_integrate_kernel), g, *io, "rls_ggx_integrate");
 }
 RLS_HIDDEN rls_status rls_fast_disney_integrate(rls_context *ctx, int g, const rlsh::DisneyIntIO *io)
 {
 #if RLS_DIAGNOSTICS
     if (unsigned long long *stamps = g == 1 ? rlsh::stamps_for_launch(ctx) : nullptr)
-        return launch_disney_stamped(ctx, *io, stamps, "rls_disney_integrate[fast, stamped]");
+        return launch_disney_stamped(ctx, *io, stamps, "rls_disney_integrate[stamped]");
 #endif
-    return launch_g(ctx, disney_integrate_kernel<1>, disney_integrate_kernel<4>, disney_integrate_kernel<16>,
-                    disney_integrate_kernel<64>, g, *io, "rls_disney_integrate[fast]");
+    return launch_g(ctx, RLS_G_FAMILY(disney_integrate_kernel), g, *io, "rls_disney_integrate");
 }
 RLS_HIDDEN rls_status rls_fast_ggx_refract_integrate(rls_context *ctx, int g, const rlsh::RefractIntIO *io)
 {
-    return launch_g(ctx, ggx_refract_integrate_kernel<1>, ggx_refract_integrate_kernel<4>, ggx_refract_integrate_kernel<16>,
-                    ggx_refract_integrate_kernel<64>, g, *io, "rls_ggx_integrate_refract[fast]");
+    return launch_g(ctx, RLS_G_FAMILY(ggx_refract_integrate_kernel), g, *io, "rls_ggx_integrate_refract");
 }
 #else
 RLS_HIDDEN rls_status rls_fast_ggx_integrate(rls_context *ctx, int g, const rlsh::GgxIntIO *io);
@@ -262,14 +259,9 @@ rls_status rls_ggx_integrate_refract(rls_context *ctx, int64_t n, const rls_ggx_
                                      const float env[3], int spp_n, uint32_t seed, uint64_t first_index,
                                      rls_rgb result, float *tir_fraction)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    if (n == 0) return RLS_OK;
+    RLS_LOOP_PROLOGUE(spp_n);
     RLS_REQUIRE(c != nullptr && env != nullptr, "closure or env is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T), "wo/N/T plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->KsColor), "KsColor planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(result), "NULL output plane");
     rlsh::RefractIntIO io = {};
     io.c = *c; io.env[0] = env[0]; io.env[1] = env[1]; io.env[2] = env[2]; io.traced = traced ? 1 : 0;
@@ -277,29 +269,21 @@ rls_status rls_ggx_integrate_refract(rls_context *ctx, int64_t n, const rls_ggx_
     io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
     int g = traced ? pick_group(ctx, n, io.spp) : 1;
     if (ctx->fast) return rls_fast_ggx_refract_integrate(ctx, g, &io);
-    return launch_g(ctx, ggx_refract_integrate_kernel<1>, ggx_refract_integrate_kernel<4>, ggx_refract_integrate_kernel<16>,
-                    ggx_refract_integrate_kernel<64>, g, io, "rls_ggx_integrate_refract");
+    return launch_g(ctx, RLS_G_FAMILY(ggx_refract_integrate_kernel), g, io, "rls_ggx_integrate_refract");
 }
 
 rls_status rls_ggx_integrate(rls_context *ctx, int64_t n, const rls_ggx_closure *c,
                              int spp_n, uint32_t seed, uint64_t first_index,
                              rls_rgb sum_f_over_pdf, float *avg_reflect_weight)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    if (n == 0) return RLS_OK;
-    RLS_REQUIRE(c != nullptr, "closure is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T), "wo/N/T plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->KsColor), "KsColor planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    RLS_LOOP_PROLOGUE(spp_n);
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(sum_f_over_pdf) && avg_reflect_weight, "NULL output plane");
     GgxIntIO io = {};
     io.c = *c; io.sum = sum_f_over_pdf; io.avgF = avg_reflect_weight; io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
     int g = pick_group(ctx, n, io.spp);
     if (ctx->fast) return rls_fast_ggx_integrate(ctx, g, &io);
-    return launch_g(ctx, ggx_integrate_kernel<1>, ggx_integrate_kernel<4>, ggx_integrate_kernel<16>,
-                    ggx_integrate_kernel<64>, g, io, "rls_ggx_integrate");
+    return launch_g(ctx, RLS_G_FAMILY(ggx_integrate_kernel), g, io, "rls_ggx_integrate");
 }
 
 rls_status rls_disney_integrate(rls_context *ctx, int64_t n, const rls_disney_closure *c,
@@ -308,14 +292,8 @@ rls_status rls_disney_integrate(rls_context *ctx, int64_t n, const rls_disney_cl
                                 rls_rgb specular_sum, float *specular_count,
                                 const rls_disney_stream_out *stream)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    if (n == 0) return RLS_OK;
-    RLS_REQUIRE(c != nullptr, "closure is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T), "wo/N/T plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->base_color), "base_color planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    RLS_LOOP_PROLOGUE(spp_n);
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(diffuse_sum) && diffuse_count && rlsh::has3(specular_sum) && specular_count,
                 "NULL output plane");
     DisneyIntIO io = {};
@@ -333,8 +311,7 @@ rls_status rls_disney_integrate(rls_context *ctx, int64_t n, const rls_disney_cl
     if (unsigned long long *stamps = g == 1 ? rlsh::stamps_for_launch(ctx) : nullptr)
         return launch_disney_stamped(ctx, io, stamps, "rls_disney_integrate[stamped]");
 #endif
-    return launch_g(ctx, disney_integrate_kernel<1>, disney_integrate_kernel<4>, disney_integrate_kernel<16>,
-                    disney_integrate_kernel<64>, g, io, "rls_disney_integrate");
+    return launch_g(ctx, RLS_G_FAMILY(disney_integrate_kernel), g, io, "rls_disney_integrate");
 }
 
 // Streamed mode in chunks of the point range (2^26 points x 128 triples x 28 B = 241 GB does not fit beside the

@@ -74,22 +74,21 @@ __global__ RLS_DISNEY_LIGHT_ATTR void disney_direct_kernel(DisneyLightIO a)
     }
 }
 
+rls_status launch_ggx_direct(rls_context *ctx, int g, const LightIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(ggx_direct_kernel), g, io, name);
+}
+rls_status launch_disney_direct(rls_context *ctx, int g, const DisneyLightIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(disney_direct_kernel), g, io, name);
+}
+
 } // namespace
 
-#if RLS_FAST
-RLS_HIDDEN rls_status rls_fast_ggx_direct(rls_context *ctx, int g, const rlsh::LightIO *io)
-{
-    return launch_g(ctx, ggx_direct_kernel<1>, ggx_direct_kernel<4>, ggx_direct_kernel<16>,
-                    ggx_direct_kernel<64>, g, *io, "rls_ggx_direct_lighting[fast]");
-}
-RLS_HIDDEN rls_status rls_fast_disney_direct(rls_context *ctx, int g, const rlsh::DisneyLightIO *io)
-{
-    return launch_g(ctx, disney_direct_kernel<1>, disney_direct_kernel<4>, disney_direct_kernel<16>,
-                    disney_direct_kernel<64>, g, *io, "rls_disney_direct_lighting[fast]");
-}
-#else
-RLS_HIDDEN rls_status rls_fast_ggx_direct(rls_context *ctx, int g, const rlsh::LightIO *io);
-RLS_HIDDEN rls_status rls_fast_disney_direct(rls_context *ctx, int g, const rlsh::DisneyLightIO *io);
+RLS_FLAVOURS(ggx_direct, rlsh::LightIO)
+RLS_FLAVOURS(disney_direct, rlsh::DisneyLightIO)
+
+#if !RLS_FAST
 
 extern "C" {
 
@@ -97,46 +96,29 @@ rls_status rls_ggx_direct_lighting(rls_context *ctx, int64_t n, const rls_ggx_cl
                                    rls_cvec3 P, const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
                                    uint64_t first_index, rls_rgb direct_diffuse, rls_rgb direct_specular)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    if (n == 0) return RLS_OK;
+    RLS_LOOP_PROLOGUE(spp_n);
     RLS_REQUIRE(c != nullptr && sh != nullptr, "closure or shader is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T) && rlsh::has3(P), "wo/N/T/P plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->KsColor) && rlsh::ok_rgb(sh->KdColor), "colour planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    if (rls_status s = rlsh::check_closure(__func__, c, &P, sh)) return s;
     RLS_REQUIRE(rlsh::has3(direct_diffuse) && rlsh::has3(direct_specular), "NULL output plane");
     LightIO io = {};
     if (rls_status st = copy_lights(lights, n_lights, 1, io.lights, &io.nl)) return st;
     io.c = *c; io.sh = *sh; io.P = P; io.dd = direct_diffuse; io.ds = direct_specular;
     io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
-    int g = pick_group(ctx, n, io.spp);
-    if (ctx->fast) return rls_fast_ggx_direct(ctx, g, &io);
-    return launch_g(ctx, ggx_direct_kernel<1>, ggx_direct_kernel<4>, ggx_direct_kernel<16>,
-                    ggx_direct_kernel<64>, g, io, "rls_ggx_direct_lighting");
+    return dispatch_ggx_direct(ctx, pick_group(ctx, n, io.spp), io, "rls_ggx_direct_lighting");
 }
 
 rls_status rls_disney_direct_lighting(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
                                       const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
                                       uint64_t first_index, rls_rgb direct_diffuse, rls_rgb direct_specular)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    if (n == 0) return RLS_OK;
-    RLS_REQUIRE(c != nullptr, "closure is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T) && rlsh::has3(P), "wo/N/T/P plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->base_color), "base_color planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    RLS_LOOP_PROLOGUE(spp_n);
+    if (rls_status s = rlsh::check_closure(__func__, c, &P)) return s;
     RLS_REQUIRE(rlsh::has3(direct_diffuse) && rlsh::has3(direct_specular), "NULL output plane");
     DisneyLightIO io = {};
     if (rls_status st = copy_lights(lights, n_lights, 1, io.lights, &io.nl)) return st;
     io.c = *c; io.P = P; io.dd = direct_diffuse; io.ds = direct_specular;
     io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
-    int g = pick_group(ctx, n, io.spp);
-    if (ctx->fast) return rls_fast_disney_direct(ctx, g, &io);
-    return launch_g(ctx, disney_direct_kernel<1>, disney_direct_kernel<4>, disney_direct_kernel<16>,
-                    disney_direct_kernel<64>, g, io, "rls_disney_direct_lighting");
+    return dispatch_disney_direct(ctx, pick_group(ctx, n, io.spp), io, "rls_disney_direct_lighting");
 }
 
 } // extern "C"

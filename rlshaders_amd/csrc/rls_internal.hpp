@@ -37,8 +37,27 @@ struct rls_context {
 };
 
 // Every kernel translation unit is compiled twice: with RLS_FAST=0 it carries the C ABI and the
-// EXACT kernels, with RLS_FAST=1 only the FAST kernels behind one hidden dispatch symbol.
+// EXACT kernels, with RLS_FAST=1 only the FAST kernels behind hidden dispatch symbols.  A unit writes the kernel selection
+// of each verb family once, as
+//     rls_status launch_<verb>(rls_context *ctx, int sel, const IO &io, const char *name)
+// in its anonymous namespace (sel: what the family's kernels are chosen by -- the op, the lane group), and RLS_FLAVOURS(<verb>,
+// IO) after it emits the rest: in the FAST object the hidden rls_fast_<verb>, which launches the FAST kernels; in the EXACT
+// object its declaration and dispatch_<verb>, which launches the flavour ctx->fast selects.  name: the entry point.
 #define RLS_HIDDEN extern "C" __attribute__((visibility("hidden")))
+#if RLS_FAST
+#define RLS_FLAVOURS(verb, IO)                                                                                \
+    RLS_HIDDEN rls_status rls_fast_##verb(rls_context *ctx, int sel, const IO *io, const char *name)         \
+    {                                                                                                         \
+        return launch_##verb(ctx, sel, *io, name);                                                            \
+    }
+#else
+#define RLS_FLAVOURS(verb, IO)                                                                                \
+    RLS_HIDDEN rls_status rls_fast_##verb(rls_context *ctx, int sel, const IO *io, const char *name);        \
+    static rls_status dispatch_##verb(rls_context *ctx, int sel, const IO &io, const char *name)              \
+    {                                                                                                         \
+        return ctx->fast ? rls_fast_##verb(ctx, sel, &io, name) : launch_##verb(ctx, sel, io, name);          \
+    }
+#endif
 
 namespace rlsh {
 
@@ -228,13 +247,27 @@ rls_status hip_fail(hipError_t e, const char *what);
         if (_e != hipSuccess) return rlsh::hip_fail(_e, #expr);             \
     } while (0)
 
-#define RLS_REQUIRE(cond, msg)                                              \
+// fn: the function the message names -- the entry point, also where a shared check (check_closure below) refuses
+#define RLS_REQUIRE_IN(fn, cond, msg)                                       \
     do {                                                                    \
         if (!(cond)) {                                                      \
-            rlsh::set_error("%s: %s", __func__, msg);                       \
+            rlsh::set_error("%s: %s", fn, msg);                             \
             return RLS_ERR_INVALID_ARGUMENT;                                \
         }                                                                   \
     } while (0)
+#define RLS_REQUIRE(cond, msg) RLS_REQUIRE_IN(__func__, cond, msg)
+
+// The prologue of a batch entry point: a context, n >= 0, and nothing to do for n == 0.  A loop verb checks spp_n (spp_n^2
+// samples per point, at most kMaxSpp: rls_loops.hpp) ahead of the n == 0 return, so an empty batch with a bad spp_n is refused.
+#define RLS_PROLOGUE()                                                      \
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");                             \
+    RLS_REQUIRE(n >= 0, "n < 0");                                           \
+    if (n == 0) return RLS_OK
+#define RLS_LOOP_PROLOGUE(spp_n)                                            \
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");                             \
+    RLS_REQUIRE(n >= 0, "n < 0");                                           \
+    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]"); \
+    if (n == 0) return RLS_OK
 
 #ifndef RLS_BLOCK
 #define RLS_BLOCK 256
@@ -325,6 +358,14 @@ inline rls_status check_launch(const char *what)
     if (e != hipSuccess) return hip_fail(e, what);
     return RLS_OK;
 }
+// what: the entry point; a launch from a FAST object (fast = RLS_FAST) is reported as "<entry point>[fast]"
+static inline rls_status check_launch(const char *what, int fast)
+{
+    if (!fast) return check_launch(what);
+    char name[128];
+    snprintf(name, sizeof(name), "%s[fast]", what);
+    return check_launch(name);
+}
 
 inline bool has3(rls_cvec3 v) { return v.x && v.y && v.z; }
 inline bool has3(rls_vec3 v) { return v.x && v.y && v.z; }
@@ -333,21 +374,80 @@ inline bool none3(rls_cvec3 v) { return !v.x && !v.y && !v.z; }
 inline bool ok_rgb(const rls_param_rgb &p) { return (p.r && p.g && p.b) || (!p.r && !p.g && !p.b); }
 inline bool ok_materials(const rls_material_index &m) { return m.id == nullptr || m.count > 0; }
 
+// The checks of the four closure types, shared by every entry point that takes one; fn names the entry point.  A verb that
+// also takes the shading points P checks them with the frame ("wo/N/T/P"); a verb with a shader checks the shader's colour
+// planes with the closure's (its KtColor too with kt).  Where a verb's own message for a NULL closure names more arguments,
+// it checks those first.
+static inline rls_status check_closure(const char *fn, const rls_ggx_closure *c, const rls_cvec3 *P = nullptr,
+                                const rls_ggx_shader *sh = nullptr, bool kt = false)
+{
+    RLS_REQUIRE_IN(fn, c != nullptr, "closure is NULL");
+    if (P) RLS_REQUIRE_IN(fn, has3(c->wo) && has3(c->N) && has3(c->T) && has3(*P), "wo/N/T/P plane is NULL");
+    else RLS_REQUIRE_IN(fn, has3(c->wo) && has3(c->N) && has3(c->T), "wo/N/T plane is NULL");
+    if (sh) RLS_REQUIRE_IN(fn, ok_rgb(c->KsColor) && ok_rgb(sh->KdColor) && (!kt || ok_rgb(sh->KtColor)),
+                           "colour planes must be all set or all NULL");
+    else RLS_REQUIRE_IN(fn, ok_rgb(c->KsColor), "KsColor planes must be all set or all NULL");
+    RLS_REQUIRE_IN(fn, ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    return RLS_OK;
+}
+static inline rls_status check_closure(const char *fn, const rls_disney_closure *c, const rls_cvec3 *P = nullptr)
+{
+    RLS_REQUIRE_IN(fn, c != nullptr, "closure is NULL");
+    if (P) RLS_REQUIRE_IN(fn, has3(c->wo) && has3(c->N) && has3(c->T) && has3(*P), "wo/N/T/P plane is NULL");
+    else RLS_REQUIRE_IN(fn, has3(c->wo) && has3(c->N) && has3(c->T), "wo/N/T plane is NULL");
+    RLS_REQUIRE_IN(fn, ok_rgb(c->base_color), "base_color planes must be all set or all NULL");
+    RLS_REQUIRE_IN(fn, ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    return RLS_OK;
+}
+// need_frame: N and T are read (the profile-only verbs take none)
+static inline rls_status check_closure(const char *fn, const rls_sss_closure *c, bool need_frame)
+{
+    RLS_REQUIRE_IN(fn, c != nullptr, "closure is NULL");
+    RLS_REQUIRE_IN(fn, ok_rgb(c->sss_color), "sss_color planes must be all set or all NULL");
+    RLS_REQUIRE_IN(fn, ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    if (need_frame) RLS_REQUIRE_IN(fn, has3(c->N) && has3(c->T), "N/T plane is NULL");
+    return RLS_OK;
+}
+static inline rls_status check_closure(const char *fn, const rls_skin_closure *c, const rls_cvec3 *P = nullptr)
+{
+    RLS_REQUIRE_IN(fn, c != nullptr, "closure is NULL");
+    if (P) RLS_REQUIRE_IN(fn, has3(c->wo) && has3(c->N) && has3(c->T) && has3(*P), "wo/N/T/P plane is NULL");
+    else RLS_REQUIRE_IN(fn, has3(c->wo) && has3(c->N) && has3(c->T), "wo/N/T plane is NULL");
+    RLS_REQUIRE_IN(fn, ok_rgb(c->sss_color) && ok_rgb(c->specular_color) && ok_rgb(c->sheen_color),
+                   "colour planes must be all set or all NULL");
+    RLS_REQUIRE_IN(fn, ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    return RLS_OK;
+}
+
 // Host side of the stamps: the buffer a launch hands to a `*_kernel_stamped` instantiation, or NULL when the product kernel is
 // to run (rls_diag_clock_stamps_begin not in force).  The slots are cleared on the launch stream first, so _read returns the
 // stamps of the LAST stamped launch only, whatever grid an earlier stamped launch of the same begin/end bracket used.  A
 // bracket and a graph recording exclude each other (context.hip), so a stamped launch is never baked into a graph.
 // (Should the clear fail, the product kernel runs and _read reports no stamps: a diagnostic never costs the caller its launch.)
+// The clear goes to ctx->stream, so ctx->device is made current first: with a NULL stream it would otherwise go to the null
+// stream of whichever device the host thread last used (grid_for makes the device current again for the launch).
+// RLS_STAMPED_LAUNCH: the stamped launch of a BASELINE kernel, in place of the product launch that follows it, when
+// `baseline` (the launch is the measured configuration) holds and a bracket is in force.  Nothing without RLS_DIAGNOSTICS.
 #if RLS_DIAGNOSTICS
 inline unsigned long long *stamps_for_launch(rls_context *ctx)
 {
     if (!ctx->stamps || ctx->capturing) return nullptr;
-    if (hipMemsetAsync(ctx->stamps + 4, 0, sizeof(unsigned long long) * 4 * (size_t)ctx->stamp_slots, ctx->stream) != hipSuccess) {
+    if (hipSetDevice(ctx->device) != hipSuccess ||
+        hipMemsetAsync(ctx->stamps + 4, 0, sizeof(unsigned long long) * 4 * (size_t)ctx->stamp_slots, ctx->stream) != hipSuccess) {
         (void)hipGetLastError();
         return nullptr;
     }
     return ctx->stamps;
 }
+#define RLS_STAMPED_LAUNCH(baseline, kernel, grid, io, name)                                                  \
+    do {                                                                                                      \
+        if (unsigned long long *_stamps = (baseline) ? rlsh::stamps_for_launch(ctx) : nullptr) {            \
+            hipLaunchKernelGGL(kernel, grid, dim3(rlsh::kBlock), 0, ctx->stream, io, _stamps);               \
+            return rlsh::check_launch(name, RLS_FAST);                                                        \
+        }                                                                                                     \
+    } while (0)
+#else
+#define RLS_STAMPED_LAUNCH(baseline, kernel, grid, io, name) do {} while (0)
 #endif
 
 } // namespace rlsh

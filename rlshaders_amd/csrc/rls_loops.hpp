@@ -983,13 +983,15 @@ int pick_group(const rls_context *ctx, int64_t n, int spp)
     return g;
 }
 
+// one launch of a G-lane kernel family, named RLS_G_FAMILY(kernel): kernel<g> for g = 1, 4, 16, 64
+#define RLS_G_FAMILY(k) k<1>, k<4>, k<16>, k<64>
 template <typename K, typename IO>
 rls_status launch_g(rls_context *ctx, K k1, K k4, K k16, K k64, int g, const IO &io, const char *name)
 {
     K k = g == 1 ? k1 : g == 4 ? k4 : g == 16 ? k16 : k64;
     dim3 grid = rlsh::grid_for(ctx, io.n, rlsh::kBlock / g);
     hipLaunchKernelGGL(k, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
-    return rlsh::check_launch(name);
+    return rlsh::check_launch(name, RLS_FAST);
 }
 
 // the lights of a light loop, validated and copied into a kernel's argument struct

@@ -40,16 +40,16 @@ __global__ RLS_INT_ATTR void sss_scatter_kernel(ScatterIO a)
     }
 }
 
+rls_status launch_sss_scatter(rls_context *ctx, int g, const ScatterIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(sss_scatter_kernel), g, io, name);
+}
+
 } // namespace
 
-#if RLS_FAST
-RLS_HIDDEN rls_status rls_fast_sss_scatter(rls_context *ctx, int g, const rlsh::ScatterIO *io)
-{
-    return launch_g(ctx, sss_scatter_kernel<1>, sss_scatter_kernel<4>, sss_scatter_kernel<16>,
-                    sss_scatter_kernel<64>, g, *io, "rls_sss_integrate_scatter[fast]");
-}
-#else
-RLS_HIDDEN rls_status rls_fast_sss_scatter(rls_context *ctx, int g, const rlsh::ScatterIO *io);
+RLS_FLAVOURS(sss_scatter, rlsh::ScatterIO)
+
+#if !RLS_FAST
 
 extern "C" {
 
@@ -57,23 +57,16 @@ rls_status rls_sss_integrate_scatter(rls_context *ctx, int64_t n, const rls_sss_
                                      const rls_sss_scene *scene, int spp_n, uint32_t seed, uint64_t first_index,
                                      rls_rgb result, float *mean_depth)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    if (n == 0) return RLS_OK;
+    RLS_LOOP_PROLOGUE(spp_n);
     RLS_REQUIRE(c != nullptr && scene != nullptr, "closure or scene is NULL");
     RLS_REQUIRE(rlsh::has3(c->N) && rlsh::has3(c->T) && rlsh::has3(P), "N/T/P plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->sss_color), "sss_color planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    if (rls_status s = rlsh::check_closure(__func__, c, false)) return s;
     RLS_REQUIRE(scene->geometry == RLS_SCENE_PLANE || scene->geometry == RLS_SCENE_SPHERE, "unknown scene geometry");
     RLS_REQUIRE(rlsh::has3(result), "NULL output plane");
     ScatterIO io = {};
     io.c = *c; io.P = P; io.scene = *scene; io.result = result; io.depth = mean_depth;
     io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
-    int g = pick_group(ctx, n, io.spp);
-    if (ctx->fast) return rls_fast_sss_scatter(ctx, g, &io);
-    return launch_g(ctx, sss_scatter_kernel<1>, sss_scatter_kernel<4>, sss_scatter_kernel<16>,
-                    sss_scatter_kernel<64>, g, io, "rls_sss_integrate_scatter");
+    return dispatch_sss_scatter(ctx, pick_group(ctx, n, io.spp), io, "rls_sss_integrate_scatter");
 }
 
 } // extern "C"

@@ -283,28 +283,26 @@ __global__ RLS_DISNEY_LIGHT_ATTR void disney_shade_kernel(DisneyShadeIO a)
     }
 }
 
+rls_status launch_skin_integrate(rls_context *ctx, int g, const SkinIntIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(skin_integrate_kernel), g, io, name);
+}
+rls_status launch_ggx_shade(rls_context *ctx, int g, const GgxShadeIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(ggx_shade_kernel), g, io, name);
+}
+rls_status launch_disney_shade(rls_context *ctx, int g, const DisneyShadeIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(disney_shade_kernel), g, io, name);
+}
+
 } // namespace
 
-#if RLS_FAST
-RLS_HIDDEN rls_status rls_fast_skin_integrate(rls_context *ctx, int g, const rlsh::SkinIntIO *io)
-{
-    return launch_g(ctx, skin_integrate_kernel<1>, skin_integrate_kernel<4>, skin_integrate_kernel<16>,
-                    skin_integrate_kernel<64>, g, *io, "rls_skin_integrate[fast]");
-}
-RLS_HIDDEN rls_status rls_fast_ggx_shade(rls_context *ctx, int g, const rlsh::GgxShadeIO *io)
-{
-    return launch_g(ctx, ggx_shade_kernel<1>, ggx_shade_kernel<4>, ggx_shade_kernel<16>, ggx_shade_kernel<64>, g, *io,
-                    "rls_ggx_shade[fast]");
-}
-RLS_HIDDEN rls_status rls_fast_disney_shade(rls_context *ctx, int g, const rlsh::DisneyShadeIO *io)
-{
-    return launch_g(ctx, disney_shade_kernel<1>, disney_shade_kernel<4>, disney_shade_kernel<16>, disney_shade_kernel<64>, g,
-                    *io, "rls_disney_shade[fast]");
-}
-#else
-RLS_HIDDEN rls_status rls_fast_skin_integrate(rls_context *ctx, int g, const rlsh::SkinIntIO *io);
-RLS_HIDDEN rls_status rls_fast_ggx_shade(rls_context *ctx, int g, const rlsh::GgxShadeIO *io);
-RLS_HIDDEN rls_status rls_fast_disney_shade(rls_context *ctx, int g, const rlsh::DisneyShadeIO *io);
+RLS_FLAVOURS(skin_integrate, rlsh::SkinIntIO)
+RLS_FLAVOURS(ggx_shade, rlsh::GgxShadeIO)
+RLS_FLAVOURS(disney_shade, rlsh::DisneyShadeIO)
+
+#if !RLS_FAST
 
 extern "C" {
 
@@ -313,15 +311,9 @@ rls_status rls_skin_integrate(rls_context *ctx, int64_t n, const rls_skin_closur
                               const rls_sphere_light *lights, int n_lights,
                               int spp_n, uint32_t seed, uint64_t first_index, const rls_skin_integrate_out *out)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    if (n == 0) return RLS_OK;
+    RLS_LOOP_PROLOGUE(spp_n);
     RLS_REQUIRE(c != nullptr && scene != nullptr && out != nullptr && env != nullptr, "closure, scene, env or out is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T) && rlsh::has3(P), "wo/N/T/P plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->sss_color) && rlsh::ok_rgb(c->specular_color) && rlsh::ok_rgb(c->sheen_color),
-                "colour planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    if (rls_status s = rlsh::check_closure(__func__, c, &P)) return s;
     RLS_REQUIRE(scene->geometry == RLS_SCENE_PLANE || scene->geometry == RLS_SCENE_SPHERE, "unknown scene geometry");
     RLS_REQUIRE(rlsh::has3(out->sheen) && rlsh::has3(out->specular) && rlsh::has3(out->sss), "NULL AOV plane");
     RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
@@ -331,25 +323,16 @@ rls_status rls_skin_integrate(rls_context *ctx, int64_t n, const rls_skin_closur
     io.sheen = out->sheen; io.specular = out->specular; io.sss = out->sss; io.out = out->out;
     io.sheenFresnel = out->sheenFresnel; io.specularFresnel = out->specularFresnel; io.sssWeight = out->sssWeight;
     io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
-    int g = pick_group(ctx, n, io.spp);
-    if (ctx->fast) return rls_fast_skin_integrate(ctx, g, &io);
-    return launch_g(ctx, skin_integrate_kernel<1>, skin_integrate_kernel<4>, skin_integrate_kernel<16>,
-                    skin_integrate_kernel<64>, g, io, "rls_skin_integrate");
+    return dispatch_skin_integrate(ctx, pick_group(ctx, n, io.spp), io, "rls_skin_integrate");
 }
 
 rls_status rls_ggx_shade(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh, rls_cvec3 P,
                          const rls_sphere_light *lights, int n_lights, const float env[3], int traced, int spp_n,
                          uint32_t seed, uint64_t first_index, const rls_ggx_shade_out *out)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    if (n == 0) return RLS_OK;
+    RLS_LOOP_PROLOGUE(spp_n);
     RLS_REQUIRE(c != nullptr && sh != nullptr && env != nullptr && out != nullptr, "closure, shader, env or out is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T) && rlsh::has3(P), "wo/N/T/P plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->KsColor) && rlsh::ok_rgb(sh->KdColor) && rlsh::ok_rgb(sh->KtColor),
-                "colour planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    if (rls_status s = rlsh::check_closure(__func__, c, &P, sh, true)) return s;
     RLS_REQUIRE(rlsh::has3(out->direct_diffuse) && rlsh::has3(out->direct_specular) && rlsh::has3(out->refraction) &&
                 rlsh::has3(out->indirect_diffuse) && rlsh::has3(out->indirect_specular), "NULL AOV plane");
     RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
@@ -359,24 +342,16 @@ rls_status rls_ggx_shade(rls_context *ctx, int64_t n, const rls_ggx_closure *c, 
     io.dd = out->direct_diffuse; io.ds = out->direct_specular; io.refr = out->refraction; io.id = out->indirect_diffuse;
     io.is = out->indirect_specular; io.out = out->out;
     io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
-    int g = pick_group(ctx, n, io.spp);
-    if (ctx->fast) return rls_fast_ggx_shade(ctx, g, &io);
-    return launch_g(ctx, ggx_shade_kernel<1>, ggx_shade_kernel<4>, ggx_shade_kernel<16>, ggx_shade_kernel<64>, g, io,
-                    "rls_ggx_shade");
+    return dispatch_ggx_shade(ctx, pick_group(ctx, n, io.spp), io, "rls_ggx_shade");
 }
 
 rls_status rls_disney_shade(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
                             const rls_sphere_light *lights, int n_lights, const float env[3], int spp_n, uint32_t seed,
                             uint64_t first_index, const rls_disney_shade_out *out)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    if (n == 0) return RLS_OK;
+    RLS_LOOP_PROLOGUE(spp_n);
     RLS_REQUIRE(c != nullptr && env != nullptr && out != nullptr, "closure, env or out is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T) && rlsh::has3(P), "wo/N/T/P plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->base_color), "base_color planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    if (rls_status s = rlsh::check_closure(__func__, c, &P)) return s;
     RLS_REQUIRE(rlsh::has3(out->direct_diffuse) && rlsh::has3(out->direct_specular) && rlsh::has3(out->indirect_diffuse) &&
                 rlsh::has3(out->indirect_specular), "NULL AOV plane");
     RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
@@ -386,10 +361,7 @@ rls_status rls_disney_shade(rls_context *ctx, int64_t n, const rls_disney_closur
     io.dd = out->direct_diffuse; io.ds = out->direct_specular; io.id = out->indirect_diffuse; io.is = out->indirect_specular;
     io.out = out->out;
     io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
-    int g = pick_group(ctx, n, io.spp);
-    if (ctx->fast) return rls_fast_disney_shade(ctx, g, &io);
-    return launch_g(ctx, disney_shade_kernel<1>, disney_shade_kernel<4>, disney_shade_kernel<16>, disney_shade_kernel<64>, g,
-                    io, "rls_disney_shade");
+    return dispatch_disney_shade(ctx, pick_group(ctx, n, io.spp), io, "rls_disney_shade");
 }
 
 } // extern "C"

@@ -190,7 +190,7 @@ __global__ RLS_SKIN_ATTR void skin_kernel_stamped(SkinIO a0, unsigned long long 
 }
 #endif
 
-rls_status launch_kernel(rls_context *ctx, const SkinIO &io, const char *name)
+rls_status launch_skin(rls_context *ctx, int, const SkinIO &io, const char *name)
 {
     const rls_skin_closure &c = io.c;
     const bool by_reference = c.materials.id != nullptr;
@@ -203,45 +203,30 @@ rls_status launch_kernel(rls_context *ctx, const SkinIO &io, const char *name)
                          !c.specular_weight.v && !c.specular_roughness.v && !c.specular_ior.v && !c.sheen_color.r &&
                          !c.sheen_weight.v && !c.sheen_roughness.v && !c.sheen_ior.v;
     const dim3 grid = rlsh::grid_for(ctx, io.n, rlsh::kBlock, RLS_CAP_MULT);
-#if RLS_DIAGNOSTICS
-    if (unsigned long long *stamps = streamed ? rlsh::stamps_for_launch(ctx) : nullptr) {
-        // BASELINE config 5 under rls_diag_clock_stamps_begin: the stamped instantiation
-        hipLaunchKernelGGL((skin_kernel_stamped<RLS_FAST, STREAMED_ALL>), grid, dim3(rlsh::kBlock), 0, ctx->stream, io, stamps);
-        return rlsh::check_launch(name);
-    }
-#endif
+    RLS_STAMPED_LAUNCH(streamed, (skin_kernel_stamped<RLS_FAST, STREAMED_ALL>), grid, io, name);   // BASELINE config 5
     if (streamed)
         hipLaunchKernelGGL((skin_kernel<RLS_FAST, STREAMED_ALL>), grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
     else if (uniform)   // a thread that hoists wants many tiles to spread the hoisted work over (grid_for_hoisting)
         hipLaunchKernelGGL((skin_kernel<RLS_FAST, UNIFORM_ALL>), rlsh::grid_for_hoisting(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
     else
         hipLaunchKernelGGL((skin_kernel<RLS_FAST, MIXED>), grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
-    return rlsh::check_launch(name);
+    return rlsh::check_launch(name, RLS_FAST);
 }
 
 } // namespace
 
-#if RLS_FAST
-RLS_HIDDEN rls_status rls_fast_skin(rls_context *ctx, const rlsh::SkinIO *io)
-{
-    return launch_kernel(ctx, *io, "rls_skin_sample_eval_pdf[fast]");
-}
-#else
-RLS_HIDDEN rls_status rls_fast_skin(rls_context *ctx, const rlsh::SkinIO *io);
+RLS_FLAVOURS(skin, rlsh::SkinIO)
+
+#if !RLS_FAST
 
 extern "C" {
 
 rls_status rls_skin_sample_eval_pdf(rls_context *ctx, int64_t n, const rls_skin_closure *c,
                                     const float *const xi[6], const rls_skin_out *out)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    if (n == 0) return RLS_OK;
+    RLS_PROLOGUE();
     RLS_REQUIRE(c != nullptr && xi != nullptr && out != nullptr, "NULL argument");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T), "wo/N/T plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->sss_color) && rlsh::ok_rgb(c->specular_color) && rlsh::ok_rgb(c->sheen_color),
-                "colour planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     for (int k = 0; k < 6; k++) RLS_REQUIRE(xi[k] != nullptr, "xi plane is NULL");
     RLS_REQUIRE(rlsh::has3(out->sheen_wi) && rlsh::has3(out->sheen_f) && out->sheen_pdf && out->sheen_fresnel &&
                 rlsh::has3(out->spec_wi) && rlsh::has3(out->spec_f) && out->spec_pdf && out->spec_fresnel &&
@@ -252,7 +237,7 @@ rls_status rls_skin_sample_eval_pdf(rls_context *ctx, int64_t n, const rls_skin_
     for (int k = 0; k < 6; k++) io.xi[k] = xi[k];
     io.o = *out;
     io.n = n;
-    return ctx->fast ? rls_fast_skin(ctx, &io) : launch_kernel(ctx, io, "rls_skin_sample_eval_pdf");
+    return dispatch_skin(ctx, 0, io, "rls_skin_sample_eval_pdf");
 }
 
 } // extern "C"

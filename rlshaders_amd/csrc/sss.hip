@@ -159,15 +159,6 @@ __global__ __launch_bounds__(rlsh::kBlock) void misc_kernel(MiscIO a)
     }
 }
 
-rls_status check_closure(const rls_sss_closure *c, bool need_frame)
-{
-    RLS_REQUIRE(c != nullptr, "closure is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->sss_color), "sss_color planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
-    if (need_frame) RLS_REQUIRE(rlsh::has3(c->N) && rlsh::has3(c->T), "N/T plane is NULL");
-    return RLS_OK;
-}
-
 template <int OP>
 rls_status launch_kernel(rls_context *ctx, const SssIO &io, const char *name)
 {
@@ -176,103 +167,94 @@ rls_status launch_kernel(rls_context *ctx, const SssIO &io, const char *name)
                          !c.sss_scatter_dist[2].v;
     // evalProfile alone uses nothing setDistance computes but maxR: no uniform specialisation of it
     constexpr bool kHoists = OP != OP_ND_EVAL;
-#if RLS_DIAGNOSTICS
-    if constexpr (OP == OP_PROBE) {      // BASELINE config 4 under rls_diag_clock_stamps_begin: the stamped instantiation
-        if (unsigned long long *stamps = (!c.materials.id && !(uniform && kHoists)) ? rlsh::stamps_for_launch(ctx) : nullptr) {
-            hipLaunchKernelGGL((sss_kernel_stamped<OP, PER_POINT>), rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io, stamps);
-            return rlsh::check_launch(name);
-        }
-    }
-#endif
+    if constexpr (OP == OP_PROBE)        // BASELINE config 4 under rls_diag_clock_stamps_begin
+        RLS_STAMPED_LAUNCH(!c.materials.id && !(uniform && kHoists), (sss_kernel_stamped<OP, PER_POINT>), rlsh::grid_for(ctx, io.n),
+                           io, name);
     if (c.materials.id)
         hipLaunchKernelGGL((sss_kernel<OP, BY_REFERENCE>), rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
     else if (uniform && kHoists)
         hipLaunchKernelGGL((sss_kernel<OP, kHoists ? UNIFORM_DISTANCE : PER_POINT>), rlsh::grid_for_hoisting(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
     else
         hipLaunchKernelGGL((sss_kernel<OP, PER_POINT>), rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
-    return rlsh::check_launch(name);
+    return rlsh::check_launch(name, RLS_FAST);
 }
 
 template <int OP>
 rls_status launch_misc_kernel(rls_context *ctx, const MiscIO &io, const char *name)
 {
     hipLaunchKernelGGL(misc_kernel<OP>, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
-    return rlsh::check_launch(name);
+    return rlsh::check_launch(name, RLS_FAST);
+}
+
+rls_status launch_sss(rls_context *ctx, int op, const SssIO &io, const char *name)
+{
+    switch (op) {
+    case OP_ND: return launch_kernel<OP_ND>(ctx, io, name);
+    case OP_ND_PDF: return launch_kernel<OP_ND_PDF>(ctx, io, name);
+    case OP_ND_EVAL: return launch_kernel<OP_ND_EVAL>(ctx, io, name);
+    case OP_PROBE: return launch_kernel<OP_PROBE>(ctx, io, name);
+    default: return launch_kernel<OP_MIS>(ctx, io, name);
+    }
 }
 
 } // namespace
 
+RLS_FLAVOURS(sss, rlsh::SssIO)
+
+// The misc kernels keep a switch of their own in the FAST object and a template per op in the EXACT one: the code objects
+// hold the kernels in the order of their first use, and the two objects use these four in different orders.
 #if RLS_FAST
-RLS_HIDDEN rls_status rls_fast_sss(rls_context *ctx, int op, const rlsh::SssIO *io)
+RLS_HIDDEN rls_status rls_fast_misc(rls_context *ctx, int op, const rlsh::MiscIO *io, const char *name)
 {
     switch (op) {
-    case OP_ND: return launch_kernel<OP_ND>(ctx, *io, "rls_nd_sample[fast]");
-    case OP_ND_PDF: return launch_kernel<OP_ND_PDF>(ctx, *io, "rls_nd_pdf[fast]");
-    case OP_ND_EVAL: return launch_kernel<OP_ND_EVAL>(ctx, *io, "rls_nd_eval[fast]");
-    case OP_PROBE: return launch_kernel<OP_PROBE>(ctx, *io, "rls_sss_probe_ray[fast]");
-    default: return launch_kernel<OP_MIS>(ctx, *io, "rls_sss_mis_pdf[fast]");
-    }
-}
-RLS_HIDDEN rls_status rls_fast_misc(rls_context *ctx, int op, const rlsh::MiscIO *io)
-{
-    switch (op) {
-    case OP_CAVITY: return launch_misc_kernel<OP_CAVITY>(ctx, *io, "rls_sss_cavity_fade[fast]");
-    case OP_DIFFUSE_DIR: return launch_misc_kernel<OP_DIFFUSE_DIR>(ctx, *io, "rls_sss_sample_diffuse_direction[fast]");
-    case OP_REFLECT_LUM: return launch_misc_kernel<OP_REFLECT_LUM>(ctx, *io, "rls_util_reflect_luminance[fast]");
-    default: return launch_misc_kernel<OP_UTIL>(ctx, *io, "rls_util_directions[fast]");
+    case OP_CAVITY: return launch_misc_kernel<OP_CAVITY>(ctx, *io, name);
+    case OP_DIFFUSE_DIR: return launch_misc_kernel<OP_DIFFUSE_DIR>(ctx, *io, name);
+    case OP_REFLECT_LUM: return launch_misc_kernel<OP_REFLECT_LUM>(ctx, *io, name);
+    default: return launch_misc_kernel<OP_UTIL>(ctx, *io, name);
     }
 }
 #else
-RLS_HIDDEN rls_status rls_fast_sss(rls_context *ctx, int op, const rlsh::SssIO *io);
-RLS_HIDDEN rls_status rls_fast_misc(rls_context *ctx, int op, const rlsh::MiscIO *io);
+RLS_HIDDEN rls_status rls_fast_misc(rls_context *ctx, int op, const rlsh::MiscIO *io, const char *name);
 
 namespace {
 template <int OP>
-rls_status launch(rls_context *ctx, const SssIO &io, const char *name)
+rls_status dispatch_misc(rls_context *ctx, const MiscIO &io, const char *name)
 {
-    return ctx->fast ? rls_fast_sss(ctx, OP, &io) : launch_kernel<OP>(ctx, io, name);
-}
-template <int OP>
-rls_status launch_misc(rls_context *ctx, const MiscIO &io, const char *name)
-{
-    return ctx->fast ? rls_fast_misc(ctx, OP, &io) : launch_misc_kernel<OP>(ctx, io, name);
+    return ctx->fast ? rls_fast_misc(ctx, OP, &io, name) : launch_misc_kernel<OP>(ctx, io, name);
 }
 } // namespace
-
-#define RLS_PROLOGUE(frame)                              \
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");          \
-    RLS_REQUIRE(n >= 0, "n < 0");                        \
-    if (n == 0) return RLS_OK;                           \
-    { rls_status _s = check_closure(c, frame); if (_s != RLS_OK) return _s; }
 
 extern "C" {
 
 rls_status rls_nd_sample(rls_context *ctx, int64_t n, const rls_sss_closure *c, const float *rx,
                          float *r, float *pdf, rls_rgb profile)
 {
-    RLS_PROLOGUE(false);
+    RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c, false)) return s;
     RLS_REQUIRE(rx && r && pdf && rlsh::has3(profile), "NULL plane");
     SssIO io = {};
     io.c = *c; io.rx = rx; io.r = r; io.pdf = pdf; io.profile = profile; io.n = n;
-    return launch<OP_ND>(ctx, io, "rls_nd_sample");
+    return dispatch_sss(ctx, OP_ND, io, "rls_nd_sample");
 }
 
 rls_status rls_nd_pdf(rls_context *ctx, int64_t n, const rls_sss_closure *c, const float *r, float *pdf)
 {
-    RLS_PROLOGUE(false);
+    RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c, false)) return s;
     RLS_REQUIRE(r && pdf, "NULL plane");
     SssIO io = {};
     io.c = *c; io.rin = r; io.pdf = pdf; io.n = n;
-    return launch<OP_ND_PDF>(ctx, io, "rls_nd_pdf");
+    return dispatch_sss(ctx, OP_ND_PDF, io, "rls_nd_pdf");
 }
 
 rls_status rls_nd_eval(rls_context *ctx, int64_t n, const rls_sss_closure *c, const float *r, rls_rgb profile)
 {
-    RLS_PROLOGUE(false);
+    RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c, false)) return s;
     RLS_REQUIRE(r && rlsh::has3(profile), "NULL plane");
     SssIO io = {};
     io.c = *c; io.rin = r; io.profile = profile; io.n = n;
-    return launch<OP_ND_EVAL>(ctx, io, "rls_nd_eval");
+    return dispatch_sss(ctx, OP_ND_EVAL, io, "rls_nd_eval");
 }
 
 rls_status rls_sss_probe_ray(rls_context *ctx, int64_t n, const rls_sss_closure *c,
@@ -280,72 +262,66 @@ rls_status rls_sss_probe_ray(rls_context *ctx, int64_t n, const rls_sss_closure 
                              float *r, rls_vec3 origin, rls_vec3 dir, float *maxdist,
                              float *pdf, rls_rgb profile)
 {
-    RLS_PROLOGUE(true);
+    RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c, true)) return s;
     RLS_REQUIRE(rx && ry, "rx/ry is NULL");
     RLS_REQUIRE(rlsh::has3(P) || rlsh::none3(P), "P planes must be all set or all NULL");
     RLS_REQUIRE(r && rlsh::has3(origin) && rlsh::has3(dir) && maxdist && pdf && rlsh::has3(profile), "NULL output plane");
     SssIO io = {};
     io.c = *c; io.rx = rx; io.ry = ry; io.P = P; io.r = r; io.origin = origin; io.dir = dir;
     io.maxdist = maxdist; io.pdf = pdf; io.profile = profile; io.n = n;
-    return launch<OP_PROBE>(ctx, io, "rls_sss_probe_ray");
+    return dispatch_sss(ctx, OP_PROBE, io, "rls_sss_probe_ray");
 }
 
 rls_status rls_sss_mis_pdf(rls_context *ctx, int64_t n, const rls_sss_closure *c,
                            rls_cvec3 disp, rls_cvec3 sampleN, int literal_matrix, float *pdf)
 {
-    RLS_PROLOGUE(true);
+    RLS_PROLOGUE();
+    if (rls_status s = rlsh::check_closure(__func__, c, true)) return s;
     RLS_REQUIRE(rlsh::has3(disp) && rlsh::has3(sampleN) && pdf, "NULL plane");
     SssIO io = {};
     io.c = *c; io.disp = disp; io.sampleN = sampleN; io.literal = literal_matrix; io.pdf = pdf; io.n = n;
-    return launch<OP_MIS>(ctx, io, "rls_sss_mis_pdf");
+    return dispatch_sss(ctx, OP_MIS, io, "rls_sss_mis_pdf");
 }
 
 rls_status rls_sss_cavity_fade(rls_context *ctx, int64_t n, rls_cvec3 disp, rls_cvec3 sampleN,
                                rls_cvec3 No, float *fade)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    if (n == 0) return RLS_OK;
+    RLS_PROLOGUE();
     RLS_REQUIRE(rlsh::has3(disp) && rlsh::has3(sampleN) && rlsh::has3(No) && fade, "NULL plane");
     MiscIO io = {};
     io.a = disp; io.b = sampleN; io.c = No; io.out = fade; io.n = n;
-    return launch_misc<OP_CAVITY>(ctx, io, "rls_sss_cavity_fade");
+    return dispatch_misc<OP_CAVITY>(ctx, io, "rls_sss_cavity_fade");
 }
 
 rls_status rls_sss_sample_diffuse_direction(rls_context *ctx, int64_t n, rls_cvec3 normal, rls_cvec3 T,
                                             const float *rx, const float *ry, rls_vec3 wi)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    if (n == 0) return RLS_OK;
+    RLS_PROLOGUE();
     RLS_REQUIRE(rlsh::has3(normal) && rlsh::has3(T) && rx && ry && rlsh::has3(wi), "NULL plane");
     MiscIO io = {};
     io.a = normal; io.b = T; io.rx = rx; io.ry = ry; io.v0 = wi; io.n = n;
-    return launch_misc<OP_DIFFUSE_DIR>(ctx, io, "rls_sss_sample_diffuse_direction");
+    return dispatch_misc<OP_DIFFUSE_DIR>(ctx, io, "rls_sss_sample_diffuse_direction");
 }
 
 rls_status rls_util_directions(rls_context *ctx, int64_t n, const float *a, const float *b,
                                rls_vec3 spherical, rls_vec3 disk)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    if (n == 0) return RLS_OK;
+    RLS_PROLOGUE();
     RLS_REQUIRE(a && b && rlsh::has3(spherical) && rlsh::has3(disk), "NULL plane");
     MiscIO io = {};
     io.rx = a; io.ry = b; io.v0 = spherical; io.v1 = disk; io.n = n;
-    return launch_misc<OP_UTIL>(ctx, io, "rls_util_directions");
+    return dispatch_misc<OP_UTIL>(ctx, io, "rls_util_directions");
 }
 
 rls_status rls_util_reflect_luminance(rls_context *ctx, int64_t n, rls_cvec3 i, rls_cvec3 nrm, rls_cvec3 color,
                                       rls_vec3 reflected, float *luminance)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    if (n == 0) return RLS_OK;
+    RLS_PROLOGUE();
     RLS_REQUIRE(rlsh::has3(i) && rlsh::has3(nrm) && rlsh::has3(color) && rlsh::has3(reflected) && luminance, "NULL plane");
     MiscIO io = {};
     io.a = i; io.b = nrm; io.c = color; io.v0 = reflected; io.out = luminance; io.n = n;
-    return launch_misc<OP_REFLECT_LUM>(ctx, io, "rls_util_reflect_luminance");
+    return dispatch_misc<OP_REFLECT_LUM>(ctx, io, "rls_util_reflect_luminance");
 }
 
 } // extern "C"

@@ -317,13 +317,11 @@ __global__ __launch_bounds__(rlsh::kBlock) void trace_resolve_kernel(TraceResolv
 #if RLS_FAST
 RLS_HIDDEN rls_status rls_trace_fast_glossy_emit(rls_context *ctx, int g, const TraceEmitIO *io)
 {
-    return launch_g(ctx, ggx_glossy_emit_kernel<1>, ggx_glossy_emit_kernel<4>, ggx_glossy_emit_kernel<16>,
-                    ggx_glossy_emit_kernel<64>, g, *io, "rls_trace_ggx_glossy_emit[fast]");
+    return launch_g(ctx, RLS_G_FAMILY(ggx_glossy_emit_kernel), g, *io, "rls_trace_ggx_glossy_emit");
 }
 RLS_HIDDEN rls_status rls_trace_fast_refract_emit(rls_context *ctx, int g, const TraceEmitIO *io)
 {
-    return launch_g(ctx, ggx_refract_emit_kernel<1>, ggx_refract_emit_kernel<4>, ggx_refract_emit_kernel<16>,
-                    ggx_refract_emit_kernel<64>, g, *io, "rls_trace_ggx_refract_emit[fast]");
+    return launch_g(ctx, RLS_G_FAMILY(ggx_refract_emit_kernel), g, *io, "rls_trace_ggx_refract_emit");
 }
 #else
 RLS_HIDDEN rls_status rls_trace_fast_glossy_emit(rls_context *ctx, int g, const TraceEmitIO *io);
@@ -370,10 +368,7 @@ rls_status emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n
                            q->offsets);
         return rlsh::check_launch(refract ? "rls_trace_ggx_refract_emit" : "rls_trace_ggx_glossy_emit");
     }
-    RLS_REQUIRE(c != nullptr, "closure is NULL");
-    RLS_REQUIRE(rlsh::has3(c->wo) && rlsh::has3(c->N) && rlsh::has3(c->T), "wo/N/T plane is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->KsColor), "KsColor planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(q->dir), "queue.dir plane is NULL");
     RLS_REQUIRE(refract ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
     RLS_REQUIRE(q->capacity >= n * spp, "queue.capacity < n * spp_n^2");
@@ -389,12 +384,10 @@ rls_status emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n
     rls_status s;
     if (refract)
         s = ctx->fast ? rls_trace_fast_refract_emit(ctx, g, &io)
-                      : launch_g(ctx, ggx_refract_emit_kernel<1>, ggx_refract_emit_kernel<4>, ggx_refract_emit_kernel<16>,
-                                 ggx_refract_emit_kernel<64>, g, io, "rls_trace_ggx_refract_emit");
+                      : launch_g(ctx, RLS_G_FAMILY(ggx_refract_emit_kernel), g, io, "rls_trace_ggx_refract_emit");
     else
         s = ctx->fast ? rls_trace_fast_glossy_emit(ctx, g, &io)
-                      : launch_g(ctx, ggx_glossy_emit_kernel<1>, ggx_glossy_emit_kernel<4>, ggx_glossy_emit_kernel<16>,
-                                 ggx_glossy_emit_kernel<64>, g, io, "rls_trace_ggx_glossy_emit");
+                      : launch_g(ctx, RLS_G_FAMILY(ggx_glossy_emit_kernel), g, io, "rls_trace_ggx_glossy_emit");
     if (s != RLS_OK) return s;
 
     // offsets: the counts scanned in place
@@ -420,10 +413,7 @@ rls_status emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n
 
 rls_status resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, int spp_n, rls_crgb radiance, rls_rgb out, bool refract)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(!refract || (spp_n >= 1 && spp_n * spp_n <= kMaxSpp), "spp_n must be in [1, 16]");
-    if (n == 0) return RLS_OK;
+    RLS_LOOP_PROLOGUE(spp_n);                            // (the glossy resolve passes spp_n = 1)
     RLS_REQUIRE(q != nullptr && q->offsets != nullptr, "queue or queue.offsets is NULL");
     RLS_REQUIRE(refract ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
     RLS_REQUIRE(radiance.r && radiance.g && radiance.b, "radiance plane is NULL");
