@@ -1,26 +1,29 @@
 /*
- * rlshaders_amd_trace.h -- caller-traced rlGgx integrators (companion library librls_trace.so).
+ * rlshaders_amd_trace.h -- caller-traced rlGgx and rlDisney integrators (companion library librls_trace.so).
  *
  * The reference traces inside its integrators: integrateGlossy hands the callback triple to AiBRDFIntegrate, which
- * traces one glossy ray per sample (src/rlGgx.h:172-179), and integrateRefract calls AiTrace per sample
- * (src/rlGgx.h:228-244).  rls_ggx_integrate / rls_ggx_integrate_refract stand in for those rays with a uniform
- * environment.  The calls below cut each integrator at the point where the reference traces, so that a renderer can
- * trace with its own tracer:
+ * traces one glossy ray per sample (src/rlGgx.h:172-179), integrateRefract calls AiTrace per sample
+ * (src/rlGgx.h:228-244), and rlDisney's integrateDiffuse / integrateGlossy hand theirs to AiBRDFIntegrate with
+ * AI_RAY_DIFFUSE / AI_RAY_GLOSSY (src/rlDisney.cpp:240-243, 279-283).  rls_ggx_integrate / rls_ggx_integrate_refract /
+ * rls_disney_integrate stand in for those rays with a uniform environment.  The calls below cut each integrator at the
+ * point where the reference traces, so that a renderer can trace with its own tracer:
  *
  *   1. emit:    every sample ray of the n^2-spp loop goes into a compacted, deterministic queue
  *               (direction, weight, point, sample[, kind]);
  *   2. (the renderer traces the queue and writes one radiance per ray);
  *   3. resolve: radiance x weight is reduced per point, in the reference's sample order.
  *
- * The samples are exactly those rls_ggx_integrate / rls_ggx_integrate_refract draw (same seed, first_index, scrambled
- * (0,2)-sequence, math mode of the context).  With a radiance of 1 on every ray the resolves return, bit for bit,
- * rls_ggx_integrate's sum_f_over_pdf and rls_ggx_integrate_refract(traced = 1, env = {1, 1, 1})'s result.
+ * The samples are exactly those rls_ggx_integrate / rls_ggx_integrate_refract / rls_disney_integrate draw (same seed,
+ * first_index, scrambled (0,2)-sequence, math mode of the context).  With a radiance of 1 on every ray the resolves
+ * return, bit for bit, rls_ggx_integrate's sum_f_over_pdf, rls_ggx_integrate_refract(traced = 1, env = {1, 1, 1})'s
+ * result and rls_disney_integrate's diffuse_sum / specular_sum.
  *
  * Queue layout: point-major, samples ascending within a point, CSR: point i's rays are [offsets[i], offsets[i+1]),
  * offsets[n] is the ray count.  The order depends on the inputs only.  offsets stays on the device (read offsets[n] with
  * rls_copy_to_host); no call here synchronises the host, so emit and resolve can be recorded into an rls_graph.
- * A sample whose weight is zero (all three channels for glossy) is not queued: it would contribute exactly +0.  The
- * resolves therefore never multiply a radiance by a zero weight -- a non-finite radiance cannot come from a dropped ray.
+ * A sample whose weight is zero (all three channels for glossy and rlDisney) is not queued: it would contribute exactly
+ * +0.  The resolves therefore never multiply a radiance by a zero weight -- a non-finite radiance cannot come from a
+ * dropped ray.
  *
  * All pointers are device pointers owned by the caller; the library allocates nothing per call.  Link
  * librls_trace.so (it needs librlshaders_amd.so, which holds the context and error calls).
@@ -44,7 +47,7 @@ typedef struct rls_ray_queue {
     int64_t capacity;      /* rays every per-ray plane holds; must be >= n * spp_n^2 */
     int64_t *offsets;      /* [n + 1], required */
     rls_vec3 dir;          /* [capacity] x 3, required: the sample direction (unit, world space) */
-    rls_rgb weight;        /* glossy: f / pdf per channel (3 planes); refraction: getSampleWeight in weight.r only */
+    rls_rgb weight;        /* glossy, rlDisney: f / pdf (3 planes); refraction: getSampleWeight in weight.r only */
     uint32_t *point;       /* [capacity], NULL-able: the point's index in this call (0 .. n-1) */
     uint8_t *sample;       /* [capacity], NULL-able: the sample's index s in [0, spp_n^2) */
     uint8_t *kind;         /* [capacity], NULL-able, refraction only: RLS_RAY_TRANSMITTED / RLS_RAY_TIR_MIRROR */
@@ -52,7 +55,7 @@ typedef struct rls_ray_queue {
     size_t scratch_bytes;
 } rls_ray_queue;
 
-/* Device scratch an emit of n points at spp_n^2 samples needs (either integrator). */
+/* Device scratch an emit of n points at spp_n^2 samples needs (any emit). */
 rls_status rls_trace_scratch_bytes(int64_t n, int spp_n, size_t *bytes);
 
 /* integrateGlossy up to AiBRDFIntegrate's trace (src/rlGgx.h:172-179): per point and sample the microfacet normal,
@@ -69,9 +72,19 @@ rls_status rls_trace_ggx_glossy_emit(rls_context *ctx, int64_t n, const rls_ggx_
 rls_status rls_trace_ggx_refract_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed,
                                       uint64_t first_index, const rls_ray_queue *q, float *tir_fraction);
 
-/* AiBRDFIntegrate's sum with the traced radiance (src/rlGgx.h:172-179): sum[i] = sum over point i's rays, in queue
- * order, of radiance[k] * weight[k] per channel -- un-normalised, the convention of rls_ggx_integrate's
- * sum_f_over_pdf.  radiance: 3 planes of offsets[n] values, indexed by ray. */
+/* integrateDiffuse / integrateGlossy of rlDisney up to AiBRDFIntegrate's trace (src/rlDisney.cpp:240-243, 279-283), one
+ * lobe per call: lobe = RLS_RAY_DIFFUSE (the cosine lobe) or RLS_RAY_GLOSSY (the specular lobe), as rls_disney_sample
+ * takes it.  Per point and sample the direction and f / pdf of the samples rls_disney_integrate draws for that lobe.  A
+ * ray is queued if the sample is valid (pdf > 1e-4, src/rlDisney.cpp:309) and f / pdf is not 0 in all three channels;
+ * kind is not written.  valid_count (NULL-able): the valid samples per point, rls_disney_integrate's diffuse_count /
+ * specular_count.  Resolve with rls_trace_ggx_glossy_resolve. */
+rls_status rls_trace_disney_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, int lobe, int spp_n,
+                                 uint32_t seed, uint64_t first_index, const rls_ray_queue *q, float *valid_count);
+
+/* AiBRDFIntegrate's sum with the traced radiance (src/rlGgx.h:172-179, src/rlDisney.cpp:240-243, 279-283): sum[i] = sum
+ * over point i's rays, in queue order, of radiance[k] * weight[k] per channel -- un-normalised, the convention of
+ * rls_ggx_integrate's sum_f_over_pdf and rls_disney_integrate's diffuse_sum / specular_sum.  Resolves rlGgx glossy
+ * queues and rlDisney queues of either lobe.  radiance: 3 planes of offsets[n] values, indexed by ray. */
 rls_status rls_trace_ggx_glossy_resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, rls_crgb radiance,
                                         rls_rgb sum);
 

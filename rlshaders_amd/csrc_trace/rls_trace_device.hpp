@@ -23,6 +23,20 @@ struct TraceEmitIO {
     uint64_t first;
 };
 
+// the rlDisney emit (one lobe per launch): the same staging and counts, f / pdf in three weight planes
+struct DisneyEmitIO {
+    rls_disney_closure c;
+    float *dir[3];
+    float *w[3];
+    uint16_t *tag;
+    int64_t *count;          // = the queue's offsets
+    float *valid;            // valid_count (the lobe's diffuse_count / specular_count), NULL-able
+    int64_t n;
+    int spp;
+    uint32_t seed;
+    uint64_t first;
+};
+
 struct TraceCompactIO {
     const float *sdir[3];
     const float *sw[3];

@@ -1,21 +1,24 @@
-// trace.hip -- caller-traced rlGgx integrators (include/rlshaders_amd_trace.h): integrateGlossy and integrateRefract's
-// traced branch (src/rlGgx.h:172-184, 228-244) cut where the reference traces, into an emit of every sample ray and a
-// resolve of the radiance the caller traced for them.
+// trace.hip -- caller-traced rlGgx and rlDisney integrators (include/rlshaders_amd_trace.h): integrateGlossy and
+// integrateRefract's traced branch (src/rlGgx.h:172-184, 228-244), rlDisney's integrateDiffuse / integrateGlossy
+// (src/rlDisney.cpp:240-243, 279-283) cut where the reference traces, into an emit of every sample ray and a resolve of
+// the radiance the caller traced for them.
 //
 // Emit, three steps on the context's stream:
-//   1. ggx_{glossy,refract}_emit_kernel: the sample loop of rls_ggx_integrate / rls_ggx_integrate_refract (one G-lane
-//      group per point, the same packed VNDF sampling), each sample computed ONCE: its record goes to a fixed staging slot
-//      s * n + i (sample-major: the lanes of a wavefront store to consecutive words) with a tag (its rank among the
-//      point's kept samples, or "dropped"), the point's kept count to offsets[i].  A count pass and a write pass would run
-//      the sample arithmetic twice.
+//   1. ggx_{glossy,refract}_emit_kernel, disney_{diffuse,specular}_emit_kernel: the sample loop of rls_ggx_integrate /
+//      rls_ggx_integrate_refract / one lobe of rls_disney_integrate (one G-lane group per point, the same packed
+//      sampling), each sample computed ONCE: its record goes to a fixed staging slot s * n + i (sample-major: the lanes of
+//      a wavefront store to consecutive words) with a tag (its rank among the point's kept samples, or "dropped"), the
+//      point's kept count to offsets[i].  A count pass and a write pass would run the sample arithmetic twice.
 //   2. trace_scan_{block,totals,add}_kernel: offsets[0, n) scanned in place (exclusive), offsets[n] = the ray count.  A
 //      multi-kernel scan (tiles, then the tile sums in one workgroup, then the add-back): no workgroup waits on another.
 //   3. trace_compact_kernel: per tile of points, the kept records move from their staging slots to offsets[i] + rank,
 //      transposed through LDS (staging rows in, the tile's contiguous queue range out).
-// Every position is a function of the inputs: no atomics anywhere.
+// Steps 2 and 3 are the same for every closure (emit() below).  Every position is a function of the inputs: no atomics
+// anywhere.
 //
 // Resolve (trace_resolve_kernel): per point the sequential sum over its rays in queue order; the products
-// radiance x weight of a tile of rays are formed with coalesced loads into LDS, then each lane adds its point's ones.
+// radiance x weight of a tile of rays are formed with coalesced loads into LDS, then each lane adds its point's ones.  The
+// glossy resolve serves the rlGgx glossy and both rlDisney queues.
 //
 // Built twice like the closure units of librlshaders_amd.so (rlshaders_amd/build.py, build_trace_library): RLS_FAST=0
 // carries the C ABI, the EXACT emit kernels and the mode-free scan / compact / resolve kernels; RLS_FAST=1 the FAST emit
@@ -168,6 +171,105 @@ __global__ RLS_INT_ATTR void ggx_refract_emit_kernel(TraceEmitIO a)
             if (a.side) stg(a.side, i, tir * (1.0f / (float)a.spp));   // as ggx_refract_loop: tir *= inv
         }
     }
+}
+
+// One lobe of rls_disney_integrate's sample loop (integrate.hip, disney_integrate_body) with the per-sample terms stored
+// instead of summed: SPEC = 0 the diffuse lobe (scramble streams +0/1), SPEC = 1 the specular lobe (+2/3, its rare branches
+// packed through SlowLds as there).  A sample is valid where pdf > 1e-4 (src/rlDisney.cpp:309) and queued where it is valid
+// and f / pdf is not 0 in all three channels: what it would add to the integrator's sum is then not +0.
+template <int G, int SPEC, int FAST_MATH>
+__device__ __forceinline__ void disney_emit_body(const DisneyEmitIO a, SlowLds<RLS_SPEC_BLOCK> *slow)
+{
+    constexpr int K = RLS_SPEC_BLOCK;
+    __shared__ uint32_t tab[2][kMaxSpp];
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    const int sub = threadIdx.x % G;
+    const int64_t groups_per_block = rlsh::kBlock / G;
+    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
+    const int64_t rounds = (a.n + stride - 1) / stride;
+    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
+    for (int64_t it = 0; it < rounds; it++, i += stride) {
+        const bool live = i < a.n;
+        const int64_t ii = live ? i : a.n - 1;
+        const DisneyEmitIO al = RLS_INT_ARGS(a);               // the closure's planes re-read per point, as there
+        const rls_disney_closure &c = al.c;
+        const PIndex<int64_t> pk = pindex(c.materials, ii);
+        V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
+        float br, bg, bb;
+        ldrgb(c.base_color, pk, br, bg, bb);
+        float sc[10];
+        sc[0] = ldp(c.subsurface, pk); sc[1] = ldp(c.metallic, pk); sc[2] = ldp(c.specular, pk);
+        sc[3] = ldp(c.specular_tint, pk); sc[4] = ldp(c.roughness, pk); sc[5] = ldp(c.anisotropic, pk);
+        sc[6] = ldp(c.sheen, pk); sc[7] = ldp(c.sheen_tint, pk); sc[8] = ldp(c.clearcoat, pk);
+        sc[9] = ldp(c.clearcoat_gloss, pk);
+        Disney d = disney_make(wo, N, T, br, bg, bb, sc);
+        disney_prepare(d);
+        VndfView w = vndf_view(d.view, d.fr, d.ax, d.ay);
+        const uint32_t sx = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + (SPEC ? 2 : 0));
+        const uint32_t sy = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + (SPEC ? 3 : 1));
+
+        float valid = 0.0f;
+        int run = 0;
+        for (int s0 = sub; s0 - sub < a.spp; s0 += K * G) {      // the same trip count in every lane
+            if constexpr (SPEC) {
+                int cnt = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const bool ok = s < a.spp;
+                    const int sc = ok ? s : 0;
+                    disney_spec_push<K>(*slow, k, cnt, ok, d, w, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
+                }
+                slow_run<K>(*slow, cnt);
+            }
+#pragma unroll 1
+            for (int k = 0; k < K; k++) {
+                const int s = s0 + k * G;
+                float tR = 0.0f, tG = 0.0f, tB = 0.0f;
+                V3 L = mk(0.0f, 0.0f, 0.0f);
+                if (s < a.spp) {
+                    float r, g, b, pdf;
+                    if constexpr (SPEC) {
+                        L = disney_spec_pop<K>(*slow, k, d, w);
+                        disney_eval_pdf<false, true, true>(d, L, r, g, b, pdf);
+                    } else {
+                        L = cosine_hemisphere(d.fr, bits_u01(tab[0][s] ^ sx), bits_u01(tab[1][s] ^ sy));
+                        disney_eval_pdf<true, true, true>(d, L, r, g, b, pdf);
+                    }
+                    if (pdf > kEps) { tR = r / pdf; tG = g / pdf; tB = b / pdf; valid += 1.0f; }
+                }
+                const bool keep = s < a.spp && !(tR == 0.0f && tG == 0.0f && tB == 0.0f);
+                const int rank = group_rank<G>(keep, sub, run);
+                if (live && s < a.spp) {
+                    const int64_t slot = (int64_t)s * a.n + i;
+                    if (keep) {
+                        a.dir[0][slot] = L.x; a.dir[1][slot] = L.y; a.dir[2][slot] = L.z;
+                        a.w[0][slot] = tR; a.w[1][slot] = tG; a.w[2][slot] = tB;
+                    }
+                    a.tag[slot] = keep ? (uint16_t)rank : kDropped;
+                }
+            }
+        }
+        if (G > 1) valid = group_sum<G>(valid);                     // a count: integers, any order
+        if (live && sub == 0) {
+            a.count[i] = run;
+            if (a.valid) stg(a.valid, i, valid);
+        }
+    }
+}
+
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void disney_diffuse_emit_kernel(DisneyEmitIO a)
+{
+    disney_emit_body<G, 0, FAST_MATH>(a, nullptr);                // (no rare branches in the cosine lobe: no queue)
+}
+
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void disney_specular_emit_kernel(DisneyEmitIO a)
+{
+    __shared__ SlowLds<RLS_SPEC_BLOCK> slow;
+    disney_emit_body<G, 1, FAST_MATH>(a, &slow);
 }
 
 #if !RLS_FAST
@@ -323,9 +425,16 @@ RLS_HIDDEN rls_status rls_trace_fast_refract_emit(rls_context *ctx, int g, const
 {
     return launch_g(ctx, RLS_G_FAMILY(ggx_refract_emit_kernel), g, *io, "rls_trace_ggx_refract_emit");
 }
+RLS_HIDDEN rls_status rls_trace_fast_disney_emit(rls_context *ctx, int g, int lobe, const DisneyEmitIO *io)
+{
+    return lobe == RLS_RAY_DIFFUSE
+        ? launch_g(ctx, RLS_G_FAMILY(disney_diffuse_emit_kernel), g, *io, "rls_trace_disney_emit")
+        : launch_g(ctx, RLS_G_FAMILY(disney_specular_emit_kernel), g, *io, "rls_trace_disney_emit");
+}
 #else
 RLS_HIDDEN rls_status rls_trace_fast_glossy_emit(rls_context *ctx, int g, const TraceEmitIO *io);
 RLS_HIDDEN rls_status rls_trace_fast_refract_emit(rls_context *ctx, int g, const TraceEmitIO *io);
+RLS_HIDDEN rls_status rls_trace_fast_disney_emit(rls_context *ctx, int g, int lobe, const DisneyEmitIO *io);
 
 namespace {
 
@@ -354,40 +463,34 @@ inline Staging staging(void *base, int64_t n, int spp)
     return s;
 }
 
-rls_status emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed, uint64_t first_index,
-                const rls_ray_queue *q, float *side, bool refract)
+// Every emit: the argument checks (lobe_ok: the rlDisney lobe, checked after spp_n), the empty queue of n == 0, the staging
+// in the caller's scratch, then launch(staging, G) -- the closure's emit kernel -- and the steps the closures share: the
+// per-point counts scanned in place into offsets, the kept records compacted into the queue (nw weight planes).  name: the
+// entry point.
+template <class Closure, class Launch>
+rls_status emit(rls_context *ctx, int64_t n, const Closure *c, int spp_n, bool lobe_ok, const rls_ray_queue *q, int nw,
+                const char *name, Launch launch)
 {
     RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
     RLS_REQUIRE(n >= 0, "n < 0");
     RLS_REQUIRE(n <= (int64_t)UINT32_MAX, "n > 2^32 - 1 (the queue's point index is 32-bit)");
     RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
+    RLS_REQUIRE(lobe_ok, "lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY");
     RLS_REQUIRE(q != nullptr && q->offsets != nullptr, "queue or queue.offsets is NULL");
     const int spp = spp_n * spp_n;
     if (n == 0) {                                        // an empty queue: offsets[0] = 0
         hipLaunchKernelGGL(trace_scan_totals_kernel, dim3(1), dim3(rlsh::kBlock), 0, ctx->stream, q->offsets, (int64_t)0,
                            q->offsets);
-        return rlsh::check_launch(refract ? "rls_trace_ggx_refract_emit" : "rls_trace_ggx_glossy_emit");
+        return rlsh::check_launch(name);
     }
     if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(q->dir), "queue.dir plane is NULL");
-    RLS_REQUIRE(refract ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
+    RLS_REQUIRE(nw == 1 ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
     RLS_REQUIRE(q->capacity >= n * spp, "queue.capacity < n * spp_n^2");
     const Staging st = staging(q->scratch, n, spp);
     RLS_REQUIRE(q->scratch != nullptr && q->scratch_bytes >= st.bytes, "queue.scratch is NULL or smaller than rls_trace_scratch_bytes");
 
-    TraceEmitIO io = {};
-    io.c = *c;
-    for (int k = 0; k < 3; k++) { io.dir[k] = st.dir[k]; io.w[k] = st.w[k]; }
-    io.tag = st.tag; io.count = q->offsets; io.side = side;
-    io.n = n; io.spp = spp; io.seed = seed; io.first = first_index;
-    const int g = pick_group(ctx, n, spp);
-    rls_status s;
-    if (refract)
-        s = ctx->fast ? rls_trace_fast_refract_emit(ctx, g, &io)
-                      : launch_g(ctx, RLS_G_FAMILY(ggx_refract_emit_kernel), g, io, "rls_trace_ggx_refract_emit");
-    else
-        s = ctx->fast ? rls_trace_fast_glossy_emit(ctx, g, &io)
-                      : launch_g(ctx, RLS_G_FAMILY(ggx_glossy_emit_kernel), g, io, "rls_trace_ggx_glossy_emit");
+    rls_status s = launch(st, pick_group(ctx, n, spp));
     if (s != RLS_OK) return s;
 
     // offsets: the counts scanned in place
@@ -406,9 +509,27 @@ rls_status emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n
     cio.tag = st.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp;
     cio.tile_points = kCompactSlots / spp < kCompactMaxPoints ? kCompactSlots / spp : kCompactMaxPoints;
     const dim3 cgrid = rlsh::grid_for(ctx, n, cio.tile_points);
-    if (refract) hipLaunchKernelGGL(trace_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    if (nw == 1) hipLaunchKernelGGL(trace_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
     else hipLaunchKernelGGL(trace_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
     return rlsh::check_launch("trace_compact_kernel");
+}
+
+rls_status ggx_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed, uint64_t first_index,
+                    const rls_ray_queue *q, float *side, bool refract)
+{
+    const char *name = refract ? "rls_trace_ggx_refract_emit" : "rls_trace_ggx_glossy_emit";
+    return emit(ctx, n, c, spp_n, true, q, refract ? 1 : 3, name, [&](const Staging &st, int g) {
+        TraceEmitIO io = {};
+        io.c = *c;
+        for (int k = 0; k < 3; k++) { io.dir[k] = st.dir[k]; io.w[k] = st.w[k]; }
+        io.tag = st.tag; io.count = q->offsets; io.side = side;
+        io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
+        if (refract)
+            return ctx->fast ? rls_trace_fast_refract_emit(ctx, g, &io)
+                             : launch_g(ctx, RLS_G_FAMILY(ggx_refract_emit_kernel), g, io, name);
+        return ctx->fast ? rls_trace_fast_glossy_emit(ctx, g, &io)
+                         : launch_g(ctx, RLS_G_FAMILY(ggx_glossy_emit_kernel), g, io, name);
+    });
 }
 
 rls_status resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, int spp_n, rls_crgb radiance, rls_rgb out, bool refract)
@@ -445,13 +566,30 @@ rls_status rls_trace_scratch_bytes(int64_t n, int spp_n, size_t *bytes)
 rls_status rls_trace_ggx_glossy_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed,
                                      uint64_t first_index, const rls_ray_queue *q, float *avg_reflect_weight)
 {
-    return emit(ctx, n, c, spp_n, seed, first_index, q, avg_reflect_weight, false);
+    return ggx_emit(ctx, n, c, spp_n, seed, first_index, q, avg_reflect_weight, false);
 }
 
 rls_status rls_trace_ggx_refract_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed,
                                       uint64_t first_index, const rls_ray_queue *q, float *tir_fraction)
 {
-    return emit(ctx, n, c, spp_n, seed, first_index, q, tir_fraction, true);
+    return ggx_emit(ctx, n, c, spp_n, seed, first_index, q, tir_fraction, true);
+}
+
+rls_status rls_trace_disney_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, int lobe, int spp_n, uint32_t seed,
+                                 uint64_t first_index, const rls_ray_queue *q, float *valid_count)
+{
+    const bool lobe_ok = lobe == RLS_RAY_DIFFUSE || lobe == RLS_RAY_GLOSSY;
+    return emit(ctx, n, c, spp_n, lobe_ok, q, 3, "rls_trace_disney_emit", [&](const Staging &st, int g) {
+        DisneyEmitIO io = {};
+        io.c = *c;
+        for (int k = 0; k < 3; k++) { io.dir[k] = st.dir[k]; io.w[k] = st.w[k]; }
+        io.tag = st.tag; io.count = q->offsets; io.valid = valid_count;
+        io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
+        if (ctx->fast) return rls_trace_fast_disney_emit(ctx, g, lobe, &io);
+        return lobe == RLS_RAY_DIFFUSE
+            ? launch_g(ctx, RLS_G_FAMILY(disney_diffuse_emit_kernel), g, io, "rls_trace_disney_emit")
+            : launch_g(ctx, RLS_G_FAMILY(disney_specular_emit_kernel), g, io, "rls_trace_disney_emit");
+    });
 }
 
 rls_status rls_trace_ggx_glossy_resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, rls_crgb radiance, rls_rgb sum)

@@ -1,5 +1,6 @@
-// example_trace.cpp -- the caller-traced rlGgx integrators from C++ (rls_trace.hpp): emit integrateGlossy's and
-// integrateRefract's sample rays, "trace" them against an analytic sky on the host, resolve.
+// example_trace.cpp -- the caller-traced rlGgx and rlDisney integrators from C++ (rls_trace.hpp): emit integrateGlossy's
+// and integrateRefract's sample rays and those of rlDisney's two lobes, "trace" them against an analytic sky on the host,
+// resolve.
 //
 //   example_trace [points] [spp_n]
 // prints one JSON line: the ray counts and a checksum (FNV-1a over the bits of the resolved planes) per integrator, which
@@ -55,26 +56,43 @@ int main(int argc, char **argv)
         c.specularRoughness = rls_param{nullptr, 0.4f};
         c.ior = rls_param{nullptr, 1.6f};
         c.anisotropic = rls_param{nullptr, 0.5f};
+        // an rlDisney closure on the same frame, uniform parameters (tests/test_gpu_trace_disney_host_cpp.py: the same)
+        rls_disney_closure dc = {};
+        dc.wo = c.wo; dc.N = c.N; dc.T = c.T;
+        dc.base_color = rlsb::ParamRGB(0.8f, 0.5f, 0.3f).c();
+        dc.subsurface = rls_param{nullptr, 0.1f};
+        dc.metallic = rls_param{nullptr, 0.2f};
+        dc.specular = rls_param{nullptr, 0.5f};
+        dc.specular_tint = rls_param{nullptr, 0.1f};
+        dc.roughness = rls_param{nullptr, 0.35f};
+        dc.anisotropic = rls_param{nullptr, 0.3f};
+        dc.sheen = rls_param{nullptr, 0.2f};
+        dc.sheen_tint = rls_param{nullptr, 0.5f};
+        dc.clearcoat = rls_param{nullptr, 0.3f};
+        dc.clearcoat_gloss = rls_param{nullptr, 0.6f};
 
         std::printf("{");
-        const rlsb::RayQueue::Kind kinds[2] = {rlsb::RayQueue::Glossy, rlsb::RayQueue::Refract};
-        for (int j = 0; j < 2; j++) {
+        const rlsb::RayQueue::Kind kinds[4] = {rlsb::RayQueue::Glossy, rlsb::RayQueue::Refract, rlsb::RayQueue::DisneyDiffuse,
+                                               rlsb::RayQueue::DisneyGlossy};
+        const char *names[4] = {"glossy", "refract", "disney_diffuse", "disney_glossy"};
+        for (int j = 0; j < 4; j++) {
             rlsb::RayQueue q(dev, n, spp_n, kinds[j]);
             rlsb::Planes side(dev, n, 1), out(dev, n, 3), radiance(dev, cap, 3);
             if (j == 0) rlsb::emitGlossy(dev, c, n, spp_n, kSeed, q, side.plane(0));
-            else rlsb::emitRefract(dev, c, n, spp_n, kSeed, q, side.plane(0));
+            else if (j == 1) rlsb::emitRefract(dev, c, n, spp_n, kSeed, q, side.plane(0));
+            else rlsb::emitDisney(dev, dc, j == 2 ? RLS_RAY_DIFFUSE : RLS_RAY_GLOSSY, n, spp_n, kSeed, q, side.plane(0));
             const int64_t count = q.count();
             std::vector<float> dz((size_t)count), L((size_t)(3 * cap), 0.0f);
             rlsb::check(rls_copy_to_host(dev.ctx(), dz.data(), q.c().dir.z, sizeof(float) * dz.size()));
             sky(dz, cap, L);
             radiance.upload(L);
-            if (j == 0) rlsb::resolveGlossy(dev, q, radiance, out);
-            else rlsb::resolveRefract(dev, q, radiance, out);
+            if (j == 1) rlsb::resolveRefract(dev, q, radiance, out);
+            else rlsb::resolveGlossy(dev, q, radiance, out);
             std::vector<float> res = out.download();
             double mean = 0.0;
             for (float v : res) mean += v;
             std::printf("%s\"%s\": {\"rays\": %lld, \"checksum\": \"%016llx\", \"mean\": %.9g}", j ? ", " : "",
-                        j == 0 ? "glossy" : "refract", (long long)count, (unsigned long long)fnv(res), mean / (double)res.size());
+                        names[j], (long long)count, (unsigned long long)fnv(res), mean / (double)res.size());
         }
         std::printf(", \"points\": %lld, \"spp_n\": %d}\n", (long long)n, spp_n);
     } catch (const rlsb::Error &e) {

@@ -1,12 +1,15 @@
-// rls_trace.hpp -- C++14 host-side mirror of the caller-traced rlGgx integrators (include/rlshaders_amd_trace.h,
-// librls_trace.so).  Header-only, in the style of rls_batch.hpp, whose Device / Planes / check it uses.
+// rls_trace.hpp -- C++14 host-side mirror of the caller-traced rlGgx and rlDisney integrators
+// (include/rlshaders_amd_trace.h, librls_trace.so).  Header-only, in the style of rls_batch.hpp, whose Device / Planes /
+// check it uses.
 //
 // Where the reference traces inside integrateGlossy / integrateRefract (AiBRDFIntegrate, src/rlGgx.h:172-179; AiTrace,
-// src/rlGgx.h:228-244), a renderer's bucket flush does three steps:
+// src/rlGgx.h:228-244) or rlDisney's integrateDiffuse / integrateGlossy (AiBRDFIntegrate, src/rlDisney.cpp:240-243,
+// 279-283), a renderer's bucket flush does three steps:
 //     rlsb::RayQueue q(dev, n, spp_n, rlsb::RayQueue::Glossy);
 //     rlsb::emitGlossy(dev, closure, n, spp_n, seed, q, avgReflectWeight);   // every sample ray, compacted
 //     ... trace q.dir() [q.count() rays] with the renderer's tracer, one radiance per ray -> radiance (3 planes) ...
 //     rlsb::resolveGlossy(dev, q, radiance, sum);                           // sum of radiance x f/pdf per point
+// rlDisney: a RayQueue of kind DisneyDiffuse / DisneyGlossy per lobe, emitDisney, and resolveGlossy likewise.
 // Nothing here synchronises the host except RayQueue::count() (it reads offsets[n]).
 #pragma once
 
@@ -20,7 +23,7 @@ namespace rlsb {
 // The device buffers of one emit: per-ray planes for n * spp_n^2 rays, offsets [n + 1] and the emit's scratch.
 class RayQueue {
 public:
-    enum Kind { Glossy, Refract };
+    enum Kind { Glossy, Refract, DisneyDiffuse, DisneyGlossy };
 
     RayQueue(const Device &d, int64_t n, int spp_n, Kind kind) : dev_(&d), n_(n), spp_n_(spp_n), kind_(kind)
     {
@@ -57,7 +60,7 @@ private:
         q_.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(n_ + 1)));
         q_.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
         q_.weight.r = falloc(cap);
-        if (kind_ == Glossy) { q_.weight.g = falloc(cap); q_.weight.b = falloc(cap); }
+        if (kind_ != Refract) { q_.weight.g = falloc(cap); q_.weight.b = falloc(cap); }
         q_.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
         q_.sample = static_cast<uint8_t *>(alloc((size_t)cap));
         if (kind_ == Refract) q_.kind = static_cast<uint8_t *>(alloc((size_t)cap));
@@ -91,7 +94,9 @@ private:
 inline void emitGlossy(const Device &d, const rls_ggx_closure &c, int64_t n, int spp_n, uint32_t seed, RayQueue &q,
                        float *avgReflectWeight = nullptr, uint64_t first_index = 0)
 {
-    if (q.kind() != RayQueue::Glossy) throw Error(RLS_ERR_INVALID_ARGUMENT, "emitGlossy: a refraction queue");
+    if (q.kind() != RayQueue::Glossy)
+        throw Error(RLS_ERR_INVALID_ARGUMENT, q.kind() == RayQueue::Refract ? "emitGlossy: a refraction queue"
+                                                                           : "emitGlossy: an rlDisney queue");
     check(rls_trace_ggx_glossy_emit(d.ctx(), n, &c, spp_n, seed, first_index, &q.c(), avgReflectWeight));
 }
 
@@ -99,11 +104,24 @@ inline void emitGlossy(const Device &d, const rls_ggx_closure &c, int64_t n, int
 inline void emitRefract(const Device &d, const rls_ggx_closure &c, int64_t n, int spp_n, uint32_t seed, RayQueue &q,
                         float *tirFraction = nullptr, uint64_t first_index = 0)
 {
-    if (q.kind() != RayQueue::Refract) throw Error(RLS_ERR_INVALID_ARGUMENT, "emitRefract: a glossy queue");
+    if (q.kind() != RayQueue::Refract)
+        throw Error(RLS_ERR_INVALID_ARGUMENT, q.kind() == RayQueue::Glossy ? "emitRefract: a glossy queue"
+                                                                          : "emitRefract: an rlDisney queue");
     check(rls_trace_ggx_refract_emit(d.ctx(), n, &c, spp_n, seed, first_index, &q.c(), tirFraction));
 }
 
-// radiance: 3 planes of >= q.count() floats, one per ray; out: 3 planes of n floats
+// the sample rays of one rlDisney lobe (src/rlDisney.cpp:240-243, 279-283): lobe RLS_RAY_DIFFUSE into a DisneyDiffuse
+// queue, RLS_RAY_GLOSSY into a DisneyGlossy one; validCount: n floats (rls_disney_integrate's count for the lobe) or nullptr
+inline void emitDisney(const Device &d, const rls_disney_closure &c, int lobe, int64_t n, int spp_n, uint32_t seed,
+                       RayQueue &q, float *validCount = nullptr, uint64_t first_index = 0)
+{
+    const RayQueue::Kind want = lobe == RLS_RAY_DIFFUSE ? RayQueue::DisneyDiffuse : RayQueue::DisneyGlossy;
+    if (q.kind() != want) throw Error(RLS_ERR_INVALID_ARGUMENT, "emitDisney: a queue of another integrator or lobe");
+    check(rls_trace_disney_emit(d.ctx(), n, &c, lobe, spp_n, seed, first_index, &q.c(), validCount));
+}
+
+// a Glossy, DisneyDiffuse or DisneyGlossy queue; radiance: 3 planes of >= q.count() floats, one per ray; out: 3 planes of
+// n floats
 inline void resolveGlossy(const Device &d, const RayQueue &q, const Planes &radiance, Planes &sum)
 {
     check(rls_trace_ggx_glossy_resolve(d.ctx(), q.points(), &q.c(),

@@ -1,9 +1,13 @@
-"""Caller-traced rlGgx integrators: emit the sample rays of integrateGlossy / integrateRefract, trace them with your own
-tracer, resolve the radiance (include/rlshaders_amd_trace.h, companion library ``librls_trace.so``).
+"""Caller-traced rlGgx and rlDisney integrators: emit the sample rays of integrateGlossy / integrateRefract (rlGgx) or of
+one rlDisney lobe, trace them with your own tracer, resolve the radiance (include/rlshaders_amd_trace.h, companion library
+``librls_trace.so``).
 
     q = trace.glossy_rays(sampler, spp_n=4, seed=7)          # RayQueue: q.dir [3, count], q.weight [3, count], ...
     L = my_tracer(origins[q.point], q.dir)                   # [3, count] radiance, one per ray
     s = q.resolve(L)                                         # [3, n]: sum of L x f/pdf per point (rls_ggx_integrate's sum)
+
+    d = trace.disney_rays(disney, RLS_RAY_DIFFUSE, 8, seed)  # one lobe per queue; q.resolve: rls_disney_integrate's
+                                                             # diffuse_sum, d.valid_count its diffuse_count
 
 ``count`` is read from the device once (it synchronises); everything else stays asynchronous on the context's stream, so
 ``glossy_rays(..., queue=q)`` / ``q.resolve(L, out=...)`` with preallocated tensors can be recorded by ``ctx.capture()``.
@@ -18,8 +22,8 @@ from typing import Optional
 import torch
 
 from . import _capi as capi
-from ._capi import check
-from .closures import GgxSampler, plane, rgb
+from ._capi import RLS_RAY_DIFFUSE, RLS_RAY_GLOSSY, check
+from .closures import DisneySampler, GgxSampler, plane, rgb
 
 TRACE_LIB_PATH = capi._PKG / "lib" / "librls_trace.so"
 
@@ -40,6 +44,8 @@ PROTOTYPES = {
     "rls_trace_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
     "rls_trace_ggx_glossy_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
     "rls_trace_ggx_refract_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
+    "rls_trace_disney_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.DisneyClosure), C.c_int, C.c_int, C.c_uint32, C.c_uint64,
+                                        _q, _vp]),
     "rls_trace_ggx_glossy_resolve": (C.c_int, [_ctx, _i64, _q, capi.CRgb, capi.Rgb]),
     "rls_trace_ggx_refract_resolve": (C.c_int, [_ctx, _i64, _q, C.c_int, capi.CRgb, capi.Rgb]),
 }
@@ -78,10 +84,14 @@ def scratch_bytes(n: int, spp_n: int) -> int:
 class RayQueue:
     """The sample rays of one emit over n points at spp_n^2 samples, point-major (CSR: point i's rays are
     [offsets[i], offsets[i+1])).  Planes are allocated for the full capacity n * spp_n^2; the properties below view the
-    first ``count`` rays."""
+    first ``count`` rays.  ``lobe`` (RLS_RAY_DIFFUSE / RLS_RAY_GLOSSY) makes it a queue of that rlDisney lobe; without it
+    the queue is rlGgx's, glossy or (``refract``) refraction."""
 
-    def __init__(self, ctx, n: int, spp_n: int, refract: bool, want_kind: bool = True):
+    def __init__(self, ctx, n: int, spp_n: int, refract: bool = False, want_kind: bool = True, *, lobe: Optional[int] = None):
+        if lobe is not None and (lobe not in (RLS_RAY_DIFFUSE, RLS_RAY_GLOSSY) or refract):
+            raise ValueError("lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY, on a queue without refract")
         self.ctx, self.n, self.spp_n, self.refract = ctx, int(n), int(spp_n), bool(refract)
+        self.lobe = lobe
         dev = ctx.torch_device
         cap = self.n * self.spp_n * self.spp_n
         self.capacity = cap
@@ -92,7 +102,8 @@ class RayQueue:
         self._sample = torch.empty(cap, dtype=torch.uint8, device=dev)
         self._kind = torch.empty(cap, dtype=torch.uint8, device=dev) if refract and want_kind else None
         self._scratch = torch.empty(max(scratch_bytes(self.n, self.spp_n), 1), dtype=torch.uint8, device=dev)
-        # per point: getAvgReflectWeight (glossy) / the fraction of totally internally reflected samples (refraction)
+        # per point: getAvgReflectWeight (glossy) / the fraction of totally internally reflected samples (refraction) /
+        # the valid samples (rlDisney)
         self.side = torch.empty(self.n, dtype=torch.float32, device=dev)
         w = self._weight
         q = RayQueue_()
@@ -133,19 +144,31 @@ class RayQueue:
 
     @property
     def avg_reflect_weight(self) -> torch.Tensor:
+        if self.lobe is not None:
+            raise AttributeError("an rlDisney queue has valid_count, not avg_reflect_weight")
         if self.refract:
             raise AttributeError("a refraction queue has tir_fraction, not avg_reflect_weight")
         return self.side
 
     @property
     def tir_fraction(self) -> torch.Tensor:
+        if self.lobe is not None:
+            raise AttributeError("an rlDisney queue has valid_count, not tir_fraction")
         if not self.refract:
             raise AttributeError("a glossy queue has avg_reflect_weight, not tir_fraction")
         return self.side
 
+    @property
+    def valid_count(self) -> torch.Tensor:
+        """[n] the lobe's valid samples per point: rls_disney_integrate's diffuse_count / specular_count"""
+        if self.lobe is None:
+            raise AttributeError("an rlGgx queue has avg_reflect_weight / tir_fraction, not valid_count")
+        return self.side
+
     def resolve(self, radiance: torch.Tensor, out: Optional[torch.Tensor] = None, count: Optional[int] = None) -> torch.Tensor:
-        """radiance [3, >= count] float32, one per ray -> [3, n]: glossy the sum of radiance x f/pdf per point (the
-        convention of rls_ggx_integrate's sum), refraction the mean of radiance x weight over the spp_n^2 samples.
+        """radiance [3, >= count] float32, one per ray -> [3, n]: glossy and rlDisney the sum of radiance x f/pdf per point
+        (the convention of rls_ggx_integrate's sum and rls_disney_integrate's diffuse_sum / specular_sum), refraction the
+        mean of radiance x weight over the spp_n^2 samples.
         ``count``: the ray count when the caller knows it (skips the read of offsets[n], e.g. while recording a graph)."""
         ctx, n = self.ctx, self.n
         count = self.count if count is None else int(count)
@@ -165,7 +188,7 @@ class RayQueue:
 def _emit(sampler: GgxSampler, spp_n: int, seed: int, first_index: int, queue: Optional[RayQueue], refract: bool) -> RayQueue:
     ctx, n = sampler.ctx, sampler.n
     q = RayQueue(ctx, n, spp_n, refract) if queue is None else queue
-    if q.n != n or q.spp_n != int(spp_n) or q.refract != refract:
+    if q.n != n or q.spp_n != int(spp_n) or q.refract != refract or q.lobe is not None:
         raise ValueError("queue: allocated for another batch size, spp_n or integrator")
     lib = load()
     fn = lib.rls_trace_ggx_refract_emit if refract else lib.rls_trace_ggx_glossy_emit
@@ -185,3 +208,18 @@ def refract_rays(sampler: GgxSampler, spp_n: int, seed: int, first_index: int = 
     a non-zero weight queued with their direction, weight and kind (RLS_RAY_TRANSMITTED / RLS_RAY_TIR_MIRROR);
     ``queue.tir_fraction`` as rls_ggx_integrate_refract writes it."""
     return _emit(sampler, spp_n, seed, first_index, queue, True)
+
+
+def disney_rays(sampler: DisneySampler, lobe: int, spp_n: int, seed: int, first_index: int = 0,
+                queue: Optional[RayQueue] = None) -> RayQueue:
+    """The sample rays of one rlDisney lobe (integrateDiffuse / integrateGlossy, src/rlDisney.cpp:240-243, 279-283; lobe
+    RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY): the samples rls_disney_integrate draws for that lobe, the valid ones (pdf > 1e-4)
+    with f/pdf != 0 queued with their direction and f/pdf; ``queue.valid_count`` is the lobe's count as rls_disney_integrate
+    writes it.  ``queue.resolve`` with radiance 1 is rls_disney_integrate's sum for the lobe."""
+    ctx, n = sampler.ctx, sampler.n
+    q = RayQueue(ctx, n, spp_n, lobe=lobe) if queue is None else queue
+    if q.n != n or q.spp_n != int(spp_n) or q.lobe != lobe:
+        raise ValueError("queue: allocated for another batch size, spp_n, integrator or lobe")
+    check(load().rls_trace_disney_emit(ctx.handle, n, C.byref(sampler.c), int(lobe), int(spp_n), int(seed) & 0xFFFFFFFF,
+                                       int(first_index), C.byref(q.q), plane(q.side, n, "valid_count") if n > 0 else None))
+    return q

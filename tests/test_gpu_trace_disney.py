@@ -1,0 +1,439 @@
+"""GPU: the caller-traced rlDisney integrator (rls_trace_disney_emit, rlshaders_amd.trace.disney_rays).
+
+One emit puts the sample rays of one rlDisney lobe (integrateDiffuse / integrateGlossy, src/rlDisney.cpp:240-243, 279-283)
+into a compacted queue; the glossy resolve reduces the radiance the caller traced.  Checked here: with radiance 1 the
+resolve IS rls_disney_integrate's sum for the lobe and valid_count its count, bit for bit (EXACT and FAST); the queue against
+the streamed integrator (the same samples) and against the oracle composed per sample (orc_sample_02 ->
+orc_batch_disney_sample_eval_pdf); a non-constant radiance against a float32 sequential sum; chunking over first_index and
+the lane-group width; argument checks; graph capture."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import cases
+import oracle_lib as O
+
+pytestmark = pytest.mark.gpu
+
+SEED = 4242
+INVALID = 1            # RLS_ERR_INVALID_ARGUMENT
+DIFFUSE, GLOSSY = 0x08, 0x10          # RLS_RAY_DIFFUSE, RLS_RAY_GLOSSY
+LOBES = [DIFFUSE, GLOSSY]
+LOBE_IDS = ["diffuse", "glossy"]
+SUM = {DIFFUSE: "diffuse_sum", GLOSSY: "specular_sum"}
+COUNT = {DIFFUSE: "diffuse_count", GLOSSY: "specular_count"}
+EPS = np.float32(1e-4)                # AI_EPSILON: a sample is valid where pdf > 1e-4 (src/rlDisney.cpp:309)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import rlshaders_amd as R
+    from rlshaders_amd import build
+    build.build_trace_library()
+    c = R.Context(0)
+    yield c
+    c.close()
+
+
+def _trace():
+    from rlshaders_amd import trace
+    return trace
+
+
+def _host(t):
+    return t.detach().cpu().numpy()
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda() if isinstance(a, np.ndarray) else a
+
+
+def _with_group(g, fn):
+    os.environ["RLS_INTEGRATE_GROUP"] = str(g)
+    try:
+        return fn()
+    finally:
+        del os.environ["RLS_INTEGRATE_GROUP"]
+
+
+def _sampler(ctx, case, materials=None):
+    import rlshaders_amd as R
+    sc = {k: _dev(case[k]) for k in R._capi.DISNEY_SCALARS if k in case}
+    return R.DisneySampler(ctx, _dev(case["wo"]), _dev(case["N"]), _dev(case["T"]),
+                           base_color=_dev(case.get("base_color", (1.0, 1.0, 1.0))), materials=materials, **sc)
+
+
+def _inputs(kind, n):
+    """(case dict for the sampler, materials or None)"""
+    if kind == "mixed":
+        return cases.disney_mixed(cases.SEED_PARITY, n), None
+    if kind.startswith("preset:"):
+        wo, N, T = cases.frame(cases.SEED_PARITY, n)
+        return dict(wo=wo, N=N, T=T, **cases.DISNEY_PRESETS[kind[7:]]), None
+    if kind == "uniform":
+        wo, N, T = cases.frame(cases.SEED_PARITY, n)
+        return dict(wo=wo, N=N, T=T, base_color=(0.8, 0.5, 0.3), subsurface=0.1, metallic=0.2, specular=0.5,
+                    specular_tint=0.1, roughness=0.35, anisotropic=0.3, sheen=0.2, sheen_tint=0.5, clearcoat=0.3,
+                    clearcoat_gloss=0.6), None
+    if kind == "materials":
+        m = 7
+        cols = cases.disney_mixed(cases.SEED_PARITY + 1, m)
+        wo, N, T = cases.frame(cases.SEED_PARITY, n)
+        ids = (O.gen_uniform(cases.SEED_PARITY, 0, n, 77) * m).astype(np.uint32) % m
+        case = dict(cols, wo=wo, N=N, T=T)
+        return case, (torch.from_numpy(ids.astype(np.int32)).cuda(), m)
+    if kind == "rare":
+        # the specular lobe's packed rare branches with every lane asking (test_gpu_disney_config3.py,
+        # test_packed_rare_branches_with_every_lane_asking): views along the normal take the uniform-slope fallback,
+        # clearcoat = 1 sends samples to the clearcoat half vector
+        wo, N, T = cases.frame(cases.SEED_PARITY, n)
+        c = cases.disney_mixed(cases.SEED_PARITY, n)
+        return dict(c, wo=N.copy(), N=N, T=T, clearcoat=np.ones(n, np.float32)), None
+    raise KeyError(kind)
+
+
+KINDS = ["mixed", "uniform", "materials", "rare"] + [f"preset:{k}" for k in cases.DISNEY_PRESETS]
+
+
+def _ones(ctx, q):
+    return torch.ones(3, max(q.count, 1), dtype=torch.float32, device=ctx.torch_device)
+
+
+# ---- 1. radiance 1: the integrator, bit for bit -----------------------------------------------------------------------------
+@pytest.mark.parametrize("fast", [False, True], ids=["exact", "fast"])
+@pytest.mark.parametrize("spp_n", [1, 2, 4, 8, 16])
+def test_unit_radiance_is_the_integrator_bit_for_bit(ctx, spp_n, fast):
+    T = _trace()
+    n = 3001 if spp_n <= 8 else 1001
+    ctx.set_math_mode(fast)
+    try:
+        for kind in KINDS:
+            case, mat = _inputs(kind, n)
+            s = _sampler(ctx, case, mat)
+            ref = s.integrate(spp_n, SEED)
+            for lobe in LOBES:
+                q = T.disney_rays(s, lobe, spp_n, SEED)
+                what = (kind, spp_n, fast, SUM[lobe])
+                cases.assert_same_bits(_host(q.resolve(_ones(ctx, q))), _host(ref[SUM[lobe]]), what)
+                cases.assert_same_bits(_host(q.valid_count), _host(ref[COUNT[lobe]]), what + ("count",))
+                assert q.count <= int(_host(ref[COUNT[lobe]]).sum()), what
+    finally:
+        ctx.set_math_mode(False)
+
+
+# ---- 2. the queue against the streamed integrator (the same samples) ------------------------------------------------------
+def _expected_from_stream(st, n, spp, lobe):
+    """the streamed samples of one lobe (sample-major: diffuse at s * n + i, specular at (spp + s) * n + i) -> point-major
+    [n, spp] arrays of wi, f, pdf, the float32 weight f / pdf and the kept mask"""
+    base = 0 if lobe == DIFFUSE else spp * n
+    sl = slice(base, base + spp * n)
+    wi = st["wi"][:, sl].reshape(3, spp, n).transpose(0, 2, 1)           # [3, n, spp]
+    f = st["f"][:, sl].reshape(3, spp, n).transpose(0, 2, 1)
+    pdf = st["pdf"][sl].reshape(spp, n).T                                 # [n, spp]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = (f / pdf[None]).astype(np.float32)
+    keep = (pdf > EPS) & ~np.all(w == 0.0, axis=0)
+    return wi, w, keep
+
+
+@pytest.mark.parametrize("fast", [False, True], ids=["exact", "fast"])
+@pytest.mark.parametrize("kind,spp_n", [("mixed", 4), ("rare", 3), ("preset:0008_anisotropic", 2), ("materials", 5)])
+def test_queue_matches_the_streamed_integrator(ctx, kind, spp_n, fast):
+    T = _trace()
+    n, spp = 1500, spp_n * spp_n
+    case, mat = _inputs(kind, n)
+    ctx.set_math_mode(fast)
+    try:
+        s = _sampler(ctx, case, mat)
+        st = {k: _host(v) for k, v in s.integrate(spp_n, SEED, streamed=True).items()}
+        for lobe in LOBES:
+            q = T.disney_rays(s, lobe, spp_n, SEED)
+            wi, w, keep = _expected_from_stream(st, n, spp, lobe)
+            off = _host(q.offsets)
+            np.testing.assert_array_equal(off, np.concatenate([[0], np.cumsum(keep.sum(axis=1))]), (kind, lobe))
+            cnt = q.count
+            pts, smp = np.nonzero(keep)                                   # point-major, samples ascending
+            np.testing.assert_array_equal(_host(q.point).astype(np.int64), pts)
+            np.testing.assert_array_equal(_host(q.sample).astype(np.int64), smp)
+            assert cnt == len(pts)
+            cases.assert_same_bits(_host(q.dir), wi[:, pts, smp], (kind, lobe, fast, "dir"))
+            qw = _host(q.weight)
+            assert not np.any(np.all(qw == 0.0, axis=0))
+            if not fast:
+                cases.assert_same_bits(qw, w[:, pts, smp], (kind, lobe, "weight = f / pdf"))
+            # valid_count counts every valid sample, queued or not (a valid one is dropped where f = 0)
+            pdf = st["pdf"][(0 if lobe == DIFFUSE else spp * n):][:spp * n].reshape(spp, n)
+            np.testing.assert_array_equal(_host(q.valid_count), (pdf > EPS).sum(axis=0).astype(np.float32))
+    finally:
+        ctx.set_math_mode(False)
+
+
+# ---- 3. the queue against the oracle ---------------------------------------------------------------------------------------
+def _oracle_queue(case, spp_n, seed, lobe, first=0):
+    """the queue composed on the CPU: per sample s the scrambled (0,2) point (orc_sample_02, dimension pair 0 for the
+    diffuse lobe, 1 for the specular one) and the oracle closure's sample / eval / pdf triple for the lobe; kept where
+    pdf > 1e-4 and f / pdf is not all zero -> dict of the flattened point-major queue and the offsets"""
+    from gpu_util import disney_oracle
+    n, spp = case["wo"].shape[1], spp_n * spp_n
+    od = disney_oracle(O, case)
+    pair = 0 if lobe == DIFFUSE else 1
+    dirs, ws, keep = [], [], []
+    for s in range(spp):
+        rx = np.empty(n, np.float32)
+        ry = np.empty(n, np.float32)
+        for i in range(n):
+            rx[i], ry[i] = O.sample_02(seed, first + i, pair, s)
+        wi, f, pdf = od.sample_eval_pdf(lobe, rx, ry)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = (f / pdf[None, :]).astype(np.float32)
+        dirs.append(wi); ws.append(t); keep.append((pdf > EPS) & ~np.all(t == 0.0, axis=0))
+    keep = np.stack(keep, axis=1)                                   # [n, spp]
+    sel = keep.reshape(-1)
+    flat = lambda a: np.stack(a, axis=2).reshape(a[0].shape[0], -1)[:, sel]
+    pts, smp = np.meshgrid(np.arange(n), np.arange(spp), indexing="ij")
+    return dict(dir=flat(dirs), weight=flat(ws), point=pts.reshape(-1)[sel], sample=smp.reshape(-1)[sel],
+                offsets=np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int64))
+
+
+@pytest.mark.parametrize("lobe", LOBES, ids=LOBE_IDS)
+@pytest.mark.parametrize("kind,spp_n", [("mixed", 4), ("rare", 3), ("preset:0006_rough_metallic", 2)])
+def test_queue_matches_the_oracle(ctx, kind, spp_n, lobe):
+    T = _trace()
+    n = 1024
+    case, _ = _inputs(kind, n)
+    q = T.disney_rays(_sampler(ctx, case), lobe, spp_n, SEED)
+    want = _oracle_queue(case, spp_n, SEED, lobe)
+    offsets = _host(q.offsets)
+    assert offsets[0] == 0 and np.all(np.diff(offsets) >= 0) and np.all(np.diff(offsets) <= spp_n * spp_n)
+    np.testing.assert_array_equal(offsets, want["offsets"])
+    assert q.count == want["offsets"][-1]
+    np.testing.assert_array_equal(_host(q.point).astype(np.int64), want["point"])
+    np.testing.assert_array_equal(_host(q.sample).astype(np.int64), want["sample"])
+    if kind == "preset:0006_rough_metallic" and lobe == DIFFUSE:
+        assert q.count == 0                                         # metallic = 1: no diffuse lobe, every sample dropped
+        return
+    cases.assert_tight(cases.summarize(cases.rel_err(_host(q.dir), want["dir"])), (kind, lobe, "dir"))
+    cases.assert_tight(cases.summarize(cases.rel_err(_host(q.weight), want["weight"])), (kind, lobe, "weight"))
+
+
+# ---- 4. a radiance that varies -----------------------------------------------------------------------------------------------
+def _radiance(d, k):
+    """a deterministic float32 sky: a function of the direction and of the ray index"""
+    d = d.astype(np.float32)
+    k = k.astype(np.float32)
+    r = np.float32(0.25) + np.float32(0.75) * np.maximum(d[2], np.float32(0.0))
+    g = np.float32(1.0) + np.float32(0.5) * d[0] * d[1]
+    b = np.float32(0.5) + np.float32(1e-3) * np.mod(k, np.float32(97.0))
+    return np.stack([r, g, b]).astype(np.float32)
+
+
+def _sequential(L, w, offsets):
+    """float32 sum per point over its rays in queue order (sum += L * w)"""
+    n = len(offsets) - 1
+    cnt = np.diff(offsets)
+    acc = np.zeros((3, n), np.float32)
+    prod = (L * w).astype(np.float32)
+    for j in range(int(cnt.max()) if n else 0):
+        m = cnt > j
+        acc[:, m] = acc[:, m] + prod[:, offsets[:-1][m] + j]
+    return acc
+
+
+@pytest.mark.parametrize("lobe", LOBES, ids=LOBE_IDS)
+def test_varying_radiance(ctx, lobe):
+    T = _trace()
+    n, spp_n = 1024, 4
+    case, _ = _inputs("mixed", n)
+    q = T.disney_rays(_sampler(ctx, case), lobe, spp_n, SEED)
+    cnt = q.count
+    d, w, off = _host(q.dir), _host(q.weight), _host(q.offsets)
+    L = _radiance(d, np.arange(cnt))
+    got = _host(q.resolve(_dev(L)))
+    cases.assert_same_bits(got, _sequential(L, w, off), "resolve vs host sequential sum over the emitted queue")
+    want = _oracle_queue(case, spp_n, SEED, lobe)
+    Lo = _radiance(want["dir"], np.arange(len(want["point"])))
+    cases.assert_tight(cases.summarize(cases.rel_err(got, _sequential(Lo, want["weight"], want["offsets"]))),
+                       "resolve vs oracle")
+
+
+# ---- 5. chunks and lane-group widths -------------------------------------------------------------------------------------------
+def _slice(case, a, b):
+    return {k: (v[..., a:b].copy() if isinstance(v, np.ndarray) else v) for k, v in case.items()}
+
+
+def _queue_host(q):
+    return dict(offsets=_host(q.offsets), dir=_host(q.dir), weight=_host(q.weight), point=_host(q.point),
+                sample=_host(q.sample), valid=_host(q.valid_count))
+
+
+@pytest.mark.parametrize("lobe", LOBES, ids=LOBE_IDS)
+def test_chunks_and_group_widths(ctx, lobe):
+    T = _trace()
+    spp_n = 8                                                             # 64 samples: tiny slices run 64 lanes per point
+    n, cut = 1 << 16, 23457
+    case, _ = _inputs("mixed", n)
+    full = T.disney_rays(_sampler(ctx, case), lobe, spp_n, SEED)
+    L = torch.rand(3, full.count, generator=torch.Generator().manual_seed(1)).cuda()
+    res_full = _host(full.resolve(L))
+    fh = _queue_host(full)
+    off = fh["offsets"]
+    parts = [(0, cut), (cut, n), (n - 64, n), (100, 117), (5000, 5001)]   # the last three: a few points, wide lane groups
+    for a, b in parts:
+        qa = T.disney_rays(_sampler(ctx, _slice(case, a, b)), lobe, spp_n, SEED, first_index=a)
+        h = _queue_host(qa)
+        np.testing.assert_array_equal(h["offsets"], off[a:b + 1] - off[a], (a, b))
+        lo, hi = int(off[a]), int(off[b])
+        cases.assert_same_bits(h["dir"], fh["dir"][:, lo:hi], (a, b, "dir"))
+        cases.assert_same_bits(h["weight"], fh["weight"][:, lo:hi], (a, b, "weight"))
+        np.testing.assert_array_equal(h["point"].astype(np.int64) + a, fh["point"][lo:hi])
+        np.testing.assert_array_equal(h["sample"], fh["sample"][lo:hi])
+        cases.assert_same_bits(h["valid"], fh["valid"][a:b], (a, b, "valid_count"))
+        cases.assert_same_bits(_host(qa.resolve(L[:, lo:hi].contiguous())), res_full[:, a:b], (a, b, "resolve"))
+    # the same bits whatever the lane-group width
+    m = 3001
+    sub = _sampler(ctx, _slice(case, 0, m))
+    base = None
+    for g in (1, 4, 16, 64):
+        q = _with_group(g, lambda: T.disney_rays(sub, lobe, spp_n, SEED))
+        h = _queue_host(q)
+        h["resolve"] = _host(q.resolve(L[:, :max(q.count, 1)].contiguous()))
+        if base is None:
+            base = h
+            continue
+        np.testing.assert_array_equal(h["offsets"], base["offsets"], g)
+        np.testing.assert_array_equal(h["point"], base["point"], g)
+        np.testing.assert_array_equal(h["sample"], base["sample"], g)
+        for k in ("dir", "weight", "valid", "resolve"):
+            cases.assert_same_bits(h[k], base[k], (g, k))
+
+
+# ---- 6. argument checks ------------------------------------------------------------------------------------------------------
+def _last_error():
+    import rlshaders_amd as R
+    return R.load().rls_last_error().decode()
+
+
+def test_argument_checks(ctx):
+    T = _trace()
+    lib = T.load()
+    n, spp_n = 256, 2
+    case, _ = _inputs("mixed", n)
+    s = _sampler(ctx, case)
+    q = T.RayQueue(ctx, n, spp_n, lobe=DIFFUSE)
+    valid = ctx.empty(n)
+
+    def emit(qq=None, lobe=DIFFUSE, spp=spp_n, nn=n, c=C.byref(s.c)):
+        return lib.rls_trace_disney_emit(ctx.handle, nn, c, lobe, spp, SEED, 0, None if qq is None else C.byref(qq),
+                                         valid.data_ptr())
+
+    def refused(status, text):
+        assert status == INVALID, text
+        assert _last_error() == "emit: " + text
+
+    def broken(**fields):
+        bad = T.RayQueue_.from_buffer_copy(q.q)
+        for k, v in fields.items():
+            if "." in k:
+                a, b = k.split(".")
+                setattr(getattr(bad, a), b, v)
+            else:
+                setattr(bad, k, v)
+        return bad
+
+    assert emit(q.q) == 0 and emit(q.q, lobe=GLOSSY) == 0
+    for lobe in (0, 1, DIFFUSE | GLOSSY, 0x20):
+        refused(emit(q.q, lobe=lobe), "lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY")
+    for spp in (0, 17):
+        refused(emit(q.q, spp=spp), "spp_n must be in [1, 16]")
+    refused(emit(q.q, spp=17, lobe=0), "spp_n must be in [1, 16]")            # spp_n is checked before the lobe
+    refused(emit(q.q, nn=-1), "n < 0")
+    refused(emit(None), "queue or queue.offsets is NULL")
+    refused(emit(broken(offsets=None)), "queue or queue.offsets is NULL")
+    refused(emit(None, lobe=0), "lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY")  # ... and the lobe before the queue
+    refused(emit(broken(**{"dir.y": None})), "queue.dir plane is NULL")
+    for ch in ("r", "g", "b"):
+        refused(emit(broken(**{f"weight.{ch}": None})), "queue.weight plane is NULL")
+    refused(emit(q.q, c=None), "closure is NULL")
+    nc = capi_copy(s.c)
+    nc.N.z = None
+    refused(emit(q.q, c=C.byref(nc)), "wo/N/T plane is NULL")
+    nc = capi_copy(s.c)
+    nc.base_color.g = None
+    refused(emit(q.q, c=C.byref(nc)), "base_color planes must be all set or all NULL")
+    refused(emit(broken(capacity=n * spp_n * spp_n - 1)), "queue.capacity < n * spp_n^2")
+    refused(emit(broken(scratch=None)), "queue.scratch is NULL or smaller than rls_trace_scratch_bytes")
+    refused(emit(broken(scratch_bytes=T.scratch_bytes(n, spp_n) - 1)),
+            "queue.scratch is NULL or smaller than rls_trace_scratch_bytes")
+    # optional planes
+    assert emit(broken(point=None, sample=None)) == 0
+    assert lib.rls_trace_disney_emit(ctx.handle, n, C.byref(s.c), GLOSSY, spp_n, SEED, 0, C.byref(q.q), None) == 0
+    # n = 0: an empty queue, offsets[0] = 0 (no closure needed)
+    q0 = T.RayQueue(ctx, 0, spp_n, lobe=GLOSSY)
+    q0.offsets.fill_(-1)
+    assert emit(q0.q, nn=0, lobe=GLOSSY, c=None) == 0
+    assert q0.count == 0
+    # the Python layer: queues of another flavour, lobe, n or spp_n
+    with pytest.raises(ValueError):
+        T.disney_rays(s, GLOSSY, spp_n, SEED, queue=q)
+    with pytest.raises(ValueError):
+        T.disney_rays(s, DIFFUSE, spp_n + 1, SEED, queue=q)
+    with pytest.raises(ValueError):
+        T.disney_rays(s, DIFFUSE, spp_n, SEED, queue=T.RayQueue(ctx, n + 1, spp_n, lobe=DIFFUSE))
+    with pytest.raises(ValueError):
+        T.disney_rays(s, DIFFUSE, spp_n, SEED, queue=T.RayQueue(ctx, n, spp_n, False))
+    with pytest.raises(ValueError):
+        T.RayQueue(ctx, n, spp_n, lobe=0)
+    with pytest.raises(AttributeError):
+        q.avg_reflect_weight
+    with pytest.raises(AttributeError):
+        q.tir_fraction
+    with pytest.raises(AttributeError):
+        T.RayQueue(ctx, n, spp_n, False).valid_count
+    ctx.synchronize()
+
+
+def capi_copy(c):
+    return type(c).from_buffer_copy(c)
+
+
+# ---- 7. graph capture --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lobe", LOBES, ids=LOBE_IDS)
+def test_emit_and_resolve_in_a_graph(ctx, lobe):
+    import rlshaders_amd as R
+    T = _trace()
+    n, spp_n = 5000, 3
+    case, _ = _inputs("mixed", n)
+    gctx = R.Context(0, use_torch_stream=False)          # the context's own stream: the NULL stream cannot be captured
+    try:
+        s = _sampler(gctx, case)
+        torch.cuda.synchronize()
+        direct = T.disney_rays(s, lobe, spp_n, SEED)
+        gctx.synchronize()
+        cnt = direct.count
+        L = torch.from_numpy(_radiance(_host(direct.dir), np.arange(cnt))).cuda()
+        q = T.RayQueue(gctx, n, spp_n, lobe=lobe)
+        out = gctx.empty(3, n)
+        torch.cuda.synchronize()
+        want = _host(direct.resolve(L))
+        gctx.synchronize()
+        with gctx.capture() as g:
+            T.disney_rays(s, lobe, spp_n, SEED, queue=q)
+            q.resolve(L, out=out, count=cnt)
+        # recording runs nothing
+        out.zero_()
+        q.offsets.zero_()
+        q.side.zero_()
+        torch.cuda.synchronize()
+        g.launch()
+        gctx.synchronize()
+        g.close()
+        np.testing.assert_array_equal(_host(q.offsets), _host(direct.offsets))
+        cases.assert_same_bits(_host(q.dir), _host(direct.dir), "dir")
+        cases.assert_same_bits(_host(q.weight), _host(direct.weight), "weight")
+        cases.assert_same_bits(_host(q.valid_count), _host(direct.valid_count), "valid_count")
+        cases.assert_same_bits(_host(out), want, "resolve")
+    finally:
+        gctx.close()

@@ -1,13 +1,16 @@
-"""Timing of the caller-traced rlGgx integrators (rlshaders_amd/trace.py): emit and resolve of integrateGlossy and
-integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same batch in the same process.
+"""Timing of the caller-traced integrators (rlshaders_amd/trace.py): emit and resolve of rlGgx's integrateGlossy and
+integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same batch in the same process; with
+--closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch.
 
-    python tools/trace_bench.py [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
+    python tools/trace_bench.py [--closure ggx|disney] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
 emit writes 12 (dir) + 12 (weight; refraction 4) + 4 (point) + 1 (sample) [+ 1 (kind)] B per kept ray; with its staging it
 also writes 12 + 12 (4) + 2 B per sample and reads them back per kept ray (`*_with_staging`).  Resolve reads 12 (radiance) +
 12 (weight; refraction 4) B per ray and 8 B per point (offsets) and writes 12 B per point.  The radiance is uniform random.
+An rlDisney lobe is accounted as glossy (3 weight planes, no kind).  Its record has integrate_ms (both lobes in one call)
+and per lobe emit_over_integrate; "emits_over_integrate" is (emit_diffuse + emit_glossy) / integrate.
 """
 from __future__ import annotations
 
@@ -38,6 +41,56 @@ def timed(fn, repeats: int, warmup: int) -> float:
     return ms[len(ms) // 2]
 
 
+def rate(bytes_, ms):
+    return round(bytes_ / (ms * 1e-3) / 1e12, 4)
+
+
+def accounting(n: int, spp: int, rays: int, ms_emit: float, ms_res: float, refract: bool) -> dict:
+    """ms per call, rays per second and the algorithmic bytes of one emit and one resolve (module docstring)"""
+    wb = 4 if refract else 12
+    per_ray = 12 + wb + 4 + 1 + (1 if refract else 0)
+    emit_bytes = rays * per_ray
+    staging = n * spp * (12 + wb + 2) + rays * (12 + wb + 2) + n * spp * 2 + n * 8 * 4   # + tags read, offsets scan
+    res_bytes = rays * (12 + wb) + n * 8 + n * 12
+    return {
+        "emit_ms": round(ms_emit, 4), "resolve_ms": round(ms_res, 4),
+        "emit_rays_per_s": round(rays / (ms_emit * 1e-3), 1), "resolve_rays_per_s": round(rays / (ms_res * 1e-3), 1),
+        "emit_tb_per_s": rate(emit_bytes, ms_emit), "emit_tb_per_s_with_staging": rate(emit_bytes + staging, ms_emit),
+        "emit_frac_of_8tbps_with_staging": round(rate(emit_bytes + staging, ms_emit) / HBM_TBPS, 4),
+        "resolve_tb_per_s": rate(res_bytes, ms_res), "resolve_frac_of_8tbps": round(rate(res_bytes, ms_res) / HBM_TBPS, 4),
+    }
+
+
+def bench_disney(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """rlDisney (BASELINE config 3's inputs: every parameter U[0,1) per point): each lobe's emit and resolve against
+    rls_disney_integrate in reduced mode"""
+    import torch
+    import rlshaders_amd as R
+    from rlshaders_amd import trace as T
+    wo, N, T_ = R.gen_frame(ctx, seed, 0, n)
+    u = lambda stream: R.gen_uniform(ctx, seed, 0, n, stream)
+    base = torch.stack([u(8 + j) for j in range(3)])
+    d = R.DisneySampler(ctx, wo, N, T_, base_color=base, **{k: u(32 + j) for j, k in enumerate(R._capi.DISNEY_SCALARS)})
+    sums = d.integrate(spp_n, seed)
+    ms_int = timed(lambda: d.integrate(spp_n, seed, out=sums), args.repeats, args.warmup)
+    rec["integrate_ms"] = round(ms_int, 4)
+    out = ctx.empty(3, n)
+    emits = 0.0
+    for name, lobe in (("diffuse", R.RLS_RAY_DIFFUSE), ("glossy", R.RLS_RAY_GLOSSY)):
+        q = T.RayQueue(ctx, n, spp_n, lobe=lobe)
+        ms_emit = timed(lambda: T.disney_rays(d, lobe, spp_n, seed, queue=q), args.repeats, args.warmup)
+        rays = q.count
+        L = torch.rand(3, max(rays, 1), device=ctx.torch_device)
+        ms_res = timed(lambda: q.resolve(L, out=out, count=rays), args.repeats, args.warmup)
+        rec[name] = {"rays": rays, "rays_per_point": round(rays / n, 4)}
+        rec[name].update(accounting(n, spp_n * spp_n, rays, ms_emit, ms_res, False))
+        rec[name]["emit_over_integrate"] = round(ms_emit / ms_int, 4)
+        emits += ms_emit
+        del q, L
+        torch.cuda.empty_cache()
+    rec["emits_over_integrate"] = round(emits / ms_int, 4)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=24)
@@ -45,6 +98,7 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
+    ap.add_argument("--closure", choices=("ggx", "disney"), default="ggx")
     args = ap.parse_args()
     if args.repeats < 3:
         ap.error("--repeats must be at least 3")
@@ -58,17 +112,20 @@ def main() -> None:
     ctx.set_math_mode(args.fast)
     n, spp_n, seed = 1 << args.log2n, args.spp_n, 1234
     spp = spp_n * spp_n
+    rec = {"tool": "trace_bench", "n": n, "spp_n": spp_n, "math": "fast" if args.fast else "exact", "repeats": args.repeats,
+           "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
+    if args.closure == "disney":
+        rec["closure"] = "disney"
+        bench_disney(args, ctx, n, spp_n, seed, rec)
+        ctx.close()
+        print(json.dumps(rec), flush=True)
+        return
     wo, N, T_ = R.gen_frame(ctx, seed, 0, n)
     ks = torch.stack([R.gen_uniform(ctx, seed, 0, n, 10 + k) for k in range(3)])
     s = R.GgxSampler(ctx, wo, N, T_, specColor=ks, ior=R.gen_uniform(ctx, seed, 0, n, 13, 1.05, 2.55),
                      roughness=R.gen_uniform(ctx, seed, 0, n, 14, 0.05, 1.0), anisotropic=R.gen_aniso(ctx, seed, 0, n))
     out = ctx.empty(3, n)
     side = ctx.empty(n)
-    rec = {"tool": "trace_bench", "n": n, "spp_n": spp_n, "math": "fast" if args.fast else "exact", "repeats": args.repeats,
-           "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
-
-    def rate(bytes_, ms):
-        return round(bytes_ / (ms * 1e-3) / 1e12, 4)
 
     for lobe in ("glossy", "refract"):
         refract = lobe == "refract"
@@ -83,20 +140,9 @@ def main() -> None:
         rays = q.count
         L = torch.rand(3, max(rays, 1), device=ctx.torch_device)
         ms_res = timed(lambda: q.resolve(L, out=out, count=rays), args.repeats, args.warmup)
-        wb = 4 if refract else 12
-        per_ray = 12 + wb + 4 + 1 + (1 if refract else 0)
-        emit_bytes = rays * per_ray
-        staging = n * spp * (12 + wb + 2) + rays * (12 + wb + 2) + n * spp * 2 + n * 8 * 4   # + tags read, offsets scan
-        res_bytes = rays * (12 + wb) + n * 8 + n * 12
-        rec[lobe] = {
-            "rays": rays, "rays_per_point": round(rays / n, 4),
-            "integrate_ms": round(ms_int, 4), "emit_ms": round(ms_emit, 4), "resolve_ms": round(ms_res, 4),
-            "emit_rays_per_s": round(rays / (ms_emit * 1e-3), 1), "resolve_rays_per_s": round(rays / (ms_res * 1e-3), 1),
-            "emit_tb_per_s": rate(emit_bytes, ms_emit), "emit_tb_per_s_with_staging": rate(emit_bytes + staging, ms_emit),
-            "emit_frac_of_8tbps_with_staging": round(rate(emit_bytes + staging, ms_emit) / HBM_TBPS, 4),
-            "resolve_tb_per_s": rate(res_bytes, ms_res), "resolve_frac_of_8tbps": round(rate(res_bytes, ms_res) / HBM_TBPS, 4),
-            "emit_over_integrate": round(ms_emit / ms_int, 4),
-        }
+        rec[lobe] = {"rays": rays, "rays_per_point": round(rays / n, 4), "integrate_ms": round(ms_int, 4)}
+        rec[lobe].update(accounting(n, spp, rays, ms_emit, ms_res, refract))
+        rec[lobe]["emit_over_integrate"] = round(ms_emit / ms_int, 4)
         del q, L
         torch.cuda.empty_cache()
     ctx.close()
