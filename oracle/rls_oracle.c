@@ -1440,6 +1440,11 @@ void orc_sample_02(uint32_t seed, uint64_t index, uint32_t dim_pair, uint32_t s,
     *ry = (float)((sobol2(s) ^ sy) >> 8) * (1.0f / 16777216.0f);
 }
 
+void orc_batch_sample_02(uint32_t seed, uint64_t first_index, int64_t n, uint32_t dim_pair, uint32_t s, float *rx, float *ry)
+{
+    for (int64_t i = 0; i < n; i++) orc_sample_02(seed, first_index + (uint64_t)i, dim_pair, s, rx + i, ry + i);
+}
+
 typedef struct {
     const orc_ggx_soa *gin; const orc_disney_soa *din; int spp; uint32_t seed; uint64_t first; int64_t n;
     orc_v3p sum, sum2; float *avg, *cnt, *cnt2; orc_v3p s_wi, s_f; float *s_pdf;

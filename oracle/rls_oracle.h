@@ -288,6 +288,8 @@ void orc_batch_skin(int64_t n, const orc_skin_soa *in, const orc_skin_out_soa *o
  * callback triple (explicit form: src/rlDisney.cpp:299-312), samples from the per-point scrambled
  * (0,2)-sequence below (stand-in for the closed AiSampler(n,2)); sums in ascending sample order. */
 void orc_sample_02(uint32_t seed, uint64_t index, uint32_t dim_pair, uint32_t s, float *rx, float *ry);
+/* sample s of points first_index .. first_index + n - 1: orc_sample_02 per point */
+void orc_batch_sample_02(uint32_t seed, uint64_t first_index, int64_t n, uint32_t dim_pair, uint32_t s, float *rx, float *ry);
 /* first_index: global index of point 0 (scrambles hash first_index + i) */
 void orc_batch_ggx_integrate(int64_t n, const orc_ggx_soa *in, int spp_n, uint32_t seed, uint64_t first_index,
                              orc_v3p sum_f_over_pdf, float *avg_reflect_weight, int nthreads);

@@ -622,6 +622,14 @@ def sample_02(seed, index, dim_pair, s):
     return rx.value, ry.value
 
 
+def batch_sample_02(seed, first, n, dim_pair, s):
+    """sample s of points first .. first + n - 1 (orc_batch_sample_02) -> (rx [n], ry [n])"""
+    rx, ry = np.empty(n, np.float32), np.empty(n, np.float32)
+    lib().orc_batch_sample_02(C.c_uint32(seed), C.c_uint64(first), C.c_int64(n), C.c_uint32(dim_pair), C.c_uint32(s),
+                              _p(rx), _p(ry))
+    return rx, ry
+
+
 # ------------------------------------------------------------------------------------------------
 def gen_frame(seed, first, n):
     wo, N, T = (np.empty((3, n), np.float32) for _ in range(3))

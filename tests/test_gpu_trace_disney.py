@@ -14,7 +14,8 @@ import pytest
 import torch
 
 import cases
-import oracle_lib as O
+from trace_util import disney_inputs as _inputs, disney_oracle_queue as _oracle_queue, radiance as _radiance, \
+    sequential as _sequential
 
 pytestmark = pytest.mark.gpu
 
@@ -64,35 +65,6 @@ def _sampler(ctx, case, materials=None):
     sc = {k: _dev(case[k]) for k in R._capi.DISNEY_SCALARS if k in case}
     return R.DisneySampler(ctx, _dev(case["wo"]), _dev(case["N"]), _dev(case["T"]),
                            base_color=_dev(case.get("base_color", (1.0, 1.0, 1.0))), materials=materials, **sc)
-
-
-def _inputs(kind, n):
-    """(case dict for the sampler, materials or None)"""
-    if kind == "mixed":
-        return cases.disney_mixed(cases.SEED_PARITY, n), None
-    if kind.startswith("preset:"):
-        wo, N, T = cases.frame(cases.SEED_PARITY, n)
-        return dict(wo=wo, N=N, T=T, **cases.DISNEY_PRESETS[kind[7:]]), None
-    if kind == "uniform":
-        wo, N, T = cases.frame(cases.SEED_PARITY, n)
-        return dict(wo=wo, N=N, T=T, base_color=(0.8, 0.5, 0.3), subsurface=0.1, metallic=0.2, specular=0.5,
-                    specular_tint=0.1, roughness=0.35, anisotropic=0.3, sheen=0.2, sheen_tint=0.5, clearcoat=0.3,
-                    clearcoat_gloss=0.6), None
-    if kind == "materials":
-        m = 7
-        cols = cases.disney_mixed(cases.SEED_PARITY + 1, m)
-        wo, N, T = cases.frame(cases.SEED_PARITY, n)
-        ids = (O.gen_uniform(cases.SEED_PARITY, 0, n, 77) * m).astype(np.uint32) % m
-        case = dict(cols, wo=wo, N=N, T=T)
-        return case, (torch.from_numpy(ids.astype(np.int32)).cuda(), m)
-    if kind == "rare":
-        # the specular lobe's packed rare branches with every lane asking (test_gpu_disney_config3.py,
-        # test_packed_rare_branches_with_every_lane_asking): views along the normal take the uniform-slope fallback,
-        # clearcoat = 1 sends samples to the clearcoat half vector
-        wo, N, T = cases.frame(cases.SEED_PARITY, n)
-        c = cases.disney_mixed(cases.SEED_PARITY, n)
-        return dict(c, wo=N.copy(), N=N, T=T, clearcoat=np.ones(n, np.float32)), None
-    raise KeyError(kind)
 
 
 KINDS = ["mixed", "uniform", "materials", "rare"] + [f"preset:{k}" for k in cases.DISNEY_PRESETS]
@@ -172,32 +144,6 @@ def test_queue_matches_the_streamed_integrator(ctx, kind, spp_n, fast):
 
 
 # ---- 3. the queue against the oracle ---------------------------------------------------------------------------------------
-def _oracle_queue(case, spp_n, seed, lobe, first=0):
-    """the queue composed on the CPU: per sample s the scrambled (0,2) point (orc_sample_02, dimension pair 0 for the
-    diffuse lobe, 1 for the specular one) and the oracle closure's sample / eval / pdf triple for the lobe; kept where
-    pdf > 1e-4 and f / pdf is not all zero -> dict of the flattened point-major queue and the offsets"""
-    from gpu_util import disney_oracle
-    n, spp = case["wo"].shape[1], spp_n * spp_n
-    od = disney_oracle(O, case)
-    pair = 0 if lobe == DIFFUSE else 1
-    dirs, ws, keep = [], [], []
-    for s in range(spp):
-        rx = np.empty(n, np.float32)
-        ry = np.empty(n, np.float32)
-        for i in range(n):
-            rx[i], ry[i] = O.sample_02(seed, first + i, pair, s)
-        wi, f, pdf = od.sample_eval_pdf(lobe, rx, ry)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            t = (f / pdf[None, :]).astype(np.float32)
-        dirs.append(wi); ws.append(t); keep.append((pdf > EPS) & ~np.all(t == 0.0, axis=0))
-    keep = np.stack(keep, axis=1)                                   # [n, spp]
-    sel = keep.reshape(-1)
-    flat = lambda a: np.stack(a, axis=2).reshape(a[0].shape[0], -1)[:, sel]
-    pts, smp = np.meshgrid(np.arange(n), np.arange(spp), indexing="ij")
-    return dict(dir=flat(dirs), weight=flat(ws), point=pts.reshape(-1)[sel], sample=smp.reshape(-1)[sel],
-                offsets=np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int64))
-
-
 @pytest.mark.parametrize("lobe", LOBES, ids=LOBE_IDS)
 @pytest.mark.parametrize("kind,spp_n", [("mixed", 4), ("rare", 3), ("preset:0006_rough_metallic", 2)])
 def test_queue_matches_the_oracle(ctx, kind, spp_n, lobe):
@@ -220,28 +166,6 @@ def test_queue_matches_the_oracle(ctx, kind, spp_n, lobe):
 
 
 # ---- 4. a radiance that varies -----------------------------------------------------------------------------------------------
-def _radiance(d, k):
-    """a deterministic float32 sky: a function of the direction and of the ray index"""
-    d = d.astype(np.float32)
-    k = k.astype(np.float32)
-    r = np.float32(0.25) + np.float32(0.75) * np.maximum(d[2], np.float32(0.0))
-    g = np.float32(1.0) + np.float32(0.5) * d[0] * d[1]
-    b = np.float32(0.5) + np.float32(1e-3) * np.mod(k, np.float32(97.0))
-    return np.stack([r, g, b]).astype(np.float32)
-
-
-def _sequential(L, w, offsets):
-    """float32 sum per point over its rays in queue order (sum += L * w)"""
-    n = len(offsets) - 1
-    cnt = np.diff(offsets)
-    acc = np.zeros((3, n), np.float32)
-    prod = (L * w).astype(np.float32)
-    for j in range(int(cnt.max()) if n else 0):
-        m = cnt > j
-        acc[:, m] = acc[:, m] + prod[:, offsets[:-1][m] + j]
-    return acc
-
-
 @pytest.mark.parametrize("lobe", LOBES, ids=LOBE_IDS)
 def test_varying_radiance(ctx, lobe):
     T = _trace()

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 import cases
-import oracle_lib as O
+from trace_util import ggx_inputs as _inputs, ggx_oracle_queue as _oracle_queue, radiance as _radiance, \
+    sequential as _sequential
 
 pytestmark = pytest.mark.gpu
 
@@ -43,38 +44,11 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda() if isinstance(a, np.ndarray) else a
 
 
-def _exiting(n):
-    return (np.arange(n) % 5 == 3).astype(np.uint8)
-
-
 def _sampler(ctx, case, exiting=None, materials=None):
     import rlshaders_amd as R
     return R.GgxSampler(ctx, _dev(case["wo"]), _dev(case["N"]), _dev(case["T"]), specColor=_dev(case["KsColor"]),
                         ior=_dev(case["ior"]), roughness=_dev(case["roughness"]), anisotropic=_dev(case["anisotropic"]),
                         exiting=None if exiting is None else torch.from_numpy(exiting).cuda(), materials=materials)
-
-
-def _inputs(kind, n):
-    """(case dict for the sampler, exiting or None, materials or None)"""
-    if kind == "mixed":
-        return cases.ggx_mixed(cases.SEED_PARITY, n), None, None
-    if kind == "edge":
-        return cases.ggx_edge(cases.SEED_EDGE, n), _exiting(n), None
-    if kind.startswith("preset:"):
-        wo, N, T = cases.frame(cases.SEED_PARITY, n)
-        return dict(wo=wo, N=N, T=T, **cases.GGX_PRESETS[kind[7:]]), None, None
-    if kind == "uniform":
-        wo, N, T = cases.frame(cases.SEED_PARITY, n)
-        return dict(wo=wo, N=N, T=T, KsColor=(0.9, 0.6, 0.3), roughness=0.4, ior=1.6, anisotropic=0.5), _exiting(n), None
-    if kind == "materials":
-        m = 7
-        cols = cases.ggx_mixed(cases.SEED_PARITY + 1, m)
-        wo, N, T = cases.frame(cases.SEED_PARITY, n)
-        ids = (O.gen_uniform(cases.SEED_PARITY, 0, n, 77) * m).astype(np.uint32) % m
-        case = dict(wo=wo, N=N, T=T, KsColor=cols["KsColor"], roughness=cols["roughness"], ior=cols["ior"],
-                    anisotropic=cols["anisotropic"])
-        return case, None, (torch.from_numpy(ids.astype(np.int32)).cuda(), m)
-    raise KeyError(kind)
 
 
 KINDS = ["mixed", "edge", "uniform", "materials"] + [f"preset:{k}" for k in cases.GGX_PRESETS]
@@ -107,35 +81,6 @@ def test_unit_radiance_is_the_integrator_bit_for_bit(ctx, spp_n, fast):
 
 
 # ---- 2. the queue against the oracle ---------------------------------------------------------------------------------------
-def _oracle_queue(case, exiting, spp_n, seed, refract, first=0):
-    """the queue composed on the CPU: per sample s the scrambled (0,2) point (orc_sample_02, dim pair 0), the oracle closure's
-    evalSample / evalBrdf / evalPdf (glossy: weight f/pdf) or refract sample (weight, refracted flag); kept unless the weight
-    is zero.  -> dict of the flattened point-major queue and the offsets"""
-    from gpu_util import ggx_oracle
-    n, spp = case["wo"].shape[1], spp_n * spp_n
-    og = ggx_oracle(O, case, exiting=exiting)
-    dirs, ws, keep, kinds = [], [], [], []
-    for s in range(spp):
-        rx = np.empty(n, np.float32)
-        ry = np.empty(n, np.float32)
-        for i in range(n):
-            rx[i], ry[i] = O.sample_02(seed, first + i, 0, s)
-        if refract:
-            wt, w, flag = og.refract(rx, ry)
-            dirs.append(wt); ws.append(w[None, :]); keep.append(w != 0.0); kinds.append(np.where(flag != 0, 0, 1))
-        else:
-            wi, f, pdf, _ = og.sample_eval_pdf(rx, ry)
-            t = (f / pdf[None, :]).astype(np.float32)
-            dirs.append(wi); ws.append(t); keep.append(~np.all(t == 0.0, axis=0)); kinds.append(np.zeros(n, np.int64))
-    keep = np.stack(keep, axis=1)                                   # [n, spp]
-    sel = keep.reshape(-1)
-    flat = lambda a: np.stack(a, axis=2).reshape(a[0].shape[0], -1)[:, sel]     # [c, n*spp] point-major -> kept
-    pts, smp = np.meshgrid(np.arange(n), np.arange(spp), indexing="ij")
-    return dict(dir=flat(dirs), weight=flat(ws), point=pts.reshape(-1)[sel], sample=smp.reshape(-1)[sel],
-                kind=np.stack(kinds, axis=1).reshape(-1)[sel],
-                offsets=np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int64))
-
-
 @pytest.mark.parametrize("refract", [False, True], ids=["glossy", "refract"])
 @pytest.mark.parametrize("kind,spp_n", [("mixed", 4), ("edge", 3), ("preset:0002_gold", 2)])
 def test_queue_matches_the_oracle(ctx, kind, spp_n, refract):
@@ -164,30 +109,6 @@ def test_queue_matches_the_oracle(ctx, kind, spp_n, refract):
 
 
 # ---- 3. a radiance that varies -----------------------------------------------------------------------------------------------
-def _radiance(d, k):
-    """a deterministic float32 sky: a function of the direction and of the ray index"""
-    d = d.astype(np.float32)
-    k = k.astype(np.float32)
-    r = np.float32(0.25) + np.float32(0.75) * np.maximum(d[2], np.float32(0.0))
-    g = np.float32(1.0) + np.float32(0.5) * d[0] * d[1]
-    b = np.float32(0.5) + np.float32(1e-3) * np.mod(k, np.float32(97.0))
-    return np.stack([r, g, b]).astype(np.float32)
-
-
-def _sequential(L, w, offsets, inv=None):
-    """float32 sum per point over its rays in queue order (sum += L * w), times inv afterwards"""
-    n = len(offsets) - 1
-    cnt = np.diff(offsets)
-    acc = np.zeros((3, n), np.float32)
-    prod = (L * w).astype(np.float32)
-    for j in range(int(cnt.max()) if n else 0):
-        m = cnt > j
-        acc[:, m] = acc[:, m] + prod[:, offsets[:-1][m] + j]
-    if inv is not None:
-        acc = acc * np.float32(inv)
-    return acc
-
-
 @pytest.mark.parametrize("refract", [False, True], ids=["glossy", "refract"])
 def test_varying_radiance(ctx, refract):
     T = _trace()

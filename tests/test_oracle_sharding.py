@@ -43,3 +43,17 @@ def test_oracle_integrators_shard_by_first_index():
               for sl in parts]
     for j in range(2):
         assert np.array_equal(np.concatenate([p[j] for p in pieces], axis=-1).view(np.uint32), whole[j].view(np.uint32))
+
+
+def test_batch_sample_02_is_the_scalar_call():
+    """orc_batch_sample_02 (the trace tests' per-sample oracle queues) draws what orc_sample_02 draws point by point,
+    including first indices that straddle and pass the 32-bit split of the scramble hash"""
+    for first in (0, 12345, (1 << 32) - 40, (1 << 33) + 17):
+        for pair in (0, 1, 3):
+            for s in (0, 1, 7, 255):
+                rx, ry = O.batch_sample_02(4242, first, 100, pair, s)
+                want = np.array([O.sample_02(4242, first + i, pair, s) for i in range(100)], np.float32).T
+                assert np.array_equal(rx.view(np.uint32), want[0].view(np.uint32)), (first, pair, s)
+                assert np.array_equal(ry.view(np.uint32), want[1].view(np.uint32)), (first, pair, s)
+    rx, ry = O.batch_sample_02(4242, 0, 0, 0, 0)
+    assert rx.size == 0 and ry.size == 0
