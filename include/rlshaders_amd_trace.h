@@ -1,12 +1,13 @@
 /*
- * rlshaders_amd_trace.h -- caller-traced rlGgx and rlDisney integrators (companion library librls_trace.so).
+ * rlshaders_amd_trace.h -- caller-traced rlGgx, rlDisney and rlSss integrators (companion library librls_trace.so).
  *
  * The reference traces inside its integrators: integrateGlossy hands the callback triple to AiBRDFIntegrate, which
  * traces one glossy ray per sample (src/rlGgx.h:172-179), integrateRefract calls AiTrace per sample
  * (src/rlGgx.h:228-244), and rlDisney's integrateDiffuse / integrateGlossy hand theirs to AiBRDFIntegrate with
  * AI_RAY_DIFFUSE / AI_RAY_GLOSSY (src/rlDisney.cpp:240-243, 279-283).  rls_ggx_integrate / rls_ggx_integrate_refract /
  * rls_disney_integrate stand in for those rays with a uniform environment.  The calls below cut each integrator at the
- * point where the reference traces, so that a renderer can trace with its own tracer:
+ * point where the reference traces, so that a renderer can trace with its own tracer (rlSss's integrateScatter, whose
+ * probe rays return hits rather than a radiance, has calls of its own: see the rlSss section below):
  *
  *   1. emit:    every sample ray of the n^2-spp loop goes into a compacted, deterministic queue
  *               (direction, weight, point, sample[, kind]);
@@ -92,6 +93,72 @@ rls_status rls_trace_ggx_glossy_resolve(rls_context *ctx, int64_t n, const rls_r
  * radiance[k] * weight[k]) * (1 / spp_n^2), the AiSamplerGetSampleInvCount normalisation. */
 rls_status rls_trace_ggx_refract_resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, int spp_n,
                                          rls_crgb radiance, rls_rgb result);
+
+/* ------------------------------------------------------------------------------------------
+ * rlSss: SssSampler::integrateScatter (src/rlSss.h:167-280) cut where the reference traces its probe rays.
+ *
+ *   1. rls_trace_sss_probe_emit: one probe ray per sample (getProbeRay, src/rlSss.h:487-533) into a DENSE queue:
+ *      ray j = i * spp_n^2 + s is sample s of point i.  Nothing is dropped -- a probe ray's contribution is not known
+ *      before its hits are -- so offsets[i] = i * spp_n^2 and no scratch is needed.
+ *   2. The renderer's part, per probe ray:
+ *        - walk the ray as traceProbe does (src/rlSss.h:293-356): every hit along the ray up to maxdist, in ascending
+ *          t, at most max_hits of them; the distance of a hit is the cumulative one along the ORIGINAL ray (0 < t <=
+ *          maxdist), continued past each hit;
+ *        - skip hits on other objects than the shading point's own (the probe's object test);
+ *        - report sg->Ns at the hit aligned to sg->N as shadeProbeSample does (alignDir, src/rlSss.h:393-398);
+ *        - evaluate its light loop at the hit (and, optionally, integrateDiffuse, src/rlSss.h:456-484) and report
+ *          E = direct + indirect / pi: the irradiance BEFORE evalProfile and the cavity fade.
+ *      The reference computes (direct * profile + indirect * profile) * fade; with one E it is (E * profile) * fade.
+ *      With an indirect term of 0 the two are the same; otherwise they may differ by one rounding.
+ *   3. rls_trace_sss_scatter_resolve: per point, the hits combined exactly as the integrator combines its own: the
+ *      duplicate-hit test, the radius cut-off, the cavity fade, the shaded-hit count, evalProfile and the three-axis MIS
+ *      pdf (src/rlSss.h:246-268, 316-317, 379-420), summed in sample order and, within a sample, in hit order.
+ *
+ * The samples are exactly those the analytic integrator (rls_sss_integrate_scatter in rlshaders_amd.h) draws: same seed,
+ * first_index, scrambled (0,2)-sequence, math mode of the context.  Trace its queue against the integrator's plane or
+ * sphere, report E = light_color * (AI_ONEOVERPI * max(0, N.L)) (0 where the gate is shut), and the resolve returns that
+ * integrator's result and mean_depth bit for bit.
+ * ---------------------------------------------------------------------------------------- */
+
+/* the deepest probe walk the resolve takes: kMaxProbeDepth, src/rlSss.h:105 */
+#define RLS_MAX_PROBE_HITS 12
+
+typedef struct rls_probe_queue {
+    int64_t capacity;      /* rays every per-ray plane holds; must be >= n * spp_n^2 */
+    int64_t *offsets;      /* [n + 1], required: CSR like rls_ray_queue; here offsets[i] = i * spp_n^2 */
+    rls_vec3 origin;       /* [capacity] x 3, required: sg->P + getProbeRay's offset (src/rlSss.h:487-533) */
+    rls_vec3 dir;          /* [capacity] x 3, required: the probe direction (one of -N, U, V of the point's frame) */
+    float *maxdist;        /* [capacity], required: ray.maxdist */
+    uint32_t *point;       /* [capacity], NULL-able: the point's index in this call (0 .. n-1) */
+    uint8_t *sample;       /* [capacity], NULL-able: the sample's index s in [0, spp_n^2) */
+} rls_probe_queue;
+
+typedef struct rls_probe_hits {
+    int max_hits;          /* 1 .. RLS_MAX_PROBE_HITS: the hit slots per ray */
+    int64_t stride;        /* >= n * spp_n^2: hit k of ray j is element k * stride + j of the planes below, which hold
+                              max_hits * stride floats each */
+    const uint8_t *count;  /* [n * spp_n^2], required: the hits reported for ray j; values above max_hits read as max_hits */
+    rls_cvec3 P;           /* required: the hit position, ascending t along the ray */
+    rls_cvec3 N;           /* required: sg->Ns at the hit, aligned to sg->N */
+    rls_crgb irradiance;   /* required: E, before evalProfile and the cavity fade (see above) */
+} rls_probe_hits;
+
+/* getProbeRay for every sample of integrateScatter's loop (src/rlSss.h:224-228): per point the closure's profile and frame
+ * (N, T, has_dPdu as the integrator reads them), P = sg->P.  Writes offsets, origin, dir, maxdist and, where given, point
+ * and sample for all n * spp_n^2 rays, point-major with samples ascending.  Never synchronises the host. */
+rls_status rls_trace_sss_probe_emit(rls_context *ctx, int64_t n, const rls_sss_closure *c, rls_cvec3 P, int spp_n,
+                                    uint32_t seed, uint64_t first_index, const rls_probe_queue *q);
+
+/* integrateScatter's combination of the renderer's hits (src/rlSss.h:245-279).  c, P, spp_n: those of the emit; q: its
+ * queue (only the capacity is read: the hits are indexed by ray).  Per point, with prev = P at the start of every ray and
+ * the hits visited in reported order: a hit is skipped unless |prev - hit| > AI_EPSILON, then prev = hit; d = hit - P,
+ * skipped if |d| > maxRadius; the cavity fade where use_cavity_fade is set, skipped unless fade > AI_EPSILON; counted as
+ * shaded; irr = (E * profile(|d|)) * fade per channel, skipped if 0 in all three; sum += irr / mis_pdf(d, N) (literal_matrix
+ * as in the MIS pdf call of rlshaders_amd.h).  result = (sss_color * sum) * (1 / spp_n^2); mean_depth (NULL-able) = shaded
+ * hits / spp_n^2. */
+rls_status rls_trace_sss_scatter_resolve(rls_context *ctx, int64_t n, const rls_sss_closure *c, rls_cvec3 P, int spp_n,
+                                         const rls_probe_queue *q, const rls_probe_hits *h, int use_cavity_fade,
+                                         int literal_matrix, rls_rgb result, float *mean_depth);
 
 #ifdef __cplusplus
 }

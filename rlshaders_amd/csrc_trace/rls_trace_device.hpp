@@ -59,6 +59,37 @@ struct TraceResolveIO {
     int64_t n;
 };
 
+// rlSss: the probe-ray emit and the scatter resolve.  Both walk tiles of `tile_points` consecutive points: ray j = i * spp + s
+// of the dense queue is ray j - p0 * spp of the tile that starts at point p0.  The emit takes up to kSssEmitRays rays per
+// tile (several per thread), the resolve up to kBlock (one per thread: its LDS holds the terms of every hit of the tile).
+struct SssEmitIO {
+    rls_sss_closure c;
+    rls_cvec3 P;
+    rls_probe_queue q;
+    int64_t n;
+    int spp;
+    int tile_points;
+    uint32_t seed;
+    uint64_t first;
+};
+
+struct SssResolveIO {
+    rls_sss_closure c;
+    rls_cvec3 P;
+    rls_probe_hits h;
+    rls_rgb result;
+    float *depth;            // mean_depth, NULL-able
+    int64_t n;
+    int spp;
+    int tile_points;
+    int cavity, literal;
+};
+
+constexpr int kSssEmitRays = 4 * rlsh::kBlock;
+constexpr int kSssEmitPoints = rlsh::kBlock;       // (one thread per point computes the point's part)
+inline int sss_emit_tile_points(int spp) { return kSssEmitRays / spp < kSssEmitPoints ? kSssEmitRays / spp : kSssEmitPoints; }
+inline int sss_resolve_tile_points(int spp) { return spp >= rlsh::kBlock ? 1 : rlsh::kBlock / spp; }
+
 // Rank of this lane's sample among the kept samples of its point, in sample order.  The G lanes of a group hold G
 // consecutive samples (lane `sub` the sub-th); `run` counts the kept samples of the group's earlier rounds and is advanced
 // past this round.  Every lane of the wavefront calls it (ballot).

@@ -1,7 +1,9 @@
-// trace.hip -- caller-traced rlGgx and rlDisney integrators (include/rlshaders_amd_trace.h): integrateGlossy and
+// trace.hip -- caller-traced rlGgx, rlDisney and rlSss integrators (include/rlshaders_amd_trace.h): integrateGlossy and
 // integrateRefract's traced branch (src/rlGgx.h:172-184, 228-244), rlDisney's integrateDiffuse / integrateGlossy
 // (src/rlDisney.cpp:240-243, 279-283) cut where the reference traces, into an emit of every sample ray and a resolve of
-// the radiance the caller traced for them.
+// the radiance the caller traced for them; rlSss's integrateScatter (src/rlSss.h:167-280) into an emit of every probe ray
+// (sss_probe_emit_kernel, a dense queue: no scan, no compaction) and a resolve of the hits the caller's probe walk
+// reports (sss_scatter_resolve_kernel).
 //
 // Emit, three steps on the context's stream:
 //   1. ggx_{glossy,refract}_emit_kernel, disney_{diffuse,specular}_emit_kernel: the sample loop of rls_ggx_integrate /
@@ -272,6 +274,153 @@ __global__ RLS_INT_ATTR void disney_specular_emit_kernel(DisneyEmitIO a)
     disney_emit_body<G, 1, FAST_MATH>(a, &slow);
 }
 
+// integrateScatter's probe rays (getProbeRay, src/rlSss.h:224-228) into the dense queue.  Per tile the points' profile,
+// frame, position and scrambles are computed once, by one thread each, into LDS; then each thread takes rays threadIdx.x,
+// threadIdx.x + kBlock, ... of the tile, draws the sample and the probe ray as scatter_loop does and stores the ray at
+// j = p0 * spp + its place in the tile: the tile's rays are one contiguous range of every plane.
+constexpr int kEmitWords = 19;               // d[3], c1[3], c2[3], maxR, U, V, N (nd_radius reads d, c1, c2, maxR only)
+template <int FAST_MATH = RLS_FAST>
+__global__ __launch_bounds__(rlsh::kBlock) void sss_probe_emit_kernel(SssEmitIO a)
+{
+    __shared__ uint32_t tab[2][kMaxSpp];
+    __shared__ float pt[kEmitWords][kSssEmitPoints];
+    __shared__ float po[3][kSssEmitPoints];
+    __shared__ uint32_t scr[2][kSssEmitPoints];
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    const int P = a.tile_points, t = (int)threadIdx.x;
+    const int64_t tiles = (a.n + P - 1) / P;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t p0 = tile * P;
+        const int pc = a.n - p0 < P ? (int)(a.n - p0) : P;
+        __syncthreads();                                         // the previous tile's points are consumed
+        if (t < pc) {
+            const int64_t i = p0 + t;
+            const rls_sss_closure &c = a.c;
+            const PIndex<int64_t> pk = pindex(c.materials, i);
+            const NdProfile p = scatter_profile(c, pk);
+            const Frame fr = sss_frame(ld3(c.N, i), ld3(c.T, i), c.has_dPdu != 0);
+            const V3 Po = ld3(a.P, i);
+            for (int k = 0; k < 3; k++) { pt[k][t] = p.d[k]; pt[3 + k][t] = p.c1[k]; pt[6 + k][t] = p.c2[k]; }
+            pt[9][t] = p.maxR;
+            pt[10][t] = fr.U.x; pt[11][t] = fr.U.y; pt[12][t] = fr.U.z;
+            pt[13][t] = fr.V.x; pt[14][t] = fr.V.y; pt[15][t] = fr.V.z;
+            pt[16][t] = fr.N.x; pt[17][t] = fr.N.y; pt[18][t] = fr.N.z;
+            po[0][t] = Po.x; po[1][t] = Po.y; po[2][t] = Po.z;
+            scr[0][t] = hash_u32(a.seed, a.first + (uint64_t)i, kScrambleStream);
+            scr[1][t] = hash_u32(a.seed, a.first + (uint64_t)i, kScrambleStream + 1);
+            a.q.offsets[i] = i * a.spp;
+            if (i == a.n - 1) a.q.offsets[a.n] = a.n * a.spp;
+        }
+        __syncthreads();
+        for (int u = t; u < pc * a.spp; u += rlsh::kBlock) {
+            const int lp = u / a.spp, s = u - lp * a.spp;
+            NdProfile p = {};
+            for (int k = 0; k < 3; k++) { p.d[k] = pt[k][lp]; p.c1[k] = pt[3 + k][lp]; p.c2[k] = pt[6 + k][lp]; }
+            p.maxR = pt[9][lp];
+            Frame fr;
+            fr.U = mk(pt[10][lp], pt[11][lp], pt[12][lp]);
+            fr.V = mk(pt[13][lp], pt[14][lp], pt[15][lp]);
+            fr.N = mk(pt[16][lp], pt[17][lp], pt[18][lp]);
+            const float rx = bits_u01(tab[0][s] ^ scr[0][lp]);
+            const float ry = bits_u01(tab[1][s] ^ scr[1][lp]);
+            V3 off, dir;
+            float maxdist;
+            sss_probe_ray(p, fr, rx, ry, off, dir, maxdist);                 // :228
+            const V3 O = mk(po[0][lp], po[1][lp], po[2][lp]) + off;
+            const int64_t j = p0 * a.spp + u;
+            const rls_probe_queue &q = a.q;
+            stg(q.origin.x, j, O.x); stg(q.origin.y, j, O.y); stg(q.origin.z, j, O.z);
+            stg(q.dir.x, j, dir.x); stg(q.dir.y, j, dir.y); stg(q.dir.z, j, dir.z);
+            stg(q.maxdist, j, maxdist);
+            if (q.point) q.point[j] = (uint32_t)(p0 + lp);
+            if (q.sample) q.sample[j] = (uint8_t)s;
+        }
+    }
+}
+
+// integrateScatter's combination (src/rlSss.h:245-279) of the hits the caller traced.  Per tile: one thread per ray walks
+// the ray's hits as scatter_loop walks the analytic ones -- duplicate test, radius cut-off, cavity fade, shaded count,
+// evalProfile, the MIS pdf -- and leaves each hit's term irr / pdf (+0 for a skipped hit) in LDS; then one thread per point
+// adds its rays' terms in sample order and, within a sample, in hit order: the order of the integrator's running sums.  The
+// per-point profile and frame are recomputed per ray (the same arithmetic as the integrator's, so the same bits): staged in
+// LDS instead, once per point, the kernel ran slower at 2^22 points x 16 rays (2.90 against 2.44 ms; 47 KB of LDS, three
+// workgroups per CU instead of four).
+template <int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void sss_scatter_resolve_kernel(SssResolveIO a)
+{
+    __shared__ float term[RLS_MAX_PROBE_HITS][3][rlsh::kBlock];
+    __shared__ uint8_t slots[rlsh::kBlock];        // the ray's hit slots: min(count, max_hits)
+    __shared__ uint8_t shaded[rlsh::kBlock];
+    stage_libm_tables();
+    const int P = a.tile_points, t = (int)threadIdx.x;
+    const int64_t tiles = (a.n + P - 1) / P;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t p0 = tile * P;
+        const int pc = a.n - p0 < P ? (int)(a.n - p0) : P;
+        __syncthreads();                                         // the previous tile's terms are consumed
+        if (t < pc * a.spp) {
+            const int lp = t / a.spp;
+            const int64_t i = p0 + lp, j = p0 * a.spp + t;
+            const SssResolveIO al = RLS_INT_ARGS(a);
+            const rls_sss_closure &c = al.c;
+            const rls_probe_hits &h = al.h;
+            const PIndex<int64_t> pk = pindex(c.materials, i);
+            const NdProfile p = scatter_profile(c, pk);
+            const Frame fr = sss_frame(ld3(c.N, i), ld3(c.T, i), c.has_dPdu != 0);
+            const V3 Po = ld3(al.P, i);
+            const int cnt = h.count[j] < h.max_hits ? (int)h.count[j] : h.max_hits;
+            V3 prev = Po;
+            int sh = 0;
+            for (int k = 0; k < cnt; k++) {
+                const int64_t at = (int64_t)k * h.stride + j;
+                const V3 hp = ld3(h.P, at), hn = ld3(h.N, at);
+                const float eR = ldg(h.irradiance.r, at), eG = ldg(h.irradiance.g, at), eB = ldg(h.irradiance.b, at);
+                float tR = 0.0f, tG = 0.0f, tB = 0.0f;
+                if (length(prev - hp) > kEps) {                                  // :316-317
+                    prev = hp;
+                    // shadeProbeSample, :379-420
+                    const V3 d = hp - Po;
+                    const float r = length(d);
+                    if (!(r > p.maxR)) {
+                        float fade = 1.0f;
+                        if (al.cavity) fade = sss_cavity_fade(d, r, hn, fr.N);
+                        if (fade > kEps) {
+                            sh++;
+                            float pr, pg, pb;
+                            nd_profile(p, r, pr, pg, pb);
+                            const float iR = eR * pr * fade, iG = eG * pg * fade, iB = eB * pb * fade;
+                            if (!(iR == 0.0f && iG == 0.0f && iB == 0.0f)) {            // :249
+                                const float pdf = sss_mis_pdf(p, fr, d, hn, al.literal != 0);
+                                tR = R_DIV(iR, pdf); tG = R_DIV(iG, pdf); tB = R_DIV(iB, pdf);
+                            }
+                        }
+                    }
+                }
+                term[k][0][t] = tR; term[k][1][t] = tG; term[k][2][t] = tB;
+            }
+            slots[t] = (uint8_t)cnt;
+            shaded[t] = (uint8_t)sh;
+        }
+        __syncthreads();
+        if (t < pc) {
+            const int64_t i = p0 + t;
+            float accR = 0.0f, accG = 0.0f, accB = 0.0f, accD = 0.0f;
+            for (int s = 0, r = t * a.spp; s < a.spp; s++, r++) {
+                const int cnt = slots[r];
+                for (int k = 0; k < cnt; k++) { accR += term[k][0][r]; accG += term[k][1][r]; accB += term[k][2][r]; }
+                accD += (float)shaded[r];
+            }
+            const SssResolveIO al = RLS_INT_ARGS(a);
+            float br, bg, bb;
+            ldrgb(al.c.sss_color, pindex(al.c.materials, i), br, bg, bb);
+            const float inv = 1.0f / (float)a.spp;                              // AiSamplerGetSampleInvCount
+            strgb(al.result, i, br * accR * inv, bg * accG * inv, bb * accB * inv);
+            if (al.depth) stg(al.depth, i, accD * inv);
+        }
+    }
+}
+
 #if !RLS_FAST
 // exclusive scan of offsets[0, n): each workgroup one tile, its sum to totals[tile]
 __global__ __launch_bounds__(rlsh::kBlock) void trace_scan_block_kernel(int64_t *v, int64_t n, int64_t *totals)
@@ -414,9 +563,26 @@ __global__ __launch_bounds__(rlsh::kBlock) void trace_resolve_kernel(TraceResolv
 }
 #endif
 
+// one launch of the rlSss emit or resolve: a workgroup per tile of io.tile_points points, grid-striding past the cap
+template <class IO>
+rls_status launch_tiles(rls_context *ctx, void (*kernel)(IO), const IO &io, const char *name)
+{
+    const dim3 grid = rlsh::grid_for(ctx, io.n, io.tile_points);
+    hipLaunchKernelGGL(kernel, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(name, RLS_FAST);
+}
+
 } // namespace
 
 #if RLS_FAST
+RLS_HIDDEN rls_status rls_trace_fast_sss_probe_emit(rls_context *ctx, const SssEmitIO *io)
+{
+    return launch_tiles(ctx, sss_probe_emit_kernel<>, *io, "rls_trace_sss_probe_emit");
+}
+RLS_HIDDEN rls_status rls_trace_fast_sss_scatter_resolve(rls_context *ctx, const SssResolveIO *io)
+{
+    return launch_tiles(ctx, sss_scatter_resolve_kernel<>, *io, "rls_trace_sss_scatter_resolve");
+}
 RLS_HIDDEN rls_status rls_trace_fast_glossy_emit(rls_context *ctx, int g, const TraceEmitIO *io)
 {
     return launch_g(ctx, RLS_G_FAMILY(ggx_glossy_emit_kernel), g, *io, "rls_trace_ggx_glossy_emit");
@@ -435,6 +601,8 @@ RLS_HIDDEN rls_status rls_trace_fast_disney_emit(rls_context *ctx, int g, int lo
 RLS_HIDDEN rls_status rls_trace_fast_glossy_emit(rls_context *ctx, int g, const TraceEmitIO *io);
 RLS_HIDDEN rls_status rls_trace_fast_refract_emit(rls_context *ctx, int g, const TraceEmitIO *io);
 RLS_HIDDEN rls_status rls_trace_fast_disney_emit(rls_context *ctx, int g, int lobe, const DisneyEmitIO *io);
+RLS_HIDDEN rls_status rls_trace_fast_sss_probe_emit(rls_context *ctx, const SssEmitIO *io);
+RLS_HIDDEN rls_status rls_trace_fast_sss_scatter_resolve(rls_context *ctx, const SssResolveIO *io);
 
 namespace {
 
@@ -601,6 +769,60 @@ rls_status rls_trace_ggx_refract_resolve(rls_context *ctx, int64_t n, const rls_
                                          rls_rgb result)
 {
     return resolve(ctx, n, q, spp_n, radiance, result, true);
+}
+
+rls_status rls_trace_sss_probe_emit(rls_context *ctx, int64_t n, const rls_sss_closure *c, rls_cvec3 P, int spp_n,
+                                    uint32_t seed, uint64_t first_index, const rls_probe_queue *q)
+{
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE(n >= 0, "n < 0");
+    RLS_REQUIRE(n <= (int64_t)UINT32_MAX, "n > 2^32 - 1 (the queue's point index is 32-bit)");
+    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
+    RLS_REQUIRE(q != nullptr && q->offsets != nullptr, "queue or queue.offsets is NULL");
+    const int spp = spp_n * spp_n;
+    if (n == 0) {                                        // an empty queue: offsets[0] = 0
+        hipLaunchKernelGGL(trace_scan_totals_kernel, dim3(1), dim3(rlsh::kBlock), 0, ctx->stream, q->offsets, (int64_t)0,
+                           q->offsets);
+        return rlsh::check_launch(__func__);
+    }
+    if (rls_status s = rlsh::check_closure(__func__, c, true)) return s;
+    RLS_REQUIRE(rlsh::has3(P), "P plane is NULL");
+    RLS_REQUIRE(rlsh::has3(q->origin) && rlsh::has3(q->dir) && q->maxdist != nullptr,
+                "queue.origin, queue.dir or queue.maxdist plane is NULL");
+    RLS_REQUIRE(q->capacity >= n * spp, "queue.capacity < n * spp_n^2");
+    SssEmitIO io = {};
+    io.c = *c; io.P = P; io.q = *q;
+    io.n = n; io.spp = spp; io.tile_points = sss_emit_tile_points(spp); io.seed = seed; io.first = first_index;
+    return ctx->fast ? rls_trace_fast_sss_probe_emit(ctx, &io)
+                     : launch_tiles(ctx, sss_probe_emit_kernel<>, io, "rls_trace_sss_probe_emit");
+}
+
+rls_status rls_trace_sss_scatter_resolve(rls_context *ctx, int64_t n, const rls_sss_closure *c, rls_cvec3 P, int spp_n,
+                                         const rls_probe_queue *q, const rls_probe_hits *h, int use_cavity_fade,
+                                         int literal_matrix, rls_rgb result, float *mean_depth)
+{
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE(n >= 0, "n < 0");
+    RLS_REQUIRE(n <= (int64_t)UINT32_MAX, "n > 2^32 - 1 (the queue's point index is 32-bit)");
+    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
+    RLS_REQUIRE(q != nullptr, "queue is NULL");
+    RLS_REQUIRE(h != nullptr, "hits is NULL");
+    RLS_REQUIRE(h->max_hits >= 1 && h->max_hits <= RLS_MAX_PROBE_HITS, "hits.max_hits must be in [1, 12]");
+    if (n == 0) return RLS_OK;
+    const int spp = spp_n * spp_n;
+    if (rls_status s = rlsh::check_closure(__func__, c, true)) return s;
+    RLS_REQUIRE(rlsh::has3(P), "P plane is NULL");
+    RLS_REQUIRE(q->capacity >= n * spp, "queue.capacity < n * spp_n^2");
+    RLS_REQUIRE(h->stride >= n * spp, "hits.stride < n * spp_n^2");
+    RLS_REQUIRE(h->count != nullptr && rlsh::has3(h->P) && rlsh::has3(h->N) && h->irradiance.r && h->irradiance.g &&
+                h->irradiance.b, "hits.count, hits.P, hits.N or hits.irradiance plane is NULL");
+    RLS_REQUIRE(rlsh::has3(result), "NULL output plane");
+    SssResolveIO io = {};
+    io.c = *c; io.P = P; io.h = *h; io.result = result; io.depth = mean_depth;
+    io.n = n; io.spp = spp; io.tile_points = sss_resolve_tile_points(spp);
+    io.cavity = use_cavity_fade != 0; io.literal = literal_matrix != 0;
+    return ctx->fast ? rls_trace_fast_sss_scatter_resolve(ctx, &io)
+                     : launch_tiles(ctx, sss_scatter_resolve_kernel<>, io, "rls_trace_sss_scatter_resolve");
 }
 
 } // extern "C"

@@ -1,6 +1,6 @@
-// example_trace.cpp -- the caller-traced rlGgx and rlDisney integrators from C++ (rls_trace.hpp): emit integrateGlossy's
-// and integrateRefract's sample rays and those of rlDisney's two lobes, "trace" them against an analytic sky on the host,
-// resolve.
+// example_trace.cpp -- the caller-traced rlGgx, rlDisney and rlSss integrators from C++ (rls_trace.hpp): emit
+// integrateGlossy's and integrateRefract's sample rays and those of rlDisney's two lobes, "trace" them against an analytic
+// sky on the host, resolve; emit rlSss's probe rays, walk them through each point's tangent plane on the host, resolve.
 //
 //   example_trace [points] [spp_n]
 // prints one JSON line: the ray counts and a checksum (FNV-1a over the bits of the resolved planes) per integrator, which
@@ -93,6 +93,62 @@ int main(int argc, char **argv)
             for (float v : res) mean += v;
             std::printf("%s\"%s\": {\"rays\": %lld, \"checksum\": \"%016llx\", \"mean\": %.9g}", j ? ", " : "",
                         names[j], (long long)count, (unsigned long long)fnv(res), mean / (double)res.size());
+        }
+        {
+            // rlSss on the same frame: each shading point at the origin of its own tangent plane (normal N), lit from N
+            // itself, E = 1 / pi.  The renderer's probe walk: the one hit of a ray on that plane, 0 < t <= maxdist.
+            rls_sss_closure sc = {};
+            sc.sss_color = rlsb::ParamRGB(0.8f, 0.5f, 0.3f).c();
+            sc.sss_dist_multiplier = rls_param{nullptr, 1.0f};
+            sc.sss_scatter_dist[0] = rls_param{nullptr, 0.05f};
+            sc.sss_scatter_dist[1] = rls_param{nullptr, 0.1f};
+            sc.sss_scatter_dist[2] = rls_param{nullptr, 0.2f};
+            sc.N = c.N; sc.T = c.T; sc.has_dPdu = 1;
+            rlsb::Planes P(dev, std::vector<float>((size_t)(3 * n), 0.0f), 3), out(dev, n, 3), depth(dev, n, 1);
+            rlsb::ProbeQueue pq(dev, n, spp_n);
+            rlsb::emitProbes(dev, sc, P, n, spp_n, kSeed, pq);
+            const int spp = spp_n * spp_n;
+            std::vector<float> org((size_t)(3 * cap)), dir((size_t)(3 * cap)), md((size_t)cap), nrm((size_t)(3 * n));
+            for (int k = 0; k < 3; k++) {
+                rlsb::check(rls_copy_to_host(dev.ctx(), &org[(size_t)(k * cap)], (&pq.c().origin.x)[k], sizeof(float) * (size_t)cap));
+                rlsb::check(rls_copy_to_host(dev.ctx(), &dir[(size_t)(k * cap)], (&pq.c().dir.x)[k], sizeof(float) * (size_t)cap));
+                rlsb::check(rls_copy_to_host(dev.ctx(), &nrm[(size_t)(k * n)], (&c.N.x)[k], sizeof(float) * (size_t)n));
+            }
+            rlsb::check(rls_copy_to_host(dev.ctx(), md.data(), pq.c().maxdist, sizeof(float) * (size_t)cap));
+            std::vector<uint8_t> cnt((size_t)cap, 0);
+            std::vector<float> hits((size_t)(9 * cap), 0.0f);             // P, N, irradiance: 3 planes each, one hit slot
+            for (int64_t j = 0; j < cap; j++) {
+                const int64_t i = j / spp;
+                float dn = 0.0f, on = 0.0f;
+                for (int k = 0; k < 3; k++) {
+                    dn += nrm[(size_t)(k * n + i)] * dir[(size_t)(k * cap + j)];
+                    on += nrm[(size_t)(k * n + i)] * org[(size_t)(k * cap + j)];
+                }
+                const float t = dn != 0.0f ? -on / dn : 0.0f;
+                if (!(t > 0.0f && t <= md[(size_t)j])) continue;
+                cnt[(size_t)j] = 1;
+                for (int k = 0; k < 3; k++) {
+                    hits[(size_t)(k * cap + j)] = org[(size_t)(k * cap + j)] + dir[(size_t)(k * cap + j)] * t;
+                    hits[(size_t)((3 + k) * cap + j)] = nrm[(size_t)(k * n + i)];
+                    hits[(size_t)((6 + k) * cap + j)] = 0.318309886f;
+                }
+            }
+            rlsb::Planes hp(dev, hits, 9);
+            void *dcnt = nullptr;
+            rlsb::check(rls_device_alloc(dev.ctx(), (size_t)cap, &dcnt));
+            rlsb::check(rls_copy_to_device(dev.ctx(), dcnt, cnt.data(), (size_t)cap));
+            rls_probe_hits h = {};
+            h.max_hits = 1; h.stride = cap; h.count = static_cast<const uint8_t *>(dcnt);
+            h.P = hp.cvec3(0); h.N = hp.cvec3(3);
+            h.irradiance = rls_crgb{hp.plane(6), hp.plane(7), hp.plane(8)};
+            rlsb::resolveScatter(dev, sc, P, pq, h, true, false, out, depth.plane(0));
+            std::vector<float> res = out.download(), dres = depth.download();
+            rls_device_free(dev.ctx(), dcnt);
+            double mean = 0.0, mdepth = 0.0;
+            for (float v : res) mean += v;
+            for (float v : dres) mdepth += v;
+            std::printf(", \"sss\": {\"rays\": %lld, \"checksum\": \"%016llx\", \"mean\": %.9g, \"mean_depth\": %.9g}",
+                        (long long)pq.count(), (unsigned long long)fnv(res), mean / (double)res.size(), mdepth / (double)n);
         }
         std::printf(", \"points\": %lld, \"spp_n\": %d}\n", (long long)n, spp_n);
     } catch (const rlsb::Error &e) {

@@ -1,4 +1,4 @@
-// rls_trace.hpp -- C++14 host-side mirror of the caller-traced rlGgx and rlDisney integrators
+// rls_trace.hpp -- C++14 host-side mirror of the caller-traced rlGgx, rlDisney and rlSss integrators
 // (include/rlshaders_amd_trace.h, librls_trace.so).  Header-only, in the style of rls_batch.hpp, whose Device / Planes /
 // check it uses.
 //
@@ -10,6 +10,11 @@
 //     ... trace q.dir() [q.count() rays] with the renderer's tracer, one radiance per ray -> radiance (3 planes) ...
 //     rlsb::resolveGlossy(dev, q, radiance, sum);                           // sum of radiance x f/pdf per point
 // rlDisney: a RayQueue of kind DisneyDiffuse / DisneyGlossy per lobe, emitDisney, and resolveGlossy likewise.
+// rlSss (integrateScatter's probe rays, src/rlSss.h:224-279):
+//     rlsb::ProbeQueue pq(dev, n, spp_n);
+//     rlsb::emitProbes(dev, sss, P, n, spp_n, seed, pq);                   // one probe ray per sample, dense
+//     ... walk every ray through the object, fill an rls_probe_hits (count, P, N, irradiance per hit slot) ...
+//     rlsb::resolveScatter(dev, sss, P, pq, hits, cavity, literal, result); // integrateScatter's result
 // Nothing here synchronises the host except RayQueue::count() (it reads offsets[n]).
 #pragma once
 
@@ -132,6 +137,77 @@ inline void resolveRefract(const Device &d, const RayQueue &q, const Planes &rad
 {
     check(rls_trace_ggx_refract_resolve(d.ctx(), q.points(), &q.c(), q.sppN(),
                                         rls_crgb{radiance.plane(0), radiance.plane(1), radiance.plane(2)}, result.rgb()));
+}
+
+// integrateScatter's probe rays: n * spp_n^2 rays, ray j = i * spp_n^2 + s (no compaction: count() is known on the host)
+class ProbeQueue {
+public:
+    ProbeQueue(const Device &d, int64_t n, int spp_n) : dev_(&d), n_(n), spp_n_(spp_n)
+    {
+        const int64_t cap = n * spp_n * spp_n;
+        try {
+            q_.capacity = cap;
+            q_.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(n + 1)));
+            q_.origin = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
+            q_.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
+            q_.maxdist = falloc(cap);
+            q_.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
+            q_.sample = static_cast<uint8_t *>(alloc((size_t)cap));
+        } catch (...) {
+            release();
+            throw;
+        }
+    }
+    ~ProbeQueue() { release(); }
+    ProbeQueue(const ProbeQueue &) = delete;
+    ProbeQueue &operator=(const ProbeQueue &) = delete;
+
+    const rls_probe_queue &c() const { return q_; }
+    int64_t points() const { return n_; }
+    int sppN() const { return spp_n_; }
+    int64_t count() const { return q_.capacity; }
+
+private:
+    void release()
+    {
+        for (int k = 0; k < nbufs_; k++) rls_device_free(dev_->ctx(), bufs_[k]);
+        nbufs_ = 0;
+    }
+    void *alloc(size_t bytes)
+    {
+        void *p = nullptr;
+        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
+        bufs_[nbufs_++] = p;
+        return p;
+    }
+    float *falloc(int64_t count) { return static_cast<float *>(alloc(sizeof(float) * (size_t)count)); }
+
+    const Device *dev_;
+    int64_t n_;
+    int spp_n_;
+    rls_probe_queue q_{};
+    void *bufs_[10] = {};
+    int nbufs_ = 0;
+};
+
+// integrateScatter's probe rays (getProbeRay, src/rlSss.h:224-228); P: 3 planes of n floats, sg->P
+inline void emitProbes(const Device &d, const rls_sss_closure &c, const Planes &P, int64_t n, int spp_n, uint32_t seed,
+                       ProbeQueue &q, uint64_t first_index = 0)
+{
+    if (q.points() != n || q.sppN() != spp_n) throw Error(RLS_ERR_INVALID_ARGUMENT, "emitProbes: a queue of another size");
+    check(rls_trace_sss_probe_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, spp_n, seed,
+                                   first_index, &q.c()));
+}
+
+// integrateScatter's combination of the caller's hits (src/rlSss.h:245-279); c and P those of the emit; result: 3 planes
+// of n floats; meanDepth: n floats or nullptr
+inline void resolveScatter(const Device &d, const rls_sss_closure &c, const Planes &P, const ProbeQueue &q,
+                           const rls_probe_hits &hits, bool cavityFade, bool literalMatrix, Planes &result,
+                           float *meanDepth = nullptr)
+{
+    check(rls_trace_sss_scatter_resolve(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, q.sppN(),
+                                        &q.c(), &hits, cavityFade ? 1 : 0, literalMatrix ? 1 : 0, result.rgb(),
+                                        meanDepth));
 }
 
 } // namespace rlsb

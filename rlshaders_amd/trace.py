@@ -1,5 +1,6 @@
-"""Caller-traced rlGgx and rlDisney integrators: emit the sample rays of integrateGlossy / integrateRefract (rlGgx) or of
-one rlDisney lobe, trace them with your own tracer, resolve the radiance (include/rlshaders_amd_trace.h, companion library
+"""Caller-traced rlGgx, rlDisney and rlSss integrators: emit the sample rays of integrateGlossy / integrateRefract (rlGgx)
+or of one rlDisney lobe, trace them with your own tracer, resolve the radiance; or emit integrateScatter's probe rays
+(rlSss), walk them through the object, resolve the hits (include/rlshaders_amd_trace.h, companion library
 ``librls_trace.so``).
 
     q = trace.glossy_rays(sampler, spp_n=4, seed=7)          # RayQueue: q.dir [3, count], q.weight [3, count], ...
@@ -8,6 +9,10 @@ one rlDisney lobe, trace them with your own tracer, resolve the radiance (includ
 
     d = trace.disney_rays(disney, RLS_RAY_DIFFUSE, 8, seed)  # one lobe per queue; q.resolve: rls_disney_integrate's
                                                              # diffuse_sum, d.valid_count its diffuse_count
+
+    p = trace.sss_probe_rays(sss, P, spp_n=4, seed=7)        # ProbeQueue: p.origin, p.dir [3, rays], p.maxdist [rays]
+    cnt, hP, hN, E = my_probe_walk(p.origin, p.dir, p.maxdist)   # hits [3, max_hits, rays], E before profile and fade
+    res = p.resolve(cnt, hP, hN, E)                          # [3, n]: integrateScatter's result
 
 ``count`` is read from the device once (it synchronises); everything else stays asynchronous on the context's stream, so
 ``glossy_rays(..., queue=q)`` / ``q.resolve(L, out=...)`` with preallocated tensors can be recorded by ``ctx.capture()``.
@@ -23,7 +28,7 @@ import torch
 
 from . import _capi as capi
 from ._capi import RLS_RAY_DIFFUSE, RLS_RAY_GLOSSY, check
-from .closures import DisneySampler, GgxSampler, plane, rgb
+from .closures import DisneySampler, GgxSampler, SssSampler, cvec3, plane, rgb
 
 TRACE_LIB_PATH = capi._PKG / "lib" / "librls_trace.so"
 
@@ -38,8 +43,23 @@ class RayQueue_(C.Structure):
                 ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
+class ProbeQueue_(C.Structure):
+    """rls_probe_queue"""
+    _fields_ = [("capacity", C.c_int64), ("offsets", C.c_void_p), ("origin", capi.Vec3), ("dir", capi.Vec3),
+                ("maxdist", C.c_void_p), ("point", C.c_void_p), ("sample", C.c_void_p)]
+
+
+class ProbeHits_(C.Structure):
+    """rls_probe_hits"""
+    _fields_ = [("max_hits", C.c_int), ("stride", C.c_int64), ("count", C.c_void_p), ("P", capi.CVec3), ("N", capi.CVec3),
+                ("irradiance", capi.CRgb)]
+
+
+RLS_MAX_PROBE_HITS = 12
+
 _ctx, _i64, _vp = C.c_void_p, C.c_int64, C.c_void_p
 _q = C.POINTER(RayQueue_)
+_pq = C.POINTER(ProbeQueue_)
 PROTOTYPES = {
     "rls_trace_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
     "rls_trace_ggx_glossy_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
@@ -48,6 +68,10 @@ PROTOTYPES = {
                                         _q, _vp]),
     "rls_trace_ggx_glossy_resolve": (C.c_int, [_ctx, _i64, _q, capi.CRgb, capi.Rgb]),
     "rls_trace_ggx_refract_resolve": (C.c_int, [_ctx, _i64, _q, C.c_int, capi.CRgb, capi.Rgb]),
+    "rls_trace_sss_probe_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.SssClosure), capi.CVec3, C.c_int, C.c_uint32, C.c_uint64,
+                                           _pq]),
+    "rls_trace_sss_scatter_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.SssClosure), capi.CVec3, C.c_int, _pq,
+                                                C.POINTER(ProbeHits_), C.c_int, C.c_int, capi.Rgb, _vp]),
 }
 
 _lib = None
@@ -222,4 +246,83 @@ def disney_rays(sampler: DisneySampler, lobe: int, spp_n: int, seed: int, first_
         raise ValueError("queue: allocated for another batch size, spp_n, integrator or lobe")
     check(load().rls_trace_disney_emit(ctx.handle, n, C.byref(sampler.c), int(lobe), int(spp_n), int(seed) & 0xFFFFFFFF,
                                        int(first_index), C.byref(q.q), plane(q.side, n, "valid_count") if n > 0 else None))
+    return q
+
+
+class ProbeQueue:
+    """integrateScatter's probe rays over n points at spp_n^2 samples: dense, point-major (ray j = i * spp_n^2 + s is sample s
+    of point i; offsets[i] = i * spp_n^2).  ``count`` is known without reading the device."""
+
+    def __init__(self, ctx, n: int, spp_n: int):
+        self.ctx, self.n, self.spp_n = ctx, int(n), int(spp_n)
+        dev = ctx.torch_device
+        cap = self.n * self.spp_n * self.spp_n
+        self.capacity = self.count = cap
+        self.offsets = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
+        self.origin = torch.empty(3, cap, dtype=torch.float32, device=dev)
+        self.dir = torch.empty(3, cap, dtype=torch.float32, device=dev)
+        self.maxdist = torch.empty(cap, dtype=torch.float32, device=dev)
+        self.point = torch.empty(cap, dtype=torch.int32, device=dev)           # uint32 on the device; n < 2^31 here
+        self.sample = torch.empty(cap, dtype=torch.uint8, device=dev)
+        q = ProbeQueue_()
+        q.capacity = cap
+        q.offsets = self.offsets.data_ptr()
+        q.origin = capi.Vec3(*[self.origin[k].data_ptr() for k in range(3)])
+        q.dir = capi.Vec3(*[self.dir[k].data_ptr() for k in range(3)])
+        q.maxdist, q.point, q.sample = self.maxdist.data_ptr(), self.point.data_ptr(), self.sample.data_ptr()
+        self.q = q
+        self.sampler: Optional[SssSampler] = None        # the closure and shading points of the last emit
+        self.P: Optional[torch.Tensor] = None
+
+    def resolve(self, count: torch.Tensor, P: torch.Tensor, N: torch.Tensor, irradiance: torch.Tensor,
+                use_cavity_fade: bool = False, literal_matrix: bool = False, want_depth: bool = False,
+                out: Optional[torch.Tensor] = None, depth_out: Optional[torch.Tensor] = None):
+        """integrateScatter's combination of the caller's hits (rls_trace_sss_scatter_resolve) -> result [3, n] (and the
+        mean number of shaded hits per probe ray [n] with ``want_depth``).
+        count: uint8 [>= rays], the hits of every ray (values above max_hits read as max_hits); P, N, irradiance: float32
+        [3, max_hits, stride] with stride >= rays: hit k of ray j at [:, k, j] -- positions in ascending t, sg->Ns aligned to
+        sg->N, E before evalProfile and the cavity fade (include/rlshaders_amd_trace.h)."""
+        if self.sampler is None:
+            raise RuntimeError("resolve: no emit has filled this queue (trace.sss_probe_rays)")
+        ctx, n, rays = self.ctx, self.n, self.count
+        if not isinstance(count, torch.Tensor) or count.dtype != torch.uint8 or not count.is_cuda or count.dim() != 1 or \
+                count.shape[0] < rays or not count.is_contiguous():
+            raise ValueError(f"count: expected a contiguous uint8 CUDA tensor [>= {rays}]")
+        shape = None
+        for what, t in (("P", P), ("N", N), ("irradiance", irradiance)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or \
+                    t.shape[0] != 3 or not 1 <= t.shape[1] <= RLS_MAX_PROBE_HITS or t.shape[2] < rays or \
+                    t.stride(2) != 1 or t.stride(1) != t.shape[2]:
+                raise ValueError(f"{what}: expected a float32 CUDA tensor [3, 1..{RLS_MAX_PROBE_HITS}, >= {rays}] whose "
+                                 f"planes are contiguous")
+            if shape is not None and t.shape != shape:
+                raise ValueError(f"{what}: shape {tuple(t.shape)} differs from P's {tuple(shape)}")
+            shape = t.shape
+        h = ProbeHits_()
+        h.max_hits, h.stride, h.count = int(shape[1]), int(shape[2]), count.data_ptr()
+        h.P = capi.CVec3(*[P[k].data_ptr() for k in range(3)])
+        h.N = capi.CVec3(*[N[k].data_ptr() for k in range(3)])
+        h.irradiance = capi.CRgb(*[irradiance[k].data_ptr() for k in range(3)])
+        res = ctx.empty(3, n) if out is None else out
+        depth = (ctx.empty(n) if depth_out is None else depth_out) if want_depth else None
+        s = self.sampler
+        check(load().rls_trace_sss_scatter_resolve(
+            ctx.handle, n, C.byref(s.c), cvec3(self.P, n, "P"), self.spp_n, C.byref(self.q), C.byref(h),
+            1 if use_cavity_fade else 0, 1 if literal_matrix else 0, rgb(res, n, "result"),
+            plane(depth, n, "mean_depth") if want_depth else None))
+        return (res, depth) if want_depth else res
+
+
+def sss_probe_rays(sampler: SssSampler, P: torch.Tensor, spp_n: int, seed: int, first_index: int = 0,
+                   queue: Optional[ProbeQueue] = None) -> ProbeQueue:
+    """integrateScatter's probe rays (getProbeRay, src/rlSss.h:224-228): the samples rls_sss_integrate_scatter draws, one ray
+    each, origin sg->P + the probe offset (P: [3, n] float32, sg->P per point)."""
+    ctx, n = sampler.ctx, sampler.n
+    q = ProbeQueue(ctx, n, spp_n) if queue is None else queue
+    if q.n != n or q.spp_n != int(spp_n):
+        raise ValueError("queue: allocated for another batch size or spp_n")
+    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
+    check(load().rls_trace_sss_probe_emit(ctx.handle, n, C.byref(sampler.c), Pv, int(spp_n), int(seed) & 0xFFFFFFFF,
+                                          int(first_index), C.byref(q.q)))
+    q.sampler, q.P = sampler, P
     return q

@@ -1,8 +1,9 @@
 """Timing of the caller-traced integrators (rlshaders_amd/trace.py): emit and resolve of rlGgx's integrateGlossy and
 integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same batch in the same process; with
---closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch.
+--closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
+--closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
+    python tools/trace_bench.py [--closure ggx|disney|sss] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -11,6 +12,10 @@ also writes 12 + 12 (4) + 2 B per sample and reads them back per kept ray (`*_wi
 12 (weight; refraction 4) B per ray and 8 B per point (offsets) and writes 12 B per point.  The radiance is uniform random.
 An rlDisney lobe is accounted as glossy (3 weight planes, no kind).  Its record has integrate_ms (both lobes in one call)
 and per lobe emit_over_integrate; "emits_over_integrate" is (emit_diffuse + emit_glossy) / integrate.
+rlSss: the emit writes 12 (origin) + 12 (dir) + 4 (maxdist) + 4 (point) + 1 (sample) = 33 B per ray, every ray (the queue is
+dense); the resolve reads 1 B of count per ray plus 12 (P) + 12 (N) + 12 (irradiance) = 36 B per reported hit slot.  Its
+hits come from a plane intersected with torch on the device (the shading points lie on the plane z = 0, lit from +z):
+timing needs plausible hits, not the oracle's.
 """
 from __future__ import annotations
 
@@ -91,6 +96,51 @@ def bench_disney(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
     rec["emits_over_integrate"] = round(emits / ms_int, 4)
 
 
+def bench_sss(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """rlSss on the plane z = 0: the probe-ray emit and the scatter resolve of device-traced hits against
+    rls_sss_integrate_scatter over the same analytic plane"""
+    import math
+    import torch
+    import rlshaders_amd as R
+    from rlshaders_amd import trace as T
+    g = torch.Generator(device=ctx.torch_device).manual_seed(seed)
+    dev = ctx.torch_device
+    Ns = torch.zeros(3, n, device=dev)
+    Ns[2] = 1
+    ang = torch.rand(n, device=dev, generator=g) * (2 * math.pi)
+    Tg = torch.stack([torch.cos(ang), torch.sin(ang), torch.zeros_like(ang)]).contiguous()
+    P = torch.zeros(3, n, device=dev)
+    P[:2] = torch.rand(2, n, device=dev, generator=g)
+    s = R.SssSampler(ctx, Ns, Tg, (0.8, 0.5, 0.3), (0.05, 0.1, 0.2))
+    sc = R.make_scene("plane", light_dir=(0, 0, 1), light_color=(1.0, 1.0, 1.0))
+    res = ctx.empty(3, n)
+    ms_int = timed(lambda: s.integrateScatter(P, sc, spp_n, seed, out=res), args.repeats, args.warmup)
+    q = T.ProbeQueue(ctx, n, spp_n)
+    ms_emit = timed(lambda: T.sss_probe_rays(s, P, spp_n, seed, queue=q), args.repeats, args.warmup)
+    O, D, md = q.origin, q.dir, q.maxdist
+    with torch.no_grad():
+        t = -O[2] / D[2]
+        ok = (D[2] != 0) & (t > 0) & (t <= md)
+        hP = (O + D * t).unsqueeze(1).contiguous()
+        hN = torch.zeros_like(hP)
+        hN[2] = 1
+        E = torch.full_like(hP, 1.0 / math.pi)
+        cnt = ok.to(torch.uint8)
+    hits = int(cnt.sum().item())
+    ms_res = timed(lambda: q.resolve(cnt, hP, hN, E, out=res), args.repeats, args.warmup)
+    rays = q.count
+    emit_bytes, res_bytes = rays * 33, rays * 1 + hits * 36
+    rec["sss"] = {
+        "rays": rays, "hits_per_ray": round(hits / rays, 4), "integrate_ms": round(ms_int, 4),
+        "emit_ms": round(ms_emit, 4), "resolve_ms": round(ms_res, 4),
+        "emit_rays_per_s": round(rays / (ms_emit * 1e-3), 1), "resolve_rays_per_s": round(rays / (ms_res * 1e-3), 1),
+        "emit_tb_per_s": rate(emit_bytes, ms_emit), "emit_frac_of_8tbps": round(rate(emit_bytes, ms_emit) / HBM_TBPS, 4),
+        "resolve_tb_per_s": rate(res_bytes, ms_res), "resolve_frac_of_8tbps": round(rate(res_bytes, ms_res) / HBM_TBPS, 4),
+        "emit_over_integrate": round(ms_emit / ms_int, 4),
+        "emit_plus_resolve_over_integrate": round((ms_emit + ms_res) / ms_int, 4),
+    }
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=24)
@@ -98,7 +148,7 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
-    ap.add_argument("--closure", choices=("ggx", "disney"), default="ggx")
+    ap.add_argument("--closure", choices=("ggx", "disney", "sss"), default="ggx")
     args = ap.parse_args()
     if args.repeats < 3:
         ap.error("--repeats must be at least 3")
@@ -114,9 +164,9 @@ def main() -> None:
     spp = spp_n * spp_n
     rec = {"tool": "trace_bench", "n": n, "spp_n": spp_n, "math": "fast" if args.fast else "exact", "repeats": args.repeats,
            "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
-    if args.closure == "disney":
-        rec["closure"] = "disney"
-        bench_disney(args, ctx, n, spp_n, seed, rec)
+    if args.closure in ("disney", "sss"):
+        rec["closure"] = args.closure
+        (bench_disney if args.closure == "disney" else bench_sss)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
         print(json.dumps(rec), flush=True)
         return
