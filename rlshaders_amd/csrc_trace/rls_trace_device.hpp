@@ -1,36 +1,33 @@
-// rls_trace_device.hpp -- device helpers of the caller-traced integrators (trace.hip): the launch descriptors, a sample's
-// rank among the kept samples of its point, and the int64 scan of the per-point ray counts.
+// rls_trace_device.hpp -- device helpers of the caller-traced integrators (trace.hip): the launch descriptors, the staging
+// format of the emits, a sample's rank among the kept samples of its point, and the int64 scan of the per-point ray counts.
 #pragma once
 #include "../csrc/rls_loops.hpp"
 #include "../../include/rlshaders_amd_trace.h"
 
 namespace {
 
-constexpr uint16_t kDropped = 0xFFFF;        // staging tag of a sample that is not queued (else rank | kind << 8)
+// The staging of an emit: sample s of point i has slot s * n + i of every staging plane (sample-major: the lanes of a
+// wavefront store to consecutive words) and a tag there: its rank among the point's kept samples | its kind << 8 (the ray's
+// RLS_RAY_* bits), or kDropped where it is not queued.
+constexpr uint16_t kDropped = 0xFFFF;
+__device__ __forceinline__ int64_t staging_slot(int s, int64_t n, int64_t i) { return (int64_t)s * n + i; }
+__device__ __forceinline__ uint16_t staging_tag(bool keep, int rank, int kind)
+{
+    return keep ? (uint16_t)(rank | kind << 8) : kDropped;
+}
+__device__ __forceinline__ int tag_rank(uint16_t tag) { return tag & 0xFF; }
+__device__ __forceinline__ int tag_kind(uint16_t tag) { return tag >> 8; }
 
-// emit: one G-lane group per point writes slot s * n + i of the staging planes for every sample, and the point's count
-// of kept samples into offsets[i] (scanned in place afterwards)
-struct TraceEmitIO {
-    rls_ggx_closure c;
+// emit: one G-lane group per point stages every sample of the point (above), and writes the point's count of kept samples
+// into offsets[i] (scanned in place afterwards) and its side output
+template <class Closure>
+struct EmitIO {
+    Closure c;
     float *dir[3];
-    float *w[3];             // glossy: 3 planes; refraction: w[0]
+    float *w[3];             // rlGgx glossy, rlDisney: 3 planes; rlGgx refraction: w[0]
     uint16_t *tag;
     int64_t *count;          // = the queue's offsets
-    float *side;             // avg_reflect_weight / tir_fraction, NULL-able
-    int64_t n;
-    int spp;
-    uint32_t seed;
-    uint64_t first;
-};
-
-// the rlDisney emit (one lobe per launch): the same staging and counts, f / pdf in three weight planes
-struct DisneyEmitIO {
-    rls_disney_closure c;
-    float *dir[3];
-    float *w[3];
-    uint16_t *tag;
-    int64_t *count;          // = the queue's offsets
-    float *valid;            // valid_count (the lobe's diffuse_count / specular_count), NULL-able
+    float *side;             // avg_reflect_weight / tir_fraction / valid_count, NULL-able
     int64_t n;
     int spp;
     uint32_t seed;

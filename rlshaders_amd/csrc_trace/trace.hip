@@ -29,12 +29,28 @@
 
 namespace {
 
-template <int G, int FAST_MATH = RLS_FAST>
-__global__ RLS_INT_ATTR void ggx_glossy_emit_kernel(TraceEmitIO a)
+// One sample as a lobe's sample() leaves it: the ray's direction, its weights (refraction: w[0] only) and kind bits; all
+// zero past spp.
+struct EmitRay {
+    V3 dir;
+    float w[3];
+    int kind;
+};
+
+// The emit of every closure: the sample loop of the integrator (one G-lane group per point, the same packed sampling) with
+// each sample staged instead of summed (staging_slot, staging_tag), the point's kept count to offsets[i] and its side output.
+// A lobe policy supplies the rest, per point:
+//   Lobe(a, ii)              the closure at point ii
+//   kStream                  its scramble streams: kScrambleStream + kStream, + kStream + 1
+//   kPush, push(...)         the first sweep of the packed rare branches (SlowLds), if it has one
+//   kWeights, sample(...)    the per-sample term, in every lane of every round; returns whether the ray is queued
+//   side(spp)                the point's side output, in every lane (group reductions)
+template <int G, class Lobe, class Closure>
+__device__ __forceinline__ void emit_points(const EmitIO<Closure> &a)
 {
     constexpr int K = RLS_SPEC_BLOCK;
     __shared__ uint32_t tab[2][kMaxSpp];
-    __shared__ SlowLds<K> slow;
+    __shared__ SlowLds<K> slow;                                  // (not allocated where no lobe code uses it)
     stage_libm_tables();
     stage_table(tab, a.spp);
     const int sub = threadIdx.x % G;
@@ -45,156 +61,138 @@ __global__ RLS_INT_ATTR void ggx_glossy_emit_kernel(TraceEmitIO a)
     for (int64_t it = 0; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
+        Lobe lobe(a, ii);
+        const uint32_t sx = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + Lobe::kStream);
+        const uint32_t sy = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + Lobe::kStream + 1);
+        int run = 0;
+        for (int s0 = sub; s0 - sub < a.spp; s0 += K * G) {      // the same trip count in every lane
+            if constexpr (Lobe::kPush) {
+                int cnt = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const int sc = s < a.spp ? s : 0;
+                    lobe.push(slow, k, cnt, s < a.spp, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
+                }
+                slow_run<K>(slow, cnt);
+            }
+#pragma unroll 1
+            for (int k = 0; k < K; k++) {
+                const int s = s0 + k * G;
+                const bool ok = s < a.spp;
+                float rx = 0.0f, ry = 0.0f;                             // a lobe without a push phase draws here
+                if (!Lobe::kPush && ok) { rx = bits_u01(tab[0][s] ^ sx); ry = bits_u01(tab[1][s] ^ sy); }
+                EmitRay r = {};
+                const bool keep = lobe.sample(slow, k, ok, rx, ry, r) && ok;      // (sample() first: every lane runs it)
+                const int rank = group_rank<G>(keep, sub, run);
+                if (live && ok) {
+                    const int64_t slot = staging_slot(s, a.n, i);
+                    if (keep) {
+                        a.dir[0][slot] = r.dir.x; a.dir[1][slot] = r.dir.y; a.dir[2][slot] = r.dir.z;
+#pragma unroll
+                        for (int c = 0; c < Lobe::kWeights; c++) a.w[c][slot] = r.w[c];
+                    }
+                    a.tag[slot] = staging_tag(keep, rank, r.kind);
+                }
+            }
+        }
+        const float side = lobe.side(a.spp);
+        if (live && sub == 0) {
+            a.count[i] = run;
+            if (a.side) stg(a.side, i, side);
+        }
+    }
+}
+
+// rlGgx, both emits: the closure, the VNDF sampler and its packed uniform-slope fallback (ggx_vndf_push / _pop)
+struct GgxLobe {
+    static constexpr int kStream = 0;
+    static constexpr bool kPush = true;
+    Ggx g;
+    VndfView w;
+    __device__ GgxLobe(const EmitIO<rls_ggx_closure> &a, int64_t ii)
+    {
         const rls_ggx_closure &c = a.c;
         const PIndex<int64_t> pk = pindex(c.materials, ii);
         V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
         float kr, kg, kb;
         ldrgb(c.KsColor, pk, kr, kg, kb);
         bool exiting = c.exiting ? (c.exiting[ii] != 0) : false;
-        Ggx g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp(c.ior, pk), ldp(c.specularRoughness, pk),
-                         ldp(c.anisotropic, pk));
-        VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
-        const uint32_t sx = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream);
-        const uint32_t sy = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + 1);
-
-        // ggx_glossy_loop (rls_loops.hpp) with the per-sample terms stored instead of summed; the Fresnel sum is folded in
-        // sample order exactly as there
-        float accF = 0.0f;
-        int run = 0;
-        for (int s0 = sub; s0 - sub < a.spp; s0 += K * G) {
-            int cnt = 0;
-#pragma unroll 1
-            for (int k = 0; k < K; k++) {
-                const int s = s0 + k * G;
-                const int sc = s < a.spp ? s : 0;
-                ggx_vndf_push<K>(slow, k, cnt, s < a.spp, w, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
-            }
-            slow_run<K>(slow, cnt);
-#pragma unroll 1
-            for (int k = 0; k < K; k++) {
-                const int s = s0 + k * G;
-                float tR = 0.0f, tG = 0.0f, tB = 0.0f, tF = 0.0f;
-                V3 L = mk(0.0f, 0.0f, 0.0f);
-                if (s < a.spp) {
-                    V3 M = ggx_vndf_pop<K>(slow, k, w, g.fr);
-                    L = reflect_direction(g.view, M);
-                    tF = ggx_fresnel(g, L, M);                      // mReflectWeight, src/rlGgx.h:103
-                    float fr, fg, fb, pdf;
-                    ggx_eval_pdf<true, true>(g, L, fr, fg, fb, pdf);
-                    tR = fr / pdf; tG = fg / pdf; tB = fb / pdf;
-                }
-                fold<G>(accF, tF);
-                const bool keep = s < a.spp && !(tR == 0.0f && tG == 0.0f && tB == 0.0f);
-                const int rank = group_rank<G>(keep, sub, run);
-                if (live && s < a.spp) {
-                    const int64_t slot = (int64_t)s * a.n + i;
-                    if (keep) {
-                        a.dir[0][slot] = L.x; a.dir[1][slot] = L.y; a.dir[2][slot] = L.z;
-                        a.w[0][slot] = tR; a.w[1][slot] = tG; a.w[2][slot] = tB;
-                    }
-                    a.tag[slot] = keep ? (uint16_t)rank : kDropped;
-                }
-            }
-        }
-        if (live && sub == 0) {
-            a.count[i] = run;
-            if (a.side) stg(a.side, i, accF / (float)a.spp);       // getAvgReflectWeight, src/rlGgx.h:181-184
-        }
+        g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp(c.ior, pk), ldp(c.specularRoughness, pk), ldp(c.anisotropic, pk));
+        w = vndf_view(g.view, g.fr, g.ax, g.ay);
     }
-}
-
-template <int G, int FAST_MATH = RLS_FAST>
-__global__ RLS_INT_ATTR void ggx_refract_emit_kernel(TraceEmitIO a)
-{
-    constexpr int K = RLS_SPEC_BLOCK;
-    __shared__ uint32_t tab[2][kMaxSpp];
-    __shared__ SlowLds<K> slow;
-    stage_libm_tables();
-    stage_table(tab, a.spp);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
-        const bool live = i < a.n;
-        const int64_t ii = live ? i : a.n - 1;
-        const rls_ggx_closure &c = a.c;
-        const PIndex<int64_t> pk = pindex(c.materials, ii);
-        V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
-        float kr, kg, kb;
-        ldrgb(c.KsColor, pk, kr, kg, kb);
-        bool exiting = c.exiting ? (c.exiting[ii] != 0) : false;
-        Ggx g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp(c.ior, pk), ldp(c.specularRoughness, pk),
-                         ldp(c.anisotropic, pk));
-        VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
-        const uint32_t sx = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream);
-        const uint32_t sy = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + 1);
-
-        // ggx_refract_loop (rls_loops.hpp) with the per-sample direction and weight stored instead of summed
-        float tir = 0.0f;
-        int run = 0;
-        for (int s0 = sub; s0 - sub < a.spp; s0 += K * G) {
-            int cnt = 0;
-#pragma unroll 1
-            for (int k = 0; k < K; k++) {
-                const int s = s0 + k * G;
-                const int sc = s < a.spp ? s : 0;
-                ggx_vndf_push<K>(slow, k, cnt, s < a.spp, w, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
-            }
-            slow_run<K>(slow, cnt);
-#pragma unroll 1
-            for (int k = 0; k < K; k++) {
-                const int s = s0 + k * G;
-                float t = 0.0f;
-                bool mirror = false;
-                V3 dir = mk(0.0f, 0.0f, 0.0f);
-                if (s < a.spp) {
-                    V3 M = ggx_vndf_pop<K>(slow, k, w, g.fr);
-                    mirror = !ggx_refract(g, M, dir);
-                    if (mirror) tir += 1.0f;
-                    t = ggx_sample_weight(g, g.view, dir, M);        // src/rlGgx.h:241
-                }
-                const bool keep = s < a.spp && !(t == 0.0f);
-                const int rank = group_rank<G>(keep, sub, run);
-                if (live && s < a.spp) {
-                    const int64_t slot = (int64_t)s * a.n + i;
-                    if (keep) {
-                        a.dir[0][slot] = dir.x; a.dir[1][slot] = dir.y; a.dir[2][slot] = dir.z;
-                        a.w[0][slot] = t;
-                    }
-                    a.tag[slot] = keep ? (uint16_t)(rank | (mirror ? RLS_RAY_TIR_MIRROR << 8 : 0)) : kDropped;
-                }
-            }
-        }
-        if (G > 1) tir = group_sum<G>(tir);                         // a count: integers, any order
-        if (live && sub == 0) {
-            a.count[i] = run;
-            if (a.side) stg(a.side, i, tir * (1.0f / (float)a.spp));   // as ggx_refract_loop: tir *= inv
-        }
+    template <int K>
+    __device__ void push(SlowLds<K> &slow, int k, int &cnt, bool ok, float rx, float ry)
+    {
+        ggx_vndf_push<K>(slow, k, cnt, ok, w, rx, ry);
     }
-}
+};
 
-// One lobe of rls_disney_integrate's sample loop (integrate.hip, disney_integrate_body) with the per-sample terms stored
-// instead of summed: SPEC = 0 the diffuse lobe (scramble streams +0/1), SPEC = 1 the specular lobe (+2/3, its rare branches
+// ggx_glossy_loop (rls_loops.hpp): f / pdf in three planes, queued where not all three are 0; the Fresnel sum folded in
+// sample order exactly as there
+template <int G>
+struct GgxGlossy : GgxLobe {
+    static constexpr int kWeights = 3;
+    float accF = 0.0f;
+    using GgxLobe::GgxLobe;
+    template <int K>
+    __device__ bool sample(const SlowLds<K> &slow, int k, bool ok, float, float, EmitRay &r)
+    {
+        float tF = 0.0f;
+        if (ok) {
+            const V3 M = ggx_vndf_pop<K>(slow, k, w, g.fr);
+            r.dir = reflect_direction(g.view, M);
+            tF = ggx_fresnel(g, r.dir, M);                          // mReflectWeight, src/rlGgx.h:103
+            float fr, fg, fb, pdf;
+            ggx_eval_pdf<true, true>(g, r.dir, fr, fg, fb, pdf);
+            r.w[0] = fr / pdf; r.w[1] = fg / pdf; r.w[2] = fb / pdf;
+        }
+        fold<G>(accF, tF);
+        return !(r.w[0] == 0.0f && r.w[1] == 0.0f && r.w[2] == 0.0f);
+    }
+    __device__ float side(int spp) const { return accF / (float)spp; }      // getAvgReflectWeight, src/rlGgx.h:181-184
+};
+
+// ggx_refract_loop (rls_loops.hpp): the weight in one plane, queued where it is not 0; a total internal reflection is a
+// mirror ray (kind RLS_RAY_TIR_MIRROR) and counts towards tir_fraction
+template <int G>
+struct GgxRefract : GgxLobe {
+    static constexpr int kWeights = 1;
+    float tir = 0.0f;
+    using GgxLobe::GgxLobe;
+    template <int K>
+    __device__ bool sample(const SlowLds<K> &slow, int k, bool ok, float, float, EmitRay &r)
+    {
+        if (ok) {
+            const V3 M = ggx_vndf_pop<K>(slow, k, w, g.fr);
+            if (!ggx_refract(g, M, r.dir)) { tir += 1.0f; r.kind = RLS_RAY_TIR_MIRROR; }
+            r.w[0] = ggx_sample_weight(g, g.view, r.dir, M);         // src/rlGgx.h:241
+        }
+        return !(r.w[0] == 0.0f);
+    }
+    __device__ float side(int spp)
+    {
+        if (G > 1) tir = group_sum<G>(tir);                          // a count: integers, any order
+        return tir * (1.0f / (float)spp);                            // as ggx_refract_loop: tir *= inv
+    }
+};
+
+// One lobe of rls_disney_integrate's sample loop (integrate.hip, disney_integrate_body): SPEC = 0 the diffuse lobe
+// (scramble streams +0/1, no rare branches: no push phase, no SlowLds), SPEC = 1 the specular lobe (+2/3, its rare branches
 // packed through SlowLds as there).  A sample is valid where pdf > 1e-4 (src/rlDisney.cpp:309) and queued where it is valid
-// and f / pdf is not 0 in all three channels: what it would add to the integrator's sum is then not +0.
-template <int G, int SPEC, int FAST_MATH>
-__device__ __forceinline__ void disney_emit_body(const DisneyEmitIO a, SlowLds<RLS_SPEC_BLOCK> *slow)
-{
-    constexpr int K = RLS_SPEC_BLOCK;
-    __shared__ uint32_t tab[2][kMaxSpp];
-    stage_libm_tables();
-    stage_table(tab, a.spp);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
-        const bool live = i < a.n;
-        const int64_t ii = live ? i : a.n - 1;
-        const DisneyEmitIO al = RLS_INT_ARGS(a);               // the closure's planes re-read per point, as there
+// and f / pdf is not 0 in all three channels: what it would add to the integrator's sum is then not +0.  The side output is
+// the lobe's valid count.
+template <int G, bool SPEC>
+struct DisneyLobe {
+    static constexpr int kStream = SPEC ? 2 : 0;
+    static constexpr bool kPush = SPEC;
+    static constexpr int kWeights = 3;
+    Disney d;
+    VndfView w;
+    float valid = 0.0f;
+    __device__ DisneyLobe(const EmitIO<rls_disney_closure> &a, int64_t ii)
+    {
+        const EmitIO<rls_disney_closure> al = RLS_INT_ARGS(a);      // the closure's planes re-read per point, as there
         const rls_disney_closure &c = al.c;
         const PIndex<int64_t> pk = pindex(c.materials, ii);
         V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
@@ -205,73 +203,57 @@ __device__ __forceinline__ void disney_emit_body(const DisneyEmitIO a, SlowLds<R
         sc[3] = ldp(c.specular_tint, pk); sc[4] = ldp(c.roughness, pk); sc[5] = ldp(c.anisotropic, pk);
         sc[6] = ldp(c.sheen, pk); sc[7] = ldp(c.sheen_tint, pk); sc[8] = ldp(c.clearcoat, pk);
         sc[9] = ldp(c.clearcoat_gloss, pk);
-        Disney d = disney_make(wo, N, T, br, bg, bb, sc);
+        d = disney_make(wo, N, T, br, bg, bb, sc);
         disney_prepare(d);
-        VndfView w = vndf_view(d.view, d.fr, d.ax, d.ay);
-        const uint32_t sx = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + (SPEC ? 2 : 0));
-        const uint32_t sy = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + (SPEC ? 3 : 1));
-
-        float valid = 0.0f;
-        int run = 0;
-        for (int s0 = sub; s0 - sub < a.spp; s0 += K * G) {      // the same trip count in every lane
-            if constexpr (SPEC) {
-                int cnt = 0;
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const int s = s0 + k * G;
-                    const bool ok = s < a.spp;
-                    const int sc = ok ? s : 0;
-                    disney_spec_push<K>(*slow, k, cnt, ok, d, w, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
-                }
-                slow_run<K>(*slow, cnt);
-            }
-#pragma unroll 1
-            for (int k = 0; k < K; k++) {
-                const int s = s0 + k * G;
-                float tR = 0.0f, tG = 0.0f, tB = 0.0f;
-                V3 L = mk(0.0f, 0.0f, 0.0f);
-                if (s < a.spp) {
-                    float r, g, b, pdf;
-                    if constexpr (SPEC) {
-                        L = disney_spec_pop<K>(*slow, k, d, w);
-                        disney_eval_pdf<false, true, true>(d, L, r, g, b, pdf);
-                    } else {
-                        L = cosine_hemisphere(d.fr, bits_u01(tab[0][s] ^ sx), bits_u01(tab[1][s] ^ sy));
-                        disney_eval_pdf<true, true, true>(d, L, r, g, b, pdf);
-                    }
-                    if (pdf > kEps) { tR = r / pdf; tG = g / pdf; tB = b / pdf; valid += 1.0f; }
-                }
-                const bool keep = s < a.spp && !(tR == 0.0f && tG == 0.0f && tB == 0.0f);
-                const int rank = group_rank<G>(keep, sub, run);
-                if (live && s < a.spp) {
-                    const int64_t slot = (int64_t)s * a.n + i;
-                    if (keep) {
-                        a.dir[0][slot] = L.x; a.dir[1][slot] = L.y; a.dir[2][slot] = L.z;
-                        a.w[0][slot] = tR; a.w[1][slot] = tG; a.w[2][slot] = tB;
-                    }
-                    a.tag[slot] = keep ? (uint16_t)rank : kDropped;
-                }
-            }
-        }
-        if (G > 1) valid = group_sum<G>(valid);                     // a count: integers, any order
-        if (live && sub == 0) {
-            a.count[i] = run;
-            if (a.valid) stg(a.valid, i, valid);
-        }
+        w = vndf_view(d.view, d.fr, d.ax, d.ay);
     }
-}
+    template <int K>
+    __device__ void push(SlowLds<K> &slow, int k, int &cnt, bool ok, float rx, float ry)
+    {
+        disney_spec_push<K>(slow, k, cnt, ok, d, w, rx, ry);
+    }
+    template <int K>
+    __device__ bool sample(const SlowLds<K> &slow, int k, bool ok, float rx, float ry, EmitRay &t)
+    {
+        if (ok) {
+            float r, g, b, pdf;
+            if constexpr (SPEC) {
+                t.dir = disney_spec_pop<K>(slow, k, d, w);
+                disney_eval_pdf<false, true, true>(d, t.dir, r, g, b, pdf);
+            } else {
+                t.dir = cosine_hemisphere(d.fr, rx, ry);
+                disney_eval_pdf<true, true, true>(d, t.dir, r, g, b, pdf);
+            }
+            if (pdf > kEps) { t.w[0] = r / pdf; t.w[1] = g / pdf; t.w[2] = b / pdf; valid += 1.0f; }
+        }
+        return !(t.w[0] == 0.0f && t.w[1] == 0.0f && t.w[2] == 0.0f);
+    }
+    __device__ float side(int)
+    {
+        if (G > 1) valid = group_sum<G>(valid);                      // a count: integers, any order
+        return valid;
+    }
+};
 
 template <int G, int FAST_MATH = RLS_FAST>
-__global__ RLS_INT_ATTR void disney_diffuse_emit_kernel(DisneyEmitIO a)
+__global__ RLS_INT_ATTR void ggx_glossy_emit_kernel(EmitIO<rls_ggx_closure> a)
 {
-    disney_emit_body<G, 0, FAST_MATH>(a, nullptr);                // (no rare branches in the cosine lobe: no queue)
+    emit_points<G, GgxGlossy<G>>(a);
 }
-
 template <int G, int FAST_MATH = RLS_FAST>
-__global__ RLS_INT_ATTR void disney_specular_emit_kernel(DisneyEmitIO a)
+__global__ RLS_INT_ATTR void ggx_refract_emit_kernel(EmitIO<rls_ggx_closure> a)
 {
-    __shared__ SlowLds<RLS_SPEC_BLOCK> slow;
-    disney_emit_body<G, 1, FAST_MATH>(a, &slow);
+    emit_points<G, GgxRefract<G>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void disney_diffuse_emit_kernel(EmitIO<rls_disney_closure> a)
+{
+    emit_points<G, DisneyLobe<G, false>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void disney_specular_emit_kernel(EmitIO<rls_disney_closure> a)
+{
+    emit_points<G, DisneyLobe<G, true>>(a);
 }
 
 // integrateScatter's probe rays (getProbeRay, src/rlSss.h:224-228) into the dense queue.  Per tile the points' profile,
@@ -475,14 +457,14 @@ __global__ __launch_bounds__(rlsh::kBlock) void trace_compact_kernel(TraceCompac
 #pragma unroll
         for (int u = 0; u < kPer; u++) {
             const int t = (int)threadIdx.x + u * rlsh::kBlock, s = t / pc, p = t - s * pc;
-            src_at[u] = (int64_t)s * a.n + p0 + p;
+            src_at[u] = staging_slot(s, a.n, p0) + p;
             tag[u] = t < slots ? a.tag[src_at[u]] : kDropped;
         }
         int pos[kPer];
 #pragma unroll
         for (int u = 0; u < kPer; u++) {
             const int t = (int)threadIdx.x + u * rlsh::kBlock, s = t / pc, p = t - s * pc;
-            pos[u] = tag[u] == kDropped ? -1 : (int)(off[p] - base) + (tag[u] & 0xFF);
+            pos[u] = tag[u] == kDropped ? -1 : (int)(off[p] - base) + tag_rank(tag[u]);
         }
         for (int plane = 0; plane < 3 + NW; plane++) {
             const float *src = plane < 3 ? a.sdir[plane] : a.sw[plane - 3];
@@ -506,7 +488,7 @@ __global__ __launch_bounds__(rlsh::kBlock) void trace_compact_kernel(TraceCompac
 #pragma unroll
             for (int u = 0; u < kPer; u++) {
                 const int t = (int)threadIdx.x + u * rlsh::kBlock, s = t / pc, p = t - s * pc;
-                if (pos[u] >= 0) ib[pos[u]] = (uint32_t)p | (uint32_t)s << 8 | (uint32_t)(tag[u] >> 8) << 16;
+                if (pos[u] >= 0) ib[pos[u]] = (uint32_t)p | (uint32_t)s << 8 | (uint32_t)tag_kind(tag[u]) << 16;
             }
             __syncthreads();
 #pragma unroll
@@ -572,37 +554,42 @@ rls_status launch_tiles(rls_context *ctx, void (*kernel)(IO), const IO &io, cons
     return rlsh::check_launch(name, RLS_FAST);
 }
 
+// the kernel selection of each verb (rls_internal.hpp, RLS_FLAVOURS): the emits by lane group g, the rlSss verbs by nothing
+rls_status launch_ggx_glossy_emit(rls_context *ctx, int g, const EmitIO<rls_ggx_closure> &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(ggx_glossy_emit_kernel), g, io, name);
+}
+rls_status launch_ggx_refract_emit(rls_context *ctx, int g, const EmitIO<rls_ggx_closure> &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(ggx_refract_emit_kernel), g, io, name);
+}
+rls_status launch_disney_diffuse_emit(rls_context *ctx, int g, const EmitIO<rls_disney_closure> &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(disney_diffuse_emit_kernel), g, io, name);
+}
+rls_status launch_disney_specular_emit(rls_context *ctx, int g, const EmitIO<rls_disney_closure> &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(disney_specular_emit_kernel), g, io, name);
+}
+rls_status launch_sss_probe_emit(rls_context *ctx, int, const SssEmitIO &io, const char *name)
+{
+    return launch_tiles(ctx, sss_probe_emit_kernel<>, io, name);
+}
+rls_status launch_sss_scatter_resolve(rls_context *ctx, int, const SssResolveIO &io, const char *name)
+{
+    return launch_tiles(ctx, sss_scatter_resolve_kernel<>, io, name);
+}
+
 } // namespace
 
-#if RLS_FAST
-RLS_HIDDEN rls_status rls_trace_fast_sss_probe_emit(rls_context *ctx, const SssEmitIO *io)
-{
-    return launch_tiles(ctx, sss_probe_emit_kernel<>, *io, "rls_trace_sss_probe_emit");
-}
-RLS_HIDDEN rls_status rls_trace_fast_sss_scatter_resolve(rls_context *ctx, const SssResolveIO *io)
-{
-    return launch_tiles(ctx, sss_scatter_resolve_kernel<>, *io, "rls_trace_sss_scatter_resolve");
-}
-RLS_HIDDEN rls_status rls_trace_fast_glossy_emit(rls_context *ctx, int g, const TraceEmitIO *io)
-{
-    return launch_g(ctx, RLS_G_FAMILY(ggx_glossy_emit_kernel), g, *io, "rls_trace_ggx_glossy_emit");
-}
-RLS_HIDDEN rls_status rls_trace_fast_refract_emit(rls_context *ctx, int g, const TraceEmitIO *io)
-{
-    return launch_g(ctx, RLS_G_FAMILY(ggx_refract_emit_kernel), g, *io, "rls_trace_ggx_refract_emit");
-}
-RLS_HIDDEN rls_status rls_trace_fast_disney_emit(rls_context *ctx, int g, int lobe, const DisneyEmitIO *io)
-{
-    return lobe == RLS_RAY_DIFFUSE
-        ? launch_g(ctx, RLS_G_FAMILY(disney_diffuse_emit_kernel), g, *io, "rls_trace_disney_emit")
-        : launch_g(ctx, RLS_G_FAMILY(disney_specular_emit_kernel), g, *io, "rls_trace_disney_emit");
-}
-#else
-RLS_HIDDEN rls_status rls_trace_fast_glossy_emit(rls_context *ctx, int g, const TraceEmitIO *io);
-RLS_HIDDEN rls_status rls_trace_fast_refract_emit(rls_context *ctx, int g, const TraceEmitIO *io);
-RLS_HIDDEN rls_status rls_trace_fast_disney_emit(rls_context *ctx, int g, int lobe, const DisneyEmitIO *io);
-RLS_HIDDEN rls_status rls_trace_fast_sss_probe_emit(rls_context *ctx, const SssEmitIO *io);
-RLS_HIDDEN rls_status rls_trace_fast_sss_scatter_resolve(rls_context *ctx, const SssResolveIO *io);
+RLS_FLAVOURS(ggx_glossy_emit, EmitIO<rls_ggx_closure>)
+RLS_FLAVOURS(ggx_refract_emit, EmitIO<rls_ggx_closure>)
+RLS_FLAVOURS(disney_diffuse_emit, EmitIO<rls_disney_closure>)
+RLS_FLAVOURS(disney_specular_emit, EmitIO<rls_disney_closure>)
+RLS_FLAVOURS(sss_probe_emit, SssEmitIO)
+RLS_FLAVOURS(sss_scatter_resolve, SssResolveIO)
+
+#if !RLS_FAST
 
 namespace {
 
@@ -631,26 +618,37 @@ inline Staging staging(void *base, int64_t n, int spp)
     return s;
 }
 
-// Every emit: the argument checks (lobe_ok: the rlDisney lobe, checked after spp_n), the empty queue of n == 0, the staging
-// in the caller's scratch, then launch(staging, G) -- the closure's emit kernel -- and the steps the closures share: the
-// per-point counts scanned in place into offsets, the kept records compacted into the queue (nw weight planes).  name: the
-// entry point.
-template <class Closure, class Launch>
-rls_status emit(rls_context *ctx, int64_t n, const Closure *c, int spp_n, bool lobe_ok, const rls_ray_queue *q, int nw,
-                const char *name, Launch launch)
+// The checks every queue verb opens with, in this order; fn: the name its messages carry
+rls_status check_batch(const char *fn, const rls_context *ctx, int64_t n, int spp_n)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(n <= (int64_t)UINT32_MAX, "n > 2^32 - 1 (the queue's point index is 32-bit)");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
+    RLS_REQUIRE_IN(fn, ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE_IN(fn, n >= 0, "n < 0");
+    RLS_REQUIRE_IN(fn, n <= (int64_t)UINT32_MAX, "n > 2^32 - 1 (the queue's point index is 32-bit)");
+    RLS_REQUIRE_IN(fn, spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
+    return RLS_OK;
+}
+
+// the queue of an empty batch: offsets[0] = 0
+rls_status empty_queue(rls_context *ctx, int64_t *offsets, const char *name)
+{
+    hipLaunchKernelGGL(trace_scan_totals_kernel, dim3(1), dim3(rlsh::kBlock), 0, ctx->stream, offsets, (int64_t)0, offsets);
+    return rlsh::check_launch(name);
+}
+
+// Every emit: the argument checks (lobe_ok: the rlDisney lobe, checked after spp_n), the empty queue of n == 0, the staging
+// in the caller's scratch, then the closure's emit kernel (dispatch, with G for the batch) and the steps the closures share:
+// the per-point counts scanned in place into offsets, the kept records compacted into the queue (nw weight planes).  side:
+// the per-point side output; name: the entry point.
+template <class Closure>
+rls_status emit(rls_context *ctx, int64_t n, const Closure *c, int spp_n, uint32_t seed, uint64_t first_index, bool lobe_ok,
+                const rls_ray_queue *q, float *side, int nw, const char *name,
+                rls_status (*dispatch)(rls_context *, int, const EmitIO<Closure> &, const char *))
+{
+    if (rls_status s = check_batch(__func__, ctx, n, spp_n)) return s;
     RLS_REQUIRE(lobe_ok, "lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY");
     RLS_REQUIRE(q != nullptr && q->offsets != nullptr, "queue or queue.offsets is NULL");
     const int spp = spp_n * spp_n;
-    if (n == 0) {                                        // an empty queue: offsets[0] = 0
-        hipLaunchKernelGGL(trace_scan_totals_kernel, dim3(1), dim3(rlsh::kBlock), 0, ctx->stream, q->offsets, (int64_t)0,
-                           q->offsets);
-        return rlsh::check_launch(name);
-    }
+    if (n == 0) return empty_queue(ctx, q->offsets, name);
     if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(q->dir), "queue.dir plane is NULL");
     RLS_REQUIRE(nw == 1 ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
@@ -658,7 +656,12 @@ rls_status emit(rls_context *ctx, int64_t n, const Closure *c, int spp_n, bool l
     const Staging st = staging(q->scratch, n, spp);
     RLS_REQUIRE(q->scratch != nullptr && q->scratch_bytes >= st.bytes, "queue.scratch is NULL or smaller than rls_trace_scratch_bytes");
 
-    rls_status s = launch(st, pick_group(ctx, n, spp));
+    EmitIO<Closure> io = {};
+    io.c = *c;
+    for (int k = 0; k < 3; k++) { io.dir[k] = st.dir[k]; io.w[k] = st.w[k]; }
+    io.tag = st.tag; io.count = q->offsets; io.side = side;
+    io.n = n; io.spp = spp; io.seed = seed; io.first = first_index;
+    rls_status s = dispatch(ctx, pick_group(ctx, n, spp), io, name);
     if (s != RLS_OK) return s;
 
     // offsets: the counts scanned in place
@@ -680,24 +683,6 @@ rls_status emit(rls_context *ctx, int64_t n, const Closure *c, int spp_n, bool l
     if (nw == 1) hipLaunchKernelGGL(trace_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
     else hipLaunchKernelGGL(trace_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
     return rlsh::check_launch("trace_compact_kernel");
-}
-
-rls_status ggx_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed, uint64_t first_index,
-                    const rls_ray_queue *q, float *side, bool refract)
-{
-    const char *name = refract ? "rls_trace_ggx_refract_emit" : "rls_trace_ggx_glossy_emit";
-    return emit(ctx, n, c, spp_n, true, q, refract ? 1 : 3, name, [&](const Staging &st, int g) {
-        TraceEmitIO io = {};
-        io.c = *c;
-        for (int k = 0; k < 3; k++) { io.dir[k] = st.dir[k]; io.w[k] = st.w[k]; }
-        io.tag = st.tag; io.count = q->offsets; io.side = side;
-        io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
-        if (refract)
-            return ctx->fast ? rls_trace_fast_refract_emit(ctx, g, &io)
-                             : launch_g(ctx, RLS_G_FAMILY(ggx_refract_emit_kernel), g, io, name);
-        return ctx->fast ? rls_trace_fast_glossy_emit(ctx, g, &io)
-                         : launch_g(ctx, RLS_G_FAMILY(ggx_glossy_emit_kernel), g, io, name);
-    });
 }
 
 rls_status resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, int spp_n, rls_crgb radiance, rls_rgb out, bool refract)
@@ -734,30 +719,21 @@ rls_status rls_trace_scratch_bytes(int64_t n, int spp_n, size_t *bytes)
 rls_status rls_trace_ggx_glossy_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed,
                                      uint64_t first_index, const rls_ray_queue *q, float *avg_reflect_weight)
 {
-    return ggx_emit(ctx, n, c, spp_n, seed, first_index, q, avg_reflect_weight, false);
+    return emit(ctx, n, c, spp_n, seed, first_index, true, q, avg_reflect_weight, 3, __func__, dispatch_ggx_glossy_emit);
 }
 
 rls_status rls_trace_ggx_refract_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, int spp_n, uint32_t seed,
                                       uint64_t first_index, const rls_ray_queue *q, float *tir_fraction)
 {
-    return ggx_emit(ctx, n, c, spp_n, seed, first_index, q, tir_fraction, true);
+    return emit(ctx, n, c, spp_n, seed, first_index, true, q, tir_fraction, 1, __func__, dispatch_ggx_refract_emit);
 }
 
 rls_status rls_trace_disney_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, int lobe, int spp_n, uint32_t seed,
                                  uint64_t first_index, const rls_ray_queue *q, float *valid_count)
 {
     const bool lobe_ok = lobe == RLS_RAY_DIFFUSE || lobe == RLS_RAY_GLOSSY;
-    return emit(ctx, n, c, spp_n, lobe_ok, q, 3, "rls_trace_disney_emit", [&](const Staging &st, int g) {
-        DisneyEmitIO io = {};
-        io.c = *c;
-        for (int k = 0; k < 3; k++) { io.dir[k] = st.dir[k]; io.w[k] = st.w[k]; }
-        io.tag = st.tag; io.count = q->offsets; io.valid = valid_count;
-        io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
-        if (ctx->fast) return rls_trace_fast_disney_emit(ctx, g, lobe, &io);
-        return lobe == RLS_RAY_DIFFUSE
-            ? launch_g(ctx, RLS_G_FAMILY(disney_diffuse_emit_kernel), g, io, "rls_trace_disney_emit")
-            : launch_g(ctx, RLS_G_FAMILY(disney_specular_emit_kernel), g, io, "rls_trace_disney_emit");
-    });
+    return emit(ctx, n, c, spp_n, seed, first_index, lobe_ok, q, valid_count, 3, __func__,
+                lobe == RLS_RAY_DIFFUSE ? dispatch_disney_diffuse_emit : dispatch_disney_specular_emit);
 }
 
 rls_status rls_trace_ggx_glossy_resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, rls_crgb radiance, rls_rgb sum)
@@ -774,17 +750,10 @@ rls_status rls_trace_ggx_refract_resolve(rls_context *ctx, int64_t n, const rls_
 rls_status rls_trace_sss_probe_emit(rls_context *ctx, int64_t n, const rls_sss_closure *c, rls_cvec3 P, int spp_n,
                                     uint32_t seed, uint64_t first_index, const rls_probe_queue *q)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(n <= (int64_t)UINT32_MAX, "n > 2^32 - 1 (the queue's point index is 32-bit)");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
+    if (rls_status s = check_batch(__func__, ctx, n, spp_n)) return s;
     RLS_REQUIRE(q != nullptr && q->offsets != nullptr, "queue or queue.offsets is NULL");
     const int spp = spp_n * spp_n;
-    if (n == 0) {                                        // an empty queue: offsets[0] = 0
-        hipLaunchKernelGGL(trace_scan_totals_kernel, dim3(1), dim3(rlsh::kBlock), 0, ctx->stream, q->offsets, (int64_t)0,
-                           q->offsets);
-        return rlsh::check_launch(__func__);
-    }
+    if (n == 0) return empty_queue(ctx, q->offsets, __func__);
     if (rls_status s = rlsh::check_closure(__func__, c, true)) return s;
     RLS_REQUIRE(rlsh::has3(P), "P plane is NULL");
     RLS_REQUIRE(rlsh::has3(q->origin) && rlsh::has3(q->dir) && q->maxdist != nullptr,
@@ -793,18 +762,14 @@ rls_status rls_trace_sss_probe_emit(rls_context *ctx, int64_t n, const rls_sss_c
     SssEmitIO io = {};
     io.c = *c; io.P = P; io.q = *q;
     io.n = n; io.spp = spp; io.tile_points = sss_emit_tile_points(spp); io.seed = seed; io.first = first_index;
-    return ctx->fast ? rls_trace_fast_sss_probe_emit(ctx, &io)
-                     : launch_tiles(ctx, sss_probe_emit_kernel<>, io, "rls_trace_sss_probe_emit");
+    return dispatch_sss_probe_emit(ctx, 0, io, __func__);
 }
 
 rls_status rls_trace_sss_scatter_resolve(rls_context *ctx, int64_t n, const rls_sss_closure *c, rls_cvec3 P, int spp_n,
                                          const rls_probe_queue *q, const rls_probe_hits *h, int use_cavity_fade,
                                          int literal_matrix, rls_rgb result, float *mean_depth)
 {
-    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
-    RLS_REQUIRE(n >= 0, "n < 0");
-    RLS_REQUIRE(n <= (int64_t)UINT32_MAX, "n > 2^32 - 1 (the queue's point index is 32-bit)");
-    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
+    if (rls_status s = check_batch(__func__, ctx, n, spp_n)) return s;
     RLS_REQUIRE(q != nullptr, "queue is NULL");
     RLS_REQUIRE(h != nullptr, "hits is NULL");
     RLS_REQUIRE(h->max_hits >= 1 && h->max_hits <= RLS_MAX_PROBE_HITS, "hits.max_hits must be in [1, 12]");
@@ -821,8 +786,7 @@ rls_status rls_trace_sss_scatter_resolve(rls_context *ctx, int64_t n, const rls_
     io.c = *c; io.P = P; io.h = *h; io.result = result; io.depth = mean_depth;
     io.n = n; io.spp = spp; io.tile_points = sss_resolve_tile_points(spp);
     io.cavity = use_cavity_fade != 0; io.literal = literal_matrix != 0;
-    return ctx->fast ? rls_trace_fast_sss_scatter_resolve(ctx, &io)
-                     : launch_tiles(ctx, sss_scatter_resolve_kernel<>, io, "rls_trace_sss_scatter_resolve");
+    return dispatch_sss_scatter_resolve(ctx, 0, io, __func__);
 }
 
 } // extern "C"
