@@ -16,6 +16,21 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 
+# a spin kernel of this many clock cycles (milliseconds) ahead of a timed region: the HIP events time the device work alone
+SPIN_CYCLES = 10_000_000
+
+
+def _event_ms(gpu, fn):
+    """HIP-event time of the launches fn() enqueues.  With an idle queue the start event completes at once and the window
+    then holds whatever time the host takes to enqueue the work (a pause of the host thread included); a spin kernel ahead
+    of it keeps the queue busy until the work is queued behind the start event."""
+    torch.cuda._sleep(SPIN_CYCLES)
+    gpu.timer_start()
+    fn()
+    gpu.timer_stop()
+    return gpu.timer_elapsed_ms()
+
+
 @pytest.mark.parametrize("name,log2n", [("ggx_reflect_refract", 22), ("sss_probe", 22), ("skin", 21), ("disney_integrate", 18)])
 def test_stamped_instantiation_same_bits_and_plausible_clock(gpu, name, log2n):
     from bench_workloads import make_workload
@@ -24,19 +39,13 @@ def test_stamped_instantiation_same_bits_and_plausible_clock(gpu, name, log2n):
     outs = list(wl.outputs.values()) if isinstance(wl.outputs, dict) else list(wl.outputs)
     for _ in range(3):
         wl.launch()
-    gpu.timer_start()
-    wl.launch()
-    gpu.timer_stop()
-    plain_ms = gpu.timer_elapsed_ms()
+    plain_ms = _event_ms(gpu, wl.launch)
     want = [R.checksum(gpu, t) for t in outs]
     for t in outs:
         t.zero_()
     gpu.clock_stamps_begin()
     try:
-        gpu.timer_start()
-        wl.launch()
-        gpu.timer_stop()
-        stamped_ms = gpu.timer_elapsed_ms()
+        stamped_ms = _event_ms(gpu, wl.launch)
         st = gpu.clock_stamps_read()
     finally:
         gpu.clock_stamps_end()

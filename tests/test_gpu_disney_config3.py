@@ -232,7 +232,8 @@ def test_packed_rare_branches_with_every_lane_asking(gpu, oracle):
     time (rls_loops.hpp, SlowLds).  Here every lane asks at every sample -- views along the normal make every visible-
     normal sample take the uniform-slope fallback, and clearcoat = 1 sends a fifth of the samples to the clearcoat lobe
     -- so the queue holds 256 requests per pass of four samples and is worked off in four rounds; also a sample count (9)
-    that is not a multiple of four, and G > 1 (the lanes of a group hold different samples)."""
+    that is not a multiple of four, and G > 1 (the lanes of a group hold different samples) in reduced mode, the mode that
+    runs G-lane groups."""
     n, seed = 1 << 11, 77
     wo, N, T = cases.frame(cases.SEED_PARITY, n)
     wo = N.copy()                                                      # theta = 0: nearNormal in every lane
@@ -248,14 +249,27 @@ def test_packed_rare_branches_with_every_lane_asking(gpu, oracle):
             alt = _with_group(g, lambda: {k: host(v) for k, v in d.integrate(spp_n, seed, streamed=True).items()})
             for k in ("wi", "f", "pdf"):                               # the samples themselves do not depend on G
                 assert np.array_equal(alt[k].view(np.uint32), got[k].view(np.uint32)), (g, k)
+        # streamed mode runs one lane per point whatever is asked (integrate.hip): the G-lane groups run in reduced mode
+        red = _with_group(1, lambda: {k: host(v) for k, v in d.integrate(spp_n, seed).items()})
+        for k in red:
+            cases.assert_tight(cases.summarize(cases.rel_err(red[k], ref[k])), ("every lane asks, reduced", spp_n, k))
+        for g in (4, 16, 64):
+            alt = _with_group(g, lambda: {k: host(v) for k, v in d.integrate(spp_n, seed).items()})
+            for k in red:
+                cases.assert_same_bits(alt[k], red[k], ("every lane asks, reduced", spp_n, g, k))
     # the rlGgx loops: the same view, low roughness
     from gpu_util import ggx_oracle, ggx_sampler
     g = cases.ggx_mixed(cases.SEED_PARITY, n)
     g = dict(g, wo=wo, N=N, T=T)
     ref = ggx_oracle(oracle, g).integrate(3, seed)
-    got = _with_group(1, lambda: [host(t) for t in ggx_sampler(gpu, g).integrate(3, seed)])
+    gs = ggx_sampler(gpu, g)
+    got = _with_group(1, lambda: [host(t) for t in gs.integrate(3, seed)])
     for nm, a, b in zip(("sum", "avg"), got, ref):
         cases.assert_tight(cases.summarize(cases.rel_err(a, b)), ("ggx every lane asks", nm))
+    for gw in (4, 16, 64):
+        alt = _with_group(gw, lambda: [host(t) for t in gs.integrate(3, seed)])
+        for nm, a, b in zip(("sum", "avg"), alt, got):
+            cases.assert_same_bits(a, b, ("ggx every lane asks", gw, nm))
 
 
 def _border_check(a, b, is_count, what):
