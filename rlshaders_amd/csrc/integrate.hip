@@ -37,23 +37,11 @@ __global__ RLS_INT_ATTR void ggx_integrate_kernel(GgxIntIO a)
     __shared__ SlowLds<RLS_SPEC_BLOCK> slow;
     stage_libm_tables();   // atanf range table (+ expf / logf / powf tables) -> LDS
     stage_table(tab, a.spp);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    // all lanes of a wave iterate the same number of times (shuffles need every lane live)
-    const int64_t rounds = (a.n + stride - 1) / stride;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
+    RLS_POINT_WALK(G, a.n)
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
-        const rls_ggx_closure &c = a.c;
-        const PIndex<int64_t> pk = pindex(c.materials, ii);      // parameters by reference (rls_material_index)
-        V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
-        float kr, kg, kb;
-        ldrgb(c.KsColor, pk, kr, kg, kb);
-        bool exiting = c.exiting ? (c.exiting[ii] != 0) : false;
-        Ggx g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp(c.ior, pk), ldp(c.specularRoughness, pk),
-                         ldp(c.anisotropic, pk));
+        RLS_GGX_LOAD(g, a.c, ii)
         VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
         const uint32_t sx = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream);
         const uint32_t sy = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + 1);
@@ -78,17 +66,14 @@ __device__ __forceinline__ void disney_integrate_body(const DisneyIntIO a)
     __shared__ SlowLds<K> slow;
     stage_libm_tables();   // powf / logf tables -> LDS (EXACT mode)
     stage_table(tab, a.spp);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
+    RLS_POINT_WALK(G, a.n)
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
         // the closure's 22 plane pointers re-read from the kernarg segment here, the 8 output pointers at the stores
         // (rls_internal.hpp, reload_args): none of them stays in a scalar register across the sample loop
         const DisneyIntIO al = RLS_INT_ARGS(a);
+        // (written out, not RLS_DISNEY_LOAD(d, al.c, ii): with the macro's order of loads this BASELINE kernel compiles to other code)
         const rls_disney_closure &c = al.c;
         const PIndex<int64_t> pk = pindex(c.materials, ii);      // parameters by reference (rls_material_index)
         V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
@@ -187,22 +172,11 @@ __global__ RLS_INT_ATTR void ggx_refract_integrate_kernel(RefractIntIO a)
     __shared__ SlowLds<RLS_SPEC_BLOCK> slow;
     stage_libm_tables();   // atanf range table (+ expf / logf / powf tables) -> LDS
     stage_table(tab, a.spp);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
+    RLS_POINT_WALK(G, a.n)
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
-        const rls_ggx_closure &c = a.c;
-        const PIndex<int64_t> pk = pindex(c.materials, ii);      // parameters by reference (rls_material_index)
-        V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
-        float kr, kg, kb;
-        ldrgb(c.KsColor, pk, kr, kg, kb);
-        bool exiting = c.exiting ? (c.exiting[ii] != 0) : false;
-        Ggx g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp(c.ior, pk), ldp(c.specularRoughness, pk),
-                         ldp(c.anisotropic, pk));
+        RLS_GGX_LOAD(g, a.c, ii)
         float acc, tir;
         if (a.traced) {
             VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
@@ -221,37 +195,44 @@ __global__ RLS_INT_ATTR void ggx_refract_integrate_kernel(RefractIntIO a)
 
 #if RLS_DIAGNOSTICS
 // BASELINE config 3 (one lane per point) under rls_diag_clock_stamps_begin: the stamped instantiation
-inline rls_status launch_disney_stamped(rls_context *ctx, const rlsh::DisneyIntIO &io, unsigned long long *stamps, const char *name)
+inline rls_status launch_disney_stamped(rls_context *ctx, const DisneyIntIO &io, unsigned long long *stamps)
 {
     hipLaunchKernelGGL(disney_integrate_kernel_stamped<1>, rlsh::grid_for(ctx, io.n, rlsh::kBlock), dim3(rlsh::kBlock), 0, ctx->stream,
                        io, stamps);
-    return rlsh::check_launch(name, RLS_FAST);
+    return rlsh::check_launch("rls_disney_integrate[stamped]", RLS_FAST);
 }
 #endif
+
+#if !RLS_FAST
+// A code object holds its kernels in the order the host code first names them, and the frozen unit ids
+// (tests/test_profile_binding.py) cover that order: stamped, then in the EXACT unit ggx_refract_integrate_kernel first (its
+// entry point used to name it first), in the FAST unit last.  Named here for that order alone.
+[[maybe_unused]] void (*const kExactUnitOrder[])(RefractIntIO) = { RLS_G_FAMILY(ggx_refract_integrate_kernel) };
+#endif
+
+rls_status launch_ggx_integrate(rls_context *ctx, int g, const GgxIntIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(ggx_integrate_kernel), g, io, name);
+}
+rls_status launch_disney_integrate(rls_context *ctx, int g, const DisneyIntIO &io, const char *name)
+{
+#if RLS_DIAGNOSTICS
+    if (unsigned long long *stamps = g == 1 ? rlsh::stamps_for_launch(ctx) : nullptr) return launch_disney_stamped(ctx, io, stamps);
+#endif
+    return launch_g(ctx, RLS_G_FAMILY(disney_integrate_kernel), g, io, name);
+}
+rls_status launch_ggx_refract_integrate(rls_context *ctx, int g, const RefractIntIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(ggx_refract_integrate_kernel), g, io, name);
+}
 
 } // namespace
 
-#if RLS_FAST
-RLS_HIDDEN rls_status rls_fast_ggx_integrate(rls_context *ctx, int g, const rlsh::GgxIntIO *io)
-{
-    return launch_g(ctx, RLS_G_FAMILY(ggx_integrate_kernel), g, *io, "rls_ggx_integrate");
-}
-RLS_HIDDEN rls_status rls_fast_disney_integrate(rls_context *ctx, int g, const rlsh::DisneyIntIO *io)
-{
-#if RLS_DIAGNOSTICS
-    if (unsigned long long *stamps = g == 1 ? rlsh::stamps_for_launch(ctx) : nullptr)
-        return launch_disney_stamped(ctx, *io, stamps, "rls_disney_integrate[stamped]");
-#endif
-    return launch_g(ctx, RLS_G_FAMILY(disney_integrate_kernel), g, *io, "rls_disney_integrate");
-}
-RLS_HIDDEN rls_status rls_fast_ggx_refract_integrate(rls_context *ctx, int g, const rlsh::RefractIntIO *io)
-{
-    return launch_g(ctx, RLS_G_FAMILY(ggx_refract_integrate_kernel), g, *io, "rls_ggx_integrate_refract");
-}
-#else
-RLS_HIDDEN rls_status rls_fast_ggx_integrate(rls_context *ctx, int g, const rlsh::GgxIntIO *io);
-RLS_HIDDEN rls_status rls_fast_disney_integrate(rls_context *ctx, int g, const rlsh::DisneyIntIO *io);
-RLS_HIDDEN rls_status rls_fast_ggx_refract_integrate(rls_context *ctx, int g, const rlsh::RefractIntIO *io);
+RLS_FLAVOURS(ggx_integrate, rlsh::GgxIntIO)
+RLS_FLAVOURS(disney_integrate, rlsh::DisneyIntIO)
+RLS_FLAVOURS(ggx_refract_integrate, rlsh::RefractIntIO)
+
+#if !RLS_FAST
 
 extern "C" {
 
@@ -264,12 +245,10 @@ rls_status rls_ggx_integrate_refract(rls_context *ctx, int64_t n, const rls_ggx_
     if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(result), "NULL output plane");
     rlsh::RefractIntIO io = {};
-    io.c = *c; io.env[0] = env[0]; io.env[1] = env[1]; io.env[2] = env[2]; io.traced = traced ? 1 : 0;
+    io.c = *c; copy_env(io.env, env); io.traced = traced ? 1 : 0;
     io.result = result; io.tir = tir_fraction;
-    io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
-    int g = traced ? pick_group(ctx, n, io.spp) : 1;
-    if (ctx->fast) return rls_fast_ggx_refract_integrate(ctx, g, &io);
-    return launch_g(ctx, RLS_G_FAMILY(ggx_refract_integrate_kernel), g, io, "rls_ggx_integrate_refract");
+    set_loop(io, n, spp_n, seed, first_index);
+    return dispatch_ggx_refract_integrate(ctx, traced ? pick_group(ctx, n, io.spp) : 1, io, "rls_ggx_integrate_refract");
 }
 
 rls_status rls_ggx_integrate(rls_context *ctx, int64_t n, const rls_ggx_closure *c,
@@ -280,10 +259,9 @@ rls_status rls_ggx_integrate(rls_context *ctx, int64_t n, const rls_ggx_closure 
     if (rls_status s = rlsh::check_closure(__func__, c)) return s;
     RLS_REQUIRE(rlsh::has3(sum_f_over_pdf) && avg_reflect_weight, "NULL output plane");
     GgxIntIO io = {};
-    io.c = *c; io.sum = sum_f_over_pdf; io.avgF = avg_reflect_weight; io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
-    int g = pick_group(ctx, n, io.spp);
-    if (ctx->fast) return rls_fast_ggx_integrate(ctx, g, &io);
-    return launch_g(ctx, RLS_G_FAMILY(ggx_integrate_kernel), g, io, "rls_ggx_integrate");
+    io.c = *c; io.sum = sum_f_over_pdf; io.avgF = avg_reflect_weight;
+    set_loop(io, n, spp_n, seed, first_index);
+    return dispatch_ggx_integrate(ctx, pick_group(ctx, n, io.spp), io, "rls_ggx_integrate");
 }
 
 rls_status rls_disney_integrate(rls_context *ctx, int64_t n, const rls_disney_closure *c,
@@ -298,20 +276,14 @@ rls_status rls_disney_integrate(rls_context *ctx, int64_t n, const rls_disney_cl
                 "NULL output plane");
     DisneyIntIO io = {};
     io.c = *c; io.dsum = diffuse_sum; io.dcount = diffuse_count; io.ssum = specular_sum; io.scount = specular_count;
-    io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
+    set_loop(io, n, spp_n, seed, first_index);
     if (stream) {
         RLS_REQUIRE(rlsh::has3(stream->wi) && rlsh::has3(stream->f) && stream->pdf, "NULL streamed-output plane");
         io.st = *stream;
         io.streamed = 1;
     }
     // streamed planes are sample-major: one lane per point keeps every store coalesced
-    int g = io.streamed ? 1 : pick_group(ctx, n, io.spp);
-    if (ctx->fast) return rls_fast_disney_integrate(ctx, g, &io);
-#if RLS_DIAGNOSTICS
-    if (unsigned long long *stamps = g == 1 ? rlsh::stamps_for_launch(ctx) : nullptr)
-        return launch_disney_stamped(ctx, io, stamps, "rls_disney_integrate[stamped]");
-#endif
-    return launch_g(ctx, RLS_G_FAMILY(disney_integrate_kernel), g, io, "rls_disney_integrate");
+    return dispatch_disney_integrate(ctx, io.streamed ? 1 : pick_group(ctx, n, io.spp), io, "rls_disney_integrate");
 }
 
 // Streamed mode in chunks of the point range (2^26 points x 128 triples x 28 B = 241 GB does not fit beside the

@@ -13,23 +13,12 @@ __global__ RLS_INT_ATTR void ggx_direct_kernel(LightIO a)
     __shared__ SlowLds<RLS_SPEC_BLOCK> slow;
     stage_libm_tables();   // atanf range table (+ expf / logf / powf tables) -> LDS
     stage_table(tab, a.spp);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
+    RLS_POINT_WALK(G, a.n)
     const float inv = 1.0f / (float)a.spp;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
-        const rls_ggx_closure &c = a.c;
-        const PIndex<int64_t> pk = pindex(c.materials, ii);      // parameters by reference (rls_material_index)
-        V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
-        float kr, kg, kb;
-        ldrgb(c.KsColor, pk, kr, kg, kb);
-        bool exiting = c.exiting ? (c.exiting[ii] != 0) : false;
-        Ggx g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp(c.ior, pk), ldp(c.specularRoughness, pk),
-                         ldp(c.anisotropic, pk));
+        RLS_GGX_LOAD(g, a.c, ii)
         VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
         OrenNayar on = oren_nayar_make(N, ldp(a.sh.diffuseRoughness, pk));
         const float ks = ldp(a.sh.Ks, pk), kd = ldp(a.sh.Kd, pk);
@@ -53,13 +42,9 @@ __global__ RLS_DISNEY_LIGHT_ATTR void disney_direct_kernel(DisneyLightIO a)
     __shared__ SlowLds<RLS_SPEC_BLOCK> slow;
     stage_libm_tables();
     stage_table(tab, a.spp);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
+    RLS_POINT_WALK(G, a.n)
     const float inv = 1.0f / (float)a.spp;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
         RLS_DISNEY_LOAD(d, a.c, ii)
@@ -103,7 +88,7 @@ rls_status rls_ggx_direct_lighting(rls_context *ctx, int64_t n, const rls_ggx_cl
     LightIO io = {};
     if (rls_status st = copy_lights(lights, n_lights, 1, io.lights, &io.nl)) return st;
     io.c = *c; io.sh = *sh; io.P = P; io.dd = direct_diffuse; io.ds = direct_specular;
-    io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
+    set_loop(io, n, spp_n, seed, first_index);
     return dispatch_ggx_direct(ctx, pick_group(ctx, n, io.spp), io, "rls_ggx_direct_lighting");
 }
 
@@ -117,7 +102,7 @@ rls_status rls_disney_direct_lighting(rls_context *ctx, int64_t n, const rls_dis
     DisneyLightIO io = {};
     if (rls_status st = copy_lights(lights, n_lights, 1, io.lights, &io.nl)) return st;
     io.c = *c; io.P = P; io.dd = direct_diffuse; io.ds = direct_specular;
-    io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
+    set_loop(io, n, spp_n, seed, first_index);
     return dispatch_disney_direct(ctx, pick_group(ctx, n, io.spp), io, "rls_disney_direct_lighting");
 }
 

@@ -3,6 +3,9 @@
 // the samplers' rare branches 64 at a time (SlowLds), and per shading point: integrateGlossy (rlGgx, rlDisney both lobes),
 // integrateRefract, the light loops of rlGgx and rlDisney, SssSampler::integrateScatter over an analytic scene.  Device
 // templates only (everything __forceinline__); the kernels and the C ABI are in the four units.  Citations per function.
+// What every loop kernel and entry point starts with is here once: the walk over the points (RLS_POINT_WALK), the closure
+// of a point (RLS_GGX_LOAD, RLS_DISNEY_LOAD), and on the host the launch by lane group (pick_group, launch_g) and the
+// argument struct's common fields (set_loop, copy_env, copy_lights).  csrc_trace/trace.hip uses them too.
 #pragma once
 #include <stdlib.h>
 
@@ -61,6 +64,23 @@ __device__ __forceinline__ void stage_table(uint32_t (*tab)[kMaxSpp], int spp)
     }
     __syncthreads();
 }
+
+// The walk of a loop kernel over its shading points: G lanes cooperate on one point (lane `sub` of the group takes samples
+// sub, sub + G, ...), a workgroup holds kBlock / G groups, and the groups of the grid stride over [0, n) from `first`:
+//     RLS_POINT_WALK(G, a.n)
+//     for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
+//         const bool live = i < a.n;
+//         const int64_t ii = live ? i : a.n - 1;
+// All lanes of a wave iterate the same number of times, `rounds` (the shuffles of fold / group_sum need every lane live):
+// a group past the end is not live, runs point ii = n - 1 again and stores nothing.
+// (A macro: as a struct filled by a force-inlined constructor or function the same lines reorder an addition in
+// ggx_integrate_kernel, ggx_refract_integrate_kernel, sss_scatter_kernel and skin_integrate_kernel, which then compile to
+// other code; with the loop as a range-for or a for_each taking a lambda every kernel does.)
+#define RLS_POINT_WALK(G, n)                                                                               \
+    const int sub = threadIdx.x % (G);                                                                     \
+    const int64_t stride = (int64_t)gridDim.x * (rlsh::kBlock / (G));                                      \
+    const int64_t rounds = ((n) + stride - 1) / stride;                                                    \
+    const int64_t first = (int64_t)blockIdx.x * (rlsh::kBlock / (G)) + threadIdx.x / (G);
 
 RLS_DEV V3 arr3(const float (&a)[3]) { return mk(a[0], a[1], a[2]); }
 
@@ -473,6 +493,17 @@ __device__ __forceinline__ void ggx_light_loops(const Ggx &g, const VndfView &w,
         out[0] += lt.rad[0] * sR * inv; out[1] += lt.rad[1] * sG * inv; out[2] += lt.rad[2] * sB * inv;
     }
 }
+
+// the rlGgx closure `g` of shading point ii, with what the kernels read beside it: pk, wo, N, T, kr kg kb (a macro, as
+// RLS_DISNEY_LOAD below and for its reason: as a function returning these the rlGgx light loop compiles to other code)
+#define RLS_GGX_LOAD(g, c, ii)                                                                             \
+    const PIndex<int64_t> pk = pindex((c).materials, ii);      /* parameters by reference (rls_material_index) */ \
+    V3 wo = ld3((c).wo, ii), N = ld3((c).N, ii), T = ld3((c).T, ii);                                       \
+    float kr, kg, kb;                                                                                      \
+    ldrgb((c).KsColor, pk, kr, kg, kb);                                                                    \
+    const bool exiting = (c).exiting ? ((c).exiting[ii] != 0) : false;                                     \
+    Ggx g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp((c).ior, pk), ldp((c).specularRoughness, pk),      \
+                     ldp((c).anisotropic, pk));
 
 // ---------------------------------------------------------------------------------------------
 using rlsh::GgxIntIO;
@@ -1007,6 +1038,15 @@ inline rls_status copy_lights(const rls_sphere_light *lights, int n_lights, int 
     *count = n_lights;
     return RLS_OK;
 }
+
+// what every loop entry point writes last into its kernel's argument struct: the batch, the samples per point, the sampler
+template <class IO>
+inline void set_loop(IO &io, int64_t n, int spp_n, uint32_t seed, uint64_t first_index)
+{
+    io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
+}
+// the uniform environment's radiance
+inline void copy_env(float (&dst)[3], const float env[3]) { dst[0] = env[0]; dst[1] = env[1]; dst[2] = env[2]; }
 
 // plane pointers advanced by k points (chunked / sharded calls)
 inline rls_param adv(rls_param p, int64_t k) { if (p.v) p.v += k; return p; }

@@ -12,12 +12,8 @@ __global__ RLS_INT_ATTR void sss_scatter_kernel(ScatterIO a)
     stage_libm_tables();
     stage_table(tab, a.spp);
     const SceneRegs sc = scene_regs(a.scene);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
+    RLS_POINT_WALK(G, a.n)
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
         const rls_sss_closure &c = a.c;
@@ -65,7 +61,7 @@ rls_status rls_sss_integrate_scatter(rls_context *ctx, int64_t n, const rls_sss_
     RLS_REQUIRE(rlsh::has3(result), "NULL output plane");
     ScatterIO io = {};
     io.c = *c; io.P = P; io.scene = *scene; io.result = result; io.depth = mean_depth;
-    io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
+    set_loop(io, n, spp_n, seed, first_index);
     return dispatch_sss_scatter(ctx, pick_group(ctx, n, io.spp), io, "rls_sss_integrate_scatter");
 }
 

@@ -22,13 +22,9 @@ __global__ RLS_INT_ATTR void skin_integrate_kernel(SkinIntIO a)
     stage_libm_tables();
     stage_table(tab, a.spp);
     const SceneRegs sc = scene_regs(a.scene);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
+    RLS_POINT_WALK(G, a.n)
     const float inv = 1.0f / (float)a.spp;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
         const rls_skin_closure &c = a.c;
@@ -124,24 +120,13 @@ __global__ RLS_INT_ATTR void ggx_shade_kernel(GgxShadeIO a)
     __shared__ SlowLds<RLS_SPEC_BLOCK> slow;
     stage_libm_tables();
     stage_table(tab, a.spp);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
+    RLS_POINT_WALK(G, a.n)
     const float inv = 1.0f / (float)a.spp;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
         const uint64_t idx = a.first + (uint64_t)ii;
-        const rls_ggx_closure &c = a.c;
-        const PIndex<int64_t> pk = pindex(c.materials, ii);      // parameters by reference (rls_material_index)
-        V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
-        float kr, kg, kb;
-        ldrgb(c.KsColor, pk, kr, kg, kb);
-        bool exiting = c.exiting ? (c.exiting[ii] != 0) : false;
-        Ggx g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp(c.ior, pk), ldp(c.specularRoughness, pk),
-                         ldp(c.anisotropic, pk));
+        RLS_GGX_LOAD(g, a.c, ii)
         VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
         OrenNayar on = oren_nayar_make(N, ldp(a.sh.diffuseRoughness, pk));
         const float ks = ldp(a.sh.Ks, pk), kd = ldp(a.sh.Kd, pk), kt = ldp(a.sh.Kt, pk);
@@ -217,13 +202,9 @@ __global__ RLS_DISNEY_LIGHT_ATTR void disney_shade_kernel(DisneyShadeIO a)
     __shared__ SlowLds<K> slow;
     stage_libm_tables();
     stage_table(tab, a.spp);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
+    RLS_POINT_WALK(G, a.n)
     const float inv = 1.0f / (float)a.spp;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
         const uint64_t idx = a.first + (uint64_t)ii;
@@ -319,10 +300,10 @@ rls_status rls_skin_integrate(rls_context *ctx, int64_t n, const rls_skin_closur
     RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
     rlsh::SkinIntIO io = {};
     if (rls_status st = copy_lights(lights, n_lights, 0, io.lights, &io.nl)) return st;
-    io.c = *c; io.P = P; io.scene = *scene; io.env[0] = env[0]; io.env[1] = env[1]; io.env[2] = env[2];
+    io.c = *c; io.P = P; io.scene = *scene; copy_env(io.env, env);
     io.sheen = out->sheen; io.specular = out->specular; io.sss = out->sss; io.out = out->out;
     io.sheenFresnel = out->sheenFresnel; io.specularFresnel = out->specularFresnel; io.sssWeight = out->sssWeight;
-    io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
+    set_loop(io, n, spp_n, seed, first_index);
     return dispatch_skin_integrate(ctx, pick_group(ctx, n, io.spp), io, "rls_skin_integrate");
 }
 
@@ -338,10 +319,10 @@ rls_status rls_ggx_shade(rls_context *ctx, int64_t n, const rls_ggx_closure *c, 
     RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
     rlsh::GgxShadeIO io = {};
     if (rls_status st = copy_lights(lights, n_lights, 0, io.lights, &io.nl)) return st;
-    io.c = *c; io.sh = *sh; io.P = P; io.env[0] = env[0]; io.env[1] = env[1]; io.env[2] = env[2]; io.traced = traced ? 1 : 0;
+    io.c = *c; io.sh = *sh; io.P = P; copy_env(io.env, env); io.traced = traced ? 1 : 0;
     io.dd = out->direct_diffuse; io.ds = out->direct_specular; io.refr = out->refraction; io.id = out->indirect_diffuse;
     io.is = out->indirect_specular; io.out = out->out;
-    io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
+    set_loop(io, n, spp_n, seed, first_index);
     return dispatch_ggx_shade(ctx, pick_group(ctx, n, io.spp), io, "rls_ggx_shade");
 }
 
@@ -357,10 +338,10 @@ rls_status rls_disney_shade(rls_context *ctx, int64_t n, const rls_disney_closur
     RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
     rlsh::DisneyShadeIO io = {};
     if (rls_status st = copy_lights(lights, n_lights, 0, io.lights, &io.nl)) return st;
-    io.c = *c; io.P = P; io.env[0] = env[0]; io.env[1] = env[1]; io.env[2] = env[2];
+    io.c = *c; io.P = P; copy_env(io.env, env);
     io.dd = out->direct_diffuse; io.ds = out->direct_specular; io.id = out->indirect_diffuse; io.is = out->indirect_specular;
     io.out = out->out;
-    io.n = n; io.spp = spp_n * spp_n; io.seed = seed; io.first = first_index;
+    set_loop(io, n, spp_n, seed, first_index);
     return dispatch_disney_shade(ctx, pick_group(ctx, n, io.spp), io, "rls_disney_shade");
 }
 

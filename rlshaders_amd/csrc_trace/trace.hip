@@ -53,12 +53,8 @@ __device__ __forceinline__ void emit_points(const EmitIO<Closure> &a)
     __shared__ SlowLds<K> slow;                                  // (not allocated where no lobe code uses it)
     stage_libm_tables();
     stage_table(tab, a.spp);
-    const int sub = threadIdx.x % G;
-    const int64_t groups_per_block = rlsh::kBlock / G;
-    const int64_t stride = (int64_t)gridDim.x * groups_per_block;
-    const int64_t rounds = (a.n + stride - 1) / stride;
-    int64_t i = (int64_t)blockIdx.x * groups_per_block + threadIdx.x / G;
-    for (int64_t it = 0; it < rounds; it++, i += stride) {
+    RLS_POINT_WALK(G, a.n)
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
         const bool live = i < a.n;
         const int64_t ii = live ? i : a.n - 1;
         Lobe lobe(a, ii);
@@ -112,13 +108,8 @@ struct GgxLobe {
     VndfView w;
     __device__ GgxLobe(const EmitIO<rls_ggx_closure> &a, int64_t ii)
     {
-        const rls_ggx_closure &c = a.c;
-        const PIndex<int64_t> pk = pindex(c.materials, ii);
-        V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
-        float kr, kg, kb;
-        ldrgb(c.KsColor, pk, kr, kg, kb);
-        bool exiting = c.exiting ? (c.exiting[ii] != 0) : false;
-        g = ggx_make(wo, N, T, exiting, kr, kg, kb, ldp(c.ior, pk), ldp(c.specularRoughness, pk), ldp(c.anisotropic, pk));
+        RLS_GGX_LOAD(loaded, a.c, ii)
+        g = loaded;
         w = vndf_view(g.view, g.fr, g.ax, g.ay);
     }
     template <int K>
@@ -660,7 +651,7 @@ rls_status emit(rls_context *ctx, int64_t n, const Closure *c, int spp_n, uint32
     io.c = *c;
     for (int k = 0; k < 3; k++) { io.dir[k] = st.dir[k]; io.w[k] = st.w[k]; }
     io.tag = st.tag; io.count = q->offsets; io.side = side;
-    io.n = n; io.spp = spp; io.seed = seed; io.first = first_index;
+    set_loop(io, n, spp_n, seed, first_index);
     rls_status s = dispatch(ctx, pick_group(ctx, n, spp), io, name);
     if (s != RLS_OK) return s;
 
@@ -761,7 +752,8 @@ rls_status rls_trace_sss_probe_emit(rls_context *ctx, int64_t n, const rls_sss_c
     RLS_REQUIRE(q->capacity >= n * spp, "queue.capacity < n * spp_n^2");
     SssEmitIO io = {};
     io.c = *c; io.P = P; io.q = *q;
-    io.n = n; io.spp = spp; io.tile_points = sss_emit_tile_points(spp); io.seed = seed; io.first = first_index;
+    set_loop(io, n, spp_n, seed, first_index);
+    io.tile_points = sss_emit_tile_points(spp);
     return dispatch_sss_probe_emit(ctx, 0, io, __func__);
 }
 
