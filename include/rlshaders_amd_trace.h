@@ -7,7 +7,8 @@
  * AI_RAY_DIFFUSE / AI_RAY_GLOSSY (src/rlDisney.cpp:240-243, 279-283).  rls_ggx_integrate / rls_ggx_integrate_refract /
  * rls_disney_integrate stand in for those rays with a uniform environment.  The calls below cut each integrator at the
  * point where the reference traces, so that a renderer can trace with its own tracer (rlSss's integrateScatter, whose
- * probe rays return hits rather than a radiance, has calls of its own: see the rlSss section below):
+ * probe rays return hits rather than a radiance, and the light loops, whose shadow rays return a visibility, have calls of
+ * their own: see the sections below):
  *
  *   1. emit:    every sample ray of the n^2-spp loop goes into a compacted, deterministic queue
  *               (direction, weight, point, sample[, kind]);
@@ -159,6 +160,82 @@ rls_status rls_trace_sss_probe_emit(rls_context *ctx, int64_t n, const rls_sss_c
 rls_status rls_trace_sss_scatter_resolve(rls_context *ctx, int64_t n, const rls_sss_closure *c, rls_cvec3 P, int spp_n,
                                          const rls_probe_queue *q, const rls_probe_hits *h, int use_cavity_fade,
                                          int literal_matrix, rls_rgb result, float *mean_depth);
+
+/* ------------------------------------------------------------------------------------------
+ * The light loops of rlGgx and rlDisney (`while (AiLightsGetSample(sg))`, src/rlGgx.cpp:285-299, src/rlDisney.cpp:695-705)
+ * cut where AiEvaluateLightSample needs the light's visibility.  rls_ggx_direct_lighting / rls_disney_direct_lighting
+ * (rlshaders_amd.h; their comment describes the estimator and the spherical lights) light the points with no occluders;
+ * here the renderer traces the shadow rays:
+ *
+ *   1. emit:    one shadow ray per term-carrying sample of the two-sample MIS estimator into a compacted queue;
+ *   2. (the renderer traces each ray from sg->P along dir up to maxdist and writes one visibility per ray and channel:
+ *      1 - sg->Lo in Arnold's terms; 1 unoccluded, 0 blocked, coloured shadows allowed);
+ *   3. resolve: visibility x weight is reduced per point and light exactly as the analytic loop reduces its terms.
+ *
+ * The samples are exactly those the analytic loops draw: light l uses the scramble streams 6 l .. 6 l + 5 of
+ * hash(seed, first_index + i), the same (0,2) table, cone sampling, BSDF samplers and tests, mis_mode per light and the math
+ * mode of the context.  With a visibility of 1 on every ray the resolves return rls_ggx_direct_lighting's and
+ * rls_disney_direct_lighting's direct_diffuse and direct_specular bit for bit.
+ *
+ * Rays.  A light-strategy sample (a direction drawn inside the light's cone) is ONE ray that carries both lobes' terms:
+ * weight_specular = f w / p of the specular lobe, weight_diffuse = f_d w_d / p of the diffuse lobe.  A BSDF-strategy
+ * sample that hits the light's cone is one ray per lobe.  A ray is queued unless every term it carries is 0; kind has one
+ * bit per lobe whose term on this ray is not 0 in every channel, and the resolves add only those terms: an absent term is
+ * never multiplied by a visibility.  (Every running sum of the analytic loop starts at +0; the +-0 terms that are dropped
+ * would not change it.)
+ *
+ * Order: point-major (CSR offsets as in rls_ray_queue); within a point the lights ascend; within a light three segments:
+ * the light-strategy samples, the BSDF diffuse-lobe samples, the BSDF specular-lobe samples; samples ascend within a
+ * segment.  The order depends on the inputs only.  No call synchronises the host.
+ * ---------------------------------------------------------------------------------------- */
+
+/* rls_shadow_queue.kind: the light's index | strategy | the terms the ray carries */
+#define RLS_SHADOW_LIGHT_MASK 0x07   /* the light's index in `lights` (0 .. RLS_MAX_LIGHTS - 1) */
+#define RLS_SHADOW_BSDF       0x08   /* set: a BSDF-strategy sample (one lobe); clear: a light-strategy sample (both) */
+#define RLS_SHADOW_SPECULAR   0x10   /* weight_specular is not 0: the resolve adds visibility x weight_specular */
+#define RLS_SHADOW_DIFFUSE    0x20   /* weight_diffuse is not 0: the resolve adds visibility x weight_diffuse */
+
+typedef struct rls_shadow_queue {
+    int64_t capacity;        /* rays every per-ray plane holds; must be >= n * n_lights * 3 * spp_n^2 */
+    int64_t *offsets;        /* [n + 1], required */
+    rls_vec3 dir;            /* required: the unit direction from sg->P towards the light */
+    float *maxdist;          /* required: the distance from sg->P along dir to the light's sphere (near intersection; to the
+                                point of closest approach where rounding lets a light sample graze past the sphere) */
+    rls_rgb weight_specular; /* required, 3 planes: the specular lobe's term (0 where the ray carries none) */
+    rls_rgb weight_diffuse;  /* required: rlDisney 3 planes; rlGgx .r only (Oren-Nayar's term is one scalar) */
+    uint8_t *kind;           /* required: RLS_SHADOW_* */
+    uint32_t *point;         /* NULL-able: the point's index in this call (0 .. n-1) */
+    uint8_t *sample;         /* NULL-able: the sample's index s in [0, spp_n^2) within its segment */
+    void *scratch;           /* device, >= rls_trace_shadow_scratch_bytes(n, n_lights, spp_n) bytes: staging of the emit */
+    size_t scratch_bytes;
+} rls_shadow_queue;
+
+/* Device scratch an emit of n points under n_lights lights at spp_n^2 samples needs. */
+rls_status rls_trace_shadow_scratch_bytes(int64_t n, int n_lights, int spp_n, size_t *bytes);
+
+/* The shadow rays of rls_ggx_direct_lighting's loop: the arguments are that call's (c, sh, P, lights; sh supplies
+ * sampleDiffuse = !AiColorIsSmall(KdColor * Kd) and the Oren-Nayar roughness). */
+rls_status rls_trace_ggx_direct_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                     rls_cvec3 P, const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                     uint64_t first_index, const rls_shadow_queue *q);
+
+/* The shadow rays of rls_disney_direct_lighting's loop. */
+rls_status rls_trace_disney_direct_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
+                                        const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                        uint64_t first_index, const rls_shadow_queue *q);
+
+/* AiEvaluateLightSample's sums with the traced visibility.  Per point, light by light, four sums (light or BSDF strategy x
+ * diffuse or specular lobe) grow in queue order by visibility[k] * weight[k] per channel, over the rays whose kind has the
+ * lobe's bit (rlGgx: weight_diffuse.r for all three channels); then s = light_sum + bsdf_sum and t = (radiance[l] * s) *
+ * (1 / spp_n^2); the first light assigns, later lights add.  rlGgx then applies diffuse *= KdColor * Kd, specular *= Ks
+ * (src/rlGgx.cpp:304-305): c (only c->materials is read) and sh as the emit took them.  lights, n_lights, spp_n: those of the
+ * emit.  visibility: 3 planes of offsets[n] values, indexed by ray. */
+rls_status rls_trace_ggx_direct_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                        const rls_sphere_light *lights, int n_lights, int spp_n, const rls_shadow_queue *q,
+                                        rls_crgb visibility, rls_rgb direct_diffuse, rls_rgb direct_specular);
+rls_status rls_trace_disney_direct_resolve(rls_context *ctx, int64_t n, const rls_sphere_light *lights, int n_lights,
+                                           int spp_n, const rls_shadow_queue *q, rls_crgb visibility,
+                                           rls_rgb direct_diffuse, rls_rgb direct_specular);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,65 @@ struct TraceResolveIO {
     int64_t n;
 };
 
+// The light loops (rls_shadow_queue).  A point has n_lights x 3 x spp slots: slot (l * 3 + segment) * spp + s is sample s of
+// light l's segment (0 the light-strategy samples, 1 the BSDF diffuse-lobe samples, 2 the BSDF specular-lobe samples), staged
+// sample-major like the other emits: slot t of point i at t * n + i.  With up to kShadowMaxSlots slots per point the rank
+// needs 13 bits: the tag is 32 bits wide, rank | kind << 16 (kind: the queue's RLS_SHADOW_* byte), or kShadowDropped.
+constexpr uint32_t kShadowDropped = 0xFFFFFFFFu;
+constexpr int kShadowSegments = 3;
+constexpr int kShadowMaxSlots = RLS_MAX_LIGHTS * kShadowSegments * kMaxSpp;      // 6144: also the slots of a compaction tile
+constexpr int kShadowPlanes = 10;            // staged floats per slot: dir[3], maxdist, weight_specular[3], weight_diffuse[3]
+__device__ __forceinline__ uint32_t shadow_tag(bool keep, int rank, int kind)
+{
+    return keep ? (uint32_t)rank | (uint32_t)kind << 16 : kShadowDropped;
+}
+
+struct NoShader {};
+template <class Closure, class Shader>
+struct ShadowEmitIO {
+    Closure c;
+    Shader sh;               // rlGgx: the node parameters the light loop reads (sampleDiffuse, Oren-Nayar's roughness)
+    rls_cvec3 P;
+    rls_sphere_light lights[RLS_MAX_LIGHTS];
+    int nl;
+    float *dir[3];
+    float *maxdist;
+    float *ws[3];
+    float *wd[3];            // rlGgx: wd[0] only
+    uint32_t *tag;
+    int64_t *count;          // = the queue's offsets
+    int64_t n;
+    int spp;
+    uint32_t seed;
+    uint64_t first;
+};
+
+struct ShadowCompactIO {
+    const float *src[kShadowPlanes];     // the staging planes, in the order of kShadowPlanes above
+    const uint32_t *tag;
+    const int64_t *offsets;
+    rls_shadow_queue q;
+    int64_t n;
+    int spp;
+    int slots;               // per point: n_lights * 3 * spp
+    int tile_points;         // min(kCompactMaxPoints, kShadowMaxSlots / slots)
+};
+
+struct ShadowResolveIO {
+    const int64_t *offsets;
+    const float *ws[3];
+    const float *wd[3];      // rlGgx: wd[0] only
+    const uint8_t *kind;
+    rls_crgb vis;
+    rls_rgb dd, ds;
+    float rad[RLS_MAX_LIGHTS][3];
+    int nl;
+    float inv;               // 1 / spp
+    rls_material_index materials;        // rlGgx: the tail diffuse *= KdColor * Kd, specular *= Ks
+    rls_ggx_shader sh;
+    int64_t n;
+};
+
 // rlSss: the probe-ray emit and the scatter resolve.  Both walk tiles of `tile_points` consecutive points: ray j = i * spp + s
 // of the dense queue is ray j - p0 * spp of the tile that starts at point p0.  The emit takes up to kSssEmitRays rays per
 // tile (several per thread), the resolve up to kBlock (one per thread: its LDS holds the terms of every hit of the tile).

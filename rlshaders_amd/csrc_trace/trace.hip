@@ -1,4 +1,5 @@
-// trace.hip -- caller-traced rlGgx, rlDisney and rlSss integrators (include/rlshaders_amd_trace.h): integrateGlossy and
+// trace.hip -- caller-traced rlGgx, rlDisney and rlSss integrators and light loops (include/rlshaders_amd_trace.h; the light
+// loops: the section "The light loops" below): integrateGlossy and
 // integrateRefract's traced branch (src/rlGgx.h:172-184, 228-244), rlDisney's integrateDiffuse / integrateGlossy
 // (src/rlDisney.cpp:240-243, 279-283) cut where the reference traces, into an emit of every sample ray and a resolve of
 // the radiance the caller traced for them; rlSss's integrateScatter (src/rlSss.h:167-280) into an emit of every probe ray
@@ -245,6 +246,300 @@ template <int G, int FAST_MATH = RLS_FAST>
 __global__ RLS_INT_ATTR void disney_specular_emit_kernel(EmitIO<rls_disney_closure> a)
 {
     emit_points<G, DisneyLobe<G, true>>(a);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The light loops: ggx_direct_loops / disney_direct_loops (rls_loops.hpp) with every term staged instead of folded.  The
+// samples, tests and packed evaluations (eval_push / *_eval_run / eval_pop through SlowLds) are theirs, line by line; where
+// they interleave the two lobes of the BSDF strategy in one pass over the samples, here each lobe is a pass of its own (the
+// queue's segments 1 and 2), so that one running count ranks a point's rays in queue order.  A change to either loop in
+// rls_loops.hpp has to be made here too (tests/test_gpu_trace_lights.py holds the two copies together bit for bit):
+//   segment 0 = the loops' first pass  (`mode != RLS_MIS_BSDF_ONLY`: cone_sample, eval_push, *_light_eval_run, eval_pop);
+//   rlGgx    segment 1 = the Oren-Nayar part of the second pass's last sweep (cosine_hemisphere, oren_nayar_pdf / _brdf),
+//            segment 2 = the rest of the second pass (ggx_vndf_push, slow_run, ggx_vndf_pop, eval_push, ggx_hit_eval_run);
+//   rlDisney segment 1 = the second pass's "diffuse lobe" half (cosine_hemisphere, disney_hit_eval_run<K, true>),
+//            segment 2 = its "specular lobe" half (disney_spec_push, slow_run, disney_spec_pop, disney_hit_eval_run<K, false>).
+
+// One point's place in the staging and its running ray count
+template <int G, class IO>
+struct ShadowStage {
+    const IO &a;
+    int64_t i;
+    bool live;
+    int sub, run;
+    // sample s of segment `seg` of light l, in every lane of the wavefront (group_rank ballots): dir and the two lobes' terms
+    // (zeros where the ray carries none); NWD: the planes of the diffuse term
+    template <int NWD>
+    __device__ __forceinline__ void put(const LightCone &cone, int l, int seg, int s, bool ok, V3 dir, const float (&ws)[3],
+                                        const float (&wd)[3])
+    {
+        const bool bs = !(ws[0] == 0.0f && ws[1] == 0.0f && ws[2] == 0.0f);
+        bool bd = !(wd[0] == 0.0f);
+        if (NWD == 3) bd = !(wd[0] == 0.0f && wd[1] == 0.0f && wd[2] == 0.0f);
+        const bool keep = ok && (bs || bd);
+        const int rank = group_rank<G>(keep, sub, run);
+        if (live && ok) {
+            const int64_t slot = staging_slot((l * kShadowSegments + seg) * a.spp + s, a.n, i);
+            const IO al = RLS_INT_ARGS(a);                       // the staging planes' pointers re-read where they are used
+            if (keep) {
+                // the near intersection of P + t dir with the light's sphere: t^2 |dir|^2 - 2 b t + c2 = 0, in the form that
+                // does not cancel; a light sample that rounding puts just outside the cone gets its closest approach
+                const float b = dot(cone.d, dir), dd = dot(dir, dir);
+                const float disc = maxf(0.0f, b * b - cone.c2 * dd);
+                al.dir[0][slot] = dir.x; al.dir[1][slot] = dir.y; al.dir[2][slot] = dir.z;
+                al.maxdist[slot] = R_DIV(cone.c2, b + R_SQRT(disc));
+#pragma unroll
+                for (int c = 0; c < 3; c++) al.ws[c][slot] = ws[c];
+#pragma unroll
+                for (int c = 0; c < NWD; c++) al.wd[c][slot] = wd[c];
+            }
+            const int kind = l | (seg ? RLS_SHADOW_BSDF : 0) | (bs ? RLS_SHADOW_SPECULAR : 0) | (bd ? RLS_SHADOW_DIFFUSE : 0);
+            al.tag[slot] = shadow_tag(keep, rank, kind);
+        }
+    }
+    // a segment the light's mis_mode skips: every slot dropped
+    __device__ __forceinline__ void skip(int l, int seg)
+    {
+        if (!live) return;
+        for (int s = sub; s < a.spp; s += G)
+            a.tag[staging_slot((l * kShadowSegments + seg) * a.spp + s, a.n, i)] = kShadowDropped;
+    }
+};
+
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_direct_emit_kernel(ShadowEmitIO<rls_ggx_closure, rls_ggx_shader> a)
+{
+    constexpr int K = RLS_SPEC_BLOCK;
+    __shared__ uint32_t tab[2][kMaxSpp];
+    __shared__ SlowLds<K> slow;
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    RLS_POINT_WALK(G, a.n)
+    const int spp = a.spp, tid = (int)threadIdx.x;
+    const float zero[3] = { 0.0f, 0.0f, 0.0f };
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
+        const bool live = i < a.n;
+        const int64_t ii = live ? i : a.n - 1;
+        RLS_GGX_LOAD(g, a.c, ii)
+        const VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
+        const OrenNayar on = oren_nayar_make(N, ldp(a.sh.diffuseRoughness, pk));
+        const float kd = ldp(a.sh.Kd, pk);
+        float dr, dg, db;
+        ldrgb(a.sh.KdColor, pk, dr, dg, db);
+        const bool sampleDiffuse = !color_is_small(dr * kd, dg * kd, db * kd);      // src/rlGgx.cpp:279-281
+        const V3 P = ld3(a.P, ii);
+        const uint64_t index = a.first + (uint64_t)ii;
+        ShadowStage<G, decltype(a)> st = { a, i, live, sub, 0 };
+        for (int l = 0; l < a.nl; l++) {
+            const LightRegs lt = light_regs(a.lights[l], P);
+            const LightCone &cone = lt.cone;
+            const int mode = lt.mode;
+            uint32_t scr[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) scr[k] = hash_u32(a.seed, index, kScrambleStream + 6 * l + k);
+
+            // segment 0: one light sample, both lobes
+            if (mode == RLS_MIS_BSDF_ONLY) st.skip(l, 0);
+            for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {
+                int qn = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const int sc = s < spp ? s : 0;
+                    const V3 L = cone_sample(cone, bits_u01(tab[0][sc] ^ scr[0]), bits_u01(tab[1][sc] ^ scr[1]));
+                    eval_push<K>(slow, k, qn, s < spp && cone.valid && dot(L, N) > 0.0f, L);
+                    slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;
+                }
+                ggx_light_eval_run<K>(slow, qn, g, on, cone.pdf, sampleDiffuse, mode);
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f }, ud[3] = { 0.0f, 0.0f, 0.0f };
+                    if (eval_pop<K>(slow, k, t)) {
+                        us[0] = t[0]; us[1] = t[1]; us[2] = t[2];
+                        if (sampleDiffuse) ud[0] = t[3];
+                    }
+                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
+                    st.template put<1>(cone, l, 0, s0 + k * G, s0 + k * G < spp, L, us, ud);
+                }
+            }
+            // segment 1: one BSDF sample of the Oren-Nayar lobe (streams +4/5), where it hits the light
+            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 1);
+            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += G) {
+                const int s = s0;
+                float ud[3] = { 0.0f, 0.0f, 0.0f };
+                V3 Ld = mk(0.0f, 0.0f, 0.0f);
+                if (s < spp && cone.valid && sampleDiffuse) {
+                    const float rx = bits_u01(tab[0][s] ^ scr[4]), ry = bits_u01(tab[1][s] ^ scr[5]);
+                    Ld = cosine_hemisphere(g.fr, rx, ry);
+                    const float pd = oren_nayar_pdf(on, Ld);
+                    if (pd > 0.0f && cone_hit(cone, Ld)) {
+                        const float fd = oren_nayar_brdf(on, wo, Ld);
+                        const float wd = mode == RLS_MIS_BSDF_ONLY ? 1.0f : power_heuristic(pd, cone.pdf);
+                        ud[0] = R_DIV(fd * wd, pd);
+                    }
+                }
+                st.template put<1>(cone, l, 1, s, s < spp, Ld, zero, ud);
+            }
+            // segment 2: one BSDF sample of the GGX lobe (streams +2/3); the few that hit the light are evaluated packed
+            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 2);
+            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
+                int qn = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const int sc = s < spp ? s : 0;
+                    ggx_vndf_push<K>(slow, k, qn, s < spp && cone.valid, w, bits_u01(tab[0][sc] ^ scr[2]),
+                                     bits_u01(tab[1][sc] ^ scr[3]));
+                }
+                slow_run<K>(slow, qn);
+                uint32_t hits = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const V3 M = ggx_vndf_pop<K>(slow, k, w, g.fr);
+                    const V3 L = reflect_direction(g.view, M);
+                    const bool hit = s < spp && cone.valid && !is_zero(L) && dot(L, N) > 0.0f && cone_hit(cone, L);
+                    hits |= (hit ? 1u : 0u) << k;
+                    slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;
+                }
+                wave_lds_fence();
+                qn = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
+                    eval_push<K>(slow, k, qn, ((hits >> k) & 1u) != 0, L);
+                }
+                ggx_hit_eval_run<K>(slow, qn, g, cone.pdf, mode);
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f };
+                    if (s < spp && cone.valid && eval_pop<K>(slow, k, t)) { us[0] = t[0]; us[1] = t[1]; us[2] = t[2]; }
+                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
+                    st.template put<1>(cone, l, 2, s, s < spp, L, us, zero);
+                }
+            }
+        }
+        if (live && sub == 0) a.count[i] = st.run;
+    }
+}
+
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_DISNEY_LIGHT_ATTR void disney_direct_emit_kernel(ShadowEmitIO<rls_disney_closure, NoShader> a)
+{
+    constexpr int K = RLS_SPEC_BLOCK;
+    __shared__ uint32_t tab[2][kMaxSpp];
+    __shared__ SlowLds<K> slow;
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    RLS_POINT_WALK(G, a.n)
+    const int spp = a.spp, tid = (int)threadIdx.x;
+    const float zero[3] = { 0.0f, 0.0f, 0.0f };
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
+        const bool live = i < a.n;
+        const int64_t ii = live ? i : a.n - 1;
+        RLS_DISNEY_LOAD(d, a.c, ii)
+        const VndfView w = vndf_view(d.view, d.fr, d.ax, d.ay);
+        const V3 N = d.fr.N, P = ld3(a.P, ii);
+        const uint64_t index = a.first + (uint64_t)ii;
+        ShadowStage<G, decltype(a)> st = { a, i, live, sub, 0 };
+        for (int l = 0; l < a.nl; l++) {
+            const LightRegs lt = light_regs(a.lights[l], P);
+            const LightCone &cone = lt.cone;
+            const int mode = lt.mode;
+            uint32_t scr[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) scr[k] = hash_u32(a.seed, index, kScrambleStream + 6 * l + k);
+
+            // segment 0: one light sample, both lobes (the specular lobe's terms come back through st[0..2]: the direction
+            // is drawn again in the second sweep)
+            if (mode == RLS_MIS_BSDF_ONLY) st.skip(l, 0);
+            for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {
+                int qn = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const int sc = s < spp ? s : 0;
+                    const V3 L = cone_sample(cone, bits_u01(tab[0][sc] ^ scr[0]), bits_u01(tab[1][sc] ^ scr[1]));
+                    eval_push<K>(slow, k, qn, s < spp && cone.valid && dot(L, N) > 0.0f, L);
+                }
+                disney_light_eval_run<K>(slow, qn, d, cone.pdf, mode);
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const int sc = s < spp ? s : 0;
+                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f }, ud[3] = { 0.0f, 0.0f, 0.0f };
+                    V3 L = mk(0.0f, 0.0f, 0.0f);
+                    if (eval_pop<K>(slow, k, t)) {
+                        ud[0] = t[0]; ud[1] = t[1]; ud[2] = t[2];
+                        us[0] = slow.st[0][k][tid]; us[1] = slow.st[1][k][tid]; us[2] = slow.st[2][k][tid];
+                        L = cone_sample(cone, bits_u01(tab[0][sc] ^ scr[0]), bits_u01(tab[1][sc] ^ scr[1]));
+                    }
+                    st.template put<3>(cone, l, 0, s, s < spp, L, us, ud);
+                }
+            }
+            // segment 1: the diffuse lobe's BSDF samples (cosine-weighted, streams +2/3) that hit the light
+            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 1);
+            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
+                int qn = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const int sc = s < spp ? s : 0;
+                    const V3 L = cosine_hemisphere(d.fr, bits_u01(tab[0][sc] ^ scr[2]), bits_u01(tab[1][sc] ^ scr[3]));
+                    eval_push<K>(slow, k, qn, s < spp && cone.valid && cone_hit(cone, L), L);
+                    slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;
+                }
+                disney_hit_eval_run<K, true>(slow, qn, d, cone.pdf, mode);
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    float t[4], ud[3] = { 0.0f, 0.0f, 0.0f };
+                    if (eval_pop<K>(slow, k, t) && t[3] != 0.0f) { ud[0] = t[0]; ud[1] = t[1]; ud[2] = t[2]; }
+                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
+                    st.template put<3>(cone, l, 1, s0 + k * G, s0 + k * G < spp, L, zero, ud);
+                }
+            }
+            // segment 2: the specular lobe's BSDF samples (streams +4/5): the sampler's rare branches packed, then the
+            // reflected directions that hit the light
+            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 2);
+            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
+                int qn = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const int sc = s < spp ? s : 0;
+                    disney_spec_push<K>(slow, k, qn, s < spp && cone.valid, d, w, bits_u01(tab[0][sc] ^ scr[4]),
+                                        bits_u01(tab[1][sc] ^ scr[5]));
+                }
+                slow_run<K>(slow, qn);
+                uint32_t hits = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const V3 L = disney_spec_pop<K>(slow, k, d, w);
+                    const bool hit = s < spp && cone.valid && cone_hit(cone, L);
+                    hits |= (hit ? 1u : 0u) << k;
+                    slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;
+                }
+                wave_lds_fence();
+                qn = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
+                    eval_push<K>(slow, k, qn, ((hits >> k) & 1u) != 0, L);
+                }
+                disney_hit_eval_run<K, false>(slow, qn, d, cone.pdf, mode);
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f };
+                    if (eval_pop<K>(slow, k, t) && t[3] != 0.0f) { us[0] = t[0]; us[1] = t[1]; us[2] = t[2]; }
+                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
+                    st.template put<3>(cone, l, 2, s0 + k * G, s0 + k * G < spp, L, us, zero);
+                }
+            }
+        }
+        if (live && sub == 0) a.count[i] = st.run;
+    }
 }
 
 // integrateScatter's probe rays (getProbeRay, src/rlSss.h:224-228) into the dense queue.  Per tile the points' profile,
@@ -534,6 +829,157 @@ __global__ __launch_bounds__(rlsh::kBlock) void trace_resolve_kernel(TraceResolv
         }
     }
 }
+
+// trace_compact_kernel for the light loops' queue: a tile of P consecutive points with a.slots slots each (P * slots <=
+// kShadowMaxSlots; one point at the limits of 8 lights x 3 segments x 256 samples).  Slot t = sp * pc + p of the tile is slot sp
+// of its point p: the staging is read in rows, the tile's rays are one contiguous range of the queue.  The positions are kept
+// in LDS (a thread has up to 24 slots), the planes go through buf one at a time.  NWD: the planes of weight_diffuse.
+// Limits of this shape: a staging row is pc points wide, so with many slots per point (tile_points = 6144 / slots: 64 at 2
+// lights x 16 samples, 1 at the maximum) the tag and plane reads are short runs n words apart rather than full cache lines, and
+// every plane's pass walks all the tile's slots (through pos), kept or not.
+template <int NWD>
+__global__ __launch_bounds__(rlsh::kBlock) void shadow_compact_kernel(ShadowCompactIO a)
+{
+    __shared__ float buf[kShadowMaxSlots];           // one plane of the tile's rays, in queue order
+    __shared__ int16_t pos[kShadowMaxSlots];         // slot -> its ray's place in the tile's range, -1: dropped
+    static_assert(kShadowMaxSlots <= 32767, "pos holds a slot's place in 16 bits");
+    static_assert(kCompactMaxPoints <= 256 && kMaxSpp <= 256, "ib packs the point's index in the tile and the sample in 8 bits each");
+    static_assert(kShadowMaxSlots <= 0x10000, "the tag's rank is 16 bits");
+    __shared__ int64_t off[kCompactMaxPoints + 1];
+    const rls_shadow_queue &q = a.q;
+    const int P = a.tile_points;
+    const int64_t tiles = (a.n + P - 1) / P;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t p0 = tile * P;
+        const int pc = a.n - p0 < P ? (int)(a.n - p0) : P;
+        const int slots = pc * a.slots;
+        __syncthreads();                                         // the previous tile is written out
+        for (int p = threadIdx.x; p <= pc; p += rlsh::kBlock) off[p] = a.offsets[p0 + p];
+        __syncthreads();
+        const int64_t base = off[0];
+        const int rays = (int)(off[pc] - base);
+        // (sp, p) of this thread's slots t = threadIdx.x, + kBlock, ...: advanced without a division per slot
+        const int sp0 = (int)threadIdx.x / pc, pp0 = (int)threadIdx.x - sp0 * pc;
+        const int dsp = rlsh::kBlock / pc, dp = rlsh::kBlock - dsp * pc;
+        uint32_t *ib = (uint32_t *)buf;
+        for (int t = threadIdx.x, sp = sp0, p = pp0; t < slots; t += rlsh::kBlock) {
+            const uint32_t tag = a.tag[staging_slot(sp, a.n, p0 + p)];
+            int at = -1;
+            if (tag != kShadowDropped) {
+                at = (int)(off[p] - base) + (int)(tag & 0xFFFFu);
+                ib[at] = (uint32_t)p | (uint32_t)(sp % a.spp) << 8 | (tag >> 16) << 16;
+            }
+            pos[t] = (int16_t)at;
+            sp += dsp; p += dp;
+            if (p >= pc) { p -= pc; sp++; }
+        }
+        __syncthreads();
+        for (int k = threadIdx.x; k < rays; k += rlsh::kBlock) {
+            const uint32_t v = ib[k];
+            q.kind[base + k] = (uint8_t)(v >> 16);
+            if (q.point) q.point[base + k] = (uint32_t)(p0 + (v & 0xFF));
+            if (q.sample) q.sample[base + k] = (uint8_t)(v >> 8);
+        }
+        for (int plane = 0; plane < 7 + NWD; plane++) {
+            const float *src = a.src[plane];
+            float *out = plane == 0 ? q.dir.x : plane == 1 ? q.dir.y : plane == 2 ? q.dir.z : plane == 3 ? q.maxdist
+                       : plane == 4 ? q.weight_specular.r : plane == 5 ? q.weight_specular.g : plane == 6 ? q.weight_specular.b
+                       : plane == 7 ? q.weight_diffuse.r : plane == 8 ? q.weight_diffuse.g : q.weight_diffuse.b;
+            __syncthreads();                                     // buf's previous contents are written out
+            for (int t = threadIdx.x, sp = sp0, p = pp0; t < slots; t += rlsh::kBlock) {
+                const int at = pos[t];
+                if (at >= 0) buf[at] = src[staging_slot(sp, a.n, p0 + p)];
+                sp += dsp; p += dp;
+                if (p >= pc) { p -= pc; sp++; }
+            }
+            __syncthreads();
+            for (int k = threadIdx.x; k < rays; k += rlsh::kBlock) out[base + k] = buf[k];
+        }
+    }
+}
+
+// The light loops' sums with the traced visibility.  Like trace_resolve_kernel a workgroup takes kBlock consecutive points, one
+// contiguous range of rays, in tiles: coalesced loads form visibility x weight of both lobes in LDS, then lane i walks its own
+// point's rays in queue order -- lights ascending -- and keeps the analytic loop's four sums per light (light or BSDF strategy x
+// lobe), closing a light with s = light_sum + bsdf_sum, t = (radiance * s) * inv, the first light assigning
+// (ggx_direct_loops / disney_direct_loops, rls_loops.hpp).  A light without rays is closed too: it adds radiance * 0 * inv.
+// NWD = 1 (rlGgx): weight_diffuse is one plane, and the tail diffuse *= KdColor * Kd, specular *= Ks follows (src/rlGgx.cpp:304-305).
+constexpr int kShadowTile = 1024;
+template <int NWD>
+__global__ __launch_bounds__(rlsh::kBlock) void shadow_resolve_kernel(ShadowResolveIO a)
+{
+    constexpr bool GGX = NWD == 1;
+    __shared__ float prod[6][kShadowTile];           // visibility x weight_specular, visibility x weight_diffuse
+    __shared__ uint8_t kinds[kShadowTile];
+    __shared__ float rad[RLS_MAX_LIGHTS][3];
+    if (threadIdx.x < RLS_MAX_LIGHTS * 3) rad[threadIdx.x / 3][threadIdx.x % 3] = a.rad[threadIdx.x / 3][threadIdx.x % 3];
+    __syncthreads();
+    for (int64_t p0 = (int64_t)blockIdx.x * rlsh::kBlock; p0 < a.n; p0 += (int64_t)gridDim.x * rlsh::kBlock) {
+        const int64_t i = p0 + threadIdx.x;
+        const bool live = i < a.n;
+        const int64_t pend = a.n - p0 < rlsh::kBlock ? a.n : p0 + rlsh::kBlock;
+        const int64_t r0 = a.offsets[p0], r1 = a.offsets[pend];
+        const int64_t lo = live ? a.offsets[i] : 0, hi = live ? a.offsets[i + 1] : 0;
+        float lS[3] = { 0.0f, 0.0f, 0.0f }, lD[3] = { 0.0f, 0.0f, 0.0f }, bS[3] = { 0.0f, 0.0f, 0.0f }, bD[3] = { 0.0f, 0.0f, 0.0f };
+        float oS[3] = { 0.0f, 0.0f, 0.0f }, oD[3] = { 0.0f, 0.0f, 0.0f };
+        int l = 0;
+        auto close_light = [&]() {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float tS = rad[l][c] * (lS[c] + bS[c]) * a.inv, tD = rad[l][c] * (lD[c] + bD[c]) * a.inv;
+                oS[c] = l == 0 ? tS : oS[c] + tS;
+                oD[c] = l == 0 ? tD : oD[c] + tD;
+                lS[c] = 0.0f; lD[c] = 0.0f; bS[c] = 0.0f; bD[c] = 0.0f;
+            }
+            l++;
+        };
+        for (int64_t t0 = r0; t0 < r1; t0 += kShadowTile) {
+            const int tn = r1 - t0 < kShadowTile ? (int)(r1 - t0) : kShadowTile;
+            __syncthreads();                                     // the previous tile's products are consumed
+            for (int k = threadIdx.x; k < tn; k += rlsh::kBlock) {
+                const int64_t r = t0 + k;
+                const float vr = a.vis.r[r], vg = a.vis.g[r], vb = a.vis.b[r];
+                prod[0][k] = vr * a.ws[0][r]; prod[1][k] = vg * a.ws[1][r]; prod[2][k] = vb * a.ws[2][r];
+                if (GGX) {
+                    const float wd = a.wd[0][r];
+                    prod[3][k] = vr * wd; prod[4][k] = vg * wd; prod[5][k] = vb * wd;
+                } else {
+                    prod[3][k] = vr * a.wd[0][r]; prod[4][k] = vg * a.wd[1][r]; prod[5][k] = vb * a.wd[2][r];
+                }
+                kinds[k] = a.kind[r];
+            }
+            __syncthreads();
+            const int64_t b = lo > t0 ? lo : t0, e = hi < t0 + tn ? hi : t0 + tn;
+            for (int64_t r = b; r < e; r++) {
+                const int k = (int)(r - t0), kind = kinds[k];
+                const int lk = (kind & RLS_SHADOW_LIGHT_MASK) < a.nl ? (kind & RLS_SHADOW_LIGHT_MASK) : a.nl - 1;
+                while (l < lk) close_light();
+                if (kind & RLS_SHADOW_BSDF) {
+                    if (kind & RLS_SHADOW_SPECULAR) { bS[0] += prod[0][k]; bS[1] += prod[1][k]; bS[2] += prod[2][k]; }
+                    if (kind & RLS_SHADOW_DIFFUSE) { bD[0] += prod[3][k]; bD[1] += prod[4][k]; bD[2] += prod[5][k]; }
+                } else {
+                    if (kind & RLS_SHADOW_SPECULAR) { lS[0] += prod[0][k]; lS[1] += prod[1][k]; lS[2] += prod[2][k]; }
+                    if (kind & RLS_SHADOW_DIFFUSE) { lD[0] += prod[3][k]; lD[1] += prod[4][k]; lD[2] += prod[5][k]; }
+                }
+            }
+        }
+        if (live) {
+            while (l < a.nl) close_light();
+            if (GGX) {
+                const PIndex<int64_t> pk = pindex(a.materials, i);
+                const float ks = ldp(a.sh.Ks, pk), kd = ldp(a.sh.Kd, pk);
+                float dr, dg, db;
+                ldrgb(a.sh.KdColor, pk, dr, dg, db);
+                dr *= kd; dg *= kd; db *= kd;                    // diffuseColor, src/rlGgx.cpp:279
+                strgb(a.ds, i, oS[0] * ks, oS[1] * ks, oS[2] * ks);
+                strgb(a.dd, i, oD[0] * dr, oD[1] * dg, oD[2] * db);
+            } else {
+                strgb(a.ds, i, oS[0], oS[1], oS[2]);
+                strgb(a.dd, i, oD[0], oD[1], oD[2]);
+            }
+        }
+    }
+}
 #endif
 
 // one launch of the rlSss emit or resolve: a workgroup per tile of io.tile_points points, grid-striding past the cap
@@ -562,6 +1008,16 @@ rls_status launch_disney_specular_emit(rls_context *ctx, int g, const EmitIO<rls
 {
     return launch_g(ctx, RLS_G_FAMILY(disney_specular_emit_kernel), g, io, name);
 }
+rls_status launch_ggx_direct_emit(rls_context *ctx, int g, const ShadowEmitIO<rls_ggx_closure, rls_ggx_shader> &io,
+                                  const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(ggx_direct_emit_kernel), g, io, name);
+}
+rls_status launch_disney_direct_emit(rls_context *ctx, int g, const ShadowEmitIO<rls_disney_closure, NoShader> &io,
+                                     const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(disney_direct_emit_kernel), g, io, name);
+}
 rls_status launch_sss_probe_emit(rls_context *ctx, int, const SssEmitIO &io, const char *name)
 {
     return launch_tiles(ctx, sss_probe_emit_kernel<>, io, name);
@@ -577,6 +1033,10 @@ RLS_FLAVOURS(ggx_glossy_emit, EmitIO<rls_ggx_closure>)
 RLS_FLAVOURS(ggx_refract_emit, EmitIO<rls_ggx_closure>)
 RLS_FLAVOURS(disney_diffuse_emit, EmitIO<rls_disney_closure>)
 RLS_FLAVOURS(disney_specular_emit, EmitIO<rls_disney_closure>)
+using GgxShadowEmitIO = ShadowEmitIO<rls_ggx_closure, rls_ggx_shader>;
+using DisneyShadowEmitIO = ShadowEmitIO<rls_disney_closure, NoShader>;
+RLS_FLAVOURS(ggx_direct_emit, GgxShadowEmitIO)
+RLS_FLAVOURS(disney_direct_emit, DisneyShadowEmitIO)
 RLS_FLAVOURS(sss_probe_emit, SssEmitIO)
 RLS_FLAVOURS(sss_scatter_resolve, SssResolveIO)
 
@@ -626,6 +1086,19 @@ rls_status empty_queue(rls_context *ctx, int64_t *offsets, const char *name)
     return rlsh::check_launch(name);
 }
 
+// offsets: the per-point counts of an emit scanned in place (exclusive), offsets[n] = the ray count
+rls_status scan_counts(rls_context *ctx, int64_t *offsets, int64_t n, int64_t *totals, int64_t tiles)
+{
+    rls_status s;
+    hipLaunchKernelGGL(trace_scan_block_kernel, dim3((unsigned)tiles), dim3(rlsh::kBlock), 0, ctx->stream, offsets, n, totals);
+    if ((s = rlsh::check_launch("trace_scan_block_kernel")) != RLS_OK) return s;
+    hipLaunchKernelGGL(trace_scan_totals_kernel, dim3(1), dim3(rlsh::kBlock), 0, ctx->stream, totals, tiles, offsets + n);
+    if ((s = rlsh::check_launch("trace_scan_totals_kernel")) != RLS_OK) return s;
+    hipLaunchKernelGGL(trace_scan_add_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, offsets, n,
+                       (const int64_t *)totals);
+    return rlsh::check_launch("trace_scan_add_kernel");
+}
+
 // Every emit: the argument checks (lobe_ok: the rlDisney lobe, checked after spp_n), the empty queue of n == 0, the staging
 // in the caller's scratch, then the closure's emit kernel (dispatch, with G for the batch) and the steps the closures share:
 // the per-point counts scanned in place into offsets, the kept records compacted into the queue (nw weight planes).  side:
@@ -655,16 +1128,7 @@ rls_status emit(rls_context *ctx, int64_t n, const Closure *c, int spp_n, uint32
     rls_status s = dispatch(ctx, pick_group(ctx, n, spp), io, name);
     if (s != RLS_OK) return s;
 
-    // offsets: the counts scanned in place
-    hipLaunchKernelGGL(trace_scan_block_kernel, dim3((unsigned)st.tiles), dim3(rlsh::kBlock), 0, ctx->stream, q->offsets, n,
-                       st.totals);
-    if ((s = rlsh::check_launch("trace_scan_block_kernel")) != RLS_OK) return s;
-    hipLaunchKernelGGL(trace_scan_totals_kernel, dim3(1), dim3(rlsh::kBlock), 0, ctx->stream, st.totals, st.tiles,
-                       q->offsets + n);
-    if ((s = rlsh::check_launch("trace_scan_totals_kernel")) != RLS_OK) return s;
-    hipLaunchKernelGGL(trace_scan_add_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, q->offsets, n,
-                       (const int64_t *)st.totals);
-    if ((s = rlsh::check_launch("trace_scan_add_kernel")) != RLS_OK) return s;
+    if ((s = scan_counts(ctx, q->offsets, n, st.totals, st.tiles)) != RLS_OK) return s;
 
     TraceCompactIO cio = {};
     for (int k = 0; k < 3; k++) { cio.sdir[k] = st.dir[k]; cio.sw[k] = st.w[k]; }
@@ -692,6 +1156,110 @@ rls_status resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, int spp_
     if (refract) hipLaunchKernelGGL(trace_resolve_kernel<1>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
     else hipLaunchKernelGGL(trace_resolve_kernel<3>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
     return rlsh::check_launch(refract ? "rls_trace_ggx_refract_resolve" : "rls_trace_ggx_glossy_resolve");
+}
+
+// the staging planes of a light-loop emit inside the caller's scratch (ShadowEmitIO), each 256-byte aligned
+struct ShadowStaging {
+    float *f[kShadowPlanes];
+    uint32_t *tag;
+    int64_t *totals;
+    int64_t tiles;
+    size_t bytes;
+};
+inline ShadowStaging shadow_staging(void *base, int64_t n, int slots_per_point)
+{
+    ShadowStaging s = {};
+    const size_t slots = (size_t)n * (size_t)slots_per_point;
+    char *p = (char *)base;
+    size_t off = 0;
+    for (int k = 0; k < kShadowPlanes; k++) { s.f[k] = (float *)(p + off); off += align256(slots * sizeof(float)); }
+    s.tag = (uint32_t *)(p + off); off += align256(slots * sizeof(uint32_t));
+    s.tiles = (n + kScanTile - 1) / kScanTile;
+    s.totals = (int64_t *)(p + off); off += align256((size_t)(s.tiles > 0 ? s.tiles : 1) * sizeof(int64_t));
+    s.bytes = off;
+    return s;
+}
+
+// the planes both light-loop verbs need of a queue; ggx: weight_diffuse is its .r plane alone
+rls_status check_shadow_queue(const char *fn, const rls_shadow_queue *q, bool ggx, int64_t n, int nl, int spp)
+{
+    RLS_REQUIRE_IN(fn, rlsh::has3(q->dir) && q->maxdist != nullptr, "queue.dir or queue.maxdist plane is NULL");
+    RLS_REQUIRE_IN(fn, rlsh::has3(q->weight_specular) && (ggx ? q->weight_diffuse.r != nullptr : rlsh::has3(q->weight_diffuse)),
+                   "queue.weight_specular or queue.weight_diffuse plane is NULL");
+    RLS_REQUIRE_IN(fn, q->kind != nullptr, "queue.kind is NULL");
+    RLS_REQUIRE_IN(fn, q->capacity >= n * nl * kShadowSegments * spp, "queue.capacity < n * n_lights * 3 * spp_n^2");
+    return RLS_OK;
+}
+
+// Both light-loop emits: the argument checks (closure: the node's checks of its closure, shader and P, which fill io), the
+// empty queue of n == 0, the staging in the caller's scratch, the closure's emit kernel (dispatch, with G for the batch), then
+// the scan of the counts and the compaction.
+template <class IO, class ClosureCheck>
+rls_status shadow_emit(rls_context *ctx, int64_t n, ClosureCheck closure, const rls_sphere_light *lights, int n_lights,
+                       int spp_n, uint32_t seed, uint64_t first_index, const rls_shadow_queue *q, bool ggx, const char *name,
+                       rls_status (*dispatch)(rls_context *, int, const IO &, const char *))
+{
+    if (rls_status s = check_batch(name, ctx, n, spp_n)) return s;
+    RLS_REQUIRE_IN(name, q != nullptr && q->offsets != nullptr, "queue or queue.offsets is NULL");
+    const int spp = spp_n * spp_n;
+    if (n == 0) return empty_queue(ctx, q->offsets, name);
+    IO io = {};
+    if (rls_status s = closure(io)) return s;
+    if (rls_status s = copy_lights(lights, n_lights, 1, io.lights, &io.nl)) return s;
+    if (rls_status s = check_shadow_queue(name, q, ggx, n, io.nl, spp)) return s;
+    const int slots = io.nl * kShadowSegments * spp;
+    const ShadowStaging st = shadow_staging(q->scratch, n, slots);
+    RLS_REQUIRE_IN(name, q->scratch != nullptr && q->scratch_bytes >= st.bytes,
+                   "queue.scratch is NULL or smaller than rls_trace_shadow_scratch_bytes");
+
+    for (int k = 0; k < 3; k++) { io.dir[k] = st.f[k]; io.ws[k] = st.f[4 + k]; io.wd[k] = st.f[7 + k]; }
+    io.maxdist = st.f[3]; io.tag = st.tag; io.count = q->offsets;
+    set_loop(io, n, spp_n, seed, first_index);
+    rls_status s = dispatch(ctx, pick_group(ctx, n, spp), io, name);
+    if (s != RLS_OK) return s;
+    if ((s = scan_counts(ctx, q->offsets, n, st.totals, st.tiles)) != RLS_OK) return s;
+
+    ShadowCompactIO cio = {};
+    for (int k = 0; k < kShadowPlanes; k++) cio.src[k] = st.f[k];
+    cio.tag = st.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp; cio.slots = slots;
+    cio.tile_points = kShadowMaxSlots / slots < kCompactMaxPoints ? kShadowMaxSlots / slots : kCompactMaxPoints;
+    const dim3 cgrid = rlsh::grid_for(ctx, n, cio.tile_points);
+    if (ggx) hipLaunchKernelGGL(shadow_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    else hipLaunchKernelGGL(shadow_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    return rlsh::check_launch("shadow_compact_kernel");
+}
+
+// Both light-loop resolves; c, sh: rlGgx's tail (NULL for rlDisney)
+rls_status shadow_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh, bool ggx,
+                          const rls_sphere_light *lights, int n_lights, int spp_n, const rls_shadow_queue *q, rls_crgb visibility,
+                          rls_rgb direct_diffuse, rls_rgb direct_specular, const char *name)
+{
+    if (rls_status s = check_batch(name, ctx, n, spp_n)) return s;
+    if (n == 0) return RLS_OK;
+    RLS_REQUIRE_IN(name, q != nullptr && q->offsets != nullptr, "queue or queue.offsets is NULL");
+    ShadowResolveIO io = {};
+    if (ggx) {
+        RLS_REQUIRE_IN(name, c != nullptr && sh != nullptr, "closure or shader is NULL");
+        RLS_REQUIRE_IN(name, rlsh::ok_rgb(sh->KdColor), "colour planes must be all set or all NULL");
+        RLS_REQUIRE_IN(name, rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+        io.materials = c->materials; io.sh = *sh;
+    }
+    rls_sphere_light lt[RLS_MAX_LIGHTS];
+    if (rls_status s = copy_lights(lights, n_lights, 1, lt, &io.nl)) return s;
+    if (rls_status s = check_shadow_queue(name, q, ggx, n, io.nl, spp_n * spp_n)) return s;
+    RLS_REQUIRE_IN(name, visibility.r && visibility.g && visibility.b, "visibility plane is NULL");
+    RLS_REQUIRE_IN(name, rlsh::has3(direct_diffuse) && rlsh::has3(direct_specular), "NULL output plane");
+    for (int l = 0; l < io.nl; l++)
+        for (int k = 0; k < 3; k++) io.rad[l][k] = lt[l].radiance[k];
+    io.offsets = q->offsets; io.kind = q->kind; io.vis = visibility; io.dd = direct_diffuse; io.ds = direct_specular;
+    io.ws[0] = q->weight_specular.r; io.ws[1] = q->weight_specular.g; io.ws[2] = q->weight_specular.b;
+    io.wd[0] = q->weight_diffuse.r; io.wd[1] = q->weight_diffuse.g; io.wd[2] = q->weight_diffuse.b;
+    io.inv = 1.0f / (float)(spp_n * spp_n);                      // as the loop kernels: 1 / spp
+    io.n = n;
+    const dim3 grid = rlsh::grid_for(ctx, n);
+    if (ggx) hipLaunchKernelGGL(shadow_resolve_kernel<1>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
+    else hipLaunchKernelGGL(shadow_resolve_kernel<3>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(name);
 }
 
 } // namespace
@@ -779,6 +1347,60 @@ rls_status rls_trace_sss_scatter_resolve(rls_context *ctx, int64_t n, const rls_
     io.n = n; io.spp = spp; io.tile_points = sss_resolve_tile_points(spp);
     io.cavity = use_cavity_fade != 0; io.literal = literal_matrix != 0;
     return dispatch_sss_scatter_resolve(ctx, 0, io, __func__);
+}
+
+rls_status rls_trace_shadow_scratch_bytes(int64_t n, int n_lights, int spp_n, size_t *bytes)
+{
+    RLS_REQUIRE(bytes != nullptr, "bytes is NULL");
+    RLS_REQUIRE(n >= 0, "n < 0");
+    RLS_REQUIRE(n_lights >= 1 && n_lights <= RLS_MAX_LIGHTS, "n_lights out of range (RLS_MAX_LIGHTS)");
+    RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
+    *bytes = shadow_staging(nullptr, n, n_lights * kShadowSegments * spp_n * spp_n).bytes;
+    return RLS_OK;
+}
+
+rls_status rls_trace_ggx_direct_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                     rls_cvec3 P, const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                     uint64_t first_index, const rls_shadow_queue *q)
+{
+    const char *fn = __func__;
+    auto closure = [&](GgxShadowEmitIO &io) -> rls_status {
+        RLS_REQUIRE_IN(fn, c != nullptr && sh != nullptr, "closure or shader is NULL");
+        if (rls_status s = rlsh::check_closure(fn, c, &P, sh)) return s;
+        io.c = *c; io.sh = *sh; io.P = P;
+        return RLS_OK;
+    };
+    return shadow_emit<GgxShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, q, true, fn,
+                                        dispatch_ggx_direct_emit);
+}
+
+rls_status rls_trace_disney_direct_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
+                                        const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                        uint64_t first_index, const rls_shadow_queue *q)
+{
+    const char *fn = __func__;
+    auto closure = [&](DisneyShadowEmitIO &io) -> rls_status {
+        if (rls_status s = rlsh::check_closure(fn, c, &P)) return s;
+        io.c = *c; io.P = P;
+        return RLS_OK;
+    };
+    return shadow_emit<DisneyShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, q, false, fn,
+                                           dispatch_disney_direct_emit);
+}
+
+rls_status rls_trace_ggx_direct_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                        const rls_sphere_light *lights, int n_lights, int spp_n, const rls_shadow_queue *q,
+                                        rls_crgb visibility, rls_rgb direct_diffuse, rls_rgb direct_specular)
+{
+    return shadow_resolve(ctx, n, c, sh, true, lights, n_lights, spp_n, q, visibility, direct_diffuse, direct_specular, __func__);
+}
+
+rls_status rls_trace_disney_direct_resolve(rls_context *ctx, int64_t n, const rls_sphere_light *lights, int n_lights,
+                                           int spp_n, const rls_shadow_queue *q, rls_crgb visibility,
+                                           rls_rgb direct_diffuse, rls_rgb direct_specular)
+{
+    return shadow_resolve(ctx, n, nullptr, nullptr, false, lights, n_lights, spp_n, q, visibility, direct_diffuse,
+                          direct_specular, __func__);
 }
 
 } // extern "C"

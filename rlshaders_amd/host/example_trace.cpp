@@ -1,10 +1,11 @@
 // example_trace.cpp -- the caller-traced rlGgx, rlDisney and rlSss integrators from C++ (rls_trace.hpp): emit
 // integrateGlossy's and integrateRefract's sample rays and those of rlDisney's two lobes, "trace" them against an analytic
-// sky on the host, resolve; emit rlSss's probe rays, walk them through each point's tangent plane on the host, resolve.
+// sky on the host, resolve; emit rlSss's probe rays, walk them through each point's tangent plane on the host, resolve;
+// emit the shadow rays of both nodes' light loops under two lights, shadow the second light with a half-space, resolve.
 //
 //   example_trace [points] [spp_n]
 // prints one JSON line: the ray counts and a checksum (FNV-1a over the bits of the resolved planes) per integrator, which
-// tests/test_gpu_trace_host_cpp.py compares with the Python path (rlshaders_amd/trace.py) on the same inputs.
+// tests/test_gpu_trace_host_cpp.py (the light loops: tests/test_gpu_trace_lights_host_cpp.py) compares with the Python path (rlshaders_amd/trace.py) on the same inputs.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -149,6 +150,53 @@ int main(int argc, char **argv)
             for (float v : dres) mdepth += v;
             std::printf(", \"sss\": {\"rays\": %lld, \"checksum\": \"%016llx\", \"mean\": %.9g, \"mean_depth\": %.9g}",
                         (long long)pq.count(), (unsigned long long)fnv(res), mean / (double)res.size(), mdepth / (double)n);
+        }
+        {
+            // The light loops of rlGgx and rlDisney on the same frame, every shading point at the origin: two spherical
+            // lights, and a wall -- the half-space x > 3 -- in front of the second one.  The renderer's shadow tracer: a ray
+            // from P = 0 along dir is blocked where it enters the half-space before maxdist.
+            rls_sphere_light lights[2] = {};
+            const float centers[2][3] = {{-4.0f, 2.0f, 3.0f}, {6.0f, 1.0f, 2.0f}};
+            const float radiances[2][3] = {{3.0f, 2.0f, 1.0f}, {1.0f, 4.0f, 2.0f}};
+            for (int l = 0; l < 2; l++) {
+                for (int k = 0; k < 3; k++) { lights[l].center[k] = centers[l][k]; lights[l].radiance[k] = radiances[l][k]; }
+                lights[l].radius = 1.0f;
+                lights[l].mis_mode = RLS_MIS_BOTH;
+            }
+            rls_ggx_shader sh = {};
+            sh.KdColor = rlsb::ParamRGB(0.7f, 0.5f, 0.2f).c();
+            sh.Kd = rls_param{nullptr, 0.8f};
+            sh.diffuseRoughness = rls_param{nullptr, 0.3f};
+            sh.Ks = rls_param{nullptr, 0.6f};
+            sh.KtColor = rlsb::ParamRGB(1.0f, 1.0f, 1.0f).c();
+            rlsb::Planes P(dev, std::vector<float>((size_t)(3 * n), 0.0f), 3);
+            const char *lnames[2] = {"ggx_lights", "disney_lights"};
+            for (int j = 0; j < 2; j++) {
+                rlsb::ShadowQueue sq(dev, n, 2, spp_n, j == 0 ? rlsb::ShadowQueue::Ggx : rlsb::ShadowQueue::Disney);
+                if (j == 0) rlsb::emitDirect(dev, c, sh, P, lights, 2, n, spp_n, kSeed, sq);
+                else rlsb::emitDirect(dev, dc, P, lights, 2, n, spp_n, kSeed, sq);
+                const int64_t count = sq.count(), scap = sq.c().capacity;
+                std::vector<float> dx((size_t)count), md((size_t)count), vis((size_t)(3 * scap), 0.0f);
+                rlsb::check(rls_copy_to_host(dev.ctx(), dx.data(), sq.c().dir.x, sizeof(float) * dx.size()));
+                rlsb::check(rls_copy_to_host(dev.ctx(), md.data(), sq.c().maxdist, sizeof(float) * md.size()));
+                int64_t blocked = 0;
+                for (int64_t k = 0; k < count; k++) {
+                    const bool hit = md[(size_t)k] * dx[(size_t)k] > 3.0f;
+                    blocked += hit ? 1 : 0;
+                    for (int ch = 0; ch < 3; ch++) vis[(size_t)(ch * scap + k)] = hit ? 0.0f : 1.0f;
+                }
+                rlsb::Planes visibility(dev, vis, 3), dd(dev, n, 3), ds(dev, n, 3);
+                if (j == 0) rlsb::resolveDirect(dev, c, sh, lights, 2, sq, visibility, dd, ds);
+                else rlsb::resolveDirect(dev, lights, 2, sq, visibility, dd, ds);
+                std::vector<float> rd = dd.download(), rs = ds.download();
+                double md_ = 0.0, ms_ = 0.0;
+                for (float v : rd) md_ += v;
+                for (float v : rs) ms_ += v;
+                std::printf(", \"%s\": {\"rays\": %lld, \"blocked\": %lld, \"direct_diffuse\": \"%016llx\", "
+                            "\"direct_specular\": \"%016llx\", \"mean_diffuse\": %.9g, \"mean_specular\": %.9g}",
+                            lnames[j], (long long)count, (long long)blocked, (unsigned long long)fnv(rd),
+                            (unsigned long long)fnv(rs), md_ / (double)rd.size(), ms_ / (double)rs.size());
+            }
         }
         std::printf(", \"points\": %lld, \"spp_n\": %d}\n", (long long)n, spp_n);
     } catch (const rlsb::Error &e) {

@@ -15,7 +15,12 @@
 //     rlsb::emitProbes(dev, sss, P, n, spp_n, seed, pq);                   // one probe ray per sample, dense
 //     ... walk every ray through the object, fill an rls_probe_hits (count, P, N, irradiance per hit slot) ...
 //     rlsb::resolveScatter(dev, sss, P, pq, hits, cavity, literal, result); // integrateScatter's result
-// Nothing here synchronises the host except RayQueue::count() (it reads offsets[n]).
+// The light loops (`while (AiLightsGetSample(sg))`, src/rlGgx.cpp:285-299, src/rlDisney.cpp:695-705):
+//     rlsb::ShadowQueue sq(dev, n, n_lights, spp_n, rlsb::ShadowQueue::Ggx);
+//     rlsb::emitDirect(dev, ggx, shader, P, lights, n_lights, n, spp_n, seed, sq);   // one shadow ray per term-carrying sample
+//     ... trace ray k from P[point[k]] along dir[k] up to maxdist[k], one visibility per ray and channel (3 planes) ...
+//     rlsb::resolveDirect(dev, ggx, shader, lights, n_lights, sq, visibility, directDiffuse, directSpecular);
+// Nothing here synchronises the host except RayQueue::count() and ShadowQueue::count() (they read offsets[n]).
 #pragma once
 
 #include <cstdint>
@@ -208,6 +213,124 @@ inline void resolveScatter(const Device &d, const rls_sss_closure &c, const Plan
     check(rls_trace_sss_scatter_resolve(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, q.sppN(),
                                         &q.c(), &hits, cavityFade ? 1 : 0, literalMatrix ? 1 : 0, result.rgb(),
                                         meanDepth));
+}
+
+// The device buffers of one light-loop emit (rls_shadow_queue): per-ray planes for n * n_lights * 3 * spp_n^2 rays, offsets
+// [n + 1] and the emit's scratch.  Ggx: weight_diffuse is its .r plane alone.
+class ShadowQueue {
+public:
+    enum Node { Ggx, Disney };
+
+    ShadowQueue(const Device &d, int64_t n, int n_lights, int spp_n, Node node)
+        : dev_(&d), n_(n), n_lights_(n_lights), spp_n_(spp_n), node_(node)
+    {
+        const int64_t cap = n * n_lights * 3 * spp_n * spp_n;
+        size_t scratch = 0;
+        check(rls_trace_shadow_scratch_bytes(n, n_lights, spp_n, &scratch));
+        try {
+            q_.capacity = cap;
+            q_.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(n + 1)));
+            q_.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
+            q_.maxdist = falloc(cap);
+            q_.weight_specular = rls_rgb{falloc(cap), falloc(cap), falloc(cap)};
+            q_.weight_diffuse.r = falloc(cap);
+            if (node == Disney) { q_.weight_diffuse.g = falloc(cap); q_.weight_diffuse.b = falloc(cap); }
+            q_.kind = static_cast<uint8_t *>(alloc((size_t)cap));
+            q_.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
+            q_.sample = static_cast<uint8_t *>(alloc((size_t)cap));
+            q_.scratch = alloc(scratch);
+            q_.scratch_bytes = scratch;
+        } catch (...) {
+            release();
+            throw;
+        }
+    }
+    ~ShadowQueue() { release(); }
+    ShadowQueue(const ShadowQueue &) = delete;
+    ShadowQueue &operator=(const ShadowQueue &) = delete;
+
+    const rls_shadow_queue &c() const { return q_; }
+    int64_t points() const { return n_; }
+    int lights() const { return n_lights_; }
+    int sppN() const { return spp_n_; }
+    Node node() const { return node_; }
+    // offsets[n]: the number of rays (synchronises)
+    int64_t count() const
+    {
+        int64_t c = 0;
+        check(rls_copy_to_host(dev_->ctx(), &c, q_.offsets + n_, sizeof(c)));
+        return c;
+    }
+
+private:
+    void release()
+    {
+        for (int k = 0; k < nbufs_; k++) rls_device_free(dev_->ctx(), bufs_[k]);
+        nbufs_ = 0;
+    }
+    void *alloc(size_t bytes)
+    {
+        void *p = nullptr;
+        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
+        bufs_[nbufs_++] = p;
+        return p;
+    }
+    float *falloc(int64_t count) { return static_cast<float *>(alloc(sizeof(float) * (size_t)count)); }
+
+    const Device *dev_;
+    int64_t n_;
+    int n_lights_, spp_n_;
+    Node node_;
+    rls_shadow_queue q_{};
+    void *bufs_[16] = {};
+    int nbufs_ = 0;
+};
+
+inline void checkShadowQueue(const ShadowQueue &q, ShadowQueue::Node node, int64_t n, int n_lights, int spp_n, const char *who)
+{
+    if (q.node() != node || q.points() != n || q.lights() != n_lights || q.sppN() != spp_n)
+        throw Error(RLS_ERR_INVALID_ARGUMENT, who);
+}
+
+// the shadow rays of rlGgx's light loop (src/rlGgx.cpp:285-299): the arguments of rls_ggx_direct_lighting; P: 3 planes of n
+// floats, sg->P
+inline void emitDirect(const Device &d, const rls_ggx_closure &c, const rls_ggx_shader &sh, const Planes &P,
+                       const rls_sphere_light *lights, int n_lights, int64_t n, int spp_n, uint32_t seed, ShadowQueue &q,
+                       uint64_t first_index = 0)
+{
+    checkShadowQueue(q, ShadowQueue::Ggx, n, n_lights, spp_n, "emitDirect: a queue of another node, size or light count");
+    check(rls_trace_ggx_direct_emit(d.ctx(), n, &c, &sh, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights,
+                                    spp_n, seed, first_index, &q.c()));
+}
+
+// the shadow rays of rlDisney's light loop (src/rlDisney.cpp:695-705): the arguments of rls_disney_direct_lighting
+inline void emitDirect(const Device &d, const rls_disney_closure &c, const Planes &P, const rls_sphere_light *lights,
+                       int n_lights, int64_t n, int spp_n, uint32_t seed, ShadowQueue &q, uint64_t first_index = 0)
+{
+    checkShadowQueue(q, ShadowQueue::Disney, n, n_lights, spp_n, "emitDirect: a queue of another node, size or light count");
+    check(rls_trace_disney_direct_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n,
+                                       seed, first_index, &q.c()));
+}
+
+// the light loop's AOVs with the traced visibility: 3 planes of >= q.count() floats, one per ray and channel; c, sh, lights:
+// those of the emit; directDiffuse, directSpecular: 3 planes of n floats each
+inline void resolveDirect(const Device &d, const rls_ggx_closure &c, const rls_ggx_shader &sh, const rls_sphere_light *lights,
+                          int n_lights, const ShadowQueue &q, const Planes &visibility, Planes &directDiffuse,
+                          Planes &directSpecular)
+{
+    checkShadowQueue(q, ShadowQueue::Ggx, q.points(), n_lights, q.sppN(), "resolveDirect: a queue of another node or light count");
+    check(rls_trace_ggx_direct_resolve(d.ctx(), q.points(), &c, &sh, lights, n_lights, q.sppN(), &q.c(),
+                                       rls_crgb{visibility.plane(0), visibility.plane(1), visibility.plane(2)},
+                                       directDiffuse.rgb(), directSpecular.rgb()));
+}
+
+inline void resolveDirect(const Device &d, const rls_sphere_light *lights, int n_lights, const ShadowQueue &q,
+                          const Planes &visibility, Planes &directDiffuse, Planes &directSpecular)
+{
+    checkShadowQueue(q, ShadowQueue::Disney, q.points(), n_lights, q.sppN(), "resolveDirect: a queue of another node or light count");
+    check(rls_trace_disney_direct_resolve(d.ctx(), q.points(), lights, n_lights, q.sppN(), &q.c(),
+                                          rls_crgb{visibility.plane(0), visibility.plane(1), visibility.plane(2)},
+                                          directDiffuse.rgb(), directSpecular.rgb()));
 }
 
 } // namespace rlsb

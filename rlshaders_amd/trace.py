@@ -14,6 +14,10 @@ or of one rlDisney lobe, trace them with your own tracer, resolve the radiance; 
     cnt, hP, hN, E = my_probe_walk(p.origin, p.dir, p.maxdist)   # hits [3, max_hits, rays], E before profile and fade
     res = p.resolve(cnt, hP, hN, E)                          # [3, n]: integrateScatter's result
 
+    s = trace.ggx_shadow_rays(sampler, shader, P, lights, 4, 7)  # ShadowQueue: s.dir, s.maxdist, s.weight_specular, s.kind, ...
+    vis = my_shadow_tracer(P[:, s.point], s.dir, s.maxdist)      # [3, count]: 1 unoccluded, 0 blocked
+    dd, ds = s.resolve(vis)                                      # [3, n] each: rls_ggx_direct_lighting's AOVs, shadowed
+
 ``count`` is read from the device once (it synchronises); everything else stays asynchronous on the context's stream, so
 ``glossy_rays(..., queue=q)`` / ``q.resolve(L, out=...)`` with preallocated tensors can be recorded by ``ctx.capture()``.
 """
@@ -28,7 +32,7 @@ import torch
 
 from . import _capi as capi
 from ._capi import RLS_RAY_DIFFUSE, RLS_RAY_GLOSSY, check
-from .closures import DisneySampler, GgxSampler, SssSampler, cvec3, plane, rgb
+from .closures import DisneySampler, GgxSampler, SssSampler, cvec3, light_array, param, param_rgb, plane, rgb
 
 TRACE_LIB_PATH = capi._PKG / "lib" / "librls_trace.so"
 
@@ -55,11 +59,26 @@ class ProbeHits_(C.Structure):
                 ("irradiance", capi.CRgb)]
 
 
+class ShadowQueue_(C.Structure):
+    """rls_shadow_queue"""
+    _fields_ = [("capacity", C.c_int64), ("offsets", C.c_void_p), ("dir", capi.Vec3), ("maxdist", C.c_void_p),
+                ("weight_specular", capi.Rgb), ("weight_diffuse", capi.Rgb), ("kind", C.c_void_p), ("point", C.c_void_p),
+                ("sample", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
 RLS_MAX_PROBE_HITS = 12
+
+# rls_shadow_queue.kind
+RLS_SHADOW_LIGHT_MASK = 0x07
+RLS_SHADOW_BSDF = 0x08
+RLS_SHADOW_SPECULAR = 0x10
+RLS_SHADOW_DIFFUSE = 0x20
 
 _ctx, _i64, _vp = C.c_void_p, C.c_int64, C.c_void_p
 _q = C.POINTER(RayQueue_)
 _pq = C.POINTER(ProbeQueue_)
+_sq = C.POINTER(ShadowQueue_)
+_lights = C.POINTER(capi.SphereLight)
 PROTOTYPES = {
     "rls_trace_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
     "rls_trace_ggx_glossy_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
@@ -72,6 +91,14 @@ PROTOTYPES = {
                                            _pq]),
     "rls_trace_sss_scatter_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.SssClosure), capi.CVec3, C.c_int, _pq,
                                                 C.POINTER(ProbeHits_), C.c_int, C.c_int, capi.Rgb, _vp]),
+    "rls_trace_shadow_scratch_bytes": (C.c_int, [_i64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "rls_trace_ggx_direct_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.POINTER(capi.GgxShader), capi.CVec3,
+                                            _lights, C.c_int, C.c_int, C.c_uint32, C.c_uint64, _sq]),
+    "rls_trace_disney_direct_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.DisneyClosure), capi.CVec3, _lights, C.c_int,
+                                               C.c_int, C.c_uint32, C.c_uint64, _sq]),
+    "rls_trace_ggx_direct_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.POINTER(capi.GgxShader), _lights,
+                                               C.c_int, C.c_int, _sq, capi.CRgb, capi.Rgb, capi.Rgb]),
+    "rls_trace_disney_direct_resolve": (C.c_int, [_ctx, _i64, _lights, C.c_int, C.c_int, _sq, capi.CRgb, capi.Rgb, capi.Rgb]),
 }
 
 _lib = None
@@ -325,4 +352,152 @@ def sss_probe_rays(sampler: SssSampler, P: torch.Tensor, spp_n: int, seed: int, 
     check(load().rls_trace_sss_probe_emit(ctx.handle, n, C.byref(sampler.c), Pv, int(spp_n), int(seed) & 0xFFFFFFFF,
                                           int(first_index), C.byref(q.q)))
     q.sampler, q.P = sampler, P
+    return q
+
+
+def shadow_scratch_bytes(n: int, n_lights: int, spp_n: int) -> int:
+    b = C.c_size_t()
+    check(load().rls_trace_shadow_scratch_bytes(int(n), int(n_lights), int(spp_n), C.byref(b)))
+    return int(b.value)
+
+
+def ggx_shader(sampler: GgxSampler, KdColor=(1.0, 1.0, 1.0), Kd=0.5, diffuseRoughness=0.0, Ks=0.5) -> "capi.GgxShader":
+    """The node parameters rlGgx's light loop reads (rls_ggx_shader), as ``GgxSampler.directLighting`` takes them."""
+    pn = sampler.pn
+    sh = capi.GgxShader(param_rgb(KdColor, pn, "KdColor"), param(Kd, pn, "Kd"),
+                        param(diffuseRoughness, pn, "diffuseRoughness"), param(Ks, pn, "Ks"),
+                        param_rgb((1.0, 1.0, 1.0), pn, "KtColor"), param(0.0, pn, "Kt"))
+    sh._keep = (KdColor, Kd, diffuseRoughness, Ks)           # tensor parameters stay alive with the struct
+    return sh
+
+
+class ShadowQueue:
+    """The shadow rays of one light-loop emit over n points under n_lights lights at spp_n^2 samples (rls_shadow_queue):
+    point-major CSR; within a point lights ascending, within a light the light-strategy samples, then the BSDF diffuse-lobe
+    samples, then the BSDF specular-lobe samples.  Planes are allocated for the full capacity n * n_lights * 3 * spp_n^2; the
+    properties view the first ``count`` rays.  ``disney``: an rlDisney queue (three planes of weight_diffuse; rlGgx has one)."""
+
+    def __init__(self, ctx, n: int, n_lights: int, spp_n: int, disney: bool = False):
+        self.ctx, self.n, self.n_lights, self.spp_n, self.disney = ctx, int(n), int(n_lights), int(spp_n), bool(disney)
+        dev = ctx.torch_device
+        cap = self.n * self.n_lights * 3 * self.spp_n * self.spp_n
+        self.capacity = cap
+        self.offsets = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
+        self._dir = torch.empty(3, cap, dtype=torch.float32, device=dev)
+        self._maxdist = torch.empty(cap, dtype=torch.float32, device=dev)
+        self._ws = torch.empty(3, cap, dtype=torch.float32, device=dev)
+        self._wd = torch.empty(3 if disney else 1, cap, dtype=torch.float32, device=dev)
+        self._kind = torch.empty(cap, dtype=torch.uint8, device=dev)
+        self._point = torch.empty(cap, dtype=torch.int32, device=dev)          # uint32 on the device; n < 2^31 here
+        self._sample = torch.empty(cap, dtype=torch.uint8, device=dev)
+        self._scratch = torch.empty(max(shadow_scratch_bytes(self.n, self.n_lights, self.spp_n), 1), dtype=torch.uint8,
+                                    device=dev)
+        q = ShadowQueue_()
+        q.capacity = cap
+        q.offsets = self.offsets.data_ptr()
+        q.dir = capi.Vec3(*[self._dir[k].data_ptr() for k in range(3)])
+        q.maxdist = self._maxdist.data_ptr()
+        q.weight_specular = capi.Rgb(*[self._ws[k].data_ptr() for k in range(3)])
+        wd = self._wd
+        q.weight_diffuse = capi.Rgb(wd[0].data_ptr(), wd[1].data_ptr() if disney else None, wd[2].data_ptr() if disney else None)
+        q.kind, q.point, q.sample = self._kind.data_ptr(), self._point.data_ptr(), self._sample.data_ptr()
+        q.scratch, q.scratch_bytes = self._scratch.data_ptr(), self._scratch.numel()
+        self.q = q
+        # what the last emit took and the resolve takes again: the lights; rlGgx: the sampler and its shader
+        self.lights = None
+        self.sampler = None
+        self.shader = None
+
+    @property
+    def count(self) -> int:
+        """offsets[n]: the number of rays (reads the device: synchronises)"""
+        return int(self.offsets[self.n].item())
+
+    @property
+    def dir(self) -> torch.Tensor:
+        return self._dir[:, :self.count]
+
+    @property
+    def maxdist(self) -> torch.Tensor:
+        return self._maxdist[:self.count]
+
+    @property
+    def weight_specular(self) -> torch.Tensor:
+        return self._ws[:, :self.count]
+
+    @property
+    def weight_diffuse(self) -> torch.Tensor:
+        """[3, count] (rlDisney) or [1, count] (rlGgx: Oren-Nayar's scalar term)"""
+        return self._wd[:, :self.count]
+
+    @property
+    def kind(self) -> torch.Tensor:
+        """uint8 [count]: light index | RLS_SHADOW_BSDF | RLS_SHADOW_SPECULAR | RLS_SHADOW_DIFFUSE"""
+        return self._kind[:self.count]
+
+    @property
+    def point(self) -> torch.Tensor:
+        return self._point[:self.count]
+
+    @property
+    def sample(self) -> torch.Tensor:
+        return self._sample[:self.count]
+
+    def resolve(self, visibility: torch.Tensor, out=None, count: Optional[int] = None):
+        """visibility [3, >= count] float32, one per ray and channel (1 unoccluded, 0 blocked) ->
+        (direct_diffuse [3, n], direct_specular [3, n]): with visibility 1 the AOVs of rls_ggx_direct_lighting /
+        rls_disney_direct_lighting.  ``count``: the ray count when the caller knows it (skips the read of offsets[n])."""
+        if self.lights is None:
+            raise RuntimeError("resolve: no emit has filled this queue (trace.ggx_shadow_rays / disney_shadow_rays)")
+        ctx, n = self.ctx, self.n
+        count = self.count if count is None else int(count)
+        v = visibility
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or not v.is_cuda or v.dim() != 2 or v.shape[0] != 3 or \
+                v.shape[1] < count or v.stride(1) != 1:
+            raise ValueError(f"visibility: expected a float32 CUDA tensor [3, >= {count}] with unit inner stride")
+        dd, ds = out if out is not None else (ctx.empty(3, n), ctx.empty(3, n))
+        vis = capi.CRgb(v[0].data_ptr(), v[1].data_ptr(), v[2].data_ptr())
+        lights, nl = self.lights
+        lib = load()
+        if self.disney:
+            check(lib.rls_trace_disney_direct_resolve(ctx.handle, n, lights, nl, self.spp_n, C.byref(self.q), vis,
+                                                      rgb(dd, n, "direct_diffuse"), rgb(ds, n, "direct_specular")))
+        else:
+            check(lib.rls_trace_ggx_direct_resolve(ctx.handle, n, C.byref(self.sampler.c), C.byref(self.shader), lights, nl,
+                                                   self.spp_n, C.byref(self.q), vis, rgb(dd, n, "direct_diffuse"),
+                                                   rgb(ds, n, "direct_specular")))
+        return dd, ds
+
+
+def _shadow_queue(sampler, lights, spp_n: int, queue: Optional[ShadowQueue], disney: bool):
+    la, nl = light_array(lights)
+    q = ShadowQueue(sampler.ctx, sampler.n, nl, spp_n, disney) if queue is None else queue
+    if q.n != sampler.n or q.spp_n != int(spp_n) or q.n_lights != nl or q.disney != disney:
+        raise ValueError("queue: allocated for another batch size, light count, spp_n or node")
+    return q, la, nl
+
+
+def ggx_shadow_rays(sampler: GgxSampler, shader: "capi.GgxShader", P: torch.Tensor, lights, spp_n: int, seed: int,
+                    first_index: int = 0, queue: Optional[ShadowQueue] = None) -> ShadowQueue:
+    """The shadow rays of rlGgx's light loop (src/rlGgx.cpp:285-299): the samples rls_ggx_direct_lighting draws, one ray per
+    term-carrying sample with direction, distance to the light and both lobes' weights.  ``shader``: ``trace.ggx_shader``;
+    ``lights``: one ``make_light`` or a sequence; P: [3, n] float32, sg->P per point."""
+    ctx, n = sampler.ctx, sampler.n
+    q, la, nl = _shadow_queue(sampler, lights, spp_n, queue, False)
+    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
+    check(load().rls_trace_ggx_direct_emit(ctx.handle, n, C.byref(sampler.c), C.byref(shader), Pv, la, nl, int(spp_n),
+                                           int(seed) & 0xFFFFFFFF, int(first_index), C.byref(q.q)))
+    q.lights, q.sampler, q.shader, q.P = (la, nl), sampler, shader, P
+    return q
+
+
+def disney_shadow_rays(sampler: DisneySampler, P: torch.Tensor, lights, spp_n: int, seed: int, first_index: int = 0,
+                       queue: Optional[ShadowQueue] = None) -> ShadowQueue:
+    """The shadow rays of rlDisney's light loop (src/rlDisney.cpp:695-705): the samples rls_disney_direct_lighting draws."""
+    ctx, n = sampler.ctx, sampler.n
+    q, la, nl = _shadow_queue(sampler, lights, spp_n, queue, True)
+    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
+    check(load().rls_trace_disney_direct_emit(ctx.handle, n, C.byref(sampler.c), Pv, la, nl, int(spp_n),
+                                              int(seed) & 0xFFFFFFFF, int(first_index), C.byref(q.q)))
+    q.lights, q.sampler, q.P = (la, nl), sampler, P
     return q

@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
+    python tools/trace_bench.py [--closure ggx|disney|sss|ggx-lights|disney-lights] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -16,6 +16,12 @@ rlSss: the emit writes 12 (origin) + 12 (dir) + 4 (maxdist) + 4 (point) + 1 (sam
 dense); the resolve reads 1 B of count per ray plus 12 (P) + 12 (N) + 12 (irradiance) = 36 B per reported hit slot.  Its
 hits come from a plane intersected with torch on the device (the shading points lie on the plane z = 0, lit from +z):
 timing needs plausible hits, not the oracle's.
+--closure ggx-lights / disney-lights: the shadow-ray emit and the visibility resolve of the node's light loop
+(trace.ggx_shadow_rays / disney_shadow_rays, ShadowQueue.resolve) next to rls_ggx_direct_lighting / rls_disney_direct_lighting on
+the same batch: --lights spherical lights (default 2, MIS on) over shading points in the slab [0,4) x [0,4) x [0,1), a uniform
+random coloured visibility.  A kept ray is 12 (dir) + 4 (maxdist) + 12 (weight_specular) + 4 or 12 (weight_diffuse: rlGgx
+one plane, rlDisney three) + 1 (kind) + 4 (point) + 1 (sample) = 38 / 46 B; the staging holds a 4 B tag for every one of the
+lights x 3 x spp slots of a point and 32 / 40 B per kept ray, read back by the compaction.  `kept` is rays / slots.
 """
 from __future__ import annotations
 
@@ -141,6 +147,66 @@ def bench_sss(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
     }
 
 
+LIGHT_SPECS = (((2.0, 2.0, 3.0), 1.25, (3.0, 2.0, 1.0)), ((1.0, 5.0, 4.0), 1.0, (5.0, 1.0, 1.0)), ((-3.0, 1.0, 2.5), 0.5, (0.5, 4.0, 2.0)),
+               ((0.5, -2.5, 6.0), 2.0, (1.0, 1.0, 6.0)), ((6.0, -1.0, 1.5), 0.8, (0.3, 0.6, 0.9)), ((-1.0, -1.0, 8.0), 3.0, (0.7, 0.7, 0.2)),
+               ((5.0, 5.0, 5.0), 1.5, (1.0, 2.0, 3.0)), ((-2.0, 6.0, 3.0), 1.0, (2.0, 1.0, 0.5)))
+
+
+def bench_lights(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """the light loop of rlGgx or rlDisney (per-point parameters U[0,1) like the other closures' batches): emit and resolve
+    against the analytic direct-lighting call"""
+    import torch
+    import rlshaders_amd as R
+    from rlshaders_amd import trace as T
+    from rlshaders_amd.closures import make_light
+    disney = args.closure == "disney-lights"
+    nl = args.lights
+    lights = [make_light(center=c, radius=r, radiance=e) for c, r, e in LIGHT_SPECS[:nl]]
+    wo, N, T_ = R.gen_frame(ctx, seed, 0, n)
+    u = lambda stream, lo=0.0, hi=1.0: R.gen_uniform(ctx, seed, 0, n, stream, lo, hi)
+    P = torch.stack([u(60, 0.0, 4.0), u(61, 0.0, 4.0), u(62)]).contiguous()
+    out = (ctx.empty(3, n), ctx.empty(3, n))
+    if disney:
+        base = torch.stack([u(8 + j) for j in range(3)])
+        s = R.DisneySampler(ctx, wo, N, T_, base_color=base, **{k: u(32 + j) for j, k in enumerate(R._capi.DISNEY_SCALARS)})
+        analytic = lambda: s.directLighting(P, lights, spp_n, seed, out=out)
+        q = T.ShadowQueue(ctx, n, nl, spp_n, disney=True)
+        emit = lambda: T.disney_shadow_rays(s, P, lights, spp_n, seed, queue=q)
+    else:
+        ks = torch.stack([u(10 + k) for k in range(3)])
+        s = R.GgxSampler(ctx, wo, N, T_, specColor=ks, ior=u(13, 1.05, 2.55), roughness=u(14, 0.05, 1.0),
+                         anisotropic=R.gen_aniso(ctx, seed, 0, n))
+        shp = dict(KdColor=torch.stack([u(20 + k) for k in range(3)]), Kd=u(23), diffuseRoughness=u(24), Ks=u(25))
+        sh = T.ggx_shader(s, **shp)
+        analytic = lambda: s.directLighting(P, lights, spp_n, seed, out=out, **shp)
+        q = T.ShadowQueue(ctx, n, nl, spp_n)
+        emit = lambda: T.ggx_shadow_rays(s, sh, P, lights, spp_n, seed, queue=q)
+    ms_int = timed(analytic, args.repeats, args.warmup)
+    ms_emit = timed(emit, args.repeats, args.warmup)
+    rays = q.count
+    vis = torch.rand(3, max(rays, 1), device=ctx.torch_device)
+    res = (ctx.empty(3, n), ctx.empty(3, n))
+    ms_res = timed(lambda: q.resolve(vis, out=res, count=rays), args.repeats, args.warmup)
+    slots = n * nl * 3 * spp_n * spp_n
+    wd = 12 if disney else 4
+    per_ray = 12 + 4 + 12 + wd + 1 + 4 + 1
+    staged = 12 + 4 + 12 + wd
+    emit_bytes = rays * per_ray
+    staging = slots * 4 * 2 + rays * staged * 2 + n * 8 * 4          # tags written and read, kept records likewise, the scan
+    res_bytes = rays * (12 + 12 + wd + 1) + n * 8 + n * 24
+    rec["lights"] = nl
+    rec[args.closure] = {
+        "rays": rays, "rays_per_point": round(rays / n, 4), "kept": round(rays / slots, 4), "bytes_per_ray": per_ray,
+        "analytic_ms": round(ms_int, 4), "emit_ms": round(ms_emit, 4), "resolve_ms": round(ms_res, 4),
+        "emit_rays_per_s": round(rays / (ms_emit * 1e-3), 1), "resolve_rays_per_s": round(rays / (ms_res * 1e-3), 1),
+        "emit_tb_per_s": rate(emit_bytes, ms_emit), "emit_tb_per_s_with_staging": rate(emit_bytes + staging, ms_emit),
+        "emit_bytes_with_staging": emit_bytes + staging,
+        "resolve_tb_per_s": rate(res_bytes, ms_res), "resolve_frac_of_8tbps": round(rate(res_bytes, ms_res) / HBM_TBPS, 4),
+        "emit_over_analytic": round(ms_emit / ms_int, 4),
+        "emit_plus_resolve_over_analytic": round((ms_emit + ms_res) / ms_int, 4),
+    }
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=24)
@@ -148,10 +214,13 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
-    ap.add_argument("--closure", choices=("ggx", "disney", "sss"), default="ggx")
+    ap.add_argument("--closure", choices=("ggx", "disney", "sss", "ggx-lights", "disney-lights"), default="ggx")
+    ap.add_argument("--lights", type=int, default=2, help="the light loops: spherical lights, 1..8")
     args = ap.parse_args()
     if args.repeats < 3:
         ap.error("--repeats must be at least 3")
+    if not 1 <= args.lights <= 8:
+        ap.error("--lights must be in 1..8")
 
     import torch
     import rlshaders_amd as R
@@ -164,9 +233,9 @@ def main() -> None:
     spp = spp_n * spp_n
     rec = {"tool": "trace_bench", "n": n, "spp_n": spp_n, "math": "fast" if args.fast else "exact", "repeats": args.repeats,
            "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
-    if args.closure in ("disney", "sss"):
+    if args.closure != "ggx":
         rec["closure"] = args.closure
-        (bench_disney if args.closure == "disney" else bench_sss)(args, ctx, n, spp_n, seed, rec)
+        {"disney": bench_disney, "sss": bench_sss}.get(args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
         print(json.dumps(rec), flush=True)
         return
