@@ -676,6 +676,61 @@ __device__ __forceinline__ void ggx_refract_untraced(const Ggx &g, float &acc, f
 
 
 // ---------------------------------------------------------------------------------------------
+// The two steps the light loops below share with each other and with the caller-traced emitters (csrc_trace/trace.hip,
+// shadow_emit_points), for the K samples s0, s0 + G, ... of one light; G and K are the enclosing template's.  (Macros, as
+// RLS_POINT_WALK and for its reason: as __forceinline__ function templates, taking values or references, with or without
+// the KEEP hook, the same lines move every ggx_direct, disney_direct, ggx_shade and disney_shade kernel.)
+// The light-sampling strategy's first sweep: one direction L towards the light per sample (scrambles sx, sy), queued for
+// evaluation where it is above the horizon; declares qn, the queue's count.  KEEP: a statement for what else the caller
+// wants of (k, L), or nothing.
+#define RLS_LIGHT_SAMPLE_PUSH(slow, qn, tab, spp, s0, cone, N, sx, sy, KEEP)                               \
+    int qn = 0;                                                                                            \
+    _Pragma("unroll 1")                                                                                    \
+    for (int k = 0; k < K; k++) {                                                                          \
+        const int s = (s0) + k * G;                                                                        \
+        const int sc = s < (spp) ? s : 0;                                                                  \
+        V3 L = cone_sample(cone, bits_u01((tab)[0][sc] ^ (sx)), bits_u01((tab)[1][sc] ^ (sy)));            \
+        eval_push<K>(slow, k, qn, s < (spp) && (cone).valid && dot(L, N) > 0.0f, L);                       \
+        KEEP                                                                                               \
+    }
+
+// The BSDF-sampling strategy of a lobe with a packed sampler, up to the evaluation: the sampler's rare branches packed
+// (lobe.push, slow_run, lobe.pop: the direction L, left in st[0..2][k]; the queue is free again once every sample's slopes
+// are picked up), then the few directions that hit the light queued and evaluated (lobe.hit: whether L can carry light at
+// all; cone_hit; lobe.run); eval_pop picks the terms up.  disney_direct_loops and both emitters use it.  In ggx_direct_loops
+// the same lines stay written out: with its lobe (GgxHitLobe, csrc_trace/trace.hip; N by value or by reference, the hit test a member or an argument of the
+// macro) they move ggx_direct_kernel and ggx_shade_kernel; disney_direct_kernel and disney_shade_kernel hold.
+#define RLS_HIT_SAMPLE_EVAL(slow, lobe, tab, spp, s0, cone, sx, sy, mode)                                  \
+    {                                                                                                      \
+        int qn_ = 0;                                                                                       \
+        _Pragma("unroll 1")                                                                                \
+        for (int k = 0; k < K; k++) {                                                                      \
+            const int s = (s0) + k * G;                                                                    \
+            const int sc = s < (spp) ? s : 0;                                                              \
+            (lobe).push(slow, k, qn_, s < (spp) && (cone).valid, bits_u01((tab)[0][sc] ^ (sx)),            \
+                        bits_u01((tab)[1][sc] ^ (sy)));                                                    \
+        }                                                                                                  \
+        slow_run<K>(slow, qn_);                                                                            \
+        uint32_t hits = 0;                                                                                 \
+        _Pragma("unroll 1")                                                                                \
+        for (int k = 0; k < K; k++) {                                                                      \
+            const int s = (s0) + k * G;                                                                    \
+            const V3 L = (lobe).pop(slow, k);                                                              \
+            const bool hit = s < (spp) && (cone).valid && (lobe).hit(L) && cone_hit(cone, L);              \
+            hits |= (hit ? 1u : 0u) << k;                                                                  \
+            (slow).st[0][k][threadIdx.x] = L.x; (slow).st[1][k][threadIdx.x] = L.y; (slow).st[2][k][threadIdx.x] = L.z; \
+        }                                                                                                  \
+        wave_lds_fence();                                                                                  \
+        qn_ = 0;                                                                                           \
+        _Pragma("unroll 1")                                                                                \
+        for (int k = 0; k < K; k++) {                                                                      \
+            const V3 L = mk((slow).st[0][k][threadIdx.x], (slow).st[1][k][threadIdx.x], (slow).st[2][k][threadIdx.x]); \
+            eval_push<K>(slow, k, qn_, ((hits >> k) & 1u) != 0, L);                                        \
+        }                                                                                                  \
+        (lobe).run(slow, qn_, (cone).pdf, mode);                                                           \
+    }
+
+// ---------------------------------------------------------------------------------------------
 // Direct lighting of the rlGgx node (src/rlGgx.cpp:274-299); include/rlshaders_amd.h,
 // rls_ggx_direct_lighting, says what stands in for the closed light loop.
 using rlsh::LightIO;
@@ -703,14 +758,7 @@ __device__ __forceinline__ void ggx_direct_loops(SlowLds<K> &slow, const Ggx &g,
         float lR = 0.0f, lG = 0.0f, lB = 0.0f, lA = 0.0f, bR = 0.0f, bG = 0.0f, bB = 0.0f, bA = 0.0f;
         for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {   // one light sample, both lobes
             // the samples above the horizon are queued and evaluated packed (eval_push / ggx_light_eval_run / eval_pop)
-            int qn = 0;
-#pragma unroll 1
-            for (int k = 0; k < K; k++) {
-                const int s = s0 + k * G;
-                const int sc = s < spp ? s : 0;
-                V3 L = cone_sample(cone, bits_u01(tab[0][sc] ^ scr[0]), bits_u01(tab[1][sc] ^ scr[1]));
-                eval_push<K>(slow, k, qn, s < spp && cone.valid && dot(L, N) > 0.0f, L);
-            }
+            RLS_LIGHT_SAMPLE_PUSH(slow, qn, tab, spp, s0, cone, N, scr[0], scr[1], )
             ggx_light_eval_run<K>(slow, qn, g, on, cone.pdf, sampleDiffuse, mode);
 #pragma unroll 1
             for (int k = 0; k < K; k++) {
@@ -723,6 +771,7 @@ __device__ __forceinline__ void ggx_direct_loops(SlowLds<K> &slow, const Ggx &g,
             }
         }
         for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {   // one BSDF sample per lobe; K per pass (SlowLds)
+            // (RLS_HIT_SAMPLE_EVAL with GgxHitLobe, written out: see there)
             int qn = 0;
 #pragma unroll 1
             for (int k = 0; k < K; k++) {
@@ -890,6 +939,19 @@ __device__ __forceinline__ void disney_hit_eval_run(SlowLds<K> &Q, int cnt, cons
     wave_lds_fence();
 }
 
+// rlDisney's specular lobe for RLS_HIT_SAMPLE_EVAL: every sampled direction may carry light (streams +4/5)
+struct DisneySpecHitLobe {
+    const Disney &d;
+    const VndfView &w;
+    template <int K>
+    RLS_DEV void push(SlowLds<K> &slow, int k, int &qn, bool ok, float rx, float ry) const { disney_spec_push<K>(slow, k, qn, ok, d, w, rx, ry); }
+    template <int K>
+    RLS_DEV V3 pop(const SlowLds<K> &slow, int k) const { return disney_spec_pop<K>(slow, k, d, w); }
+    RLS_DEV bool hit(V3) const { return true; }
+    template <int K>
+    RLS_DEV void run(SlowLds<K> &slow, int qn, float conePdf, int mode) const { disney_hit_eval_run<K, false>(slow, qn, d, conePdf, mode); }
+};
+
 // The light loop of rlDisney (src/rlDisney.cpp:695-705) for one shading point: oD / oS = the sums over the lights of
 // evalDiffuseLightSample / evalSpecularLightSample, group-reduced.  Light l: sample streams 3 l .. 3 l + 2.
 template <int G, int K, class IO>
@@ -912,14 +974,7 @@ __device__ __forceinline__ void disney_direct_loops(SlowLds<K> &slow, const Disn
         float lD[3] = { 0.0f, 0.0f, 0.0f }, lS[3] = { 0.0f, 0.0f, 0.0f }, bD[3] = { 0.0f, 0.0f, 0.0f }, bS[3] = { 0.0f, 0.0f, 0.0f };
         const int tid = (int)threadIdx.x;
         for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {     // one light sample, both lobes
-            int qn = 0;
-#pragma unroll 1
-            for (int k = 0; k < K; k++) {
-                const int s = s0 + k * G;
-                const int sc = s < spp ? s : 0;
-                V3 L = cone_sample(cone, bits_u01(tab[0][sc] ^ scr[0]), bits_u01(tab[1][sc] ^ scr[1]));
-                eval_push<K>(slow, k, qn, s < spp && cone.valid && dot(L, N) > 0.0f, L);
-            }
+            RLS_LIGHT_SAMPLE_PUSH(slow, qn, tab, spp, s0, cone, N, scr[0], scr[1], )
             disney_light_eval_run<K>(slow, qn, d, cone.pdf, mode);
 #pragma unroll 1
             for (int k = 0; k < K; k++) {
@@ -952,32 +1007,7 @@ __device__ __forceinline__ void disney_direct_loops(SlowLds<K> &slow, const Disn
                 fold<G>(bD[0], u[0]); fold<G>(bD[1], u[1]); fold<G>(bD[2], u[2]);
             }
             // specular lobe: the sampler's rare branches packed, then the reflected directions that hit the light
-            qn = 0;
-#pragma unroll 1
-            for (int k = 0; k < K; k++) {
-                const int s = s0 + k * G;
-                const int sc = s < spp ? s : 0;
-                disney_spec_push<K>(slow, k, qn, s < spp && cone.valid, d, w, bits_u01(tab[0][sc] ^ scr[4]),
-                                    bits_u01(tab[1][sc] ^ scr[5]));
-            }
-            slow_run<K>(slow, qn);
-            uint32_t hits = 0;
-#pragma unroll 1
-            for (int k = 0; k < K; k++) {
-                const int s = s0 + k * G;
-                const V3 L = disney_spec_pop<K>(slow, k, d, w);
-                const bool hit = s < spp && cone.valid && cone_hit(cone, L);
-                hits |= (hit ? 1u : 0u) << k;
-                slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;
-            }
-            wave_lds_fence();
-            qn = 0;
-#pragma unroll 1
-            for (int k = 0; k < K; k++) {
-                const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
-                eval_push<K>(slow, k, qn, ((hits >> k) & 1u) != 0, L);
-            }
-            disney_hit_eval_run<K, false>(slow, qn, d, cone.pdf, mode);
+            RLS_HIT_SAMPLE_EVAL(slow, (DisneySpecHitLobe{ d, w }), tab, spp, s0, cone, scr[4], scr[5], mode)
 #pragma unroll 1
             for (int k = 0; k < K; k++) {
                 float t[4];

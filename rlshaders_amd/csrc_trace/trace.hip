@@ -18,6 +18,9 @@
 //      transposed through LDS (staging rows in, the tile's contiguous queue range out).
 // Steps 2 and 3 are the same for every closure (emit() below).  Every position is a function of the inputs: no atomics
 // anywhere.
+// The light loops' emit has the same three steps with a queue of its own (rls_shadow_queue): ggx_direct_emit_kernel /
+// disney_direct_emit_kernel, the scan, shadow_compact_kernel; the host side shares the staging's carve (staging) and the
+// launch of steps 1 and 2 (emit_and_scan) with the sample-ray emits.
 //
 // Resolve (trace_resolve_kernel): per point the sequential sum over its rays in queue order; the products
 // radiance x weight of a tile of rays are formed with coalesced loads into LDS, then each lane adds its point's ones.  The
@@ -249,16 +252,33 @@ __global__ RLS_INT_ATTR void disney_specular_emit_kernel(EmitIO<rls_disney_closu
 }
 
 // ---------------------------------------------------------------------------------------------
-// The light loops: ggx_direct_loops / disney_direct_loops (rls_loops.hpp) with every term staged instead of folded.  The
-// samples, tests and packed evaluations (eval_push / *_eval_run / eval_pop through SlowLds) are theirs, line by line; where
+// The light loops: ggx_direct_loops / disney_direct_loops (rls_loops.hpp) with every term staged instead of folded.  Where
 // they interleave the two lobes of the BSDF strategy in one pass over the samples, here each lobe is a pass of its own (the
-// queue's segments 1 and 2), so that one running count ranks a point's rays in queue order.  A change to either loop in
-// rls_loops.hpp has to be made here too (tests/test_gpu_trace_lights.py holds the two copies together bit for bit):
-//   segment 0 = the loops' first pass  (`mode != RLS_MIS_BSDF_ONLY`: cone_sample, eval_push, *_light_eval_run, eval_pop);
-//   rlGgx    segment 1 = the Oren-Nayar part of the second pass's last sweep (cosine_hemisphere, oren_nayar_pdf / _brdf),
-//            segment 2 = the rest of the second pass (ggx_vndf_push, slow_run, ggx_vndf_pop, eval_push, ggx_hit_eval_run);
-//   rlDisney segment 1 = the second pass's "diffuse lobe" half (cosine_hemisphere, disney_hit_eval_run<K, true>),
-//            segment 2 = its "specular lobe" half (disney_spec_push, slow_run, disney_spec_pop, disney_hit_eval_run<K, false>).
+// queue's segments 1 and 2), so that one running count ranks a point's rays in queue order:
+//   segment 0 = the loops' first pass, the light strategy (RLS_LIGHT_SAMPLE_PUSH, *_light_eval_run, eval_pop);
+//   segment 1 = the BSDF strategy's diffuse lobe: rlGgx's Oren-Nayar sample, rlDisney's packed cosine-weighted one;
+//   segment 2 = the BSDF strategy's specular lobe (RLS_HIT_SAMPLE_EVAL, eval_pop).
+// The two macros are the analytic loops' own lines (rls_loops.hpp).  Still written there and here, to be changed together
+// (tests/test_gpu_trace_lights.py holds the copies together bit for bit): the pick-up sweeps after the evaluations, the
+// Oren-Nayar sample, rlDisney's diffuse-lobe sweeps, and rlGgx's RLS_HIT_SAMPLE_EVAL lines, written out in ggx_direct_loops.
+// The two kernels stay written out: with their common walk in a force-inlined shadow_emit_points<G, Node> (the argument
+// struct by reference or by value, the segments as members of a node policy) rlDisney's kernel spilled 8 more vector
+// registers at every G (scratch 56 -> 96 B at G = 1) and ran 0.8 % slower; rlDisney's body alone behind a force-inlined
+// function taking the struct by reference went from 56 to 144 B.
+
+// rlGgx's lobe for RLS_HIT_SAMPLE_EVAL: the VNDF sampler, the reflected direction (streams +2/3)
+struct GgxHitLobe {
+    const Ggx &g;
+    const VndfView &w;
+    V3 N;
+    template <int K>
+    RLS_DEV void push(SlowLds<K> &slow, int k, int &qn, bool ok, float rx, float ry) const { ggx_vndf_push<K>(slow, k, qn, ok, w, rx, ry); }
+    template <int K>
+    RLS_DEV V3 pop(const SlowLds<K> &slow, int k) const { return reflect_direction(g.view, ggx_vndf_pop<K>(slow, k, w, g.fr)); }
+    RLS_DEV bool hit(V3 L) const { return !is_zero(L) && dot(L, N) > 0.0f; }
+    template <int K>
+    RLS_DEV void run(SlowLds<K> &slow, int qn, float conePdf, int mode) const { ggx_hit_eval_run<K>(slow, qn, g, conePdf, mode); }
+};
 
 // One point's place in the staging and its running ray count
 template <int G, class IO>
@@ -341,15 +361,8 @@ __global__ RLS_INT_ATTR void ggx_direct_emit_kernel(ShadowEmitIO<rls_ggx_closure
             // segment 0: one light sample, both lobes
             if (mode == RLS_MIS_BSDF_ONLY) st.skip(l, 0);
             for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {
-                int qn = 0;
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const int s = s0 + k * G;
-                    const int sc = s < spp ? s : 0;
-                    const V3 L = cone_sample(cone, bits_u01(tab[0][sc] ^ scr[0]), bits_u01(tab[1][sc] ^ scr[1]));
-                    eval_push<K>(slow, k, qn, s < spp && cone.valid && dot(L, N) > 0.0f, L);
-                    slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;
-                }
+                RLS_LIGHT_SAMPLE_PUSH(slow, qn, tab, spp, s0, cone, N, scr[0], scr[1],
+                                      slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;)
                 ggx_light_eval_run<K>(slow, qn, g, on, cone.pdf, sampleDiffuse, mode);
 #pragma unroll 1
                 for (int k = 0; k < K; k++) {
@@ -383,33 +396,7 @@ __global__ RLS_INT_ATTR void ggx_direct_emit_kernel(ShadowEmitIO<rls_ggx_closure
             // segment 2: one BSDF sample of the GGX lobe (streams +2/3); the few that hit the light are evaluated packed
             if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 2);
             for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
-                int qn = 0;
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const int s = s0 + k * G;
-                    const int sc = s < spp ? s : 0;
-                    ggx_vndf_push<K>(slow, k, qn, s < spp && cone.valid, w, bits_u01(tab[0][sc] ^ scr[2]),
-                                     bits_u01(tab[1][sc] ^ scr[3]));
-                }
-                slow_run<K>(slow, qn);
-                uint32_t hits = 0;
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const int s = s0 + k * G;
-                    const V3 M = ggx_vndf_pop<K>(slow, k, w, g.fr);
-                    const V3 L = reflect_direction(g.view, M);
-                    const bool hit = s < spp && cone.valid && !is_zero(L) && dot(L, N) > 0.0f && cone_hit(cone, L);
-                    hits |= (hit ? 1u : 0u) << k;
-                    slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;
-                }
-                wave_lds_fence();
-                qn = 0;
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
-                    eval_push<K>(slow, k, qn, ((hits >> k) & 1u) != 0, L);
-                }
-                ggx_hit_eval_run<K>(slow, qn, g, cone.pdf, mode);
+                RLS_HIT_SAMPLE_EVAL(slow, (GgxHitLobe{ g, w, N }), tab, spp, s0, cone, scr[2], scr[3], mode)
 #pragma unroll 1
                 for (int k = 0; k < K; k++) {
                     const int s = s0 + k * G;
@@ -455,14 +442,7 @@ __global__ RLS_DISNEY_LIGHT_ATTR void disney_direct_emit_kernel(ShadowEmitIO<rls
             // is drawn again in the second sweep)
             if (mode == RLS_MIS_BSDF_ONLY) st.skip(l, 0);
             for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {
-                int qn = 0;
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const int s = s0 + k * G;
-                    const int sc = s < spp ? s : 0;
-                    const V3 L = cone_sample(cone, bits_u01(tab[0][sc] ^ scr[0]), bits_u01(tab[1][sc] ^ scr[1]));
-                    eval_push<K>(slow, k, qn, s < spp && cone.valid && dot(L, N) > 0.0f, L);
-                }
+                RLS_LIGHT_SAMPLE_PUSH(slow, qn, tab, spp, s0, cone, N, scr[0], scr[1], )
                 disney_light_eval_run<K>(slow, qn, d, cone.pdf, mode);
 #pragma unroll 1
                 for (int k = 0; k < K; k++) {
@@ -503,32 +483,7 @@ __global__ RLS_DISNEY_LIGHT_ATTR void disney_direct_emit_kernel(ShadowEmitIO<rls
             // reflected directions that hit the light
             if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 2);
             for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
-                int qn = 0;
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const int s = s0 + k * G;
-                    const int sc = s < spp ? s : 0;
-                    disney_spec_push<K>(slow, k, qn, s < spp && cone.valid, d, w, bits_u01(tab[0][sc] ^ scr[4]),
-                                        bits_u01(tab[1][sc] ^ scr[5]));
-                }
-                slow_run<K>(slow, qn);
-                uint32_t hits = 0;
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const int s = s0 + k * G;
-                    const V3 L = disney_spec_pop<K>(slow, k, d, w);
-                    const bool hit = s < spp && cone.valid && cone_hit(cone, L);
-                    hits |= (hit ? 1u : 0u) << k;
-                    slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;
-                }
-                wave_lds_fence();
-                qn = 0;
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
-                    eval_push<K>(slow, k, qn, ((hits >> k) & 1u) != 0, L);
-                }
-                disney_hit_eval_run<K, false>(slow, qn, d, cone.pdf, mode);
+                RLS_HIT_SAMPLE_EVAL(slow, (DisneySpecHitLobe{ d, w }), tab, spp, s0, cone, scr[4], scr[5], mode)
 #pragma unroll 1
                 for (int k = 0; k < K; k++) {
                     float t[4], us[3] = { 0.0f, 0.0f, 0.0f };
@@ -1044,25 +999,27 @@ RLS_FLAVOURS(sss_scatter_resolve, SssResolveIO)
 
 namespace {
 
-// the staging planes of an emit inside the caller's scratch, each 256-byte aligned
+// The staging of an emit carved out of the caller's scratch, each part 256-byte aligned: `planes` float planes and the tags
+// (tag_bytes each) of n * slots_per_point slots, then the scan's tile sums.  The sample-ray emits: dir[3], w[3], 16-bit tags,
+// spp slots a point; the light loops: ShadowCompactIO's planes, 32-bit tags, n_lights * 3 * spp slots a point.
+constexpr int kRayPlanes = 6;
 struct Staging {
-    float *dir[3];
-    float *w[3];
-    uint16_t *tag;
+    float *f[kShadowPlanes];
+    void *tag;
     int64_t *totals;
     int64_t tiles;
     size_t bytes;
 };
+static_assert(kRayPlanes <= kShadowPlanes, "Staging::f holds the planes of either emit");
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline Staging staging(void *base, int64_t n, int spp)
+inline Staging staging(void *base, int64_t n, int slots_per_point, int planes, size_t tag_bytes)
 {
     Staging s = {};
-    const size_t slots = (size_t)n * (size_t)spp;
+    const size_t slots = (size_t)n * (size_t)slots_per_point;
     char *p = (char *)base;
     size_t off = 0;
-    for (int k = 0; k < 3; k++) { s.dir[k] = (float *)(p + off); off += align256(slots * sizeof(float)); }
-    for (int k = 0; k < 3; k++) { s.w[k] = (float *)(p + off); off += align256(slots * sizeof(float)); }
-    s.tag = (uint16_t *)(p + off); off += align256(slots * sizeof(uint16_t));
+    for (int k = 0; k < planes; k++) { s.f[k] = (float *)(p + off); off += align256(slots * sizeof(float)); }
+    s.tag = p + off; off += align256(slots * tag_bytes);
     s.tiles = (n + kScanTile - 1) / kScanTile;
     s.totals = (int64_t *)(p + off); off += align256((size_t)(s.tiles > 0 ? s.tiles : 1) * sizeof(int64_t));
     s.bytes = off;
@@ -1099,6 +1056,20 @@ rls_status scan_counts(rls_context *ctx, int64_t *offsets, int64_t n, int64_t *t
     return rlsh::check_launch("trace_scan_add_kernel");
 }
 
+// What every emit does between its checks and its compaction: the closure's emit kernel (dispatch, with G for the batch)
+// leaves the per-point counts in offsets, which are then scanned in place.
+template <class IO>
+rls_status emit_and_scan(rls_context *ctx, IO &io, int64_t n, int spp_n, uint32_t seed, uint64_t first_index, int64_t *offsets,
+                         const Staging &st, const char *name, rls_status (*dispatch)(rls_context *, int, const IO &, const char *))
+{
+    io.count = offsets;
+    set_loop(io, n, spp_n, seed, first_index);
+    const rls_status s = dispatch(ctx, pick_group(ctx, n, spp_n * spp_n), io, name);
+    return s != RLS_OK ? s : scan_counts(ctx, offsets, n, st.totals, st.tiles);
+}
+// points per compaction tile: as many as tile_slots slots hold, a point's index in its tile being 8 bits
+inline int compact_tile_points(int tile_slots, int per_point) { return std::min(tile_slots / per_point, kCompactMaxPoints); }
+
 // Every emit: the argument checks (lobe_ok: the rlDisney lobe, checked after spp_n), the empty queue of n == 0, the staging
 // in the caller's scratch, then the closure's emit kernel (dispatch, with G for the batch) and the steps the closures share:
 // the per-point counts scanned in place into offsets, the kept records compacted into the queue (nw weight planes).  side:
@@ -1117,23 +1088,19 @@ rls_status emit(rls_context *ctx, int64_t n, const Closure *c, int spp_n, uint32
     RLS_REQUIRE(rlsh::has3(q->dir), "queue.dir plane is NULL");
     RLS_REQUIRE(nw == 1 ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
     RLS_REQUIRE(q->capacity >= n * spp, "queue.capacity < n * spp_n^2");
-    const Staging st = staging(q->scratch, n, spp);
+    const Staging st = staging(q->scratch, n, spp, kRayPlanes, sizeof(uint16_t));
     RLS_REQUIRE(q->scratch != nullptr && q->scratch_bytes >= st.bytes, "queue.scratch is NULL or smaller than rls_trace_scratch_bytes");
 
     EmitIO<Closure> io = {};
     io.c = *c;
-    for (int k = 0; k < 3; k++) { io.dir[k] = st.dir[k]; io.w[k] = st.w[k]; }
-    io.tag = st.tag; io.count = q->offsets; io.side = side;
-    set_loop(io, n, spp_n, seed, first_index);
-    rls_status s = dispatch(ctx, pick_group(ctx, n, spp), io, name);
-    if (s != RLS_OK) return s;
-
-    if ((s = scan_counts(ctx, q->offsets, n, st.totals, st.tiles)) != RLS_OK) return s;
+    for (int k = 0; k < 3; k++) { io.dir[k] = st.f[k]; io.w[k] = st.f[3 + k]; }
+    io.tag = (uint16_t *)st.tag; io.side = side;
+    if (rls_status s = emit_and_scan(ctx, io, n, spp_n, seed, first_index, q->offsets, st, name, dispatch)) return s;
 
     TraceCompactIO cio = {};
-    for (int k = 0; k < 3; k++) { cio.sdir[k] = st.dir[k]; cio.sw[k] = st.w[k]; }
-    cio.tag = st.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp;
-    cio.tile_points = kCompactSlots / spp < kCompactMaxPoints ? kCompactSlots / spp : kCompactMaxPoints;
+    for (int k = 0; k < 3; k++) { cio.sdir[k] = st.f[k]; cio.sw[k] = st.f[3 + k]; }
+    cio.tag = io.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp;
+    cio.tile_points = compact_tile_points(kCompactSlots, spp);
     const dim3 cgrid = rlsh::grid_for(ctx, n, cio.tile_points);
     if (nw == 1) hipLaunchKernelGGL(trace_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
     else hipLaunchKernelGGL(trace_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
@@ -1156,28 +1123,6 @@ rls_status resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, int spp_
     if (refract) hipLaunchKernelGGL(trace_resolve_kernel<1>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
     else hipLaunchKernelGGL(trace_resolve_kernel<3>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
     return rlsh::check_launch(refract ? "rls_trace_ggx_refract_resolve" : "rls_trace_ggx_glossy_resolve");
-}
-
-// the staging planes of a light-loop emit inside the caller's scratch (ShadowEmitIO), each 256-byte aligned
-struct ShadowStaging {
-    float *f[kShadowPlanes];
-    uint32_t *tag;
-    int64_t *totals;
-    int64_t tiles;
-    size_t bytes;
-};
-inline ShadowStaging shadow_staging(void *base, int64_t n, int slots_per_point)
-{
-    ShadowStaging s = {};
-    const size_t slots = (size_t)n * (size_t)slots_per_point;
-    char *p = (char *)base;
-    size_t off = 0;
-    for (int k = 0; k < kShadowPlanes; k++) { s.f[k] = (float *)(p + off); off += align256(slots * sizeof(float)); }
-    s.tag = (uint32_t *)(p + off); off += align256(slots * sizeof(uint32_t));
-    s.tiles = (n + kScanTile - 1) / kScanTile;
-    s.totals = (int64_t *)(p + off); off += align256((size_t)(s.tiles > 0 ? s.tiles : 1) * sizeof(int64_t));
-    s.bytes = off;
-    return s;
 }
 
 // the planes both light-loop verbs need of a queue; ggx: weight_diffuse is its .r plane alone
@@ -1208,21 +1153,18 @@ rls_status shadow_emit(rls_context *ctx, int64_t n, ClosureCheck closure, const 
     if (rls_status s = copy_lights(lights, n_lights, 1, io.lights, &io.nl)) return s;
     if (rls_status s = check_shadow_queue(name, q, ggx, n, io.nl, spp)) return s;
     const int slots = io.nl * kShadowSegments * spp;
-    const ShadowStaging st = shadow_staging(q->scratch, n, slots);
+    const Staging st = staging(q->scratch, n, slots, kShadowPlanes, sizeof(uint32_t));
     RLS_REQUIRE_IN(name, q->scratch != nullptr && q->scratch_bytes >= st.bytes,
                    "queue.scratch is NULL or smaller than rls_trace_shadow_scratch_bytes");
 
     for (int k = 0; k < 3; k++) { io.dir[k] = st.f[k]; io.ws[k] = st.f[4 + k]; io.wd[k] = st.f[7 + k]; }
-    io.maxdist = st.f[3]; io.tag = st.tag; io.count = q->offsets;
-    set_loop(io, n, spp_n, seed, first_index);
-    rls_status s = dispatch(ctx, pick_group(ctx, n, spp), io, name);
-    if (s != RLS_OK) return s;
-    if ((s = scan_counts(ctx, q->offsets, n, st.totals, st.tiles)) != RLS_OK) return s;
+    io.maxdist = st.f[3]; io.tag = (uint32_t *)st.tag;
+    if (rls_status s = emit_and_scan(ctx, io, n, spp_n, seed, first_index, q->offsets, st, name, dispatch)) return s;
 
     ShadowCompactIO cio = {};
     for (int k = 0; k < kShadowPlanes; k++) cio.src[k] = st.f[k];
-    cio.tag = st.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp; cio.slots = slots;
-    cio.tile_points = kShadowMaxSlots / slots < kCompactMaxPoints ? kShadowMaxSlots / slots : kCompactMaxPoints;
+    cio.tag = io.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp; cio.slots = slots;
+    cio.tile_points = compact_tile_points(kShadowMaxSlots, slots);
     const dim3 cgrid = rlsh::grid_for(ctx, n, cio.tile_points);
     if (ggx) hipLaunchKernelGGL(shadow_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
     else hipLaunchKernelGGL(shadow_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
@@ -1271,7 +1213,7 @@ rls_status rls_trace_scratch_bytes(int64_t n, int spp_n, size_t *bytes)
     RLS_REQUIRE(bytes != nullptr, "bytes is NULL");
     RLS_REQUIRE(n >= 0, "n < 0");
     RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    *bytes = staging(nullptr, n, spp_n * spp_n).bytes;
+    *bytes = staging(nullptr, n, spp_n * spp_n, kRayPlanes, sizeof(uint16_t)).bytes;
     return RLS_OK;
 }
 
@@ -1355,7 +1297,7 @@ rls_status rls_trace_shadow_scratch_bytes(int64_t n, int n_lights, int spp_n, si
     RLS_REQUIRE(n >= 0, "n < 0");
     RLS_REQUIRE(n_lights >= 1 && n_lights <= RLS_MAX_LIGHTS, "n_lights out of range (RLS_MAX_LIGHTS)");
     RLS_REQUIRE(spp_n >= 1 && spp_n * spp_n <= kMaxSpp, "spp_n must be in [1, 16]");
-    *bytes = shadow_staging(nullptr, n, n_lights * kShadowSegments * spp_n * spp_n).bytes;
+    *bytes = staging(nullptr, n, n_lights * kShadowSegments * spp_n * spp_n, kShadowPlanes, sizeof(uint32_t)).bytes;
     return RLS_OK;
 }
 
