@@ -237,6 +237,102 @@ rls_status rls_trace_disney_direct_resolve(rls_context *ctx, int64_t n, const rl
                                            int spp_n, const rls_shadow_queue *q, rls_crgb visibility,
                                            rls_rgb direct_diffuse, rls_rgb direct_specular);
 
+/* ------------------------------------------------------------------------------------------
+ * Whole nodes: shader_evaluate of rlGgx and rlDisney (src/rlGgx.cpp:248-327, src/rlDisney.cpp:685-727) cut at every
+ * place it traces.  rls_ggx_shade / rls_disney_shade (rlshaders_amd.h) run the light loop and the indirect loops back to
+ * back with no occluders and a uniform environment; here the node's emit fills one queue per loop, the renderer traces
+ * them, and ONE resolve composes the node's AOVs and sg->out.RGB.
+ *
+ * The samples are the whole-node calls' own, NOT the stand-alone integrators': light l draws from scramble streams
+ * 6 l .. 6 l + 5, and the indirect loops from the stream pairs after the lights' (pair p = streams 2 p, 2 p + 1):
+ *   rlGgx:    pair 24 integrateGlossy, pair 25 integrateRefract, pair 26 indirect diffuse (AiBRDFIntegrate over the
+ *             Oren-Nayar closure, src/rlGgx.cpp:315-319);
+ *   rlDisney: pair 24 integrateDiffuse, pair 25 integrateGlossy.
+ * (rls_trace_ggx_glossy_emit, rls_trace_ggx_refract_emit and rls_trace_disney_emit draw from pairs 0 and 1: their
+ * queues are not a node's.)  The node's gates are applied by the emit and again by the resolve:
+ *   rlGgx glossy:    a point whose KsColor is small (every channel below AI_EPSILON, src/rlGgx.h:174-176) has no rays;
+ *   rlGgx refract:   a point with small KtColor * Kt has no rays (src/rlGgx.cpp:307-309).  traced != 0: the samples of
+ *                    integrateRefract's traced branch (dir, weight.r, kind).  traced == 0: the ONE ray of the untraced
+ *                    branch (src/rlGgx.h:213-222), the refraction of the view about the shading normal, weight.r =
+ *                    SQR(iorOut / iorIn) * |N . dir|, sample 0, kind RLS_RAY_TRANSMITTED; no ray on total internal
+ *                    reflection;
+ *   rlGgx diffuse:   a point with sampleDiffuse false (small KdColor * Kd, src/rlGgx.cpp:279-281) has no rays; else per
+ *                    sample a cosine-weighted direction about the shading normal and weight.r = brdf / pdf of the
+ *                    Oren-Nayar closure where pdf > 0, queued unless it is 0;
+ *   rlDisney:        both lobes as rls_trace_disney_emit queues them (valid: pdf > 1e-4; f / pdf not 0 in all channels).
+ * The shadow member is exactly what rls_trace_ggx_direct_emit / rls_trace_disney_direct_emit produce.
+ *
+ * Every queue is laid out as above (point-major CSR, deterministic, no atomics); the emit fills the node's queues one
+ * after another on the context's stream, one emit kernel per queue (each builds the point's closure again), and never
+ * synchronises the host.  Each queue brings its own scratch of rls_trace_scratch_bytes / rls_trace_shadow_scratch_bytes;
+ * the queues of ONE node emit may all point at the same scratch block, sized to the largest of them.
+ *
+ * Resolve, one launch: per point the light loop's sums as rls_trace_*_direct_resolve forms them and, per ray queue and
+ * channel c, S_c = (sum radiance_c w) * inv with inv = 1 / spp_n^2 (1 for the refraction queue when traced == 0); then
+ *   rlGgx:    direct_diffuse, direct_specular: as rls_trace_ggx_direct_resolve (black when n_lights == 0);
+ *             refraction_c        = S_c(refract) * (KtColor_c * Kt)
+ *             indirect_diffuse_c  = (KdColor_c * Kd) * S_c(diffuse)
+ *             indirect_specular_c = S_c(glossy) * Ks
+ *             out = ((direct_diffuse + direct_specular) + refraction) + (indirect_diffuse + indirect_specular)
+ *   rlDisney: indirect_diffuse_c = S_c(diffuse), indirect_specular_c = S_c(specular);
+ *             out = (direct_diffuse + direct_specular) + (indirect_diffuse + indirect_specular)
+ * S is summed about a reference radiance, so that a uniform environment reproduces the analytic call: with Lref_c the
+ * radiance of smallest magnitude among the point's rays (a property of the set of rays, not of their order), A = sum w and
+ * B_c = sum (radiance_c - Lref_c) w, both grown in queue order,
+ *             S_c = (A * inv) * Lref_c + B_c * inv
+ * which in exact arithmetic is (sum radiance_c w) * inv; in float32 it is within (k + 3) 2^-24 inv (|Lref_c| sum |w| +
+ * sum |radiance_c - Lref_c| |w|) of it for a point with k rays, and since |Lref_c| <= |radiance_c| on every ray, within
+ * 3 (k + 3) 2^-24 inv sum |radiance_c| |w| (2 for radiances of one sign): a bound relative to the sum of the terms' magnitudes,
+ * as a plain sum's, however bright a single ray is.  Where every ray of a point carries the same radiance, B is
+ * exactly 0 and S = (sum w * inv) * radiance: the analytic loops' own expression.  An AOV whose gate is shut is exactly 0.
+ * With a visibility of 1 and the same radiance env on every ray of the ray queues the resolve returns rls_ggx_shade /
+ * rls_disney_shade at that env bit for bit -- env = {1, 1, 1} or any other: every AOV and out, EXACT and FAST, traced 0 and 1.
+ * ---------------------------------------------------------------------------------------- */
+
+typedef struct rls_ggx_node_queues {
+    const rls_shadow_queue *shadow;  /* the light loop; NULL if and only if n_lights == 0 */
+    const rls_ray_queue *glossy;     /* integrateGlossy, pair 24: dir, weight (3 planes) */
+    const rls_ray_queue *refract;    /* integrateRefract, pair 25: dir, weight.r, kind */
+    const rls_ray_queue *diffuse;    /* Oren-Nayar indirect diffuse, pair 26: dir, weight.r */
+} rls_ggx_node_queues;
+
+/* what the renderer traced: per queue 3 planes of offsets[n] values, indexed by ray */
+typedef struct rls_ggx_node_traced {
+    rls_crgb visibility;             /* the shadow queue's; not read when n_lights == 0 */
+    rls_crgb glossy, refract, diffuse;   /* the radiance along each ray queue's rays */
+} rls_ggx_node_traced;
+
+typedef struct rls_disney_node_queues {
+    const rls_shadow_queue *shadow;  /* the light loop; NULL if and only if n_lights == 0 */
+    const rls_ray_queue *diffuse;    /* integrateDiffuse, pair 24: dir, weight (3 planes) */
+    const rls_ray_queue *specular;   /* integrateGlossy, pair 25: dir, weight (3 planes) */
+} rls_disney_node_queues;
+
+typedef struct rls_disney_node_traced {
+    rls_crgb visibility;             /* the shadow queue's; not read when n_lights == 0 */
+    rls_crgb diffuse, specular;
+} rls_disney_node_traced;
+
+/* The rays of rls_ggx_shade: the arguments are that call's (without env).  n == 0 writes empty queues. */
+rls_status rls_trace_ggx_shade_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                    rls_cvec3 P, const rls_sphere_light *lights, int n_lights, int traced, int spp_n,
+                                    uint32_t seed, uint64_t first_index, const rls_ggx_node_queues *q);
+
+/* rls_ggx_shade's AOVs and sg->out.RGB from what the renderer traced.  c, sh, lights, n_lights, traced, spp_n: those of the
+ * emit.  The five AOV planes of out are required, out->out may be NULL (all three planes). */
+rls_status rls_trace_ggx_shade_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                       const rls_sphere_light *lights, int n_lights, int traced, int spp_n,
+                                       const rls_ggx_node_queues *q, const rls_ggx_node_traced *t,
+                                       const rls_ggx_shade_out *out);
+
+/* The rays of rls_disney_shade, and its AOVs and sg->out.RGB from what the renderer traced. */
+rls_status rls_trace_disney_shade_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
+                                       const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                       uint64_t first_index, const rls_disney_node_queues *q);
+rls_status rls_trace_disney_shade_resolve(rls_context *ctx, int64_t n, const rls_sphere_light *lights, int n_lights,
+                                          int spp_n, const rls_disney_node_queues *q, const rls_disney_node_traced *t,
+                                          const rls_disney_shade_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,35 @@ struct ShadowResolveIO {
     int64_t n;
 };
 
+// Whole nodes (rls_trace_*_shade_emit / _resolve).  The node's indirect loops draw from the stream pairs after the lights'
+// (shade.hip, kShadeStream): kNodeStream is their first scramble stream, relative to kScrambleStream like a lobe's kStream.
+constexpr int kNodeStream = 2 * 3 * RLS_MAX_LIGHTS;      // pair 24
+
+// a ray emit of the rlGgx node: the closure's emit with the node parameters its gates read
+struct GgxNodeEmitIO : EmitIO<rls_ggx_closure> {
+    rls_ggx_shader sh;
+    int traced;              // the refraction queue: integrateRefract's traced branch, or (0) the one ray of the untraced one
+};
+
+// the node resolves: the light loop as shadow_resolve_kernel takes it (s.nl == 0: no queue; s.dd / s.ds: the two direct AOVs;
+// s.materials, s.sh: rlGgx's tails), a TraceResolveIO per ray queue (out: the queue's AOV), sg->out.RGB (NULL-able)
+struct GgxNodeResolveIO {
+    ShadowResolveIO s;
+    TraceResolveIO glossy, refract, diffuse;
+    rls_param_rgb KsColor;   // integrateGlossy's gate
+    rls_rgb out;
+    float inv;               // 1 / spp
+    int traced;
+    int64_t n;
+};
+struct DisneyNodeResolveIO {
+    ShadowResolveIO s;
+    TraceResolveIO diffuse, specular;
+    rls_rgb out;
+    float inv;
+    int64_t n;
+};
+
 // rlSss: the probe-ray emit and the scatter resolve.  Both walk tiles of `tile_points` consecutive points: ray j = i * spp + s
 // of the dense queue is ray j - p0 * spp of the tile that starts at point p0.  The emit takes up to kSssEmitRays rays per
 // tile (several per thread), the resolve up to kBlock (one per thread: its LDS holds the terms of every hit of the tile).

@@ -26,9 +26,16 @@
 // radiance x weight of a tile of rays are formed with coalesced loads into LDS, then each lane adds its point's ones.  The
 // glossy resolve serves the rlGgx glossy and both rlDisney queues.
 //
+// Whole nodes (rls_trace_*_shade_emit / _resolve; the section "Whole nodes" below): one emit kernel per queue of
+// rls_ggx_shade / rls_disney_shade -- the lobes above at the node's stream pairs, behind the node's gates -- and one resolve
+// launch per node (ggx_node_resolve_kernel, disney_node_resolve_kernel) that walks every queue with the two resolves' tile
+// walks (shadow_sums; ray_sums_about_reference, ray_sums' walk about a reference radiance) and composes the AOVs in registers.
+//
 // Built twice like the closure units of librlshaders_amd.so (rlshaders_amd/build.py, build_trace_library): RLS_FAST=0
 // carries the C ABI, the EXACT emit kernels and the mode-free scan / compact / resolve kernels; RLS_FAST=1 the FAST emit
 // kernels behind hidden symbols.
+#include <string.h>
+
 #include "rls_trace_device.hpp"
 
 namespace {
@@ -46,11 +53,12 @@ struct EmitRay {
 // A lobe policy supplies the rest, per point:
 //   Lobe(a, ii)              the closure at point ii
 //   kStream                  its scramble streams: kScrambleStream + kStream, + kStream + 1
+//   kGated, open             a node's gate (kGated): a point whose gate is shut (!open) draws nothing and queues nothing
 //   kPush, push(...)         the first sweep of the packed rare branches (SlowLds), if it has one
 //   kWeights, sample(...)    the per-sample term, in every lane of every round; returns whether the ray is queued
 //   side(spp)                the point's side output, in every lane (group reductions)
-template <int G, class Lobe, class Closure>
-__device__ __forceinline__ void emit_points(const EmitIO<Closure> &a)
+template <int G, class Lobe, class IO>
+__device__ __forceinline__ void emit_points(const IO &a)
 {
     constexpr int K = RLS_SPEC_BLOCK;
     __shared__ uint32_t tab[2][kMaxSpp];
@@ -65,6 +73,8 @@ __device__ __forceinline__ void emit_points(const EmitIO<Closure> &a)
         const uint32_t sx = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + Lobe::kStream);
         const uint32_t sy = hash_u32(a.seed, a.first + (uint64_t)ii, kScrambleStream + Lobe::kStream + 1);
         int run = 0;
+        bool open = true;
+        if constexpr (Lobe::kGated) open = lobe.open;
         for (int s0 = sub; s0 - sub < a.spp; s0 += K * G) {      // the same trip count in every lane
             if constexpr (Lobe::kPush) {
                 int cnt = 0;
@@ -72,20 +82,20 @@ __device__ __forceinline__ void emit_points(const EmitIO<Closure> &a)
                 for (int k = 0; k < K; k++) {
                     const int s = s0 + k * G;
                     const int sc = s < a.spp ? s : 0;
-                    lobe.push(slow, k, cnt, s < a.spp, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
+                    lobe.push(slow, k, cnt, s < a.spp && open, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
                 }
                 slow_run<K>(slow, cnt);
             }
 #pragma unroll 1
             for (int k = 0; k < K; k++) {
                 const int s = s0 + k * G;
-                const bool ok = s < a.spp;
+                const bool in = s < a.spp, ok = in && open;
                 float rx = 0.0f, ry = 0.0f;                             // a lobe without a push phase draws here
                 if (!Lobe::kPush && ok) { rx = bits_u01(tab[0][s] ^ sx); ry = bits_u01(tab[1][s] ^ sy); }
                 EmitRay r = {};
                 const bool keep = lobe.sample(slow, k, ok, rx, ry, r) && ok;      // (sample() first: every lane runs it)
                 const int rank = group_rank<G>(keep, sub, run);
-                if (live && ok) {
+                if (live && in) {
                     const int64_t slot = staging_slot(s, a.n, i);
                     if (keep) {
                         a.dir[0][slot] = r.dir.x; a.dir[1][slot] = r.dir.y; a.dir[2][slot] = r.dir.z;
@@ -108,6 +118,7 @@ __device__ __forceinline__ void emit_points(const EmitIO<Closure> &a)
 struct GgxLobe {
     static constexpr int kStream = 0;
     static constexpr bool kPush = true;
+    static constexpr bool kGated = false;
     Ggx g;
     VndfView w;
     __device__ GgxLobe(const EmitIO<rls_ggx_closure> &a, int64_t ii)
@@ -177,10 +188,12 @@ struct GgxRefract : GgxLobe {
 // packed through SlowLds as there).  A sample is valid where pdf > 1e-4 (src/rlDisney.cpp:309) and queued where it is valid
 // and f / pdf is not 0 in all three channels: what it would add to the integrator's sum is then not +0.  The side output is
 // the lobe's valid count.
-template <int G, bool SPEC>
+// STREAM: the lobe's first scramble stream; the node's loops draw from kNodeStream on (disney_shade_kernel).
+template <int G, bool SPEC, int STREAM = (SPEC ? 2 : 0)>
 struct DisneyLobe {
-    static constexpr int kStream = SPEC ? 2 : 0;
+    static constexpr int kStream = STREAM;
     static constexpr bool kPush = SPEC;
+    static constexpr bool kGated = false;
     static constexpr int kWeights = 3;
     Disney d;
     VndfView w;
@@ -249,6 +262,119 @@ template <int G, int FAST_MATH = RLS_FAST>
 __global__ RLS_INT_ATTR void disney_specular_emit_kernel(EmitIO<rls_disney_closure> a)
 {
     emit_points<G, DisneyLobe<G, true>>(a);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Whole nodes: the indirect loops of ggx_shade_kernel / disney_shade_kernel (csrc/shade.hip) as queues.  The lobes above with
+// the node's stream pairs (kNodeStream: 24 glossy, 25 refraction, 26 Oren-Nayar for rlGgx; 24 diffuse, 25 specular for
+// rlDisney) and, for rlGgx, the node's gates.  One emit kernel per queue: each builds the point's closure again.
+
+// integrateGlossy as the node calls it: black for a small KsColor without sampling (src/rlGgx.h:174-176)
+template <int G>
+struct GgxNodeGlossy : GgxGlossy<G> {
+    static constexpr int kStream = kNodeStream;
+    static constexpr bool kGated = true;
+    bool open;
+    __device__ GgxNodeGlossy(const GgxNodeEmitIO &a, int64_t ii) : GgxGlossy<G>(a, ii)
+    {
+        float kr, kg, kb;
+        ldrgb(a.c.KsColor, pindex(a.c.materials, ii), kr, kg, kb);
+        open = !color_is_small(kr, kg, kb);
+    }
+};
+
+// integrateRefract behind transmission's gate (src/rlGgx.cpp:307-309).  traced: ggx_refract_loop's samples; else the host
+// launches with one sample per point, and that sample is ggx_refract_untraced's ray (rls_loops.hpp): the refraction about the
+// shading normal, eta2 * |N . dir|, nothing on total internal reflection.
+template <int G>
+struct GgxNodeRefract : GgxRefract<G> {
+    static constexpr int kStream = kNodeStream + 2;
+    static constexpr bool kGated = true;
+    bool open, traced;
+    __device__ GgxNodeRefract(const GgxNodeEmitIO &a, int64_t ii) : GgxRefract<G>(a, ii)
+    {
+        const PIndex<int64_t> pk = pindex(a.c.materials, ii);
+        const float kt = ldp(a.sh.Kt, pk);
+        float tr, tg, tb;
+        ldrgb(a.sh.KtColor, pk, tr, tg, tb);
+        open = !color_is_small(tr * kt, tg * kt, tb * kt);
+        traced = a.traced != 0;
+    }
+    template <int K>
+    __device__ void push(SlowLds<K> &slow, int k, int &cnt, bool ok, float rx, float ry)
+    {
+        GgxLobe::template push<K>(slow, k, cnt, ok && traced, rx, ry);
+    }
+    template <int K>
+    __device__ bool sample(const SlowLds<K> &slow, int k, bool ok, float rx, float ry, EmitRay &r)
+    {
+        if (traced) return GgxRefract<G>::template sample<K>(slow, k, ok, rx, ry, r);
+        const Ggx &g = this->g;
+        if (ok && ggx_refract(g, g.fr.N, r.dir)) r.w[0] = g.eta2 * absf(dot(g.fr.N, r.dir));      // src/rlGgx.h:216
+        return !(r.w[0] == 0.0f);
+    }
+};
+
+// the indirect diffuse loop of ggx_shade_kernel (src/rlGgx.cpp:315-319): cosine-weighted directions about the shading
+// normal, brdf / pdf of the Oren-Nayar closure where pdf > 0, in one plane; queued where it is not 0
+template <int G>
+struct GgxNodeDiffuse {
+    static constexpr int kStream = kNodeStream + 4;
+    static constexpr bool kPush = false;
+    static constexpr bool kGated = true;
+    static constexpr int kWeights = 1;
+    Frame fr;
+    OrenNayar on;
+    V3 view;
+    bool open;
+    __device__ GgxNodeDiffuse(const GgxNodeEmitIO &a, int64_t ii)
+    {
+        RLS_GGX_LOAD(g, a.c, ii)
+        fr = g.fr;
+        view = wo;
+        on = oren_nayar_make(N, ldp(a.sh.diffuseRoughness, pk));
+        const float kd = ldp(a.sh.Kd, pk);
+        float dr, dg, db;
+        ldrgb(a.sh.KdColor, pk, dr, dg, db);
+        open = !color_is_small(dr * kd, dg * kd, db * kd);          // sampleDiffuse, src/rlGgx.cpp:279-281
+    }
+    template <int K>
+    __device__ bool sample(const SlowLds<K> &, int, bool ok, float rx, float ry, EmitRay &r)
+    {
+        if (ok) {
+            r.dir = cosine_hemisphere(fr, rx, ry);
+            const float pd = oren_nayar_pdf(on, r.dir);
+            if (pd > 0.0f) r.w[0] = R_DIV(oren_nayar_brdf(on, view, r.dir), pd);
+        }
+        return !(r.w[0] == 0.0f);
+    }
+    __device__ float side(int) const { return 0.0f; }
+};
+
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_node_glossy_emit_kernel(GgxNodeEmitIO a)
+{
+    emit_points<G, GgxNodeGlossy<G>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_node_refract_emit_kernel(GgxNodeEmitIO a)
+{
+    emit_points<G, GgxNodeRefract<G>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_node_diffuse_emit_kernel(GgxNodeEmitIO a)
+{
+    emit_points<G, GgxNodeDiffuse<G>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void disney_node_diffuse_emit_kernel(EmitIO<rls_disney_closure> a)
+{
+    emit_points<G, DisneyLobe<G, false, kNodeStream>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void disney_node_specular_emit_kernel(EmitIO<rls_disney_closure> a)
+{
+    emit_points<G, DisneyLobe<G, true, kNodeStream + 2>>(a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -749,40 +875,107 @@ __global__ __launch_bounds__(rlsh::kBlock) void trace_compact_kernel(TraceCompac
 // i.e. one contiguous range of rays, in tiles of kResolveTile rays: coalesced loads form the products L x weight in LDS,
 // then lane i adds those of its own rays, in order.
 constexpr int kResolveTile = 1024;
+// The tile walk over one ray queue for the workgroup's points p0 .. p0 + kBlock - 1 (trace_resolve_kernel and the node
+// resolves): acc = the sum over this lane's point's rays of L x weight, in queue order.  Whole workgroup; the walk opens
+// with a barrier, so prod may hold an earlier walk's products.  NW: the weight's planes.
+template <int NW>
+__device__ __forceinline__ void ray_sums(float (*prod)[kResolveTile], const TraceResolveIO &a, int64_t p0, int64_t n,
+                                         float (&acc)[3])
+{
+    const int64_t i = p0 + threadIdx.x;
+    const bool live = i < n;
+    const int64_t pend = n - p0 < rlsh::kBlock ? n : p0 + rlsh::kBlock;
+    const int64_t r0 = a.offsets[p0], r1 = a.offsets[pend];
+    const int64_t lo = live ? a.offsets[i] : 0, hi = live ? a.offsets[i + 1] : 0;
+    float aR = 0.0f, aG = 0.0f, aB = 0.0f;
+    for (int64_t t0 = r0; t0 < r1; t0 += kResolveTile) {
+        const int tn = r1 - t0 < kResolveTile ? (int)(r1 - t0) : kResolveTile;
+        __syncthreads();                                     // the previous tile's products are consumed
+        for (int k = threadIdx.x; k < tn; k += rlsh::kBlock) {
+            const int64_t q = t0 + k;
+            if (NW == 3) {
+                prod[0][k] = a.L.r[q] * a.w[0][q]; prod[1][k] = a.L.g[q] * a.w[1][q]; prod[2][k] = a.L.b[q] * a.w[2][q];
+            } else {
+                const float wq = a.w[0][q];
+                prod[0][k] = a.L.r[q] * wq; prod[1][k] = a.L.g[q] * wq; prod[2][k] = a.L.b[q] * wq;
+            }
+        }
+        __syncthreads();
+        const int64_t b = lo > t0 ? lo : t0, e = hi < t0 + tn ? hi : t0 + tn;
+        for (int64_t q = b; q < e; q++) {
+            aR += prod[0][q - t0]; aG += prod[1][q - t0]; aB += prod[2][q - t0];
+        }
+    }
+    acc[0] = aR; acc[1] = aG; acc[2] = aB;
+}
+
 template <int NW>
 __global__ __launch_bounds__(rlsh::kBlock) void trace_resolve_kernel(TraceResolveIO a)
 {
     __shared__ float prod[3][kResolveTile];
     for (int64_t p0 = (int64_t)blockIdx.x * rlsh::kBlock; p0 < a.n; p0 += (int64_t)gridDim.x * rlsh::kBlock) {
         const int64_t i = p0 + threadIdx.x;
-        const bool live = i < a.n;
-        const int64_t pend = a.n - p0 < rlsh::kBlock ? a.n : p0 + rlsh::kBlock;
-        const int64_t r0 = a.offsets[p0], r1 = a.offsets[pend];
-        const int64_t lo = live ? a.offsets[i] : 0, hi = live ? a.offsets[i + 1] : 0;
-        float aR = 0.0f, aG = 0.0f, aB = 0.0f;
-        for (int64_t t0 = r0; t0 < r1; t0 += kResolveTile) {
-            const int tn = r1 - t0 < kResolveTile ? (int)(r1 - t0) : kResolveTile;
-            __syncthreads();                                     // the previous tile's products are consumed
-            for (int k = threadIdx.x; k < tn; k += rlsh::kBlock) {
-                const int64_t q = t0 + k;
-                if (NW == 3) {
-                    prod[0][k] = a.L.r[q] * a.w[0][q]; prod[1][k] = a.L.g[q] * a.w[1][q]; prod[2][k] = a.L.b[q] * a.w[2][q];
-                } else {
-                    const float wq = a.w[0][q];
-                    prod[0][k] = a.L.r[q] * wq; prod[1][k] = a.L.g[q] * wq; prod[2][k] = a.L.b[q] * wq;
-                }
-            }
-            __syncthreads();
-            const int64_t b = lo > t0 ? lo : t0, e = hi < t0 + tn ? hi : t0 + tn;
-            for (int64_t q = b; q < e; q++) {
-                aR += prod[0][q - t0]; aG += prod[1][q - t0]; aB += prod[2][q - t0];
-            }
-        }
-        if (live) {
-            if (NW == 1) { aR *= a.scale; aG *= a.scale; aB *= a.scale; }
-            a.out.r[i] = aR; a.out.g[i] = aG; a.out.b[i] = aB;
+        float acc[3];
+        ray_sums<NW>(prod, a, p0, a.n, acc);
+        if (i < a.n) {
+            if (NW == 1) { acc[0] *= a.scale; acc[1] *= a.scale; acc[2] *= a.scale; }
+            a.out.r[i] = acc[0]; a.out.g[i] = acc[1]; a.out.b[i] = acc[2];
         }
     }
+}
+
+// The node resolves' walk over one ray queue: the sum over this lane's point's rays of L x weight, x inv, formed about a
+// reference radiance so that a UNIFORM radiance gives the analytic call's bits.  Per channel, with Lref = the radiance of
+// smallest magnitude among the point's rays (the first such in queue order; a property of the set of rays, not of their order):
+//     A = sum w (in queue order: the analytic loop's sum),  B = sum (L - Lref) w,   S = (A inv) Lref + B inv
+// In exact arithmetic S = inv sum L w.  Where every ray of the point carries the same radiance env, every term of B is
+// exactly 0 and S = (A inv) env: what ggx_shade_kernel / disney_shade_kernel form from their sum and env (csrc/shade.hip),
+// for env = 1 and for any other.  Rounding: with k rays, |S - inv sum L w| <= (k + 3) 2^-24 inv (|Lref| sum |w| +
+// sum |L - Lref| |w|); |Lref| <= |L| on every ray, so that is at most 3 (k + 3) 2^-24 inv sum |L| |w| (2 for radiances of one
+// sign): a bound relative to the sum of the terms' magnitudes, as the plain sum's, whatever single ray is bright.
+// Lref is found in a pass of its own over the lane's rays in global memory (they are read again, coalesced, by the tiles).
+// The radiance and the weight of a tile go to LDS side by side (coalesced loads), lane i multiplies.
+// planes: 3 + NW rows.  A point without rays: S = 0.
+template <int NW>
+__device__ __forceinline__ void ray_sums_about_reference(float (*planes)[kResolveTile], const TraceResolveIO &a, int64_t p0,
+                                                         int64_t n, float inv, float (&S)[3])
+{
+    const int64_t i = p0 + threadIdx.x;
+    const bool live = i < n;
+    const int64_t pend = n - p0 < rlsh::kBlock ? n : p0 + rlsh::kBlock;
+    const int64_t r0 = a.offsets[p0], r1 = a.offsets[pend];
+    const int64_t lo = live ? a.offsets[i] : 0, hi = live ? a.offsets[i + 1] : 0;
+    float ref[3] = { 0.0f, 0.0f, 0.0f };
+    if (hi > lo) { ref[0] = a.L.r[lo]; ref[1] = a.L.g[lo]; ref[2] = a.L.b[lo]; }
+    for (int64_t q = lo + 1; q < hi; q++) {
+        const float v[3] = { a.L.r[q], a.L.g[q], a.L.b[q] };
+#pragma unroll
+        for (int c = 0; c < 3; c++) if (absf(v[c]) < absf(ref[c])) ref[c] = v[c];
+    }
+    float A[3] = { 0.0f, 0.0f, 0.0f }, B[3] = { 0.0f, 0.0f, 0.0f };
+    for (int64_t t0 = r0; t0 < r1; t0 += kResolveTile) {
+        const int tn = r1 - t0 < kResolveTile ? (int)(r1 - t0) : kResolveTile;
+        __syncthreads();                                     // the previous tile is consumed
+        for (int k = threadIdx.x; k < tn; k += rlsh::kBlock) {
+            const int64_t q = t0 + k;
+            planes[0][k] = a.L.r[q]; planes[1][k] = a.L.g[q]; planes[2][k] = a.L.b[q];
+#pragma unroll
+            for (int c = 0; c < NW; c++) planes[3 + c][k] = a.w[c][q];
+        }
+        __syncthreads();
+        const int64_t b = lo > t0 ? lo : t0, e = hi < t0 + tn ? hi : t0 + tn;
+        for (int64_t q = b; q < e; q++) {
+            const int k = (int)(q - t0);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float w = planes[3 + (NW == 3 ? c : 0)][k];
+                if (NW == 3 || c == 0) A[c] += w;
+                B[c] += (planes[c][k] - ref[c]) * w;
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) S[c] = (A[NW == 3 ? c : 0] * inv) * ref[c] + B[c] * inv;
 }
 
 // trace_compact_kernel for the light loops' queue: a tile of P consecutive points with a.slots slots each (P * slots <=
@@ -860,6 +1053,94 @@ __global__ __launch_bounds__(rlsh::kBlock) void shadow_compact_kernel(ShadowComp
 // (ggx_direct_loops / disney_direct_loops, rls_loops.hpp).  A light without rays is closed too: it adds radiance * 0 * inv.
 // NWD = 1 (rlGgx): weight_diffuse is one plane, and the tail diffuse *= KdColor * Kd, specular *= Ks follows (src/rlGgx.cpp:304-305).
 constexpr int kShadowTile = 1024;
+static_assert(kShadowTile == kResolveTile, "the node resolves walk both kinds of queue through one product store");
+
+// the lights' radiance into LDS, once per workgroup (the walk below indexes it by a per-lane light)
+__device__ __forceinline__ void stage_radiance(float (*rad)[3], const ShadowResolveIO &a)
+{
+    if (threadIdx.x < RLS_MAX_LIGHTS * 3) rad[threadIdx.x / 3][threadIdx.x % 3] = a.rad[threadIdx.x / 3][threadIdx.x % 3];
+    __syncthreads();
+}
+
+// The tile walk over the light loops' queue for the workgroup's points p0 .. p0 + kBlock - 1 (shadow_resolve_kernel and the
+// node resolves): oS / oD = the point's specular / diffuse sum over the lights, before rlGgx's tail.  Whole workgroup; opens
+// with a barrier like ray_sums.
+template <int NWD>
+__device__ __forceinline__ void shadow_sums(float (*prod)[kShadowTile], uint8_t *kinds, const float (*rad)[3],
+                                            const ShadowResolveIO &a, int64_t p0, float (&oS)[3], float (&oD)[3])
+{
+    constexpr bool GGX = NWD == 1;
+    const int64_t i = p0 + threadIdx.x;
+    const bool live = i < a.n;
+    const int64_t pend = a.n - p0 < rlsh::kBlock ? a.n : p0 + rlsh::kBlock;
+    const int64_t r0 = a.offsets[p0], r1 = a.offsets[pend];
+    const int64_t lo = live ? a.offsets[i] : 0, hi = live ? a.offsets[i + 1] : 0;
+    float lS[3] = { 0.0f, 0.0f, 0.0f }, lD[3] = { 0.0f, 0.0f, 0.0f }, bS[3] = { 0.0f, 0.0f, 0.0f }, bD[3] = { 0.0f, 0.0f, 0.0f };
+    for (int c = 0; c < 3; c++) { oS[c] = 0.0f; oD[c] = 0.0f; }
+    int l = 0;
+    auto close_light = [&]() {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float tS = rad[l][c] * (lS[c] + bS[c]) * a.inv, tD = rad[l][c] * (lD[c] + bD[c]) * a.inv;
+            oS[c] = l == 0 ? tS : oS[c] + tS;
+            oD[c] = l == 0 ? tD : oD[c] + tD;
+            lS[c] = 0.0f; lD[c] = 0.0f; bS[c] = 0.0f; bD[c] = 0.0f;
+        }
+        l++;
+    };
+    for (int64_t t0 = r0; t0 < r1; t0 += kShadowTile) {
+        const int tn = r1 - t0 < kShadowTile ? (int)(r1 - t0) : kShadowTile;
+        __syncthreads();                                     // the previous tile's products are consumed
+        for (int k = threadIdx.x; k < tn; k += rlsh::kBlock) {
+            const int64_t r = t0 + k;
+            const float vr = a.vis.r[r], vg = a.vis.g[r], vb = a.vis.b[r];
+            prod[0][k] = vr * a.ws[0][r]; prod[1][k] = vg * a.ws[1][r]; prod[2][k] = vb * a.ws[2][r];
+            if (GGX) {
+                const float wd = a.wd[0][r];
+                prod[3][k] = vr * wd; prod[4][k] = vg * wd; prod[5][k] = vb * wd;
+            } else {
+                prod[3][k] = vr * a.wd[0][r]; prod[4][k] = vg * a.wd[1][r]; prod[5][k] = vb * a.wd[2][r];
+            }
+            kinds[k] = a.kind[r];
+        }
+        __syncthreads();
+        const int64_t b = lo > t0 ? lo : t0, e = hi < t0 + tn ? hi : t0 + tn;
+        for (int64_t r = b; r < e; r++) {
+            const int k = (int)(r - t0), kind = kinds[k];
+            const int lk = (kind & RLS_SHADOW_LIGHT_MASK) < a.nl ? (kind & RLS_SHADOW_LIGHT_MASK) : a.nl - 1;
+            while (l < lk) close_light();
+            if (kind & RLS_SHADOW_BSDF) {
+                if (kind & RLS_SHADOW_SPECULAR) { bS[0] += prod[0][k]; bS[1] += prod[1][k]; bS[2] += prod[2][k]; }
+                if (kind & RLS_SHADOW_DIFFUSE) { bD[0] += prod[3][k]; bD[1] += prod[4][k]; bD[2] += prod[5][k]; }
+            } else {
+                if (kind & RLS_SHADOW_SPECULAR) { lS[0] += prod[0][k]; lS[1] += prod[1][k]; lS[2] += prod[2][k]; }
+                if (kind & RLS_SHADOW_DIFFUSE) { lD[0] += prod[3][k]; lD[1] += prod[4][k]; lD[2] += prod[5][k]; }
+            }
+        }
+    }
+    if (live) {
+        while (l < a.nl) close_light();
+    }
+}
+
+// rlGgx's node parameters at point i, as ggx_shade_kernel forms them (src/rlGgx.cpp:279, 308)
+struct GgxTail { float ks, d[3], t[3]; };
+__device__ __forceinline__ GgxTail ggx_tail(const rls_material_index &materials, const rls_ggx_shader &sh, int64_t i, bool kt)
+{
+    GgxTail r = {};
+    const PIndex<int64_t> pk = pindex(materials, i);
+    const float kd = ldp(sh.Kd, pk);
+    r.ks = ldp(sh.Ks, pk);
+    ldrgb(sh.KdColor, pk, r.d[0], r.d[1], r.d[2]);
+    r.d[0] *= kd; r.d[1] *= kd; r.d[2] *= kd;                // diffuseColor, src/rlGgx.cpp:279
+    if (kt) {
+        const float k = ldp(sh.Kt, pk);
+        ldrgb(sh.KtColor, pk, r.t[0], r.t[1], r.t[2]);
+        r.t[0] *= k; r.t[1] *= k; r.t[2] *= k;               // ktColor, :308
+    }
+    return r;
+}
+
 template <int NWD>
 __global__ __launch_bounds__(rlsh::kBlock) void shadow_resolve_kernel(ShadowResolveIO a)
 {
@@ -867,72 +1148,149 @@ __global__ __launch_bounds__(rlsh::kBlock) void shadow_resolve_kernel(ShadowReso
     __shared__ float prod[6][kShadowTile];           // visibility x weight_specular, visibility x weight_diffuse
     __shared__ uint8_t kinds[kShadowTile];
     __shared__ float rad[RLS_MAX_LIGHTS][3];
-    if (threadIdx.x < RLS_MAX_LIGHTS * 3) rad[threadIdx.x / 3][threadIdx.x % 3] = a.rad[threadIdx.x / 3][threadIdx.x % 3];
-    __syncthreads();
+    stage_radiance(rad, a);
     for (int64_t p0 = (int64_t)blockIdx.x * rlsh::kBlock; p0 < a.n; p0 += (int64_t)gridDim.x * rlsh::kBlock) {
         const int64_t i = p0 + threadIdx.x;
-        const bool live = i < a.n;
-        const int64_t pend = a.n - p0 < rlsh::kBlock ? a.n : p0 + rlsh::kBlock;
-        const int64_t r0 = a.offsets[p0], r1 = a.offsets[pend];
-        const int64_t lo = live ? a.offsets[i] : 0, hi = live ? a.offsets[i + 1] : 0;
-        float lS[3] = { 0.0f, 0.0f, 0.0f }, lD[3] = { 0.0f, 0.0f, 0.0f }, bS[3] = { 0.0f, 0.0f, 0.0f }, bD[3] = { 0.0f, 0.0f, 0.0f };
-        float oS[3] = { 0.0f, 0.0f, 0.0f }, oD[3] = { 0.0f, 0.0f, 0.0f };
-        int l = 0;
-        auto close_light = [&]() {
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const float tS = rad[l][c] * (lS[c] + bS[c]) * a.inv, tD = rad[l][c] * (lD[c] + bD[c]) * a.inv;
-                oS[c] = l == 0 ? tS : oS[c] + tS;
-                oD[c] = l == 0 ? tD : oD[c] + tD;
-                lS[c] = 0.0f; lD[c] = 0.0f; bS[c] = 0.0f; bD[c] = 0.0f;
-            }
-            l++;
-        };
-        for (int64_t t0 = r0; t0 < r1; t0 += kShadowTile) {
-            const int tn = r1 - t0 < kShadowTile ? (int)(r1 - t0) : kShadowTile;
-            __syncthreads();                                     // the previous tile's products are consumed
-            for (int k = threadIdx.x; k < tn; k += rlsh::kBlock) {
-                const int64_t r = t0 + k;
-                const float vr = a.vis.r[r], vg = a.vis.g[r], vb = a.vis.b[r];
-                prod[0][k] = vr * a.ws[0][r]; prod[1][k] = vg * a.ws[1][r]; prod[2][k] = vb * a.ws[2][r];
-                if (GGX) {
-                    const float wd = a.wd[0][r];
-                    prod[3][k] = vr * wd; prod[4][k] = vg * wd; prod[5][k] = vb * wd;
-                } else {
-                    prod[3][k] = vr * a.wd[0][r]; prod[4][k] = vg * a.wd[1][r]; prod[5][k] = vb * a.wd[2][r];
-                }
-                kinds[k] = a.kind[r];
-            }
-            __syncthreads();
-            const int64_t b = lo > t0 ? lo : t0, e = hi < t0 + tn ? hi : t0 + tn;
-            for (int64_t r = b; r < e; r++) {
-                const int k = (int)(r - t0), kind = kinds[k];
-                const int lk = (kind & RLS_SHADOW_LIGHT_MASK) < a.nl ? (kind & RLS_SHADOW_LIGHT_MASK) : a.nl - 1;
-                while (l < lk) close_light();
-                if (kind & RLS_SHADOW_BSDF) {
-                    if (kind & RLS_SHADOW_SPECULAR) { bS[0] += prod[0][k]; bS[1] += prod[1][k]; bS[2] += prod[2][k]; }
-                    if (kind & RLS_SHADOW_DIFFUSE) { bD[0] += prod[3][k]; bD[1] += prod[4][k]; bD[2] += prod[5][k]; }
-                } else {
-                    if (kind & RLS_SHADOW_SPECULAR) { lS[0] += prod[0][k]; lS[1] += prod[1][k]; lS[2] += prod[2][k]; }
-                    if (kind & RLS_SHADOW_DIFFUSE) { lD[0] += prod[3][k]; lD[1] += prod[4][k]; lD[2] += prod[5][k]; }
-                }
-            }
-        }
-        if (live) {
-            while (l < a.nl) close_light();
+        float oS[3], oD[3];
+        shadow_sums<NWD>(prod, kinds, rad, a, p0, oS, oD);
+        if (i < a.n) {
             if (GGX) {
-                const PIndex<int64_t> pk = pindex(a.materials, i);
-                const float ks = ldp(a.sh.Ks, pk), kd = ldp(a.sh.Kd, pk);
-                float dr, dg, db;
-                ldrgb(a.sh.KdColor, pk, dr, dg, db);
-                dr *= kd; dg *= kd; db *= kd;                    // diffuseColor, src/rlGgx.cpp:279
-                strgb(a.ds, i, oS[0] * ks, oS[1] * ks, oS[2] * ks);
-                strgb(a.dd, i, oD[0] * dr, oD[1] * dg, oD[2] * db);
+                const GgxTail t = ggx_tail(a.materials, a.sh, i, false);
+                strgb(a.ds, i, oS[0] * t.ks, oS[1] * t.ks, oS[2] * t.ks);
+                strgb(a.dd, i, oD[0] * t.d[0], oD[1] * t.d[1], oD[2] * t.d[2]);
             } else {
                 strgb(a.ds, i, oS[0], oS[1], oS[2]);
                 strgb(a.dd, i, oD[0], oD[1], oD[2]);
             }
         }
+    }
+}
+
+// The node resolves: one launch composes rls_ggx_shade's / rls_disney_shade's AOVs and sg->out.RGB.  A workgroup takes kBlock
+// consecutive points and walks their contiguous ray range of each queue in turn -- the light loop's (shadow_sums), then each
+// indirect loop's (ray_sums_about_reference) -- through ONE LDS store (the light loop's six product planes; a ray queue keeps
+// its radiance and weight planes there), lane i keeping its point's sums in registers; then the composition of
+// ggx_shade_kernel / disney_shade_kernel (csrc/shade.hip) line by line, with the traced sum S where they have
+// (sum x inv) x env.  No per-queue sum goes to memory.  LDS: 25.1 KB a workgroup, as shadow_resolve_kernel: six workgroups
+// (24 waves) a CU; the walks' LDS access patterns are the two existing kernels'.
+__global__ __launch_bounds__(rlsh::kBlock) void ggx_node_resolve_kernel(GgxNodeResolveIO a)
+{
+    __shared__ float prod[6][kShadowTile];
+    __shared__ uint8_t kinds[kShadowTile];
+    __shared__ float rad[RLS_MAX_LIGHTS][3];
+    stage_radiance(rad, a.s);
+    for (int64_t p0 = (int64_t)blockIdx.x * rlsh::kBlock; p0 < a.n; p0 += (int64_t)gridDim.x * rlsh::kBlock) {
+        const int64_t i = p0 + threadIdx.x;
+        float oS[3] = { 0.0f, 0.0f, 0.0f }, oD[3] = { 0.0f, 0.0f, 0.0f }, sG[3], sT[3], sD[3];
+        if (a.s.nl > 0) shadow_sums<1>(prod, kinds, rad, a.s, p0, oS, oD);
+        ray_sums_about_reference<3>(prod, a.glossy, p0, a.n, a.inv, sG);
+        ray_sums_about_reference<1>(prod, a.refract, p0, a.n, a.traced ? a.inv : 1.0f, sT);      // (untraced: no "x inv")
+        ray_sums_about_reference<1>(prod, a.diffuse, p0, a.n, a.inv, sD);
+        if (i < a.n) {
+            const GgxTail t = ggx_tail(a.s.materials, a.s.sh, i, true);
+            float kr, kg, kb;
+            ldrgb(a.KsColor, pindex(a.s.materials, i), kr, kg, kb);
+            float dD[3], dS[3], tx[3] = { 0.0f, 0.0f, 0.0f }, iD[3] = { 0.0f, 0.0f, 0.0f }, iS[3] = { 0.0f, 0.0f, 0.0f };
+#pragma unroll
+            for (int c = 0; c < 3; c++) { dD[c] = oD[c] * t.d[c]; dS[c] = oS[c] * t.ks; }          // :304-305
+            if (!color_is_small(t.t[0], t.t[1], t.t[2])) {                                         // :307-309
+#pragma unroll
+                for (int c = 0; c < 3; c++) tx[c] = sT[c] * t.t[c];
+            }
+            if (!color_is_small(t.d[0], t.d[1], t.d[2])) {                                         // sampleDiffuse, :315-319
+#pragma unroll
+                for (int c = 0; c < 3; c++) iD[c] = t.d[c] * sD[c];
+            }
+            if (!color_is_small(kr, kg, kb)) {                                                     // :321
+#pragma unroll
+                for (int c = 0; c < 3; c++) iS[c] = sG[c] * t.ks;
+            }
+            strgb(a.s.dd, i, dD[0], dD[1], dD[2]);
+            strgb(a.s.ds, i, dS[0], dS[1], dS[2]);
+            strgb(a.refract.out, i, tx[0], tx[1], tx[2]);
+            strgb(a.diffuse.out, i, iD[0], iD[1], iD[2]);
+            strgb(a.glossy.out, i, iS[0], iS[1], iS[2]);
+            // result = diffuse + specular + transmission (:311); result += indirectDiffuse + indirectGlossy (:323)
+            if (a.out.r) strgb(a.out, i, ((dD[0] + dS[0]) + tx[0]) + (iD[0] + iS[0]), ((dD[1] + dS[1]) + tx[1]) + (iD[1] + iS[1]),
+                               ((dD[2] + dS[2]) + tx[2]) + (iD[2] + iS[2]));
+        }
+    }
+}
+
+__global__ __launch_bounds__(rlsh::kBlock) void disney_node_resolve_kernel(DisneyNodeResolveIO a)
+{
+    __shared__ float prod[6][kShadowTile];
+    __shared__ uint8_t kinds[kShadowTile];
+    __shared__ float rad[RLS_MAX_LIGHTS][3];
+    stage_radiance(rad, a.s);
+    for (int64_t p0 = (int64_t)blockIdx.x * rlsh::kBlock; p0 < a.n; p0 += (int64_t)gridDim.x * rlsh::kBlock) {
+        const int64_t i = p0 + threadIdx.x;
+        float dS[3] = { 0.0f, 0.0f, 0.0f }, dD[3] = { 0.0f, 0.0f, 0.0f }, sD[3], sS[3];
+        if (a.s.nl > 0) shadow_sums<3>(prod, kinds, rad, a.s, p0, dS, dD);
+        ray_sums_about_reference<3>(prod, a.diffuse, p0, a.n, a.inv, sD);
+        ray_sums_about_reference<3>(prod, a.specular, p0, a.n, a.inv, sS);
+        if (i < a.n) {
+            const float (&iD)[3] = sD, (&iS)[3] = sS;
+            strgb(a.s.dd, i, dD[0], dD[1], dD[2]);
+            strgb(a.s.ds, i, dS[0], dS[1], dS[2]);
+            strgb(a.diffuse.out, i, iD[0], iD[1], iD[2]);
+            strgb(a.specular.out, i, iS[0], iS[1], iS[2]);
+            // result = diffuse + specular (src/rlDisney.cpp:712); result += indirectDiffuse + indirectGlossy (:722)
+            if (a.out.r) strgb(a.out, i, (dD[0] + dS[0]) + (iD[0] + iS[0]), (dD[1] + dS[1]) + (iD[1] + iS[1]),
+                               (dD[2] + dS[2]) + (iD[2] + iS[2]));
+        }
+    }
+}
+
+// The node resolves as the EXISTING resolve kernels plus a compose pass (RLS_NODE_RESOLVE=separate; for measurement,
+// tools/trace_bench.py): shadow_resolve_kernel leaves the direct AOVs, trace_resolve_kernel one PLAIN sum of radiance x weight
+// per ray queue in that queue's AOV plane (refraction and the Oren-Nayar queue already x inv, the three-plane queues not), and
+// these kernels turn the planes into the AOVs in place and add sg->out.RGB.  Not the default: a plain sum rounds a uniform
+// radiance into every term, so this path does not return the analytic call's bits for env other than 1.
+__global__ __launch_bounds__(rlsh::kBlock) void ggx_node_compose_kernel(GgxNodeResolveIO a)
+{
+    for (int64_t i = (int64_t)blockIdx.x * rlsh::kBlock + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * rlsh::kBlock) {
+        const GgxTail t = ggx_tail(a.s.materials, a.s.sh, i, true);
+        float kr, kg, kb;
+        ldrgb(a.KsColor, pindex(a.s.materials, i), kr, kg, kb);
+        float dD[3], dS[3], tx[3] = { 0.0f, 0.0f, 0.0f }, iD[3] = { 0.0f, 0.0f, 0.0f }, iS[3] = { 0.0f, 0.0f, 0.0f };
+        float *const pd[3] = { a.s.dd.r, a.s.dd.g, a.s.dd.b }, *const ps[3] = { a.s.ds.r, a.s.ds.g, a.s.ds.b };
+        float *const pt[3] = { a.refract.out.r, a.refract.out.g, a.refract.out.b };
+        float *const pi[3] = { a.diffuse.out.r, a.diffuse.out.g, a.diffuse.out.b };
+        float *const pg[3] = { a.glossy.out.r, a.glossy.out.g, a.glossy.out.b };
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            dD[c] = a.s.nl > 0 ? pd[c][i] : 0.0f * t.d[c];
+            dS[c] = a.s.nl > 0 ? ps[c][i] : 0.0f * t.ks;
+        }
+        if (!color_is_small(t.t[0], t.t[1], t.t[2]))
+            for (int c = 0; c < 3; c++) tx[c] = pt[c][i] * t.t[c];
+        if (!color_is_small(t.d[0], t.d[1], t.d[2]))
+            for (int c = 0; c < 3; c++) iD[c] = t.d[c] * pi[c][i];
+        if (!color_is_small(kr, kg, kb))
+            for (int c = 0; c < 3; c++) iS[c] = pg[c][i] * a.inv * t.ks;
+#pragma unroll
+        for (int c = 0; c < 3; c++) { pd[c][i] = dD[c]; ps[c][i] = dS[c]; pt[c][i] = tx[c]; pi[c][i] = iD[c]; pg[c][i] = iS[c]; }
+        if (a.out.r) strgb(a.out, i, ((dD[0] + dS[0]) + tx[0]) + (iD[0] + iS[0]), ((dD[1] + dS[1]) + tx[1]) + (iD[1] + iS[1]),
+                           ((dD[2] + dS[2]) + tx[2]) + (iD[2] + iS[2]));
+    }
+}
+
+__global__ __launch_bounds__(rlsh::kBlock) void disney_node_compose_kernel(DisneyNodeResolveIO a)
+{
+    for (int64_t i = (int64_t)blockIdx.x * rlsh::kBlock + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * rlsh::kBlock) {
+        float *const pd[3] = { a.s.dd.r, a.s.dd.g, a.s.dd.b }, *const ps[3] = { a.s.ds.r, a.s.ds.g, a.s.ds.b };
+        float *const pi[3] = { a.diffuse.out.r, a.diffuse.out.g, a.diffuse.out.b };
+        float *const pg[3] = { a.specular.out.r, a.specular.out.g, a.specular.out.b };
+        float o[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float dD = a.s.nl > 0 ? pd[c][i] : 0.0f, dS = a.s.nl > 0 ? ps[c][i] : 0.0f;
+            const float iD = pi[c][i] * a.inv, iS = pg[c][i] * a.inv;
+            pd[c][i] = dD; ps[c][i] = dS; pi[c][i] = iD; pg[c][i] = iS;
+            o[c] = (dD + dS) + (iD + iS);
+        }
+        if (a.out.r) strgb(a.out, i, o[0], o[1], o[2]);
     }
 }
 #endif
@@ -963,6 +1321,26 @@ rls_status launch_disney_specular_emit(rls_context *ctx, int g, const EmitIO<rls
 {
     return launch_g(ctx, RLS_G_FAMILY(disney_specular_emit_kernel), g, io, name);
 }
+rls_status launch_ggx_node_glossy_emit(rls_context *ctx, int g, const GgxNodeEmitIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(ggx_node_glossy_emit_kernel), g, io, name);
+}
+rls_status launch_ggx_node_refract_emit(rls_context *ctx, int g, const GgxNodeEmitIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(ggx_node_refract_emit_kernel), g, io, name);
+}
+rls_status launch_ggx_node_diffuse_emit(rls_context *ctx, int g, const GgxNodeEmitIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(ggx_node_diffuse_emit_kernel), g, io, name);
+}
+rls_status launch_disney_node_diffuse_emit(rls_context *ctx, int g, const EmitIO<rls_disney_closure> &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(disney_node_diffuse_emit_kernel), g, io, name);
+}
+rls_status launch_disney_node_specular_emit(rls_context *ctx, int g, const EmitIO<rls_disney_closure> &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(disney_node_specular_emit_kernel), g, io, name);
+}
 rls_status launch_ggx_direct_emit(rls_context *ctx, int g, const ShadowEmitIO<rls_ggx_closure, rls_ggx_shader> &io,
                                   const char *name)
 {
@@ -988,6 +1366,11 @@ RLS_FLAVOURS(ggx_glossy_emit, EmitIO<rls_ggx_closure>)
 RLS_FLAVOURS(ggx_refract_emit, EmitIO<rls_ggx_closure>)
 RLS_FLAVOURS(disney_diffuse_emit, EmitIO<rls_disney_closure>)
 RLS_FLAVOURS(disney_specular_emit, EmitIO<rls_disney_closure>)
+RLS_FLAVOURS(ggx_node_glossy_emit, GgxNodeEmitIO)
+RLS_FLAVOURS(ggx_node_refract_emit, GgxNodeEmitIO)
+RLS_FLAVOURS(ggx_node_diffuse_emit, GgxNodeEmitIO)
+RLS_FLAVOURS(disney_node_diffuse_emit, EmitIO<rls_disney_closure>)
+RLS_FLAVOURS(disney_node_specular_emit, EmitIO<rls_disney_closure>)
 using GgxShadowEmitIO = ShadowEmitIO<rls_ggx_closure, rls_ggx_shader>;
 using DisneyShadowEmitIO = ShadowEmitIO<rls_disney_closure, NoShader>;
 RLS_FLAVOURS(ggx_direct_emit, GgxShadowEmitIO)
@@ -1070,6 +1453,42 @@ rls_status emit_and_scan(rls_context *ctx, IO &io, int64_t n, int spp_n, uint32_
 // points per compaction tile: as many as tile_slots slots hold, a point's index in its tile being 8 bits
 inline int compact_tile_points(int tile_slots, int per_point) { return std::min(tile_slots / per_point, kCompactMaxPoints); }
 
+// the planes a ray emit needs of its queue (nw: the weight's planes), for n points at spp_n^2 samples; fn: the name the
+// messages carry
+rls_status check_ray_queue(const char *fn, const rls_ray_queue *q, int nw, int64_t n, int spp_n)
+{
+    RLS_REQUIRE_IN(fn, rlsh::has3(q->dir), "queue.dir plane is NULL");
+    RLS_REQUIRE_IN(fn, nw == 1 ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
+    RLS_REQUIRE_IN(fn, q->capacity >= n * spp_n * spp_n, "queue.capacity < n * spp_n^2");
+    RLS_REQUIRE_IN(fn, q->scratch != nullptr && q->scratch_bytes >= staging(nullptr, n, spp_n * spp_n, kRayPlanes, sizeof(uint16_t)).bytes,
+                   "queue.scratch is NULL or smaller than rls_trace_scratch_bytes");
+    return RLS_OK;
+}
+
+// A checked ray emit of n > 0 points at `spp` samples a point (a node's untraced refraction: 1): the staging in the queue's
+// scratch, the closure's emit kernel (io: its closure part filled), the scan, the compaction.
+template <class IO>
+rls_status run_ray_emit(rls_context *ctx, int64_t n, IO &io, int spp, uint32_t seed, uint64_t first_index, const rls_ray_queue *q,
+                        float *side, int nw, const char *name, rls_status (*dispatch)(rls_context *, int, const IO &, const char *))
+{
+    const Staging st = staging(q->scratch, n, spp, kRayPlanes, sizeof(uint16_t));
+    for (int k = 0; k < 3; k++) { io.dir[k] = st.f[k]; io.w[k] = st.f[3 + k]; }
+    io.tag = (uint16_t *)st.tag; io.side = side;
+    io.count = q->offsets;
+    io.n = n; io.spp = spp; io.seed = seed; io.first = first_index;
+    if (rls_status s = dispatch(ctx, pick_group(ctx, n, spp), io, name)) return s;
+    if (rls_status s = scan_counts(ctx, q->offsets, n, st.totals, st.tiles)) return s;
+
+    TraceCompactIO cio = {};
+    for (int k = 0; k < 3; k++) { cio.sdir[k] = st.f[k]; cio.sw[k] = st.f[3 + k]; }
+    cio.tag = io.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp;
+    cio.tile_points = compact_tile_points(kCompactSlots, spp);
+    const dim3 cgrid = rlsh::grid_for(ctx, n, cio.tile_points);
+    if (nw == 1) hipLaunchKernelGGL(trace_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    else hipLaunchKernelGGL(trace_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    return rlsh::check_launch("trace_compact_kernel");
+}
+
 // Every emit: the argument checks (lobe_ok: the rlDisney lobe, checked after spp_n), the empty queue of n == 0, the staging
 // in the caller's scratch, then the closure's emit kernel (dispatch, with G for the batch) and the steps the closures share:
 // the per-point counts scanned in place into offsets, the kept records compacted into the queue (nw weight planes).  side:
@@ -1082,29 +1501,12 @@ rls_status emit(rls_context *ctx, int64_t n, const Closure *c, int spp_n, uint32
     if (rls_status s = check_batch(__func__, ctx, n, spp_n)) return s;
     RLS_REQUIRE(lobe_ok, "lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY");
     RLS_REQUIRE(q != nullptr && q->offsets != nullptr, "queue or queue.offsets is NULL");
-    const int spp = spp_n * spp_n;
     if (n == 0) return empty_queue(ctx, q->offsets, name);
     if (rls_status s = rlsh::check_closure(__func__, c)) return s;
-    RLS_REQUIRE(rlsh::has3(q->dir), "queue.dir plane is NULL");
-    RLS_REQUIRE(nw == 1 ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
-    RLS_REQUIRE(q->capacity >= n * spp, "queue.capacity < n * spp_n^2");
-    const Staging st = staging(q->scratch, n, spp, kRayPlanes, sizeof(uint16_t));
-    RLS_REQUIRE(q->scratch != nullptr && q->scratch_bytes >= st.bytes, "queue.scratch is NULL or smaller than rls_trace_scratch_bytes");
-
+    if (rls_status s = check_ray_queue(__func__, q, nw, n, spp_n)) return s;
     EmitIO<Closure> io = {};
     io.c = *c;
-    for (int k = 0; k < 3; k++) { io.dir[k] = st.f[k]; io.w[k] = st.f[3 + k]; }
-    io.tag = (uint16_t *)st.tag; io.side = side;
-    if (rls_status s = emit_and_scan(ctx, io, n, spp_n, seed, first_index, q->offsets, st, name, dispatch)) return s;
-
-    TraceCompactIO cio = {};
-    for (int k = 0; k < 3; k++) { cio.sdir[k] = st.f[k]; cio.sw[k] = st.f[3 + k]; }
-    cio.tag = io.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp;
-    cio.tile_points = compact_tile_points(kCompactSlots, spp);
-    const dim3 cgrid = rlsh::grid_for(ctx, n, cio.tile_points);
-    if (nw == 1) hipLaunchKernelGGL(trace_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
-    else hipLaunchKernelGGL(trace_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
-    return rlsh::check_launch("trace_compact_kernel");
+    return run_ray_emit(ctx, n, io, spp_n * spp_n, seed, first_index, q, side, nw, name, dispatch);
 }
 
 rls_status resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, int spp_n, rls_crgb radiance, rls_rgb out, bool refract)
@@ -1171,6 +1573,25 @@ rls_status shadow_emit(rls_context *ctx, int64_t n, ClosureCheck closure, const 
     return rlsh::check_launch("shadow_compact_kernel");
 }
 
+// The light loop's part of a resolve's argument struct (the light-loop resolves and the node resolves): the lights, the queue's
+// planes, the visibility, 1 / spp.  n_lights >= 1.
+rls_status shadow_resolve_io(const char *name, ShadowResolveIO &io, int64_t n, bool ggx, const rls_sphere_light *lights,
+                             int n_lights, int spp_n, const rls_shadow_queue *q, rls_crgb visibility)
+{
+    rls_sphere_light lt[RLS_MAX_LIGHTS];
+    if (rls_status s = copy_lights(lights, n_lights, 1, lt, &io.nl)) return s;
+    if (rls_status s = check_shadow_queue(name, q, ggx, n, io.nl, spp_n * spp_n)) return s;
+    RLS_REQUIRE_IN(name, visibility.r && visibility.g && visibility.b, "visibility plane is NULL");
+    for (int l = 0; l < io.nl; l++)
+        for (int k = 0; k < 3; k++) io.rad[l][k] = lt[l].radiance[k];
+    io.offsets = q->offsets; io.kind = q->kind; io.vis = visibility;
+    io.ws[0] = q->weight_specular.r; io.ws[1] = q->weight_specular.g; io.ws[2] = q->weight_specular.b;
+    io.wd[0] = q->weight_diffuse.r; io.wd[1] = q->weight_diffuse.g; io.wd[2] = q->weight_diffuse.b;
+    io.inv = 1.0f / (float)(spp_n * spp_n);                      // as the loop kernels: 1 / spp
+    io.n = n;
+    return RLS_OK;
+}
+
 // Both light-loop resolves; c, sh: rlGgx's tail (NULL for rlDisney)
 rls_status shadow_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh, bool ggx,
                           const rls_sphere_light *lights, int n_lights, int spp_n, const rls_shadow_queue *q, rls_crgb visibility,
@@ -1186,21 +1607,56 @@ rls_status shadow_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c,
         RLS_REQUIRE_IN(name, rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
         io.materials = c->materials; io.sh = *sh;
     }
-    rls_sphere_light lt[RLS_MAX_LIGHTS];
-    if (rls_status s = copy_lights(lights, n_lights, 1, lt, &io.nl)) return s;
-    if (rls_status s = check_shadow_queue(name, q, ggx, n, io.nl, spp_n * spp_n)) return s;
-    RLS_REQUIRE_IN(name, visibility.r && visibility.g && visibility.b, "visibility plane is NULL");
+    if (rls_status s = shadow_resolve_io(name, io, n, ggx, lights, n_lights, spp_n, q, visibility)) return s;
     RLS_REQUIRE_IN(name, rlsh::has3(direct_diffuse) && rlsh::has3(direct_specular), "NULL output plane");
-    for (int l = 0; l < io.nl; l++)
-        for (int k = 0; k < 3; k++) io.rad[l][k] = lt[l].radiance[k];
-    io.offsets = q->offsets; io.kind = q->kind; io.vis = visibility; io.dd = direct_diffuse; io.ds = direct_specular;
-    io.ws[0] = q->weight_specular.r; io.ws[1] = q->weight_specular.g; io.ws[2] = q->weight_specular.b;
-    io.wd[0] = q->weight_diffuse.r; io.wd[1] = q->weight_diffuse.g; io.wd[2] = q->weight_diffuse.b;
-    io.inv = 1.0f / (float)(spp_n * spp_n);                      // as the loop kernels: 1 / spp
-    io.n = n;
+    io.dd = direct_diffuse; io.ds = direct_specular;
     const dim3 grid = rlsh::grid_for(ctx, n);
     if (ggx) hipLaunchKernelGGL(shadow_resolve_kernel<1>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
     else hipLaunchKernelGGL(shadow_resolve_kernel<3>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(name);
+}
+
+// What the node verbs check first: the batch, the queue struct, the light count, and the shadow queue present exactly where
+// there are lights
+rls_status check_node(const char *fn, const rls_context *ctx, int64_t n, int spp_n, int n_lights, bool have_queues,
+                      const rls_shadow_queue *const *shadow)
+{
+    if (rls_status s = check_batch(fn, ctx, n, spp_n)) return s;
+    RLS_REQUIRE_IN(fn, have_queues, "queues is NULL");
+    RLS_REQUIRE_IN(fn, n_lights >= 0 && n_lights <= RLS_MAX_LIGHTS, "n_lights out of range (RLS_MAX_LIGHTS)");
+    RLS_REQUIRE_IN(fn, n_lights > 0 || *shadow == nullptr, "queues.shadow is set but n_lights is 0");
+    RLS_REQUIRE_IN(fn, n_lights == 0 || *shadow != nullptr, "queues.shadow is NULL but n_lights > 0");
+    return RLS_OK;
+}
+
+// one ray queue of a node resolve: its planes, the radiance traced for it, the AOV it feeds
+rls_status node_ray_io(const char *fn, TraceResolveIO &io, const rls_ray_queue *q, int nw, int64_t n, int spp_n, rls_crgb radiance,
+                       rls_rgb aov)
+{
+    RLS_REQUIRE_IN(fn, q->offsets != nullptr, "queue.offsets is NULL");
+    RLS_REQUIRE_IN(fn, nw == 1 ? q->weight.r != nullptr : rlsh::has3(q->weight), "queue.weight plane is NULL");
+    RLS_REQUIRE_IN(fn, q->capacity >= n * spp_n * spp_n, "queue.capacity < n * spp_n^2");
+    RLS_REQUIRE_IN(fn, radiance.r && radiance.g && radiance.b, "radiance plane is NULL");
+    io.offsets = q->offsets;
+    io.w[0] = q->weight.r; io.w[1] = q->weight.g; io.w[2] = q->weight.b;
+    io.L = radiance; io.out = aov; io.scale = 1.0f; io.n = n;
+    return RLS_OK;
+}
+
+// RLS_NODE_RESOLVE=separate: the node resolves through the existing resolve kernels and a compose pass (see
+// ggx_node_compose_kernel)
+bool separate_node_resolve()
+{
+    const char *e = getenv("RLS_NODE_RESOLVE");
+    return e != nullptr && strcmp(e, "separate") == 0;
+}
+// one existing ray resolve of that path: the queue's plain sum (x scale for a one-plane queue) into its AOV plane
+rls_status launch_ray_resolve(rls_context *ctx, TraceResolveIO io, int nw, float scale, const char *name)
+{
+    io.scale = scale;
+    const dim3 grid = rlsh::grid_for(ctx, io.n);
+    if (nw == 1) hipLaunchKernelGGL(trace_resolve_kernel<1>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
+    else hipLaunchKernelGGL(trace_resolve_kernel<3>, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
     return rlsh::check_launch(name);
 }
 
@@ -1343,6 +1799,157 @@ rls_status rls_trace_disney_direct_resolve(rls_context *ctx, int64_t n, const rl
 {
     return shadow_resolve(ctx, n, nullptr, nullptr, false, lights, n_lights, spp_n, q, visibility, direct_diffuse,
                           direct_specular, __func__);
+}
+
+rls_status rls_trace_ggx_shade_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                    rls_cvec3 P, const rls_sphere_light *lights, int n_lights, int traced, int spp_n,
+                                    uint32_t seed, uint64_t first_index, const rls_ggx_node_queues *q)
+{
+    const char *fn = __func__;
+    if (rls_status s = check_node(fn, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    RLS_REQUIRE(q->glossy != nullptr && q->refract != nullptr && q->diffuse != nullptr,
+                "queues.glossy, queues.refract or queues.diffuse is NULL");
+    const rls_ray_queue *const rq[3] = { q->glossy, q->refract, q->diffuse };
+    const int nw[3] = { 3, 1, 1 };
+    for (int k = 0; k < 3; k++) RLS_REQUIRE(rq[k]->offsets != nullptr, "queue.offsets is NULL");
+    if (n > 0) {
+        RLS_REQUIRE(c != nullptr && sh != nullptr, "closure or shader is NULL");
+        if (rls_status s = rlsh::check_closure(fn, c, &P, sh, true)) return s;
+        for (int k = 0; k < 3; k++)
+            if (rls_status s = check_ray_queue(fn, rq[k], nw[k], n, spp_n)) return s;
+    }
+    if (n_lights > 0) {                                          // the light loop: rls_trace_ggx_direct_emit's queue
+        auto closure = [&](GgxShadowEmitIO &io) -> rls_status {
+            io.c = *c; io.sh = *sh; io.P = P;
+            return RLS_OK;
+        };
+        if (rls_status s = shadow_emit<GgxShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, q->shadow,
+                                                        true, fn, dispatch_ggx_direct_emit)) return s;
+    }
+    if (n == 0) {
+        for (int k = 0; k < 3; k++)
+            if (rls_status s = empty_queue(ctx, rq[k]->offsets, fn)) return s;
+        return RLS_OK;
+    }
+    GgxNodeEmitIO io = {};
+    io.c = *c; io.sh = *sh; io.traced = traced ? 1 : 0;
+    const int spp = spp_n * spp_n;
+    if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, q->glossy, nullptr, 3, fn, dispatch_ggx_node_glossy_emit))
+        return s;
+    // the untraced branch is one ray a point: one sample (GgxNodeRefract)
+    if (rls_status s = run_ray_emit(ctx, n, io, traced ? spp : 1, seed, first_index, q->refract, nullptr, 1, fn,
+                                    dispatch_ggx_node_refract_emit)) return s;
+    return run_ray_emit(ctx, n, io, spp, seed, first_index, q->diffuse, nullptr, 1, fn, dispatch_ggx_node_diffuse_emit);
+}
+
+rls_status rls_trace_ggx_shade_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                       const rls_sphere_light *lights, int n_lights, int traced, int spp_n,
+                                       const rls_ggx_node_queues *q, const rls_ggx_node_traced *t,
+                                       const rls_ggx_shade_out *out)
+{
+    const char *fn = __func__;
+    if (rls_status s = check_node(fn, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    RLS_REQUIRE(q->glossy != nullptr && q->refract != nullptr && q->diffuse != nullptr,
+                "queues.glossy, queues.refract or queues.diffuse is NULL");
+    RLS_REQUIRE(t != nullptr && out != nullptr, "traced or out is NULL");
+    if (n == 0) return RLS_OK;
+    RLS_REQUIRE(c != nullptr && sh != nullptr, "closure or shader is NULL");
+    RLS_REQUIRE(rlsh::ok_rgb(c->KsColor) && rlsh::ok_rgb(sh->KdColor) && rlsh::ok_rgb(sh->KtColor),
+                "colour planes must be all set or all NULL");
+    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    RLS_REQUIRE(rlsh::has3(out->direct_diffuse) && rlsh::has3(out->direct_specular) && rlsh::has3(out->refraction) &&
+                rlsh::has3(out->indirect_diffuse) && rlsh::has3(out->indirect_specular), "NULL AOV plane");
+    RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
+    GgxNodeResolveIO io = {};
+    if (n_lights > 0)
+        if (rls_status s = shadow_resolve_io(fn, io.s, n, true, lights, n_lights, spp_n, q->shadow, t->visibility)) return s;
+    io.s.materials = c->materials; io.s.sh = *sh; io.s.n = n;
+    io.s.dd = out->direct_diffuse; io.s.ds = out->direct_specular;
+    if (rls_status s = node_ray_io(fn, io.glossy, q->glossy, 3, n, spp_n, t->glossy, out->indirect_specular)) return s;
+    if (rls_status s = node_ray_io(fn, io.refract, q->refract, 1, n, spp_n, t->refract, out->refraction)) return s;
+    if (rls_status s = node_ray_io(fn, io.diffuse, q->diffuse, 1, n, spp_n, t->diffuse, out->indirect_diffuse)) return s;
+    io.KsColor = c->KsColor; io.out = out->out; io.traced = traced ? 1 : 0; io.n = n;
+    io.inv = 1.0f / (float)(spp_n * spp_n);                      // as the loop kernels: 1 / spp
+    if (separate_node_resolve()) {
+        if (io.s.nl > 0) {
+            hipLaunchKernelGGL(shadow_resolve_kernel<1>, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, io.s);
+            if (rls_status s = rlsh::check_launch(fn)) return s;
+        }
+        if (rls_status s = launch_ray_resolve(ctx, io.glossy, 3, 1.0f, fn)) return s;
+        if (rls_status s = launch_ray_resolve(ctx, io.refract, 1, traced ? io.inv : 1.0f, fn)) return s;
+        if (rls_status s = launch_ray_resolve(ctx, io.diffuse, 1, io.inv, fn)) return s;
+        hipLaunchKernelGGL(ggx_node_compose_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+        return rlsh::check_launch(fn);
+    }
+    hipLaunchKernelGGL(ggx_node_resolve_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(fn);
+}
+
+rls_status rls_trace_disney_shade_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
+                                       const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                       uint64_t first_index, const rls_disney_node_queues *q)
+{
+    const char *fn = __func__;
+    if (rls_status s = check_node(fn, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    RLS_REQUIRE(q->diffuse != nullptr && q->specular != nullptr, "queues.diffuse or queues.specular is NULL");
+    RLS_REQUIRE(q->diffuse->offsets != nullptr && q->specular->offsets != nullptr, "queue.offsets is NULL");
+    if (n > 0) {
+        if (rls_status s = rlsh::check_closure(fn, c, &P)) return s;
+        if (rls_status s = check_ray_queue(fn, q->diffuse, 3, n, spp_n)) return s;
+        if (rls_status s = check_ray_queue(fn, q->specular, 3, n, spp_n)) return s;
+    }
+    if (n_lights > 0) {                                          // the light loop: rls_trace_disney_direct_emit's queue
+        auto closure = [&](DisneyShadowEmitIO &io) -> rls_status {
+            io.c = *c; io.P = P;
+            return RLS_OK;
+        };
+        if (rls_status s = shadow_emit<DisneyShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, q->shadow,
+                                                           false, fn, dispatch_disney_direct_emit)) return s;
+    }
+    if (n == 0) {
+        if (rls_status s = empty_queue(ctx, q->diffuse->offsets, fn)) return s;
+        return empty_queue(ctx, q->specular->offsets, fn);
+    }
+    EmitIO<rls_disney_closure> io = {};
+    io.c = *c;
+    const int spp = spp_n * spp_n;
+    if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, q->diffuse, nullptr, 3, fn, dispatch_disney_node_diffuse_emit))
+        return s;
+    return run_ray_emit(ctx, n, io, spp, seed, first_index, q->specular, nullptr, 3, fn, dispatch_disney_node_specular_emit);
+}
+
+rls_status rls_trace_disney_shade_resolve(rls_context *ctx, int64_t n, const rls_sphere_light *lights, int n_lights,
+                                          int spp_n, const rls_disney_node_queues *q, const rls_disney_node_traced *t,
+                                          const rls_disney_shade_out *out)
+{
+    const char *fn = __func__;
+    if (rls_status s = check_node(fn, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    RLS_REQUIRE(q->diffuse != nullptr && q->specular != nullptr, "queues.diffuse or queues.specular is NULL");
+    RLS_REQUIRE(t != nullptr && out != nullptr, "traced or out is NULL");
+    if (n == 0) return RLS_OK;
+    RLS_REQUIRE(rlsh::has3(out->direct_diffuse) && rlsh::has3(out->direct_specular) && rlsh::has3(out->indirect_diffuse) &&
+                rlsh::has3(out->indirect_specular), "NULL AOV plane");
+    RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
+    DisneyNodeResolveIO io = {};
+    if (n_lights > 0)
+        if (rls_status s = shadow_resolve_io(fn, io.s, n, false, lights, n_lights, spp_n, q->shadow, t->visibility)) return s;
+    io.s.n = n; io.s.dd = out->direct_diffuse; io.s.ds = out->direct_specular;
+    if (rls_status s = node_ray_io(fn, io.diffuse, q->diffuse, 3, n, spp_n, t->diffuse, out->indirect_diffuse)) return s;
+    if (rls_status s = node_ray_io(fn, io.specular, q->specular, 3, n, spp_n, t->specular, out->indirect_specular)) return s;
+    io.out = out->out; io.n = n;
+    io.inv = 1.0f / (float)(spp_n * spp_n);
+    if (separate_node_resolve()) {
+        if (io.s.nl > 0) {
+            hipLaunchKernelGGL(shadow_resolve_kernel<3>, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, io.s);
+            if (rls_status s = rlsh::check_launch(fn)) return s;
+        }
+        if (rls_status s = launch_ray_resolve(ctx, io.diffuse, 3, 1.0f, fn)) return s;
+        if (rls_status s = launch_ray_resolve(ctx, io.specular, 3, 1.0f, fn)) return s;
+        hipLaunchKernelGGL(disney_node_compose_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+        return rlsh::check_launch(fn);
+    }
+    hipLaunchKernelGGL(disney_node_resolve_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(fn);
 }
 
 } // extern "C"

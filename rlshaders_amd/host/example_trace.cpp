@@ -1,11 +1,13 @@
 // example_trace.cpp -- the caller-traced rlGgx, rlDisney and rlSss integrators from C++ (rls_trace.hpp): emit
 // integrateGlossy's and integrateRefract's sample rays and those of rlDisney's two lobes, "trace" them against an analytic
 // sky on the host, resolve; emit rlSss's probe rays, walk them through each point's tangent plane on the host, resolve;
-// emit the shadow rays of both nodes' light loops under two lights, shadow the second light with a half-space, resolve.
+// emit the shadow rays of both nodes' light loops under two lights, shadow the second light with a half-space, resolve;
+// emit every queue of the two whole nodes, shadow the second light with the same half-space and light the ray queues with the
+// sky, resolve the AOVs in one call.
 //
 //   example_trace [points] [spp_n]
 // prints one JSON line: the ray counts and a checksum (FNV-1a over the bits of the resolved planes) per integrator, which
-// tests/test_gpu_trace_host_cpp.py (the light loops: tests/test_gpu_trace_lights_host_cpp.py) compares with the Python path (rlshaders_amd/trace.py) on the same inputs.
+// tests/test_gpu_trace_host_cpp.py (the light loops: tests/test_gpu_trace_lights_host_cpp.py; the whole nodes: tests/test_gpu_trace_shade_host_cpp.py) compares with the Python path (rlshaders_amd/trace.py) on the same inputs.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -196,6 +198,80 @@ int main(int argc, char **argv)
                             "\"direct_specular\": \"%016llx\", \"mean_diffuse\": %.9g, \"mean_specular\": %.9g}",
                             lnames[j], (long long)count, (long long)blocked, (unsigned long long)fnv(rd),
                             (unsigned long long)fnv(rs), md_ / (double)rd.size(), ms_ / (double)rs.size());
+            }
+        }
+        {
+            // The whole nodes on the same frame, every shading point at the origin, the two lights and the wall x > 3 of the
+            // light loops above: the shadow queue is traced against the wall, every ray queue sees the sky.  rlGgx with
+            // transmission (KtColor * Kt), its refraction traced.
+            rls_sphere_light lights[2] = {};
+            const float centers[2][3] = {{-4.0f, 2.0f, 3.0f}, {6.0f, 1.0f, 2.0f}};
+            const float radiances[2][3] = {{3.0f, 2.0f, 1.0f}, {1.0f, 4.0f, 2.0f}};
+            for (int l = 0; l < 2; l++) {
+                for (int k = 0; k < 3; k++) { lights[l].center[k] = centers[l][k]; lights[l].radiance[k] = radiances[l][k]; }
+                lights[l].radius = 1.0f;
+                lights[l].mis_mode = RLS_MIS_BOTH;
+            }
+            rls_ggx_shader sh = {};
+            sh.KdColor = rlsb::ParamRGB(0.7f, 0.5f, 0.2f).c();
+            sh.Kd = rls_param{nullptr, 0.8f};
+            sh.diffuseRoughness = rls_param{nullptr, 0.3f};
+            sh.Ks = rls_param{nullptr, 0.6f};
+            sh.KtColor = rlsb::ParamRGB(0.2f, 0.9f, 0.7f).c();
+            sh.Kt = rls_param{nullptr, 0.5f};
+            rlsb::Planes P(dev, std::vector<float>((size_t)(3 * n), 0.0f), 3);
+            // the shadow tracer of the light loops' section; -> the visibility planes, the rays and the blocked rays
+            auto shadowed = [&](const rlsb::ShadowQueue &sq, int64_t &count, int64_t &blocked) {
+                count = sq.count();
+                const int64_t scap = sq.c().capacity;
+                std::vector<float> dx((size_t)count), md((size_t)count), vis((size_t)(3 * scap), 0.0f);
+                rlsb::check(rls_copy_to_host(dev.ctx(), dx.data(), sq.c().dir.x, sizeof(float) * dx.size()));
+                rlsb::check(rls_copy_to_host(dev.ctx(), md.data(), sq.c().maxdist, sizeof(float) * md.size()));
+                blocked = 0;
+                for (int64_t k = 0; k < count; k++) {
+                    const bool hit = md[(size_t)k] * dx[(size_t)k] > 3.0f;
+                    blocked += hit ? 1 : 0;
+                    for (int ch = 0; ch < 3; ch++) vis[(size_t)(ch * scap + k)] = hit ? 0.0f : 1.0f;
+                }
+                return rlsb::Planes(dev, vis, 3);
+            };
+            // the sky along a ray queue's rays; -> the radiance planes and the rays
+            auto lit = [&](const rlsb::RayQueue &q, int64_t &count) {
+                count = q.count();
+                std::vector<float> dz((size_t)count), L((size_t)(3 * cap), 0.0f);
+                rlsb::check(rls_copy_to_host(dev.ctx(), dz.data(), q.c().dir.z, sizeof(float) * dz.size()));
+                sky(dz, cap, L);
+                return rlsb::Planes(dev, L, 3);
+            };
+            auto report = [&](const char *name, const int64_t *rays, int nq, int64_t blocked, const rlsb::Planes &aovs,
+                              const rlsb::Planes &out) {
+                std::vector<float> ra = aovs.download(), ro = out.download();
+                double mean = 0.0;
+                for (float v : ro) mean += v;
+                std::printf(", \"%s\": {\"rays\": [", name);
+                for (int k = 0; k < nq; k++) std::printf("%s%lld", k ? ", " : "", (long long)rays[k]);
+                std::printf("], \"blocked\": %lld, \"aovs\": \"%016llx\", \"out\": \"%016llx\", \"mean_out\": %.9g}",
+                            (long long)blocked, (unsigned long long)fnv(ra), (unsigned long long)fnv(ro), mean / (double)ro.size());
+            };
+            {
+                rlsb::GgxNodeQueues nq(dev, n, 2, spp_n);
+                rlsb::emitNode(dev, c, sh, P, lights, 2, true, n, spp_n, kSeed, nq);
+                int64_t rays[4], blocked = 0;
+                rlsb::Planes vis = shadowed(*nq.shadow(), rays[0], blocked);
+                rlsb::Planes Lg = lit(nq.glossy(), rays[1]), Lt = lit(nq.refract(), rays[2]), Ld = lit(nq.diffuse(), rays[3]);
+                rlsb::Planes aovs(dev, n, 15), out(dev, n, 3);
+                rlsb::resolveNode(dev, c, sh, lights, 2, true, nq, vis, Lg, Lt, Ld, aovs, &out);
+                report("ggx_node", rays, 4, blocked, aovs, out);
+            }
+            {
+                rlsb::DisneyNodeQueues nq(dev, n, 2, spp_n);
+                rlsb::emitNode(dev, dc, P, lights, 2, n, spp_n, kSeed, nq);
+                int64_t rays[3], blocked = 0;
+                rlsb::Planes vis = shadowed(*nq.shadow(), rays[0], blocked);
+                rlsb::Planes Ld = lit(nq.diffuse(), rays[1]), Ls = lit(nq.specular(), rays[2]);
+                rlsb::Planes aovs(dev, n, 12), out(dev, n, 3);
+                rlsb::resolveNode(dev, lights, 2, nq, vis, Ld, Ls, aovs, &out);
+                report("disney_node", rays, 3, blocked, aovs, out);
             }
         }
         std::printf(", \"points\": %lld, \"spp_n\": %d}\n", (long long)n, spp_n);

@@ -20,6 +20,11 @@
 //     rlsb::emitDirect(dev, ggx, shader, P, lights, n_lights, n, spp_n, seed, sq);   // one shadow ray per term-carrying sample
 //     ... trace ray k from P[point[k]] along dir[k] up to maxdist[k], one visibility per ray and channel (3 planes) ...
 //     rlsb::resolveDirect(dev, ggx, shader, lights, n_lights, sq, visibility, directDiffuse, directSpecular);
+// Whole nodes (shader_evaluate of rlGgx / rlDisney, every loop at once):
+//     rlsb::GgxNodeQueues nq(dev, n, n_lights, spp_n);                     // shadow (with lights), glossy, refract, diffuse
+//     rlsb::emitNode(dev, ggx, shader, P, lights, n_lights, traced, n, spp_n, seed, nq);
+//     ... trace every queue: a visibility per shadow ray, a radiance per ray of the ray queues ...
+//     rlsb::resolveNode(dev, ggx, shader, lights, n_lights, traced, nq, visibility, Lglossy, Lrefract, Ldiffuse, aovs, &out);
 // Nothing here synchronises the host except RayQueue::count() and ShadowQueue::count() (they read offsets[n]).
 #pragma once
 
@@ -33,7 +38,8 @@ namespace rlsb {
 // The device buffers of one emit: per-ray planes for n * spp_n^2 rays, offsets [n + 1] and the emit's scratch.
 class RayQueue {
 public:
-    enum Kind { Glossy, Refract, DisneyDiffuse, DisneyGlossy };
+    // NodeDiffuse: the rlGgx node's Oren-Nayar queue -- one weight plane like Refract, no kind plane
+    enum Kind { Glossy, Refract, DisneyDiffuse, DisneyGlossy, NodeDiffuse };
 
     RayQueue(const Device &d, int64_t n, int spp_n, Kind kind) : dev_(&d), n_(n), spp_n_(spp_n), kind_(kind)
     {
@@ -70,7 +76,7 @@ private:
         q_.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(n_ + 1)));
         q_.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
         q_.weight.r = falloc(cap);
-        if (kind_ != Refract) { q_.weight.g = falloc(cap); q_.weight.b = falloc(cap); }
+        if (kind_ != Refract && kind_ != NodeDiffuse) { q_.weight.g = falloc(cap); q_.weight.b = falloc(cap); }
         q_.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
         q_.sample = static_cast<uint8_t *>(alloc((size_t)cap));
         if (kind_ == Refract) q_.kind = static_cast<uint8_t *>(alloc((size_t)cap));
@@ -331,6 +337,128 @@ inline void resolveDirect(const Device &d, const rls_sphere_light *lights, int n
     check(rls_trace_disney_direct_resolve(d.ctx(), q.points(), lights, n_lights, q.sppN(), &q.c(),
                                           rls_crgb{visibility.plane(0), visibility.plane(1), visibility.plane(2)},
                                           directDiffuse.rgb(), directSpecular.rgb()));
+}
+
+// The queues of a whole-node emit (rls_ggx_node_queues): the light loop's shadow queue (none with n_lights == 0) and one ray
+// queue per indirect loop.  Each queue owns its scratch.
+class GgxNodeQueues {
+public:
+    GgxNodeQueues(const Device &d, int64_t n, int n_lights, int spp_n)
+        : n_(n), n_lights_(n_lights), spp_n_(spp_n), shadow_(n_lights > 0 ? new ShadowQueue(d, n, n_lights, spp_n, ShadowQueue::Ggx) : nullptr),
+          glossy_(d, n, spp_n, RayQueue::Glossy), refract_(d, n, spp_n, RayQueue::Refract), diffuse_(d, n, spp_n, RayQueue::NodeDiffuse)
+    {
+        q_.shadow = shadow_ ? &shadow_->c() : nullptr;
+        q_.glossy = &glossy_.c(); q_.refract = &refract_.c(); q_.diffuse = &diffuse_.c();
+    }
+    ~GgxNodeQueues() { delete shadow_; }
+    GgxNodeQueues(const GgxNodeQueues &) = delete;
+    GgxNodeQueues &operator=(const GgxNodeQueues &) = delete;
+
+    const rls_ggx_node_queues &c() const { return q_; }
+    const ShadowQueue *shadow() const { return shadow_; }          // nullptr without lights
+    const RayQueue &glossy() const { return glossy_; }
+    const RayQueue &refract() const { return refract_; }
+    const RayQueue &diffuse() const { return diffuse_; }
+    int64_t points() const { return n_; }
+    int lights() const { return n_lights_; }
+    int sppN() const { return spp_n_; }
+
+private:
+    int64_t n_;
+    int n_lights_, spp_n_;
+    ShadowQueue *shadow_;
+    RayQueue glossy_, refract_, diffuse_;
+    rls_ggx_node_queues q_{};
+};
+
+// rls_disney_node_queues: the shadow queue (none with n_lights == 0), integrateDiffuse's and integrateGlossy's queues
+class DisneyNodeQueues {
+public:
+    DisneyNodeQueues(const Device &d, int64_t n, int n_lights, int spp_n)
+        : n_(n), n_lights_(n_lights), spp_n_(spp_n),
+          shadow_(n_lights > 0 ? new ShadowQueue(d, n, n_lights, spp_n, ShadowQueue::Disney) : nullptr),
+          diffuse_(d, n, spp_n, RayQueue::DisneyDiffuse), specular_(d, n, spp_n, RayQueue::DisneyGlossy)
+    {
+        q_.shadow = shadow_ ? &shadow_->c() : nullptr;
+        q_.diffuse = &diffuse_.c(); q_.specular = &specular_.c();
+    }
+    ~DisneyNodeQueues() { delete shadow_; }
+    DisneyNodeQueues(const DisneyNodeQueues &) = delete;
+    DisneyNodeQueues &operator=(const DisneyNodeQueues &) = delete;
+
+    const rls_disney_node_queues &c() const { return q_; }
+    const ShadowQueue *shadow() const { return shadow_; }
+    const RayQueue &diffuse() const { return diffuse_; }
+    const RayQueue &specular() const { return specular_; }
+    int64_t points() const { return n_; }
+    int lights() const { return n_lights_; }
+    int sppN() const { return spp_n_; }
+
+private:
+    int64_t n_;
+    int n_lights_, spp_n_;
+    ShadowQueue *shadow_;
+    RayQueue diffuse_, specular_;
+    rls_disney_node_queues q_{};
+};
+
+namespace detail {
+inline rls_crgb crgb(const Planes &p) { return p.empty() ? rls_crgb{nullptr, nullptr, nullptr} : rls_crgb{p.plane(0), p.plane(1), p.plane(2)}; }
+template <class Q>
+inline void checkNodeQueues(const Q &q, int64_t n, int n_lights, int spp_n, const char *who)
+{
+    if (q.points() != n || q.lights() != n_lights || q.sppN() != spp_n) throw Error(RLS_ERR_INVALID_ARGUMENT, who);
+}
+} // namespace detail
+
+// every ray of rlGgx's shader_evaluate as rls_ggx_shade samples it (rls_trace_ggx_shade_emit): the arguments of rls_ggx_shade
+// without env; traced false: the one ray of integrateRefract's untraced branch
+inline void emitNode(const Device &d, const rls_ggx_closure &c, const rls_ggx_shader &sh, const Planes &P,
+                     const rls_sphere_light *lights, int n_lights, bool traced, int64_t n, int spp_n, uint32_t seed,
+                     GgxNodeQueues &q, uint64_t first_index = 0)
+{
+    detail::checkNodeQueues(q, n, n_lights, spp_n, "emitNode: queues of another size or light count");
+    check(rls_trace_ggx_shade_emit(d.ctx(), n, &c, &sh, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights,
+                                   traced ? 1 : 0, spp_n, seed, first_index, &q.c()));
+}
+
+// every ray of rlDisney's shader_evaluate as rls_disney_shade samples it (rls_trace_disney_shade_emit)
+inline void emitNode(const Device &d, const rls_disney_closure &c, const Planes &P, const rls_sphere_light *lights,
+                     int n_lights, int64_t n, int spp_n, uint32_t seed, DisneyNodeQueues &q, uint64_t first_index = 0)
+{
+    detail::checkNodeQueues(q, n, n_lights, spp_n, "emitNode: queues of another size or light count");
+    check(rls_trace_disney_shade_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n,
+                                      seed, first_index, &q.c()));
+}
+
+// rls_ggx_shade's AOVs from what the renderer traced.  visibility (an empty Planes without lights) and the three radiances:
+// 3 planes of >= the queue's count floats each.  aovs: 15 planes of n floats -- direct_diffuse, direct_specular, refraction,
+// indirect_diffuse, indirect_specular, 3 each; out: sg->out.RGB, 3 planes of n floats, or nullptr
+inline void resolveNode(const Device &d, const rls_ggx_closure &c, const rls_ggx_shader &sh, const rls_sphere_light *lights,
+                        int n_lights, bool traced, const GgxNodeQueues &q, const Planes &visibility, const Planes &glossy,
+                        const Planes &refract, const Planes &diffuse, Planes &aovs, Planes *out = nullptr)
+{
+    detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveNode: queues of another light count");
+    rls_ggx_node_traced t = {detail::crgb(visibility), detail::crgb(glossy), detail::crgb(refract), detail::crgb(diffuse)};
+    rls_ggx_shade_out o = {};
+    o.direct_diffuse = aovs.rgb(0); o.direct_specular = aovs.rgb(3); o.refraction = aovs.rgb(6);
+    o.indirect_diffuse = aovs.rgb(9); o.indirect_specular = aovs.rgb(12);
+    if (out) o.out = out->rgb();
+    check(rls_trace_ggx_shade_resolve(d.ctx(), q.points(), &c, &sh, lights, n_lights, traced ? 1 : 0, q.sppN(), &q.c(), &t, &o));
+}
+
+// rls_disney_shade's AOVs.  aovs: 12 planes -- direct_diffuse, direct_specular, indirect_diffuse, indirect_specular
+inline void resolveNode(const Device &d, const rls_sphere_light *lights, int n_lights, const DisneyNodeQueues &q,
+                        const Planes &visibility, const Planes &diffuse, const Planes &specular, Planes &aovs,
+                        Planes *out = nullptr)
+{
+    detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveNode: queues of another light count");
+    rls_disney_node_traced t = {detail::crgb(visibility), detail::crgb(diffuse), detail::crgb(specular)};
+    rls_disney_shade_out o = {};
+    o.direct_diffuse = aovs.rgb(0); o.direct_specular = aovs.rgb(3); o.indirect_diffuse = aovs.rgb(6);
+    o.indirect_specular = aovs.rgb(9);
+    if (out) o.out = out->rgb();
+    check(rls_trace_disney_shade_resolve(d.ctx(), q.points(), lights, n_lights, q.sppN(), &q.c(), &t, &o));
 }
 
 } // namespace rlsb

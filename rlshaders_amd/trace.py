@@ -18,6 +18,9 @@ or of one rlDisney lobe, trace them with your own tracer, resolve the radiance; 
     vis = my_shadow_tracer(P[:, s.point], s.dir, s.maxdist)      # [3, count]: 1 unoccluded, 0 blocked
     dd, ds = s.resolve(vis)                                      # [3, n] each: rls_ggx_direct_lighting's AOVs, shadowed
 
+    nq = trace.ggx_node_rays(sampler, shader, P, lights, 4, 7)   # GgxNodeQueues: the whole node's rays, nq.shadow, nq.glossy,
+    aov = nq.resolve(vis, Lg, Lt, Ld)                            # nq.refract, nq.diffuse -> rls_ggx_shade's dict, traced
+
 ``count`` is read from the device once (it synchronises); everything else stays asynchronous on the context's stream, so
 ``glossy_rays(..., queue=q)`` / ``q.resolve(L, out=...)`` with preallocated tensors can be recorded by ``ctx.capture()``.
 """
@@ -79,6 +82,28 @@ _q = C.POINTER(RayQueue_)
 _pq = C.POINTER(ProbeQueue_)
 _sq = C.POINTER(ShadowQueue_)
 _lights = C.POINTER(capi.SphereLight)
+
+
+class GgxNodeQueues_(C.Structure):
+    """rls_ggx_node_queues"""
+    _fields_ = [("shadow", _sq), ("glossy", _q), ("refract", _q), ("diffuse", _q)]
+
+
+class GgxNodeTraced_(C.Structure):
+    """rls_ggx_node_traced"""
+    _fields_ = [("visibility", capi.CRgb), ("glossy", capi.CRgb), ("refract", capi.CRgb), ("diffuse", capi.CRgb)]
+
+
+class DisneyNodeQueues_(C.Structure):
+    """rls_disney_node_queues"""
+    _fields_ = [("shadow", _sq), ("diffuse", _q), ("specular", _q)]
+
+
+class DisneyNodeTraced_(C.Structure):
+    """rls_disney_node_traced"""
+    _fields_ = [("visibility", capi.CRgb), ("diffuse", capi.CRgb), ("specular", capi.CRgb)]
+
+
 PROTOTYPES = {
     "rls_trace_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
     "rls_trace_ggx_glossy_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
@@ -99,6 +124,16 @@ PROTOTYPES = {
     "rls_trace_ggx_direct_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.POINTER(capi.GgxShader), _lights,
                                                C.c_int, C.c_int, _sq, capi.CRgb, capi.Rgb, capi.Rgb]),
     "rls_trace_disney_direct_resolve": (C.c_int, [_ctx, _i64, _lights, C.c_int, C.c_int, _sq, capi.CRgb, capi.Rgb, capi.Rgb]),
+    "rls_trace_ggx_shade_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.POINTER(capi.GgxShader), capi.CVec3,
+                                           _lights, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64,
+                                           C.POINTER(GgxNodeQueues_)]),
+    "rls_trace_ggx_shade_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.POINTER(capi.GgxShader), _lights,
+                                              C.c_int, C.c_int, C.c_int, C.POINTER(GgxNodeQueues_),
+                                              C.POINTER(GgxNodeTraced_), C.POINTER(capi.GgxShadeOut)]),
+    "rls_trace_disney_shade_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.DisneyClosure), capi.CVec3, _lights, C.c_int,
+                                              C.c_int, C.c_uint32, C.c_uint64, C.POINTER(DisneyNodeQueues_)]),
+    "rls_trace_disney_shade_resolve": (C.c_int, [_ctx, _i64, _lights, C.c_int, C.c_int, C.POINTER(DisneyNodeQueues_),
+                                                 C.POINTER(DisneyNodeTraced_), C.POINTER(capi.DisneyShadeOut)]),
 }
 
 _lib = None
@@ -138,21 +173,31 @@ class RayQueue:
     first ``count`` rays.  ``lobe`` (RLS_RAY_DIFFUSE / RLS_RAY_GLOSSY) makes it a queue of that rlDisney lobe; without it
     the queue is rlGgx's, glossy or (``refract``) refraction."""
 
-    def __init__(self, ctx, n: int, spp_n: int, refract: bool = False, want_kind: bool = True, *, lobe: Optional[int] = None):
+    def __init__(self, ctx, n: int, spp_n: int, refract: bool = False, want_kind: bool = True, *, lobe: Optional[int] = None,
+                 scratch: Optional[torch.Tensor] = None, planes: Optional[int] = None):
         if lobe is not None and (lobe not in (RLS_RAY_DIFFUSE, RLS_RAY_GLOSSY) or refract):
             raise ValueError("lobe must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY, on a queue without refract")
+        if planes not in (None, 1) or (planes == 1 and (refract or lobe is not None)):
+            raise ValueError("planes: 1 (a scalar weight, as the rlGgx node's Oren-Nayar queue), on a queue that is neither "
+                             "refract nor an rlDisney lobe's")
         self.ctx, self.n, self.spp_n, self.refract = ctx, int(n), int(spp_n), bool(refract)
         self.lobe = lobe
+        # one weight plane: refraction (with a kind plane) or planes=1 (without); its resolve is the mean over the spp_n^2
+        # samples, rls_trace_ggx_refract_resolve
+        self.scalar = self.refract or planes == 1
+        scalar = self.scalar
         dev = ctx.torch_device
         cap = self.n * self.spp_n * self.spp_n
         self.capacity = cap
         self.offsets = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
         self._dir = torch.empty(3, cap, dtype=torch.float32, device=dev)
-        self._weight = torch.empty(1 if refract else 3, cap, dtype=torch.float32, device=dev)
+        self._weight = torch.empty(1 if scalar else 3, cap, dtype=torch.float32, device=dev)
         self._point = torch.empty(cap, dtype=torch.int32, device=dev)          # uint32 on the device; n < 2^31 here
         self._sample = torch.empty(cap, dtype=torch.uint8, device=dev)
         self._kind = torch.empty(cap, dtype=torch.uint8, device=dev) if refract and want_kind else None
-        self._scratch = torch.empty(max(scratch_bytes(self.n, self.spp_n), 1), dtype=torch.uint8, device=dev)
+        # (``scratch``: a uint8 block to use instead of one of its own -- the queues of one node emit may share one)
+        self._scratch = scratch if scratch is not None else \
+            torch.empty(max(scratch_bytes(self.n, self.spp_n), 1), dtype=torch.uint8, device=dev)
         # per point: getAvgReflectWeight (glossy) / the fraction of totally internally reflected samples (refraction) /
         # the valid samples (rlDisney)
         self.side = torch.empty(self.n, dtype=torch.float32, device=dev)
@@ -161,7 +206,7 @@ class RayQueue:
         q.capacity = cap
         q.offsets = self.offsets.data_ptr()
         q.dir = capi.Vec3(*[self._dir[k].data_ptr() for k in range(3)])
-        q.weight = capi.Rgb(w[0].data_ptr(), None if refract else w[1].data_ptr(), None if refract else w[2].data_ptr())
+        q.weight = capi.Rgb(w[0].data_ptr(), None if scalar else w[1].data_ptr(), None if scalar else w[2].data_ptr())
         q.point, q.sample = self._point.data_ptr(), self._sample.data_ptr()
         q.kind = self._kind.data_ptr() if self._kind is not None else None
         q.scratch, q.scratch_bytes = self._scratch.data_ptr(), self._scratch.numel()
@@ -218,8 +263,8 @@ class RayQueue:
 
     def resolve(self, radiance: torch.Tensor, out: Optional[torch.Tensor] = None, count: Optional[int] = None) -> torch.Tensor:
         """radiance [3, >= count] float32, one per ray -> [3, n]: glossy and rlDisney the sum of radiance x f/pdf per point
-        (the convention of rls_ggx_integrate's sum and rls_disney_integrate's diffuse_sum / specular_sum), refraction the
-        mean of radiance x weight over the spp_n^2 samples.
+        (the convention of rls_ggx_integrate's sum and rls_disney_integrate's diffuse_sum / specular_sum), refraction and
+        planes=1 queues the mean of radiance x weight over the spp_n^2 samples.
         ``count``: the ray count when the caller knows it (skips the read of offsets[n], e.g. while recording a graph)."""
         ctx, n = self.ctx, self.n
         count = self.count if count is None else int(count)
@@ -229,7 +274,7 @@ class RayQueue:
         res = ctx.empty(3, n) if out is None else out
         L = capi.CRgb(radiance[0].data_ptr(), radiance[1].data_ptr(), radiance[2].data_ptr())
         lib = load()
-        if self.refract:
+        if self.scalar:
             check(lib.rls_trace_ggx_refract_resolve(ctx.handle, n, C.byref(self.q), self.spp_n, L, rgb(res, n, "result")))
         else:
             check(lib.rls_trace_ggx_glossy_resolve(ctx.handle, n, C.byref(self.q), L, rgb(res, n, "sum")))
@@ -361,13 +406,15 @@ def shadow_scratch_bytes(n: int, n_lights: int, spp_n: int) -> int:
     return int(b.value)
 
 
-def ggx_shader(sampler: GgxSampler, KdColor=(1.0, 1.0, 1.0), Kd=0.5, diffuseRoughness=0.0, Ks=0.5) -> "capi.GgxShader":
-    """The node parameters rlGgx's light loop reads (rls_ggx_shader), as ``GgxSampler.directLighting`` takes them."""
+def ggx_shader(sampler: GgxSampler, KdColor=(1.0, 1.0, 1.0), Kd=0.5, diffuseRoughness=0.0, Ks=0.5,
+               KtColor=(1.0, 1.0, 1.0), Kt=0.0) -> "capi.GgxShader":
+    """The node parameters of rlGgx (rls_ggx_shader) as ``GgxSampler.directLighting`` / ``GgxSampler.shade`` take them: the
+    light loop reads the first four, the whole node (``ggx_node_rays``) KtColor and Kt too."""
     pn = sampler.pn
     sh = capi.GgxShader(param_rgb(KdColor, pn, "KdColor"), param(Kd, pn, "Kd"),
                         param(diffuseRoughness, pn, "diffuseRoughness"), param(Ks, pn, "Ks"),
-                        param_rgb((1.0, 1.0, 1.0), pn, "KtColor"), param(0.0, pn, "Kt"))
-    sh._keep = (KdColor, Kd, diffuseRoughness, Ks)           # tensor parameters stay alive with the struct
+                        param_rgb(KtColor, pn, "KtColor"), param(Kt, pn, "Kt"))
+    sh._keep = (KdColor, Kd, diffuseRoughness, Ks, KtColor, Kt)      # tensor parameters stay alive with the struct
     return sh
 
 
@@ -377,7 +424,7 @@ class ShadowQueue:
     samples, then the BSDF specular-lobe samples.  Planes are allocated for the full capacity n * n_lights * 3 * spp_n^2; the
     properties view the first ``count`` rays.  ``disney``: an rlDisney queue (three planes of weight_diffuse; rlGgx has one)."""
 
-    def __init__(self, ctx, n: int, n_lights: int, spp_n: int, disney: bool = False):
+    def __init__(self, ctx, n: int, n_lights: int, spp_n: int, disney: bool = False, scratch: Optional[torch.Tensor] = None):
         self.ctx, self.n, self.n_lights, self.spp_n, self.disney = ctx, int(n), int(n_lights), int(spp_n), bool(disney)
         dev = ctx.torch_device
         cap = self.n * self.n_lights * 3 * self.spp_n * self.spp_n
@@ -390,8 +437,8 @@ class ShadowQueue:
         self._kind = torch.empty(cap, dtype=torch.uint8, device=dev)
         self._point = torch.empty(cap, dtype=torch.int32, device=dev)          # uint32 on the device; n < 2^31 here
         self._sample = torch.empty(cap, dtype=torch.uint8, device=dev)
-        self._scratch = torch.empty(max(shadow_scratch_bytes(self.n, self.n_lights, self.spp_n), 1), dtype=torch.uint8,
-                                    device=dev)
+        self._scratch = scratch if scratch is not None else \
+            torch.empty(max(shadow_scratch_bytes(self.n, self.n_lights, self.spp_n), 1), dtype=torch.uint8, device=dev)
         q = ShadowQueue_()
         q.capacity = cap
         q.offsets = self.offsets.data_ptr()
@@ -500,4 +547,165 @@ def disney_shadow_rays(sampler: DisneySampler, P: torch.Tensor, lights, spp_n: i
     check(load().rls_trace_disney_direct_emit(ctx.handle, n, C.byref(sampler.c), Pv, la, nl, int(spp_n),
                                               int(seed) & 0xFFFFFFFF, int(first_index), C.byref(q.q)))
     q.lights, q.sampler, q.P = (la, nl), sampler, P
+    return q
+
+
+# ---------------------------------------------------------------------------------------------
+# Whole nodes: every ray of rls_ggx_shade / rls_disney_shade in one emit, their AOVs in one resolve
+
+
+def _radiance(t: torch.Tensor, count: int, what: str) -> "capi.CRgb":
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.shape[0] != 3 or \
+            t.shape[1] < count or t.stride(1) != 1:
+        raise ValueError(f"{what}: expected a float32 CUDA tensor [3, >= {count}] with unit inner stride")
+    return capi.CRgb(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+
+
+def node_scratch_bytes(n: int, n_lights: int, spp_n: int) -> int:
+    """The scratch block the queues of one node emit can share: the largest any of them needs."""
+    b = scratch_bytes(n, spp_n)
+    return max(b, shadow_scratch_bytes(n, n_lights, spp_n)) if n_lights > 0 else b
+
+
+class _NodeQueues:
+    """What the two nodes' queue sets share: the shadow queue (None without lights), the ray queues by member name, the
+    C struct, what the last emit took."""
+    RAY_MEMBERS = ()         # (member name, RayQueue's keyword arguments) per ray queue, in the C struct's order
+    RAYS = ()                # the member names
+    disney = False
+
+    def __init__(self, ctx, n: int, n_lights: int, spp_n: int, share_scratch: bool = False):
+        self.ctx, self.n, self.n_lights, self.spp_n = ctx, int(n), int(n_lights), int(spp_n)
+        scratch = None
+        if share_scratch:
+            scratch = torch.empty(max(node_scratch_bytes(self.n, self.n_lights, self.spp_n), 1), dtype=torch.uint8,
+                                  device=ctx.torch_device)
+        self.scratch = scratch
+        self.shadow = ShadowQueue(ctx, n, n_lights, spp_n, self.disney, scratch=scratch) if self.n_lights > 0 else None
+        for name, kw in self.RAY_MEMBERS:
+            setattr(self, name, RayQueue(ctx, n, spp_n, scratch=scratch, **kw))
+        self.lights = None
+        self.sampler = None
+        self.shader = None
+        self.traced = True
+
+    def _struct(self, cls):
+        q = cls()
+        q.shadow = C.pointer(self.shadow.q) if self.shadow is not None else None
+        for name, _ in self.RAY_MEMBERS:
+            setattr(q, name, C.pointer(getattr(self, name).q))
+        return q
+
+    def _matches(self, sampler, nl: int, spp_n: int) -> bool:
+        return self.n == sampler.n and self.spp_n == int(spp_n) and self.n_lights == nl
+
+    def _out(self, sampler, out, cls):
+        n, ctx = self.n, self.ctx
+        if out is None:
+            out = {k: ctx.empty(3, n) for k in sampler.SHADE_AOVS + ("out",)}
+        o = cls()
+        for k in sampler.SHADE_AOVS:
+            setattr(o, k, rgb(out[k], n, k))
+        if "out" in out:
+            o.out = rgb(out["out"], n, "out")
+        return out, o
+
+    def counts(self) -> dict:
+        """the ray count of every queue (reads the device: synchronises)"""
+        c = {"shadow": self.shadow.count if self.shadow is not None else 0}
+        c.update({name: getattr(self, name).count for name, _ in self.RAY_MEMBERS})
+        return c
+
+
+class GgxNodeQueues(_NodeQueues):
+    """The rays of the whole rlGgx node (rls_trace_ggx_shade_emit): ``shadow`` (ShadowQueue, None without lights), ``glossy``
+    (3 weight planes), ``refract`` (weight [1, count], kind) and ``diffuse`` (weight [1, count]) RayQueues -- the samples
+    ``GgxSampler.shade`` draws."""
+    RAY_MEMBERS = (("glossy", {}), ("refract", {"refract": True}), ("diffuse", {"planes": 1}))
+    RAYS = ("glossy", "refract", "diffuse")
+
+    def resolve(self, visibility, glossy, refract, diffuse, out=None, counts: Optional[dict] = None) -> dict:
+        """What the renderer traced, [3, >= count] float32 per queue (``visibility`` is not read without lights and may be
+        None) -> the dict ``GgxSampler.shade`` returns: the five AOVs and out, [3, n] each.  ``counts``: the ray counts where
+        the caller knows them (skips the reads of offsets[n], e.g. while recording a graph)."""
+        if self.sampler is None:
+            raise RuntimeError("resolve: no emit has filled these queues (trace.ggx_node_rays)")
+        cnt = self.counts() if counts is None else counts
+        t = GgxNodeTraced_()
+        if self.shadow is not None:
+            t.visibility = _radiance(visibility, cnt["shadow"], "visibility")
+        t.glossy = _radiance(glossy, cnt["glossy"], "glossy")
+        t.refract = _radiance(refract, cnt["refract"], "refract")
+        t.diffuse = _radiance(diffuse, cnt["diffuse"], "diffuse")
+        out, o = self._out(self.sampler, out, capi.GgxShadeOut)
+        la, nl = self.lights
+        q = self._struct(GgxNodeQueues_)
+        check(load().rls_trace_ggx_shade_resolve(self.ctx.handle, self.n, C.byref(self.sampler.c), C.byref(self.shader), la, nl,
+                                                 1 if self.traced else 0, self.spp_n, C.byref(q), C.byref(t), C.byref(o)))
+        return out
+
+
+class DisneyNodeQueues(_NodeQueues):
+    """The rays of the whole rlDisney node (rls_trace_disney_shade_emit): ``shadow`` (None without lights), ``diffuse`` and
+    ``specular`` RayQueues -- the samples ``DisneySampler.shade`` draws."""
+    RAY_MEMBERS = (("diffuse", {"lobe": RLS_RAY_DIFFUSE}), ("specular", {"lobe": RLS_RAY_GLOSSY}))
+    RAYS = ("diffuse", "specular")
+    disney = True
+
+    def resolve(self, visibility, diffuse, specular, out=None, counts: Optional[dict] = None) -> dict:
+        """-> the dict ``DisneySampler.shade`` returns: the four AOVs and out, [3, n] each."""
+        if self.sampler is None:
+            raise RuntimeError("resolve: no emit has filled these queues (trace.disney_node_rays)")
+        cnt = self.counts() if counts is None else counts
+        t = DisneyNodeTraced_()
+        if self.shadow is not None:
+            t.visibility = _radiance(visibility, cnt["shadow"], "visibility")
+        t.diffuse = _radiance(diffuse, cnt["diffuse"], "diffuse")
+        t.specular = _radiance(specular, cnt["specular"], "specular")
+        out, o = self._out(self.sampler, out, capi.DisneyShadeOut)
+        la, nl = self.lights
+        q = self._struct(DisneyNodeQueues_)
+        check(load().rls_trace_disney_shade_resolve(self.ctx.handle, self.n, la, nl, self.spp_n, C.byref(q), C.byref(t),
+                                                    C.byref(o)))
+        return out
+
+
+def ggx_node_rays(sampler: GgxSampler, shader: "capi.GgxShader", P: torch.Tensor, lights, spp_n: int, seed: int,
+                  first_index: int = 0, traced: bool = True, queues: Optional[GgxNodeQueues] = None,
+                  share_scratch: bool = False) -> GgxNodeQueues:
+    """Every ray of rlGgx's shader_evaluate (src/rlGgx.cpp:248-327) as ``GgxSampler.shade`` samples it: the light loop's shadow
+    rays, integrateGlossy (stream pair 24), integrateRefract (25; ``traced=False``: the one ray of the untraced branch) and the
+    Oren-Nayar indirect diffuse loop (26), behind the node's gates.  ``shader``: ``trace.ggx_shader`` with KtColor / Kt;
+    ``lights``: None, one ``make_light`` or a sequence.  ``share_scratch``: the queues share one scratch block."""
+    ctx, n = sampler.ctx, sampler.n
+    la, nl = light_array(lights)
+    q = GgxNodeQueues(ctx, n, nl, spp_n, share_scratch) if queues is None else queues
+    if not q._matches(sampler, nl, spp_n):
+        raise ValueError("queues: allocated for another batch size, light count or spp_n")
+    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
+    cq = q._struct(GgxNodeQueues_)
+    check(load().rls_trace_ggx_shade_emit(ctx.handle, n, C.byref(sampler.c), C.byref(shader), Pv, la, nl, 1 if traced else 0,
+                                          int(spp_n), int(seed) & 0xFFFFFFFF, int(first_index), C.byref(cq)))
+    q.lights, q.sampler, q.shader, q.P, q.traced = (la, nl), sampler, shader, P, bool(traced)
+    if q.shadow is not None:
+        q.shadow.lights, q.shadow.sampler, q.shadow.shader, q.shadow.P = (la, nl), sampler, shader, P
+    return q
+
+
+def disney_node_rays(sampler: DisneySampler, P: torch.Tensor, lights, spp_n: int, seed: int, first_index: int = 0,
+                     queues: Optional[DisneyNodeQueues] = None, share_scratch: bool = False) -> DisneyNodeQueues:
+    """Every ray of rlDisney's shader_evaluate (src/rlDisney.cpp:685-727) as ``DisneySampler.shade`` samples it: the light
+    loop's shadow rays, integrateDiffuse (stream pair 24) and integrateGlossy (25)."""
+    ctx, n = sampler.ctx, sampler.n
+    la, nl = light_array(lights)
+    q = DisneyNodeQueues(ctx, n, nl, spp_n, share_scratch) if queues is None else queues
+    if not q._matches(sampler, nl, spp_n):
+        raise ValueError("queues: allocated for another batch size, light count or spp_n")
+    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
+    cq = q._struct(DisneyNodeQueues_)
+    check(load().rls_trace_disney_shade_emit(ctx.handle, n, C.byref(sampler.c), Pv, la, nl, int(spp_n),
+                                             int(seed) & 0xFFFFFFFF, int(first_index), C.byref(cq)))
+    q.lights, q.sampler, q.P = (la, nl), sampler, P
+    if q.shadow is not None:
+        q.shadow.lights, q.shadow.sampler, q.shadow.P = (la, nl), sampler, P
     return q

@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss|ggx-lights|disney-lights] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
+    python tools/trace_bench.py [--closure ggx|disney|sss|ggx-lights|disney-lights|ggx-node|disney-node] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -22,6 +22,12 @@ the same batch: --lights spherical lights (default 2, MIS on) over shading point
 random coloured visibility.  A kept ray is 12 (dir) + 4 (maxdist) + 12 (weight_specular) + 4 or 12 (weight_diffuse: rlGgx
 one plane, rlDisney three) + 1 (kind) + 4 (point) + 1 (sample) = 38 / 46 B; the staging holds a 4 B tag for every one of the
 lights x 3 x spp slots of a point and 32 / 40 B per kept ray, read back by the compaction.  `kept` is rays / slots.
+--closure ggx-node / disney-node: the whole node (trace.ggx_node_rays / disney_node_rays) on the batch of the light-loop runs
+(the slab, --lights lights, per-point parameters; rlGgx with KtColor, Kt U[0,1)): the node emit (all queues, one call), the
+light loop's share of it (the same kernels through the light-loop emit), the node resolve (one launch), the SEPARATE existing
+resolves on the same queues (the light-loop resolve plus one glossy / refraction resolve per ray queue: they write one sum
+per queue and leave the composition to the caller), and rls_ggx_shade / rls_disney_shade.  Uniform random radiance and
+visibility.  The queues share one scratch block.
 """
 from __future__ import annotations
 
@@ -207,6 +213,72 @@ def bench_lights(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
     }
 
 
+def bench_node(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """the whole rlGgx or rlDisney node on bench_lights' batch: emit, fused resolve, the separate resolves, the analytic call"""
+    import torch
+    import rlshaders_amd as R
+    from rlshaders_amd import trace as T
+    from rlshaders_amd.closures import make_light
+    disney = args.closure == "disney-node"
+    nl = args.lights
+    lights = [make_light(center=c, radius=r, radiance=e) for c, r, e in LIGHT_SPECS[:nl]]
+    wo, N, T_ = R.gen_frame(ctx, seed, 0, n)
+    u = lambda stream, lo=0.0, hi=1.0: R.gen_uniform(ctx, seed, 0, n, stream, lo, hi)
+    P = torch.stack([u(60, 0.0, 4.0), u(61, 0.0, 4.0), u(62)]).contiguous()
+    if disney:
+        base = torch.stack([u(8 + j) for j in range(3)])
+        s = R.DisneySampler(ctx, wo, N, T_, base_color=base, **{k: u(32 + j) for j, k in enumerate(R._capi.DISNEY_SCALARS)})
+        aov = {k: ctx.empty(3, n) for k in s.SHADE_AOVS + ("out",)}
+        analytic = lambda: s.shade(P, lights, spp_n, seed, out=aov)
+        nq = T.DisneyNodeQueues(ctx, n, nl, spp_n, share_scratch=True)
+        emit = lambda: T.disney_node_rays(s, P, lights, spp_n, seed, queues=nq)
+        shadow_emit = lambda: T.disney_shadow_rays(s, P, lights, spp_n, seed, queue=nq.shadow)
+    else:
+        ks = torch.stack([u(10 + k) for k in range(3)])
+        s = R.GgxSampler(ctx, wo, N, T_, specColor=ks, ior=u(13, 1.05, 2.55), roughness=u(14, 0.05, 1.0),
+                         anisotropic=R.gen_aniso(ctx, seed, 0, n))
+        shp = dict(KdColor=torch.stack([u(20 + k) for k in range(3)]), Kd=u(23), diffuseRoughness=u(24), Ks=u(25),
+                   KtColor=torch.stack([u(26 + k) for k in range(3)]), Kt=u(29))
+        sh = T.ggx_shader(s, **shp)
+        aov = {k: ctx.empty(3, n) for k in s.SHADE_AOVS + ("out",)}
+        analytic = lambda: s.shade(P, lights, spp_n, seed, out=aov, **shp)
+        nq = T.GgxNodeQueues(ctx, n, nl, spp_n, share_scratch=True)
+        emit = lambda: T.ggx_node_rays(s, sh, P, lights, spp_n, seed, queues=nq)
+        shadow_emit = lambda: T.ggx_shadow_rays(s, sh, P, lights, spp_n, seed, queue=nq.shadow)
+    ms_int = timed(analytic, args.repeats, args.warmup)
+    ms_shadow = timed(shadow_emit, args.repeats, args.warmup)
+    ms_emit = timed(emit, args.repeats, args.warmup)
+    cnt = nq.counts()
+    planes = [torch.rand(3, max(cnt[r], 1), device=ctx.torch_device) for r in ("shadow",) + nq.RAYS]
+    res = {k: ctx.empty(3, n) for k in aov}
+    ms_res = timed(lambda: nq.resolve(*planes, out=res, counts=cnt), args.repeats, args.warmup)
+    # the same entry point as the existing resolve kernels plus a compose kernel (RLS_NODE_RESOLVE=separate: plain sums)
+    import os
+    os.environ["RLS_NODE_RESOLVE"] = "separate"
+    try:
+        ms_res_sep = timed(lambda: nq.resolve(*planes, out=res, counts=cnt), args.repeats, args.warmup)
+    finally:
+        del os.environ["RLS_NODE_RESOLVE"]
+    # the separate existing resolves on the same queues, each timed on its own and all of them back to back
+    two = (ctx.empty(3, n), ctx.empty(3, n))
+    sums = [ctx.empty(3, n) for _ in nq.RAYS]
+    parts = [lambda: nq.shadow.resolve(planes[0], out=two, count=cnt["shadow"])]
+    for j, r in enumerate(nq.RAYS):
+        parts.append(lambda j=j, r=r: getattr(nq, r).resolve(planes[1 + j], out=sums[j], count=cnt[r]))
+    ms_parts = [timed(f, args.repeats, args.warmup) for f in parts]
+    ms_sep = timed(lambda: [f() for f in parts], args.repeats, args.warmup)
+    rec["lights"] = nl
+    rec[args.closure] = {
+        "rays": cnt, "analytic_ms": round(ms_int, 4), "emit_ms": round(ms_emit, 4),
+        "shadow_emit_ms": round(ms_shadow, 4), "ray_emits_ms": round(ms_emit - ms_shadow, 4),
+        "node_resolve_ms": round(ms_res, 4), "node_resolve_as_separate_kernels_plus_compose_ms": round(ms_res_sep, 4),
+        "separate_resolves_ms": round(ms_sep, 4),
+        "separate_resolve_ms_each": dict(zip(("shadow",) + nq.RAYS, [round(m, 4) for m in ms_parts])),
+        "node_resolve_over_separate": round(ms_res / ms_sep, 4), "emit_over_analytic": round(ms_emit / ms_int, 4),
+        "emit_plus_resolve_over_analytic": round((ms_emit + ms_res) / ms_int, 4),
+    }
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=24)
@@ -214,7 +286,8 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
-    ap.add_argument("--closure", choices=("ggx", "disney", "sss", "ggx-lights", "disney-lights"), default="ggx")
+    ap.add_argument("--closure", choices=("ggx", "disney", "sss", "ggx-lights", "disney-lights", "ggx-node", "disney-node"),
+                    default="ggx")
     ap.add_argument("--lights", type=int, default=2, help="the light loops: spherical lights, 1..8")
     args = ap.parse_args()
     if args.repeats < 3:
@@ -235,7 +308,8 @@ def main() -> None:
            "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
     if args.closure != "ggx":
         rec["closure"] = args.closure
-        {"disney": bench_disney, "sss": bench_sss}.get(args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
+        {"disney": bench_disney, "sss": bench_sss, "ggx-node": bench_node, "disney-node": bench_node}.get(
+            args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
         print(json.dumps(rec), flush=True)
         return
