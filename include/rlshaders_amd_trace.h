@@ -333,6 +333,89 @@ rls_status rls_trace_disney_shade_resolve(rls_context *ctx, int64_t n, const rls
                                           int spp_n, const rls_disney_node_queues *q, const rls_disney_node_traced *t,
                                           const rls_disney_shade_out *out);
 
+/* ------------------------------------------------------------------------------------------
+ * Whole node: rlSkin.  shader_evaluate of rlSkin (src/rlSkin.cpp:174-254) cut at every place it traces.  rls_skin_integrate
+ * (rlshaders_amd.h) lights the node with no occluders, a uniform environment and an analytic plane or sphere; here the emit
+ * fills five queues, the renderer traces them, and ONE resolve composes the three AOVs and sg->out.RGB.
+ *
+ * Samples: exactly rls_skin_integrate's -- hash(seed, first_index + i), the same (0,2) table, the math mode of the context;
+ * stream pair 0 the sheen lobe's integrateGlossy, 1 the specular lobe's, 2 integrateScatter; light l of the sheen lobe pairs
+ * 3 + 4 l (light samples) and 4 + 4 l (BSDF samples), of the specular lobe 5 + 4 l and 6 + 4 l.  The closures are built as
+ * rls_skin_integrate builds them: both lobes share one local view, neither has anisotropy.
+ *
+ * Emit, on the context's stream, never synchronising the host; n == 0 writes empty queues:
+ *   shadow queues (sheen_shadow, specular_shadow; the light loops of :193-198 / :217-222), one per lobe, in rls_shadow_queue:
+ *       weight_diffuse may be NULL and is not written; only weight_specular carries terms; kind = light | (RLS_SHADOW_BSDF for a
+ *       BSDF-strategy ray) | RLS_SHADOW_SPECULAR.  A ray is queued unless its term is 0 in all three channels.  ORDER WITHIN A
+ *       POINT DIFFERS FROM THE rlGgx QUEUE'S: the loop grows ONE sum per light, sample by sample, the light sample's term and
+ *       then the BSDF sample's; so lights ascend, within a light samples ascend, and within a sample the light-strategy ray
+ *       comes before the BSDF-strategy ray.  capacity >= n * n_lights * 2 * spp_n^2; rls_trace_shadow_scratch_bytes(n, n_lights,
+ *       spp_n) is enough scratch; maxdist as in the light loops' queue.  A light whose cone is not valid (P inside it) draws
+ *       nothing; a lobe whose weight is <= AI_EPSILON (:191, :214) has no rays.
+ *   glossy queues (sheen_glossy, specular_glossy), one per lobe: the rays rls_trace_ggx_glossy_emit queues for a rlGgx closure
+ *       with the lobe's colour, ior and roughness, at the lobe's stream pair.  A lobe with weight <= AI_EPSILON or a small
+ *       colour (every channel below AI_EPSILON, src/rlGgx.h:174-176) has no rays.
+ *   the mean Fresnel hand-down (src/rlSkin.cpp:204, 228, 238).  getAvgReflectWeight (src/rlGgx.h:181-184) is ONE running float
+ *       sum: first over the light loops' BSDF samples (all lights, sample order), then over integrateGlossy's samples, divided
+ *       by their count; with a small colour the light loops' part alone; 1 when nothing was drawn.  The emit forms that sum in
+ *       that order: a lobe's shadow emit leaves (sum, count) per point in the lobe's Fresnel plane and in sssWeight, the lobe's
+ *       glossy emit starts its fold there.  So the hand-over lives in the three scalar planes, never in a queue's scratch: the
+ *       five queues may share one scratch block sized to the largest, and are filled one after another.  At the end
+ *       sheenFresnel = avg_sheen * sheen_weight (0 for a sheen_weight <= AI_EPSILON), specularFresnel likewise, sssWeight =
+ *       sss_weight * (1 - specularFresnel * (1 - sheenFresnel)): rls_skin_integrate's optional outputs bit for bit.  None of
+ *       the three depends on what the renderer traces.
+ *       (The three planes are the emit's working storage too: after an emit that was refused or failed their contents are
+ *       undefined, and the emit's launches must stay in order on the context's stream.)
+ *   probe queue (probes): rls_trace_sss_probe_emit's dense queue for scatterDist = sss_scatter_dist * sss_dist_multiplier and the
+ *       frame sss_frame(N, T, dPdu = T), at pair 2; no scratch.  A point with sssWeight < AI_EPSILON (:244) has its rays
+ *       written with maxdist = 0 -- the renderer finds nothing along them -- and the resolve does not read that point's hits.
+ *
+ * Resolve, ONE launch.  Per point, with inv = 1 / spp_n^2 and per channel c:
+ *     lit_c      = +0; per light l in order: s_c = the sum in queue order of visibility_c[k] * weight_specular_c[k];
+ *                  lit_c += (radiance_c[l] * s_c) * inv
+ *     lobe_c     = lit_c + S_c(glossy), S_c about a reference radiance exactly as in the rlGgx / rlDisney node resolves above
+ *     sheen_c    = lobe_c(sheen) * sheen_weight                            (0 * weight where the lobe's gate is shut)
+ *     specular_c = lobe_c(specular) * (specular_weight * (1 - sheenFresnel))
+ *     sss_c      = sssWeight < AI_EPSILON ? 0 : scatter_c * sssWeight,
+ *                  scatter_c = rls_trace_sss_scatter_resolve's result, (sss_color_c * sum_c) * inv
+ *     out_c      = (sheen_c + specular_c) + sss_c
+ * sheenFresnel, specularFresnel and sssWeight are read from the queues struct and copied to `out` where its optional planes are
+ * given.  Sums and products only, but for the scatter resolve's profile and MIS arithmetic, which follows the context's math
+ * mode.  With a visibility of 1, the same radiance env on every glossy ray and the probe rays traced through
+ * rls_skin_integrate's scene with E = light_color * (AI_ONEOVERPI * max(0, N.L)), the resolve returns rls_skin_integrate(env,
+ * scene, lights) bit for bit: the three AOVs, out and the three scalars, EXACT and FAST.
+ *
+ * Both calls return RLS_ERR_INVALID_ARGUMENT, before the context is read, for: a NULL struct or required plane; shadow queues
+ * that are not both present exactly when n_lights > 0; n_lights outside 0 .. RLS_MAX_LIGHTS; spp_n outside 1 .. 16; a capacity
+ * or scratch too small; hits->max_hits outside 1 .. RLS_MAX_PROBE_HITS or hits->stride < n * spp_n^2.
+ * ---------------------------------------------------------------------------------------- */
+
+typedef struct rls_skin_node_queues {
+    const rls_shadow_queue *sheen_shadow, *specular_shadow; /* light loops of :193-198 / :217-222; both NULL iff n_lights == 0 */
+    const rls_ray_queue    *sheen_glossy, *specular_glossy; /* integrateGlossy per lobe: dir, weight (3 planes) */
+    const rls_probe_queue  *probes;                         /* integrateScatter's probe rays, dense */
+    float *sheenFresnel, *specularFresnel, *sssWeight;      /* [n] each, required: written by the emit, read by the resolve */
+} rls_skin_node_queues;
+
+typedef struct rls_skin_node_traced {
+    rls_crgb sheen_visibility, specular_visibility;         /* not read when n_lights == 0 */
+    rls_crgb sheen_glossy, specular_glossy;                 /* radiance per ray */
+    const rls_probe_hits *hits;                             /* as rls_trace_sss_scatter_resolve takes them */
+} rls_skin_node_traced;
+
+/* The rays of rls_skin_integrate: the arguments are that call's (without scene and env). */
+rls_status rls_trace_skin_emit(rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
+                               const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                               uint64_t first_index, const rls_skin_node_queues *q);
+
+/* rls_skin_integrate's AOVs, sg->out.RGB and hand-down scalars from what the renderer traced.  c, P, lights, n_lights, spp_n:
+ * those of the emit; use_cavity_fade, literal_matrix: as rls_trace_sss_scatter_resolve takes them.  The three AOV planes of out
+ * are required; out->out (all three planes) and the three scalars are optional. */
+rls_status rls_trace_skin_resolve(rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
+                                  const rls_sphere_light *lights, int n_lights, int use_cavity_fade, int literal_matrix,
+                                  int spp_n, const rls_skin_node_queues *q, const rls_skin_node_traced *t,
+                                  const rls_skin_integrate_out *out);
+
 #ifdef __cplusplus
 }
 #endif

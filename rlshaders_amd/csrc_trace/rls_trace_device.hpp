@@ -144,6 +144,61 @@ struct DisneyNodeResolveIO {
     int64_t n;
 };
 
+// rlSkin's node (rls_trace_skin_emit / _resolve).  A lobe's light loop (ggx_light_loops, rls_loops.hpp) draws a light sample and a
+// BSDF sample of the ONE GGX lobe per light and sample: two segments a light (0 the light-strategy ray, 1 the BSDF-strategy
+// ray), slot (l * 2 + segment) * spp + s, seven staged planes (no diffuse term), the tag and the compaction of the light loops.
+constexpr int kSkinShadowSegments = 2;
+constexpr int kSkinShadowPlanes = 7;         // dir[3], maxdist, weight_specular[3]
+struct SkinShadowEmitIO {
+    rls_skin_closure c;
+    rls_cvec3 P;
+    rls_sphere_light lights[RLS_MAX_LIGHTS];
+    int nl;
+    int lobe;                // 0 sheen (stream pairs 3 + 4 l, 4 + 4 l), 1 specular (5 + 4 l, 6 + 4 l)
+    float *dir[3];
+    float *maxdist;
+    float *ws[3];
+    uint32_t *tag;
+    int64_t *count;          // = the queue's offsets
+    float *fsum, *fcnt;      // the hand-over to the lobe's glossy emit: the Fresnel sum and count of the loop's BSDF samples
+    int64_t n;
+    int spp;
+    uint32_t seed;
+    uint64_t first;
+};
+// a lobe's integrateGlossy: fsum / fcnt as the lobe's light loop left them (NULL without lights); side: the lobe's Fresnel plane
+struct SkinGlossyEmitIO : EmitIO<rls_skin_closure> {
+    const float *fsum, *fcnt;
+};
+struct SkinProbeEmitIO {
+    rls_skin_closure c;
+    rls_cvec3 P;
+    rls_probe_queue q;
+    const float *sheenFresnel, *specularFresnel;
+    float *sssWeight;        // written: sss_weight * (1 - specularFresnel * (1 - sheenFresnel))
+    int64_t n;
+    int spp;
+    int tile_points;
+    uint32_t seed;
+    uint64_t first;
+};
+// the node's resolve: per lobe the light loop's queue (ShadowResolveIO: offsets, ws, kind, vis, rad, nl, inv) and the glossy
+// queue; the probe hits; the three scalars of the emit; the AOVs
+struct SkinNodeResolveIO {
+    rls_skin_closure c;
+    rls_cvec3 P;
+    ShadowResolveIO sheen_s, spec_s;
+    TraceResolveIO sheen_g, spec_g;
+    rls_probe_hits h;
+    const float *sheenFresnel, *specularFresnel, *sssWeight;
+    rls_skin_integrate_out o;
+    float inv;               // 1 / spp
+    int spp;
+    int tile_points;         // of the scatter walk: sss_resolve_tile_points(spp)
+    int cavity, literal;
+    int64_t n;
+};
+
 // rlSss: the probe-ray emit and the scatter resolve.  Both walk tiles of `tile_points` consecutive points: ray j = i * spp + s
 // of the dense queue is ray j - p0 * spp of the tile that starts at point p0.  The emit takes up to kSssEmitRays rays per
 // tile (several per thread), the resolve up to kBlock (one per thread: its LDS holds the terms of every hit of the tile).

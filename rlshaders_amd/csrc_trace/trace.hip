@@ -121,6 +121,7 @@ struct GgxLobe {
     static constexpr bool kGated = false;
     Ggx g;
     VndfView w;
+    GgxLobe() = default;                                         // (rlSkin's lobes build g and w themselves: SkinGlossy)
     __device__ GgxLobe(const EmitIO<rls_ggx_closure> &a, int64_t ii)
     {
         RLS_GGX_LOAD(loaded, a.c, ii)
@@ -406,8 +407,8 @@ struct GgxHitLobe {
     RLS_DEV void run(SlowLds<K> &slow, int qn, float conePdf, int mode) const { ggx_hit_eval_run<K>(slow, qn, g, conePdf, mode); }
 };
 
-// One point's place in the staging and its running ray count
-template <int G, class IO>
+// One point's place in the staging and its running ray count; SEGS: the segments of a light
+template <int G, class IO, int SEGS = kShadowSegments>
 struct ShadowStage {
     const IO &a;
     int64_t i;
@@ -424,8 +425,33 @@ struct ShadowStage {
         if (NWD == 3) bd = !(wd[0] == 0.0f && wd[1] == 0.0f && wd[2] == 0.0f);
         const bool keep = ok && (bs || bd);
         const int rank = group_rank<G>(keep, sub, run);
+        store<NWD>(cone, l, seg, s, ok, keep, rank, bs, bd, dir, ws, wd);
+    }
+    // rlSkin's light loops grow ONE sum per light, sample by sample, the light sample's term and then the BSDF sample's
+    // (fold2 in ggx_light_loops): sample s's two rays, A the light-strategy one (segment 0) and B the BSDF-strategy one
+    // (segment 1), ranked by a prefix count over the PAIRS of the point's earlier samples; A before B.  Specular terms only.
+    __device__ __forceinline__ void put_pair(const LightCone &cone, int l, int s, bool ok, V3 dirA, const float (&wa)[3], V3 dirB,
+                                             const float (&wb)[3])
+    {
+        const bool ka = ok && !(wa[0] == 0.0f && wa[1] == 0.0f && wa[2] == 0.0f);
+        const bool kb = ok && !(wb[0] == 0.0f && wb[1] == 0.0f && wb[2] == 0.0f);
+        const uint64_t ma = __builtin_amdgcn_ballot_w64(ka), mb = __builtin_amdgcn_ballot_w64(kb);
+        const int base = (int)(threadIdx.x & 63u) & ~(G - 1);
+        uint64_t ga = ma, gb = mb;
+        if constexpr (G < 64) { ga = (ma >> base) & ((1ull << G) - 1ull); gb = (mb >> base) & ((1ull << G) - 1ull); }
+        const uint64_t below = (1ull << sub) - 1ull;
+        const int rankA = run + __builtin_popcountll(ga & below) + __builtin_popcountll(gb & below);
+        const int rankB = rankA + (ka ? 1 : 0);
+        run += __builtin_popcountll(ga) + __builtin_popcountll(gb);
+        store<0>(cone, l, 0, s, ok, ka, rankA, true, false, dirA, wa, wa);
+        store<0>(cone, l, 1, s, ok, kb, rankB, true, false, dirB, wb, wb);
+    }
+    template <int NWD>
+    __device__ __forceinline__ void store(const LightCone &cone, int l, int seg, int s, bool ok, bool keep, int rank, bool bs,
+                                          bool bd, V3 dir, const float (&ws)[3], const float (&wd)[3])
+    {
         if (live && ok) {
-            const int64_t slot = staging_slot((l * kShadowSegments + seg) * a.spp + s, a.n, i);
+            const int64_t slot = staging_slot((l * SEGS + seg) * a.spp + s, a.n, i);
             const IO al = RLS_INT_ARGS(a);                       // the staging planes' pointers re-read where they are used
             if (keep) {
                 // the near intersection of P + t dir with the light's sphere: t^2 |dir|^2 - 2 b t + c2 = 0, in the form that
@@ -436,8 +462,10 @@ struct ShadowStage {
                 al.maxdist[slot] = R_DIV(cone.c2, b + R_SQRT(disc));
 #pragma unroll
                 for (int c = 0; c < 3; c++) al.ws[c][slot] = ws[c];
+                if constexpr (NWD > 0) {
 #pragma unroll
-                for (int c = 0; c < NWD; c++) al.wd[c][slot] = wd[c];
+                    for (int c = 0; c < NWD; c++) al.wd[c][slot] = wd[c];
+                }
             }
             const int kind = l | (seg ? RLS_SHADOW_BSDF : 0) | (bs ? RLS_SHADOW_SPECULAR : 0) | (bd ? RLS_SHADOW_DIFFUSE : 0);
             al.tag[slot] = shadow_tag(keep, rank, kind);
@@ -448,7 +476,7 @@ struct ShadowStage {
     {
         if (!live) return;
         for (int s = sub; s < a.spp; s += G)
-            a.tag[staging_slot((l * kShadowSegments + seg) * a.spp + s, a.n, i)] = kShadowDropped;
+            a.tag[staging_slot((l * SEGS + seg) * a.spp + s, a.n, i)] = kShadowDropped;
     }
 };
 
@@ -623,13 +651,167 @@ __global__ RLS_DISNEY_LIGHT_ATTR void disney_direct_emit_kernel(ShadowEmitIO<rls
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// rlSkin's node: shader_evaluate (src/rlSkin.cpp:174-254) as skin_integrate_kernel (csrc/shade.hip) runs it, cut at every place
+// it traces.  Per GGX lobe (sheen, then specular) the light loop's shadow rays (skin_shadow_emit_kernel), then integrateGlossy's
+// rays (skin_*_glossy_emit_kernel: GgxGlossy on the lobe's closure); then integrateScatter's probe rays
+// (skin_probe_emit_kernel).  The mean Fresnel a layer hands down (getAvgReflectWeight, src/rlGgx.h:181-184) is ONE running
+// float sum over the light loops' BSDF samples and then integrateGlossy's: the shadow emit leaves (sum, count) per point in
+// two of the caller's three scalar planes -- the sum in the lobe's own Fresnel plane, the count in sssWeight -- the glossy emit
+// starts its fold there and overwrites the Fresnel plane with avg * weight; the probe emit, last, writes sssWeight.  So the
+// hand-over never lives in a queue's scratch, and the five queues may share one scratch block.
+
+// One GGX lobe of the node at point ii, built as skin_integrate_kernel builds it (csrc/shade.hip:36-49, 66-69): both lobes share
+// the frame and the local view; ggx_make<true>: no anisotropy.
+struct SkinLobe {
+    Ggx g;
+    VndfView w;
+    V3 N;
+    float weight;
+    bool small;              // integrateGlossy draws nothing (src/rlGgx.h:174-176); the light loop does
+};
+__device__ __forceinline__ SkinLobe skin_lobe(const rls_skin_closure &c, int64_t ii, int lobe)
+{
+    SkinLobe r;
+    const PIndex<int64_t> pk = pindex(c.materials, ii);
+    const V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
+    Frame gfr;
+    gfr.N = N; gfr.U = T; gfr.V = cross(N, T);
+    const V3 local = vndf_local(wo, gfr);
+    float cr, cg, cb, ior, rough;
+    if (lobe == 0) {
+        r.weight = ldp(c.sheen_weight, pk);
+        ldrgb(c.sheen_color, pk, cr, cg, cb);
+        ior = ldp(c.sheen_ior, pk); rough = ldp(c.sheen_roughness, pk);
+    } else {
+        r.weight = ldp(c.specular_weight, pk);
+        ldrgb(c.specular_color, pk, cr, cg, cb);
+        ior = ldp(c.specular_ior, pk); rough = ldp(c.specular_roughness, pk);
+    }
+    r.g = ggx_make<true>(wo, N, T, false, cr, cg, cb, ior, rough, 0.0f);
+    r.w = vndf_view_from(local, r.g.ax, r.g.ay);
+    r.N = N;
+    r.small = absf(cr) < kEps && absf(cg) < kEps && absf(cb) < kEps;
+    return r;
+}
+
+// A lobe's light loop: ggx_light_loops (rls_loops.hpp:447-495; its lines restated here, to be changed together --
+// tests/test_gpu_trace_skin.py holds the copies together bit for bit) with both terms of a sample staged instead of folded
+// into the light's one sum.  The Fresnel sum f grows over every BSDF sample of every light, in sample order (fold), cnt counts
+// them; a lobe whose weight is <= AI_EPSILON (src/rlSkin.cpp:191, 214) or a light whose cone is not valid draws nothing.
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void skin_shadow_emit_kernel(SkinShadowEmitIO a)
+{
+    __shared__ uint32_t tab[2][kMaxSpp];
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    RLS_POINT_WALK(G, a.n)
+    const int spp = a.spp;
+    const uint32_t stream = a.lobe ? 5u : 3u;
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
+        const bool live = i < a.n;
+        const int64_t ii = live ? i : a.n - 1;
+        const SkinLobe sl = skin_lobe(a.c, ii, a.lobe);
+        const Ggx &g = sl.g;
+        const V3 N = sl.N, P = ld3(a.P, ii);
+        const uint64_t index = a.first + (uint64_t)ii;
+        ShadowStage<G, SkinShadowEmitIO, kSkinShadowSegments> st = { a, i, live, sub, 0 };
+        float f = 0.0f, cnt = 0.0f;
+        for (int l = 0; l < a.nl; l++) {
+            const LightRegs lt = light_regs(a.lights[l], P);
+            const LightCone &cone = lt.cone;
+            const int mode = lt.mode;
+            uint32_t scr[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) scr[k] = hash_u32(a.seed, index, kScrambleStream + 2 * (stream + 4 * l) + k);
+            const bool draw = sl.weight > kEps && cone.valid;
+            for (int s0 = 0; s0 < spp; s0 += G) {               // the same trip count in every lane (ballots, shuffles)
+                const int s = s0 + sub;
+                const bool ok = s < spp;
+                float wa[3] = { 0.0f, 0.0f, 0.0f }, wb[3] = { 0.0f, 0.0f, 0.0f }, tF = 0.0f, tC = 0.0f;
+                V3 La = mk(0.0f, 0.0f, 0.0f), Lb = mk(0.0f, 0.0f, 0.0f);
+                if (draw && ok && mode != RLS_MIS_BSDF_ONLY) {
+                    float rx = bits_u01(tab[0][s] ^ scr[0]), ry = bits_u01(tab[1][s] ^ scr[1]);
+                    La = cone_sample(cone, rx, ry);
+                    if (dot(La, N) > 0.0f) {
+                        float fr, fg, fb, pb;
+                        ggx_eval_pdf<true, true>(g, La, fr, fg, fb, pb);
+                        float wgt = mode == RLS_MIS_LIGHT_ONLY ? 1.0f : power_heuristic(cone.pdf, pb);
+                        wa[0] = R_DIV(fr * wgt, cone.pdf); wa[1] = R_DIV(fg * wgt, cone.pdf); wa[2] = R_DIV(fb * wgt, cone.pdf);
+                    }
+                }
+                if (draw && ok && mode != RLS_MIS_LIGHT_ONLY) {
+                    float rx = bits_u01(tab[0][s] ^ scr[2]), ry = bits_u01(tab[1][s] ^ scr[3]);
+                    V3 M = vndf_microfacet(sl.w, g.fr, rx, ry);
+                    Lb = reflect_direction(g.view, M);
+                    tF = ggx_fresnel(g, Lb, M);                     // mReflectWeight += ..., mMisSampleCount += 1
+                    tC = 1.0f;
+                    if (!is_zero(Lb) && dot(Lb, N) > 0.0f && cone_hit(cone, Lb)) {
+                        float fr, fg, fb, pb;
+                        ggx_eval_pdf<true, true>(g, Lb, fr, fg, fb, pb);
+                        float wgt = mode == RLS_MIS_BSDF_ONLY ? 1.0f : power_heuristic(pb, cone.pdf);
+                        wb[0] = R_DIV(fr * wgt, pb); wb[1] = R_DIV(fg * wgt, pb); wb[2] = R_DIV(fb * wgt, pb);
+                    }
+                }
+                st.put_pair(cone, l, s, ok, La, wa, Lb, wb);
+                fold<G>(f, tF);
+                cnt += G == 1 ? tC : group_sum<G>(tC);
+            }
+        }
+        if (live && sub == 0) {
+            a.count[i] = st.run;
+            a.fsum[i] = f; a.fcnt[i] = cnt;
+        }
+    }
+}
+
+// A lobe's integrateGlossy (LOBE 0 sheen: stream pair 0; 1 specular: pair 1): GgxGlossy's rays on the lobe's closure, behind
+// the lobe's gates -- no rays for a weight <= AI_EPSILON (:191, :214) or a small colour (src/rlGgx.h:174-176).  The Fresnel
+// fold starts from the light loop's (sum, count); the side output is the layer's hand-down avg * weight (:204, :228): avg over
+// the light loops' samples alone for a small colour, 1 when nothing was drawn, and the scalar 0 where the weight shuts the lobe.
+template <int G, int LOBE>
+struct SkinGlossy : GgxGlossy<G> {
+    static constexpr int kStream = 2 * LOBE;
+    static constexpr bool kGated = true;
+    bool open, lobe_open;
+    float weight, cnt = 0.0f;
+    __device__ SkinGlossy(const SkinGlossyEmitIO &a, int64_t ii)
+    {
+        const SkinLobe sl = skin_lobe(a.c, ii, LOBE);
+        this->g = sl.g; this->w = sl.w;
+        weight = sl.weight;
+        lobe_open = weight > kEps;
+        open = lobe_open && !sl.small;
+        if (a.fsum) { this->accF = a.fsum[ii]; cnt = a.fcnt[ii]; }
+    }
+    __device__ float side(int spp) const
+    {
+        if (!lobe_open) return 0.0f;
+        const float fcnt = open ? cnt + (float)spp : cnt;
+        const float avg = fcnt > 0.0f ? R_DIV(this->accF, fcnt) : 1.0f;
+        return avg * weight;
+    }
+};
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void skin_sheen_glossy_emit_kernel(SkinGlossyEmitIO a)
+{
+    emit_points<G, SkinGlossy<G, 0>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void skin_specular_glossy_emit_kernel(SkinGlossyEmitIO a)
+{
+    emit_points<G, SkinGlossy<G, 1>>(a);
+}
+
 // integrateScatter's probe rays (getProbeRay, src/rlSss.h:224-228) into the dense queue.  Per tile the points' profile,
 // frame, position and scrambles are computed once, by one thread each, into LDS; then each thread takes rays threadIdx.x,
 // threadIdx.x + kBlock, ... of the tile, draws the sample and the probe ray as scatter_loop does and stores the ray at
 // j = p0 * spp + its place in the tile: the tile's rays are one contiguous range of every plane.
-constexpr int kEmitWords = 19;               // d[3], c1[3], c2[3], maxR, U, V, N (nd_radius reads d, c1, c2, maxR only)
-template <int FAST_MATH = RLS_FAST>
-__global__ __launch_bounds__(rlsh::kBlock) void sss_probe_emit_kernel(SssEmitIO a)
+// STREAM: the first scramble stream; point(i, p, fr): the profile and frame of point i, returns whether its rays are to be
+// traced (else they are written with maxdist = 0: rlSkin's sssWeight gate).
+constexpr int kEmitWords = 20;               // d[3], c1[3], c2[3], maxR, U, V, N, traced (nd_radius reads d, c1, c2, maxR only)
+template <int STREAM, class IO, class PointFn>
+__device__ __forceinline__ void probe_emit_tiles(const IO &a, PointFn point)
 {
     __shared__ uint32_t tab[2][kMaxSpp];
     __shared__ float pt[kEmitWords][kSssEmitPoints];
@@ -645,19 +827,19 @@ __global__ __launch_bounds__(rlsh::kBlock) void sss_probe_emit_kernel(SssEmitIO 
         __syncthreads();                                         // the previous tile's points are consumed
         if (t < pc) {
             const int64_t i = p0 + t;
-            const rls_sss_closure &c = a.c;
-            const PIndex<int64_t> pk = pindex(c.materials, i);
-            const NdProfile p = scatter_profile(c, pk);
-            const Frame fr = sss_frame(ld3(c.N, i), ld3(c.T, i), c.has_dPdu != 0);
+            NdProfile p;
+            Frame fr;
+            const bool traced = point(i, p, fr);
             const V3 Po = ld3(a.P, i);
             for (int k = 0; k < 3; k++) { pt[k][t] = p.d[k]; pt[3 + k][t] = p.c1[k]; pt[6 + k][t] = p.c2[k]; }
             pt[9][t] = p.maxR;
             pt[10][t] = fr.U.x; pt[11][t] = fr.U.y; pt[12][t] = fr.U.z;
             pt[13][t] = fr.V.x; pt[14][t] = fr.V.y; pt[15][t] = fr.V.z;
             pt[16][t] = fr.N.x; pt[17][t] = fr.N.y; pt[18][t] = fr.N.z;
+            pt[19][t] = traced ? 1.0f : 0.0f;
             po[0][t] = Po.x; po[1][t] = Po.y; po[2][t] = Po.z;
-            scr[0][t] = hash_u32(a.seed, a.first + (uint64_t)i, kScrambleStream);
-            scr[1][t] = hash_u32(a.seed, a.first + (uint64_t)i, kScrambleStream + 1);
+            scr[0][t] = hash_u32(a.seed, a.first + (uint64_t)i, kScrambleStream + STREAM);
+            scr[1][t] = hash_u32(a.seed, a.first + (uint64_t)i, kScrambleStream + STREAM + 1);
             a.q.offsets[i] = i * a.spp;
             if (i == a.n - 1) a.q.offsets[a.n] = a.n * a.spp;
         }
@@ -676,6 +858,7 @@ __global__ __launch_bounds__(rlsh::kBlock) void sss_probe_emit_kernel(SssEmitIO 
             V3 off, dir;
             float maxdist;
             sss_probe_ray(p, fr, rx, ry, off, dir, maxdist);                 // :228
+            if (pt[19][lp] == 0.0f) maxdist = 0.0f;
             const V3 O = mk(po[0][lp], po[1][lp], po[2][lp]) + off;
             const int64_t j = p0 * a.spp + u;
             const rls_probe_queue &q = a.q;
@@ -688,6 +871,37 @@ __global__ __launch_bounds__(rlsh::kBlock) void sss_probe_emit_kernel(SssEmitIO 
     }
 }
 
+template <int FAST_MATH = RLS_FAST>
+__global__ __launch_bounds__(rlsh::kBlock) void sss_probe_emit_kernel(SssEmitIO a)
+{
+    probe_emit_tiles<0>(a, [&](int64_t i, NdProfile &p, Frame &fr) {
+        const rls_sss_closure &c = a.c;
+        p = scatter_profile(c, pindex(c.materials, i));
+        fr = sss_frame(ld3(c.N, i), ld3(c.T, i), c.has_dPdu != 0);
+        return true;
+    });
+}
+
+// rlSkin's integrateScatter (src/rlSkin.cpp:235-246): scatterDist = sss_scatter_dist * sss_dist_multiplier, the frame with
+// dPdu, stream pair 2.  sssWeight (:238) is formed here from the two lobes' hand-downs and written; a point whose sssWeight is
+// below AI_EPSILON (:244) traces nothing: its rays carry maxdist = 0.
+template <int FAST_MATH = RLS_FAST>
+__global__ __launch_bounds__(rlsh::kBlock) void skin_probe_emit_kernel(SkinProbeEmitIO a)
+{
+    probe_emit_tiles<4>(a, [&](int64_t i, NdProfile &p, Frame &fr) {
+        const rls_skin_closure &c = a.c;
+        const PIndex<int64_t> pk = pindex(c.materials, i);
+        const float mult = ldp(c.sss_dist_multiplier, pk);                            // :235-236
+        float sssWeight = ldp(c.sss_weight, pk);
+        sssWeight *= 1.0f - a.specularFresnel[i] * (1.0f - a.sheenFresnel[i]);        // :238
+        a.sssWeight[i] = sssWeight;
+        p = nd_make<true>(ldp(c.sss_scatter_dist[0], pk) * mult, ldp(c.sss_scatter_dist[1], pk) * mult,
+                          ldp(c.sss_scatter_dist[2], pk) * mult);
+        fr = sss_frame(ld3(c.N, i), ld3(c.T, i), true);
+        return !(sssWeight < kEps);
+    });
+}
+
 // integrateScatter's combination (src/rlSss.h:245-279) of the hits the caller traced.  Per tile: one thread per ray walks
 // the ray's hits as scatter_loop walks the analytic ones -- duplicate test, radius cut-off, cavity fade, shaded count,
 // evalProfile, the MIS pdf -- and leaves each hit's term irr / pdf (+0 for a skipped hit) in LDS; then one thread per point
@@ -695,6 +909,59 @@ __global__ __launch_bounds__(rlsh::kBlock) void sss_probe_emit_kernel(SssEmitIO 
 // per-point profile and frame are recomputed per ray (the same arithmetic as the integrator's, so the same bits): staged in
 // LDS instead, once per point, the kernel ran slower at 2^22 points x 16 rays (2.90 against 2.44 ms; 47 KB of LDS, three
 // workgroups per CU instead of four).
+// One probe ray's walk (thread t of a tile, ray j of the queue, about the shading point Po with profile p and frame fr): the
+// term irr / pdf of each of its hits to term[k][.][t], its hit slots min(count, max_hits) and its shaded hits.
+__device__ __forceinline__ void scatter_ray_terms(float (*term)[3][rlsh::kBlock], uint8_t *slots, uint8_t *shaded, int t,
+                                                  const NdProfile &p, const Frame &fr, V3 Po, const rls_probe_hits &h, int64_t j,
+                                                  bool cavity, bool literal)
+{
+    const int cnt = h.count[j] < h.max_hits ? (int)h.count[j] : h.max_hits;
+    V3 prev = Po;
+    int sh = 0;
+    for (int k = 0; k < cnt; k++) {
+        const int64_t at = (int64_t)k * h.stride + j;
+        const V3 hp = ld3(h.P, at), hn = ld3(h.N, at);
+        const float eR = ldg(h.irradiance.r, at), eG = ldg(h.irradiance.g, at), eB = ldg(h.irradiance.b, at);
+        float tR = 0.0f, tG = 0.0f, tB = 0.0f;
+        if (length(prev - hp) > kEps) {                                  // :316-317
+            prev = hp;
+            // shadeProbeSample, :379-420
+            const V3 d = hp - Po;
+            const float r = length(d);
+            if (!(r > p.maxR)) {
+                float fade = 1.0f;
+                if (cavity) fade = sss_cavity_fade(d, r, hn, fr.N);
+                if (fade > kEps) {
+                    sh++;
+                    float pr, pg, pb;
+                    nd_profile(p, r, pr, pg, pb);
+                    const float iR = eR * pr * fade, iG = eG * pg * fade, iB = eB * pb * fade;
+                    if (!(iR == 0.0f && iG == 0.0f && iB == 0.0f)) {            // :249
+                        const float pdf = sss_mis_pdf(p, fr, d, hn, literal);
+                        tR = R_DIV(iR, pdf); tG = R_DIV(iG, pdf); tB = R_DIV(iB, pdf);
+                    }
+                }
+            }
+        }
+        term[k][0][t] = tR; term[k][1][t] = tG; term[k][2][t] = tB;
+    }
+    slots[t] = (uint8_t)cnt;
+    shaded[t] = (uint8_t)sh;
+}
+// a point's sums over its spp rays, the tile's rays r0 .. r0 + spp - 1: in sample order and, within a sample, in hit order
+__device__ __forceinline__ void scatter_point_sums(const float (*term)[3][rlsh::kBlock], const uint8_t *slots,
+                                                   const uint8_t *shaded, int r0, int spp, float (&acc)[3], float &accD)
+{
+    float accR = 0.0f, accG = 0.0f, accB = 0.0f;
+    accD = 0.0f;
+    for (int s = 0, r = r0; s < spp; s++, r++) {
+        const int cnt = slots[r];
+        for (int k = 0; k < cnt; k++) { accR += term[k][0][r]; accG += term[k][1][r]; accB += term[k][2][r]; }
+        accD += (float)shaded[r];
+    }
+    acc[0] = accR; acc[1] = accG; acc[2] = accB;
+}
+
 template <int FAST_MATH = RLS_FAST>
 __global__ RLS_INT_ATTR void sss_scatter_resolve_kernel(SssResolveIO a)
 {
@@ -713,53 +980,17 @@ __global__ RLS_INT_ATTR void sss_scatter_resolve_kernel(SssResolveIO a)
             const int64_t i = p0 + lp, j = p0 * a.spp + t;
             const SssResolveIO al = RLS_INT_ARGS(a);
             const rls_sss_closure &c = al.c;
-            const rls_probe_hits &h = al.h;
             const PIndex<int64_t> pk = pindex(c.materials, i);
             const NdProfile p = scatter_profile(c, pk);
             const Frame fr = sss_frame(ld3(c.N, i), ld3(c.T, i), c.has_dPdu != 0);
-            const V3 Po = ld3(al.P, i);
-            const int cnt = h.count[j] < h.max_hits ? (int)h.count[j] : h.max_hits;
-            V3 prev = Po;
-            int sh = 0;
-            for (int k = 0; k < cnt; k++) {
-                const int64_t at = (int64_t)k * h.stride + j;
-                const V3 hp = ld3(h.P, at), hn = ld3(h.N, at);
-                const float eR = ldg(h.irradiance.r, at), eG = ldg(h.irradiance.g, at), eB = ldg(h.irradiance.b, at);
-                float tR = 0.0f, tG = 0.0f, tB = 0.0f;
-                if (length(prev - hp) > kEps) {                                  // :316-317
-                    prev = hp;
-                    // shadeProbeSample, :379-420
-                    const V3 d = hp - Po;
-                    const float r = length(d);
-                    if (!(r > p.maxR)) {
-                        float fade = 1.0f;
-                        if (al.cavity) fade = sss_cavity_fade(d, r, hn, fr.N);
-                        if (fade > kEps) {
-                            sh++;
-                            float pr, pg, pb;
-                            nd_profile(p, r, pr, pg, pb);
-                            const float iR = eR * pr * fade, iG = eG * pg * fade, iB = eB * pb * fade;
-                            if (!(iR == 0.0f && iG == 0.0f && iB == 0.0f)) {            // :249
-                                const float pdf = sss_mis_pdf(p, fr, d, hn, al.literal != 0);
-                                tR = R_DIV(iR, pdf); tG = R_DIV(iG, pdf); tB = R_DIV(iB, pdf);
-                            }
-                        }
-                    }
-                }
-                term[k][0][t] = tR; term[k][1][t] = tG; term[k][2][t] = tB;
-            }
-            slots[t] = (uint8_t)cnt;
-            shaded[t] = (uint8_t)sh;
+            scatter_ray_terms(term, slots, shaded, t, p, fr, ld3(al.P, i), al.h, j, al.cavity != 0, al.literal != 0);
         }
         __syncthreads();
         if (t < pc) {
             const int64_t i = p0 + t;
-            float accR = 0.0f, accG = 0.0f, accB = 0.0f, accD = 0.0f;
-            for (int s = 0, r = t * a.spp; s < a.spp; s++, r++) {
-                const int cnt = slots[r];
-                for (int k = 0; k < cnt; k++) { accR += term[k][0][r]; accG += term[k][1][r]; accB += term[k][2][r]; }
-                accD += (float)shaded[r];
-            }
+            float acc[3], accD;
+            scatter_point_sums(term, slots, shaded, t * a.spp, a.spp, acc, accD);
+            const float accR = acc[0], accG = acc[1], accB = acc[2];
             const SssResolveIO al = RLS_INT_ARGS(a);
             float br, bg, bb;
             ldrgb(al.c.sss_color, pindex(al.c.materials, i), br, bg, bb);
@@ -796,6 +1027,9 @@ __global__ __launch_bounds__(rlsh::kBlock) void trace_scan_add_kernel(int64_t *v
     for (int64_t j = (int64_t)blockIdx.x * rlsh::kBlock + threadIdx.x; j < n; j += (int64_t)gridDim.x * rlsh::kBlock)
         v[j] += totals[j / kScanTile];
 }
+#endif
+// (What follows, down to the node resolves, is templates and inline device functions: the mode-free kernels among them are
+// instantiated by the EXACT unit's host code alone; rlSkin's node resolve, built per math mode, uses the walks in both units.)
 
 // A tile of P consecutive points (P * spp <= kCompactSlots): sample (i, s) moves from staging slot s * n + i to queue position
 // offsets[i] + rank.  Through LDS, one plane at a time, so that both sides are coalesced: the staging is read in rows (one
@@ -1069,7 +1303,9 @@ template <int NWD>
 __device__ __forceinline__ void shadow_sums(float (*prod)[kShadowTile], uint8_t *kinds, const float (*rad)[3],
                                             const ShadowResolveIO &a, int64_t p0, float (&oS)[3], float (&oD)[3])
 {
-    constexpr bool GGX = NWD == 1;
+    // NWD = 0: a lobe of rlSkin (ggx_light_loops, rls_loops.hpp): no diffuse term, and ONE sum per light that takes the rays of
+    // both strategies in queue order; the lights' terms are added to +0
+    constexpr bool GGX = NWD == 1, ONE = NWD == 0;
     const int64_t i = p0 + threadIdx.x;
     const bool live = i < a.n;
     const int64_t pend = a.n - p0 < rlsh::kBlock ? a.n : p0 + rlsh::kBlock;
@@ -1081,8 +1317,9 @@ __device__ __forceinline__ void shadow_sums(float (*prod)[kShadowTile], uint8_t 
     auto close_light = [&]() {
 #pragma unroll
         for (int c = 0; c < 3; c++) {
+            // (ONE: bS stays +0, and a sum that starts at +0 is never -0: lS + bS is lS)
             const float tS = rad[l][c] * (lS[c] + bS[c]) * a.inv, tD = rad[l][c] * (lD[c] + bD[c]) * a.inv;
-            oS[c] = l == 0 ? tS : oS[c] + tS;
+            oS[c] = l == 0 && !ONE ? tS : oS[c] + tS;
             oD[c] = l == 0 ? tD : oD[c] + tD;
             lS[c] = 0.0f; lD[c] = 0.0f; bS[c] = 0.0f; bD[c] = 0.0f;
         }
@@ -1098,7 +1335,7 @@ __device__ __forceinline__ void shadow_sums(float (*prod)[kShadowTile], uint8_t 
             if (GGX) {
                 const float wd = a.wd[0][r];
                 prod[3][k] = vr * wd; prod[4][k] = vg * wd; prod[5][k] = vb * wd;
-            } else {
+            } else if (!ONE) {
                 prod[3][k] = vr * a.wd[0][r]; prod[4][k] = vg * a.wd[1][r]; prod[5][k] = vb * a.wd[2][r];
             }
             kinds[k] = a.kind[r];
@@ -1109,7 +1346,9 @@ __device__ __forceinline__ void shadow_sums(float (*prod)[kShadowTile], uint8_t 
             const int k = (int)(r - t0), kind = kinds[k];
             const int lk = (kind & RLS_SHADOW_LIGHT_MASK) < a.nl ? (kind & RLS_SHADOW_LIGHT_MASK) : a.nl - 1;
             while (l < lk) close_light();
-            if (kind & RLS_SHADOW_BSDF) {
+            if (ONE) {
+                lS[0] += prod[0][k]; lS[1] += prod[1][k]; lS[2] += prod[2][k];
+            } else if (kind & RLS_SHADOW_BSDF) {
                 if (kind & RLS_SHADOW_SPECULAR) { bS[0] += prod[0][k]; bS[1] += prod[1][k]; bS[2] += prod[2][k]; }
                 if (kind & RLS_SHADOW_DIFFUSE) { bD[0] += prod[3][k]; bD[1] += prod[4][k]; bD[2] += prod[5][k]; }
             } else {
@@ -1166,6 +1405,7 @@ __global__ __launch_bounds__(rlsh::kBlock) void shadow_resolve_kernel(ShadowReso
     }
 }
 
+#if !RLS_FAST
 // The node resolves: one launch composes rls_ggx_shade's / rls_disney_shade's AOVs and sg->out.RGB.  A workgroup takes kBlock
 // consecutive points and walks their contiguous ray range of each queue in turn -- the light loop's (shadow_sums), then each
 // indirect loop's (ray_sums_about_reference) -- through ONE LDS store (the light loop's six product planes; a ray queue keeps
@@ -1295,6 +1535,93 @@ __global__ __launch_bounds__(rlsh::kBlock) void disney_node_compose_kernel(Disne
 }
 #endif
 
+// rlSkin's node resolve: ONE launch composes rls_skin_integrate's three AOVs and sg->out.RGB (src/rlSkin.cpp:249-254).  A
+// workgroup takes kBlock consecutive points and walks, through ONE LDS store, per lobe the light loop's queue (shadow_sums<0>)
+// and the glossy queue (ray_sums_about_reference), then the points' probe rays in sub-tiles of tile_points points -- one thread
+// per ray (scatter_ray_terms), then the point's own lane sums its rays (scatter_point_sums): sss_scatter_resolve_kernel's two
+// steps -- and composes as skin_integrate_kernel does (csrc/shade.hip:61-63, 79-82, 95, 101).  Sums and products only, but for
+// the scatter walk's profile and MIS arithmetic, which is per math mode: built in both units like sss_scatter_resolve_kernel.
+// A point whose sssWeight is below AI_EPSILON has its hits left unread and sss = 0.  LDS: 37.9 KB a workgroup (the scatter
+// terms, as sss_scatter_resolve_kernel; the light loop's product planes and a ray queue's planes lie in the same store): four
+// workgroups (16 waves) a CU.
+template <int FAST_MATH = RLS_FAST>
+__global__ __launch_bounds__(rlsh::kBlock) void skin_node_resolve_kernel(SkinNodeResolveIO a)
+{
+    __shared__ float lds[RLS_MAX_PROBE_HITS * 3 * rlsh::kBlock];
+    __shared__ uint8_t kinds[kShadowTile];
+    __shared__ float rad[RLS_MAX_LIGHTS][3];
+    __shared__ uint8_t slots[rlsh::kBlock];
+    __shared__ uint8_t shaded[rlsh::kBlock];
+    static_assert(RLS_MAX_PROBE_HITS * 3 * rlsh::kBlock >= 6 * kShadowTile, "the scatter terms' store holds the product planes");
+    float (*prod)[kShadowTile] = (float (*)[kShadowTile])lds;
+    float (*term)[3][rlsh::kBlock] = (float (*)[3][rlsh::kBlock])lds;
+    stage_libm_tables();
+    stage_radiance(rad, a.sheen_s);                              // (both lobes: the same lights)
+    const int t = (int)threadIdx.x, P = a.tile_points;
+    for (int64_t p0 = (int64_t)blockIdx.x * rlsh::kBlock; p0 < a.n; p0 += (int64_t)gridDim.x * rlsh::kBlock) {
+        const int64_t i = p0 + t;
+        float litA[3] = { 0.0f, 0.0f, 0.0f }, litB[3] = { 0.0f, 0.0f, 0.0f }, none[3], gA[3], gB[3];
+        if (a.sheen_s.nl > 0) shadow_sums<0>(prod, kinds, rad, a.sheen_s, p0, litA, none);              // :193-198
+        ray_sums_about_reference<3>(prod, a.sheen_g, p0, a.n, a.inv, gA);
+        if (a.spec_s.nl > 0) shadow_sums<0>(prod, kinds, rad, a.spec_s, p0, litB, none);                // :217-222
+        ray_sums_about_reference<3>(prod, a.spec_g, p0, a.n, a.inv, gB);
+        // integrateScatter, :244-246
+        const int bc = a.n - p0 < rlsh::kBlock ? (int)(a.n - p0) : rlsh::kBlock;
+        float sc[3] = { 0.0f, 0.0f, 0.0f };
+        for (int q0 = 0; q0 < bc; q0 += P) {
+            const int pc = bc - q0 < P ? bc - q0 : P;
+            __syncthreads();                                     // the store's previous contents are consumed
+            if (t < pc * a.spp) {
+                const int lp = t / a.spp;
+                const int64_t pi = p0 + q0 + lp, j = (p0 + q0) * a.spp + t;
+                const SkinNodeResolveIO al = RLS_INT_ARGS(a);
+                if (al.sssWeight[pi] < kEps) {
+                    slots[t] = 0; shaded[t] = 0;
+                } else {
+                    const rls_skin_closure &c = al.c;
+                    const PIndex<int64_t> pk = pindex(c.materials, pi);
+                    const float mult = ldp(c.sss_dist_multiplier, pk);
+                    const NdProfile p = nd_make<true>(ldp(c.sss_scatter_dist[0], pk) * mult, ldp(c.sss_scatter_dist[1], pk) * mult,
+                                                      ldp(c.sss_scatter_dist[2], pk) * mult);
+                    const Frame fr = sss_frame(ld3(c.N, pi), ld3(c.T, pi), true);
+                    scatter_ray_terms(term, slots, shaded, t, p, fr, ld3(al.P, pi), al.h, j, al.cavity != 0, al.literal != 0);
+                }
+            }
+            __syncthreads();
+            if (t >= q0 && t < q0 + pc) {
+                float depth;
+                scatter_point_sums(term, slots, shaded, (t - q0) * a.spp, a.spp, sc, depth);
+            }
+        }
+        if (i < a.n) {
+            const SkinNodeResolveIO al = RLS_INT_ARGS(a);
+            const rls_skin_closure &c = al.c;
+            const PIndex<int64_t> pk = pindex(c.materials, i);
+            const float sheenWeight = ldp(c.sheen_weight, pk), specWeight = ldp(c.specular_weight, pk);
+            const float sheenFresnel = al.sheenFresnel[i], specularFresnel = al.specularFresnel[i], sssWeight = al.sssWeight[i];
+            float br, bg, bb;
+            ldrgb(c.sss_color, pk, br, bg, bb);
+            const float bc3[3] = { br, bg, bb };
+            const float sw = specWeight * (1.0f - sheenFresnel);                      // :231
+            float sh[3], sp[3], ss[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                sh[k] = (sheenWeight > kEps ? litA[k] + gA[k] : 0.0f) * sheenWeight;  // :191, :207
+                sp[k] = (specWeight > kEps ? litB[k] + gB[k] : 0.0f) * sw;            // :214, :231
+                ss[k] = sssWeight < kEps ? 0.0f : bc3[k] * sc[k] * a.inv * sssWeight; // :244-246
+            }
+            const rls_skin_integrate_out &o = al.o;
+            strgb(o.sheen, i, sh[0], sh[1], sh[2]);
+            strgb(o.specular, i, sp[0], sp[1], sp[2]);
+            strgb(o.sss, i, ss[0], ss[1], ss[2]);
+            if (o.out.r) strgb(o.out, i, sh[0] + sp[0] + ss[0], sh[1] + sp[1] + ss[1], sh[2] + sp[2] + ss[2]);   // :254
+            if (o.sheenFresnel) stg(o.sheenFresnel, i, sheenFresnel);
+            if (o.specularFresnel) stg(o.specularFresnel, i, specularFresnel);
+            if (o.sssWeight) stg(o.sssWeight, i, sssWeight);
+        }
+    }
+}
+
 // one launch of the rlSss emit or resolve: a workgroup per tile of io.tile_points points, grid-striding past the cap
 template <class IO>
 rls_status launch_tiles(rls_context *ctx, void (*kernel)(IO), const IO &io, const char *name)
@@ -1359,6 +1686,27 @@ rls_status launch_sss_scatter_resolve(rls_context *ctx, int, const SssResolveIO 
 {
     return launch_tiles(ctx, sss_scatter_resolve_kernel<>, io, name);
 }
+rls_status launch_skin_shadow_emit(rls_context *ctx, int g, const SkinShadowEmitIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(skin_shadow_emit_kernel), g, io, name);
+}
+rls_status launch_skin_sheen_glossy_emit(rls_context *ctx, int g, const SkinGlossyEmitIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(skin_sheen_glossy_emit_kernel), g, io, name);
+}
+rls_status launch_skin_specular_glossy_emit(rls_context *ctx, int g, const SkinGlossyEmitIO &io, const char *name)
+{
+    return launch_g(ctx, RLS_G_FAMILY(skin_specular_glossy_emit_kernel), g, io, name);
+}
+rls_status launch_skin_probe_emit(rls_context *ctx, int, const SkinProbeEmitIO &io, const char *name)
+{
+    return launch_tiles(ctx, skin_probe_emit_kernel<>, io, name);
+}
+rls_status launch_skin_node_resolve(rls_context *ctx, int, const SkinNodeResolveIO &io, const char *name)
+{
+    hipLaunchKernelGGL(skin_node_resolve_kernel<>, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(name, RLS_FAST);
+}
 
 } // namespace
 
@@ -1377,6 +1725,11 @@ RLS_FLAVOURS(ggx_direct_emit, GgxShadowEmitIO)
 RLS_FLAVOURS(disney_direct_emit, DisneyShadowEmitIO)
 RLS_FLAVOURS(sss_probe_emit, SssEmitIO)
 RLS_FLAVOURS(sss_scatter_resolve, SssResolveIO)
+RLS_FLAVOURS(skin_shadow_emit, SkinShadowEmitIO)
+RLS_FLAVOURS(skin_sheen_glossy_emit, SkinGlossyEmitIO)
+RLS_FLAVOURS(skin_specular_glossy_emit, SkinGlossyEmitIO)
+RLS_FLAVOURS(skin_probe_emit, SkinProbeEmitIO)
+RLS_FLAVOURS(skin_node_resolve, SkinNodeResolveIO)
 
 #if !RLS_FAST
 
@@ -1527,23 +1880,33 @@ rls_status resolve(rls_context *ctx, int64_t n, const rls_ray_queue *q, int spp_
     return rlsh::check_launch(refract ? "rls_trace_ggx_refract_resolve" : "rls_trace_ggx_glossy_resolve");
 }
 
-// the planes both light-loop verbs need of a queue; ggx: weight_diffuse is its .r plane alone
-rls_status check_shadow_queue(const char *fn, const rls_shadow_queue *q, bool ggx, int64_t n, int nl, int spp)
+// the planes both light-loop verbs need of a queue; nwd: the planes of weight_diffuse (rlDisney 3; rlGgx 1, its .r; a lobe of
+// rlSkin 0: none, and two segments a light instead of three)
+rls_status check_shadow_queue(const char *fn, const rls_shadow_queue *q, int nwd, int64_t n, int nl, int spp)
 {
     RLS_REQUIRE_IN(fn, rlsh::has3(q->dir) && q->maxdist != nullptr, "queue.dir or queue.maxdist plane is NULL");
-    RLS_REQUIRE_IN(fn, rlsh::has3(q->weight_specular) && (ggx ? q->weight_diffuse.r != nullptr : rlsh::has3(q->weight_diffuse)),
-                   "queue.weight_specular or queue.weight_diffuse plane is NULL");
+    if (nwd == 0) RLS_REQUIRE_IN(fn, rlsh::has3(q->weight_specular), "queue.weight_specular plane is NULL");
+    else RLS_REQUIRE_IN(fn, rlsh::has3(q->weight_specular) && (nwd == 1 ? q->weight_diffuse.r != nullptr : rlsh::has3(q->weight_diffuse)),
+                        "queue.weight_specular or queue.weight_diffuse plane is NULL");
     RLS_REQUIRE_IN(fn, q->kind != nullptr, "queue.kind is NULL");
-    RLS_REQUIRE_IN(fn, q->capacity >= n * nl * kShadowSegments * spp, "queue.capacity < n * n_lights * 3 * spp_n^2");
+    if (nwd == 0) RLS_REQUIRE_IN(fn, q->capacity >= n * nl * kSkinShadowSegments * spp, "queue.capacity < n * n_lights * 2 * spp_n^2");
+    else RLS_REQUIRE_IN(fn, q->capacity >= n * nl * kShadowSegments * spp, "queue.capacity < n * n_lights * 3 * spp_n^2");
     return RLS_OK;
 }
+// the staged diffuse planes of a light-loop emit (rlSkin's has none)
+template <class C, class S>
+void set_diffuse_staging(ShadowEmitIO<C, S> &io, const Staging &st) { for (int k = 0; k < 3; k++) io.wd[k] = st.f[7 + k]; }
+void set_diffuse_staging(SkinShadowEmitIO &, const Staging &) {}
+// a point's staging slots and the staged planes of a light-loop emit
+inline int shadow_slots(int nwd, int nl, int spp) { return nl * (nwd == 0 ? kSkinShadowSegments : kShadowSegments) * spp; }
+inline int shadow_planes(int nwd) { return nwd == 0 ? kSkinShadowPlanes : kShadowPlanes; }
 
 // Both light-loop emits: the argument checks (closure: the node's checks of its closure, shader and P, which fill io), the
 // empty queue of n == 0, the staging in the caller's scratch, the closure's emit kernel (dispatch, with G for the batch), then
 // the scan of the counts and the compaction.
 template <class IO, class ClosureCheck>
 rls_status shadow_emit(rls_context *ctx, int64_t n, ClosureCheck closure, const rls_sphere_light *lights, int n_lights,
-                       int spp_n, uint32_t seed, uint64_t first_index, const rls_shadow_queue *q, bool ggx, const char *name,
+                       int spp_n, uint32_t seed, uint64_t first_index, const rls_shadow_queue *q, int nwd, const char *name,
                        rls_status (*dispatch)(rls_context *, int, const IO &, const char *))
 {
     if (rls_status s = check_batch(name, ctx, n, spp_n)) return s;
@@ -1553,34 +1916,36 @@ rls_status shadow_emit(rls_context *ctx, int64_t n, ClosureCheck closure, const 
     IO io = {};
     if (rls_status s = closure(io)) return s;
     if (rls_status s = copy_lights(lights, n_lights, 1, io.lights, &io.nl)) return s;
-    if (rls_status s = check_shadow_queue(name, q, ggx, n, io.nl, spp)) return s;
-    const int slots = io.nl * kShadowSegments * spp;
-    const Staging st = staging(q->scratch, n, slots, kShadowPlanes, sizeof(uint32_t));
+    if (rls_status s = check_shadow_queue(name, q, nwd, n, io.nl, spp)) return s;
+    const int slots = shadow_slots(nwd, io.nl, spp);
+    const Staging st = staging(q->scratch, n, slots, shadow_planes(nwd), sizeof(uint32_t));
     RLS_REQUIRE_IN(name, q->scratch != nullptr && q->scratch_bytes >= st.bytes,
                    "queue.scratch is NULL or smaller than rls_trace_shadow_scratch_bytes");
 
-    for (int k = 0; k < 3; k++) { io.dir[k] = st.f[k]; io.ws[k] = st.f[4 + k]; io.wd[k] = st.f[7 + k]; }
+    for (int k = 0; k < 3; k++) { io.dir[k] = st.f[k]; io.ws[k] = st.f[4 + k]; }
+    set_diffuse_staging(io, st);
     io.maxdist = st.f[3]; io.tag = (uint32_t *)st.tag;
     if (rls_status s = emit_and_scan(ctx, io, n, spp_n, seed, first_index, q->offsets, st, name, dispatch)) return s;
 
     ShadowCompactIO cio = {};
-    for (int k = 0; k < kShadowPlanes; k++) cio.src[k] = st.f[k];
+    for (int k = 0; k < shadow_planes(nwd); k++) cio.src[k] = st.f[k];
     cio.tag = io.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp; cio.slots = slots;
     cio.tile_points = compact_tile_points(kShadowMaxSlots, slots);
     const dim3 cgrid = rlsh::grid_for(ctx, n, cio.tile_points);
-    if (ggx) hipLaunchKernelGGL(shadow_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    if (nwd == 0) hipLaunchKernelGGL(shadow_compact_kernel<0>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    else if (nwd == 1) hipLaunchKernelGGL(shadow_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
     else hipLaunchKernelGGL(shadow_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
     return rlsh::check_launch("shadow_compact_kernel");
 }
 
 // The light loop's part of a resolve's argument struct (the light-loop resolves and the node resolves): the lights, the queue's
 // planes, the visibility, 1 / spp.  n_lights >= 1.
-rls_status shadow_resolve_io(const char *name, ShadowResolveIO &io, int64_t n, bool ggx, const rls_sphere_light *lights,
+rls_status shadow_resolve_io(const char *name, ShadowResolveIO &io, int64_t n, int nwd, const rls_sphere_light *lights,
                              int n_lights, int spp_n, const rls_shadow_queue *q, rls_crgb visibility)
 {
     rls_sphere_light lt[RLS_MAX_LIGHTS];
     if (rls_status s = copy_lights(lights, n_lights, 1, lt, &io.nl)) return s;
-    if (rls_status s = check_shadow_queue(name, q, ggx, n, io.nl, spp_n * spp_n)) return s;
+    if (rls_status s = check_shadow_queue(name, q, nwd, n, io.nl, spp_n * spp_n)) return s;
     RLS_REQUIRE_IN(name, visibility.r && visibility.g && visibility.b, "visibility plane is NULL");
     for (int l = 0; l < io.nl; l++)
         for (int k = 0; k < 3; k++) io.rad[l][k] = lt[l].radiance[k];
@@ -1607,7 +1972,7 @@ rls_status shadow_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c,
         RLS_REQUIRE_IN(name, rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
         io.materials = c->materials; io.sh = *sh;
     }
-    if (rls_status s = shadow_resolve_io(name, io, n, ggx, lights, n_lights, spp_n, q, visibility)) return s;
+    if (rls_status s = shadow_resolve_io(name, io, n, ggx ? 1 : 3, lights, n_lights, spp_n, q, visibility)) return s;
     RLS_REQUIRE_IN(name, rlsh::has3(direct_diffuse) && rlsh::has3(direct_specular), "NULL output plane");
     io.dd = direct_diffuse; io.ds = direct_specular;
     const dim3 grid = rlsh::grid_for(ctx, n);
@@ -1768,7 +2133,7 @@ rls_status rls_trace_ggx_direct_emit(rls_context *ctx, int64_t n, const rls_ggx_
         io.c = *c; io.sh = *sh; io.P = P;
         return RLS_OK;
     };
-    return shadow_emit<GgxShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, q, true, fn,
+    return shadow_emit<GgxShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, q, 1, fn,
                                         dispatch_ggx_direct_emit);
 }
 
@@ -1782,7 +2147,7 @@ rls_status rls_trace_disney_direct_emit(rls_context *ctx, int64_t n, const rls_d
         io.c = *c; io.P = P;
         return RLS_OK;
     };
-    return shadow_emit<DisneyShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, q, false, fn,
+    return shadow_emit<DisneyShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, q, 3, fn,
                                            dispatch_disney_direct_emit);
 }
 
@@ -1824,7 +2189,7 @@ rls_status rls_trace_ggx_shade_emit(rls_context *ctx, int64_t n, const rls_ggx_c
             return RLS_OK;
         };
         if (rls_status s = shadow_emit<GgxShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, q->shadow,
-                                                        true, fn, dispatch_ggx_direct_emit)) return s;
+                                                        1, fn, dispatch_ggx_direct_emit)) return s;
     }
     if (n == 0) {
         for (int k = 0; k < 3; k++)
@@ -1862,7 +2227,7 @@ rls_status rls_trace_ggx_shade_resolve(rls_context *ctx, int64_t n, const rls_gg
     RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
     GgxNodeResolveIO io = {};
     if (n_lights > 0)
-        if (rls_status s = shadow_resolve_io(fn, io.s, n, true, lights, n_lights, spp_n, q->shadow, t->visibility)) return s;
+        if (rls_status s = shadow_resolve_io(fn, io.s, n, 1, lights, n_lights, spp_n, q->shadow, t->visibility)) return s;
     io.s.materials = c->materials; io.s.sh = *sh; io.s.n = n;
     io.s.dd = out->direct_diffuse; io.s.ds = out->direct_specular;
     if (rls_status s = node_ray_io(fn, io.glossy, q->glossy, 3, n, spp_n, t->glossy, out->indirect_specular)) return s;
@@ -1904,7 +2269,7 @@ rls_status rls_trace_disney_shade_emit(rls_context *ctx, int64_t n, const rls_di
             return RLS_OK;
         };
         if (rls_status s = shadow_emit<DisneyShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, q->shadow,
-                                                           false, fn, dispatch_disney_direct_emit)) return s;
+                                                           3, fn, dispatch_disney_direct_emit)) return s;
     }
     if (n == 0) {
         if (rls_status s = empty_queue(ctx, q->diffuse->offsets, fn)) return s;
@@ -1932,7 +2297,7 @@ rls_status rls_trace_disney_shade_resolve(rls_context *ctx, int64_t n, const rls
     RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
     DisneyNodeResolveIO io = {};
     if (n_lights > 0)
-        if (rls_status s = shadow_resolve_io(fn, io.s, n, false, lights, n_lights, spp_n, q->shadow, t->visibility)) return s;
+        if (rls_status s = shadow_resolve_io(fn, io.s, n, 3, lights, n_lights, spp_n, q->shadow, t->visibility)) return s;
     io.s.n = n; io.s.dd = out->direct_diffuse; io.s.ds = out->direct_specular;
     if (rls_status s = node_ray_io(fn, io.diffuse, q->diffuse, 3, n, spp_n, t->diffuse, out->indirect_diffuse)) return s;
     if (rls_status s = node_ray_io(fn, io.specular, q->specular, 3, n, spp_n, t->specular, out->indirect_specular)) return s;
@@ -1950,6 +2315,123 @@ rls_status rls_trace_disney_shade_resolve(rls_context *ctx, int64_t n, const rls
     }
     hipLaunchKernelGGL(disney_node_resolve_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, io);
     return rlsh::check_launch(fn);
+}
+
+// What both rlSkin verbs check first, in check_node's style: the batch, the queue struct and its members, the light count, and
+// the two shadow queues present exactly where there are lights
+static rls_status check_skin_node(const char *fn, const rls_context *ctx, int64_t n, int spp_n, const rls_sphere_light *lights,
+                                  int n_lights, const rls_skin_node_queues *q)
+{
+    if (rls_status s = check_batch(fn, ctx, n, spp_n)) return s;
+    RLS_REQUIRE_IN(fn, q != nullptr, "queues is NULL");
+    RLS_REQUIRE_IN(fn, n_lights >= 0 && n_lights <= RLS_MAX_LIGHTS, "n_lights out of range (RLS_MAX_LIGHTS)");
+    RLS_REQUIRE_IN(fn, n_lights == 0 || lights != nullptr, "lights is NULL");
+    RLS_REQUIRE_IN(fn, n_lights > 0 || (q->sheen_shadow == nullptr && q->specular_shadow == nullptr),
+                   "queues.sheen_shadow or queues.specular_shadow is set but n_lights is 0");
+    RLS_REQUIRE_IN(fn, n_lights == 0 || (q->sheen_shadow != nullptr && q->specular_shadow != nullptr),
+                   "queues.sheen_shadow or queues.specular_shadow is NULL but n_lights > 0");
+    RLS_REQUIRE_IN(fn, q->sheen_glossy != nullptr && q->specular_glossy != nullptr && q->probes != nullptr,
+                   "queues.sheen_glossy, queues.specular_glossy or queues.probes is NULL");
+    RLS_REQUIRE_IN(fn, q->sheenFresnel != nullptr && q->specularFresnel != nullptr && q->sssWeight != nullptr,
+                   "queues.sheenFresnel, queues.specularFresnel or queues.sssWeight is NULL");
+    RLS_REQUIRE_IN(fn, q->sheen_glossy->offsets != nullptr && q->specular_glossy->offsets != nullptr && q->probes->offsets != nullptr &&
+                   (n_lights == 0 || (q->sheen_shadow->offsets != nullptr && q->specular_shadow->offsets != nullptr)),
+                   "queue.offsets is NULL");
+    return RLS_OK;
+}
+
+rls_status rls_trace_skin_emit(rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
+                               const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                               uint64_t first_index, const rls_skin_node_queues *q)
+{
+    const char *fn = __func__;
+    if (rls_status s = check_skin_node(fn, ctx, n, spp_n, lights, n_lights, q)) return s;
+    const rls_shadow_queue *const sq[2] = { q->sheen_shadow, q->specular_shadow };
+    const rls_ray_queue *const gq[2] = { q->sheen_glossy, q->specular_glossy };
+    float *const fresnel[2] = { q->sheenFresnel, q->specularFresnel };
+    const int spp = spp_n * spp_n;
+    if (n == 0) {
+        for (int k = 0; k < 2; k++) {
+            if (n_lights > 0)
+                if (rls_status s = empty_queue(ctx, sq[k]->offsets, fn)) return s;
+            if (rls_status s = empty_queue(ctx, gq[k]->offsets, fn)) return s;
+        }
+        return empty_queue(ctx, q->probes->offsets, fn);
+    }
+    if (rls_status s = rlsh::check_closure(fn, c, &P)) return s;
+    for (int k = 0; k < 2; k++)
+        if (rls_status s = check_ray_queue(fn, gq[k], 3, n, spp_n)) return s;
+    RLS_REQUIRE(rlsh::has3(q->probes->origin) && rlsh::has3(q->probes->dir) && q->probes->maxdist != nullptr,
+                "queue.origin, queue.dir or queue.maxdist plane is NULL");
+    RLS_REQUIRE(q->probes->capacity >= n * spp, "queue.capacity < n * spp_n^2");
+    for (int k = 0; k < 2 && n_lights > 0; k++) {                // (ahead of the first launch: a refused call writes nothing)
+        if (rls_status s = check_shadow_queue(fn, sq[k], 0, n, n_lights, spp)) return s;
+        RLS_REQUIRE(sq[k]->scratch != nullptr &&
+                    sq[k]->scratch_bytes >= staging(nullptr, n, shadow_slots(0, n_lights, spp), shadow_planes(0), sizeof(uint32_t)).bytes,
+                    "queue.scratch is NULL or smaller than rls_trace_shadow_scratch_bytes");
+    }
+    // per lobe: the light loop, which leaves its Fresnel (sum, count) in (the lobe's Fresnel plane, sssWeight); integrateGlossy,
+    // which folds on from there and writes the lobe's hand-down into its Fresnel plane
+    for (int k = 0; k < 2; k++) {
+        if (n_lights > 0) {
+            auto closure = [&](SkinShadowEmitIO &io) -> rls_status {
+                io.c = *c; io.P = P; io.lobe = k; io.fsum = fresnel[k]; io.fcnt = q->sssWeight;
+                return RLS_OK;
+            };
+            if (rls_status s = shadow_emit<SkinShadowEmitIO>(ctx, n, closure, lights, n_lights, spp_n, seed, first_index, sq[k], 0,
+                                                             fn, dispatch_skin_shadow_emit)) return s;
+        }
+        SkinGlossyEmitIO io = {};
+        io.c = *c;
+        if (n_lights > 0) { io.fsum = fresnel[k]; io.fcnt = q->sssWeight; }
+        if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, gq[k], fresnel[k], 3, fn,
+                                        k == 0 ? dispatch_skin_sheen_glossy_emit : dispatch_skin_specular_glossy_emit)) return s;
+    }
+    // integrateScatter's probe rays; sssWeight from the two hand-downs
+    SkinProbeEmitIO io = {};
+    io.c = *c; io.P = P; io.q = *q->probes;
+    io.sheenFresnel = q->sheenFresnel; io.specularFresnel = q->specularFresnel; io.sssWeight = q->sssWeight;
+    set_loop(io, n, spp_n, seed, first_index);
+    io.tile_points = sss_emit_tile_points(spp);
+    return dispatch_skin_probe_emit(ctx, 0, io, fn);
+}
+
+rls_status rls_trace_skin_resolve(rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
+                                  const rls_sphere_light *lights, int n_lights, int use_cavity_fade, int literal_matrix,
+                                  int spp_n, const rls_skin_node_queues *q, const rls_skin_node_traced *t,
+                                  const rls_skin_integrate_out *out)
+{
+    const char *fn = __func__;
+    if (rls_status s = check_skin_node(fn, ctx, n, spp_n, lights, n_lights, q)) return s;
+    RLS_REQUIRE(t != nullptr && out != nullptr, "traced or out is NULL");
+    RLS_REQUIRE(t->hits != nullptr, "traced.hits is NULL");
+    RLS_REQUIRE(t->hits->max_hits >= 1 && t->hits->max_hits <= RLS_MAX_PROBE_HITS, "hits.max_hits must be in [1, 12]");
+    if (n == 0) return RLS_OK;
+    const int spp = spp_n * spp_n;
+    if (rls_status s = rlsh::check_closure(fn, c, &P)) return s;
+    RLS_REQUIRE(rlsh::has3(out->sheen) && rlsh::has3(out->specular) && rlsh::has3(out->sss), "NULL AOV plane");
+    RLS_REQUIRE(rlsh::has3(out->out) || (!out->out.r && !out->out.g && !out->out.b), "out planes must be all set or all NULL");
+    SkinNodeResolveIO io = {};
+    if (n_lights > 0) {
+        if (rls_status s = shadow_resolve_io(fn, io.sheen_s, n, 0, lights, n_lights, spp_n, q->sheen_shadow, t->sheen_visibility))
+            return s;
+        if (rls_status s = shadow_resolve_io(fn, io.spec_s, n, 0, lights, n_lights, spp_n, q->specular_shadow, t->specular_visibility))
+            return s;
+    }
+    io.sheen_s.n = n; io.spec_s.n = n;
+    if (rls_status s = node_ray_io(fn, io.sheen_g, q->sheen_glossy, 3, n, spp_n, t->sheen_glossy, out->sheen)) return s;
+    if (rls_status s = node_ray_io(fn, io.spec_g, q->specular_glossy, 3, n, spp_n, t->specular_glossy, out->specular)) return s;
+    const rls_probe_hits *h = t->hits;
+    RLS_REQUIRE(q->probes->capacity >= n * spp, "queue.capacity < n * spp_n^2");
+    RLS_REQUIRE(h->stride >= n * spp, "hits.stride < n * spp_n^2");
+    RLS_REQUIRE(h->count != nullptr && rlsh::has3(h->P) && rlsh::has3(h->N) && h->irradiance.r && h->irradiance.g &&
+                h->irradiance.b, "hits.count, hits.P, hits.N or hits.irradiance plane is NULL");
+    io.c = *c; io.P = P; io.h = *h; io.o = *out;
+    io.sheenFresnel = q->sheenFresnel; io.specularFresnel = q->specularFresnel; io.sssWeight = q->sssWeight;
+    io.inv = 1.0f / (float)spp;                                  // as the loop kernels: 1 / spp
+    io.spp = spp; io.tile_points = sss_resolve_tile_points(spp);
+    io.cavity = use_cavity_fade != 0; io.literal = literal_matrix != 0; io.n = n;
+    return dispatch_skin_node_resolve(ctx, 0, io, fn);
 }
 
 } // extern "C"

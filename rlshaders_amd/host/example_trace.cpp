@@ -3,11 +3,12 @@
 // sky on the host, resolve; emit rlSss's probe rays, walk them through each point's tangent plane on the host, resolve;
 // emit the shadow rays of both nodes' light loops under two lights, shadow the second light with a half-space, resolve;
 // emit every queue of the two whole nodes, shadow the second light with the same half-space and light the ray queues with the
-// sky, resolve the AOVs in one call.
+// sky, resolve the AOVs in one call; emit the five queues of the rlSkin node, leave its lights unoccluded, light its glossy
+// rays uniformly, walk its probe rays through each point's tangent plane, resolve the AOVs in one call.
 //
 //   example_trace [points] [spp_n]
 // prints one JSON line: the ray counts and a checksum (FNV-1a over the bits of the resolved planes) per integrator, which
-// tests/test_gpu_trace_host_cpp.py (the light loops: tests/test_gpu_trace_lights_host_cpp.py; the whole nodes: tests/test_gpu_trace_shade_host_cpp.py) compares with the Python path (rlshaders_amd/trace.py) on the same inputs.
+// tests/test_gpu_trace_host_cpp.py (the light loops: tests/test_gpu_trace_lights_host_cpp.py; the whole nodes: tests/test_gpu_trace_shade_host_cpp.py, tests/test_gpu_trace_skin_host_cpp.py) compares with the Python path (rlshaders_amd/trace.py) on the same inputs.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -273,6 +274,94 @@ int main(int argc, char **argv)
                 rlsb::resolveNode(dev, lights, 2, nq, vis, Ld, Ls, aovs, &out);
                 report("disney_node", rays, 3, blocked, aovs, out);
             }
+        }
+        {
+            // The rlSkin node on the same frame, every shading point at the origin of its own tangent plane, the two lights of
+            // the sections above unoccluded (visibility 1), a uniform radiance on every glossy ray, and the probe walk of the
+            // rlSss section: the one hit of a probe ray on the point's tangent plane, E = 1 / pi.
+            rls_sphere_light lights[2] = {};
+            const float centers[2][3] = {{-4.0f, 2.0f, 3.0f}, {6.0f, 1.0f, 2.0f}};
+            const float radiances[2][3] = {{3.0f, 2.0f, 1.0f}, {1.0f, 4.0f, 2.0f}};
+            for (int l = 0; l < 2; l++) {
+                for (int k = 0; k < 3; k++) { lights[l].center[k] = centers[l][k]; lights[l].radiance[k] = radiances[l][k]; }
+                lights[l].radius = 1.0f;
+                lights[l].mis_mode = RLS_MIS_BOTH;
+            }
+            rls_skin_closure kc = {};
+            kc.wo = c.wo; kc.N = c.N; kc.T = c.T;
+            kc.sss_color = rlsb::ParamRGB(0.8f, 0.5f, 0.3f).c();
+            kc.sss_weight = rls_param{nullptr, 0.9f};
+            kc.sss_dist_multiplier = rls_param{nullptr, 0.5f};
+            kc.sss_scatter_dist[0] = rls_param{nullptr, 0.1f};
+            kc.sss_scatter_dist[1] = rls_param{nullptr, 0.2f};
+            kc.sss_scatter_dist[2] = rls_param{nullptr, 0.4f};
+            kc.specular_color = rlsb::ParamRGB(0.9f, 0.95f, 1.0f).c();
+            kc.specular_weight = rls_param{nullptr, 0.6f};
+            kc.specular_roughness = rls_param{nullptr, 0.5f};
+            kc.specular_ior = rls_param{nullptr, 1.44f};
+            kc.sheen_color = rlsb::ParamRGB(1.0f, 0.9f, 0.8f).c();
+            kc.sheen_weight = rls_param{nullptr, 0.3f};
+            kc.sheen_roughness = rls_param{nullptr, 0.35f};
+            kc.sheen_ior = rls_param{nullptr, 1.3f};
+            rlsb::Planes P(dev, std::vector<float>((size_t)(3 * n), 0.0f), 3);
+            rlsb::SkinNodeQueues nq(dev, n, 2, spp_n);
+            rlsb::emitNode(dev, kc, P, lights, 2, n, spp_n, kSeed, nq);
+            const int64_t rays[4] = {nq.sheenShadow()->count(), nq.specularShadow()->count(), nq.sheenGlossy().count(),
+                                     nq.specularGlossy().count()};
+            const int64_t scap = nq.sheenShadow()->c().capacity;
+            rlsb::Planes vis(dev, std::vector<float>((size_t)(3 * scap), 1.0f), 3);
+            const float env[3] = {0.7f, 0.8f, 0.9f};
+            std::vector<float> L((size_t)(3 * cap));
+            for (int k = 0; k < 3; k++) std::fill(L.begin() + (size_t)(k * cap), L.begin() + (size_t)((k + 1) * cap), env[k]);
+            rlsb::Planes radiance(dev, L, 3);
+            const rls_probe_queue &pq = nq.probes().c();
+            const int spp = spp_n * spp_n;
+            std::vector<float> org((size_t)(3 * cap)), dir((size_t)(3 * cap)), md((size_t)cap), nrm((size_t)(3 * n));
+            for (int k = 0; k < 3; k++) {
+                rlsb::check(rls_copy_to_host(dev.ctx(), &org[(size_t)(k * cap)], (&pq.origin.x)[k], sizeof(float) * (size_t)cap));
+                rlsb::check(rls_copy_to_host(dev.ctx(), &dir[(size_t)(k * cap)], (&pq.dir.x)[k], sizeof(float) * (size_t)cap));
+                rlsb::check(rls_copy_to_host(dev.ctx(), &nrm[(size_t)(k * n)], (&c.N.x)[k], sizeof(float) * (size_t)n));
+            }
+            rlsb::check(rls_copy_to_host(dev.ctx(), md.data(), pq.maxdist, sizeof(float) * (size_t)cap));
+            std::vector<uint8_t> cnt((size_t)cap, 0);
+            std::vector<float> hits((size_t)(9 * cap), 0.0f);             // P, N, irradiance: 3 planes each, one hit slot
+            int64_t found = 0;
+            for (int64_t j = 0; j < cap; j++) {
+                const int64_t i = j / spp;
+                float dn = 0.0f, on = 0.0f;
+                for (int k = 0; k < 3; k++) {
+                    dn += nrm[(size_t)(k * n + i)] * dir[(size_t)(k * cap + j)];
+                    on += nrm[(size_t)(k * n + i)] * org[(size_t)(k * cap + j)];
+                }
+                const float t = dn != 0.0f ? -on / dn : 0.0f;
+                if (!(t > 0.0f && t <= md[(size_t)j])) continue;
+                cnt[(size_t)j] = 1;
+                found++;
+                for (int k = 0; k < 3; k++) {
+                    hits[(size_t)(k * cap + j)] = org[(size_t)(k * cap + j)] + dir[(size_t)(k * cap + j)] * t;
+                    hits[(size_t)((3 + k) * cap + j)] = nrm[(size_t)(k * n + i)];
+                    hits[(size_t)((6 + k) * cap + j)] = 0.318309886f;
+                }
+            }
+            rlsb::Planes hp(dev, hits, 9);
+            void *dcnt = nullptr;
+            rlsb::check(rls_device_alloc(dev.ctx(), (size_t)cap, &dcnt));
+            rlsb::check(rls_copy_to_device(dev.ctx(), dcnt, cnt.data(), (size_t)cap));
+            rls_probe_hits h = {};
+            h.max_hits = 1; h.stride = cap; h.count = static_cast<const uint8_t *>(dcnt);
+            h.P = hp.cvec3(0); h.N = hp.cvec3(3);
+            h.irradiance = rls_crgb{hp.plane(6), hp.plane(7), hp.plane(8)};
+            rlsb::Planes aovs(dev, n, 9), out(dev, n, 3);
+            rlsb::resolveNode(dev, kc, P, lights, 2, nq, vis, vis, radiance, radiance, h, true, false, aovs, &out);
+            std::vector<float> ra = aovs.download(), ro = out.download(), sc = nq.scalars().download();
+            rls_device_free(dev.ctx(), dcnt);
+            double mean = 0.0;
+            for (float v : ro) mean += v;
+            std::printf(", \"skin_node\": {\"rays\": [%lld, %lld, %lld, %lld, %lld], \"hits\": %lld, \"aovs\": \"%016llx\", "
+                        "\"out\": \"%016llx\", \"scalars\": \"%016llx\", \"mean_out\": %.9g}",
+                        (long long)rays[0], (long long)rays[1], (long long)rays[2], (long long)rays[3], (long long)cap,
+                        (long long)found, (unsigned long long)fnv(ra), (unsigned long long)fnv(ro), (unsigned long long)fnv(sc),
+                        mean / (double)ro.size());
         }
         std::printf(", \"points\": %lld, \"spp_n\": %d}\n", (long long)n, spp_n);
     } catch (const rlsb::Error &e) {

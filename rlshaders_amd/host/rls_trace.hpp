@@ -222,15 +222,16 @@ inline void resolveScatter(const Device &d, const rls_sss_closure &c, const Plan
 }
 
 // The device buffers of one light-loop emit (rls_shadow_queue): per-ray planes for n * n_lights * 3 * spp_n^2 rays, offsets
-// [n + 1] and the emit's scratch.  Ggx: weight_diffuse is its .r plane alone.
+// [n + 1] and the emit's scratch.  Ggx: weight_diffuse is its .r plane alone.  Skin: a lobe's light loop of the rlSkin node --
+// no weight_diffuse, two rays a sample at most (n * n_lights * 2 * spp_n^2 rays).
 class ShadowQueue {
 public:
-    enum Node { Ggx, Disney };
+    enum Node { Ggx, Disney, Skin };
 
     ShadowQueue(const Device &d, int64_t n, int n_lights, int spp_n, Node node)
         : dev_(&d), n_(n), n_lights_(n_lights), spp_n_(spp_n), node_(node)
     {
-        const int64_t cap = n * n_lights * 3 * spp_n * spp_n;
+        const int64_t cap = n * n_lights * (node == Skin ? 2 : 3) * spp_n * spp_n;
         size_t scratch = 0;
         check(rls_trace_shadow_scratch_bytes(n, n_lights, spp_n, &scratch));
         try {
@@ -239,7 +240,7 @@ public:
             q_.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
             q_.maxdist = falloc(cap);
             q_.weight_specular = rls_rgb{falloc(cap), falloc(cap), falloc(cap)};
-            q_.weight_diffuse.r = falloc(cap);
+            if (node != Skin) q_.weight_diffuse.r = falloc(cap);
             if (node == Disney) { q_.weight_diffuse.g = falloc(cap); q_.weight_diffuse.b = falloc(cap); }
             q_.kind = static_cast<uint8_t *>(alloc((size_t)cap));
             q_.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
@@ -402,6 +403,47 @@ private:
     rls_disney_node_queues q_{};
 };
 
+// rls_skin_node_queues: per GGX lobe the light loop's shadow queue (none with n_lights == 0) and integrateGlossy's queue,
+// integrateScatter's probe queue, and the three hand-down scalars (n floats each), which the emit writes and the resolve reads
+class SkinNodeQueues {
+public:
+    SkinNodeQueues(const Device &d, int64_t n, int n_lights, int spp_n)
+        : n_(n), n_lights_(n_lights), spp_n_(spp_n),
+          sheen_shadow_(n_lights > 0 ? new ShadowQueue(d, n, n_lights, spp_n, ShadowQueue::Skin) : nullptr),
+          specular_shadow_(n_lights > 0 ? new ShadowQueue(d, n, n_lights, spp_n, ShadowQueue::Skin) : nullptr),
+          sheen_glossy_(d, n, spp_n, RayQueue::Glossy), specular_glossy_(d, n, spp_n, RayQueue::Glossy), probes_(d, n, spp_n),
+          scalars_(d, n, 3)
+    {
+        q_.sheen_shadow = sheen_shadow_ ? &sheen_shadow_->c() : nullptr;
+        q_.specular_shadow = specular_shadow_ ? &specular_shadow_->c() : nullptr;
+        q_.sheen_glossy = &sheen_glossy_.c(); q_.specular_glossy = &specular_glossy_.c(); q_.probes = &probes_.c();
+        q_.sheenFresnel = scalars_.plane(0); q_.specularFresnel = scalars_.plane(1); q_.sssWeight = scalars_.plane(2);
+    }
+    ~SkinNodeQueues() { delete sheen_shadow_; delete specular_shadow_; }
+    SkinNodeQueues(const SkinNodeQueues &) = delete;
+    SkinNodeQueues &operator=(const SkinNodeQueues &) = delete;
+
+    const rls_skin_node_queues &c() const { return q_; }
+    const ShadowQueue *sheenShadow() const { return sheen_shadow_; }          // nullptr without lights
+    const ShadowQueue *specularShadow() const { return specular_shadow_; }
+    const RayQueue &sheenGlossy() const { return sheen_glossy_; }
+    const RayQueue &specularGlossy() const { return specular_glossy_; }
+    const ProbeQueue &probes() const { return probes_; }
+    const Planes &scalars() const { return scalars_; }            // sheenFresnel, specularFresnel, sssWeight
+    int64_t points() const { return n_; }
+    int lights() const { return n_lights_; }
+    int sppN() const { return spp_n_; }
+
+private:
+    int64_t n_;
+    int n_lights_, spp_n_;
+    ShadowQueue *sheen_shadow_, *specular_shadow_;
+    RayQueue sheen_glossy_, specular_glossy_;
+    ProbeQueue probes_;
+    Planes scalars_;
+    rls_skin_node_queues q_{};
+};
+
 namespace detail {
 inline rls_crgb crgb(const Planes &p) { return p.empty() ? rls_crgb{nullptr, nullptr, nullptr} : rls_crgb{p.plane(0), p.plane(1), p.plane(2)}; }
 template <class Q>
@@ -459,6 +501,34 @@ inline void resolveNode(const Device &d, const rls_sphere_light *lights, int n_l
     o.indirect_specular = aovs.rgb(9);
     if (out) o.out = out->rgb();
     check(rls_trace_disney_shade_resolve(d.ctx(), q.points(), lights, n_lights, q.sppN(), &q.c(), &t, &o));
+}
+
+// every ray of rlSkin's shader_evaluate as rls_skin_integrate samples it (rls_trace_skin_emit): the arguments of
+// rls_skin_integrate without scene and env
+inline void emitNode(const Device &d, const rls_skin_closure &c, const Planes &P, const rls_sphere_light *lights, int n_lights,
+                     int64_t n, int spp_n, uint32_t seed, SkinNodeQueues &q, uint64_t first_index = 0)
+{
+    detail::checkNodeQueues(q, n, n_lights, spp_n, "emitNode: queues of another size or light count");
+    check(rls_trace_skin_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n, seed,
+                              first_index, &q.c()));
+}
+
+// rls_skin_integrate's AOVs from what the renderer traced.  The visibilities (empty Planes without lights) and the radiances:
+// 3 planes of >= the queue's count floats each; hits: as resolveScatter takes them.  aovs: 9 planes of n floats -- sheen,
+// specular, sss; out: sg->out.RGB, 3 planes of n floats, or nullptr
+inline void resolveNode(const Device &d, const rls_skin_closure &c, const Planes &P, const rls_sphere_light *lights, int n_lights,
+                        const SkinNodeQueues &q, const Planes &sheenVisibility, const Planes &specularVisibility,
+                        const Planes &sheenGlossy, const Planes &specularGlossy, const rls_probe_hits &hits, bool cavityFade,
+                        bool literalMatrix, Planes &aovs, Planes *out = nullptr)
+{
+    detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveNode: queues of another light count");
+    rls_skin_node_traced t = {detail::crgb(sheenVisibility), detail::crgb(specularVisibility), detail::crgb(sheenGlossy),
+                              detail::crgb(specularGlossy), &hits};
+    rls_skin_integrate_out o = {};
+    o.sheen = aovs.rgb(0); o.specular = aovs.rgb(3); o.sss = aovs.rgb(6);
+    if (out) o.out = out->rgb();
+    check(rls_trace_skin_resolve(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights,
+                                 cavityFade ? 1 : 0, literalMatrix ? 1 : 0, q.sppN(), &q.c(), &t, &o));
 }
 
 } // namespace rlsb

@@ -21,6 +21,9 @@ or of one rlDisney lobe, trace them with your own tracer, resolve the radiance; 
     nq = trace.ggx_node_rays(sampler, shader, P, lights, 4, 7)   # GgxNodeQueues: the whole node's rays, nq.shadow, nq.glossy,
     aov = nq.resolve(vis, Lg, Lt, Ld)                            # nq.refract, nq.diffuse -> rls_ggx_shade's dict, traced
 
+    sq = trace.skin_node_rays(skin, P, lights, 4, 7)             # SkinNodeQueues: sheen_shadow, specular_shadow, sheen_glossy,
+    aov = sq.resolve(vis_a, vis_b, La, Lb, cnt, hP, hN, E)       # specular_glossy, probes -> SkinShader.integrate's dict, traced
+
 ``count`` is read from the device once (it synchronises); everything else stays asynchronous on the context's stream, so
 ``glossy_rays(..., queue=q)`` / ``q.resolve(L, out=...)`` with preallocated tensors can be recorded by ``ctx.capture()``.
 """
@@ -104,6 +107,18 @@ class DisneyNodeTraced_(C.Structure):
     _fields_ = [("visibility", capi.CRgb), ("diffuse", capi.CRgb), ("specular", capi.CRgb)]
 
 
+class SkinNodeQueues_(C.Structure):
+    """rls_skin_node_queues"""
+    _fields_ = [("sheen_shadow", _sq), ("specular_shadow", _sq), ("sheen_glossy", _q), ("specular_glossy", _q), ("probes", _pq),
+                ("sheenFresnel", C.c_void_p), ("specularFresnel", C.c_void_p), ("sssWeight", C.c_void_p)]
+
+
+class SkinNodeTraced_(C.Structure):
+    """rls_skin_node_traced"""
+    _fields_ = [("sheen_visibility", capi.CRgb), ("specular_visibility", capi.CRgb), ("sheen_glossy", capi.CRgb),
+                ("specular_glossy", capi.CRgb), ("hits", C.POINTER(ProbeHits_))]
+
+
 PROTOTYPES = {
     "rls_trace_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
     "rls_trace_ggx_glossy_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
@@ -134,6 +149,11 @@ PROTOTYPES = {
                                               C.c_int, C.c_uint32, C.c_uint64, C.POINTER(DisneyNodeQueues_)]),
     "rls_trace_disney_shade_resolve": (C.c_int, [_ctx, _i64, _lights, C.c_int, C.c_int, C.POINTER(DisneyNodeQueues_),
                                                  C.POINTER(DisneyNodeTraced_), C.POINTER(capi.DisneyShadeOut)]),
+    "rls_trace_skin_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.SkinClosure), capi.CVec3, _lights, C.c_int, C.c_int, C.c_uint32,
+                                      C.c_uint64, C.POINTER(SkinNodeQueues_)]),
+    "rls_trace_skin_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.SkinClosure), capi.CVec3, _lights, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.POINTER(SkinNodeQueues_), C.POINTER(SkinNodeTraced_),
+                                         C.POINTER(capi.SkinIntegrateOut)]),
 }
 
 _lib = None
@@ -422,18 +442,25 @@ class ShadowQueue:
     """The shadow rays of one light-loop emit over n points under n_lights lights at spp_n^2 samples (rls_shadow_queue):
     point-major CSR; within a point lights ascending, within a light the light-strategy samples, then the BSDF diffuse-lobe
     samples, then the BSDF specular-lobe samples.  Planes are allocated for the full capacity n * n_lights * 3 * spp_n^2; the
-    properties view the first ``count`` rays.  ``disney``: an rlDisney queue (three planes of weight_diffuse; rlGgx has one)."""
+    properties view the first ``count`` rays.  ``disney``: an rlDisney queue (three planes of weight_diffuse; rlGgx has one).
+    ``skin``: a lobe's light loop of the rlSkin node: no weight_diffuse, two rays a sample at most (capacity n * n_lights * 2 *
+    spp_n^2), within a light the samples ascending and a sample's light-strategy ray before its BSDF-strategy ray; resolved by
+    ``SkinNodeQueues.resolve``."""
 
-    def __init__(self, ctx, n: int, n_lights: int, spp_n: int, disney: bool = False, scratch: Optional[torch.Tensor] = None):
+    def __init__(self, ctx, n: int, n_lights: int, spp_n: int, disney: bool = False, scratch: Optional[torch.Tensor] = None,
+                 skin: bool = False):
         self.ctx, self.n, self.n_lights, self.spp_n, self.disney = ctx, int(n), int(n_lights), int(spp_n), bool(disney)
+        self.skin = bool(skin)
+        if self.skin and self.disney:
+            raise ValueError("skin and disney exclude each other")
         dev = ctx.torch_device
-        cap = self.n * self.n_lights * 3 * self.spp_n * self.spp_n
+        cap = self.n * self.n_lights * (2 if skin else 3) * self.spp_n * self.spp_n
         self.capacity = cap
         self.offsets = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
         self._dir = torch.empty(3, cap, dtype=torch.float32, device=dev)
         self._maxdist = torch.empty(cap, dtype=torch.float32, device=dev)
         self._ws = torch.empty(3, cap, dtype=torch.float32, device=dev)
-        self._wd = torch.empty(3 if disney else 1, cap, dtype=torch.float32, device=dev)
+        self._wd = torch.empty(0 if skin else 3 if disney else 1, cap, dtype=torch.float32, device=dev)
         self._kind = torch.empty(cap, dtype=torch.uint8, device=dev)
         self._point = torch.empty(cap, dtype=torch.int32, device=dev)          # uint32 on the device; n < 2^31 here
         self._sample = torch.empty(cap, dtype=torch.uint8, device=dev)
@@ -446,7 +473,8 @@ class ShadowQueue:
         q.maxdist = self._maxdist.data_ptr()
         q.weight_specular = capi.Rgb(*[self._ws[k].data_ptr() for k in range(3)])
         wd = self._wd
-        q.weight_diffuse = capi.Rgb(wd[0].data_ptr(), wd[1].data_ptr() if disney else None, wd[2].data_ptr() if disney else None)
+        q.weight_diffuse = capi.Rgb(None if skin else wd[0].data_ptr(), wd[1].data_ptr() if disney else None,
+                                    wd[2].data_ptr() if disney else None)
         q.kind, q.point, q.sample = self._kind.data_ptr(), self._point.data_ptr(), self._sample.data_ptr()
         q.scratch, q.scratch_bytes = self._scratch.data_ptr(), self._scratch.numel()
         self.q = q
@@ -494,6 +522,8 @@ class ShadowQueue:
         """visibility [3, >= count] float32, one per ray and channel (1 unoccluded, 0 blocked) ->
         (direct_diffuse [3, n], direct_specular [3, n]): with visibility 1 the AOVs of rls_ggx_direct_lighting /
         rls_disney_direct_lighting.  ``count``: the ray count when the caller knows it (skips the read of offsets[n])."""
+        if self.skin:
+            raise RuntimeError("resolve: a lobe's shadow queue of the rlSkin node is resolved by SkinNodeQueues.resolve")
         if self.lights is None:
             raise RuntimeError("resolve: no emit has filled this queue (trace.ggx_shadow_rays / disney_shadow_rays)")
         ctx, n = self.ctx, self.n
@@ -581,13 +611,18 @@ class _NodeQueues:
             scratch = torch.empty(max(node_scratch_bytes(self.n, self.n_lights, self.spp_n), 1), dtype=torch.uint8,
                                   device=ctx.torch_device)
         self.scratch = scratch
-        self.shadow = ShadowQueue(ctx, n, n_lights, spp_n, self.disney, scratch=scratch) if self.n_lights > 0 else None
+        self._make_shadow_queues(scratch)
         for name, kw in self.RAY_MEMBERS:
             setattr(self, name, RayQueue(ctx, n, spp_n, scratch=scratch, **kw))
         self.lights = None
         self.sampler = None
         self.shader = None
         self.traced = True
+
+    def _make_shadow_queues(self, scratch):
+        """the node's light loop(s): one queue, ``shadow`` (None without lights)"""
+        self.shadow = ShadowQueue(self.ctx, self.n, self.n_lights, self.spp_n, self.disney, scratch=scratch) \
+            if self.n_lights > 0 else None
 
     def _struct(self, cls):
         q = cls()
@@ -708,4 +743,117 @@ def disney_node_rays(sampler: DisneySampler, P: torch.Tensor, lights, spp_n: int
     q.lights, q.sampler, q.P = (la, nl), sampler, P
     if q.shadow is not None:
         q.shadow.lights, q.shadow.sampler, q.shadow.P = (la, nl), sampler, P
+    return q
+
+
+class SkinNodeQueues(_NodeQueues):
+    """The rays of the whole rlSkin node (rls_trace_skin_emit): per GGX lobe a ShadowQueue of the lobe's light loop
+    (``sheen_shadow``, ``specular_shadow``; None without lights; specular terms only, two rays a sample at most: capacity
+    n * n_lights * 2 * spp_n^2) and a RayQueue of its integrateGlossy (``sheen_glossy``, ``specular_glossy``), and the ProbeQueue
+    of integrateScatter (``probes``) -- the samples ``SkinShader.integrate`` draws.  ``sheenFresnel``, ``specularFresnel``,
+    ``sssWeight`` [n]: the layers' hand-down scalars, written by the emit."""
+    RAY_MEMBERS = (("sheen_glossy", {}), ("specular_glossy", {}))
+    RAYS = ("sheen_glossy", "specular_glossy")
+    SHADOWS = ("sheen_shadow", "specular_shadow")
+
+    def _make_shadow_queues(self, scratch):
+        """a light loop per lobe"""
+        self.shadow = None
+        for name in self.SHADOWS:
+            setattr(self, name, ShadowQueue(self.ctx, self.n, self.n_lights, self.spp_n, scratch=scratch, skin=True)
+                    if self.n_lights > 0 else None)
+
+    def __init__(self, ctx, n: int, n_lights: int, spp_n: int, share_scratch: bool = False):
+        super().__init__(ctx, n, n_lights, spp_n, share_scratch)
+        self.probes = ProbeQueue(ctx, n, spp_n)
+        self.sheenFresnel, self.specularFresnel, self.sssWeight = (torch.empty(self.n, dtype=torch.float32,
+                                                                               device=ctx.torch_device) for _ in range(3))
+        self.P = None
+
+    def _struct(self, cls=None):
+        q = SkinNodeQueues_()
+        for name in self.SHADOWS:
+            sq = getattr(self, name)
+            setattr(q, name, C.pointer(sq.q) if sq is not None else None)
+        for name in self.RAYS:
+            setattr(q, name, C.pointer(getattr(self, name).q))
+        q.probes = C.pointer(self.probes.q)
+        q.sheenFresnel, q.specularFresnel, q.sssWeight = (t.data_ptr() for t in (self.sheenFresnel, self.specularFresnel,
+                                                                                 self.sssWeight))
+        return q
+
+    def counts(self) -> dict:
+        """the ray count of every compacted queue (reads the device: synchronises); the probe queue is dense"""
+        c = {name: (getattr(self, name).count if getattr(self, name) is not None else 0) for name in self.SHADOWS}
+        c.update({name: getattr(self, name).count for name in self.RAYS})
+        return c
+
+    def resolve(self, sheen_visibility, specular_visibility, sheen_glossy, specular_glossy, count, P, N, irradiance,
+                use_cavity_fade: bool = False, literal_matrix: bool = False, out=None, counts: Optional[dict] = None) -> dict:
+        """What the renderer traced -> the dict ``SkinShader.integrate`` returns: sheen, specular, sss, out [3, n] and
+        sheenFresnel, specularFresnel, sssWeight [n].  The visibilities and radiances are [3, >= count] float32 per queue (the
+        visibilities are not read without lights and may be None); count, P, N, irradiance are the probe hits as
+        ``ProbeQueue.resolve`` takes them.  ``counts``: the ray counts where the caller knows them (skips the reads of
+        offsets[n], e.g. while recording a graph)."""
+        if self.sampler is None:
+            raise RuntimeError("resolve: no emit has filled these queues (trace.skin_node_rays)")
+        ctx, n, rays = self.ctx, self.n, self.probes.count
+        cnt = self.counts() if counts is None else counts
+        t = SkinNodeTraced_()
+        if self.n_lights > 0:
+            t.sheen_visibility = _radiance(sheen_visibility, cnt["sheen_shadow"], "sheen_visibility")
+            t.specular_visibility = _radiance(specular_visibility, cnt["specular_shadow"], "specular_visibility")
+        t.sheen_glossy = _radiance(sheen_glossy, cnt["sheen_glossy"], "sheen_glossy")
+        t.specular_glossy = _radiance(specular_glossy, cnt["specular_glossy"], "specular_glossy")
+        if not isinstance(count, torch.Tensor) or count.dtype != torch.uint8 or not count.is_cuda or count.dim() != 1 or \
+                count.shape[0] < rays or not count.is_contiguous():
+            raise ValueError(f"count: expected a contiguous uint8 CUDA tensor [>= {rays}]")
+        shape = None
+        for what, h in (("P", P), ("N", N), ("irradiance", irradiance)):
+            if not isinstance(h, torch.Tensor) or h.dtype != torch.float32 or not h.is_cuda or h.dim() != 3 or \
+                    h.shape[0] != 3 or not 1 <= h.shape[1] <= RLS_MAX_PROBE_HITS or h.shape[2] < rays or \
+                    h.stride(2) != 1 or h.stride(1) != h.shape[2] or (shape is not None and h.shape != shape):
+                raise ValueError(f"{what}: expected a float32 CUDA tensor [3, 1..{RLS_MAX_PROBE_HITS}, >= {rays}] whose "
+                                 f"planes are contiguous, of one shape with the other hit planes")
+            shape = h.shape
+        hits = ProbeHits_()
+        hits.max_hits, hits.stride, hits.count = int(shape[1]), int(shape[2]), count.data_ptr()
+        hits.P = capi.CVec3(*[P[k].data_ptr() for k in range(3)])
+        hits.N = capi.CVec3(*[N[k].data_ptr() for k in range(3)])
+        hits.irradiance = capi.CRgb(*[irradiance[k].data_ptr() for k in range(3)])
+        t.hits = C.pointer(hits)
+        if out is None:
+            out = {k: ctx.empty(3, n) for k in ("sheen", "specular", "sss", "out")}
+            out.update({k: ctx.empty(n) for k in ("sheenFresnel", "specularFresnel", "sssWeight")})
+        o = capi.SkinIntegrateOut()
+        for k in ("sheen", "specular", "sss", "out"):
+            if k in out:
+                setattr(o, k, rgb(out[k], n, k))
+        for k in ("sheenFresnel", "specularFresnel", "sssWeight"):
+            if k in out:
+                setattr(o, k, plane(out[k], n, k))
+        la, nl = self.lights
+        q = self._struct()
+        check(load().rls_trace_skin_resolve(ctx.handle, n, C.byref(self.sampler.c), cvec3(self.P, n, "P") if n > 0 else
+                                            capi.CVec3(None, None, None), la, nl, 1 if use_cavity_fade else 0,
+                                            1 if literal_matrix else 0, self.spp_n, C.byref(q), C.byref(t), C.byref(o)))
+        return out
+
+
+def skin_node_rays(shader, P: torch.Tensor, lights, spp_n: int, seed: int, first_index: int = 0,
+                   queues: Optional[SkinNodeQueues] = None, share_scratch: bool = False) -> SkinNodeQueues:
+    """Every ray of rlSkin's shader_evaluate (src/rlSkin.cpp:174-254) as ``SkinShader.integrate`` samples it: per GGX lobe the
+    light loop's shadow rays and integrateGlossy's rays (stream pairs 0 and 1), then integrateScatter's probe rays (pair 2).
+    ``shader``: a ``SkinShader``; ``lights``: None, one ``make_light`` or a sequence; P: [3, n] float32, sg->P per point.
+    ``share_scratch``: the queues share one scratch block."""
+    ctx, n = shader.ctx, shader.n
+    la, nl = light_array(lights)
+    q = SkinNodeQueues(ctx, n, nl, spp_n, share_scratch) if queues is None else queues
+    if not q._matches(shader, nl, spp_n):
+        raise ValueError("queues: allocated for another batch size, light count or spp_n")
+    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
+    cq = q._struct()
+    check(load().rls_trace_skin_emit(ctx.handle, n, C.byref(shader.c), Pv, la, nl, int(spp_n), int(seed) & 0xFFFFFFFF,
+                                     int(first_index), C.byref(cq)))
+    q.lights, q.sampler, q.P = (la, nl), shader, P
     return q

@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss|ggx-lights|disney-lights|ggx-node|disney-node] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
+    python tools/trace_bench.py [--closure ggx|disney|sss|ggx-lights|disney-lights|ggx-node|disney-node|skin-node] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -28,6 +28,12 @@ light loop's share of it (the same kernels through the light-loop emit), the nod
 resolves on the same queues (the light-loop resolve plus one glossy / refraction resolve per ray queue: they write one sum
 per queue and leave the composition to the caller), and rls_ggx_shade / rls_disney_shade.  Uniform random radiance and
 visibility.  The queues share one scratch block.
+--closure skin-node: the rlSkin node (trace.skin_node_rays) with per-point parameters on the plane z = 0 (shading points in
+[0,4) x [0,4), the plane lit from +z) under --lights lights: the node emit (five queues, one call), the node resolve (one
+launch; uniform random visibility and radiance, the probe hits of the plane intersected with torch on the device),
+rls_skin_integrate on the same batch, and the existing stand-alone resolves that fit the node's queues -- one glossy resolve
+per lobe and the scatter resolve.  The lobes' shadow queues (one sum per light, no diffuse planes) have no stand-alone
+resolve, and there is no compose kernel for this node: `separate_partial_ms` is a LOWER bound on a separate-kernels path.
 """
 from __future__ import annotations
 
@@ -279,6 +285,75 @@ def bench_node(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
     }
 
 
+def bench_skin_node(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """the whole rlSkin node on the plane z = 0: emit, the one-launch resolve, the stand-alone resolves that exist, the analytic call"""
+    import math
+    import torch
+    import rlshaders_amd as R
+    from rlshaders_amd import trace as T
+    from rlshaders_amd.closures import make_light
+    nl = args.lights
+    dev = ctx.torch_device
+    lights = [make_light(center=c, radius=r, radiance=e) for c, r, e in LIGHT_SPECS[:nl]]
+    wo, _, _ = R.gen_frame(ctx, seed, 0, n)
+    wo[2] = wo[2].abs() + 0.05
+    wo = (wo / wo.norm(dim=0, keepdim=True)).contiguous()
+    u = lambda stream, lo=0.0, hi=1.0: R.gen_uniform(ctx, seed, 0, n, stream, lo, hi)
+    u3 = lambda stream, lo=0.0, hi=1.0: torch.stack([u(stream + k, lo, hi) for k in range(3)])
+    Ns = torch.zeros(3, n, device=dev)
+    Ns[2] = 1
+    ang = u(63, 0.0, 2 * math.pi)
+    Tg = torch.stack([torch.cos(ang), torch.sin(ang), torch.zeros_like(ang)]).contiguous()
+    P = torch.stack([u(60, 0.0, 4.0), u(61, 0.0, 4.0), torch.zeros(n, device=dev)]).contiguous()
+    dist, mult = u3(30, 0.02, 0.3), u(33, 0.5, 1.5)
+    p = dict(sss_color=u3(10), sss_weight=u(13, 0.2, 1.0), sss_dist_multiplier=mult, sss_scatter_dist=dist,
+             specular_color=u3(14), specular_weight=u(17, 0.1, 0.9), specular_roughness=u(18, 0.05, 1.0), specular_ior=u(19, 1.05, 2.0),
+             sheen_color=u3(20), sheen_weight=u(23, 0.1, 0.9), sheen_roughness=u(24, 0.05, 1.0), sheen_ior=u(25, 1.05, 2.0))
+    sk = R.SkinShader(ctx, wo, Ns, Tg, **p)
+    scene = R.make_scene("plane", light_dir=(0, 0, 1), light_color=(1.0, 1.0, 1.0))
+    keys3, keys1 = ("sheen", "specular", "sss", "out"), ("sheenFresnel", "specularFresnel", "sssWeight")
+    aov = {k: ctx.empty(3, n) for k in keys3}
+    aov.update({k: ctx.empty(n) for k in keys1})
+    ms_int = timed(lambda: sk.integrate(P, scene, spp_n, seed, env=(0.7, 0.8, 0.9), out=aov, lights=lights), args.repeats, args.warmup)
+    nq = T.SkinNodeQueues(ctx, n, nl, spp_n, share_scratch=True)
+    ms_emit = timed(lambda: T.skin_node_rays(sk, P, lights, spp_n, seed, queues=nq), args.repeats, args.warmup)
+    cnt = nq.counts()
+    O, D, md = nq.probes.origin, nq.probes.dir, nq.probes.maxdist
+    with torch.no_grad():
+        t = -O[2] / D[2]
+        ok = (D[2] != 0) & (t > 0) & (t <= md)
+        hP = (O + D * t).unsqueeze(1).contiguous()
+        hN = torch.zeros_like(hP)
+        hN[2] = 1
+        E = torch.full_like(hP, 1.0 / math.pi)
+        hc = ok.to(torch.uint8)
+    hits = int(hc.sum().item())
+    rnd = lambda k: torch.rand(3, max(cnt[k], 1), device=dev)
+    planes = [rnd("sheen_shadow"), rnd("specular_shadow"), rnd("sheen_glossy"), rnd("specular_glossy")]
+    res = {k: ctx.empty(3, n) for k in keys3}
+    res.update({k: ctx.empty(n) for k in keys1})
+    ms_res = timed(lambda: nq.resolve(*planes, hc, hP, hN, E, out=res, counts=cnt), args.repeats, args.warmup)
+    # the existing stand-alone resolves that fit: one glossy resolve per lobe, the scatter resolve
+    ss = R.SssSampler(ctx, Ns, Tg, p["sss_color"], dist, multiplier=mult)
+    nq.probes.sampler, nq.probes.P = ss, P
+    sums = [ctx.empty(3, n) for _ in range(3)]
+    parts = [lambda: nq.sheen_glossy.resolve(planes[2], out=sums[0], count=cnt["sheen_glossy"]),
+             lambda: nq.specular_glossy.resolve(planes[3], out=sums[1], count=cnt["specular_glossy"]),
+             lambda: nq.probes.resolve(hc, hP, hN, E, out=sums[2])]
+    ms_parts = [timed(f, args.repeats, args.warmup) for f in parts]
+    ms_sep = timed(lambda: [f() for f in parts], args.repeats, args.warmup)
+    rec["lights"] = nl
+    rec[args.closure] = {
+        "rays": dict(cnt, probes=nq.probes.count), "hits_per_probe": round(hits / max(nq.probes.count, 1), 4),
+        "analytic_ms": round(ms_int, 4), "emit_ms": round(ms_emit, 4), "node_resolve_ms": round(ms_res, 4),
+        "separate_partial_ms": round(ms_sep, 4),
+        "separate_partial_ms_each": dict(zip(("sheen_glossy", "specular_glossy", "scatter"), [round(m, 4) for m in ms_parts])),
+        "separate_partial_lacks": "the two lobes' light-loop sums and the composition: no stand-alone kernels exist for them",
+        "emit_over_analytic": round(ms_emit / ms_int, 4),
+        "emit_plus_resolve_over_analytic": round((ms_emit + ms_res) / ms_int, 4),
+    }
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=24)
@@ -286,7 +361,7 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
-    ap.add_argument("--closure", choices=("ggx", "disney", "sss", "ggx-lights", "disney-lights", "ggx-node", "disney-node"),
+    ap.add_argument("--closure", choices=("ggx", "disney", "sss", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node"),
                     default="ggx")
     ap.add_argument("--lights", type=int, default=2, help="the light loops: spherical lights, 1..8")
     args = ap.parse_args()
@@ -308,7 +383,8 @@ def main() -> None:
            "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
     if args.closure != "ggx":
         rec["closure"] = args.closure
-        {"disney": bench_disney, "sss": bench_sss, "ggx-node": bench_node, "disney-node": bench_node}.get(
+        {"disney": bench_disney, "sss": bench_sss, "ggx-node": bench_node, "disney-node": bench_node,
+         "skin-node": bench_skin_node}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
         print(json.dumps(rec), flush=True)
