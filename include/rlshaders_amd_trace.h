@@ -278,7 +278,8 @@ rls_status rls_trace_disney_direct_resolve(rls_context *ctx, int64_t n, const rl
  *             out = (direct_diffuse + direct_specular) + (indirect_diffuse + indirect_specular)
  * S is summed about a reference radiance, so that a uniform environment reproduces the analytic call: with Lref_c the
  * radiance of smallest magnitude among the point's rays (a property of the set of rays, not of their order), A = sum w and
- * B_c = sum (radiance_c - Lref_c) w, both grown in queue order,
+ * B_c = sum (radiance_c - Lref_c) w, both grown in queue order (a ray whose radiance_c IS Lref_c adds nothing to B_c, also
+ * where its weight is infinite),
  *             S_c = (A * inv) * Lref_c + B_c * inv
  * which in exact arithmetic is (sum radiance_c w) * inv; in float32 it is within (k + 3) 2^-24 inv (|Lref_c| sum |w| +
  * sum |radiance_c - Lref_c| |w|) of it for a point with k rays, and since |Lref_c| <= |radiance_c| on every ray, within

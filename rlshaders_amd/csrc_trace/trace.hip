@@ -1163,8 +1163,9 @@ __global__ __launch_bounds__(rlsh::kBlock) void trace_resolve_kernel(TraceResolv
 // smallest magnitude among the point's rays (the first such in queue order; a property of the set of rays, not of their order):
 //     A = sum w (in queue order: the analytic loop's sum),  B = sum (L - Lref) w,   S = (A inv) Lref + B inv
 // In exact arithmetic S = inv sum L w.  Where every ray of the point carries the same radiance env, every term of B is
-// exactly 0 and S = (A inv) env: what ggx_shade_kernel / disney_shade_kernel form from their sum and env (csrc/shade.hip),
-// for env = 1 and for any other.  Rounding: with k rays, |S - inv sum L w| <= (k + 3) 2^-24 inv (|Lref| sum |w| +
+// exactly 0 -- also where a weight is infinite: a term whose L - Lref is 0 is skipped, which changes no finite sum (B is never
+// -0) -- and S = (A inv) env: what ggx_shade_kernel / disney_shade_kernel form from their sum and env (csrc/shade.hip), for
+// env = 1 and for any other.  Rounding: with k rays, |S - inv sum L w| <= (k + 3) 2^-24 inv (|Lref| sum |w| +
 // sum |L - Lref| |w|); |Lref| <= |L| on every ray, so that is at most 3 (k + 3) 2^-24 inv sum |L| |w| (2 for radiances of one
 // sign): a bound relative to the sum of the terms' magnitudes, as the plain sum's, whatever single ray is bright.
 // Lref is found in a pass of its own over the lane's rays in global memory (they are read again, coalesced, by the tiles).
@@ -1204,7 +1205,11 @@ __device__ __forceinline__ void ray_sums_about_reference(float (*planes)[kResolv
             for (int c = 0; c < 3; c++) {
                 const float w = planes[3 + (NW == 3 ? c : 0)][k];
                 if (NW == 3 || c == 0) A[c] += w;
-                B[c] += (planes[c][k] - ref[c]) * w;
+                // (a ray AT the reference adds nothing, whatever its weight: 0 x inf would be NaN where the analytic sum is inf.
+                // That is all the skip guarantees -- the uniform radiance of the contract; under a non-uniform radiance an infinite
+                // weight may still meet Lref = 0 in (A inv) Lref and give NaN where the plain sum is inf)
+                const float d = planes[c][k] - ref[c];
+                B[c] += d == 0.0f ? 0.0f : d * w;
             }
         }
     }

@@ -18,7 +18,7 @@ import cases
 import rlshaders_amd as R
 from gpu_util import dev, disney_oracle, disney_sampler, ggx_oracle, ggx_sampler, host
 from test_gpu_loop_edges import LIGHTS, _lights, _sl, _slab, make_case
-from trace_lights_util import BSDF, DIFFUSE, LIGHT_MASK, SPECULAR, compose, cone, cone_hit, near_hit_f64, queue_host, segment
+from trace_lights_util import BSDF, DIFFUSE, LIGHT_MASK, SPECULAR, assert_float64_bound, compose, cone, cone_hit, near_hit_f64, queue_host, segment
 from trace_util import disney_inputs, ggx_inputs
 
 pytestmark = pytest.mark.gpu
@@ -266,6 +266,29 @@ def test_single_weights_against_the_analytic_loop(gpu, oracle, T, node):
         assert np.all(h["ws"][:, ~s] == 0) and np.all(h["wd"][:, ~d] == 0)
 
 
+def bsdf_directions_against_the_oracle(oracle, node, c, h, nl, spp_n, seed=SEED, first=0):
+    """the BSDF-strategy rays of the queue h (queue_host) of the points c under nl lights, per (light, segment, sample) against
+    the oracle's samplers -> {(light, segment): rays checked}"""
+    n = c["wo"].shape[1]
+    seg, l = segment(h["kind"]), h["kind"] & LIGHT_MASK
+    checked = {}
+    for li in range(nl):
+        for s in range(spp_n * spp_n):
+            if node == "ggx":
+                jobs = [(2, 3 * li + 1, lambda rx, ry: ggx_oracle(oracle, c).sample_eval_pdf(rx, ry)[0])]
+            else:
+                od = disney_oracle(oracle, c)
+                jobs = [(1, 3 * li + 1, lambda rx, ry: od.sample(0x08, rx, ry)), (2, 3 * li + 2, lambda rx, ry: od.sample(0x10, rx, ry))]
+            for sg, pair, fn in jobs:
+                rx, ry = oracle.batch_sample_02(seed, first, n, pair, s)
+                want = fn(rx, ry)
+                m = (seg == sg) & (l == li) & (h["sample"] == s)
+                checked[(li, sg)] = checked.get((li, sg), 0) + int(m.sum())
+                if m.any():
+                    cases.assert_tight(cases.summarize(cases.rel_err(h["dir"][:, m], want[:, h["point"][m]])), (node, li, sg, s))
+    return checked
+
+
 @pytest.mark.parametrize("node", NODES)
 def test_bsdf_directions_are_the_oracle_samplers(gpu, oracle, T, node):
     """BSDF-strategy rays: the direction of (point, light, segment, sample) is the oracle sampler's on the numbers
@@ -277,22 +300,7 @@ def test_bsdf_directions_are_the_oracle_samplers(gpu, oracle, T, node):
     n, spp_n = 2048, 3
     b = Batch(T, gpu, node, n, oracle)
     h = queue_host(b.emit(lights, spp_n))
-    seg, l = segment(h["kind"]), h["kind"] & LIGHT_MASK
-    checked = {}
-    for li in range(2):
-        for s in range(spp_n * spp_n):
-            if node == "ggx":
-                jobs = [(2, 3 * li + 1, lambda rx, ry: ggx_oracle(oracle, b.c).sample_eval_pdf(rx, ry)[0])]
-            else:
-                od = disney_oracle(oracle, b.c)
-                jobs = [(1, 3 * li + 1, lambda rx, ry: od.sample(0x08, rx, ry)), (2, 3 * li + 2, lambda rx, ry: od.sample(0x10, rx, ry))]
-            for sg, pair, fn in jobs:
-                rx, ry = oracle.batch_sample_02(SEED, 0, n, pair, s)
-                want = fn(rx, ry)
-                m = (seg == sg) & (l == li) & (h["sample"] == s)
-                checked[(li, sg)] = checked.get((li, sg), 0) + int(m.sum())
-                if m.any():
-                    cases.assert_tight(cases.summarize(cases.rel_err(h["dir"][:, m], want[:, h["point"][m]])), (node, li, sg, s))
+    checked = bsdf_directions_against_the_oracle(oracle, node, b.c, h, 2, spp_n)
     # every (light, segment) that has an oracle sampler was checked, on a share of the points that hit the light
     assert set(checked) == {(li, sg) for li in range(2) for sg in ((2,) if node == "ggx" else (1, 2))}
     assert all(v >= 20 for v in checked.values()), checked
@@ -360,18 +368,7 @@ def test_coloured_visibility_is_the_documented_composition(gpu, oracle, T, node)
     got = _resolve(q, dev(vis))
     want = compose(h, vis, _rad(lights), spp_n * spp_n, tail=b.tail())
     _same(got, want, (node, "numpy float32 composition"))
-    # float64: one rounding per product and per addition over a light's k rays, two for the tail of a light, one per
-    # addition of a light, two for rlGgx's tail -> (k + 3 nl + 2) 2^-24 of the sum of magnitudes (test_gpu_trace_edges.py)
-    e64 = compose(h, vis, _rad(lights), spp_n * spp_n, dtype=np.float64, tail=b.tail())
-    habs = dict(h, ws=np.abs(h["ws"]), wd=np.abs(h["wd"]))
-    tail = b.tail()
-    mag = compose(habs, vis, np.abs(_rad(lights)), spp_n * spp_n, dtype=np.float64,
-                  tail=None if tail is None else (np.abs(tail[0]), np.abs(tail[1])))
-    k = np.diff(h["offsets"]).astype(np.float64) + 3 * len(lights) + 2
-    for a in range(2):
-        err = np.abs(got[a].astype(np.float64) - e64[a])
-        bound = k * 2.0 ** -24 * mag[a] + 1e-30
-        assert np.all(err <= bound), (node, a, "worst ratio", float((err / bound).max()))
+    assert_float64_bound(h, vis, _rad(lights), spp_n * spp_n, got, b.tail(), node)
 
 
 # ---- 4. occlusion ----------------------------------------------------------------------------------------------------------------

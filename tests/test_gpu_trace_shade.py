@@ -63,13 +63,15 @@ class Node:
     """one node over the first n points of tests/test_gpu_shade.py's inputs: the closure, the slab, rlGgx's node parameters
     with Kd = 0, Kt = 0 and a black KsColor on the residues 0, 1, 2 of i % 8"""
 
-    def __init__(self, T, ctx, oracle, node, n, a=0, full=None):
+    def __init__(self, T, ctx, oracle, node, n, a=0, full=None, case=None):
+        """case: the caller's own points instead -- dict(P [3, n], c the closure's planes, shh rlGgx's node parameters), numpy"""
         self.T, self.ctx, self.node, self.n = T, ctx, node, n
         m = max(a + n, 128) if full is None else full
         sl = lambda v: np.ascontiguousarray(v[..., a:a + n])
-        self.Ph = sl(_slab(m))
-        self.P = dev(self.Ph)
-        if node == "ggx":
+        self.k = np.arange(a, a + n) % 8
+        if case is not None:
+            self.Ph, self.c, self.shh = case["P"], case["c"], case.get("shh")
+        elif node == "ggx":
             c = cases.ggx_mixed(cases.SEED_PARITY, m)
             u = lambda j: oracle.gen_uniform(cases.SEED_PARITY, 0, m, oracle.S_PARAM0 + j, 0.0, 1.0)
             kdc, ktc = np.stack([u(j) for j in range(3)]), np.stack([u(3 + j) for j in range(3)])
@@ -79,13 +81,17 @@ class Node:
             kt = np.where(k == 1, np.float32(0.0), kt).astype(np.float32)
             c = dict(c, KsColor=np.where((k == 2)[None, :], np.float32(0.0), c["KsColor"]).astype(np.float32))
             self.c = {q: sl(v) for q, v in c.items()}
-            self.k = sl(k)
             self.shh = dict(KdColor=sl(kdc), Kd=sl(kd), diffuseRoughness=sl(kdr), Ks=sl(ks), KtColor=sl(ktc), Kt=sl(kt))
+            self.Ph = sl(_slab(m))
+        else:
+            self.c = {q: sl(v) for q, v in cases.disney_mixed(cases.SEED_PARITY, m).items()}
+            self.shh = None
+            self.Ph = sl(_slab(m))
+        self.P = dev(self.Ph)
+        if node == "ggx":
             self.sh = {q: dev(v) for q, v in self.shh.items()}
             self.s = ggx_sampler(ctx, self.c)
         else:
-            c = cases.disney_mixed(cases.SEED_PARITY, m)
-            self.c = {q: sl(v) for q, v in c.items()}
             self.s = disney_sampler(ctx, self.c)
             self.sh = self.shh = None
         self.rays = GGX_RAYS if node == "ggx" else DISNEY_RAYS
@@ -304,18 +310,30 @@ def _matches(h, want, what, kind=False):
     cases.assert_tight(cases.summarize(cases.rel_err(h["weight"], want["weight"])), (what, "weight"))
 
 
+def _assert_ggx_queues_are_the_oracle_samplers(oracle, b, nq, spp_n, first, seed=SEED):
+    """the glossy and refract queues of an rlGgx node emit (traced, one lane per point or any width: the queue does not depend
+    on it) against the oracle's samplers at pairs 24 and 25, behind the node's gates"""
+    h = b.shh
+    open_g = ~np.all(np.abs(b.c["KsColor"]) < EPS, axis=0)
+    open_t = ~np.all(np.abs(h["KtColor"] * h["Kt"][None, :]) < EPS, axis=0)
+    for member, refract, pair, gate in (("glossy", False, PAIR0, open_g), ("refract", True, PAIR0 + 1, open_t)):
+        dirs, ws, keep, kinds = _ggx_oracle_queue(oracle, b.c, spp_n, seed, refract, pair, first)
+        want = _queue(dirs, ws, [k & gate for k in keep], kinds)
+        _matches(_ray_host(getattr(nq, member)), want, ("ggx", member, pair), kind=refract)
+
+
+def _assert_disney_queues_are_the_oracle_samplers(oracle, b, nq, spp_n, first, seed=SEED):
+    for member, lobe, pair in (("diffuse", DIFFUSE, PAIR0), ("specular", GLOSSY, PAIR0 + 1)):
+        _matches(_ray_host(getattr(nq, member)), _disney_oracle_queue(oracle, b.c, spp_n, seed, lobe, pair, first),
+                 ("disney", member, pair))
+
+
 def test_ggx_queues_are_the_oracle_samplers_at_the_node_pairs(gpu, oracle, T, monkeypatch):
     _, lights = _lights(oracle)
     n, spp_n, first = 1024, 3, 1 << 36
     b = Node(T, gpu, oracle, "ggx", n)
     nq = _at(monkeypatch, 1, lambda: b.emit(lights, spp_n, first=first))
-    h = b.shh
-    open_g = ~np.all(np.abs(b.c["KsColor"]) < EPS, axis=0)
-    open_t = ~np.all(np.abs(h["KtColor"] * h["Kt"][None, :]) < EPS, axis=0)
-    for member, refract, pair, gate in (("glossy", False, PAIR0, open_g), ("refract", True, PAIR0 + 1, open_t)):
-        dirs, ws, keep, kinds = _ggx_oracle_queue(oracle, b.c, spp_n, SEED, refract, pair, first)
-        want = _queue(dirs, ws, [k & gate for k in keep], kinds)
-        _matches(_ray_host(getattr(nq, member)), want, ("ggx", member, pair), kind=refract)
+    _assert_ggx_queues_are_the_oracle_samplers(oracle, b, nq, spp_n, first)
     # the stream fix: the stand-alone integrator's queue (pair 0) is another queue
     alone = _ray_host(_at(monkeypatch, 1, lambda: T.glossy_rays(b.s, spp_n, SEED, first)))
     mine = _ray_host(nq.glossy)
@@ -379,9 +397,7 @@ def test_disney_queues_are_the_oracle_samplers_at_the_node_pairs(gpu, oracle, T,
     n, spp_n, first = 1024, 3, 98765
     b = Node(T, gpu, oracle, "disney", n)
     nq = _at(monkeypatch, 1, lambda: b.emit(lights, spp_n, first=first))
-    for member, lobe, pair in (("diffuse", DIFFUSE, PAIR0), ("specular", GLOSSY, PAIR0 + 1)):
-        _matches(_ray_host(getattr(nq, member)), _disney_oracle_queue(oracle, b.c, spp_n, SEED, lobe, pair, first),
-                 ("disney", member, pair))
+    _assert_disney_queues_are_the_oracle_samplers(oracle, b, nq, spp_n, first)
     alone = _ray_host(_at(monkeypatch, 1, lambda: T.disney_rays(b.s, GLOSSY, spp_n, SEED, first)))
     mine = _ray_host(nq.specular)
     m = min(alone["count"], mine["count"])
@@ -537,7 +553,8 @@ def _compose_node(b, nq, planes, lights, spp_n, traced, dtype, absolute=False, p
                 at = off[:-1][m] + i
                 d = (L[:, at] - ref[:, m]).astype(dtype)
                 A[:, m] = A[:, m] + w[:, at]
-                B[:, m] = B[:, m] + ((np.abs(d) if absolute else d) * w[:, at]).astype(dtype)
+                # (a ray AT the reference adds nothing, whatever its weight: ray_sums_about_reference)
+                B[:, m] = B[:, m] + np.where(d == 0, dtype(0), (np.abs(d) if absolute else d) * w[:, at]).astype(dtype)
             sums[r] = ((A * inv_r).astype(dtype) * f(ref)).astype(dtype) + (B * inv_r).astype(dtype)
     out = dict(direct_diffuse=dd, direct_specular=ds)
     if b.node == "ggx":
@@ -553,17 +570,9 @@ def _compose_node(b, nq, planes, lights, spp_n, traced, dtype, absolute=False, p
         np.diff(hs["offsets"])
 
 
-@pytest.mark.parametrize("hdr", [False, True], ids=["ldr", "hdr"])
-@pytest.mark.parametrize("node,traced", [("ggx", True), ("ggx", False), ("disney", True)])
-def test_random_radiance_is_the_documented_composition(gpu, oracle, T, node, traced, hdr):
-    _, lights = _lights(oracle)
-    n, spp_n = 1500, 4
-    b = Node(T, gpu, oracle, node, n)
-    nq = b.emit(lights, spp_n, traced=traced)
-    planes = _random_planes(nq, hdr=hdr)
-    got = _resolve(nq, [p.cuda() for p in planes])
-    want, _, _ = _compose_node(b, nq, planes, lights, spp_n, traced, np.float32)
-    _same(got, want, (node, traced, "numpy float32 composition"))
+def _assert_within_the_float64_bound(b, nq, planes, lights, spp_n, traced, got, what=""):
+    """got: the resolve of nq under `planes`, {AOV: [3, b.n]}"""
+    node = b.node
     # float64, against the PLAIN sum inv sum L w, the quantity the resolve stands for, and relative to the plain sum's own
     # magnitude inv sum |L| |w| x |tail|.  Over a queue's k rays of the point: one rounding per addition into A, three per term
     # of B (L - Lref, x w, +), then x inv (twice), x Lref, the final + and up to two for the tail: (k + 6) 2^-24 of
@@ -581,7 +590,21 @@ def test_random_radiance_is_the_documented_composition(gpu, oracle, T, node, tra
     bounds["out"] = sum(bounds.values()) + 4 * u * mag["out"]
     for q, bd in bounds.items():
         err = np.abs(got[q].astype(np.float64) - e64[q])
-        assert np.all(err <= bd + 1e-30), (node, q, "worst ratio", float((err / (bd + 1e-30)).max()))
+        assert np.all(err <= bd + 1e-30), (what, node, q, "worst ratio", float((err / (bd + 1e-30)).max()))
+
+
+@pytest.mark.parametrize("hdr", [False, True], ids=["ldr", "hdr"])
+@pytest.mark.parametrize("node,traced", [("ggx", True), ("ggx", False), ("disney", True)])
+def test_random_radiance_is_the_documented_composition(gpu, oracle, T, node, traced, hdr):
+    _, lights = _lights(oracle)
+    n, spp_n = 1500, 4
+    b = Node(T, gpu, oracle, node, n)
+    nq = b.emit(lights, spp_n, traced=traced)
+    planes = _random_planes(nq, hdr=hdr)
+    got = _resolve(nq, [p.cuda() for p in planes])
+    want, _, _ = _compose_node(b, nq, planes, lights, spp_n, traced, np.float32)
+    _same(got, want, (node, traced, "numpy float32 composition"))
+    _assert_within_the_float64_bound(b, nq, planes, lights, spp_n, traced, got)
 
 
 # ---- 5. robustness ---------------------------------------------------------------------------------------------------------------

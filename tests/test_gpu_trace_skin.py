@@ -69,7 +69,8 @@ class Skin:
     tests/test_gpu_skin_integrate.py"""
 
     def __init__(self, gpu, oracle, n, geometry="plane", cavity=False, literal=False, params=None, a=0, full=None,
-                 materials=None):
+                 materials=None, case=None):
+        """case: the caller's own points on the plane z = 0 instead -- dict(wo, N, T, P [3, n], params), numpy"""
         m = max(a + n, 64) if full is None else full
         c = cases.skin_mixed(cases.SEED_PARITY, m)
         sl = lambda v: np.ascontiguousarray(np.asarray(v)[..., a:a + n])
@@ -92,6 +93,9 @@ class Skin:
             wo = sl((wo / np.linalg.norm(wo, axis=0, keepdims=True)).astype(F))
         if params is not None:
             p = params(p, n) if callable(params) else params
+        if case is not None:
+            assert geometry == "plane"
+            wo, N, Tt, P, p = case["wo"], case["N"], case["T"], case["P"], case["params"]
         self.n, self.gpu, self.oracle, self.cavity, self.literal = n, gpu, oracle, cavity, literal
         self.Ph, self.p = P, p
         self.P = dev(P)
@@ -322,11 +326,19 @@ def test_specular_glossy_queue_is_the_oracle_sampler_at_pair_1(gpu, oracle, T, m
     n, spp_n, first = 131, 3, (1 << 36) + 5
     b = Skin(gpu, oracle, n, "sphere")
     q = _at(monkeypatch, 1, lambda: b.emit(T, None, spp_n, first=first))
+    _assert_glossy_queues_are_the_oracle_sampler(oracle, b, q, spp_n, first)
+
+
+def _assert_glossy_queues_are_the_oracle_sampler(oracle, b, q, spp_n, first, seed=SEED):
+    """both glossy queues of a skin emit against the oracle's rlGgx sampler on the lobe's parameters at pairs 0 and 1"""
+    from test_gpu_trace_shade import _ggx_oracle_queue, _matches, _ray_host
+    from trace_util import _queue
     wo, N, Tt = b.frame
+    n = b.n
     for lobe, pair in (("sheen", 0), ("specular", 1)):
         case = dict(wo=wo, N=N, T=Tt, KsColor=b.p[lobe + "_color"], ior=b.p[lobe + "_ior"], roughness=b.p[lobe + "_roughness"],
                     anisotropic=np.zeros(n, F))
-        dirs, ws, keep, kinds = _ggx_oracle_queue(oracle, case, spp_n, SEED, False, pair, first)
+        dirs, ws, keep, kinds = _ggx_oracle_queue(oracle, case, spp_n, seed, False, pair, first)
         gate = (b.p[lobe + "_weight"] > EPS) & ~np.all(np.abs(b.p[lobe + "_color"]) < EPS, axis=0)
         assert gate.any()
         _matches(_ray_host(getattr(q, lobe + "_glossy")), _queue(dirs, ws, [k & gate for k in keep], kinds), (lobe, pair))
@@ -459,21 +471,13 @@ def _bound(k, inv, terms):
     return (3.0 * (k + 3) * u * inv * terms), 4.0 * u
 
 
-def test_random_visibility_and_radiance_follow_the_documented_composition(gpu, oracle, T):
-    n, spp_n = 67, 4
-    spp = spp_n * spp_n
+def _documented_composition(b, q, specs, spp_n, vis, rad, hits, got):
+    """the header's composition on the host, for the resolve `got` of q under the visibilities vis and radiances rad (dicts by
+    queue name, numpy [3, count]) and the hits (count, P, N, E): the scatter part and out bit for bit, the lobes within the bound
+    of _bound about the float32 light part -> (lit {lobe: [3, n]}, gate, W), what the lobes are composed of"""
+    n, spp = b.n, spp_n * spp_n
     inv32 = F(1) / F(spp)
-    b = Skin(gpu, oracle, n, "plane", cavity=True)
-    specs = MIXED3
-    q = b.emit(T, _mk_lights(specs), spp_n)
-    cnt = q.counts()
-    rng = np.random.default_rng(5)
-    vis = {k: rng.random((3, cnt[k])).astype(F) for k in ("sheen_shadow", "specular_shadow")}
-    rad = {k: (rng.random((3, cnt[k])) * 10.0 ** rng.uniform(-4, 4, (3, cnt[k]))).astype(F) for k in ("sheen_glossy", "specular_glossy")}
-    hc, hP, hN, E = b.hits(q)
-    E = (E * rng.random(E.shape).astype(F)).astype(F)
-    got = _resolve(b, q, (dev(vis["sheen_shadow"]), dev(vis["specular_shadow"]), dev(rad["sheen_glossy"]),
-                          dev(rad["specular_glossy"])), (hc, hP, hN, E))
+    hc, hP, hN, E = hits
     sF, pF, sW = host(q.sheenFresnel), host(q.specularFresnel), host(q.sssWeight)
     # light part, float32 in queue order
     lit = {}
@@ -493,7 +497,7 @@ def test_random_visibility_and_radiance_follow_the_documented_composition(gpu, o
     case = dict(P=b.Ph, N=b.frame[1], T=b.frame[2], albedo=np.broadcast_to(np.asarray(b.p["sss_color"], F).reshape(3, -1), (3, n)).copy(),
                 dist=(np.asarray(b.p["sss_scatter_dist"], F).reshape(3, -1) * np.asarray(b.p["sss_dist_multiplier"], F)).astype(F)
                 * np.ones((3, n), F))
-    scat, _ = U.host_resolve(case, spp, hc, hP, hN, E, hP.shape[1], True, False)
+    scat, _ = U.host_resolve(case, spp, hc, hP, hN, E, hP.shape[1], b.cavity, b.literal)
     sss = np.where(sW < EPS, F(0), (scat * sW).astype(F)).astype(F)
     U.same_bits_or_both_nan(got["sss"], sss, "sss")
     W = {"sheen": np.asarray(b.p["sheen_weight"], F) * np.ones(n, F),
@@ -513,6 +517,25 @@ def test_random_visibility_and_radiance_follow_the_documented_composition(gpu, o
             tol = abs(float(W[name][i])) * (bS + u4 * (np.abs(lit[name][:, i]) + mag)) * (1 + 2.0 ** -23)
             assert (np.abs(got[name][:, i] - want) <= tol).all(), (name, i, got[name][:, i], want, tol)
     U.same_bits_or_both_nan(got["out"], ((got["sheen"] + got["specular"]).astype(F) + got["sss"]).astype(F), "out")
+    return lit, gate, W
+
+
+def test_random_visibility_and_radiance_follow_the_documented_composition(gpu, oracle, T):
+    n, spp_n = 67, 4
+    spp = spp_n * spp_n
+    inv32 = F(1) / F(spp)
+    b = Skin(gpu, oracle, n, "plane", cavity=True)
+    specs = MIXED3
+    q = b.emit(T, _mk_lights(specs), spp_n)
+    cnt = q.counts()
+    rng = np.random.default_rng(5)
+    vis = {k: rng.random((3, cnt[k])).astype(F) for k in ("sheen_shadow", "specular_shadow")}
+    rad = {k: (rng.random((3, cnt[k])) * 10.0 ** rng.uniform(-4, 4, (3, cnt[k]))).astype(F) for k in ("sheen_glossy", "specular_glossy")}
+    hc, hP, hN, E = b.hits(q)
+    E = (E * rng.random(E.shape).astype(F)).astype(F)
+    got = _resolve(b, q, (dev(vis["sheen_shadow"]), dev(vis["specular_shadow"]), dev(rad["sheen_glossy"]),
+                          dev(rad["specular_glossy"])), (hc, hP, hN, E))
+    lit, gate, W = _documented_composition(b, q, specs, spp_n, vis, rad, (hc, hP, hN, E), got)
     # with the glossy radiance 0 the lobes are the light part alone, bit for bit
     zero = {k: np.zeros_like(v) for k, v in rad.items()}
     got0 = _resolve(b, q, (dev(vis["sheen_shadow"]), dev(vis["specular_shadow"]), dev(zero["sheen_glossy"]),

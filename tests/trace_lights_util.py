@@ -62,6 +62,21 @@ def compose(h, vis, radiance, spp, dtype=np.float32, tail=None):
     return oD.astype(dtype), oS.astype(dtype)
 
 
+def assert_float64_bound(h, vis, radiance, spp, got, tail, what=""):
+    """the resolve `got` (direct_diffuse, direct_specular) of the queue h under vis within the float64 rounding bound:
+    one rounding per product and per addition over a light's k rays, two for the tail of a light, one per addition of a light, two
+    for rlGgx's tail -> (k + 3 nl + 2) 2^-24 of the sum of magnitudes (test_gpu_trace_edges.py)"""
+    e64 = compose(h, vis, radiance, spp, dtype=np.float64, tail=tail)
+    habs = dict(h, ws=np.abs(h["ws"]), wd=np.abs(h["wd"]))
+    mag = compose(habs, vis, np.abs(radiance), spp, dtype=np.float64,
+                  tail=None if tail is None else (np.abs(tail[0]), np.abs(tail[1])))
+    k = np.diff(h["offsets"]).astype(np.float64) + 3 * len(radiance) + 2
+    for a in range(2):
+        err = np.abs(got[a].astype(np.float64) - e64[a])
+        bound = k * 2.0 ** -24 * mag[a] + 1e-30
+        assert np.all(err <= bound), (what, a, "worst ratio", float((err / bound).max()))
+
+
 def cone(center, radius, P):
     """float32, as the kernels' cone_make: d = center - P, c2 = |d|^2 - r^2"""
     f = np.float32
