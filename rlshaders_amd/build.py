@@ -110,7 +110,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str = "",
 TRACE_CSRC = PKG / "csrc_trace"
 TRACE_SOURCES = ["trace.hip"]
 TRACE_LIB = LIBDIR / "librls_trace.so"
-TRACE_HEADERS = [TRACE_CSRC / "rls_trace_device.hpp", PKG.parent / "include" / "rlshaders_amd_trace.h"]
+TRACE_HEADERS = [*sorted(TRACE_CSRC.glob("*.hpp")), PKG.parent / "include" / "rlshaders_amd_trace.h"]
 
 
 def build_trace_library(force: bool = False, verbose: bool = False) -> Path:

@@ -55,6 +55,7 @@ struct TraceResolveIO {
     float scale;             // refraction: 1 / spp (applied after the sum); glossy: unused
     int64_t n;
 };
+constexpr int kResolveTile = 1024;           // rays per tile of a resolve's walk (ray_sums, rls_trace_queue.hpp)
 
 // The light loops (rls_shadow_queue).  A point has n_lights x 3 x spp slots: slot (l * 3 + segment) * spp + s is sample s of
 // light l's segment (0 the light-strategy samples, 1 the BSDF diffuse-lobe samples, 2 the BSDF specular-lobe samples), staged
@@ -114,6 +115,8 @@ struct ShadowResolveIO {
     rls_ggx_shader sh;
     int64_t n;
 };
+constexpr int kShadowTile = 1024;            // rays per tile of a light-loop resolve's walk (shadow_sums, rls_trace_queue.hpp)
+static_assert(kShadowTile == kResolveTile, "the node resolves walk both kinds of queue through one product store");
 
 // Whole nodes (rls_trace_*_shade_emit / _resolve).  The node's indirect loops draw from the stream pairs after the lights'
 // (shade.hip, kShadeStream): kNodeStream is their first scramble stream, relative to kScrambleStream like a lobe's kStream.

@@ -1,0 +1,429 @@
+// rls_trace_shadow_emit.hpp -- the light loops' shadow-ray emits and rlSkin's shadow and glossy emits (part of trace.hip,
+// included there inside its anonymous namespace, after rls_trace_emit.hpp).  The light loops' emit has the sample-ray emits'
+// three steps with a queue of its own (rls_shadow_queue): ggx_direct_emit_kernel / disney_direct_emit_kernel /
+// skin_shadow_emit_kernel, the scan, shadow_compact_kernel (rls_trace_queue.hpp).
+
+// ---------------------------------------------------------------------------------------------
+// The light loops: ggx_direct_loops / disney_direct_loops (rls_loops.hpp) with every term staged instead of folded.  Where
+// they interleave the two lobes of the BSDF strategy in one pass over the samples, here each lobe is a pass of its own (the
+// queue's segments 1 and 2), so that one running count ranks a point's rays in queue order:
+//   segment 0 = the loops' first pass, the light strategy (RLS_LIGHT_SAMPLE_PUSH, *_light_eval_run, eval_pop);
+//   segment 1 = the BSDF strategy's diffuse lobe: rlGgx's Oren-Nayar sample, rlDisney's packed cosine-weighted one;
+//   segment 2 = the BSDF strategy's specular lobe (RLS_HIT_SAMPLE_EVAL, eval_pop).
+// The two macros are the analytic loops' own lines (rls_loops.hpp).  Still written there and here, to be changed together
+// (tests/test_gpu_trace_lights.py holds the copies together bit for bit): the pick-up sweeps after the evaluations, the
+// Oren-Nayar sample, rlDisney's diffuse-lobe sweeps, and rlGgx's RLS_HIT_SAMPLE_EVAL lines, written out in ggx_direct_loops.
+// The two kernels stay written out: with their common walk in a force-inlined shadow_emit_points<G, Node> (the argument
+// struct by reference or by value, the segments as members of a node policy) rlDisney's kernel spilled 8 more vector
+// registers at every G (scratch 56 -> 96 B at G = 1) and ran 0.8 % slower; rlDisney's body alone behind a force-inlined
+// function taking the struct by reference went from 56 to 144 B.
+
+// rlGgx's lobe for RLS_HIT_SAMPLE_EVAL: the VNDF sampler, the reflected direction (streams +2/3)
+struct GgxHitLobe {
+    const Ggx &g;
+    const VndfView &w;
+    V3 N;
+    template <int K>
+    RLS_DEV void push(SlowLds<K> &slow, int k, int &qn, bool ok, float rx, float ry) const { ggx_vndf_push<K>(slow, k, qn, ok, w, rx, ry); }
+    template <int K>
+    RLS_DEV V3 pop(const SlowLds<K> &slow, int k) const { return reflect_direction(g.view, ggx_vndf_pop<K>(slow, k, w, g.fr)); }
+    RLS_DEV bool hit(V3 L) const { return !is_zero(L) && dot(L, N) > 0.0f; }
+    template <int K>
+    RLS_DEV void run(SlowLds<K> &slow, int qn, float conePdf, int mode) const { ggx_hit_eval_run<K>(slow, qn, g, conePdf, mode); }
+};
+
+// One point's place in the staging and its running ray count; SEGS: the segments of a light
+template <int G, class IO, int SEGS = kShadowSegments>
+struct ShadowStage {
+    const IO &a;
+    int64_t i;
+    bool live;
+    int sub, run;
+    // sample s of segment `seg` of light l, in every lane of the wavefront (group_rank ballots): dir and the two lobes' terms
+    // (zeros where the ray carries none); NWD: the planes of the diffuse term
+    template <int NWD>
+    __device__ __forceinline__ void put(const LightCone &cone, int l, int seg, int s, bool ok, V3 dir, const float (&ws)[3],
+                                        const float (&wd)[3])
+    {
+        const bool bs = !(ws[0] == 0.0f && ws[1] == 0.0f && ws[2] == 0.0f);
+        bool bd = !(wd[0] == 0.0f);
+        if (NWD == 3) bd = !(wd[0] == 0.0f && wd[1] == 0.0f && wd[2] == 0.0f);
+        const bool keep = ok && (bs || bd);
+        const int rank = group_rank<G>(keep, sub, run);
+        store<NWD>(cone, l, seg, s, ok, keep, rank, bs, bd, dir, ws, wd);
+    }
+    // rlSkin's light loops grow ONE sum per light, sample by sample, the light sample's term and then the BSDF sample's
+    // (fold2 in ggx_light_loops): sample s's two rays, A the light-strategy one (segment 0) and B the BSDF-strategy one
+    // (segment 1), ranked by a prefix count over the PAIRS of the point's earlier samples; A before B.  Specular terms only.
+    __device__ __forceinline__ void put_pair(const LightCone &cone, int l, int s, bool ok, V3 dirA, const float (&wa)[3], V3 dirB,
+                                             const float (&wb)[3])
+    {
+        const bool ka = ok && !(wa[0] == 0.0f && wa[1] == 0.0f && wa[2] == 0.0f);
+        const bool kb = ok && !(wb[0] == 0.0f && wb[1] == 0.0f && wb[2] == 0.0f);
+        const uint64_t ma = __builtin_amdgcn_ballot_w64(ka), mb = __builtin_amdgcn_ballot_w64(kb);
+        const int base = (int)(threadIdx.x & 63u) & ~(G - 1);
+        uint64_t ga = ma, gb = mb;
+        if constexpr (G < 64) { ga = (ma >> base) & ((1ull << G) - 1ull); gb = (mb >> base) & ((1ull << G) - 1ull); }
+        const uint64_t below = (1ull << sub) - 1ull;
+        const int rankA = run + __builtin_popcountll(ga & below) + __builtin_popcountll(gb & below);
+        const int rankB = rankA + (ka ? 1 : 0);
+        run += __builtin_popcountll(ga) + __builtin_popcountll(gb);
+        store<0>(cone, l, 0, s, ok, ka, rankA, true, false, dirA, wa, wa);
+        store<0>(cone, l, 1, s, ok, kb, rankB, true, false, dirB, wb, wb);
+    }
+    template <int NWD>
+    __device__ __forceinline__ void store(const LightCone &cone, int l, int seg, int s, bool ok, bool keep, int rank, bool bs,
+                                          bool bd, V3 dir, const float (&ws)[3], const float (&wd)[3])
+    {
+        if (live && ok) {
+            const int64_t slot = staging_slot((l * SEGS + seg) * a.spp + s, a.n, i);
+            const IO al = RLS_INT_ARGS(a);                       // the staging planes' pointers re-read where they are used
+            if (keep) {
+                // the near intersection of P + t dir with the light's sphere: t^2 |dir|^2 - 2 b t + c2 = 0, in the form that
+                // does not cancel; a light sample that rounding puts just outside the cone gets its closest approach
+                const float b = dot(cone.d, dir), dd = dot(dir, dir);
+                const float disc = maxf(0.0f, b * b - cone.c2 * dd);
+                al.dir[0][slot] = dir.x; al.dir[1][slot] = dir.y; al.dir[2][slot] = dir.z;
+                al.maxdist[slot] = R_DIV(cone.c2, b + R_SQRT(disc));
+#pragma unroll
+                for (int c = 0; c < 3; c++) al.ws[c][slot] = ws[c];
+                if constexpr (NWD > 0) {
+#pragma unroll
+                    for (int c = 0; c < NWD; c++) al.wd[c][slot] = wd[c];
+                }
+            }
+            const int kind = l | (seg ? RLS_SHADOW_BSDF : 0) | (bs ? RLS_SHADOW_SPECULAR : 0) | (bd ? RLS_SHADOW_DIFFUSE : 0);
+            al.tag[slot] = shadow_tag(keep, rank, kind);
+        }
+    }
+    // a segment the light's mis_mode skips: every slot dropped
+    __device__ __forceinline__ void skip(int l, int seg)
+    {
+        if (!live) return;
+        for (int s = sub; s < a.spp; s += G)
+            a.tag[staging_slot((l * SEGS + seg) * a.spp + s, a.n, i)] = kShadowDropped;
+    }
+};
+
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_direct_emit_kernel(ShadowEmitIO<rls_ggx_closure, rls_ggx_shader> a)
+{
+    constexpr int K = RLS_SPEC_BLOCK;
+    __shared__ uint32_t tab[2][kMaxSpp];
+    __shared__ SlowLds<K> slow;
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    RLS_POINT_WALK(G, a.n)
+    const int spp = a.spp, tid = (int)threadIdx.x;
+    const float zero[3] = { 0.0f, 0.0f, 0.0f };
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
+        const bool live = i < a.n;
+        const int64_t ii = live ? i : a.n - 1;
+        RLS_GGX_LOAD(g, a.c, ii)
+        const VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
+        const OrenNayar on = oren_nayar_make(N, ldp(a.sh.diffuseRoughness, pk));
+        const float kd = ldp(a.sh.Kd, pk);
+        float dr, dg, db;
+        ldrgb(a.sh.KdColor, pk, dr, dg, db);
+        const bool sampleDiffuse = !color_is_small(dr * kd, dg * kd, db * kd);      // src/rlGgx.cpp:279-281
+        const V3 P = ld3(a.P, ii);
+        const uint64_t index = a.first + (uint64_t)ii;
+        ShadowStage<G, decltype(a)> st = { a, i, live, sub, 0 };
+        for (int l = 0; l < a.nl; l++) {
+            const LightRegs lt = light_regs(a.lights[l], P);
+            const LightCone &cone = lt.cone;
+            const int mode = lt.mode;
+            uint32_t scr[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) scr[k] = hash_u32(a.seed, index, kScrambleStream + 6 * l + k);
+
+            // segment 0: one light sample, both lobes
+            if (mode == RLS_MIS_BSDF_ONLY) st.skip(l, 0);
+            for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {
+                RLS_LIGHT_SAMPLE_PUSH(slow, qn, tab, spp, s0, cone, N, scr[0], scr[1],
+                                      slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;)
+                ggx_light_eval_run<K>(slow, qn, g, on, cone.pdf, sampleDiffuse, mode);
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f }, ud[3] = { 0.0f, 0.0f, 0.0f };
+                    if (eval_pop<K>(slow, k, t)) {
+                        us[0] = t[0]; us[1] = t[1]; us[2] = t[2];
+                        if (sampleDiffuse) ud[0] = t[3];
+                    }
+                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
+                    st.template put<1>(cone, l, 0, s0 + k * G, s0 + k * G < spp, L, us, ud);
+                }
+            }
+            // segment 1: one BSDF sample of the Oren-Nayar lobe (streams +4/5), where it hits the light
+            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 1);
+            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += G) {
+                const int s = s0;
+                float ud[3] = { 0.0f, 0.0f, 0.0f };
+                V3 Ld = mk(0.0f, 0.0f, 0.0f);
+                if (s < spp && cone.valid && sampleDiffuse) {
+                    const float rx = bits_u01(tab[0][s] ^ scr[4]), ry = bits_u01(tab[1][s] ^ scr[5]);
+                    Ld = cosine_hemisphere(g.fr, rx, ry);
+                    const float pd = oren_nayar_pdf(on, Ld);
+                    if (pd > 0.0f && cone_hit(cone, Ld)) {
+                        const float fd = oren_nayar_brdf(on, wo, Ld);
+                        const float wd = mode == RLS_MIS_BSDF_ONLY ? 1.0f : power_heuristic(pd, cone.pdf);
+                        ud[0] = R_DIV(fd * wd, pd);
+                    }
+                }
+                st.template put<1>(cone, l, 1, s, s < spp, Ld, zero, ud);
+            }
+            // segment 2: one BSDF sample of the GGX lobe (streams +2/3); the few that hit the light are evaluated packed
+            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 2);
+            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
+                RLS_HIT_SAMPLE_EVAL(slow, (GgxHitLobe{ g, w, N }), tab, spp, s0, cone, scr[2], scr[3], mode)
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f };
+                    if (s < spp && cone.valid && eval_pop<K>(slow, k, t)) { us[0] = t[0]; us[1] = t[1]; us[2] = t[2]; }
+                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
+                    st.template put<1>(cone, l, 2, s, s < spp, L, us, zero);
+                }
+            }
+        }
+        if (live && sub == 0) a.count[i] = st.run;
+    }
+}
+
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_DISNEY_LIGHT_ATTR void disney_direct_emit_kernel(ShadowEmitIO<rls_disney_closure, NoShader> a)
+{
+    constexpr int K = RLS_SPEC_BLOCK;
+    __shared__ uint32_t tab[2][kMaxSpp];
+    __shared__ SlowLds<K> slow;
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    RLS_POINT_WALK(G, a.n)
+    const int spp = a.spp, tid = (int)threadIdx.x;
+    const float zero[3] = { 0.0f, 0.0f, 0.0f };
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
+        const bool live = i < a.n;
+        const int64_t ii = live ? i : a.n - 1;
+        RLS_DISNEY_LOAD(d, a.c, ii)
+        const VndfView w = vndf_view(d.view, d.fr, d.ax, d.ay);
+        const V3 N = d.fr.N, P = ld3(a.P, ii);
+        const uint64_t index = a.first + (uint64_t)ii;
+        ShadowStage<G, decltype(a)> st = { a, i, live, sub, 0 };
+        for (int l = 0; l < a.nl; l++) {
+            const LightRegs lt = light_regs(a.lights[l], P);
+            const LightCone &cone = lt.cone;
+            const int mode = lt.mode;
+            uint32_t scr[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) scr[k] = hash_u32(a.seed, index, kScrambleStream + 6 * l + k);
+
+            // segment 0: one light sample, both lobes (the specular lobe's terms come back through st[0..2]: the direction
+            // is drawn again in the second sweep)
+            if (mode == RLS_MIS_BSDF_ONLY) st.skip(l, 0);
+            for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {
+                RLS_LIGHT_SAMPLE_PUSH(slow, qn, tab, spp, s0, cone, N, scr[0], scr[1], )
+                disney_light_eval_run<K>(slow, qn, d, cone.pdf, mode);
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const int sc = s < spp ? s : 0;
+                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f }, ud[3] = { 0.0f, 0.0f, 0.0f };
+                    V3 L = mk(0.0f, 0.0f, 0.0f);
+                    if (eval_pop<K>(slow, k, t)) {
+                        ud[0] = t[0]; ud[1] = t[1]; ud[2] = t[2];
+                        us[0] = slow.st[0][k][tid]; us[1] = slow.st[1][k][tid]; us[2] = slow.st[2][k][tid];
+                        L = cone_sample(cone, bits_u01(tab[0][sc] ^ scr[0]), bits_u01(tab[1][sc] ^ scr[1]));
+                    }
+                    st.template put<3>(cone, l, 0, s, s < spp, L, us, ud);
+                }
+            }
+            // segment 1: the diffuse lobe's BSDF samples (cosine-weighted, streams +2/3) that hit the light
+            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 1);
+            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
+                int qn = 0;
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    const int s = s0 + k * G;
+                    const int sc = s < spp ? s : 0;
+                    const V3 L = cosine_hemisphere(d.fr, bits_u01(tab[0][sc] ^ scr[2]), bits_u01(tab[1][sc] ^ scr[3]));
+                    eval_push<K>(slow, k, qn, s < spp && cone.valid && cone_hit(cone, L), L);
+                    slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;
+                }
+                disney_hit_eval_run<K, true>(slow, qn, d, cone.pdf, mode);
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    float t[4], ud[3] = { 0.0f, 0.0f, 0.0f };
+                    if (eval_pop<K>(slow, k, t) && t[3] != 0.0f) { ud[0] = t[0]; ud[1] = t[1]; ud[2] = t[2]; }
+                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
+                    st.template put<3>(cone, l, 1, s0 + k * G, s0 + k * G < spp, L, zero, ud);
+                }
+            }
+            // segment 2: the specular lobe's BSDF samples (streams +4/5): the sampler's rare branches packed, then the
+            // reflected directions that hit the light
+            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 2);
+            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
+                RLS_HIT_SAMPLE_EVAL(slow, (DisneySpecHitLobe{ d, w }), tab, spp, s0, cone, scr[4], scr[5], mode)
+#pragma unroll 1
+                for (int k = 0; k < K; k++) {
+                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f };
+                    if (eval_pop<K>(slow, k, t) && t[3] != 0.0f) { us[0] = t[0]; us[1] = t[1]; us[2] = t[2]; }
+                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
+                    st.template put<3>(cone, l, 2, s0 + k * G, s0 + k * G < spp, L, us, zero);
+                }
+            }
+        }
+        if (live && sub == 0) a.count[i] = st.run;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// rlSkin's node: shader_evaluate (src/rlSkin.cpp:174-254) as skin_integrate_kernel (csrc/shade.hip) runs it, cut at every place
+// it traces.  Per GGX lobe (sheen, then specular) the light loop's shadow rays (skin_shadow_emit_kernel), then integrateGlossy's
+// rays (skin_*_glossy_emit_kernel: GgxGlossy on the lobe's closure); then integrateScatter's probe rays
+// (skin_probe_emit_kernel).  The mean Fresnel a layer hands down (getAvgReflectWeight, src/rlGgx.h:181-184) is ONE running
+// float sum over the light loops' BSDF samples and then integrateGlossy's: the shadow emit leaves (sum, count) per point in
+// two of the caller's three scalar planes -- the sum in the lobe's own Fresnel plane, the count in sssWeight -- the glossy emit
+// starts its fold there and overwrites the Fresnel plane with avg * weight; the probe emit, last, writes sssWeight.  So the
+// hand-over never lives in a queue's scratch, and the five queues may share one scratch block.
+
+// One GGX lobe of the node at point ii, built as skin_integrate_kernel builds it (csrc/shade.hip:36-49, 66-69): both lobes share
+// the frame and the local view; ggx_make<true>: no anisotropy.
+struct SkinLobe {
+    Ggx g;
+    VndfView w;
+    V3 N;
+    float weight;
+    bool small;              // integrateGlossy draws nothing (src/rlGgx.h:174-176); the light loop does
+};
+__device__ __forceinline__ SkinLobe skin_lobe(const rls_skin_closure &c, int64_t ii, int lobe)
+{
+    SkinLobe r;
+    const PIndex<int64_t> pk = pindex(c.materials, ii);
+    const V3 wo = ld3(c.wo, ii), N = ld3(c.N, ii), T = ld3(c.T, ii);
+    Frame gfr;
+    gfr.N = N; gfr.U = T; gfr.V = cross(N, T);
+    const V3 local = vndf_local(wo, gfr);
+    float cr, cg, cb, ior, rough;
+    if (lobe == 0) {
+        r.weight = ldp(c.sheen_weight, pk);
+        ldrgb(c.sheen_color, pk, cr, cg, cb);
+        ior = ldp(c.sheen_ior, pk); rough = ldp(c.sheen_roughness, pk);
+    } else {
+        r.weight = ldp(c.specular_weight, pk);
+        ldrgb(c.specular_color, pk, cr, cg, cb);
+        ior = ldp(c.specular_ior, pk); rough = ldp(c.specular_roughness, pk);
+    }
+    r.g = ggx_make<true>(wo, N, T, false, cr, cg, cb, ior, rough, 0.0f);
+    r.w = vndf_view_from(local, r.g.ax, r.g.ay);
+    r.N = N;
+    r.small = absf(cr) < kEps && absf(cg) < kEps && absf(cb) < kEps;
+    return r;
+}
+
+// A lobe's light loop: ggx_light_loops (rls_loops.hpp:447-495; its lines restated here, to be changed together --
+// tests/test_gpu_trace_skin.py holds the copies together bit for bit) with both terms of a sample staged instead of folded
+// into the light's one sum.  The Fresnel sum f grows over every BSDF sample of every light, in sample order (fold), cnt counts
+// them; a lobe whose weight is <= AI_EPSILON (src/rlSkin.cpp:191, 214) or a light whose cone is not valid draws nothing.
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void skin_shadow_emit_kernel(SkinShadowEmitIO a)
+{
+    __shared__ uint32_t tab[2][kMaxSpp];
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    RLS_POINT_WALK(G, a.n)
+    const int spp = a.spp;
+    const uint32_t stream = a.lobe ? 5u : 3u;
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
+        const bool live = i < a.n;
+        const int64_t ii = live ? i : a.n - 1;
+        const SkinLobe sl = skin_lobe(a.c, ii, a.lobe);
+        const Ggx &g = sl.g;
+        const V3 N = sl.N, P = ld3(a.P, ii);
+        const uint64_t index = a.first + (uint64_t)ii;
+        ShadowStage<G, SkinShadowEmitIO, kSkinShadowSegments> st = { a, i, live, sub, 0 };
+        float f = 0.0f, cnt = 0.0f;
+        for (int l = 0; l < a.nl; l++) {
+            const LightRegs lt = light_regs(a.lights[l], P);
+            const LightCone &cone = lt.cone;
+            const int mode = lt.mode;
+            uint32_t scr[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) scr[k] = hash_u32(a.seed, index, kScrambleStream + 2 * (stream + 4 * l) + k);
+            const bool draw = sl.weight > kEps && cone.valid;
+            for (int s0 = 0; s0 < spp; s0 += G) {               // the same trip count in every lane (ballots, shuffles)
+                const int s = s0 + sub;
+                const bool ok = s < spp;
+                float wa[3] = { 0.0f, 0.0f, 0.0f }, wb[3] = { 0.0f, 0.0f, 0.0f }, tF = 0.0f, tC = 0.0f;
+                V3 La = mk(0.0f, 0.0f, 0.0f), Lb = mk(0.0f, 0.0f, 0.0f);
+                if (draw && ok && mode != RLS_MIS_BSDF_ONLY) {
+                    float rx = bits_u01(tab[0][s] ^ scr[0]), ry = bits_u01(tab[1][s] ^ scr[1]);
+                    La = cone_sample(cone, rx, ry);
+                    if (dot(La, N) > 0.0f) {
+                        float fr, fg, fb, pb;
+                        ggx_eval_pdf<true, true>(g, La, fr, fg, fb, pb);
+                        float wgt = mode == RLS_MIS_LIGHT_ONLY ? 1.0f : power_heuristic(cone.pdf, pb);
+                        wa[0] = R_DIV(fr * wgt, cone.pdf); wa[1] = R_DIV(fg * wgt, cone.pdf); wa[2] = R_DIV(fb * wgt, cone.pdf);
+                    }
+                }
+                if (draw && ok && mode != RLS_MIS_LIGHT_ONLY) {
+                    float rx = bits_u01(tab[0][s] ^ scr[2]), ry = bits_u01(tab[1][s] ^ scr[3]);
+                    V3 M = vndf_microfacet(sl.w, g.fr, rx, ry);
+                    Lb = reflect_direction(g.view, M);
+                    tF = ggx_fresnel(g, Lb, M);                     // mReflectWeight += ..., mMisSampleCount += 1
+                    tC = 1.0f;
+                    if (!is_zero(Lb) && dot(Lb, N) > 0.0f && cone_hit(cone, Lb)) {
+                        float fr, fg, fb, pb;
+                        ggx_eval_pdf<true, true>(g, Lb, fr, fg, fb, pb);
+                        float wgt = mode == RLS_MIS_BSDF_ONLY ? 1.0f : power_heuristic(pb, cone.pdf);
+                        wb[0] = R_DIV(fr * wgt, pb); wb[1] = R_DIV(fg * wgt, pb); wb[2] = R_DIV(fb * wgt, pb);
+                    }
+                }
+                st.put_pair(cone, l, s, ok, La, wa, Lb, wb);
+                fold<G>(f, tF);
+                cnt += G == 1 ? tC : group_sum<G>(tC);
+            }
+        }
+        if (live && sub == 0) {
+            a.count[i] = st.run;
+            a.fsum[i] = f; a.fcnt[i] = cnt;
+        }
+    }
+}
+
+// A lobe's integrateGlossy (LOBE 0 sheen: stream pair 0; 1 specular: pair 1): GgxGlossy's rays on the lobe's closure, behind
+// the lobe's gates -- no rays for a weight <= AI_EPSILON (:191, :214) or a small colour (src/rlGgx.h:174-176).  The Fresnel
+// fold starts from the light loop's (sum, count); the side output is the layer's hand-down avg * weight (:204, :228): avg over
+// the light loops' samples alone for a small colour, 1 when nothing was drawn, and the scalar 0 where the weight shuts the lobe.
+template <int G, int LOBE>
+struct SkinGlossy : GgxGlossy<G> {
+    static constexpr int kStream = 2 * LOBE;
+    static constexpr bool kGated = true;
+    bool open, lobe_open;
+    float weight, cnt = 0.0f;
+    __device__ SkinGlossy(const SkinGlossyEmitIO &a, int64_t ii)
+    {
+        const SkinLobe sl = skin_lobe(a.c, ii, LOBE);
+        this->g = sl.g; this->w = sl.w;
+        weight = sl.weight;
+        lobe_open = weight > kEps;
+        open = lobe_open && !sl.small;
+        if (a.fsum) { this->accF = a.fsum[ii]; cnt = a.fcnt[ii]; }
+    }
+    __device__ float side(int spp) const
+    {
+        if (!lobe_open) return 0.0f;
+        const float fcnt = open ? cnt + (float)spp : cnt;
+        const float avg = fcnt > 0.0f ? R_DIV(this->accF, fcnt) : 1.0f;
+        return avg * weight;
+    }
+};
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void skin_sheen_glossy_emit_kernel(SkinGlossyEmitIO a)
+{
+    emit_points<G, SkinGlossy<G, 0>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void skin_specular_glossy_emit_kernel(SkinGlossyEmitIO a)
+{
+    emit_points<G, SkinGlossy<G, 1>>(a);
+}

@@ -181,6 +181,19 @@ def load() -> C.CDLL:
     return lib
 
 
+def _radiance(t: torch.Tensor, count: int, what: str) -> "capi.CRgb":
+    """one traced value per ray and channel: radiance, or a shadow ray's visibility"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.shape[0] != 3 or \
+            t.shape[1] < count or t.stride(1) != 1:
+        raise ValueError(f"{what}: expected a float32 CUDA tensor [3, >= {count}] with unit inner stride")
+    return capi.CRgb(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+
+
+def _points(P: torch.Tensor, n: int) -> "capi.CVec3":
+    """sg->P per point; an empty batch reads none"""
+    return cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
+
+
 def scratch_bytes(n: int, spp_n: int) -> int:
     b = C.c_size_t()
     check(load().rls_trace_scratch_bytes(int(n), int(spp_n), C.byref(b)))
@@ -288,11 +301,8 @@ class RayQueue:
         ``count``: the ray count when the caller knows it (skips the read of offsets[n], e.g. while recording a graph)."""
         ctx, n = self.ctx, self.n
         count = self.count if count is None else int(count)
-        if not isinstance(radiance, torch.Tensor) or radiance.dtype != torch.float32 or not radiance.is_cuda or \
-                radiance.dim() != 2 or radiance.shape[0] != 3 or radiance.shape[1] < count or radiance.stride(1) != 1:
-            raise ValueError(f"radiance: expected a float32 CUDA tensor [3, >= {count}] with unit inner stride")
+        L = _radiance(radiance, count, "radiance")
         res = ctx.empty(3, n) if out is None else out
-        L = capi.CRgb(radiance[0].data_ptr(), radiance[1].data_ptr(), radiance[2].data_ptr())
         lib = load()
         if self.scalar:
             check(lib.rls_trace_ggx_refract_resolve(ctx.handle, n, C.byref(self.q), self.spp_n, L, rgb(res, n, "result")))
@@ -341,6 +351,30 @@ def disney_rays(sampler: DisneySampler, lobe: int, spp_n: int, seed: int, first_
     return q
 
 
+def _probe_hits(count, P, N, irradiance, rays: int) -> ProbeHits_:
+    """The caller's hits of `rays` probe rays, validated, as rls_probe_hits (``ProbeQueue.resolve`` describes them).  The struct
+    holds pointers only: the tensors stay the caller's."""
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.uint8 or not count.is_cuda or count.dim() != 1 or \
+            count.shape[0] < rays or not count.is_contiguous():
+        raise ValueError(f"count: expected a contiguous uint8 CUDA tensor [>= {rays}]")
+    shape = None
+    for what, t in (("P", P), ("N", N), ("irradiance", irradiance)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or \
+                t.shape[0] != 3 or not 1 <= t.shape[1] <= RLS_MAX_PROBE_HITS or t.shape[2] < rays or \
+                t.stride(2) != 1 or t.stride(1) != t.shape[2]:
+            raise ValueError(f"{what}: expected a float32 CUDA tensor [3, 1..{RLS_MAX_PROBE_HITS}, >= {rays}] whose "
+                             f"planes are contiguous")
+        if shape is not None and t.shape != shape:
+            raise ValueError(f"{what}: shape {tuple(t.shape)} differs from P's {tuple(shape)}")
+        shape = t.shape
+    h = ProbeHits_()
+    h.max_hits, h.stride, h.count = int(shape[1]), int(shape[2]), count.data_ptr()
+    h.P = capi.CVec3(*[P[k].data_ptr() for k in range(3)])
+    h.N = capi.CVec3(*[N[k].data_ptr() for k in range(3)])
+    h.irradiance = capi.CRgb(*[irradiance[k].data_ptr() for k in range(3)])
+    return h
+
+
 class ProbeQueue:
     """integrateScatter's probe rays over n points at spp_n^2 samples: dense, point-major (ray j = i * spp_n^2 + s is sample s
     of point i; offsets[i] = i * spp_n^2).  ``count`` is known without reading the device."""
@@ -376,30 +410,13 @@ class ProbeQueue:
         sg->N, E before evalProfile and the cavity fade (include/rlshaders_amd_trace.h)."""
         if self.sampler is None:
             raise RuntimeError("resolve: no emit has filled this queue (trace.sss_probe_rays)")
-        ctx, n, rays = self.ctx, self.n, self.count
-        if not isinstance(count, torch.Tensor) or count.dtype != torch.uint8 or not count.is_cuda or count.dim() != 1 or \
-                count.shape[0] < rays or not count.is_contiguous():
-            raise ValueError(f"count: expected a contiguous uint8 CUDA tensor [>= {rays}]")
-        shape = None
-        for what, t in (("P", P), ("N", N), ("irradiance", irradiance)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or \
-                    t.shape[0] != 3 or not 1 <= t.shape[1] <= RLS_MAX_PROBE_HITS or t.shape[2] < rays or \
-                    t.stride(2) != 1 or t.stride(1) != t.shape[2]:
-                raise ValueError(f"{what}: expected a float32 CUDA tensor [3, 1..{RLS_MAX_PROBE_HITS}, >= {rays}] whose "
-                                 f"planes are contiguous")
-            if shape is not None and t.shape != shape:
-                raise ValueError(f"{what}: shape {tuple(t.shape)} differs from P's {tuple(shape)}")
-            shape = t.shape
-        h = ProbeHits_()
-        h.max_hits, h.stride, h.count = int(shape[1]), int(shape[2]), count.data_ptr()
-        h.P = capi.CVec3(*[P[k].data_ptr() for k in range(3)])
-        h.N = capi.CVec3(*[N[k].data_ptr() for k in range(3)])
-        h.irradiance = capi.CRgb(*[irradiance[k].data_ptr() for k in range(3)])
+        ctx, n = self.ctx, self.n
+        h = _probe_hits(count, P, N, irradiance, self.count)
         res = ctx.empty(3, n) if out is None else out
         depth = (ctx.empty(n) if depth_out is None else depth_out) if want_depth else None
         s = self.sampler
         check(load().rls_trace_sss_scatter_resolve(
-            ctx.handle, n, C.byref(s.c), cvec3(self.P, n, "P"), self.spp_n, C.byref(self.q), C.byref(h),
+            ctx.handle, n, C.byref(s.c), _points(self.P, n), self.spp_n, C.byref(self.q), C.byref(h),
             1 if use_cavity_fade else 0, 1 if literal_matrix else 0, rgb(res, n, "result"),
             plane(depth, n, "mean_depth") if want_depth else None))
         return (res, depth) if want_depth else res
@@ -413,8 +430,7 @@ def sss_probe_rays(sampler: SssSampler, P: torch.Tensor, spp_n: int, seed: int, 
     q = ProbeQueue(ctx, n, spp_n) if queue is None else queue
     if q.n != n or q.spp_n != int(spp_n):
         raise ValueError("queue: allocated for another batch size or spp_n")
-    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
-    check(load().rls_trace_sss_probe_emit(ctx.handle, n, C.byref(sampler.c), Pv, int(spp_n), int(seed) & 0xFFFFFFFF,
+    check(load().rls_trace_sss_probe_emit(ctx.handle, n, C.byref(sampler.c), _points(P, n), int(spp_n), int(seed) & 0xFFFFFFFF,
                                           int(first_index), C.byref(q.q)))
     q.sampler, q.P = sampler, P
     return q
@@ -528,12 +544,8 @@ class ShadowQueue:
             raise RuntimeError("resolve: no emit has filled this queue (trace.ggx_shadow_rays / disney_shadow_rays)")
         ctx, n = self.ctx, self.n
         count = self.count if count is None else int(count)
-        v = visibility
-        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or not v.is_cuda or v.dim() != 2 or v.shape[0] != 3 or \
-                v.shape[1] < count or v.stride(1) != 1:
-            raise ValueError(f"visibility: expected a float32 CUDA tensor [3, >= {count}] with unit inner stride")
+        vis = _radiance(visibility, count, "visibility")
         dd, ds = out if out is not None else (ctx.empty(3, n), ctx.empty(3, n))
-        vis = capi.CRgb(v[0].data_ptr(), v[1].data_ptr(), v[2].data_ptr())
         lights, nl = self.lights
         lib = load()
         if self.disney:
@@ -561,9 +573,8 @@ def ggx_shadow_rays(sampler: GgxSampler, shader: "capi.GgxShader", P: torch.Tens
     ``lights``: one ``make_light`` or a sequence; P: [3, n] float32, sg->P per point."""
     ctx, n = sampler.ctx, sampler.n
     q, la, nl = _shadow_queue(sampler, lights, spp_n, queue, False)
-    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
-    check(load().rls_trace_ggx_direct_emit(ctx.handle, n, C.byref(sampler.c), C.byref(shader), Pv, la, nl, int(spp_n),
-                                           int(seed) & 0xFFFFFFFF, int(first_index), C.byref(q.q)))
+    check(load().rls_trace_ggx_direct_emit(ctx.handle, n, C.byref(sampler.c), C.byref(shader), _points(P, n), la, nl,
+                                           int(spp_n), int(seed) & 0xFFFFFFFF, int(first_index), C.byref(q.q)))
     q.lights, q.sampler, q.shader, q.P = (la, nl), sampler, shader, P
     return q
 
@@ -573,8 +584,7 @@ def disney_shadow_rays(sampler: DisneySampler, P: torch.Tensor, lights, spp_n: i
     """The shadow rays of rlDisney's light loop (src/rlDisney.cpp:695-705): the samples rls_disney_direct_lighting draws."""
     ctx, n = sampler.ctx, sampler.n
     q, la, nl = _shadow_queue(sampler, lights, spp_n, queue, True)
-    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
-    check(load().rls_trace_disney_direct_emit(ctx.handle, n, C.byref(sampler.c), Pv, la, nl, int(spp_n),
+    check(load().rls_trace_disney_direct_emit(ctx.handle, n, C.byref(sampler.c), _points(P, n), la, nl, int(spp_n),
                                               int(seed) & 0xFFFFFFFF, int(first_index), C.byref(q.q)))
     q.lights, q.sampler, q.P = (la, nl), sampler, P
     return q
@@ -584,13 +594,6 @@ def disney_shadow_rays(sampler: DisneySampler, P: torch.Tensor, lights, spp_n: i
 # Whole nodes: every ray of rls_ggx_shade / rls_disney_shade in one emit, their AOVs in one resolve
 
 
-def _radiance(t: torch.Tensor, count: int, what: str) -> "capi.CRgb":
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.shape[0] != 3 or \
-            t.shape[1] < count or t.stride(1) != 1:
-        raise ValueError(f"{what}: expected a float32 CUDA tensor [3, >= {count}] with unit inner stride")
-    return capi.CRgb(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-
-
 def node_scratch_bytes(n: int, n_lights: int, spp_n: int) -> int:
     """The scratch block the queues of one node emit can share: the largest any of them needs."""
     b = scratch_bytes(n, spp_n)
@@ -598,11 +601,19 @@ def node_scratch_bytes(n: int, n_lights: int, spp_n: int) -> int:
 
 
 class _NodeQueues:
-    """What the two nodes' queue sets share: the shadow queue (None without lights), the ray queues by member name, the
-    C struct, what the last emit took."""
+    """What the nodes' queue sets share, each node describing its members: the shadow queues (None without lights), the ray
+    queues and rlSkin's probe queue by member name, the C struct, the emit's C call, what the last emit took."""
+    SHADOWS = ("shadow",)    # the ShadowQueue members and ShadowQueue's keyword arguments
+    SHADOW_KW = {}
     RAY_MEMBERS = ()         # (member name, RayQueue's keyword arguments) per ray queue, in the C struct's order
-    RAYS = ()                # the member names
-    disney = False
+    RAYS = ()                # their names (__init_subclass__)
+    SCALARS = ()             # rlSkin: ``probes`` (a ProbeQueue) and these [n] planes follow the ray queues
+    STRUCT = None            # the C struct of the set, the name of the emit's C call
+    EMIT = ""
+    shadow = None            # (a node that names its shadow queues otherwise has none of this name)
+
+    def __init_subclass__(cls):
+        cls.RAYS = tuple(name for name, _ in cls.RAY_MEMBERS)
 
     def __init__(self, ctx, n: int, n_lights: int, spp_n: int, share_scratch: bool = False):
         self.ctx, self.n, self.n_lights, self.spp_n = ctx, int(n), int(n_lights), int(spp_n)
@@ -611,24 +622,33 @@ class _NodeQueues:
             scratch = torch.empty(max(node_scratch_bytes(self.n, self.n_lights, self.spp_n), 1), dtype=torch.uint8,
                                   device=ctx.torch_device)
         self.scratch = scratch
-        self._make_shadow_queues(scratch)
+        for name in self.SHADOWS:
+            setattr(self, name, ShadowQueue(ctx, self.n, self.n_lights, self.spp_n, scratch=scratch, **self.SHADOW_KW)
+                    if self.n_lights > 0 else None)
         for name, kw in self.RAY_MEMBERS:
             setattr(self, name, RayQueue(ctx, n, spp_n, scratch=scratch, **kw))
+        if self.SCALARS:
+            self.probes = ProbeQueue(ctx, n, spp_n)
+            for name in self.SCALARS:
+                setattr(self, name, torch.empty(self.n, dtype=torch.float32, device=ctx.torch_device))
         self.lights = None
         self.sampler = None
         self.shader = None
+        self.P = None
         self.traced = True
 
-    def _make_shadow_queues(self, scratch):
-        """the node's light loop(s): one queue, ``shadow`` (None without lights)"""
-        self.shadow = ShadowQueue(self.ctx, self.n, self.n_lights, self.spp_n, self.disney, scratch=scratch) \
-            if self.n_lights > 0 else None
+    def _queues(self) -> dict:
+        """the compacted queues by member name, in the C struct's order"""
+        return {name: getattr(self, name) for name in self.SHADOWS + self.RAYS}
 
-    def _struct(self, cls):
-        q = cls()
-        q.shadow = C.pointer(self.shadow.q) if self.shadow is not None else None
-        for name, _ in self.RAY_MEMBERS:
-            setattr(q, name, C.pointer(getattr(self, name).q))
+    def _struct(self):
+        q = self.STRUCT()
+        for name, m in self._queues().items():
+            setattr(q, name, C.pointer(m.q) if m is not None else None)
+        if self.SCALARS:
+            q.probes = C.pointer(self.probes.q)
+            for name in self.SCALARS:
+                setattr(q, name, getattr(self, name).data_ptr())
         return q
 
     def _matches(self, sampler, nl: int, spp_n: int) -> bool:
@@ -646,10 +666,8 @@ class _NodeQueues:
         return out, o
 
     def counts(self) -> dict:
-        """the ray count of every queue (reads the device: synchronises)"""
-        c = {"shadow": self.shadow.count if self.shadow is not None else 0}
-        c.update({name: getattr(self, name).count for name, _ in self.RAY_MEMBERS})
-        return c
+        """the ray count of every compacted queue (reads the device: synchronises); rlSkin's probe queue is dense"""
+        return {name: m.count if m is not None else 0 for name, m in self._queues().items()}
 
 
 class GgxNodeQueues(_NodeQueues):
@@ -657,7 +675,7 @@ class GgxNodeQueues(_NodeQueues):
     (3 weight planes), ``refract`` (weight [1, count], kind) and ``diffuse`` (weight [1, count]) RayQueues -- the samples
     ``GgxSampler.shade`` draws."""
     RAY_MEMBERS = (("glossy", {}), ("refract", {"refract": True}), ("diffuse", {"planes": 1}))
-    RAYS = ("glossy", "refract", "diffuse")
+    STRUCT, EMIT = GgxNodeQueues_, "rls_trace_ggx_shade_emit"
 
     def resolve(self, visibility, glossy, refract, diffuse, out=None, counts: Optional[dict] = None) -> dict:
         """What the renderer traced, [3, >= count] float32 per queue (``visibility`` is not read without lights and may be
@@ -674,7 +692,7 @@ class GgxNodeQueues(_NodeQueues):
         t.diffuse = _radiance(diffuse, cnt["diffuse"], "diffuse")
         out, o = self._out(self.sampler, out, capi.GgxShadeOut)
         la, nl = self.lights
-        q = self._struct(GgxNodeQueues_)
+        q = self._struct()
         check(load().rls_trace_ggx_shade_resolve(self.ctx.handle, self.n, C.byref(self.sampler.c), C.byref(self.shader), la, nl,
                                                  1 if self.traced else 0, self.spp_n, C.byref(q), C.byref(t), C.byref(o)))
         return out
@@ -683,9 +701,9 @@ class GgxNodeQueues(_NodeQueues):
 class DisneyNodeQueues(_NodeQueues):
     """The rays of the whole rlDisney node (rls_trace_disney_shade_emit): ``shadow`` (None without lights), ``diffuse`` and
     ``specular`` RayQueues -- the samples ``DisneySampler.shade`` draws."""
+    SHADOW_KW = {"disney": True}
     RAY_MEMBERS = (("diffuse", {"lobe": RLS_RAY_DIFFUSE}), ("specular", {"lobe": RLS_RAY_GLOSSY}))
-    RAYS = ("diffuse", "specular")
-    disney = True
+    STRUCT, EMIT = DisneyNodeQueues_, "rls_trace_disney_shade_emit"
 
     def resolve(self, visibility, diffuse, specular, out=None, counts: Optional[dict] = None) -> dict:
         """-> the dict ``DisneySampler.shade`` returns: the four AOVs and out, [3, n] each."""
@@ -699,10 +717,33 @@ class DisneyNodeQueues(_NodeQueues):
         t.specular = _radiance(specular, cnt["specular"], "specular")
         out, o = self._out(self.sampler, out, capi.DisneyShadeOut)
         la, nl = self.lights
-        q = self._struct(DisneyNodeQueues_)
+        q = self._struct()
         check(load().rls_trace_disney_shade_resolve(self.ctx.handle, self.n, la, nl, self.spp_n, C.byref(q), C.byref(t),
                                                     C.byref(o)))
         return out
+
+
+def _node_emit(cls, sampler, shader, P, lights, spp_n: int, seed: int, first_index: int, queues, share_scratch: bool,
+               traced: Optional[bool] = None):
+    """One node emit into a queue set of class ``cls`` (``queues``, or a new one): the C call takes the closure, the node
+    parameters where the node has them (``shader``), P and the lights, ``traced`` where the node has the switch, then the
+    sampling and the queues.  The set -- and its ``shadow`` queue, which resolves by itself too -- remembers what the emit took."""
+    ctx, n = sampler.ctx, sampler.n
+    la, nl = light_array(lights)
+    q = cls(ctx, n, nl, spp_n, share_scratch) if queues is None else queues
+    if not q._matches(sampler, nl, spp_n):
+        raise ValueError("queues: allocated for another batch size, light count or spp_n")
+    cq = q._struct()
+    closure = (C.byref(sampler.c),) if shader is None else (C.byref(sampler.c), C.byref(shader))
+    switch = () if traced is None else (1 if traced else 0,)
+    check(getattr(load(), cls.EMIT)(ctx.handle, n, *closure, _points(P, n), la, nl, *switch, int(spp_n), int(seed) & 0xFFFFFFFF,
+                                    int(first_index), C.byref(cq)))
+    for m in (q, q.shadow):
+        if m is not None:
+            m.lights, m.sampler, m.shader, m.P = (la, nl), sampler, shader, P
+    if traced is not None:
+        q.traced = bool(traced)
+    return q
 
 
 def ggx_node_rays(sampler: GgxSampler, shader: "capi.GgxShader", P: torch.Tensor, lights, spp_n: int, seed: int,
@@ -712,38 +753,14 @@ def ggx_node_rays(sampler: GgxSampler, shader: "capi.GgxShader", P: torch.Tensor
     rays, integrateGlossy (stream pair 24), integrateRefract (25; ``traced=False``: the one ray of the untraced branch) and the
     Oren-Nayar indirect diffuse loop (26), behind the node's gates.  ``shader``: ``trace.ggx_shader`` with KtColor / Kt;
     ``lights``: None, one ``make_light`` or a sequence.  ``share_scratch``: the queues share one scratch block."""
-    ctx, n = sampler.ctx, sampler.n
-    la, nl = light_array(lights)
-    q = GgxNodeQueues(ctx, n, nl, spp_n, share_scratch) if queues is None else queues
-    if not q._matches(sampler, nl, spp_n):
-        raise ValueError("queues: allocated for another batch size, light count or spp_n")
-    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
-    cq = q._struct(GgxNodeQueues_)
-    check(load().rls_trace_ggx_shade_emit(ctx.handle, n, C.byref(sampler.c), C.byref(shader), Pv, la, nl, 1 if traced else 0,
-                                          int(spp_n), int(seed) & 0xFFFFFFFF, int(first_index), C.byref(cq)))
-    q.lights, q.sampler, q.shader, q.P, q.traced = (la, nl), sampler, shader, P, bool(traced)
-    if q.shadow is not None:
-        q.shadow.lights, q.shadow.sampler, q.shadow.shader, q.shadow.P = (la, nl), sampler, shader, P
-    return q
+    return _node_emit(GgxNodeQueues, sampler, shader, P, lights, spp_n, seed, first_index, queues, share_scratch, bool(traced))
 
 
 def disney_node_rays(sampler: DisneySampler, P: torch.Tensor, lights, spp_n: int, seed: int, first_index: int = 0,
                      queues: Optional[DisneyNodeQueues] = None, share_scratch: bool = False) -> DisneyNodeQueues:
     """Every ray of rlDisney's shader_evaluate (src/rlDisney.cpp:685-727) as ``DisneySampler.shade`` samples it: the light
     loop's shadow rays, integrateDiffuse (stream pair 24) and integrateGlossy (25)."""
-    ctx, n = sampler.ctx, sampler.n
-    la, nl = light_array(lights)
-    q = DisneyNodeQueues(ctx, n, nl, spp_n, share_scratch) if queues is None else queues
-    if not q._matches(sampler, nl, spp_n):
-        raise ValueError("queues: allocated for another batch size, light count or spp_n")
-    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
-    cq = q._struct(DisneyNodeQueues_)
-    check(load().rls_trace_disney_shade_emit(ctx.handle, n, C.byref(sampler.c), Pv, la, nl, int(spp_n),
-                                             int(seed) & 0xFFFFFFFF, int(first_index), C.byref(cq)))
-    q.lights, q.sampler, q.P = (la, nl), sampler, P
-    if q.shadow is not None:
-        q.shadow.lights, q.shadow.sampler, q.shadow.P = (la, nl), sampler, P
-    return q
+    return _node_emit(DisneyNodeQueues, sampler, None, P, lights, spp_n, seed, first_index, queues, share_scratch)
 
 
 class SkinNodeQueues(_NodeQueues):
@@ -752,41 +769,11 @@ class SkinNodeQueues(_NodeQueues):
     n * n_lights * 2 * spp_n^2) and a RayQueue of its integrateGlossy (``sheen_glossy``, ``specular_glossy``), and the ProbeQueue
     of integrateScatter (``probes``) -- the samples ``SkinShader.integrate`` draws.  ``sheenFresnel``, ``specularFresnel``,
     ``sssWeight`` [n]: the layers' hand-down scalars, written by the emit."""
-    RAY_MEMBERS = (("sheen_glossy", {}), ("specular_glossy", {}))
-    RAYS = ("sheen_glossy", "specular_glossy")
     SHADOWS = ("sheen_shadow", "specular_shadow")
-
-    def _make_shadow_queues(self, scratch):
-        """a light loop per lobe"""
-        self.shadow = None
-        for name in self.SHADOWS:
-            setattr(self, name, ShadowQueue(self.ctx, self.n, self.n_lights, self.spp_n, scratch=scratch, skin=True)
-                    if self.n_lights > 0 else None)
-
-    def __init__(self, ctx, n: int, n_lights: int, spp_n: int, share_scratch: bool = False):
-        super().__init__(ctx, n, n_lights, spp_n, share_scratch)
-        self.probes = ProbeQueue(ctx, n, spp_n)
-        self.sheenFresnel, self.specularFresnel, self.sssWeight = (torch.empty(self.n, dtype=torch.float32,
-                                                                               device=ctx.torch_device) for _ in range(3))
-        self.P = None
-
-    def _struct(self, cls=None):
-        q = SkinNodeQueues_()
-        for name in self.SHADOWS:
-            sq = getattr(self, name)
-            setattr(q, name, C.pointer(sq.q) if sq is not None else None)
-        for name in self.RAYS:
-            setattr(q, name, C.pointer(getattr(self, name).q))
-        q.probes = C.pointer(self.probes.q)
-        q.sheenFresnel, q.specularFresnel, q.sssWeight = (t.data_ptr() for t in (self.sheenFresnel, self.specularFresnel,
-                                                                                 self.sssWeight))
-        return q
-
-    def counts(self) -> dict:
-        """the ray count of every compacted queue (reads the device: synchronises); the probe queue is dense"""
-        c = {name: (getattr(self, name).count if getattr(self, name) is not None else 0) for name in self.SHADOWS}
-        c.update({name: getattr(self, name).count for name in self.RAYS})
-        return c
+    SHADOW_KW = {"skin": True}
+    RAY_MEMBERS = (("sheen_glossy", {}), ("specular_glossy", {}))
+    SCALARS = ("sheenFresnel", "specularFresnel", "sssWeight")
+    STRUCT, EMIT = SkinNodeQueues_, "rls_trace_skin_emit"
 
     def resolve(self, sheen_visibility, specular_visibility, sheen_glossy, specular_glossy, count, P, N, irradiance,
                 use_cavity_fade: bool = False, literal_matrix: bool = False, out=None, counts: Optional[dict] = None) -> dict:
@@ -797,7 +784,7 @@ class SkinNodeQueues(_NodeQueues):
         offsets[n], e.g. while recording a graph)."""
         if self.sampler is None:
             raise RuntimeError("resolve: no emit has filled these queues (trace.skin_node_rays)")
-        ctx, n, rays = self.ctx, self.n, self.probes.count
+        ctx, n = self.ctx, self.n
         cnt = self.counts() if counts is None else counts
         t = SkinNodeTraced_()
         if self.n_lights > 0:
@@ -805,38 +792,23 @@ class SkinNodeQueues(_NodeQueues):
             t.specular_visibility = _radiance(specular_visibility, cnt["specular_shadow"], "specular_visibility")
         t.sheen_glossy = _radiance(sheen_glossy, cnt["sheen_glossy"], "sheen_glossy")
         t.specular_glossy = _radiance(specular_glossy, cnt["specular_glossy"], "specular_glossy")
-        if not isinstance(count, torch.Tensor) or count.dtype != torch.uint8 or not count.is_cuda or count.dim() != 1 or \
-                count.shape[0] < rays or not count.is_contiguous():
-            raise ValueError(f"count: expected a contiguous uint8 CUDA tensor [>= {rays}]")
-        shape = None
-        for what, h in (("P", P), ("N", N), ("irradiance", irradiance)):
-            if not isinstance(h, torch.Tensor) or h.dtype != torch.float32 or not h.is_cuda or h.dim() != 3 or \
-                    h.shape[0] != 3 or not 1 <= h.shape[1] <= RLS_MAX_PROBE_HITS or h.shape[2] < rays or \
-                    h.stride(2) != 1 or h.stride(1) != h.shape[2] or (shape is not None and h.shape != shape):
-                raise ValueError(f"{what}: expected a float32 CUDA tensor [3, 1..{RLS_MAX_PROBE_HITS}, >= {rays}] whose "
-                                 f"planes are contiguous, of one shape with the other hit planes")
-            shape = h.shape
-        hits = ProbeHits_()
-        hits.max_hits, hits.stride, hits.count = int(shape[1]), int(shape[2]), count.data_ptr()
-        hits.P = capi.CVec3(*[P[k].data_ptr() for k in range(3)])
-        hits.N = capi.CVec3(*[N[k].data_ptr() for k in range(3)])
-        hits.irradiance = capi.CRgb(*[irradiance[k].data_ptr() for k in range(3)])
+        hits = _probe_hits(count, P, N, irradiance, self.probes.count)
         t.hits = C.pointer(hits)
         if out is None:
             out = {k: ctx.empty(3, n) for k in ("sheen", "specular", "sss", "out")}
-            out.update({k: ctx.empty(n) for k in ("sheenFresnel", "specularFresnel", "sssWeight")})
+            out.update({k: ctx.empty(n) for k in self.SCALARS})
         o = capi.SkinIntegrateOut()
         for k in ("sheen", "specular", "sss", "out"):
             if k in out:
                 setattr(o, k, rgb(out[k], n, k))
-        for k in ("sheenFresnel", "specularFresnel", "sssWeight"):
+        for k in self.SCALARS:
             if k in out:
                 setattr(o, k, plane(out[k], n, k))
         la, nl = self.lights
         q = self._struct()
-        check(load().rls_trace_skin_resolve(ctx.handle, n, C.byref(self.sampler.c), cvec3(self.P, n, "P") if n > 0 else
-                                            capi.CVec3(None, None, None), la, nl, 1 if use_cavity_fade else 0,
-                                            1 if literal_matrix else 0, self.spp_n, C.byref(q), C.byref(t), C.byref(o)))
+        check(load().rls_trace_skin_resolve(ctx.handle, n, C.byref(self.sampler.c), _points(self.P, n), la, nl,
+                                            1 if use_cavity_fade else 0, 1 if literal_matrix else 0, self.spp_n, C.byref(q),
+                                            C.byref(t), C.byref(o)))
         return out
 
 
@@ -846,14 +818,4 @@ def skin_node_rays(shader, P: torch.Tensor, lights, spp_n: int, seed: int, first
     light loop's shadow rays and integrateGlossy's rays (stream pairs 0 and 1), then integrateScatter's probe rays (pair 2).
     ``shader``: a ``SkinShader``; ``lights``: None, one ``make_light`` or a sequence; P: [3, n] float32, sg->P per point.
     ``share_scratch``: the queues share one scratch block."""
-    ctx, n = shader.ctx, shader.n
-    la, nl = light_array(lights)
-    q = SkinNodeQueues(ctx, n, nl, spp_n, share_scratch) if queues is None else queues
-    if not q._matches(shader, nl, spp_n):
-        raise ValueError("queues: allocated for another batch size, light count or spp_n")
-    Pv = cvec3(P, n, "P") if n > 0 else capi.CVec3(None, None, None)
-    cq = q._struct()
-    check(load().rls_trace_skin_emit(ctx.handle, n, C.byref(shader.c), Pv, la, nl, int(spp_n), int(seed) & 0xFFFFFFFF,
-                                     int(first_index), C.byref(cq)))
-    q.lights, q.sampler, q.P = (la, nl), shader, P
-    return q
+    return _node_emit(SkinNodeQueues, shader, None, P, lights, spp_n, seed, first_index, queues, share_scratch)

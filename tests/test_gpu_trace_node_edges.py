@@ -27,7 +27,7 @@ upright frame under lights that cover the hemisphere, a low roughness), a point 
 from below or every lobe gated), and the nodes' gates; every test asserts that both extremes occur in every compacted queue.
 
 Tile constants (named here, read from the sources below): kBlock 256 (rls_internal.hpp); kScanTile 2048, kCompactSlots 4096,
-kCompactMaxPoints 256, kShadowMaxSlots 6144 (rls_trace_device.hpp); kShadowTile = kResolveTile 1024 (trace.hip); the scatter
+kCompactMaxPoints 256, kShadowMaxSlots 6144, kShadowTile = kResolveTile 1024 (rls_trace_device.hpp); the scatter
 walk's sub-tile kBlock / spp points (sss_resolve_tile_points)."""
 import os
 import re
@@ -52,8 +52,8 @@ from trace_lights_util import assert_float64_bound, compose, queue_host
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
-_SRC = "".join((ROOT / "rlshaders_amd" / p).read_text() for p in ("csrc/rls_internal.hpp", "csrc_trace/rls_trace_device.hpp",
-                                                                 "csrc_trace/trace.hip"))
+_SRC = "".join(p.read_text() for p in [ROOT / "rlshaders_amd" / "csrc" / "rls_internal.hpp",
+                                       *sorted((ROOT / "rlshaders_amd" / "csrc_trace").iterdir())])
 
 
 def _const(name):

@@ -256,3 +256,16 @@ def test_a_resolve_of_nothing_succeeds_without_a_device(trace_lib, node):
     assert w.resolve() == 0
     w.spp_n = 17
     assert w.resolve() == INVALID
+
+
+@pytest.mark.parametrize("node", ["ggx", "disney"])
+def test_an_emit_refused_at_its_last_ray_queue_launches_nothing(trace_lib, node):
+    """A valid call but for the last-checked argument of the last ray queue, its scratch one byte short: every check of a
+    node emit runs ahead of its first launch, so the call is refused with the entry point's name before the (dummy) context
+    is read -- the light loop's emit, first in stream order, included."""
+    from rlshaders_amd import _capi as capi
+    w = World(node)
+    _last_ray(w).scratch_bytes -= 1
+    assert w.emit() == INVALID
+    assert capi.load().rls_last_error().decode() == \
+        f"rls_trace_{node}_shade_emit: queue.scratch is NULL or smaller than rls_trace_scratch_bytes"

@@ -250,3 +250,17 @@ def test_a_resolve_of_nothing_succeeds_without_a_device(trace_lib):
     assert w.resolve() == 0
     w.spp_n = 17
     assert w.resolve() == INVALID
+
+
+@pytest.mark.parametrize("node", ["skin"])
+def test_an_emit_refused_at_its_last_shadow_queue_launches_nothing(trace_lib, node):
+    """A valid call but for the last-checked argument of the last queue, the second lobe's shadow scratch too small (World
+    sizes it with rls_trace_shadow_scratch_bytes, more than a lobe's two-segment loop needs: hence 16 bytes, not one byte less):
+    every check of the node emit runs ahead of its first launch, so the call is refused with the entry point's name before the
+    (dummy) context is read -- the first lobe's emits, earlier in stream order, included."""
+    from rlshaders_amd import _capi as capi
+    w = World()
+    w.shadows[1].scratch_bytes = 16
+    assert w.emit() == INVALID
+    assert capi.load().rls_last_error().decode() == \
+        f"rls_trace_{node}_emit: queue.scratch is NULL or smaller than rls_trace_shadow_scratch_bytes"
