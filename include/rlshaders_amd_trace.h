@@ -107,8 +107,10 @@ rls_status rls_trace_ggx_refract_resolve(rls_context *ctx, int64_t n, const rls_
  *          maxdist), continued past each hit;
  *        - skip hits on other objects than the shading point's own (the probe's object test);
  *        - report sg->Ns at the hit aligned to sg->N as shadeProbeSample does (alignDir, src/rlSss.h:393-398);
- *        - evaluate its light loop at the hit (and, optionally, integrateDiffuse, src/rlSss.h:456-484) and report
- *          E = direct + indirect / pi: the irradiance BEFORE evalProfile and the cavity fade.
+ *        - report E = direct + indirect / pi at the hit: the irradiance BEFORE evalProfile and the cavity fade.  Either
+ *          hand the hits to rls_trace_sss_hits_emit / _resolve (below, after the light loops), which emit the shadow rays of
+ *          evalLightSample's light loop and integrateDiffuse's ray at every shaded hit and fill E from what the renderer
+ *          traced for them; or evaluate both in the renderer's own code.
  *      The reference computes (direct * profile + indirect * profile) * fade; with one E it is (E * profile) * fade.
  *      With an indirect term of 0 the two are the same; otherwise they may differ by one rounding.
  *   3. rls_trace_sss_scatter_resolve: per point, the hits combined exactly as the integrator combines its own: the
@@ -236,6 +238,87 @@ rls_status rls_trace_ggx_direct_resolve(rls_context *ctx, int64_t n, const rls_g
 rls_status rls_trace_disney_direct_resolve(rls_context *ctx, int64_t n, const rls_sphere_light *lights, int n_lights,
                                            int spp_n, const rls_shadow_queue *q, rls_crgb visibility,
                                            rls_rgb direct_diffuse, rls_rgb direct_specular);
+
+/* ------------------------------------------------------------------------------------------
+ * rlSss: shadeProbeSample's shading of the probe hits (src/rlSss.h:415-418) cut where it traces: evalLightSample (:439-454),
+ * an Oren-Nayar MIS light loop at roughness 0, and integrateDiffuse (:456-484), one cosine-weighted ray.  With these the
+ * renderer traces only: the probe rays; the shadow rays and diffuse rays leaving the hits; and rls_trace_sss_scatter_resolve /
+ * rls_trace_skin_resolve, unchanged, run on the E planes filled here.
+ *
+ *   1. rls_trace_sss_hits_emit: lists the hits the scatter resolves count as shaded and emits, per listed hit, the light
+ *      loop's shadow rays and (trace_diffuse) the diffuse ray, into two compacted queues over the LIST;
+ *   2. (the renderer traces the shadow rays from the hit's position P[hit_element[point]] for a visibility, the diffuse rays
+ *      for a radiance);
+ *   3. rls_trace_sss_hits_resolve: E at every element of the hit planes.
+ *
+ * Which hits are listed: exactly those rls_trace_sss_scatter_resolve counts as shaded, by the one copy of its gate.  Per ray j,
+ * with prev = P of the ray's point and the slots k < min(count[j], max_hits) in order, a hit is kept if |prev - hit| >
+ * AI_EPSILON (then prev = hit), |hit - P| <= maxRadius and, where use_cavity_fade is set, fade > AI_EPSILON: the reference's
+ * condition for calling evalLightSample / integrateDiffuse (:386, :415).  hit_element holds the kept hits' elements
+ * k * stride + j, ray-major: j ascending, k ascending within a ray.
+ *
+ * Overflow: hits past hit_capacity are not listed and nothing is written past any capacity; hit_count still holds the true
+ * number, and offsets[h] = offsets[min(hit_count, hit_capacity)] for every later h, so that offsets[hit_capacity] is the ray
+ * count, as offsets[n] is elsewhere.
+ *
+ * Samples: the listed hit with element e draws from hash(seed, hit_first_index + e) -- by its element, not by its place in
+ * the list -- the context's math mode applies, and light l uses the scramble streams 6 l .. 6 l + 5 exactly as
+ * rls_trace_ggx_direct_emit does: segment 0 the light strategy (streams +0/1), segment 1 the diffuse BSDF strategy (streams
+ * +4/5); there is no specular segment; mis_mode applies per light.  The closure is AiOrenNayarMISCreateData(sg, 0.0f) about the
+ * hit's normal, its view along that normal (at roughness 0 the lobe reads the view only to test its side).  The frame is
+ * (hitN, hitT, hitN x hitT); with hitT NULL the tangent is T = (1 + sg Nx Nx a, sg (Nx Ny a), -sg Nx), sg = copysign(1, Nz),
+ * a = -1 / (sg + Nz), in IEEE float32 operations in either math mode: a stand-in for the closed AiBuildLocalFramePolar, which
+ * this library takes as an input everywhere else.  maxdist, kind, the order of a hit's rays (lights ascending; within a light
+ * segment 0, then 1; samples ascending) and sample are rls_shadow_queue's; point is the hit's index in the LIST.  So the rays of
+ * element e are the diffuse-carrying rays rls_trace_ggx_direct_emit queues for a point with P = hitP[e], N = wo = hitN[e],
+ * T = hitT[e], diffuseRoughness 0 and a KdColor * Kd that is not small, first_index = hit_first_index + e.
+ *
+ * Diffuse ray (trace_diffuse != 0; the reference asserts one sample, :481): dir = sampleDiffuseDirection(rx, ry, hitN) in the
+ * frame above (rls_sss_sample_diffuse_direction), (rx, ry) the first point of the scrambled (0,2) sequence at stream pair 24 of
+ * the same hash (what the nodes' indirect loops draw at spp_n = 1); weight.r = CLAMP(N . dir, 0, 1); queued unless the weight is
+ * 0.  point is the hit's list index, sample 0; kind is not meaningful.
+ *
+ * Resolve: E is written at every one of the max_hits * stride elements, exactly 0 where the hit is not listed.  At a listed
+ * hit direct = the light loop's diffuse sum exactly as rls_trace_ggx_direct_resolve forms it before its KdColor * Kd tail (four
+ * sums a light, (radiance[l] * s) * (1 / hit_spp_n^2), the first light assigns, later lights add; black at n_lights == 0), and
+ * E_c = direct_c + (radiance_c * weight) * AI_ONEOVERPI where the hit has a diffuse ray, else direct_c.  A term absent from a
+ * queue never meets a visibility or a radiance.
+ *
+ * No call synchronises the host; both can be recorded into an rls_graph.  The list's length stays on the device: the emit
+ * and the resolve run over hit_capacity entries and skip those past hit_count.
+ * ---------------------------------------------------------------------------------------- */
+
+typedef struct rls_hit_queues {
+    int64_t hit_capacity;    /* shaded hits the lists below hold (at most 2^32 - 1) */
+    int64_t *hit_count;      /* [1], device, required: the TRUE number of shaded hits, also when it exceeds hit_capacity */
+    int64_t *hit_element;    /* [hit_capacity], required: element k * stride + j of rls_probe_hits, ray-major */
+    rls_shadow_queue shadow; /* offsets [hit_capacity + 1], CSR over the hit LIST; point = list index; weight_diffuse.r only,
+                                weight_specular NULL-able and never written; capacity >= hit_capacity * n_lights * 2 *
+                                hit_spp_n^2; its scratch members are not read.  Not read at all when n_lights == 0 */
+    rls_ray_queue diffuse;   /* integrateDiffuse's ray: offsets [hit_capacity + 1], dir, weight.r; at most one per listed hit:
+                                capacity >= hit_capacity; its scratch members are not read.  Unused when trace_diffuse == 0 */
+    void *scratch;           /* device, >= rls_trace_sss_hits_scratch_bytes(...) bytes: the list's and both emits' staging */
+    size_t scratch_bytes;
+} rls_hit_queues;
+
+/* Device scratch a hits emit of n points at spp_n^2 probe rays needs for this list capacity, light count and hit_spp_n. */
+rls_status rls_trace_sss_hits_scratch_bytes(int64_t n, int spp_n, int max_hits, int64_t hit_capacity, int n_lights,
+                                            int hit_spp_n, size_t *bytes);
+
+/* c, P, spp_n, q, use_cavity_fade: those of the scatter resolve the hits go to (q: only the capacity is read).  h: count, P
+ * and N are read, irradiance is not.  hitT: the tangent at each hit in the hit planes' layout, all three planes NULL for the
+ * library's own.  lights: n_lights in 0 .. RLS_MAX_LIGHTS.  hit_spp_n: the light loop's samples per hit are hit_spp_n^2. */
+rls_status rls_trace_sss_hits_emit(rls_context *ctx, int64_t n, const rls_sss_closure *c, rls_cvec3 P, int spp_n,
+                                   const rls_probe_queue *q, const rls_probe_hits *h, rls_cvec3 hitT, int use_cavity_fade,
+                                   const rls_sphere_light *lights, int n_lights, int hit_spp_n, int trace_diffuse,
+                                   uint32_t seed, uint64_t hit_first_index, const rls_hit_queues *hq);
+
+/* h: max_hits and stride are read.  lights, n_lights, hit_spp_n, trace_diffuse, hq: those of the emit.  visibility: 3 planes
+ * indexed by shadow ray (not read when n_lights == 0); radiance: 3 planes indexed by diffuse ray, NULL when !trace_diffuse.
+ * E: 3 planes of max_hits * stride floats, the layout of rls_probe_hits.irradiance. */
+rls_status rls_trace_sss_hits_resolve(rls_context *ctx, const rls_probe_hits *h, const rls_sphere_light *lights, int n_lights,
+                                      int hit_spp_n, int trace_diffuse, const rls_hit_queues *hq, rls_crgb visibility,
+                                      rls_crgb radiance, rls_rgb E);
 
 /* ------------------------------------------------------------------------------------------
  * Whole nodes: shader_evaluate of rlGgx and rlDisney (src/rlGgx.cpp:248-327, src/rlDisney.cpp:685-727) cut at every

@@ -228,6 +228,64 @@ struct SssResolveIO {
     int cavity, literal;
 };
 
+// rlSss's probe hits shaded through the caller's tracer (rls_trace_sss_hits_emit / _resolve, rls_trace_hits.hpp).  The gate
+// pass walks the probe rays in the probe emit's tiles and leaves per ray the mask of its shaded slots and their number (scanned
+// in place afterwards); the list pass turns both into hit_element and hit_count.
+struct HitGateIO {
+    rls_sss_closure c;
+    rls_cvec3 P;
+    rls_probe_hits h;        // count, P, N read
+    uint16_t *mask;          // [rays]: bit k set where slot k of the ray is shaded
+    int64_t *count;          // [rays + 1]
+    int64_t n;
+    int spp;
+    int tile_points;
+    int cavity;
+};
+struct HitListIO {
+    const uint16_t *mask;
+    const int64_t *offsets;  // the scanned counts: offsets[rays] = the shaded hits
+    int64_t rays, stride, capacity;
+    int64_t *hit_element, *hit_count;
+};
+// The light loop and the diffuse ray over the hit LIST: "point" i is list entry i of n = hit_capacity, live while i <
+// min(*hit_count, n).  The light loop's staging is the light loops' with two segments a light and without the specular
+// planes (kStageSpecular below); the diffuse ray's is a sample-ray emit's at one sample: dir, weight.r, 16-bit tags.
+struct HitEmitIO {
+    rls_probe_hits h;        // P, N read
+    rls_cvec3 T;             // hitT, all NULL: the library's own tangent (hit_tangent)
+    const int64_t *hit_count, *hit_element;
+    rls_sphere_light lights[RLS_MAX_LIGHTS];
+    int nl;
+    float *dir[3];
+    float *maxdist;
+    float *wd[3];            // wd[0] only
+    uint32_t *tag;
+    int64_t *count;          // = the shadow queue's offsets; NULL without lights
+    float *ddir[3];          // the diffuse ray's staging; dtag NULL: no diffuse ray
+    float *dw;
+    uint16_t *dtag;
+    int64_t *dcount;         // = the diffuse queue's offsets
+    int64_t n;               // hit_capacity
+    int spp;
+    uint32_t seed;
+    uint64_t first;
+};
+struct HitResolveIO {
+    ShadowResolveIO s;       // the light loop over the list (s.n = hit_capacity; s.nl == 0: no queue); ws, dd, ds unused
+    const int64_t *hit_count, *hit_element;
+    const int64_t *doffsets; // the diffuse queue's offsets, NULL: no diffuse ray
+    const float *dw;
+    rls_crgb L;              // the diffuse rays' radiance
+    rls_rgb E;
+    int64_t n;               // hit_capacity
+};
+constexpr int kHitStagePlanes = 5;           // dir[3], maxdist, weight_diffuse.r
+
+// whether a light-loop emit stages weight_specular (ShadowStage, rls_trace_shadow_emit.hpp): all but the hits' Oren-Nayar loop
+template <class IO> constexpr bool kStageSpecular = true;
+template <> constexpr bool kStageSpecular<HitEmitIO> = false;
+
 constexpr int kSssEmitRays = 4 * rlsh::kBlock;
 constexpr int kSssEmitPoints = rlsh::kBlock;       // (one thread per point computes the point's part)
 inline int sss_emit_tile_points(int spp) { return kSssEmitRays / spp < kSssEmitPoints ? kSssEmitRays / spp : kSssEmitPoints; }

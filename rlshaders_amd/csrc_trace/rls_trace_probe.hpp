@@ -109,6 +109,23 @@ __global__ __launch_bounds__(rlsh::kBlock) void skin_probe_emit_kernel(SkinProbe
 // per-point profile and frame are recomputed per ray (the same arithmetic as the integrator's, so the same bits): staged in
 // LDS instead, once per point, the kernel ran slower at 2^22 points x 16 rays (2.90 against 2.44 ms; 47 KB of LDS, three
 // workgroups per CU instead of four).
+// Whether a probe hit is shaded (src/rlSss.h:316-317, 386, 401-415: the condition for calling evalLightSample /
+// integrateDiffuse): the duplicate test against the ray's previous hit `prev` (advanced past a hit that passes it), the radius
+// cut-off about the shading point Po, the cavity fade against the shading normal No.  d = hit - Po, r = |d| and fade are left
+// for a shaded hit.  The one copy of the gate: the scatter resolves' walk below and the hit list (rls_trace_hits.hpp) run it.
+__device__ __forceinline__ bool probe_hit_shaded(V3 &prev, V3 Po, V3 hp, V3 hn, float maxR, V3 No, bool cavity, V3 &d, float &r,
+                                                 float &fade)
+{
+    if (!(length(prev - hp) > kEps)) return false;                       // :316-317
+    prev = hp;
+    d = hp - Po;
+    r = length(d);
+    if (r > maxR) return false;                                          // :386
+    fade = 1.0f;
+    if (cavity) fade = sss_cavity_fade(d, r, hn, No);
+    return fade > kEps;                                                  // :415
+}
+
 // One probe ray's walk (thread t of a tile, ray j of the queue, about the shading point Po with profile p and frame fr): the
 // term irr / pdf of each of its hits to term[k][.][t], its hit slots min(count, max_hits) and its shaded hits.
 __device__ __forceinline__ void scatter_ray_terms(float (*term)[3][rlsh::kBlock], uint8_t *slots, uint8_t *shaded, int t,
@@ -123,24 +140,16 @@ __device__ __forceinline__ void scatter_ray_terms(float (*term)[3][rlsh::kBlock]
         const V3 hp = ld3(h.P, at), hn = ld3(h.N, at);
         const float eR = ldg(h.irradiance.r, at), eG = ldg(h.irradiance.g, at), eB = ldg(h.irradiance.b, at);
         float tR = 0.0f, tG = 0.0f, tB = 0.0f;
-        if (length(prev - hp) > kEps) {                                  // :316-317
-            prev = hp;
-            // shadeProbeSample, :379-420
-            const V3 d = hp - Po;
-            const float r = length(d);
-            if (!(r > p.maxR)) {
-                float fade = 1.0f;
-                if (cavity) fade = sss_cavity_fade(d, r, hn, fr.N);
-                if (fade > kEps) {
-                    sh++;
-                    float pr, pg, pb;
-                    nd_profile(p, r, pr, pg, pb);
-                    const float iR = eR * pr * fade, iG = eG * pg * fade, iB = eB * pb * fade;
-                    if (!(iR == 0.0f && iG == 0.0f && iB == 0.0f)) {            // :249
-                        const float pdf = sss_mis_pdf(p, fr, d, hn, literal);
-                        tR = R_DIV(iR, pdf); tG = R_DIV(iG, pdf); tB = R_DIV(iB, pdf);
-                    }
-                }
+        V3 d;
+        float r, fade;
+        if (probe_hit_shaded(prev, Po, hp, hn, p.maxR, fr.N, cavity, d, r, fade)) {      // shadeProbeSample, :379-420
+            sh++;
+            float pr, pg, pb;
+            nd_profile(p, r, pr, pg, pb);
+            const float iR = eR * pr * fade, iG = eG * pg * fade, iB = eB * pb * fade;
+            if (!(iR == 0.0f && iG == 0.0f && iB == 0.0f)) {            // :249
+                const float pdf = sss_mis_pdf(p, fr, d, hn, literal);
+                tR = R_DIV(iR, pdf); tG = R_DIV(iG, pdf); tB = R_DIV(iB, pdf);
             }
         }
         term[k][0][t] = tR; term[k][1][t] = tG; term[k][2][t] = tB;

@@ -233,8 +233,10 @@ __device__ __forceinline__ void ray_sums_about_reference(float (*planes)[kResolv
 // Limits of this shape: a staging row is pc points wide, so with many slots per point (tile_points = 6144 / slots: 64 at 2
 // lights x 16 samples, 1 at the maximum) the tag and plane reads are short runs n words apart rather than full cache lines, and
 // every plane's pass walks all the tile's slots (through pos), kept or not.
-template <int NWD>
-__global__ __launch_bounds__(rlsh::kBlock) void shadow_compact_kernel(ShadowCompactIO a)
+// HITS: the queue over rlSss's hit list (rls_trace_hits.hpp): no weight_specular planes, staged or queued, and a point without
+// rays -- every entry past the list's end -- has no tags staged: its slots read as dropped.
+template <int NWD, bool HITS>
+__device__ __forceinline__ void shadow_compact_tiles(const ShadowCompactIO &a)
 {
     __shared__ float buf[kShadowMaxSlots];           // one plane of the tile's rays, in queue order
     __shared__ int16_t pos[kShadowMaxSlots];         // slot -> its ray's place in the tile's range, -1: dropped
@@ -254,12 +256,13 @@ __global__ __launch_bounds__(rlsh::kBlock) void shadow_compact_kernel(ShadowComp
         __syncthreads();
         const int64_t base = off[0];
         const int rays = (int)(off[pc] - base);
+        if (HITS && rays == 0) continue;
         // (sp, p) of this thread's slots t = threadIdx.x, + kBlock, ...: advanced without a division per slot
         const int sp0 = (int)threadIdx.x / pc, pp0 = (int)threadIdx.x - sp0 * pc;
         const int dsp = rlsh::kBlock / pc, dp = rlsh::kBlock - dsp * pc;
         uint32_t *ib = (uint32_t *)buf;
         for (int t = threadIdx.x, sp = sp0, p = pp0; t < slots; t += rlsh::kBlock) {
-            const uint32_t tag = a.tag[staging_slot(sp, a.n, p0 + p)];
+            const uint32_t tag = HITS && off[p + 1] == off[p] ? kShadowDropped : a.tag[staging_slot(sp, a.n, p0 + p)];
             int at = -1;
             if (tag != kShadowDropped) {
                 at = (int)(off[p] - base) + (int)(tag & 0xFFFFu);
@@ -277,6 +280,7 @@ __global__ __launch_bounds__(rlsh::kBlock) void shadow_compact_kernel(ShadowComp
             if (q.sample) q.sample[base + k] = (uint8_t)(v >> 8);
         }
         for (int plane = 0; plane < 7 + NWD; plane++) {
+            if (HITS && plane >= 4 && plane < 7) continue;
             const float *src = a.src[plane];
             float *out = plane == 0 ? q.dir.x : plane == 1 ? q.dir.y : plane == 2 ? q.dir.z : plane == 3 ? q.maxdist
                        : plane == 4 ? q.weight_specular.r : plane == 5 ? q.weight_specular.g : plane == 6 ? q.weight_specular.b
@@ -293,6 +297,18 @@ __global__ __launch_bounds__(rlsh::kBlock) void shadow_compact_kernel(ShadowComp
         }
     }
 }
+
+template <int NWD>
+__global__ __launch_bounds__(rlsh::kBlock) void shadow_compact_kernel(ShadowCompactIO a)
+{
+    shadow_compact_tiles<NWD, false>(a);
+}
+#if !RLS_FAST
+__global__ __launch_bounds__(rlsh::kBlock) void hits_compact_kernel(ShadowCompactIO a)
+{
+    shadow_compact_tiles<1, true>(a);
+}
+#endif
 
 // The light loops' sums with the traced visibility.  Like trace_resolve_kernel a workgroup takes kBlock consecutive points, one
 // contiguous range of rays, in tiles: coalesced loads form visibility x weight of both lobes in LDS, then lane i walks its own
@@ -312,7 +328,8 @@ __device__ __forceinline__ void stage_radiance(float (*rad)[3], const ShadowReso
 // The tile walk over the light loops' queue for the workgroup's points p0 .. p0 + kBlock - 1 (shadow_resolve_kernel and the
 // node resolves): oS / oD = the point's specular / diffuse sum over the lights, before rlGgx's tail.  Whole workgroup; opens
 // with a barrier like ray_sums.
-template <int NWD>
+// SPEC = false: a queue without weight_specular planes (the hit list's): oS is +0.
+template <int NWD, bool SPEC = true>
 __device__ __forceinline__ void shadow_sums(float (*prod)[kShadowTile], uint8_t *kinds, const float (*rad)[3],
                                             const ShadowResolveIO &a, int64_t p0, float (&oS)[3], float (&oD)[3])
 {
@@ -344,7 +361,7 @@ __device__ __forceinline__ void shadow_sums(float (*prod)[kShadowTile], uint8_t 
         for (int k = threadIdx.x; k < tn; k += rlsh::kBlock) {
             const int64_t r = t0 + k;
             const float vr = a.vis.r[r], vg = a.vis.g[r], vb = a.vis.b[r];
-            prod[0][k] = vr * a.ws[0][r]; prod[1][k] = vg * a.ws[1][r]; prod[2][k] = vb * a.ws[2][r];
+            if (SPEC) { prod[0][k] = vr * a.ws[0][r]; prod[1][k] = vg * a.ws[1][r]; prod[2][k] = vb * a.ws[2][r]; }
             if (GGX) {
                 const float wd = a.wd[0][r];
                 prod[3][k] = vr * wd; prod[4][k] = vg * wd; prod[5][k] = vb * wd;
@@ -362,10 +379,10 @@ __device__ __forceinline__ void shadow_sums(float (*prod)[kShadowTile], uint8_t 
             if (ONE) {
                 lS[0] += prod[0][k]; lS[1] += prod[1][k]; lS[2] += prod[2][k];
             } else if (kind & RLS_SHADOW_BSDF) {
-                if (kind & RLS_SHADOW_SPECULAR) { bS[0] += prod[0][k]; bS[1] += prod[1][k]; bS[2] += prod[2][k]; }
+                if (SPEC && (kind & RLS_SHADOW_SPECULAR)) { bS[0] += prod[0][k]; bS[1] += prod[1][k]; bS[2] += prod[2][k]; }
                 if (kind & RLS_SHADOW_DIFFUSE) { bD[0] += prod[3][k]; bD[1] += prod[4][k]; bD[2] += prod[5][k]; }
             } else {
-                if (kind & RLS_SHADOW_SPECULAR) { lS[0] += prod[0][k]; lS[1] += prod[1][k]; lS[2] += prod[2][k]; }
+                if (SPEC && (kind & RLS_SHADOW_SPECULAR)) { lS[0] += prod[0][k]; lS[1] += prod[1][k]; lS[2] += prod[2][k]; }
                 if (kind & RLS_SHADOW_DIFFUSE) { lD[0] += prod[3][k]; lD[1] += prod[4][k]; lD[2] += prod[5][k]; }
             }
         }

@@ -85,8 +85,10 @@ struct ShadowStage {
                 const float disc = maxf(0.0f, b * b - cone.c2 * dd);
                 al.dir[0][slot] = dir.x; al.dir[1][slot] = dir.y; al.dir[2][slot] = dir.z;
                 al.maxdist[slot] = R_DIV(cone.c2, b + R_SQRT(disc));
+                if constexpr (kStageSpecular<IO>) {
 #pragma unroll
-                for (int c = 0; c < 3; c++) al.ws[c][slot] = ws[c];
+                    for (int c = 0; c < 3; c++) al.ws[c][slot] = ws[c];
+                }
                 if constexpr (NWD > 0) {
 #pragma unroll
                     for (int c = 0; c < NWD; c++) al.wd[c][slot] = wd[c];

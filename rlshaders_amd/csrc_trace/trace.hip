@@ -25,6 +25,7 @@ namespace {
 #include "rls_trace_probe.hpp"
 #include "rls_trace_queue.hpp"
 #include "rls_trace_node_resolve.hpp"
+#include "rls_trace_hits.hpp"
 
 // one launch of the rlSss emit or resolve: a workgroup per tile of io.tile_points points, grid-striding past the cap
 template <class IO>
@@ -83,6 +84,12 @@ static rls_status launch_skin_node_resolve(rls_context *ctx, int, const SkinNode
     return rlsh::check_launch(name, RLS_FAST);
 }
 RLS_FLAVOURS(skin_node_resolve, SkinNodeResolveIO)
+static rls_status launch_sss_hits_gate(rls_context *ctx, int, const HitGateIO &io, const char *name)
+{
+    return launch_tiles(ctx, sss_hits_gate_kernel<>, io, name);
+}
+RLS_FLAVOURS(sss_hits_gate, HitGateIO)
+RLS_TRACE_G_VERB(sss_hits_emit, HitEmitIO)
 
 #if !RLS_FAST
 
@@ -122,6 +129,37 @@ inline int shadow_planes(int nwd) { return nwd == 0 ? kSkinShadowPlanes : kShado
 inline Staging shadow_staging(void *base, int64_t n, int nwd, int nl, int spp)
 {
     return staging(base, n, shadow_slots(nwd, nl, spp), shadow_planes(nwd), sizeof(uint32_t));
+}
+
+// The scratch of the hit verbs (rls_hit_queues.scratch), each part 256-byte aligned: the gate's per-ray masks and counts, the
+// tile sums of the three scans (one after another on the stream: one block, sized to the longest), the light loop's staging
+// over the list (kHitStagePlanes float planes and 32-bit tags of hit_capacity * n_lights * 2 * hit_spp_n^2 slots) and the
+// diffuse ray's (dir[3], weight, 16-bit tags of hit_capacity slots).
+struct HitScratch {
+    uint16_t *mask;
+    int64_t *ray_count, *totals;
+    float *f[kHitStagePlanes], *df[4];
+    uint32_t *tag;
+    uint16_t *dtag;
+    size_t bytes;
+};
+inline int64_t scan_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
+inline HitScratch hit_scratch(void *base, int64_t rays, int64_t capacity, int nl, int hit_spp)
+{
+    HitScratch s = {};
+    char *p = (char *)base;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { char *at = p + off; off += align256(bytes); return (void *)at; };
+    s.mask = (uint16_t *)carve((size_t)rays * sizeof(uint16_t));
+    s.ray_count = (int64_t *)carve((size_t)(rays + 1) * sizeof(int64_t));
+    s.totals = (int64_t *)carve((size_t)std::max<int64_t>(std::max(scan_tiles(rays), scan_tiles(capacity)), 1) * sizeof(int64_t));
+    const size_t slots = (size_t)capacity * (size_t)(nl * kSkinShadowSegments * hit_spp);
+    for (int k = 0; k < kHitStagePlanes; k++) s.f[k] = (float *)carve(slots * sizeof(float));
+    s.tag = (uint32_t *)carve(slots * sizeof(uint32_t));
+    for (int k = 0; k < 4; k++) s.df[k] = (float *)carve((size_t)capacity * sizeof(float));
+    s.dtag = (uint16_t *)carve((size_t)capacity * sizeof(uint16_t));
+    s.bytes = off;
+    return s;
 }
 
 // ---- the argument checks, each written once; fn: the name its messages carry --------------------------------------------------
@@ -222,6 +260,36 @@ rls_status check_probe_hits(const char *fn, const rls_probe_queue *q, const rls_
     RLS_REQUIRE_IN(fn, h->stride >= rays, "hits.stride < n * spp_n^2");
     RLS_REQUIRE_IN(fn, h->count != nullptr && rlsh::has3(h->P) && rlsh::has3(h->N) && h->irradiance.r && h->irradiance.g &&
                    h->irradiance.b, "hits.count, hits.P, hits.N or hits.irradiance plane is NULL");
+    return RLS_OK;
+}
+
+// What both hit verbs check of their list, loop and queues (emit: the scratch and the staging's limits too)
+rls_status check_hit_queues(const char *fn, const rls_hit_queues *hq, int n_lights, int hit_spp_n, int trace_diffuse)
+{
+    RLS_REQUIRE_IN(fn, hq != nullptr, "queues is NULL");
+    RLS_REQUIRE_IN(fn, n_lights >= 0 && n_lights <= RLS_MAX_LIGHTS, "n_lights out of range (RLS_MAX_LIGHTS)");
+    RLS_REQUIRE_IN(fn, hit_spp_n >= 1 && hit_spp_n * hit_spp_n <= kMaxSpp, "hit_spp_n must be in [1, 16]");
+    RLS_REQUIRE_IN(fn, hq->hit_capacity >= 0, "queues.hit_capacity < 0");
+    RLS_REQUIRE_IN(fn, hq->hit_capacity <= (int64_t)UINT32_MAX, "queues.hit_capacity > 2^32 - 1 (the queue's point index is 32-bit)");
+    RLS_REQUIRE_IN(fn, hq->hit_count != nullptr && (hq->hit_capacity == 0 || hq->hit_element != nullptr),
+                   "queues.hit_count or queues.hit_element is NULL");
+    const bool planes = hq->hit_capacity > 0;                    // (a list of no entries has no rays: offsets[0] alone)
+    if (n_lights > 0) {
+        const rls_shadow_queue &q = hq->shadow;
+        RLS_REQUIRE_IN(fn, q.offsets != nullptr, "queue or queue.offsets is NULL");
+        RLS_REQUIRE_IN(fn, !planes || (rlsh::has3(q.dir) && q.maxdist != nullptr), "queue.dir or queue.maxdist plane is NULL");
+        RLS_REQUIRE_IN(fn, !planes || q.weight_diffuse.r != nullptr, "queue.weight_specular or queue.weight_diffuse plane is NULL");
+        RLS_REQUIRE_IN(fn, !planes || q.kind != nullptr, "queue.kind is NULL");
+        RLS_REQUIRE_IN(fn, q.capacity >= hq->hit_capacity * n_lights * kSkinShadowSegments * hit_spp_n * hit_spp_n,
+                       "queue.capacity < n * n_lights * 2 * spp_n^2");
+    }
+    if (trace_diffuse) {
+        const rls_ray_queue &q = hq->diffuse;
+        RLS_REQUIRE_IN(fn, q.offsets != nullptr, "queue or queue.offsets is NULL");
+        RLS_REQUIRE_IN(fn, !planes || rlsh::has3(q.dir), "queue.dir plane is NULL");
+        RLS_REQUIRE_IN(fn, !planes || q.weight.r != nullptr, "queue.weight plane is NULL");
+        RLS_REQUIRE_IN(fn, q.capacity >= hq->hit_capacity, "queue.capacity < n * spp_n^2");
+    }
     return RLS_OK;
 }
 
@@ -825,6 +893,135 @@ rls_status rls_trace_skin_resolve(rls_context *ctx, int64_t n, const rls_skin_cl
     io.spp = spp; io.tile_points = sss_resolve_tile_points(spp);
     io.cavity = use_cavity_fade != 0; io.literal = literal_matrix != 0; io.n = n;
     return dispatch_skin_node_resolve(ctx, 0, io, fn);
+}
+
+rls_status rls_trace_sss_hits_scratch_bytes(int64_t n, int spp_n, int max_hits, int64_t hit_capacity, int n_lights,
+                                            int hit_spp_n, size_t *bytes)
+{
+    RLS_REQUIRE(bytes != nullptr, "bytes is NULL");
+    if (rls_status s = check_n(__func__, n)) return s;
+    if (rls_status s = check_spp_n(__func__, spp_n)) return s;
+    RLS_REQUIRE(max_hits >= 1 && max_hits <= RLS_MAX_PROBE_HITS, "hits.max_hits must be in [1, 12]");
+    RLS_REQUIRE(hit_capacity >= 0, "queues.hit_capacity < 0");
+    RLS_REQUIRE(n_lights >= 0 && n_lights <= RLS_MAX_LIGHTS, "n_lights out of range (RLS_MAX_LIGHTS)");
+    RLS_REQUIRE(hit_spp_n >= 1 && hit_spp_n * hit_spp_n <= kMaxSpp, "hit_spp_n must be in [1, 16]");
+    *bytes = hit_scratch(nullptr, n * spp_n * spp_n, hit_capacity, n_lights, hit_spp_n * hit_spp_n).bytes;
+    return RLS_OK;
+}
+
+rls_status rls_trace_sss_hits_emit(rls_context *ctx, int64_t n, const rls_sss_closure *c, rls_cvec3 P, int spp_n,
+                                   const rls_probe_queue *q, const rls_probe_hits *h, rls_cvec3 hitT, int use_cavity_fade,
+                                   const rls_sphere_light *lights, int n_lights, int hit_spp_n, int trace_diffuse,
+                                   uint32_t seed, uint64_t hit_first_index, const rls_hit_queues *hq)
+{
+    const char *fn = __func__;
+    if (rls_status s = check_batch(fn, ctx, n, spp_n)) return s;
+    RLS_REQUIRE(q != nullptr, "queue is NULL");
+    RLS_REQUIRE(h != nullptr, "hits is NULL");
+    if (rls_status s = check_max_hits(fn, h)) return s;
+    if (rls_status s = check_hit_queues(fn, hq, n_lights, hit_spp_n, trace_diffuse)) return s;
+    const int spp = spp_n * spp_n, hit_spp = hit_spp_n * hit_spp_n;
+    const int64_t rays = n * spp, cap = hq->hit_capacity;
+    HitEmitIO io = {};
+    if (rls_status s = copy_lights(lights, n_lights, 0, io.lights, &io.nl)) return s;
+    const HitScratch sc = hit_scratch(hq->scratch, rays, cap, io.nl, hit_spp);
+    RLS_REQUIRE(hq->scratch != nullptr && hq->scratch_bytes >= sc.bytes,
+                "queues.scratch is NULL or smaller than rls_trace_sss_hits_scratch_bytes");
+    RLS_REQUIRE(rlsh::has3(hitT) || rlsh::none3(hitT), "hitT planes must be all set or all NULL");
+    if (n > 0) {
+        if (rls_status s = rlsh::check_closure(fn, c, true)) return s;
+        RLS_REQUIRE(rlsh::has3(P), "P plane is NULL");
+        RLS_REQUIRE(q->capacity >= rays, "queue.capacity < n * spp_n^2");
+        RLS_REQUIRE(h->stride >= rays, "hits.stride < n * spp_n^2");
+        RLS_REQUIRE(h->count != nullptr && rlsh::has3(h->P) && rlsh::has3(h->N), "hits.count, hits.P or hits.N plane is NULL");
+        // the list: the gate, the scan of the rays' shaded counts, hit_element and hit_count
+        HitGateIO gio = {};
+        gio.c = *c; gio.P = P; gio.h = *h; gio.mask = sc.mask; gio.count = sc.ray_count;
+        gio.n = n; gio.spp = spp; gio.tile_points = sss_emit_tile_points(spp); gio.cavity = use_cavity_fade != 0;
+        if (rls_status s = dispatch_sss_hits_gate(ctx, 0, gio, fn)) return s;
+        if (rls_status s = scan_counts(ctx, sc.ray_count, rays, sc.totals, scan_tiles(rays))) return s;
+        HitListIO lio = { sc.mask, sc.ray_count, rays, h->stride, cap, hq->hit_element, hq->hit_count };
+        hipLaunchKernelGGL(sss_hits_list_kernel, rlsh::grid_for(ctx, rays), dim3(rlsh::kBlock), 0, ctx->stream, lio);
+        if (rls_status s = rlsh::check_launch("sss_hits_list_kernel")) return s;
+    } else if (rls_status s = empty_queue(ctx, hq->hit_count, fn)) return s;
+    const bool shadow = io.nl > 0, diffuse = trace_diffuse != 0;
+    if (cap == 0) {
+        if (shadow)
+            if (rls_status s = empty_queue(ctx, hq->shadow.offsets, fn)) return s;
+        return diffuse ? empty_queue(ctx, hq->diffuse.offsets, fn) : RLS_OK;
+    }
+    if (!shadow && !diffuse) return RLS_OK;
+    // the two emits over the list in one kernel, then each queue's scan and compaction
+    io.h = *h; io.T = hitT; io.hit_count = hq->hit_count; io.hit_element = hq->hit_element;
+    for (int k = 0; k < 3; k++) io.dir[k] = sc.f[k];
+    io.maxdist = sc.f[3]; io.wd[0] = sc.f[4]; io.tag = sc.tag;
+    io.count = shadow ? hq->shadow.offsets : nullptr;
+    if (diffuse) {
+        for (int k = 0; k < 3; k++) io.ddir[k] = sc.df[k];
+        io.dw = sc.df[3]; io.dtag = sc.dtag; io.dcount = hq->diffuse.offsets;
+    }
+    set_loop(io, cap, hit_spp_n, seed, hit_first_index);
+    if (rls_status s = dispatch_sss_hits_emit(ctx, pick_group(ctx, cap, hit_spp), io, fn)) return s;
+    if (shadow) {
+        if (rls_status s = scan_counts(ctx, hq->shadow.offsets, cap, sc.totals, scan_tiles(cap))) return s;
+        ShadowCompactIO cio = {};
+        for (int k = 0; k < 4; k++) cio.src[k] = sc.f[k];
+        cio.src[7] = sc.f[4];
+        cio.tag = sc.tag; cio.offsets = hq->shadow.offsets; cio.q = hq->shadow; cio.n = cap; cio.spp = hit_spp;
+        cio.slots = io.nl * kSkinShadowSegments * hit_spp;
+        cio.tile_points = compact_tile_points(kShadowMaxSlots, cio.slots);
+        hipLaunchKernelGGL(hits_compact_kernel, rlsh::grid_for(ctx, cap, cio.tile_points), dim3(rlsh::kBlock), 0,
+                           ctx->stream, cio);
+        if (rls_status s = rlsh::check_launch("hits_compact_kernel")) return s;
+    }
+    if (diffuse) {
+        if (rls_status s = scan_counts(ctx, hq->diffuse.offsets, cap, sc.totals, scan_tiles(cap))) return s;
+        TraceCompactIO cio = {};
+        for (int k = 0; k < 3; k++) cio.sdir[k] = sc.df[k];
+        cio.sw[0] = sc.df[3];
+        cio.tag = sc.dtag; cio.offsets = hq->diffuse.offsets; cio.q = hq->diffuse; cio.n = cap; cio.spp = 1;
+        cio.tile_points = compact_tile_points(kCompactSlots, 1);
+        hipLaunchKernelGGL(trace_compact_kernel<1>, rlsh::grid_for(ctx, cap, cio.tile_points), dim3(rlsh::kBlock), 0, ctx->stream,
+                           cio);
+        if (rls_status s = rlsh::check_launch("trace_compact_kernel")) return s;
+    }
+    return RLS_OK;
+}
+
+rls_status rls_trace_sss_hits_resolve(rls_context *ctx, const rls_probe_hits *h, const rls_sphere_light *lights, int n_lights,
+                                      int hit_spp_n, int trace_diffuse, const rls_hit_queues *hq, rls_crgb visibility,
+                                      rls_crgb radiance, rls_rgb E)
+{
+    const char *fn = __func__;
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE(h != nullptr, "hits is NULL");
+    if (rls_status s = check_max_hits(fn, h)) return s;
+    RLS_REQUIRE(h->stride >= 0, "hits.stride < 0");
+    if (rls_status s = check_hit_queues(fn, hq, n_lights, hit_spp_n, trace_diffuse)) return s;
+    HitResolveIO io = {};
+    rls_sphere_light lt[RLS_MAX_LIGHTS];
+    if (rls_status s = copy_lights(lights, n_lights, 0, lt, &io.s.nl)) return s;
+    RLS_REQUIRE(io.s.nl == 0 || (visibility.r && visibility.g && visibility.b), "visibility plane is NULL");
+    RLS_REQUIRE(!trace_diffuse || (radiance.r && radiance.g && radiance.b), "radiance plane is NULL");
+    const int64_t elements = (int64_t)h->max_hits * h->stride;
+    if (elements == 0) return RLS_OK;
+    RLS_REQUIRE(rlsh::has3(E), "NULL output plane");
+    hipLaunchKernelGGL(sss_hits_fill_kernel, rlsh::grid_for(ctx, elements), dim3(rlsh::kBlock), 0, ctx->stream, E, elements);
+    if (rls_status s = rlsh::check_launch("sss_hits_fill_kernel")) return s;
+    if (hq->hit_capacity == 0) return RLS_OK;
+    for (int l = 0; l < io.s.nl; l++)
+        for (int k = 0; k < 3; k++) io.s.rad[l][k] = lt[l].radiance[k];
+    if (io.s.nl > 0) {
+        io.s.offsets = hq->shadow.offsets; io.s.kind = hq->shadow.kind; io.s.vis = visibility;
+        io.s.wd[0] = hq->shadow.weight_diffuse.r;
+    }
+    io.s.inv = 1.0f / (float)(hit_spp_n * hit_spp_n);                // as the loop kernels: 1 / spp
+    io.s.n = hq->hit_capacity;
+    io.hit_count = hq->hit_count; io.hit_element = hq->hit_element;
+    if (trace_diffuse) { io.doffsets = hq->diffuse.offsets; io.dw = hq->diffuse.weight.r; io.L = radiance; }
+    io.E = E; io.n = hq->hit_capacity;
+    hipLaunchKernelGGL(sss_hits_resolve_kernel, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(fn);
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
 // example_trace.cpp -- the caller-traced rlGgx, rlDisney and rlSss integrators from C++ (rls_trace.hpp): emit
 // integrateGlossy's and integrateRefract's sample rays and those of rlDisney's two lobes, "trace" them against an analytic
-// sky on the host, resolve; emit rlSss's probe rays, walk them through each point's tangent plane on the host, resolve;
+// sky on the host, resolve; emit rlSss's probe rays, walk them through each point's tangent plane on the host, resolve --
+// once with the hits' irradiance formed by hand, once lit through the library (emitHits / resolveHits);
 // emit the shadow rays of both nodes' light loops under two lights, shadow the second light with a half-space, resolve;
 // emit every queue of the two whole nodes, shadow the second light with the same half-space and light the ray queues with the
 // sky, resolve the AOVs in one call; emit the five queues of the rlSkin node, leave its lights unoccluded, light its glossy
@@ -8,7 +9,7 @@
 //
 //   example_trace [points] [spp_n]
 // prints one JSON line: the ray counts and a checksum (FNV-1a over the bits of the resolved planes) per integrator, which
-// tests/test_gpu_trace_host_cpp.py (the light loops: tests/test_gpu_trace_lights_host_cpp.py; the whole nodes: tests/test_gpu_trace_shade_host_cpp.py, tests/test_gpu_trace_skin_host_cpp.py) compares with the Python path (rlshaders_amd/trace.py) on the same inputs.
+// tests/test_gpu_trace_host_cpp.py (the lit hits: tests/test_gpu_trace_hits_host_cpp.py; the light loops: tests/test_gpu_trace_lights_host_cpp.py; the whole nodes: tests/test_gpu_trace_shade_host_cpp.py, tests/test_gpu_trace_skin_host_cpp.py) compares with the Python path (rlshaders_amd/trace.py) on the same inputs.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -147,12 +148,42 @@ int main(int argc, char **argv)
             h.irradiance = rls_crgb{hp.plane(6), hp.plane(7), hp.plane(8)};
             rlsb::resolveScatter(dev, sc, P, pq, h, true, false, out, depth.plane(0));
             std::vector<float> res = out.download(), dres = depth.download();
-            rls_device_free(dev.ctx(), dcnt);
             double mean = 0.0, mdepth = 0.0;
             for (float v : res) mean += v;
             for (float v : dres) mdepth += v;
             std::printf(", \"sss\": {\"rays\": %lld, \"checksum\": \"%016llx\", \"mean\": %.9g, \"mean_depth\": %.9g}",
                         (long long)pq.count(), (unsigned long long)fnv(res), mean / (double)res.size(), mdepth / (double)n);
+
+            // The same hits shaded through the library instead of by hand (shadeProbeSample's light loop and diffuse ray):
+            // one spherical light, unoccluded (visibility 1), the diffuse rays lit by the sky; E goes where the hits'
+            // irradiance was, and the scatter resolve runs again on it.
+            rls_sphere_light light = {};
+            light.center[0] = 1.5f; light.center[1] = 2.5f; light.center[2] = 3.5f;
+            light.radius = 1.25f; light.mis_mode = RLS_MIS_BOTH;
+            light.radiance[0] = 3.0f; light.radiance[1] = 2.0f; light.radiance[2] = 0.5f;
+            const int hit_spp_n = 2;
+            rlsb::HitQueues hq(dev, n, spp_n, 1, cap, 1, hit_spp_n, true);
+            rlsb::emitHits(dev, sc, P, pq, h, nullptr, true, &light, 1, kSeed, hq);
+            const int64_t listed = hq.listed(), shadow = hq.shadowCount(), diffuse = hq.diffuseCount();
+            const int64_t scap = hq.c().shadow.capacity;
+            rlsb::Planes vis(dev, std::vector<float>((size_t)(3 * scap), 1.0f), 3), Ld(dev, cap, 3), E(dev, cap, 3);
+            std::vector<float> ddz((size_t)diffuse), L((size_t)(3 * cap), 0.0f);
+            rlsb::check(rls_copy_to_host(dev.ctx(), ddz.data(), hq.c().diffuse.dir.z, sizeof(float) * ddz.size()));
+            sky(ddz, cap, L);
+            Ld.upload(L);
+            rlsb::resolveHits(dev, h, &light, 1, hq, vis, &Ld, E);
+            rls_probe_hits lit = h;
+            lit.irradiance = rls_crgb{E.plane(0), E.plane(1), E.plane(2)};
+            rlsb::resolveScatter(dev, sc, P, pq, lit, true, false, out, nullptr);
+            std::vector<float> eres = E.download(), lres = out.download();
+            double emean = 0.0, lmean = 0.0;
+            for (float v : eres) emean += v;
+            for (float v : lres) lmean += v;
+            std::printf(", \"sss_hits\": {\"hits\": %lld, \"shadow_rays\": %lld, \"diffuse_rays\": %lld, \"E_checksum\": "
+                        "\"%016llx\", \"E_mean\": %.9g, \"checksum\": \"%016llx\", \"mean\": %.9g}",
+                        (long long)listed, (long long)shadow, (long long)diffuse, (unsigned long long)fnv(eres),
+                        emean / (double)eres.size(), (unsigned long long)fnv(lres), lmean / (double)lres.size());
+            rls_device_free(dev.ctx(), dcnt);
         }
         {
             // The light loops of rlGgx and rlDisney on the same frame, every shading point at the origin: two spherical

@@ -15,6 +15,11 @@
 //     rlsb::emitProbes(dev, sss, P, n, spp_n, seed, pq);                   // one probe ray per sample, dense
 //     ... walk every ray through the object, fill an rls_probe_hits (count, P, N, irradiance per hit slot) ...
 //     rlsb::resolveScatter(dev, sss, P, pq, hits, cavity, literal, result); // integrateScatter's result
+// The irradiance of those hits through the renderer's tracer too (shadeProbeSample's light loop and diffuse ray, :415-418):
+//     rlsb::HitQueues hq(dev, n, spp_n, hits.max_hits, hitCapacity, n_lights, hit_spp_n, traceDiffuse);
+//     rlsb::emitHits(dev, sss, P, pq, hits, nullptr, cavity, lights, n_lights, seed, hq);   // hits.irradiance is not read
+//     ... trace hq.c().shadow from the hits' positions for a visibility, hq.c().diffuse for a radiance ...
+//     rlsb::resolveHits(dev, hits, lights, n_lights, hq, visibility, &radiance, E);    // E: what hits.irradiance points at
 // The light loops (`while (AiLightsGetSample(sg))`, src/rlGgx.cpp:285-299, src/rlDisney.cpp:695-705):
 //     rlsb::ShadowQueue sq(dev, n, n_lights, spp_n, rlsb::ShadowQueue::Ggx);
 //     rlsb::emitDirect(dev, ggx, shader, P, lights, n_lights, n, spp_n, seed, sq);   // one shadow ray per term-carrying sample
@@ -219,6 +224,122 @@ inline void resolveScatter(const Device &d, const rls_sss_closure &c, const Plan
     check(rls_trace_sss_scatter_resolve(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, q.sppN(),
                                         &q.c(), &hits, cavityFade ? 1 : 0, literalMatrix ? 1 : 0, result.rgb(),
                                         meanDepth));
+}
+
+// The shaded probe hits of one emitHits and the rays leaving them (rls_hit_queues): the list (hit_count, hit_element), the
+// light loop's shadow queue over the list (no weight_specular; absent without lights), integrateDiffuse's ray queue (with
+// traceDiffuse) and the scratch.  hitCapacity: the hits the list holds; max_hits * n * spp_n^2 holds every slot.
+class HitQueues {
+public:
+    HitQueues(const Device &d, int64_t n, int spp_n, int max_hits, int64_t hitCapacity, int n_lights, int hit_spp_n,
+              bool traceDiffuse)
+        : dev_(&d), n_(n), spp_n_(spp_n), n_lights_(n_lights), hit_spp_n_(hit_spp_n), diffuse_(traceDiffuse)
+    {
+        size_t scratch = 0;
+        check(rls_trace_sss_hits_scratch_bytes(n, spp_n, max_hits, hitCapacity, n_lights, hit_spp_n, &scratch));
+        const int64_t cap = hitCapacity, scap = cap * n_lights * 2 * hit_spp_n * hit_spp_n;
+        try {
+            q_.hit_capacity = cap;
+            q_.hit_count = static_cast<int64_t *>(alloc(sizeof(int64_t)));
+            q_.hit_element = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)cap));
+            if (n_lights > 0) {
+                rls_shadow_queue &s = q_.shadow;
+                s.capacity = scap;
+                s.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(cap + 1)));
+                s.dir = rls_vec3{falloc(scap), falloc(scap), falloc(scap)};
+                s.maxdist = falloc(scap);
+                s.weight_diffuse.r = falloc(scap);
+                s.kind = static_cast<uint8_t *>(alloc((size_t)scap));
+                s.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)scap));
+                s.sample = static_cast<uint8_t *>(alloc((size_t)scap));
+            }
+            if (traceDiffuse) {
+                rls_ray_queue &r = q_.diffuse;
+                r.capacity = cap;
+                r.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(cap + 1)));
+                r.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
+                r.weight.r = falloc(cap);
+                r.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
+            }
+            q_.scratch = alloc(scratch);
+            q_.scratch_bytes = scratch;
+        } catch (...) {
+            release();
+            throw;
+        }
+    }
+    ~HitQueues() { release(); }
+    HitQueues(const HitQueues &) = delete;
+    HitQueues &operator=(const HitQueues &) = delete;
+
+    const rls_hit_queues &c() const { return q_; }
+    int64_t points() const { return n_; }
+    int sppN() const { return spp_n_; }
+    int lights() const { return n_lights_; }
+    int hitSppN() const { return hit_spp_n_; }
+    bool traceDiffuse() const { return diffuse_; }
+    // the TRUE number of shaded hits, the shadow rays, the diffuse rays (each synchronises)
+    int64_t hitCount() const { return read(q_.hit_count); }
+    int64_t listed() const { const int64_t c = hitCount(); return c < q_.hit_capacity ? c : q_.hit_capacity; }
+    int64_t shadowCount() const { return n_lights_ > 0 ? read(q_.shadow.offsets + q_.hit_capacity) : 0; }
+    int64_t diffuseCount() const { return diffuse_ ? read(q_.diffuse.offsets + q_.hit_capacity) : 0; }
+
+private:
+    int64_t read(const int64_t *p) const
+    {
+        int64_t c = 0;
+        check(rls_copy_to_host(dev_->ctx(), &c, p, sizeof(c)));
+        return c;
+    }
+    void release()
+    {
+        for (int k = 0; k < nbufs_; k++) rls_device_free(dev_->ctx(), bufs_[k]);
+        nbufs_ = 0;
+    }
+    void *alloc(size_t bytes)
+    {
+        void *p = nullptr;
+        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
+        bufs_[nbufs_++] = p;
+        return p;
+    }
+    float *falloc(int64_t count) { return static_cast<float *>(alloc(sizeof(float) * (size_t)count)); }
+
+    const Device *dev_;
+    int64_t n_;
+    int spp_n_, n_lights_, hit_spp_n_;
+    bool diffuse_;
+    rls_hit_queues q_{};
+    void *bufs_[20] = {};
+    int nbufs_ = 0;
+};
+
+// shadeProbeSample's rays at the caller's hits (src/rlSss.h:415-418): c, P, q, cavityFade those of the scatter resolve the
+// hits go to; hits: count, P, N (irradiance is not read); hitT: the tangents at the hits, 3 planes in the hits' layout, or
+// nullptr for the library's own; the hit with element e samples from hash(seed, hit_first_index + e)
+inline void emitHits(const Device &d, const rls_sss_closure &c, const Planes &P, const ProbeQueue &q, const rls_probe_hits &hits,
+                     const Planes *hitT, bool cavityFade, const rls_sphere_light *lights, int n_lights, uint32_t seed,
+                     HitQueues &hq, uint64_t hit_first_index = 0)
+{
+    if (hq.points() != q.points() || hq.sppN() != q.sppN() || hq.lights() != n_lights)
+        throw Error(RLS_ERR_INVALID_ARGUMENT, "emitHits: queues of another size or light count");
+    const rls_cvec3 T = hitT ? rls_cvec3{hitT->plane(0), hitT->plane(1), hitT->plane(2)} : rls_cvec3{nullptr, nullptr, nullptr};
+    check(rls_trace_sss_hits_emit(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, q.sppN(), &q.c(), &hits,
+                                  T, cavityFade ? 1 : 0, lights, n_lights, hq.hitSppN(), hq.traceDiffuse() ? 1 : 0, seed,
+                                  hit_first_index, &hq.c()));
+}
+
+// E at every hit slot from what the renderer traced: visibility 3 planes of >= hq.shadowCount() floats (not read without
+// lights), radiance 3 planes of >= hq.diffuseCount() floats or nullptr without traceDiffuse; E: 3 planes of max_hits * stride
+// floats, the layout of hits.irradiance (exactly 0 at every hit that is not listed)
+inline void resolveHits(const Device &d, const rls_probe_hits &hits, const rls_sphere_light *lights, int n_lights,
+                        const HitQueues &hq, const Planes &visibility, const Planes *radiance, Planes &E)
+{
+    if (hq.lights() != n_lights) throw Error(RLS_ERR_INVALID_ARGUMENT, "resolveHits: queues of another light count");
+    const rls_crgb L = radiance ? rls_crgb{radiance->plane(0), radiance->plane(1), radiance->plane(2)}
+                                : rls_crgb{nullptr, nullptr, nullptr};
+    check(rls_trace_sss_hits_resolve(d.ctx(), &hits, lights, n_lights, hq.hitSppN(), hq.traceDiffuse() ? 1 : 0, &hq.c(),
+                                     rls_crgb{visibility.plane(0), visibility.plane(1), visibility.plane(2)}, L, E.rgb()));
 }
 
 // The device buffers of one light-loop emit (rls_shadow_queue): per-ray planes for n * n_lights * 3 * spp_n^2 rays, offsets

@@ -21,6 +21,9 @@ or of one rlDisney lobe, trace them with your own tracer, resolve the radiance; 
     nq = trace.ggx_node_rays(sampler, shader, P, lights, 4, 7)   # GgxNodeQueues: the whole node's rays, nq.shadow, nq.glossy,
     aov = nq.resolve(vis, Lg, Lt, Ld)                            # nq.refract, nq.diffuse -> rls_ggx_shade's dict, traced
 
+    hq = trace.sss_hit_rays(sss, P, p, cnt, hP, hN, lights, 2, 7, trace_diffuse=True)   # HitQueues: the shaded hits' shadow
+    E = hq.resolve(vis, Ld)                                      # rays and diffuse ray -> the E of p.resolve, traced
+
     sq = trace.skin_node_rays(skin, P, lights, 4, 7)             # SkinNodeQueues: sheen_shadow, specular_shadow, sheen_glossy,
     aov = sq.resolve(vis_a, vis_b, La, Lb, cnt, hP, hN, E)       # specular_glossy, probes -> SkinShader.integrate's dict, traced
 
@@ -70,6 +73,12 @@ class ShadowQueue_(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("offsets", C.c_void_p), ("dir", capi.Vec3), ("maxdist", C.c_void_p),
                 ("weight_specular", capi.Rgb), ("weight_diffuse", capi.Rgb), ("kind", C.c_void_p), ("point", C.c_void_p),
                 ("sample", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+class HitQueues_(C.Structure):
+    """rls_hit_queues"""
+    _fields_ = [("hit_capacity", C.c_int64), ("hit_count", C.c_void_p), ("hit_element", C.c_void_p), ("shadow", ShadowQueue_),
+                ("diffuse", RayQueue_), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
 RLS_MAX_PROBE_HITS = 12
@@ -131,6 +140,12 @@ PROTOTYPES = {
                                            _pq]),
     "rls_trace_sss_scatter_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.SssClosure), capi.CVec3, C.c_int, _pq,
                                                 C.POINTER(ProbeHits_), C.c_int, C.c_int, capi.Rgb, _vp]),
+    "rls_trace_sss_hits_scratch_bytes": (C.c_int, [_i64, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "rls_trace_sss_hits_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.SssClosure), capi.CVec3, C.c_int, _pq,
+                                          C.POINTER(ProbeHits_), capi.CVec3, C.c_int, _lights, C.c_int, C.c_int, C.c_int,
+                                          C.c_uint32, C.c_uint64, C.POINTER(HitQueues_)]),
+    "rls_trace_sss_hits_resolve": (C.c_int, [_ctx, C.POINTER(ProbeHits_), _lights, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(HitQueues_), capi.CRgb, capi.CRgb, capi.Rgb]),
     "rls_trace_shadow_scratch_bytes": (C.c_int, [_i64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "rls_trace_ggx_direct_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.POINTER(capi.GgxShader), capi.CVec3,
                                             _lights, C.c_int, C.c_int, C.c_uint32, C.c_uint64, _sq]),
@@ -353,12 +368,14 @@ def disney_rays(sampler: DisneySampler, lobe: int, spp_n: int, seed: int, first_
 
 def _probe_hits(count, P, N, irradiance, rays: int) -> ProbeHits_:
     """The caller's hits of `rays` probe rays, validated, as rls_probe_hits (``ProbeQueue.resolve`` describes them).  The struct
-    holds pointers only: the tensors stay the caller's."""
+    holds pointers only: the tensors stay the caller's.  irradiance None (the hits emit reads none): its planes stay NULL."""
     if not isinstance(count, torch.Tensor) or count.dtype != torch.uint8 or not count.is_cuda or count.dim() != 1 or \
             count.shape[0] < rays or not count.is_contiguous():
         raise ValueError(f"count: expected a contiguous uint8 CUDA tensor [>= {rays}]")
     shape = None
     for what, t in (("P", P), ("N", N), ("irradiance", irradiance)):
+        if t is None and what == "irradiance":
+            continue
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or \
                 t.shape[0] != 3 or not 1 <= t.shape[1] <= RLS_MAX_PROBE_HITS or t.shape[2] < rays or \
                 t.stride(2) != 1 or t.stride(1) != t.shape[2]:
@@ -371,7 +388,8 @@ def _probe_hits(count, P, N, irradiance, rays: int) -> ProbeHits_:
     h.max_hits, h.stride, h.count = int(shape[1]), int(shape[2]), count.data_ptr()
     h.P = capi.CVec3(*[P[k].data_ptr() for k in range(3)])
     h.N = capi.CVec3(*[N[k].data_ptr() for k in range(3)])
-    h.irradiance = capi.CRgb(*[irradiance[k].data_ptr() for k in range(3)])
+    if irradiance is not None:
+        h.irradiance = capi.CRgb(*[irradiance[k].data_ptr() for k in range(3)])
     return h
 
 
@@ -433,6 +451,152 @@ def sss_probe_rays(sampler: SssSampler, P: torch.Tensor, spp_n: int, seed: int, 
     check(load().rls_trace_sss_probe_emit(ctx.handle, n, C.byref(sampler.c), _points(P, n), int(spp_n), int(seed) & 0xFFFFFFFF,
                                           int(first_index), C.byref(q.q)))
     q.sampler, q.P = sampler, P
+    return q
+
+
+def sss_hits_scratch_bytes(n: int, spp_n: int, max_hits: int, hit_capacity: int, n_lights: int, hit_spp_n: int) -> int:
+    b = C.c_size_t()
+    check(load().rls_trace_sss_hits_scratch_bytes(int(n), int(spp_n), int(max_hits), int(hit_capacity), int(n_lights),
+                                                  int(hit_spp_n), C.byref(b)))
+    return int(b.value)
+
+
+class HitQueues:
+    """The shaded probe hits of one ``sss_hit_rays`` call and the rays leaving them (rls_hit_queues): ``hit_element`` [listed]
+    int64, the listed hits' elements k * stride + j of the hit planes, ray-major; ``hit_count`` the TRUE number of shaded hits
+    (``listed`` = min(hit_count, hit_capacity)); ``shadow`` a light-loop queue over the LIST (dir, maxdist, weight_diffuse [1, .],
+    kind, point = list index, sample; no weight_specular), ``diffuse`` integrateDiffuse's rays (dir, weight [1, .], point), at
+    most one per listed hit.  ``hit_count`` and the views read the device once each (they synchronise)."""
+
+    def __init__(self, ctx, n: int, spp_n: int, max_hits: int, stride: int, hit_capacity: int, n_lights: int, hit_spp_n: int,
+                 trace_diffuse: bool = False, scratch: Optional[torch.Tensor] = None):
+        self.ctx, self.n, self.spp_n, self.max_hits, self.stride = ctx, int(n), int(spp_n), int(max_hits), int(stride)
+        self.hit_capacity, self.n_lights, self.hit_spp_n = int(hit_capacity), int(n_lights), int(hit_spp_n)
+        self.trace_diffuse = bool(trace_diffuse)
+        dev, cap = ctx.torch_device, self.hit_capacity
+        i64 = dict(dtype=torch.int64, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self._hit_count = torch.zeros(1, **i64)
+        self._hit_element = torch.empty(cap, **i64)
+        self.shadow_capacity = scap = cap * self.n_lights * 2 * self.hit_spp_n * self.hit_spp_n
+        self.shadow_offsets = torch.zeros(cap + 1, **i64)
+        self._sdir, self._smaxdist, self._swd = torch.empty(3, scap, **f32), torch.empty(scap, **f32), torch.empty(1, scap, **f32)
+        self._skind = torch.empty(scap, dtype=torch.uint8, device=dev)
+        self._spoint = torch.empty(scap, dtype=torch.int32, device=dev)         # uint32 on the device
+        self._ssample = torch.empty(scap, dtype=torch.uint8, device=dev)
+        dcap = cap if self.trace_diffuse else 0
+        self.diffuse_offsets = torch.zeros(cap + 1, **i64)
+        self._ddir, self._dw = torch.empty(3, dcap, **f32), torch.empty(1, dcap, **f32)
+        self._dpoint = torch.empty(dcap, dtype=torch.int32, device=dev)
+        self._scratch = scratch if scratch is not None else torch.empty(
+            max(sss_hits_scratch_bytes(self.n, self.spp_n, self.max_hits, cap, self.n_lights, self.hit_spp_n), 1),
+            dtype=torch.uint8, device=dev)
+        q = HitQueues_()
+        q.hit_capacity, q.hit_count, q.hit_element = cap, self._hit_count.data_ptr(), self._hit_element.data_ptr()
+        q.shadow.capacity, q.shadow.offsets = scap, self.shadow_offsets.data_ptr()
+        q.shadow.dir = capi.Vec3(*[self._sdir[k].data_ptr() for k in range(3)])
+        q.shadow.maxdist = self._smaxdist.data_ptr()
+        q.shadow.weight_diffuse = capi.Rgb(self._swd[0].data_ptr(), None, None)
+        q.shadow.kind, q.shadow.point, q.shadow.sample = self._skind.data_ptr(), self._spoint.data_ptr(), self._ssample.data_ptr()
+        q.diffuse.capacity, q.diffuse.offsets = dcap, self.diffuse_offsets.data_ptr()
+        q.diffuse.dir = capi.Vec3(*[self._ddir[k].data_ptr() for k in range(3)])
+        q.diffuse.weight = capi.Rgb(self._dw[0].data_ptr(), None, None)
+        q.diffuse.point = self._dpoint.data_ptr()
+        q.scratch, q.scratch_bytes = self._scratch.data_ptr(), self._scratch.numel()
+        self.q = q
+        self.lights = None       # what the last emit took and the resolve takes again
+        self.hits = None
+
+    @property
+    def hit_count(self) -> int:
+        return int(self._hit_count.item())
+
+    @property
+    def listed(self) -> int:
+        return min(self.hit_count, self.hit_capacity)
+
+    @property
+    def hit_element(self) -> torch.Tensor:
+        return self._hit_element[:self.listed]
+
+    @property
+    def shadow_count(self) -> int:
+        return int(self.shadow_offsets[self.hit_capacity].item()) if self.n_lights > 0 else 0
+
+    @property
+    def diffuse_count(self) -> int:
+        return int(self.diffuse_offsets[self.hit_capacity].item()) if self.trace_diffuse else 0
+
+    @property
+    def shadow(self) -> dict:
+        """the shadow rays' planes, the first ``shadow_count`` of each"""
+        c = self.shadow_count
+        return {"dir": self._sdir[:, :c], "maxdist": self._smaxdist[:c], "weight_diffuse": self._swd[:, :c],
+                "kind": self._skind[:c], "point": self._spoint[:c], "sample": self._ssample[:c]}
+
+    @property
+    def diffuse(self) -> dict:
+        c = self.diffuse_count
+        return {"dir": self._ddir[:, :c], "weight": self._dw[:, :c], "point": self._dpoint[:c]}
+
+    def resolve(self, visibility: Optional[torch.Tensor], radiance: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None, counts: Optional[tuple] = None) -> torch.Tensor:
+        """visibility [3, >= shadow_count] (None without lights), radiance [3, >= diffuse_count] (with trace_diffuse) -> E
+        [3, max_hits, stride], the layout of the hits' irradiance: exactly 0 at every hit that is not listed.  ``counts``:
+        (shadow_count, diffuse_count) where the caller knows them (skips the reads of the offsets)."""
+        if self.hits is None:
+            raise RuntimeError("resolve: no emit has filled these queues (trace.sss_hit_rays)")
+        ctx = self.ctx
+        sc, dc = counts if counts is not None else (self.shadow_count, self.diffuse_count)
+        vis = _radiance(visibility, sc, "visibility") if self.n_lights > 0 else capi.CRgb(None, None, None)
+        rad = _radiance(radiance, dc, "radiance") if self.trace_diffuse else capi.CRgb(None, None, None)
+        E = ctx.empty(3, self.max_hits, self.stride) if out is None else out
+        if E.dtype != torch.float32 or not E.is_cuda or E.shape != (3, self.max_hits, self.stride) or not E.is_contiguous():
+            raise ValueError(f"out: expected a contiguous float32 CUDA tensor [3, {self.max_hits}, {self.stride}]")
+        la, nl = self.lights
+        check(load().rls_trace_sss_hits_resolve(ctx.handle, C.byref(self.hits), la, nl, self.hit_spp_n,
+                                                1 if self.trace_diffuse else 0, C.byref(self.q), vis, rad,
+                                                capi.Rgb(*[E[k].data_ptr() for k in range(3)])))
+        return E
+
+
+def sss_hit_rays(sampler: SssSampler, P: torch.Tensor, probe_queue: ProbeQueue, count: torch.Tensor, hitP: torch.Tensor,
+                 hitN: torch.Tensor, lights, hit_spp_n: int, seed: int, *, hitT: Optional[torch.Tensor] = None,
+                 use_cavity_fade: bool = False, trace_diffuse: bool = False, hit_capacity: Optional[int] = None,
+                 hit_first_index: int = 0, queues: Optional[HitQueues] = None) -> HitQueues:
+    """shadeProbeSample's shading of the probe hits (src/rlSss.h:415-418) up to its traces: lists the hits the scatter resolve
+    counts as shaded and emits evalLightSample's shadow rays (an Oren-Nayar MIS light loop at roughness 0, hit_spp_n^2 samples a
+    light) and, with ``trace_diffuse``, integrateDiffuse's one ray at each.  sampler, P, probe_queue: those of the probe emit
+    (``sss_probe_rays``, or the ``probes`` of ``skin_node_rays`` with an SssSampler of the node's scatter parameters); count,
+    hitP, hitN: the hits as ``ProbeQueue.resolve`` takes them; hitT: the tangents at the hits in hitP's layout (None: the
+    library's own); lights: None, one ``make_light`` or a sequence; hit_capacity: the hits the list holds (default: every slot,
+    max_hits * rays).  The hit with element e samples from hash(seed, hit_first_index + e).  ``HitQueues.resolve`` turns the traced
+    visibility and radiance into the E planes of ``ProbeQueue.resolve`` / ``SkinNodeQueues.resolve``."""
+    ctx, n = sampler.ctx, sampler.n
+    if probe_queue.n != n:
+        raise ValueError("probe_queue: emitted for another batch size")
+    rays = probe_queue.count
+    hits = _probe_hits(count, hitP, hitN, None, rays)
+    T = capi.CVec3(None, None, None)
+    if hitT is not None:
+        if not isinstance(hitT, torch.Tensor) or hitT.dtype != torch.float32 or not hitT.is_cuda or hitT.shape != hitP.shape or \
+                not hitT.is_contiguous():
+            raise ValueError("hitT: expected a contiguous float32 CUDA tensor of hitP's shape")
+        T = capi.CVec3(*[hitT[k].data_ptr() for k in range(3)])
+    la, nl = light_array(lights)
+    cap = hits.max_hits * rays if hit_capacity is None else int(hit_capacity)
+    q = HitQueues(ctx, n, probe_queue.spp_n, hits.max_hits, hits.stride, cap, nl, hit_spp_n, trace_diffuse) \
+        if queues is None else queues
+    if (q.n, q.spp_n, q.max_hits, q.stride, q.n_lights, q.hit_spp_n, q.trace_diffuse) != \
+            (n, probe_queue.spp_n, hits.max_hits, hits.stride, nl, int(hit_spp_n), bool(trace_diffuse)) or \
+            (hit_capacity is not None and q.hit_capacity != cap):
+        raise ValueError("queues: allocated for another batch, hit layout, light count, hit_spp_n or trace_diffuse")
+    check(load().rls_trace_sss_hits_emit(ctx.handle, n, C.byref(sampler.c), _points(P, n), probe_queue.spp_n,
+                                         C.byref(probe_queue.q), C.byref(hits), T, 1 if use_cavity_fade else 0, la, nl,
+                                         int(hit_spp_n), 1 if trace_diffuse else 0, int(seed) & 0xFFFFFFFF, int(hit_first_index),
+                                         C.byref(q.q)))
+    q.lights, q.hits = (la, nl), hits
+    q._keep = (count, hitP, hitN, hitT)
     return q
 
 

@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss|ggx-lights|disney-lights|ggx-node|disney-node|skin-node] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
+    python tools/trace_bench.py [--closure ggx|disney|sss|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -16,6 +16,11 @@ rlSss: the emit writes 12 (origin) + 12 (dir) + 4 (maxdist) + 4 (point) + 1 (sam
 dense); the resolve reads 1 B of count per ray plus 12 (P) + 12 (N) + 12 (irradiance) = 36 B per reported hit slot.  Its
 hits come from a plane intersected with torch on the device (the shading points lie on the plane z = 0, lit from +z):
 timing needs plausible hits, not the oracle's.
+--closure sss-hits: the same plane and probe hits (about 0.5 a ray) shaded through the caller's tracer (trace.sss_hit_rays,
+HitQueues.resolve) under --lights lights at --hit-spp-n^2 samples a light (default 1), with the diffuse ray: the hits emit (the
+gate, the list, both queues) and the resolve, uniform random visibility and radiance; hit_capacity is the ray count (one slot a
+ray).  Beside them rls_trace_ggx_direct_emit over as many POINTS as there were listed hits (the hits' positions and normals,
+wo = N, diffuseRoughness 0) at the same lights and samples: the light loop alone, point-major, with its specular lobe.
 --closure ggx-lights / disney-lights: the shadow-ray emit and the visibility resolve of the node's light loop
 (trace.ggx_shadow_rays / disney_shadow_rays, ShadowQueue.resolve) next to rls_ggx_direct_lighting / rls_disney_direct_lighting on
 the same batch: --lights spherical lights (default 2, MIS on) over shading points in the slab [0,4) x [0,4) x [0,1), a uniform
@@ -156,6 +161,67 @@ def bench_sss(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
         "resolve_tb_per_s": rate(res_bytes, ms_res), "resolve_frac_of_8tbps": round(rate(res_bytes, ms_res) / HBM_TBPS, 4),
         "emit_over_integrate": round(ms_emit / ms_int, 4),
         "emit_plus_resolve_over_integrate": round((ms_emit + ms_res) / ms_int, 4),
+    }
+
+
+def bench_sss_hits(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """bench_sss's plane and hits, lit through the hit verbs; the rlGgx light-loop emit over as many points beside them"""
+    import math
+    import torch
+    import rlshaders_amd as R
+    from rlshaders_amd import trace as T
+    from rlshaders_amd.closures import make_light
+    g = torch.Generator(device=ctx.torch_device).manual_seed(seed)
+    dev = ctx.torch_device
+    nl, hs = args.lights, args.hit_spp_n
+    lights = [make_light(center=c, radius=r, radiance=e) for c, r, e in LIGHT_SPECS[:nl]]
+    Ns = torch.zeros(3, n, device=dev)
+    Ns[2] = 1
+    ang = torch.rand(n, device=dev, generator=g) * (2 * math.pi)
+    Tg = torch.stack([torch.cos(ang), torch.sin(ang), torch.zeros_like(ang)]).contiguous()
+    P = torch.zeros(3, n, device=dev)
+    P[:2] = torch.rand(2, n, device=dev, generator=g)
+    s = R.SssSampler(ctx, Ns, Tg, (0.8, 0.5, 0.3), (0.05, 0.1, 0.2))
+    q = T.sss_probe_rays(s, P, spp_n, seed)
+    O, D, md = q.origin, q.dir, q.maxdist
+    with torch.no_grad():
+        t = -O[2] / D[2]
+        ok = (D[2] != 0) & (t > 0) & (t <= md)
+        hP = torch.where(ok, O + D * t, torch.zeros_like(O)).unsqueeze(1).contiguous()
+        hN = torch.zeros_like(hP)
+        hN[2] = 1
+        hT = torch.zeros_like(hP)
+        hT[0] = 1
+        cnt = ok.to(torch.uint8)
+    rays = q.count
+    hq = T.HitQueues(ctx, n, spp_n, 1, rays, rays, nl, hs, True)
+    emit = lambda: T.sss_hit_rays(s, P, q, cnt, hP, hN, lights, hs, seed, hitT=hT, trace_diffuse=True, queues=hq)
+    ms_emit = timed(emit, args.repeats, args.warmup)
+    listed, sc, dc = hq.listed, hq.shadow_count, hq.diffuse_count
+    vis = torch.rand(3, max(sc, 1), device=dev)
+    rad = torch.rand(3, max(dc, 1), device=dev)
+    E = ctx.empty(3, 1, rays)
+    ms_res = timed(lambda: hq.resolve(vis, rad, out=E, counts=(sc, dc)), args.repeats, args.warmup)
+    # the light loop alone over `listed` points: the listed hits as an rlGgx batch
+    el = hq.hit_element
+    gP, gN, gT = (x.reshape(3, -1)[:, el].contiguous() for x in (hP, hN, hT))
+    m = max(listed, 1)
+    gg = R.GgxSampler(ctx, gN, gN, gT, specColor=(0.9, 0.5, 0.3), ior=1.45, roughness=0.3) if listed else None
+    ms_ggx, ggx_rays = float("nan"), 0
+    if gg is not None:
+        sh = T.ggx_shader(gg, KdColor=(1.0, 1.0, 1.0), Kd=1.0, diffuseRoughness=0.0, Ks=0.5)
+        gq = T.ShadowQueue(ctx, m, nl, hs)
+        ms_ggx = timed(lambda: T.ggx_shadow_rays(gg, sh, gP, lights, hs, seed, queue=gq), args.repeats, args.warmup)
+        ggx_rays = gq.count
+    out_rays = sc + dc
+    rec["lights"], rec["hit_spp_n"] = nl, hs
+    rec["sss-hits"] = {
+        "probe_rays": rays, "hit_capacity": rays, "listed_hits": listed, "hits_per_ray": round(listed / rays, 4),
+        "shadow_rays": sc, "diffuse_rays": dc, "emit_ms": round(ms_emit, 4), "resolve_ms": round(ms_res, 4),
+        "emit_rays_per_s": round(out_rays / (ms_emit * 1e-3), 1), "resolve_rays_per_s": round(out_rays / (ms_res * 1e-3), 1),
+        "emit_hits_per_s": round(listed / (ms_emit * 1e-3), 1),
+        "ggx_direct_emit_ms_over_listed_points": round(ms_ggx, 4), "ggx_direct_emit_rays": ggx_rays,
+        "emit_over_ggx_direct_emit": round(ms_emit / ms_ggx, 4),
     }
 
 
@@ -361,9 +427,10 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
-    ap.add_argument("--closure", choices=("ggx", "disney", "sss", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node"),
+    ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node"),
                     default="ggx")
     ap.add_argument("--lights", type=int, default=2, help="the light loops: spherical lights, 1..8")
+    ap.add_argument("--hit-spp-n", type=int, default=1, help="sss-hits: the light loop at the hits draws hit_spp_n^2 samples a light")
     args = ap.parse_args()
     if args.repeats < 3:
         ap.error("--repeats must be at least 3")
@@ -383,7 +450,7 @@ def main() -> None:
            "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
     if args.closure != "ggx":
         rec["closure"] = args.closure
-        {"disney": bench_disney, "sss": bench_sss, "ggx-node": bench_node, "disney-node": bench_node,
+        {"disney": bench_disney, "sss": bench_sss, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
          "skin-node": bench_skin_node}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
