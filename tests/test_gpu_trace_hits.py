@@ -53,12 +53,20 @@ class Hits:
     """one synthetic hit list over N_PTS points (trace_hits_util.synthetic_hits) on the device, with the probe queue the verbs
     take and the flattened elements the references run over"""
 
-    def __init__(self, T, ctx, n=N_PTS, spp_n=SPP_N, max_hits=MAX_HITS, pad=5, seed=3, dense=False):
+    def __init__(self, T, ctx, n=N_PTS, spp_n=SPP_N, max_hits=MAX_HITS, pad=5, seed=3, dense=False, shape=None, src=None):
+        """shape(self): edits the host planes (case, cnt, hP, hN, hT) before they go to the device; src: another Hits of the
+        same sizes whose host planes are taken as they are (the same hits on another context)"""
         self.T, self.ctx, self.n, self.spp_n, self.max_hits = T, ctx, n, spp_n, max_hits
         self.spp = spp_n * spp_n
         self.stride = n * self.spp + pad
-        self.case, self.cnt, self.hP, self.hN = synthetic_hits(n, self.spp, max_hits, self.stride, seed, dense)
-        self.hT = orthogonal_tangent(self.hN.reshape(3, -1), seed + 1).reshape(self.hN.shape)
+        if src is None:
+            self.case, self.cnt, self.hP, self.hN = synthetic_hits(n, self.spp, max_hits, self.stride, seed, dense)
+            self.hT = orthogonal_tangent(self.hN.reshape(3, -1), seed + 1).reshape(self.hN.shape)
+            if shape is not None:
+                shape(self)
+        else:
+            assert (src.n, src.spp_n, src.max_hits, src.stride) == (n, spp_n, max_hits, self.stride)
+            self.case, self.cnt, self.hP, self.hN, self.hT = src.case, src.cnt, src.hP, src.hN, src.hT
         self.s = _sss(ctx, self.case)
         self.P = dev(self.case["P"])
         self.pq = T.sss_probe_rays(self.s, self.P, spp_n, SEED)
@@ -230,35 +238,33 @@ def test_the_list_is_the_scatter_resolves_gate(gpu, oracle, T, cavity):
 
 
 # ---- 3. the shadow queue --------------------------------------------------------------------------------------------------------
-def test_shadow_rays_are_the_diffuse_rays_of_the_ggx_emit(gpu, oracle, T):
-    specs = LIGHTS
-    _, lights = _lights(oracle, specs)
-    hits = Hits(T, gpu)
-    hit_spp_n = 3
-    hit_spp = hit_spp_n * hit_spp_n
-    el = hits.elements(True)
-    hq = hits.emit(lights, hit_spp_n, use_cavity_fade=True)
-    sh, _, elements, _ = queues_host(hq)
-    np.testing.assert_array_equal(elements, el)
+def assert_shadow_rays_are_the_ggx_emit(T, hits, sh, elements, lights, hit_spp_n, first=0, min_rays=1000):
+    """the shadow queue `sh` over the list `elements` holds the diffuse-carrying rays of rls_trace_ggx_direct_emit over the
+    flattened elements (hits: a Hits on the context the reference runs on), by (element, light, segment, sample): the same set,
+    the same dir, weight_diffuse and maxdist bits"""
     g, Pf = hits.ggx()
     q = T.ggx_shadow_rays(g, T.ggx_shader(g, KdColor=(1.0, 1.0, 1.0), Kd=1.0, diffuseRoughness=0.0, Ks=0.5), Pf, lights,
-                          hit_spp_n, SEED)
+                          hit_spp_n, SEED, first)
     h = queue_host(q)
     listed = np.zeros(hits.max_hits * hits.stride, bool)
-    listed[el] = True
+    listed[elements] = True
     m = ((h["kind"] & DIFFUSE) != 0) & listed[h["point"]]
     ref = {k: h[k][..., m] for k in ("dir", "maxdist", "wd", "kind", "point", "sample")}
     ours, theirs = shadow_keys(sh, elements), shadow_keys(ref)
-    assert sh["count"] > 1000
+    assert sh["count"] > min_rays
     # the same (element, light, segment, sample) set; ours in list order, theirs in element order
     oa, ob = np.argsort(ours, kind="stable"), np.argsort(theirs, kind="stable")
     np.testing.assert_array_equal(ours[oa], theirs[ob])
     assert np.all(np.diff(ours[oa]) > 0)
     for k in ("dir", "wd", "maxdist"):
         assert _bytes_equal(sh[k][..., oa], ref[k][..., ob]), k
-    # order, kind, cone and maxdist invariants, as tests/test_gpu_trace_lights.py holds them for a light loop's queue
+
+
+def assert_shadow_queue_invariants(hits, sh, elements, cap, specs, hit_spp, maxdist=True):
+    """order, kind, cone and maxdist invariants of the shadow queue `sh` over the list `elements` (capacity `cap`), as
+    tests/test_gpu_trace_lights.py holds them for a light loop's queue; specs: the lights' dicts"""
+    el = elements
     off, kind = sh["offsets"], sh["kind"]
-    cap = hq.hit_capacity
     assert off[0] == 0 and np.all(np.diff(off) >= 0) and np.all(np.diff(off) <= len(specs) * 2 * hit_spp)
     assert off[cap] == sh["count"] and np.all(off[len(el):] == sh["count"])
     np.testing.assert_array_equal(sh["point"], np.repeat(np.arange(cap), np.diff(off)))
@@ -267,18 +273,34 @@ def test_shadow_rays_are_the_diffuse_rays_of_the_ggx_emit(gpu, oracle, T):
     assert np.all(sh["sample"] < hit_spp)
     modes = np.array([sp["mis_mode"] for sp in specs])[kind & LIGHT_MASK]
     bs = (kind & BSDF) != 0
-    assert not np.any(bs & (modes == 1)) and not np.any(~bs & (modes == 2)) and bs.any() and (~bs).any()
-    assert not np.any((kind & LIGHT_MASK) == 3)                      # the light around every hit
+    assert not np.any(bs & (modes == 1)) and not np.any(~bs & (modes == 2))
     assert np.all(np.isfinite(sh["maxdist"])) and np.all(sh["maxdist"] > 0) and np.all(sh["wd"] != 0)
     hP, hN = hits.hP.reshape(3, -1)[:, elements[sh["point"]]], hits.hN.reshape(3, -1)[:, elements[sh["point"]]]
     assert np.all((sh["dir"] * hN).sum(axis=0, dtype=F) > 0)         # above the hit's horizon
     for li, sp in enumerate(specs):
         mm = (kind & LIGHT_MASK) == li
-        if mm.any():
+        if maxdist and mm.any():
             t, disc, b = near_hit_f64(sp["center"], sp["radius"], hP[:, mm], sh["dir"][:, mm])
             away = disc >= 1e-5 * b * b                              # (within a few ulp of tangency maxdist loses its digits)
             rel = np.abs(sh["maxdist"][mm].astype(np.float64) - t) / t
             assert rel[away].max() <= 4 * 4.097e-5, (li, rel[away].max())   # test_gpu_trace_lights.py's bound
+
+
+def test_shadow_rays_are_the_diffuse_rays_of_the_ggx_emit(gpu, oracle, T):
+    specs = LIGHTS
+    _, lights = _lights(oracle, specs)
+    hits = Hits(T, gpu)
+    hit_spp_n = 3
+    el = hits.elements(True)
+    hq = hits.emit(lights, hit_spp_n, use_cavity_fade=True)
+    sh, _, elements, _ = queues_host(hq)
+    np.testing.assert_array_equal(elements, el)
+    assert_shadow_rays_are_the_ggx_emit(T, hits, sh, elements, lights, hit_spp_n)
+    assert_shadow_queue_invariants(hits, sh, elements, hq.hit_capacity, specs, hit_spp_n * hit_spp_n)
+    kind = sh["kind"]
+    bs = (kind & BSDF) != 0
+    assert bs.any() and (~bs).any()
+    assert not np.any((kind & LIGHT_MASK) == 3)                      # the light around every hit
 
 
 # ---- 4. the diffuse ray ---------------------------------------------------------------------------------------------------------
@@ -310,7 +332,7 @@ def test_diffuse_ray_direction_and_weight(gpu, oracle, T, fast):
         gpu.set_math_mode(False)
 
 
-def test_coloured_visibility_and_radiance_follow_the_documented_composition(gpu, oracle, T):
+def assert_documented_composition(gpu, hits, lights, hit_spp_n, seed=17):
     """E_c = direct_c + (radiance_c * weight) * AI_ONEOVERPI in float32 in that order, bit for bit; and within a float64 bound.
     The bound, as tests/trace_lights_util.assert_float64_bound derives shadow_resolve_kernel's: a light's k_l rays cost one
     rounding per product and at most k_l per sum's additions, the light's close three more (the two strategies' sums added, x
@@ -318,13 +340,10 @@ def test_coloured_visibility_and_radiance_follow_the_documented_composition(gpu,
     terms' magnitudes, k the hit's rays, u = 2^-24 (no tail here: rlGgx's two are not spent).  The diffuse term has two roundings,
     the final addition one more on everything: |E - exact| <= ((k + 3 nl + 1) M_direct + 3 M_diffuse) u to first order, taken as
     gamma_m = m u / (1 - m u) per count m.  The float64 composition uses the float32 constant AI_ONEOVERPI, as the kernel."""
-    _, lights = _lights(oracle, LIGHTS)
     rad_l = np.array([[l.radiance[k] for k in range(3)] for l in lights], F)
-    hits = Hits(T, gpu)
-    hit_spp_n = 2
     hq = hits.emit(lights, hit_spp_n, trace_diffuse=True, use_cavity_fade=True)
     sh, df, elements, _ = queues_host(hq)
-    rng = np.random.default_rng(17)
+    rng = np.random.default_rng(seed)
     vis = (10.0 ** rng.uniform(-8, 0, (3, sh["count"]))).astype(F)
     rad = (rng.random((3, df["count"])) * 10.0 ** rng.uniform(-4, 4, (3, df["count"]))).astype(F)
     # past the rays: NaN that nothing may read; E inside sentinels
@@ -348,6 +367,18 @@ def test_coloured_visibility_and_radiance_follow_the_documented_composition(gpu,
     bound = gamma(k + 3 * len(lights) + 1)[None, :] * mdir + gamma(3.0) * mdif + 1e-44
     err = np.abs(E.reshape(3, -1)[:, elements].astype(np.float64) - e64.reshape(3, -1)[:, elements])
     assert np.all(err <= bound), float((err / bound).max())
+    return dict(hq=hq, sh=sh, df=df, elements=elements, rng=rng, vis=vis, rad=rad, visd=visd, radd=radd, E=E, shape=shape,
+                rad_l=rad_l, listed=listed)
+
+
+def test_coloured_visibility_and_radiance_follow_the_documented_composition(gpu, oracle, T):
+    """assert_documented_composition at hit_spp_n = 2 under the eight lights; then non-finite values"""
+    _, lights = _lights(oracle, LIGHTS)
+    hits = Hits(T, gpu)
+    hit_spp_n = 2
+    r = assert_documented_composition(gpu, hits, lights, hit_spp_n)
+    hq, sh, df, elements, rng, vis, rad = (r[k] for k in ("hq", "sh", "df", "elements", "rng", "vis", "rad"))
+    visd, radd, E, shape, rad_l, listed = (r[k] for k in ("visd", "radd", "E", "shape", "rad_l", "listed"))
     # a non-finite visibility or radiance stays in its hit
     vis2, rad2 = vis.copy(), rad.copy()
     bad_s, bad_d = rng.choice(sh["count"], 9, replace=False), rng.choice(df["count"], 5, replace=False)

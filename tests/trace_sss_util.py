@@ -79,6 +79,42 @@ def trace_plane_np(plane_point, plane_normal, origin, dirs, maxdist):
     return ok.astype(np.uint8), np.ascontiguousarray(hP), np.ascontiguousarray(hN)
 
 
+def trace_sphere_np(center, radius, origin, dirs, maxdist):
+    """orc_scene_trace of a sphere, vectorised in float32 with the same operations in the same order (the two roots in
+    ascending order, those in (0, maxdist] kept and packed to the front) -> (count uint8, P [3, 2, rays], N [3, 2, rays])"""
+    f = np.float32
+    c, rad = np.asarray(center, f), f(radius)
+    dot = lambda a, b: ((a[0] * b[0] + a[1] * b[1]).astype(f) + a[2] * b[2]).astype(f)
+    rays = origin.shape[1]
+    cnt = np.zeros(rays, np.uint8)
+    hP, hN = np.zeros((3, 2, rays), f), np.zeros((3, 2, rays), f)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        oc = (origin - c[:, None]).astype(f)
+        a, b = dot(dirs, dirs), dot(oc, dirs)
+        cc = (dot(oc, oc) - (rad * rad).astype(f)).astype(f)
+        disc = ((b * b).astype(f) - (a * cc).astype(f)).astype(f)
+        roots = ~(disc < 0) & (a != 0)
+        sq = np.sqrt(disc).astype(f)
+        for cand in (((-b - sq).astype(f) / a).astype(f), ((-b + sq).astype(f) / a).astype(f)):
+            ok = roots & (cand > 0) & (cand <= maxdist)
+            hp = (origin + (dirs * cand).astype(f)).astype(f)
+            v = (hp - c[:, None]).astype(f)
+            ln = np.sqrt(dot(v, v)).astype(f)
+            inv = np.where(ln != 0, f(1) / ln, ln).astype(f)
+            hn = (v * inv).astype(f)
+            j = np.flatnonzero(ok)
+            hP[:, cnt[j], j], hN[:, cnt[j], j] = hp[:, j], hn[:, j]
+            cnt[j] += 1
+    return cnt, hP, hN
+
+
+def trace_np(scene, origin, dirs, maxdist):
+    """orc_scene_trace of every ray, vectorised (trace_plane_np / trace_sphere_np by the scene's geometry)"""
+    if scene.geometry == 0:
+        return trace_plane_np(scene.plane_point[:], scene.plane_normal[:], origin, dirs, maxdist)
+    return trace_sphere_np(scene.sphere_center[:], scene.sphere_radius, origin, dirs, maxdist)
+
+
 def light_irradiance(scene, hP, hN):
     """E = light_color * (AI_ONEOVERPI * max(0, N.L)), 0 where the gate is shut: evalLightSample of the analytic scene
     before evalProfile and the fade (float32, the integrator's operations) -> [3, K, stride]"""
