@@ -500,6 +500,98 @@ rls_status rls_trace_skin_resolve(rls_context *ctx, int64_t n, const rls_skin_cl
                                   int spp_n, const rls_skin_node_queues *q, const rls_skin_node_traced *t,
                                   const rls_skin_integrate_out *out);
 
+/* ------------------------------------------------------------------------------------------
+ * Secondary-ray hits: rlGgx and rlDisney shaded at the hits of the rays a node emit queued.  rls_trace_*_shade_emit / _resolve
+ * shade every point as a camera ray at depth 0; the rays they emit land on surfaces that carry the same nodes, and there
+ * shader_evaluate reads sg->Rt, the sg->Rr* counters and the options' GI_*_depth (src/rlGgx.cpp:264-323,
+ * src/rlDisney.cpp:706-725).  The bounce calls take that state PER POINT, so that one wavefront of hits may mix ray types
+ * and depths; queue structs, traced structs, output structs, scratch rules and capacities are the node calls' own (a
+ * refraction queue still needs n * spp_n^2 slots), and so are the samples: with every point a camera ray at depth 0 and
+ * depths that leave every switch open the bounce calls write the node calls' bytes (rlGgx: traced = 1; depths.refraction = 0
+ * gives traced = 0).
+ *
+ * Per point i, with rt = ray_type[i] (tested with & as the reference tests sg->Rt) and d = *depths:
+ *   a point with rt & RLS_RT_SHADOW queues nothing and every output plane is +0 there (the reference returns an opacity, which
+ *   stays with the caller, like the opacity branch itself); for every other point, cam = rt & RLS_RT_CAMERA and
+ *
+ *   rlGgx     sD = !small(KdColor * Kd) && Rr_diff[i] <= d.diffuse            (sampleDiffuse)
+ *             sS = Rr_gloss[i] <= d.glossy
+ *             tr = Rr_refr[i] < d.refraction && Rr[i] < d.total               (integrateRefract's traced branch)
+ *     shadow queue:   rls_trace_ggx_direct_emit's rays, each with the terms of the open lobes only: the diffuse term and the BSDF
+ *                     diffuse-lobe segment exist iff sD, the specular term and the BSDF specular-lobe segment iff sS.  A ray whose
+ *                     terms are all shut is not queued; kind has the bits of the terms that are left; dir, maxdist and both
+ *                     weight planes are what rls_trace_ggx_direct_emit writes for that ray (a weight whose bit is clear is not
+ *                     meaningful), and the order is kept.
+ *     refract queue:  behind small(KtColor * Kt) as in the node call; a tr point has integrateRefract's samples (pair 25), any
+ *                     other the ONE ray of the untraced branch at sample 0, kind RLS_RAY_TRANSMITTED, none on total internal
+ *                     reflection.
+ *     glossy queue:   the node call's rays iff cam.      diffuse queue: the node call's rays iff cam && sD.
+ *     resolve:        direct_diffuse = o_D * (KdColor * Kd), direct_specular = o_S * Ks with o_D / o_S the light loop's sums, +0
+ *                     where !sD / !sS; refraction as in the node call with inv = 1 / spp_n^2 at a tr point and 1 at any other;
+ *                     indirect_diffuse and indirect_specular as in the node call where cam, else 0;
+ *                     out = ((direct_diffuse + direct_specular) + refraction) + (indirect_diffuse + indirect_specular) where
+ *                     cam, else (direct_diffuse + direct_specular) + refraction.
+ *   rlDisney  the light loop is whole: the shadow queue is rls_trace_disney_direct_emit's.
+ *     diffuse queue:  the node call's rays iff cam && Rr_diff[i] < d.diffuse && Rr[i] < d.total     (shouldTraceDiffuse)
+ *     specular queue: the node call's rays iff cam && Rr_gloss[i] < d.glossy && Rr[i] < d.total     (shouldTraceGlossy)
+ *     resolve:        where rt & (RLS_RT_DIFFUSE | RLS_RT_GLOSSY): direct_diffuse = sum * indirectDiffuseScale, direct_specular
+ *                     = sum * indirectSpecularScale, each product rounded to float32 before any sum; the indirect AOVs as in the
+ *                     node call where cam, else 0; out = (direct_diffuse + direct_specular) + (indirect_diffuse +
+ *                     indirect_specular) where cam, else direct_diffuse + direct_specular.
+ * The AOV planes are written for every point: whether a secondary ray's AOVs are kept is the renderer's decision.
+ *
+ * Both calls return RLS_ERR_INVALID_ARGUMENT before the context is read for a NULL state, a NULL depths or a NULL plane of the
+ * state (n > 0), and for whatever the node calls refuse.  Neither synchronises the host; both can be recorded into an
+ * rls_graph.  The state planes are indexed by the point's index in THIS call, like P.
+ *
+ * Not covered: rlSkin (its Rr == 0 test changes the mean-Fresnel hand-down, and integrateScatter swaps to an Oren-Nayar light
+ * loop on diffuse rays), the opacity branch and the shadow-ray branch of either node.
+ * ---------------------------------------------------------------------------------------- */
+
+/* sg->Rt */
+enum { RLS_RT_CAMERA = 0x01, RLS_RT_SHADOW = 0x02, RLS_RT_REFLECTED = 0x04, RLS_RT_REFRACTED = 0x08,
+       RLS_RT_DIFFUSE = 0x20, RLS_RT_GLOSSY = 0x40 };
+/* the options' GI_total_depth, GI_diffuse_depth, GI_glossy_depth, GI_refraction_depth */
+typedef struct rls_gi_depths { int total, diffuse, glossy, refraction; } rls_gi_depths;
+/* sg->Rt, sg->Rr, sg->Rr_diff, sg->Rr_gloss, sg->Rr_refr per point: [n] each, device, all five required */
+typedef struct rls_ray_state {
+    const uint8_t *ray_type, *Rr, *Rr_diff, *Rr_gloss, *Rr_refr;
+} rls_ray_state;
+
+/* rls_trace_ggx_shade_emit / _resolve with the per-point state in place of the call-level `traced`. */
+rls_status rls_trace_ggx_bounce_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                     rls_cvec3 P, const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                     uint64_t first_index, const rls_ray_state *state, const rls_gi_depths *depths,
+                                     const rls_ggx_node_queues *q);
+rls_status rls_trace_ggx_bounce_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                        const rls_sphere_light *lights, int n_lights, int spp_n, const rls_ray_state *state,
+                                        const rls_gi_depths *depths, const rls_ggx_node_queues *q,
+                                        const rls_ggx_node_traced *t, const rls_ggx_shade_out *out);
+
+/* rls_trace_disney_shade_emit / _resolve with the per-point state.  The resolve takes the node's indirectDiffuseScale and
+ * indirectSpecularScale, parameters like the closure's: per-point planes, uniform values, or looked up through c->materials
+ * (of c the resolve reads nothing else). */
+rls_status rls_trace_disney_bounce_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
+                                        const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                        uint64_t first_index, const rls_ray_state *state, const rls_gi_depths *depths,
+                                        const rls_disney_node_queues *q);
+rls_status rls_trace_disney_bounce_resolve(rls_context *ctx, int64_t n, const rls_disney_closure *c,
+                                           rls_param indirectDiffuseScale, rls_param indirectSpecularScale,
+                                           const rls_sphere_light *lights, int n_lights, int spp_n,
+                                           const rls_ray_state *state, const rls_gi_depths *depths,
+                                           const rls_disney_node_queues *q, const rls_disney_node_traced *t,
+                                           const rls_disney_shade_out *out);
+
+/* The state of the hits of a queue's rays.  point: the queue's point plane (rls_ray_queue.point / rls_shadow_queue.point), rays:
+ * its ray count, which the caller has read (offsets[n]); parent: the state of the points the queue was emitted for; ray_type:
+ * the RLS_RT_* bits of the queue's rays; child: five WRITABLE planes of `rays` bytes.  Per ray k, with p = point[k]:
+ *     child.ray_type[k] = ray_type;  child.Rr[k] = min(255, parent.Rr[p] + 1);
+ *     child.Rr_diff / Rr_gloss / Rr_refr[k] = min(255, parent's + 1) where ray_type has RLS_RT_DIFFUSE / _GLOSSY / _REFRACTED,
+ *     else the parent's.
+ * rays == 0 launches nothing.  Never synchronises the host. */
+rls_status rls_trace_ray_state_advance(rls_context *ctx, int64_t rays, const uint32_t *point, const rls_ray_state *parent,
+                                       int ray_type, const rls_ray_state *child);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,11 +145,12 @@ def build_trace_library(force: bool = False, verbose: bool = False) -> Path:
     return TRACE_LIB
 
 
-def build_trace_example(verbose: bool = False) -> Path:
-    """host/example_trace.cpp against both libraries (emit -> a host-side \"tracer\" -> resolve)."""
+def build_trace_example(verbose: bool = False, name: str = "example_trace") -> Path:
+    """host/example_trace.cpp (or ``name``: example_trace_bounce) against both libraries (emit -> a host-side \"tracer\" ->
+    resolve)."""
     OBJDIR.mkdir(exist_ok=True)
     lib = build_trace_library(verbose=verbose)
-    src, out = PKG / "host" / "example_trace.cpp", OBJDIR / "example_trace"
+    src, out = PKG / "host" / f"{name}.cpp", OBJDIR / name
     if _stale(out, [src, PKG / "host" / "rls_trace.hpp", lib, LIB, *HEADERS, *TRACE_HEADERS]):
         cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{PKG / 'host'}", str(src), "-o", str(out),
                f"-L{LIBDIR}", "-lrls_trace", "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
@@ -157,7 +158,7 @@ def build_trace_example(verbose: bool = False) -> Path:
             print(" ".join(cmd), flush=True)
         p = subprocess.run(cmd, capture_output=True, text=True)
         if p.returncode != 0:
-            raise RuntimeError(f"host example example_trace failed to build:\n{p.stdout}\n{p.stderr}")
+            raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
     return out
 
 

@@ -70,6 +70,39 @@ __device__ __forceinline__ uint32_t shadow_tag(bool keep, int rank, int kind)
     return keep ? (uint32_t)rank | (uint32_t)kind << 16 : kShadowDropped;
 }
 
+// Secondary-ray hits (rls_trace_*_bounce_emit / _resolve): the caller's per-point ray state and the options' depth limits, and
+// the ray-depth switches of the two shader_evaluate read off them at point i -- each switch written here once, for the emits
+// that gate a queue by it and the resolve that gates the AOV.  A point of a shadow ray (sg->Rt & AI_RAY_SHADOW,
+// src/rlGgx.cpp:264-269) shades nothing: every switch is shut.
+struct BounceState {
+    rls_ray_state s;
+    rls_gi_depths d;
+};
+struct BounceGates {
+    bool lit;                // not a shadow ray's point: the light loop runs
+    bool cam;                // sg->Rt & AI_RAY_CAMERA: the indirect loops and their AOVs (src/rlGgx.cpp:307, src/rlDisney.cpp:713)
+    bool diffuse;            // rlGgx: Rr_diff <= GI_diffuse_depth, sampleDiffuse's depth half (src/rlGgx.cpp:280)
+    bool specular;           // rlGgx: Rr_gloss <= GI_glossy_depth (:292)
+    bool traced;             // rlGgx: Rr_refr < GI_refraction_depth && Rr < GI_total_depth, integrateRefract's branch (src/rlGgx.h:210)
+    bool scaled;             // rlDisney: sg->Rt & (AI_RAY_DIFFUSE | AI_RAY_GLOSSY), the direct terms' scales (src/rlDisney.cpp:706)
+    bool trace_diffuse;      // rlDisney: cam && Rr_diff < GI_diffuse_depth && Rr < GI_total_depth (shouldTraceDiffuse, :75-83)
+    bool trace_glossy;       // rlDisney: cam && Rr_gloss < GI_glossy_depth && Rr < GI_total_depth
+};
+__device__ __forceinline__ BounceGates bounce_gates(const BounceState &b, int64_t i)
+{
+    const int rt = b.s.ray_type[i], rr = b.s.Rr[i], rd = b.s.Rr_diff[i], rg = b.s.Rr_gloss[i], rf = b.s.Rr_refr[i];
+    BounceGates g;
+    g.lit = !(rt & RLS_RT_SHADOW);
+    g.cam = g.lit && (rt & RLS_RT_CAMERA);
+    g.diffuse = g.lit && rd <= b.d.diffuse;
+    g.specular = g.lit && rg <= b.d.glossy;
+    g.traced = rf < b.d.refraction && rr < b.d.total;
+    g.scaled = (rt & (RLS_RT_DIFFUSE | RLS_RT_GLOSSY)) != 0;
+    g.trace_diffuse = g.cam && rd < b.d.diffuse && rr < b.d.total;
+    g.trace_glossy = g.cam && rg < b.d.glossy && rr < b.d.total;
+    return g;
+}
+
 struct NoShader {};
 template <class Closure, class Shader>
 struct ShadowEmitIO {
@@ -88,6 +121,7 @@ struct ShadowEmitIO {
     int spp;
     uint32_t seed;
     uint64_t first;
+    BounceState st;          // the bounce calls' kernels alone read it
 };
 
 struct ShadowCompactIO {
@@ -136,8 +170,9 @@ struct GgxNodeResolveIO {
     rls_param_rgb KsColor;   // integrateGlossy's gate
     rls_rgb out;
     float inv;               // 1 / spp
-    int traced;
+    int traced;              // (the bounce call: per point, off st)
     int64_t n;
+    BounceState st;          // the bounce call's kernel alone reads it
 };
 struct DisneyNodeResolveIO {
     ShadowResolveIO s;
@@ -145,6 +180,26 @@ struct DisneyNodeResolveIO {
     rls_rgb out;
     float inv;
     int64_t n;
+    BounceState st;          // the bounce call's kernel alone reads these: the state, and the node's two scales on the direct
+    rls_material_index materials;                // terms (indirectDiffuseScale, indirectSpecularScale)
+    rls_param diffuse_scale, specular_scale;
+};
+
+// the bounce calls' ray emits: the node emits' argument structs with the state (the light loops' emit and the resolves carry it
+// in their own structs: one body serves both of their kernels)
+struct GgxBounceEmitIO : GgxNodeEmitIO {
+    BounceState st;
+};
+struct DisneyBounceEmitIO : EmitIO<rls_disney_closure> {
+    BounceState st;
+};
+// rls_trace_ray_state_advance
+struct StateAdvanceIO {
+    const uint32_t *point;
+    rls_ray_state parent;
+    uint8_t *child[5];       // ray_type, Rr, Rr_diff, Rr_gloss, Rr_refr
+    int ray_type;
+    int64_t rays;
 };
 
 // rlSkin's node (rls_trace_skin_emit / _resolve).  A lobe's light loop (ggx_light_loops, rls_loops.hpp) draws a light sample and a

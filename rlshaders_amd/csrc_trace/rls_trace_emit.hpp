@@ -24,6 +24,7 @@ struct EmitRay {
 //   Lobe(a, ii)              the closure at point ii
 //   kStream                  its scramble streams: kScrambleStream + kStream, + kStream + 1
 //   kGated, open             a node's gate (kGated): a point whose gate is shut (!open) draws nothing and queues nothing
+//   kPerSample, wants(s)     a lobe that takes only some of an open point's samples (kPerSample): the others draw and queue nothing
 //   kPush, push(...)         the first sweep of the packed rare branches (SlowLds), if it has one
 //   kWeights, sample(...)    the per-sample term, in every lane of every round; returns whether the ray is queued
 //   side(spp)                the point's side output, in every lane (group reductions)
@@ -52,14 +53,18 @@ __device__ __forceinline__ void emit_points(const IO &a)
                 for (int k = 0; k < K; k++) {
                     const int s = s0 + k * G;
                     const int sc = s < a.spp ? s : 0;
-                    lobe.push(slow, k, cnt, s < a.spp && open, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
+                    bool ok = s < a.spp && open;
+                    if constexpr (Lobe::kPerSample) ok = ok && lobe.wants(s);
+                    lobe.push(slow, k, cnt, ok, bits_u01(tab[0][sc] ^ sx), bits_u01(tab[1][sc] ^ sy));
                 }
                 slow_run<K>(slow, cnt);
             }
 #pragma unroll 1
             for (int k = 0; k < K; k++) {
                 const int s = s0 + k * G;
-                const bool in = s < a.spp, ok = in && open;
+                const bool in = s < a.spp;
+                bool ok = in && open;
+                if constexpr (Lobe::kPerSample) ok = ok && lobe.wants(s);
                 float rx = 0.0f, ry = 0.0f;                             // a lobe without a push phase draws here
                 if (!Lobe::kPush && ok) { rx = bits_u01(tab[0][s] ^ sx); ry = bits_u01(tab[1][s] ^ sy); }
                 EmitRay r = {};
@@ -89,6 +94,7 @@ struct GgxLobe {
     static constexpr int kStream = 0;
     static constexpr bool kPush = true;
     static constexpr bool kGated = false;
+    static constexpr bool kPerSample = false;
     Ggx g;
     VndfView w;
     GgxLobe() = default;                                         // (rlSkin's lobes build g and w themselves: SkinGlossy)
@@ -165,6 +171,7 @@ struct DisneyLobe {
     static constexpr int kStream = STREAM;
     static constexpr bool kPush = SPEC;
     static constexpr bool kGated = false;
+    static constexpr bool kPerSample = false;
     static constexpr int kWeights = 3;
     Disney d;
     VndfView w;
@@ -293,6 +300,7 @@ struct GgxNodeDiffuse {
     static constexpr int kStream = kNodeStream + 4;
     static constexpr bool kPush = false;
     static constexpr bool kGated = true;
+    static constexpr bool kPerSample = false;
     static constexpr int kWeights = 1;
     Frame fr;
     OrenNayar on;
@@ -346,4 +354,75 @@ template <int G, int FAST_MATH = RLS_FAST>
 __global__ RLS_INT_ATTR void disney_node_specular_emit_kernel(EmitIO<rls_disney_closure> a)
 {
     emit_points<G, DisneyLobe<G, true, kNodeStream + 2>>(a);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Secondary-ray hits (rls_trace_*_bounce_emit): the node's lobes with `open`, and for refraction `traced`, read off the point's
+// ray state (bounce_gates, rls_trace_device.hpp) on top of the node's own gates.  Every point of a launch runs at the call's spp.
+
+// integrateGlossy: camera rays only (src/rlGgx.cpp:307)
+template <int G>
+struct GgxBounceGlossy : GgxNodeGlossy<G> {
+    __device__ GgxBounceGlossy(const GgxBounceEmitIO &a, int64_t ii) : GgxNodeGlossy<G>(a, ii)
+    {
+        this->open = this->open && bounce_gates(a.st, ii).cam;
+    }
+};
+// integrateRefract: the branch per point; the untraced branch's one ray is sample 0 of the point
+template <int G>
+struct GgxBounceRefract : GgxNodeRefract<G> {
+    static constexpr bool kPerSample = true;
+    __device__ GgxBounceRefract(const GgxBounceEmitIO &a, int64_t ii) : GgxNodeRefract<G>(a, ii)
+    {
+        const BounceGates b = bounce_gates(a.st, ii);
+        this->open = this->open && b.lit;
+        this->traced = b.traced;
+    }
+    __device__ bool wants(int s) const { return this->traced || s == 0; }
+};
+// the indirect diffuse loop: camera rays with sampleDiffuse, its depth half included (src/rlGgx.cpp:280, 313)
+template <int G>
+struct GgxBounceDiffuse : GgxNodeDiffuse<G> {
+    __device__ GgxBounceDiffuse(const GgxBounceEmitIO &a, int64_t ii) : GgxNodeDiffuse<G>(a, ii)
+    {
+        const BounceGates b = bounce_gates(a.st, ii);
+        this->open = this->open && b.cam && b.diffuse;
+    }
+};
+// rlDisney's lobes behind shouldTraceDiffuse / shouldTraceGlossy (src/rlDisney.cpp:75-83, 713-719)
+template <int G, bool SPEC>
+struct DisneyBounceLobe : DisneyLobe<G, SPEC, kNodeStream + (SPEC ? 2 : 0)> {
+    static constexpr bool kGated = true;
+    bool open;
+    __device__ DisneyBounceLobe(const DisneyBounceEmitIO &a, int64_t ii) : DisneyLobe<G, SPEC, kNodeStream + (SPEC ? 2 : 0)>(a, ii)
+    {
+        const BounceGates b = bounce_gates(a.st, ii);
+        open = SPEC ? b.trace_glossy : b.trace_diffuse;
+    }
+};
+
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_bounce_glossy_emit_kernel(GgxBounceEmitIO a)
+{
+    emit_points<G, GgxBounceGlossy<G>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_bounce_refract_emit_kernel(GgxBounceEmitIO a)
+{
+    emit_points<G, GgxBounceRefract<G>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_bounce_diffuse_emit_kernel(GgxBounceEmitIO a)
+{
+    emit_points<G, GgxBounceDiffuse<G>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void disney_bounce_diffuse_emit_kernel(DisneyBounceEmitIO a)
+{
+    emit_points<G, DisneyBounceLobe<G, false>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void disney_bounce_specular_emit_kernel(DisneyBounceEmitIO a)
+{
+    emit_points<G, DisneyBounceLobe<G, true>>(a);
 }

@@ -142,7 +142,7 @@ __global__ RLS_INT_ATTR void sss_hits_emit_kernel(HitEmitIO a)
         fr.N = N; fr.U = T; fr.V = cross(N, T);
         const OrenNayar on = oren_nayar_make(N, 0.0f);           // AiOrenNayarMISCreateData(sg, 0.0f), :443
         const uint64_t index = a.first + (uint64_t)e;
-        ShadowStage<G, HitEmitIO, SEGS> st = { a, i, live, sub, 0 };
+        ShadowStage<G, HitEmitIO, SEGS> st = { a, i, live, sub, 0, 0 };
         for (int l = 0; l < a.nl; l++) {
             const LightRegs lt = light_regs(a.lights[l], P);
             const LightCone &cone = lt.cone;

@@ -11,72 +11,49 @@
 // ggx_shade_kernel / disney_shade_kernel (csrc/shade.hip) line by line, with the traced sum S where they have
 // (sum x inv) x env.  No per-queue sum goes to memory.  LDS: 25.1 KB a workgroup, as shadow_resolve_kernel: six workgroups
 // (24 waves) a CU; the walks' LDS access patterns are the two existing kernels'.
+// STATE (rls_trace_ggx_bounce_resolve): the same walks; per point the ray-depth switches of shader_evaluate (bounce_gates) shut
+// a direct sum (o_D / o_S = +0), pick the refraction queue's factor (1 / spp on the traced branch, 1 on the one-ray branch)
+// and, off a camera ray, leave the indirect AOVs 0 and out without them (src/rlGgx.cpp:280, 292, 307-323; src/rlGgx.h:210-222).
+// A shadow ray's point is +0 everywhere.
 __global__ __launch_bounds__(rlsh::kBlock) void ggx_node_resolve_kernel(GgxNodeResolveIO a)
 {
-    __shared__ float prod[6][kShadowTile];
-    __shared__ uint8_t kinds[kShadowTile];
-    __shared__ float rad[RLS_MAX_LIGHTS][3];
-    stage_radiance(rad, a.s);
-    for (int64_t p0 = (int64_t)blockIdx.x * rlsh::kBlock; p0 < a.n; p0 += (int64_t)gridDim.x * rlsh::kBlock) {
-        const int64_t i = p0 + threadIdx.x;
-        float oS[3] = { 0.0f, 0.0f, 0.0f }, oD[3] = { 0.0f, 0.0f, 0.0f }, sG[3], sT[3], sD[3];
-        if (a.s.nl > 0) shadow_sums<1>(prod, kinds, rad, a.s, p0, oS, oD);
-        ray_sums_about_reference<3>(prod, a.glossy, p0, a.n, a.inv, sG);
-        ray_sums_about_reference<1>(prod, a.refract, p0, a.n, a.traced ? a.inv : 1.0f, sT);      // (untraced: no "x inv")
-        ray_sums_about_reference<1>(prod, a.diffuse, p0, a.n, a.inv, sD);
-        if (i < a.n) {
-            const GgxTail t = ggx_tail(a.s.materials, a.s.sh, i, true);
-            float kr, kg, kb;
-            ldrgb(a.KsColor, pindex(a.s.materials, i), kr, kg, kb);
-            float dD[3], dS[3], tx[3] = { 0.0f, 0.0f, 0.0f }, iD[3] = { 0.0f, 0.0f, 0.0f }, iS[3] = { 0.0f, 0.0f, 0.0f };
-#pragma unroll
-            for (int c = 0; c < 3; c++) { dD[c] = oD[c] * t.d[c]; dS[c] = oS[c] * t.ks; }          // :304-305
-            if (!color_is_small(t.t[0], t.t[1], t.t[2])) {                                         // :307-309
-#pragma unroll
-                for (int c = 0; c < 3; c++) tx[c] = sT[c] * t.t[c];
-            }
-            if (!color_is_small(t.d[0], t.d[1], t.d[2])) {                                         // sampleDiffuse, :315-319
-#pragma unroll
-                for (int c = 0; c < 3; c++) iD[c] = t.d[c] * sD[c];
-            }
-            if (!color_is_small(kr, kg, kb)) {                                                     // :321
-#pragma unroll
-                for (int c = 0; c < 3; c++) iS[c] = sG[c] * t.ks;
-            }
-            strgb(a.s.dd, i, dD[0], dD[1], dD[2]);
-            strgb(a.s.ds, i, dS[0], dS[1], dS[2]);
-            strgb(a.refract.out, i, tx[0], tx[1], tx[2]);
-            strgb(a.diffuse.out, i, iD[0], iD[1], iD[2]);
-            strgb(a.glossy.out, i, iS[0], iS[1], iS[2]);
-            // result = diffuse + specular + transmission (:311); result += indirectDiffuse + indirectGlossy (:323)
-            if (a.out.r) strgb(a.out, i, ((dD[0] + dS[0]) + tx[0]) + (iD[0] + iS[0]), ((dD[1] + dS[1]) + tx[1]) + (iD[1] + iS[1]),
-                               ((dD[2] + dS[2]) + tx[2]) + (iD[2] + iS[2]));
-        }
-    }
+    constexpr bool STATE = false;
+#include "rls_trace_body_ggx_node_resolve.hpp"
+}
+__global__ __launch_bounds__(rlsh::kBlock) void ggx_bounce_resolve_kernel(GgxNodeResolveIO a)
+{
+    constexpr bool STATE = true;
+#include "rls_trace_body_ggx_node_resolve.hpp"
 }
 
+// STATE (rls_trace_disney_bounce_resolve): on a diffuse or glossy ray the direct sums x indirectDiffuseScale /
+// indirectSpecularScale, each product rounded before the sum that follows (src/rlDisney.cpp:706-711); off a camera ray the
+// indirect AOVs are 0 and out is without them (:713-725) -- the queues' own gates (shouldTraceDiffuse / shouldTraceGlossy) are
+// the emit's: a lobe without rays sums to 0.  A shadow ray's point is +0 everywhere.
 __global__ __launch_bounds__(rlsh::kBlock) void disney_node_resolve_kernel(DisneyNodeResolveIO a)
 {
-    __shared__ float prod[6][kShadowTile];
-    __shared__ uint8_t kinds[kShadowTile];
-    __shared__ float rad[RLS_MAX_LIGHTS][3];
-    stage_radiance(rad, a.s);
-    for (int64_t p0 = (int64_t)blockIdx.x * rlsh::kBlock; p0 < a.n; p0 += (int64_t)gridDim.x * rlsh::kBlock) {
-        const int64_t i = p0 + threadIdx.x;
-        float dS[3] = { 0.0f, 0.0f, 0.0f }, dD[3] = { 0.0f, 0.0f, 0.0f }, sD[3], sS[3];
-        if (a.s.nl > 0) shadow_sums<3>(prod, kinds, rad, a.s, p0, dS, dD);
-        ray_sums_about_reference<3>(prod, a.diffuse, p0, a.n, a.inv, sD);
-        ray_sums_about_reference<3>(prod, a.specular, p0, a.n, a.inv, sS);
-        if (i < a.n) {
-            const float (&iD)[3] = sD, (&iS)[3] = sS;
-            strgb(a.s.dd, i, dD[0], dD[1], dD[2]);
-            strgb(a.s.ds, i, dS[0], dS[1], dS[2]);
-            strgb(a.diffuse.out, i, iD[0], iD[1], iD[2]);
-            strgb(a.specular.out, i, iS[0], iS[1], iS[2]);
-            // result = diffuse + specular (src/rlDisney.cpp:712); result += indirectDiffuse + indirectGlossy (:722)
-            if (a.out.r) strgb(a.out, i, (dD[0] + dS[0]) + (iD[0] + iS[0]), (dD[1] + dS[1]) + (iD[1] + iS[1]),
-                               (dD[2] + dS[2]) + (iD[2] + iS[2]));
-        }
+    constexpr bool STATE = false;
+#include "rls_trace_body_disney_node_resolve.hpp"
+}
+__global__ __launch_bounds__(rlsh::kBlock) void disney_bounce_resolve_kernel(DisneyNodeResolveIO a)
+{
+    constexpr bool STATE = true;
+#include "rls_trace_body_disney_node_resolve.hpp"
+}
+
+// rls_trace_ray_state_advance: the state of the hits of a queue's rays.  Ray k leaves point[k] as a ray of `ray_type`: sg->Rr
+// and the counter of its type grow by one (saturating at 255, the counters' range), the other counters are the parent's.
+__global__ __launch_bounds__(rlsh::kBlock) void state_advance_kernel(StateAdvanceIO a)
+{
+    for (int64_t k = (int64_t)blockIdx.x * rlsh::kBlock + threadIdx.x; k < a.rays; k += (int64_t)gridDim.x * rlsh::kBlock) {
+        const int64_t p = a.point[k];
+        const int rt = a.ray_type;
+        auto up = [](int v, bool grow) { return (uint8_t)(grow && v < 255 ? v + 1 : v); };
+        a.child[0][k] = (uint8_t)rt;
+        a.child[1][k] = up(a.parent.Rr[p], true);
+        a.child[2][k] = up(a.parent.Rr_diff[p], (rt & RLS_RT_DIFFUSE) != 0);
+        a.child[3][k] = up(a.parent.Rr_gloss[p], (rt & RLS_RT_GLOSSY) != 0);
+        a.child[4][k] = up(a.parent.Rr_refr[p], (rt & RLS_RT_REFRACTED) != 0);
     }
 }
 

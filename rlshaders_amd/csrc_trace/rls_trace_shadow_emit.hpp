@@ -16,7 +16,10 @@
 // The two kernels stay written out: with their common walk in a force-inlined shadow_emit_points<G, Node> (the argument
 // struct by reference or by value, the segments as members of a node policy) rlDisney's kernel spilled 8 more vector
 // registers at every G (scratch 56 -> 96 B at G = 1) and ran 0.8 % slower; rlDisney's body alone behind a force-inlined
-// function taking the struct by reference went from 56 to 144 B.
+// function taking the struct by reference went from 56 to 144 B (measured again with the bounce calls: 56 -> 144 B, and
+// rlGgx's 0 -> 32 B).  So the state-gated instantiations of the bounce calls (ggx_bounce_direct_emit_kernel,
+// disney_bounce_direct_emit_kernel) share their parent's lines as an INCLUDED body, rls_trace_body_*_direct_emit.hpp, with
+// `if constexpr (STATE)` around the few lines that differ: the parents compile to the code they had.
 
 // rlGgx's lobe for RLS_HIT_SAMPLE_EVAL: the VNDF sampler, the reflected direction (streams +2/3)
 struct GgxHitLobe {
@@ -32,22 +35,25 @@ struct GgxHitLobe {
     RLS_DEV void run(SlowLds<K> &slow, int qn, float conePdf, int mode) const { ggx_hit_eval_run<K>(slow, qn, g, conePdf, mode); }
 };
 
-// One point's place in the staging and its running ray count; SEGS: the segments of a light
-template <int G, class IO, int SEGS = kShadowSegments>
+// One point's place in the staging and its running ray count; SEGS: the segments of a light.  STATE (the bounce calls): `lobes`,
+// the RLS_SHADOW_SPECULAR / _DIFFUSE bits of the lobes the point's ray state leaves; a term of another lobe is not the ray's.
+template <int G, class IO, int SEGS = kShadowSegments, bool STATE = false>
 struct ShadowStage {
     const IO &a;
     int64_t i;
     bool live;
     int sub, run;
+    int lobes;
     // sample s of segment `seg` of light l, in every lane of the wavefront (group_rank ballots): dir and the two lobes' terms
     // (zeros where the ray carries none); NWD: the planes of the diffuse term
     template <int NWD>
     __device__ __forceinline__ void put(const LightCone &cone, int l, int seg, int s, bool ok, V3 dir, const float (&ws)[3],
                                         const float (&wd)[3])
     {
-        const bool bs = !(ws[0] == 0.0f && ws[1] == 0.0f && ws[2] == 0.0f);
+        bool bs = !(ws[0] == 0.0f && ws[1] == 0.0f && ws[2] == 0.0f);
         bool bd = !(wd[0] == 0.0f);
         if (NWD == 3) bd = !(wd[0] == 0.0f && wd[1] == 0.0f && wd[2] == 0.0f);
+        if constexpr (STATE) { bs = bs && (lobes & RLS_SHADOW_SPECULAR); bd = bd && (lobes & RLS_SHADOW_DIFFUSE); }
         const bool keep = ok && (bs || bd);
         const int rank = group_rank<G>(keep, sub, run);
         store<NWD>(cone, l, seg, s, ok, keep, rank, bs, bd, dir, ws, wd);
@@ -107,175 +113,36 @@ struct ShadowStage {
     }
 };
 
+// STATE, the bounce call's instantiation (rls_trace_ggx_bounce_emit): the loop runs whole -- sampleDiffuse stays the colour's
+// test, so every weight is the parent's -- and the point's ray state decides which lobes' terms its rays carry (ShadowStage):
+// the diffuse term and segment 1 exist iff Rr_diff <= GI_diffuse_depth, the specular term and segment 2 iff Rr_gloss <=
+// GI_glossy_depth (src/rlGgx.cpp:280, 292), neither at a shadow ray's point.
 template <int G, int FAST_MATH = RLS_FAST>
 __global__ RLS_INT_ATTR void ggx_direct_emit_kernel(ShadowEmitIO<rls_ggx_closure, rls_ggx_shader> a)
 {
-    constexpr int K = RLS_SPEC_BLOCK;
-    __shared__ uint32_t tab[2][kMaxSpp];
-    __shared__ SlowLds<K> slow;
-    stage_libm_tables();
-    stage_table(tab, a.spp);
-    RLS_POINT_WALK(G, a.n)
-    const int spp = a.spp, tid = (int)threadIdx.x;
-    const float zero[3] = { 0.0f, 0.0f, 0.0f };
-    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
-        const bool live = i < a.n;
-        const int64_t ii = live ? i : a.n - 1;
-        RLS_GGX_LOAD(g, a.c, ii)
-        const VndfView w = vndf_view(g.view, g.fr, g.ax, g.ay);
-        const OrenNayar on = oren_nayar_make(N, ldp(a.sh.diffuseRoughness, pk));
-        const float kd = ldp(a.sh.Kd, pk);
-        float dr, dg, db;
-        ldrgb(a.sh.KdColor, pk, dr, dg, db);
-        const bool sampleDiffuse = !color_is_small(dr * kd, dg * kd, db * kd);      // src/rlGgx.cpp:279-281
-        const V3 P = ld3(a.P, ii);
-        const uint64_t index = a.first + (uint64_t)ii;
-        ShadowStage<G, decltype(a)> st = { a, i, live, sub, 0 };
-        for (int l = 0; l < a.nl; l++) {
-            const LightRegs lt = light_regs(a.lights[l], P);
-            const LightCone &cone = lt.cone;
-            const int mode = lt.mode;
-            uint32_t scr[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++) scr[k] = hash_u32(a.seed, index, kScrambleStream + 6 * l + k);
-
-            // segment 0: one light sample, both lobes
-            if (mode == RLS_MIS_BSDF_ONLY) st.skip(l, 0);
-            for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {
-                RLS_LIGHT_SAMPLE_PUSH(slow, qn, tab, spp, s0, cone, N, scr[0], scr[1],
-                                      slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;)
-                ggx_light_eval_run<K>(slow, qn, g, on, cone.pdf, sampleDiffuse, mode);
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f }, ud[3] = { 0.0f, 0.0f, 0.0f };
-                    if (eval_pop<K>(slow, k, t)) {
-                        us[0] = t[0]; us[1] = t[1]; us[2] = t[2];
-                        if (sampleDiffuse) ud[0] = t[3];
-                    }
-                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
-                    st.template put<1>(cone, l, 0, s0 + k * G, s0 + k * G < spp, L, us, ud);
-                }
-            }
-            // segment 1: one BSDF sample of the Oren-Nayar lobe (streams +4/5), where it hits the light
-            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 1);
-            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += G) {
-                const int s = s0;
-                float ud[3] = { 0.0f, 0.0f, 0.0f };
-                V3 Ld = mk(0.0f, 0.0f, 0.0f);
-                if (s < spp && cone.valid && sampleDiffuse) {
-                    const float rx = bits_u01(tab[0][s] ^ scr[4]), ry = bits_u01(tab[1][s] ^ scr[5]);
-                    Ld = cosine_hemisphere(g.fr, rx, ry);
-                    const float pd = oren_nayar_pdf(on, Ld);
-                    if (pd > 0.0f && cone_hit(cone, Ld)) {
-                        const float fd = oren_nayar_brdf(on, wo, Ld);
-                        const float wd = mode == RLS_MIS_BSDF_ONLY ? 1.0f : power_heuristic(pd, cone.pdf);
-                        ud[0] = R_DIV(fd * wd, pd);
-                    }
-                }
-                st.template put<1>(cone, l, 1, s, s < spp, Ld, zero, ud);
-            }
-            // segment 2: one BSDF sample of the GGX lobe (streams +2/3); the few that hit the light are evaluated packed
-            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 2);
-            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
-                RLS_HIT_SAMPLE_EVAL(slow, (GgxHitLobe{ g, w, N }), tab, spp, s0, cone, scr[2], scr[3], mode)
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const int s = s0 + k * G;
-                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f };
-                    if (s < spp && cone.valid && eval_pop<K>(slow, k, t)) { us[0] = t[0]; us[1] = t[1]; us[2] = t[2]; }
-                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
-                    st.template put<1>(cone, l, 2, s, s < spp, L, us, zero);
-                }
-            }
-        }
-        if (live && sub == 0) a.count[i] = st.run;
-    }
+    constexpr bool STATE = false;
+#include "rls_trace_body_ggx_direct_emit.hpp"
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void ggx_bounce_direct_emit_kernel(ShadowEmitIO<rls_ggx_closure, rls_ggx_shader> a)
+{
+    constexpr bool STATE = true;
+#include "rls_trace_body_ggx_direct_emit.hpp"
 }
 
+// STATE (rls_trace_disney_bounce_emit): rlDisney's light loop is whole at every depth (src/rlDisney.cpp:695-705); a shadow
+// ray's point has no rays.
 template <int G, int FAST_MATH = RLS_FAST>
 __global__ RLS_DISNEY_LIGHT_ATTR void disney_direct_emit_kernel(ShadowEmitIO<rls_disney_closure, NoShader> a)
 {
-    constexpr int K = RLS_SPEC_BLOCK;
-    __shared__ uint32_t tab[2][kMaxSpp];
-    __shared__ SlowLds<K> slow;
-    stage_libm_tables();
-    stage_table(tab, a.spp);
-    RLS_POINT_WALK(G, a.n)
-    const int spp = a.spp, tid = (int)threadIdx.x;
-    const float zero[3] = { 0.0f, 0.0f, 0.0f };
-    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
-        const bool live = i < a.n;
-        const int64_t ii = live ? i : a.n - 1;
-        RLS_DISNEY_LOAD(d, a.c, ii)
-        const VndfView w = vndf_view(d.view, d.fr, d.ax, d.ay);
-        const V3 N = d.fr.N, P = ld3(a.P, ii);
-        const uint64_t index = a.first + (uint64_t)ii;
-        ShadowStage<G, decltype(a)> st = { a, i, live, sub, 0 };
-        for (int l = 0; l < a.nl; l++) {
-            const LightRegs lt = light_regs(a.lights[l], P);
-            const LightCone &cone = lt.cone;
-            const int mode = lt.mode;
-            uint32_t scr[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++) scr[k] = hash_u32(a.seed, index, kScrambleStream + 6 * l + k);
-
-            // segment 0: one light sample, both lobes (the specular lobe's terms come back through st[0..2]: the direction
-            // is drawn again in the second sweep)
-            if (mode == RLS_MIS_BSDF_ONLY) st.skip(l, 0);
-            for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {
-                RLS_LIGHT_SAMPLE_PUSH(slow, qn, tab, spp, s0, cone, N, scr[0], scr[1], )
-                disney_light_eval_run<K>(slow, qn, d, cone.pdf, mode);
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const int s = s0 + k * G;
-                    const int sc = s < spp ? s : 0;
-                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f }, ud[3] = { 0.0f, 0.0f, 0.0f };
-                    V3 L = mk(0.0f, 0.0f, 0.0f);
-                    if (eval_pop<K>(slow, k, t)) {
-                        ud[0] = t[0]; ud[1] = t[1]; ud[2] = t[2];
-                        us[0] = slow.st[0][k][tid]; us[1] = slow.st[1][k][tid]; us[2] = slow.st[2][k][tid];
-                        L = cone_sample(cone, bits_u01(tab[0][sc] ^ scr[0]), bits_u01(tab[1][sc] ^ scr[1]));
-                    }
-                    st.template put<3>(cone, l, 0, s, s < spp, L, us, ud);
-                }
-            }
-            // segment 1: the diffuse lobe's BSDF samples (cosine-weighted, streams +2/3) that hit the light
-            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 1);
-            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
-                int qn = 0;
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    const int s = s0 + k * G;
-                    const int sc = s < spp ? s : 0;
-                    const V3 L = cosine_hemisphere(d.fr, bits_u01(tab[0][sc] ^ scr[2]), bits_u01(tab[1][sc] ^ scr[3]));
-                    eval_push<K>(slow, k, qn, s < spp && cone.valid && cone_hit(cone, L), L);
-                    slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;
-                }
-                disney_hit_eval_run<K, true>(slow, qn, d, cone.pdf, mode);
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    float t[4], ud[3] = { 0.0f, 0.0f, 0.0f };
-                    if (eval_pop<K>(slow, k, t) && t[3] != 0.0f) { ud[0] = t[0]; ud[1] = t[1]; ud[2] = t[2]; }
-                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
-                    st.template put<3>(cone, l, 1, s0 + k * G, s0 + k * G < spp, L, zero, ud);
-                }
-            }
-            // segment 2: the specular lobe's BSDF samples (streams +4/5): the sampler's rare branches packed, then the
-            // reflected directions that hit the light
-            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 2);
-            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += K * G) {
-                RLS_HIT_SAMPLE_EVAL(slow, (DisneySpecHitLobe{ d, w }), tab, spp, s0, cone, scr[4], scr[5], mode)
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    float t[4], us[3] = { 0.0f, 0.0f, 0.0f };
-                    if (eval_pop<K>(slow, k, t) && t[3] != 0.0f) { us[0] = t[0]; us[1] = t[1]; us[2] = t[2]; }
-                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
-                    st.template put<3>(cone, l, 2, s0 + k * G, s0 + k * G < spp, L, us, zero);
-                }
-            }
-        }
-        if (live && sub == 0) a.count[i] = st.run;
-    }
+    constexpr bool STATE = false;
+#include "rls_trace_body_disney_direct_emit.hpp"
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_DISNEY_LIGHT_ATTR void disney_bounce_direct_emit_kernel(ShadowEmitIO<rls_disney_closure, NoShader> a)
+{
+    constexpr bool STATE = true;
+#include "rls_trace_body_disney_direct_emit.hpp"
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -342,7 +209,7 @@ __global__ RLS_INT_ATTR void skin_shadow_emit_kernel(SkinShadowEmitIO a)
         const Ggx &g = sl.g;
         const V3 N = sl.N, P = ld3(a.P, ii);
         const uint64_t index = a.first + (uint64_t)ii;
-        ShadowStage<G, SkinShadowEmitIO, kSkinShadowSegments> st = { a, i, live, sub, 0 };
+        ShadowStage<G, SkinShadowEmitIO, kSkinShadowSegments> st = { a, i, live, sub, 0, 0 };
         float f = 0.0f, cnt = 0.0f;
         for (int l = 0; l < a.nl; l++) {
             const LightRegs lt = light_regs(a.lights[l], P);

@@ -9,6 +9,10 @@
 // (run_shadow_emit) share the staging's carve (staging) and the scan (scan_counts); the probe emits write a dense queue.
 // Resolve: one launch per verb; a whole node's walks every queue of the node and composes the AOVs in registers.
 //
+// rlGgx's and rlDisney's whole nodes have a second pair of verbs for the hits of secondary rays (rls_trace_*_bounce_*): the
+// same checks and steps (ggx_node_emit, ggx_node_resolve, disney_node_emit, disney_node_resolve) with the per-point ray state
+// and the kernels that read it.
+//
 // Built twice like the closure units of librlshaders_amd.so (rlshaders_amd/build.py, build_trace_library): RLS_FAST=0
 // carries the C ABI, the EXACT emit kernels and the mode-free scan / compact / resolve kernels; RLS_FAST=1 the FAST emit
 // kernels behind hidden symbols.
@@ -90,6 +94,13 @@ static rls_status launch_sss_hits_gate(rls_context *ctx, int, const HitGateIO &i
 }
 RLS_FLAVOURS(sss_hits_gate, HitGateIO)
 RLS_TRACE_G_VERB(sss_hits_emit, HitEmitIO)
+RLS_TRACE_G_VERB(ggx_bounce_direct_emit, GgxShadowEmitIO)
+RLS_TRACE_G_VERB(ggx_bounce_glossy_emit, GgxBounceEmitIO)
+RLS_TRACE_G_VERB(ggx_bounce_refract_emit, GgxBounceEmitIO)
+RLS_TRACE_G_VERB(ggx_bounce_diffuse_emit, GgxBounceEmitIO)
+RLS_TRACE_G_VERB(disney_bounce_direct_emit, DisneyShadowEmitIO)
+RLS_TRACE_G_VERB(disney_bounce_diffuse_emit, DisneyBounceEmitIO)
+RLS_TRACE_G_VERB(disney_bounce_specular_emit, DisneyBounceEmitIO)
 
 #if !RLS_FAST
 
@@ -655,27 +666,42 @@ rls_status rls_trace_disney_direct_resolve(rls_context *ctx, int64_t n, const rl
                           direct_specular, __func__);
 }
 
-rls_status rls_trace_ggx_shade_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
-                                    rls_cvec3 P, const rls_sphere_light *lights, int n_lights, int traced, int spp_n,
-                                    uint32_t seed, uint64_t first_index, const rls_ggx_node_queues *q)
+} // extern "C"
+
+namespace {
+
+// ---- the whole nodes of rlGgx and rlDisney: the node calls (st == NULL: a camera ray at depth 0 at every point) and the bounce
+// calls (st: the per-point ray state) are one set of checks and steps each; only the kernels differ ----------------------------
+// a bounce call's state, checked and copied into st; planes: n > 0
+rls_status check_state(const char *fn, const rls_ray_state *state, const rls_gi_depths *depths, bool planes, BounceState &st)
 {
-    const char *fn = __func__;
-    if (rls_status s = check_node(fn, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
-    RLS_REQUIRE(q->glossy != nullptr && q->refract != nullptr && q->diffuse != nullptr,
-                "queues.glossy, queues.refract or queues.diffuse is NULL");
+    RLS_REQUIRE_IN(fn, state != nullptr, "state is NULL");
+    RLS_REQUIRE_IN(fn, depths != nullptr, "depths is NULL");
+    RLS_REQUIRE_IN(fn, !planes || (state->ray_type && state->Rr && state->Rr_diff && state->Rr_gloss && state->Rr_refr),
+                   "state.ray_type, state.Rr, state.Rr_diff, state.Rr_gloss or state.Rr_refr plane is NULL");
+    st.s = *state; st.d = *depths;
+    return RLS_OK;
+}
+
+rls_status ggx_node_emit(const char *fn, rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                         rls_cvec3 P, const rls_sphere_light *lights, int n_lights, int traced, int spp_n, uint32_t seed,
+                         uint64_t first_index, const BounceState *st, const rls_ggx_node_queues *q)
+{
+    RLS_REQUIRE_IN(fn, q->glossy != nullptr && q->refract != nullptr && q->diffuse != nullptr,
+                   "queues.glossy, queues.refract or queues.diffuse is NULL");
     const rls_ray_queue *const rq[3] = { q->glossy, q->refract, q->diffuse };
     const int nw[3] = { 3, 1, 1 }, spp = spp_n * spp_n;
-    for (int k = 0; k < 3; k++) RLS_REQUIRE(rq[k]->offsets != nullptr, "queue.offsets is NULL");
-    GgxShadowEmitIO sio = {};                                    // the light loop: rls_trace_ggx_direct_emit's queue
+    for (int k = 0; k < 3; k++) RLS_REQUIRE_IN(fn, rq[k]->offsets != nullptr, "queue.offsets is NULL");
+    GgxShadowEmitIO sio = {};                              // the light loop: rls_trace_ggx_direct_emit's queue
     if (n > 0) {
-        RLS_REQUIRE(c != nullptr && sh != nullptr, "closure or shader is NULL");
+        RLS_REQUIRE_IN(fn, c != nullptr && sh != nullptr, "closure or shader is NULL");
         if (rls_status s = rlsh::check_closure(fn, c, &P, sh, true)) return s;
         for (int k = 0; k < 3; k++)
             if (rls_status s = check_ray_queue(fn, rq[k], nw[k], n, spp_n)) return s;
         sio.c = *c; sio.sh = *sh; sio.P = P;
     }
     if (n_lights > 0) {                                          // (with this every check has passed: what follows launches)
-        RLS_REQUIRE(q->shadow->offsets != nullptr, "queue or queue.offsets is NULL");
+        RLS_REQUIRE_IN(fn, q->shadow->offsets != nullptr, "queue or queue.offsets is NULL");
         if (n > 0)
             if (rls_status s = check_shadow_emit(fn, sio, lights, n_lights, q->shadow, 1, n, spp)) return s;
     }
@@ -686,34 +712,44 @@ rls_status rls_trace_ggx_shade_emit(rls_context *ctx, int64_t n, const rls_ggx_c
             if (rls_status s = empty_queue(ctx, rq[k]->offsets, fn)) return s;
         return RLS_OK;
     }
+    GgxBounceEmitIO io = {};
+    io.c = *c; io.sh = *sh; io.traced = traced ? 1 : 0;
+    if (st) {
+        sio.st = *st; io.st = *st;
+        if (n_lights > 0)
+            if (rls_status s = run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, q->shadow, 1, fn, dispatch_ggx_bounce_direct_emit))
+                return s;
+        if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, q->glossy, nullptr, 3, fn, dispatch_ggx_bounce_glossy_emit))
+            return s;
+        // both branches of integrateRefract in one launch at the call's spp: an untraced point's one ray is its sample 0
+        if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, q->refract, nullptr, 1, fn,
+                                        dispatch_ggx_bounce_refract_emit)) return s;
+        return run_ray_emit(ctx, n, io, spp, seed, first_index, q->diffuse, nullptr, 1, fn, dispatch_ggx_bounce_diffuse_emit);
+    }
+    GgxNodeEmitIO &pio = io;                                     // (the node call's ray emits take the struct without the state)
     if (n_lights > 0)
         if (rls_status s = run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, q->shadow, 1, fn, dispatch_ggx_direct_emit))
             return s;
-    GgxNodeEmitIO io = {};
-    io.c = *c; io.sh = *sh; io.traced = traced ? 1 : 0;
-    if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, q->glossy, nullptr, 3, fn, dispatch_ggx_node_glossy_emit))
+    if (rls_status s = run_ray_emit(ctx, n, pio, spp, seed, first_index, q->glossy, nullptr, 3, fn, dispatch_ggx_node_glossy_emit))
         return s;
     // the untraced branch is one ray a point: one sample (GgxNodeRefract)
-    if (rls_status s = run_ray_emit(ctx, n, io, traced ? spp : 1, seed, first_index, q->refract, nullptr, 1, fn,
+    if (rls_status s = run_ray_emit(ctx, n, pio, traced ? spp : 1, seed, first_index, q->refract, nullptr, 1, fn,
                                     dispatch_ggx_node_refract_emit)) return s;
-    return run_ray_emit(ctx, n, io, spp, seed, first_index, q->diffuse, nullptr, 1, fn, dispatch_ggx_node_diffuse_emit);
+    return run_ray_emit(ctx, n, pio, spp, seed, first_index, q->diffuse, nullptr, 1, fn, dispatch_ggx_node_diffuse_emit);
 }
 
-rls_status rls_trace_ggx_shade_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
-                                       const rls_sphere_light *lights, int n_lights, int traced, int spp_n,
-                                       const rls_ggx_node_queues *q, const rls_ggx_node_traced *t,
-                                       const rls_ggx_shade_out *out)
+rls_status ggx_node_resolve(const char *fn, rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                            const rls_sphere_light *lights, int n_lights, int traced, int spp_n, const BounceState *st,
+                            const rls_ggx_node_queues *q, const rls_ggx_node_traced *t, const rls_ggx_shade_out *out)
 {
-    const char *fn = __func__;
-    if (rls_status s = check_node(fn, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
-    RLS_REQUIRE(q->glossy != nullptr && q->refract != nullptr && q->diffuse != nullptr,
-                "queues.glossy, queues.refract or queues.diffuse is NULL");
-    RLS_REQUIRE(t != nullptr && out != nullptr, "traced or out is NULL");
+    RLS_REQUIRE_IN(fn, q->glossy != nullptr && q->refract != nullptr && q->diffuse != nullptr,
+                   "queues.glossy, queues.refract or queues.diffuse is NULL");
+    RLS_REQUIRE_IN(fn, t != nullptr && out != nullptr, "traced or out is NULL");
     if (n == 0) return RLS_OK;
-    RLS_REQUIRE(c != nullptr && sh != nullptr, "closure or shader is NULL");
-    RLS_REQUIRE(rlsh::ok_rgb(c->KsColor) && rlsh::ok_rgb(sh->KdColor) && rlsh::ok_rgb(sh->KtColor),
-                "colour planes must be all set or all NULL");
-    RLS_REQUIRE(rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    RLS_REQUIRE_IN(fn, c != nullptr && sh != nullptr, "closure or shader is NULL");
+    RLS_REQUIRE_IN(fn, rlsh::ok_rgb(c->KsColor) && rlsh::ok_rgb(sh->KdColor) && rlsh::ok_rgb(sh->KtColor),
+                   "colour planes must be all set or all NULL");
+    RLS_REQUIRE_IN(fn, rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
     if (rls_status s = check_aov_planes(fn, { out->direct_diffuse, out->direct_specular, out->refraction, out->indirect_diffuse,
                                               out->indirect_specular }, out->out)) return s;
     GgxNodeResolveIO io = {};
@@ -727,6 +763,11 @@ rls_status rls_trace_ggx_shade_resolve(rls_context *ctx, int64_t n, const rls_gg
         return s;
     if (rls_status s = node_ray_io(fn, io.diffuse, q->diffuse, 1, n, spp_n, t->diffuse, out->indirect_diffuse, io.inv)) return s;
     io.KsColor = c->KsColor; io.out = out->out; io.traced = traced ? 1 : 0; io.n = n;
+    if (st) {
+        io.st = *st;
+        hipLaunchKernelGGL(ggx_bounce_resolve_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+        return rlsh::check_launch(fn);
+    }
     if (separate_node_resolve()) {
         if (io.s.nl > 0)
             if (rls_status s = launch_shadow_resolve(ctx, io.s, 1, fn)) return s;
@@ -740,16 +781,14 @@ rls_status rls_trace_ggx_shade_resolve(rls_context *ctx, int64_t n, const rls_gg
     return rlsh::check_launch(fn);
 }
 
-rls_status rls_trace_disney_shade_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
-                                       const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
-                                       uint64_t first_index, const rls_disney_node_queues *q)
+rls_status disney_node_emit(const char *fn, rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
+                            const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed, uint64_t first_index,
+                            const BounceState *st, const rls_disney_node_queues *q)
 {
-    const char *fn = __func__;
-    if (rls_status s = check_node(fn, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
-    RLS_REQUIRE(q->diffuse != nullptr && q->specular != nullptr, "queues.diffuse or queues.specular is NULL");
-    RLS_REQUIRE(q->diffuse->offsets != nullptr && q->specular->offsets != nullptr, "queue.offsets is NULL");
+    RLS_REQUIRE_IN(fn, q->diffuse != nullptr && q->specular != nullptr, "queues.diffuse or queues.specular is NULL");
+    RLS_REQUIRE_IN(fn, q->diffuse->offsets != nullptr && q->specular->offsets != nullptr, "queue.offsets is NULL");
     const int spp = spp_n * spp_n;
-    DisneyShadowEmitIO sio = {};                                 // the light loop: rls_trace_disney_direct_emit's queue
+    DisneyShadowEmitIO sio = {};                           // the light loop: rls_trace_disney_direct_emit's queue
     if (n > 0) {
         if (rls_status s = rlsh::check_closure(fn, c, &P)) return s;
         if (rls_status s = check_ray_queue(fn, q->diffuse, 3, n, spp_n)) return s;
@@ -757,7 +796,7 @@ rls_status rls_trace_disney_shade_emit(rls_context *ctx, int64_t n, const rls_di
         sio.c = *c; sio.P = P;
     }
     if (n_lights > 0) {                                          // (with this every check has passed: what follows launches)
-        RLS_REQUIRE(q->shadow->offsets != nullptr, "queue or queue.offsets is NULL");
+        RLS_REQUIRE_IN(fn, q->shadow->offsets != nullptr, "queue or queue.offsets is NULL");
         if (n > 0)
             if (rls_status s = check_shadow_emit(fn, sio, lights, n_lights, q->shadow, 3, n, spp)) return s;
     }
@@ -767,25 +806,39 @@ rls_status rls_trace_disney_shade_emit(rls_context *ctx, int64_t n, const rls_di
         if (rls_status s = empty_queue(ctx, q->diffuse->offsets, fn)) return s;
         return empty_queue(ctx, q->specular->offsets, fn);
     }
+    DisneyBounceEmitIO io = {};
+    io.c = *c;
+    if (st) {
+        sio.st = *st; io.st = *st;
+        if (n_lights > 0)
+            if (rls_status s = run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, q->shadow, 3, fn,
+                                               dispatch_disney_bounce_direct_emit)) return s;
+        if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, q->diffuse, nullptr, 3, fn,
+                                        dispatch_disney_bounce_diffuse_emit)) return s;
+        return run_ray_emit(ctx, n, io, spp, seed, first_index, q->specular, nullptr, 3, fn, dispatch_disney_bounce_specular_emit);
+    }
+    EmitIO<rls_disney_closure> &pio = io;
     if (n_lights > 0)
         if (rls_status s = run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, q->shadow, 3, fn, dispatch_disney_direct_emit))
             return s;
-    EmitIO<rls_disney_closure> io = {};
-    io.c = *c;
-    if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, q->diffuse, nullptr, 3, fn, dispatch_disney_node_diffuse_emit))
+    if (rls_status s = run_ray_emit(ctx, n, pio, spp, seed, first_index, q->diffuse, nullptr, 3, fn, dispatch_disney_node_diffuse_emit))
         return s;
-    return run_ray_emit(ctx, n, io, spp, seed, first_index, q->specular, nullptr, 3, fn, dispatch_disney_node_specular_emit);
+    return run_ray_emit(ctx, n, pio, spp, seed, first_index, q->specular, nullptr, 3, fn, dispatch_disney_node_specular_emit);
 }
 
-rls_status rls_trace_disney_shade_resolve(rls_context *ctx, int64_t n, const rls_sphere_light *lights, int n_lights,
-                                          int spp_n, const rls_disney_node_queues *q, const rls_disney_node_traced *t,
-                                          const rls_disney_shade_out *out)
+// sc: the bounce call's closure and scales (its materials index alone is read), checked by the caller
+rls_status disney_node_resolve(const char *fn, rls_context *ctx, int64_t n, const rls_sphere_light *lights, int n_lights,
+                               int spp_n, const BounceState *st, const rls_disney_closure *c, rls_param diffuse_scale,
+                               rls_param specular_scale, const rls_disney_node_queues *q, const rls_disney_node_traced *t,
+                               const rls_disney_shade_out *out)
 {
-    const char *fn = __func__;
-    if (rls_status s = check_node(fn, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
-    RLS_REQUIRE(q->diffuse != nullptr && q->specular != nullptr, "queues.diffuse or queues.specular is NULL");
-    RLS_REQUIRE(t != nullptr && out != nullptr, "traced or out is NULL");
+    RLS_REQUIRE_IN(fn, q->diffuse != nullptr && q->specular != nullptr, "queues.diffuse or queues.specular is NULL");
+    RLS_REQUIRE_IN(fn, t != nullptr && out != nullptr, "traced or out is NULL");
     if (n == 0) return RLS_OK;
+    if (st) {
+        RLS_REQUIRE_IN(fn, c != nullptr, "closure is NULL");
+        RLS_REQUIRE_IN(fn, rlsh::ok_materials(c->materials), "materials.id is set but materials.count is 0");
+    }
     if (rls_status s = check_aov_planes(fn, { out->direct_diffuse, out->direct_specular, out->indirect_diffuse,
                                               out->indirect_specular }, out->out)) return s;
     DisneyNodeResolveIO io = {};
@@ -796,6 +849,11 @@ rls_status rls_trace_disney_shade_resolve(rls_context *ctx, int64_t n, const rls
     if (rls_status s = node_ray_io(fn, io.specular, q->specular, 3, n, spp_n, t->specular, out->indirect_specular)) return s;
     io.out = out->out; io.n = n;
     io.inv = 1.0f / (float)(spp_n * spp_n);
+    if (st) {
+        io.st = *st; io.materials = c->materials; io.diffuse_scale = diffuse_scale; io.specular_scale = specular_scale;
+        hipLaunchKernelGGL(disney_bounce_resolve_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+        return rlsh::check_launch(fn);
+    }
     if (separate_node_resolve()) {
         if (io.s.nl > 0)
             if (rls_status s = launch_shadow_resolve(ctx, io.s, 3, fn)) return s;
@@ -806,6 +864,110 @@ rls_status rls_trace_disney_shade_resolve(rls_context *ctx, int64_t n, const rls
     }
     hipLaunchKernelGGL(disney_node_resolve_kernel, rlsh::grid_for(ctx, n), dim3(rlsh::kBlock), 0, ctx->stream, io);
     return rlsh::check_launch(fn);
+}
+
+} // namespace
+
+extern "C" {
+
+rls_status rls_trace_ggx_shade_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                    rls_cvec3 P, const rls_sphere_light *lights, int n_lights, int traced, int spp_n,
+                                    uint32_t seed, uint64_t first_index, const rls_ggx_node_queues *q)
+{
+    if (rls_status s = check_node(__func__, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    return ggx_node_emit(__func__, ctx, n, c, sh, P, lights, n_lights, traced, spp_n, seed, first_index, nullptr, q);
+}
+
+rls_status rls_trace_ggx_shade_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                       const rls_sphere_light *lights, int n_lights, int traced, int spp_n,
+                                       const rls_ggx_node_queues *q, const rls_ggx_node_traced *t,
+                                       const rls_ggx_shade_out *out)
+{
+    if (rls_status s = check_node(__func__, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    return ggx_node_resolve(__func__, ctx, n, c, sh, lights, n_lights, traced, spp_n, nullptr, q, t, out);
+}
+
+rls_status rls_trace_disney_shade_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
+                                       const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                       uint64_t first_index, const rls_disney_node_queues *q)
+{
+    if (rls_status s = check_node(__func__, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    return disney_node_emit(__func__, ctx, n, c, P, lights, n_lights, spp_n, seed, first_index, nullptr, q);
+}
+
+rls_status rls_trace_disney_shade_resolve(rls_context *ctx, int64_t n, const rls_sphere_light *lights, int n_lights,
+                                          int spp_n, const rls_disney_node_queues *q, const rls_disney_node_traced *t,
+                                          const rls_disney_shade_out *out)
+{
+    if (rls_status s = check_node(__func__, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    return disney_node_resolve(__func__, ctx, n, lights, n_lights, spp_n, nullptr, nullptr, rls_param{}, rls_param{}, q, t, out);
+}
+
+rls_status rls_trace_ggx_bounce_emit(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                     rls_cvec3 P, const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                     uint64_t first_index, const rls_ray_state *state, const rls_gi_depths *depths,
+                                     const rls_ggx_node_queues *q)
+{
+    BounceState st = {};
+    if (rls_status s = check_node(__func__, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    if (rls_status s = check_state(__func__, state, depths, n > 0, st)) return s;
+    return ggx_node_emit(__func__, ctx, n, c, sh, P, lights, n_lights, 1, spp_n, seed, first_index, &st, q);
+}
+
+rls_status rls_trace_ggx_bounce_resolve(rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
+                                        const rls_sphere_light *lights, int n_lights, int spp_n, const rls_ray_state *state,
+                                        const rls_gi_depths *depths, const rls_ggx_node_queues *q,
+                                        const rls_ggx_node_traced *t, const rls_ggx_shade_out *out)
+{
+    BounceState st = {};
+    if (rls_status s = check_node(__func__, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    if (rls_status s = check_state(__func__, state, depths, n > 0, st)) return s;
+    return ggx_node_resolve(__func__, ctx, n, c, sh, lights, n_lights, 1, spp_n, &st, q, t, out);
+}
+
+rls_status rls_trace_disney_bounce_emit(rls_context *ctx, int64_t n, const rls_disney_closure *c, rls_cvec3 P,
+                                        const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                        uint64_t first_index, const rls_ray_state *state, const rls_gi_depths *depths,
+                                        const rls_disney_node_queues *q)
+{
+    BounceState st = {};
+    if (rls_status s = check_node(__func__, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    if (rls_status s = check_state(__func__, state, depths, n > 0, st)) return s;
+    return disney_node_emit(__func__, ctx, n, c, P, lights, n_lights, spp_n, seed, first_index, &st, q);
+}
+
+rls_status rls_trace_disney_bounce_resolve(rls_context *ctx, int64_t n, const rls_disney_closure *c,
+                                           rls_param indirectDiffuseScale, rls_param indirectSpecularScale,
+                                           const rls_sphere_light *lights, int n_lights, int spp_n,
+                                           const rls_ray_state *state, const rls_gi_depths *depths,
+                                           const rls_disney_node_queues *q, const rls_disney_node_traced *t,
+                                           const rls_disney_shade_out *out)
+{
+    BounceState st = {};
+    if (rls_status s = check_node(__func__, ctx, n, spp_n, n_lights, q != nullptr, q ? &q->shadow : nullptr)) return s;
+    if (rls_status s = check_state(__func__, state, depths, n > 0, st)) return s;
+    return disney_node_resolve(__func__, ctx, n, lights, n_lights, spp_n, &st, c, indirectDiffuseScale, indirectSpecularScale, q, t,
+                               out);
+}
+
+rls_status rls_trace_ray_state_advance(rls_context *ctx, int64_t rays, const uint32_t *point, const rls_ray_state *parent,
+                                       int ray_type, const rls_ray_state *child)
+{
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE(rays >= 0, "rays < 0");
+    RLS_REQUIRE(parent != nullptr && child != nullptr, "parent or child is NULL");
+    RLS_REQUIRE(ray_type >= 0 && ray_type <= 0xFF, "ray_type is not a byte of RLS_RT_* bits");
+    if (rays == 0) return RLS_OK;
+    RLS_REQUIRE(point != nullptr, "point is NULL");
+    for (const rls_ray_state *s : { parent, child })
+        RLS_REQUIRE(s->ray_type && s->Rr && s->Rr_diff && s->Rr_gloss && s->Rr_refr,
+                    "state.ray_type, state.Rr, state.Rr_diff, state.Rr_gloss or state.Rr_refr plane is NULL");
+    StateAdvanceIO io = {};
+    io.point = point; io.parent = *parent; io.ray_type = ray_type; io.rays = rays;
+    const uint8_t *const planes[5] = { child->ray_type, child->Rr, child->Rr_diff, child->Rr_gloss, child->Rr_refr };
+    for (int k = 0; k < 5; k++) io.child[k] = const_cast<uint8_t *>(planes[k]);
+    hipLaunchKernelGGL(state_advance_kernel, rlsh::grid_for(ctx, rays), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(__func__);
 }
 
 rls_status rls_trace_skin_emit(rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,

@@ -30,10 +30,16 @@
 //     rlsb::emitNode(dev, ggx, shader, P, lights, n_lights, traced, n, spp_n, seed, nq);
 //     ... trace every queue: a visibility per shadow ray, a radiance per ray of the ray queues ...
 //     rlsb::resolveNode(dev, ggx, shader, lights, n_lights, traced, nq, visibility, Lglossy, Lrefract, Ldiffuse, aovs, &out);
+// The same nodes at the hits of secondary rays, the ray type and depth counters per point (RayState):
+//     rlsb::emitBounce(dev, ggx, shader, P, lights, n_lights, n, spp_n, seed, state.c(), depths, nq);
+//     rlsb::resolveBounce(dev, ggx, shader, lights, n_lights, state.c(), depths, nq, visibility, Lglossy, Lrefract, Ldiffuse, aovs, &out);
+//     rlsb::advanceState(dev, rays, nq.glossy().c().point, state.c(), RLS_RT_GLOSSY, child);   // the state of those rays' hits
 // Nothing here synchronises the host except RayQueue::count() and ShadowQueue::count() (they read offsets[n]).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <vector>
 
 #include "rls_batch.hpp"
 #include "rlshaders_amd_trace.h"
@@ -622,6 +628,113 @@ inline void resolveNode(const Device &d, const rls_sphere_light *lights, int n_l
     o.indirect_specular = aovs.rgb(9);
     if (out) o.out = out->rgb();
     check(rls_trace_disney_shade_resolve(d.ctx(), q.points(), lights, n_lights, q.sppN(), &q.c(), &t, &o));
+}
+
+// sg->Rt and the sg->Rr* counters of n shading points (rls_ray_state): five planes of n bytes in one device allocation, in the
+// struct's order -- ray_type, Rr, Rr_diff, Rr_gloss, Rr_refr
+class RayState {
+public:
+    RayState(const Device &d, int64_t n) : dev_(&d), n_(n)
+    {
+        void *p = nullptr;
+        check(rls_device_alloc(d.ctx(), (size_t)(5 * n > 0 ? 5 * n : 1), &p));
+        ptr_ = static_cast<uint8_t *>(p);
+    }
+    // host: 5 * n bytes, plane by plane
+    RayState(const Device &d, const std::vector<uint8_t> &host) : RayState(d, (int64_t)(host.size() / 5))
+    {
+        if (!host.empty()) check(rls_copy_to_device(d.ctx(), ptr_, host.data(), host.size()));
+    }
+    // camera rays at depth 0
+    static RayState camera(const Device &d, int64_t n)
+    {
+        std::vector<uint8_t> h((size_t)(5 * n), 0);
+        std::fill(h.begin(), h.begin() + (size_t)n, (uint8_t)RLS_RT_CAMERA);
+        return RayState(d, h);
+    }
+    ~RayState() { if (ptr_) rls_device_free(dev_->ctx(), ptr_); }
+    RayState(RayState &&o) noexcept : dev_(o.dev_), ptr_(o.ptr_), n_(o.n_) { o.ptr_ = nullptr; }
+    RayState(const RayState &) = delete;
+    RayState &operator=(const RayState &) = delete;
+
+    // the planes from point `first` on: the state of a chunk, or of the first points of a longer state
+    rls_ray_state c(int64_t first = 0) const
+    {
+        return rls_ray_state{plane(0) + first, plane(1) + first, plane(2) + first, plane(3) + first, plane(4) + first};
+    }
+    uint8_t *plane(int k) const { return ptr_ + (size_t)k * (size_t)n_; }
+    int64_t points() const { return n_; }
+    std::vector<uint8_t> download() const
+    {
+        std::vector<uint8_t> h((size_t)(5 * n_));
+        if (!h.empty()) check(rls_copy_to_host(dev_->ctx(), h.data(), ptr_, h.size()));
+        return h;
+    }
+
+private:
+    const Device *dev_;
+    uint8_t *ptr_ = nullptr;
+    int64_t n_;
+};
+
+// rlGgx / rlDisney at the hits of secondary rays (rls_trace_ggx_bounce_emit / rls_trace_disney_bounce_emit): emitNode with the
+// ray state per point and the options' GI depths in place of `traced`; state: n points' planes (RayState::c)
+inline void emitBounce(const Device &d, const rls_ggx_closure &c, const rls_ggx_shader &sh, const Planes &P,
+                       const rls_sphere_light *lights, int n_lights, int64_t n, int spp_n, uint32_t seed,
+                       const rls_ray_state &state, const rls_gi_depths &depths, GgxNodeQueues &q, uint64_t first_index = 0)
+{
+    detail::checkNodeQueues(q, n, n_lights, spp_n, "emitBounce: queues of another size or light count");
+    check(rls_trace_ggx_bounce_emit(d.ctx(), n, &c, &sh, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n,
+                                    seed, first_index, &state, &depths, &q.c()));
+}
+inline void emitBounce(const Device &d, const rls_disney_closure &c, const Planes &P, const rls_sphere_light *lights,
+                       int n_lights, int64_t n, int spp_n, uint32_t seed, const rls_ray_state &state,
+                       const rls_gi_depths &depths, DisneyNodeQueues &q, uint64_t first_index = 0)
+{
+    detail::checkNodeQueues(q, n, n_lights, spp_n, "emitBounce: queues of another size or light count");
+    check(rls_trace_disney_bounce_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n,
+                                       seed, first_index, &state, &depths, &q.c()));
+}
+
+// resolveNode under the emit's state and depths: planes as there
+inline void resolveBounce(const Device &d, const rls_ggx_closure &c, const rls_ggx_shader &sh, const rls_sphere_light *lights,
+                          int n_lights, const rls_ray_state &state, const rls_gi_depths &depths, const GgxNodeQueues &q,
+                          const Planes &visibility, const Planes &glossy, const Planes &refract, const Planes &diffuse,
+                          Planes &aovs, Planes *out = nullptr)
+{
+    detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveBounce: queues of another light count");
+    rls_ggx_node_traced t = {detail::crgb(visibility), detail::crgb(glossy), detail::crgb(refract), detail::crgb(diffuse)};
+    rls_ggx_shade_out o = {};
+    o.direct_diffuse = aovs.rgb(0); o.direct_specular = aovs.rgb(3); o.refraction = aovs.rgb(6);
+    o.indirect_diffuse = aovs.rgb(9); o.indirect_specular = aovs.rgb(12);
+    if (out) o.out = out->rgb();
+    check(rls_trace_ggx_bounce_resolve(d.ctx(), q.points(), &c, &sh, lights, n_lights, q.sppN(), &state, &depths, &q.c(), &t, &o));
+}
+// rlDisney: c as the emit took it (its materials index serves the scales), the node's indirectDiffuseScale / indirectSpecularScale
+inline void resolveBounce(const Device &d, const rls_disney_closure &c, rls_param indirectDiffuseScale,
+                          rls_param indirectSpecularScale, const rls_sphere_light *lights, int n_lights,
+                          const rls_ray_state &state, const rls_gi_depths &depths, const DisneyNodeQueues &q,
+                          const Planes &visibility, const Planes &diffuse, const Planes &specular, Planes &aovs,
+                          Planes *out = nullptr)
+{
+    detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveBounce: queues of another light count");
+    rls_disney_node_traced t = {detail::crgb(visibility), detail::crgb(diffuse), detail::crgb(specular)};
+    rls_disney_shade_out o = {};
+    o.direct_diffuse = aovs.rgb(0); o.direct_specular = aovs.rgb(3); o.indirect_diffuse = aovs.rgb(6);
+    o.indirect_specular = aovs.rgb(9);
+    if (out) o.out = out->rgb();
+    check(rls_trace_disney_bounce_resolve(d.ctx(), q.points(), &c, indirectDiffuseScale, indirectSpecularScale, lights, n_lights,
+                                          q.sppN(), &state, &depths, &q.c(), &t, &o));
+}
+
+// the state of the hits of a queue's `rays` rays (rls_trace_ray_state_advance): point: the queue's point plane; parent: the state
+// the queue was emitted under; ray_type: the RLS_RT_* bits of its rays; child: >= rays points
+inline void advanceState(const Device &d, int64_t rays, const uint32_t *point, const rls_ray_state &parent, int ray_type,
+                         RayState &child)
+{
+    if (child.points() < rays) throw Error(RLS_ERR_INVALID_ARGUMENT, "advanceState: child holds fewer points than the queue has rays");
+    const rls_ray_state cs = child.c();
+    check(rls_trace_ray_state_advance(d.ctx(), rays, point, &parent, ray_type, &cs));
 }
 
 // every ray of rlSkin's shader_evaluate as rls_skin_integrate samples it (rls_trace_skin_emit): the arguments of

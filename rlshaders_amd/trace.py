@@ -27,6 +27,10 @@ or of one rlDisney lobe, trace them with your own tracer, resolve the radiance; 
     sq = trace.skin_node_rays(skin, P, lights, 4, 7)             # SkinNodeQueues: sheen_shadow, specular_shadow, sheen_glossy,
     aov = sq.resolve(vis_a, vis_b, La, Lb, cnt, hP, hN, E)       # specular_glossy, probes -> SkinShader.integrate's dict, traced
 
+    st = trace.RayState.camera(ctx, n)                           # sg->Rt and the sg->Rr* counters per point
+    bq = trace.ggx_bounce_rays(sampler, shader, P, lights, 4, 7, st, depths=(8, 2, 2, 4))   # the node under that state
+    hits = trace.advance_state(ctx, bq.glossy, st, trace.RLS_RT_GLOSSY)                     # the state of those rays' hits
+
 ``count`` is read from the device once (it synchronises); everything else stays asynchronous on the context's stream, so
 ``glossy_rays(..., queue=q)`` / ``q.resolve(L, out=...)`` with preallocated tensors can be recorded by ``ctx.capture()``.
 """
@@ -128,6 +132,28 @@ class SkinNodeTraced_(C.Structure):
                 ("specular_glossy", capi.CRgb), ("hits", C.POINTER(ProbeHits_))]
 
 
+# rls_ray_state.ray_type: sg->Rt
+RLS_RT_CAMERA = 0x01
+RLS_RT_SHADOW = 0x02
+RLS_RT_REFLECTED = 0x04
+RLS_RT_REFRACTED = 0x08
+RLS_RT_DIFFUSE = 0x20
+RLS_RT_GLOSSY = 0x40
+
+
+class GiDepths_(C.Structure):
+    """rls_gi_depths"""
+    _fields_ = [("total", C.c_int), ("diffuse", C.c_int), ("glossy", C.c_int), ("refraction", C.c_int)]
+
+
+class RayState_(C.Structure):
+    """rls_ray_state"""
+    _fields_ = [("ray_type", C.c_void_p), ("Rr", C.c_void_p), ("Rr_diff", C.c_void_p), ("Rr_gloss", C.c_void_p),
+                ("Rr_refr", C.c_void_p)]
+
+
+_state, _depths = C.POINTER(RayState_), C.POINTER(GiDepths_)
+
 PROTOTYPES = {
     "rls_trace_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
     "rls_trace_ggx_glossy_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
@@ -164,6 +190,19 @@ PROTOTYPES = {
                                               C.c_int, C.c_uint32, C.c_uint64, C.POINTER(DisneyNodeQueues_)]),
     "rls_trace_disney_shade_resolve": (C.c_int, [_ctx, _i64, _lights, C.c_int, C.c_int, C.POINTER(DisneyNodeQueues_),
                                                  C.POINTER(DisneyNodeTraced_), C.POINTER(capi.DisneyShadeOut)]),
+    "rls_trace_ggx_bounce_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.POINTER(capi.GgxShader), capi.CVec3,
+                                            _lights, C.c_int, C.c_int, C.c_uint32, C.c_uint64, _state, _depths,
+                                            C.POINTER(GgxNodeQueues_)]),
+    "rls_trace_ggx_bounce_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.POINTER(capi.GgxShader), _lights,
+                                               C.c_int, C.c_int, _state, _depths, C.POINTER(GgxNodeQueues_),
+                                               C.POINTER(GgxNodeTraced_), C.POINTER(capi.GgxShadeOut)]),
+    "rls_trace_disney_bounce_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.DisneyClosure), capi.CVec3, _lights, C.c_int,
+                                               C.c_int, C.c_uint32, C.c_uint64, _state, _depths,
+                                               C.POINTER(DisneyNodeQueues_)]),
+    "rls_trace_disney_bounce_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.DisneyClosure), capi.Param, capi.Param, _lights,
+                                                  C.c_int, C.c_int, _state, _depths, C.POINTER(DisneyNodeQueues_),
+                                                  C.POINTER(DisneyNodeTraced_), C.POINTER(capi.DisneyShadeOut)]),
+    "rls_trace_ray_state_advance": (C.c_int, [_ctx, _i64, _vp, _state, C.c_int, _state]),
     "rls_trace_skin_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.SkinClosure), capi.CVec3, _lights, C.c_int, C.c_int, C.c_uint32,
                                       C.c_uint64, C.POINTER(SkinNodeQueues_)]),
     "rls_trace_skin_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.SkinClosure), capi.CVec3, _lights, C.c_int, C.c_int, C.c_int,
@@ -800,6 +839,8 @@ class _NodeQueues:
         self.shader = None
         self.P = None
         self.traced = True
+        self.state = None        # a bounce emit's (RayState, GiDepths_): its resolve takes them again
+        self.scales = None       # rlDisney's bounce emit: (indirectDiffuseScale, indirectSpecularScale)
 
     def _queues(self) -> dict:
         """the compacted queues by member name, in the C struct's order"""
@@ -839,7 +880,7 @@ class GgxNodeQueues(_NodeQueues):
     (3 weight planes), ``refract`` (weight [1, count], kind) and ``diffuse`` (weight [1, count]) RayQueues -- the samples
     ``GgxSampler.shade`` draws."""
     RAY_MEMBERS = (("glossy", {}), ("refract", {"refract": True}), ("diffuse", {"planes": 1}))
-    STRUCT, EMIT = GgxNodeQueues_, "rls_trace_ggx_shade_emit"
+    STRUCT, EMIT, BOUNCE_EMIT = GgxNodeQueues_, "rls_trace_ggx_shade_emit", "rls_trace_ggx_bounce_emit"
 
     def resolve(self, visibility, glossy, refract, diffuse, out=None, counts: Optional[dict] = None) -> dict:
         """What the renderer traced, [3, >= count] float32 per queue (``visibility`` is not read without lights and may be
@@ -857,6 +898,12 @@ class GgxNodeQueues(_NodeQueues):
         out, o = self._out(self.sampler, out, capi.GgxShadeOut)
         la, nl = self.lights
         q = self._struct()
+        if self.state is not None:
+            state, depths = self.state
+            check(load().rls_trace_ggx_bounce_resolve(self.ctx.handle, self.n, C.byref(self.sampler.c), C.byref(self.shader), la,
+                                                      nl, self.spp_n, C.byref(state.struct(self.n)), C.byref(depths), C.byref(q),
+                                                      C.byref(t), C.byref(o)))
+            return out
         check(load().rls_trace_ggx_shade_resolve(self.ctx.handle, self.n, C.byref(self.sampler.c), C.byref(self.shader), la, nl,
                                                  1 if self.traced else 0, self.spp_n, C.byref(q), C.byref(t), C.byref(o)))
         return out
@@ -867,7 +914,7 @@ class DisneyNodeQueues(_NodeQueues):
     ``specular`` RayQueues -- the samples ``DisneySampler.shade`` draws."""
     SHADOW_KW = {"disney": True}
     RAY_MEMBERS = (("diffuse", {"lobe": RLS_RAY_DIFFUSE}), ("specular", {"lobe": RLS_RAY_GLOSSY}))
-    STRUCT, EMIT = DisneyNodeQueues_, "rls_trace_disney_shade_emit"
+    STRUCT, EMIT, BOUNCE_EMIT = DisneyNodeQueues_, "rls_trace_disney_shade_emit", "rls_trace_disney_bounce_emit"
 
     def resolve(self, visibility, diffuse, specular, out=None, counts: Optional[dict] = None) -> dict:
         """-> the dict ``DisneySampler.shade`` returns: the four AOVs and out, [3, n] each."""
@@ -882,16 +929,26 @@ class DisneyNodeQueues(_NodeQueues):
         out, o = self._out(self.sampler, out, capi.DisneyShadeOut)
         la, nl = self.lights
         q = self._struct()
+        if self.state is not None:
+            state, depths = self.state
+            m = self.sampler.c.materials                          # a tensor scale: per material where the closure has an index
+            pn = int(m.count) if m.id else self.n
+            kd, ks = (param(v, pn, what) for v, what in zip(self.scales, ("indirectDiffuseScale", "indirectSpecularScale")))
+            check(load().rls_trace_disney_bounce_resolve(self.ctx.handle, self.n, C.byref(self.sampler.c), kd, ks, la, nl,
+                                                         self.spp_n, C.byref(state.struct(self.n)), C.byref(depths), C.byref(q),
+                                                         C.byref(t), C.byref(o)))
+            return out
         check(load().rls_trace_disney_shade_resolve(self.ctx.handle, self.n, la, nl, self.spp_n, C.byref(q), C.byref(t),
                                                     C.byref(o)))
         return out
 
 
 def _node_emit(cls, sampler, shader, P, lights, spp_n: int, seed: int, first_index: int, queues, share_scratch: bool,
-               traced: Optional[bool] = None):
+               traced: Optional[bool] = None, state=None, scales=None):
     """One node emit into a queue set of class ``cls`` (``queues``, or a new one): the C call takes the closure, the node
     parameters where the node has them (``shader``), P and the lights, ``traced`` where the node has the switch, then the
-    sampling and the queues.  The set -- and its ``shadow`` queue, which resolves by itself too -- remembers what the emit took."""
+    sampling and the queues.  The set -- and its ``shadow`` queue, which resolves by itself too -- remembers what the emit took.
+    ``state``: (RayState, depths) for the node's bounce call, which takes them after the sampling in place of ``traced``."""
     ctx, n = sampler.ctx, sampler.n
     la, nl = light_array(lights)
     q = cls(ctx, n, nl, spp_n, share_scratch) if queues is None else queues
@@ -900,8 +957,14 @@ def _node_emit(cls, sampler, shader, P, lights, spp_n: int, seed: int, first_ind
     cq = q._struct()
     closure = (C.byref(sampler.c),) if shader is None else (C.byref(sampler.c), C.byref(shader))
     switch = () if traced is None else (1 if traced else 0,)
-    check(getattr(load(), cls.EMIT)(ctx.handle, n, *closure, _points(P, n), la, nl, *switch, int(spp_n), int(seed) & 0xFFFFFFFF,
-                                    int(first_index), C.byref(cq)))
+    emit, bounce = cls.EMIT, ()
+    if state is not None:
+        state = (state[0], gi_depths(state[1]))
+        emit, switch = cls.BOUNCE_EMIT, ()
+        bounce = (C.byref(state[0].struct(n)), C.byref(state[1]))
+    check(getattr(load(), emit)(ctx.handle, n, *closure, _points(P, n), la, nl, *switch, int(spp_n), int(seed) & 0xFFFFFFFF,
+                                int(first_index), *bounce, C.byref(cq)))
+    q.state, q.scales = state, scales
     for m in (q, q.shadow):
         if m is not None:
             m.lights, m.sampler, m.shader, m.P = (la, nl), sampler, shader, P
@@ -925,6 +988,86 @@ def disney_node_rays(sampler: DisneySampler, P: torch.Tensor, lights, spp_n: int
     """Every ray of rlDisney's shader_evaluate (src/rlDisney.cpp:685-727) as ``DisneySampler.shade`` samples it: the light
     loop's shadow rays, integrateDiffuse (stream pair 24) and integrateGlossy (25)."""
     return _node_emit(DisneyNodeQueues, sampler, None, P, lights, spp_n, seed, first_index, queues, share_scratch)
+
+
+# ---------------------------------------------------------------------------------------------
+# Secondary-ray hits: the two nodes shaded under a per-point ray state (rls_trace_*_bounce_emit / _resolve)
+
+
+def gi_depths(depths) -> GiDepths_:
+    """The options' GI depths as rls_gi_depths: a GiDepths_, a mapping with the keys total / diffuse / glossy / refraction, or
+    the four values in that order."""
+    if isinstance(depths, GiDepths_):
+        return depths
+    if isinstance(depths, dict):
+        return GiDepths_(*(int(depths[k]) for k in ("total", "diffuse", "glossy", "refraction")))
+    total, diffuse, glossy, refraction = depths
+    return GiDepths_(int(total), int(diffuse), int(glossy), int(refraction))
+
+
+class RayState:
+    """sg->Rt and the sg->Rr* counters per shading point (rls_ray_state): five uint8 CUDA tensors [n] -- ``ray_type`` (RLS_RT_*
+    bits), ``Rr``, ``Rr_diff``, ``Rr_gloss``, ``Rr_refr``.  ``RayState.camera(ctx, n)``: camera rays at depth 0."""
+    PLANES = ("ray_type", "Rr", "Rr_diff", "Rr_gloss", "Rr_refr")
+
+    def __init__(self, ray_type, Rr, Rr_diff, Rr_gloss, Rr_refr):
+        self.ray_type, self.Rr, self.Rr_diff, self.Rr_gloss, self.Rr_refr = ray_type, Rr, Rr_diff, Rr_gloss, Rr_refr
+        n = int(ray_type.shape[0]) if isinstance(ray_type, torch.Tensor) and ray_type.dim() == 1 else -1
+        for name in self.PLANES:
+            t = getattr(self, name)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.shape != (n,) or \
+                    not t.is_contiguous():
+                raise TypeError(f"RayState.{name}: expected a contiguous uint8 CUDA tensor [n]")
+        self.n = n
+
+    @classmethod
+    def camera(cls, ctx, n: int) -> "RayState":
+        z = [torch.zeros(int(n), dtype=torch.uint8, device=ctx.torch_device) for _ in range(4)]
+        return cls(torch.full((int(n),), RLS_RT_CAMERA, dtype=torch.uint8, device=ctx.torch_device), *z)
+
+    @classmethod
+    def empty(cls, ctx, n: int) -> "RayState":
+        return cls(*[torch.empty(int(n), dtype=torch.uint8, device=ctx.torch_device) for _ in cls.PLANES])
+
+    def struct(self, n: int) -> RayState_:
+        if self.n < int(n):
+            raise ValueError(f"RayState: {self.n} points, the call has {n}")
+        return RayState_(*[getattr(self, name).data_ptr() if self.n > 0 else None for name in self.PLANES])
+
+
+def ggx_bounce_rays(sampler: GgxSampler, shader: "capi.GgxShader", P: torch.Tensor, lights, spp_n: int, seed: int,
+                    state: RayState, depths, first_index: int = 0, queues: Optional[GgxNodeQueues] = None,
+                    share_scratch: bool = False) -> GgxNodeQueues:
+    """``ggx_node_rays`` at the hits of secondary rays (rls_trace_ggx_bounce_emit): per point the ray-depth switches of rlGgx's
+    shader_evaluate read off ``state`` and ``depths`` (``gi_depths``) decide which lobes the shadow rays carry, which branch of
+    integrateRefract the point takes, and whether the indirect loops run (camera rays only).  The queues remember the state:
+    ``.resolve(...)`` is the bounce resolve."""
+    return _node_emit(GgxNodeQueues, sampler, shader, P, lights, spp_n, seed, first_index, queues, share_scratch,
+                      state=(state, depths))
+
+
+def disney_bounce_rays(sampler: DisneySampler, P: torch.Tensor, lights, spp_n: int, seed: int, state: RayState, depths,
+                       first_index: int = 0, queues: Optional[DisneyNodeQueues] = None, share_scratch: bool = False,
+                       indirectDiffuseScale=1.0, indirectSpecularScale=1.0) -> DisneyNodeQueues:
+    """``disney_node_rays`` at the hits of secondary rays (rls_trace_disney_bounce_emit): the indirect loops run on camera rays
+    within the depth limits; on diffuse and glossy rays the resolve scales the direct terms by the node's ``indirectDiffuseScale`` /
+    ``indirectSpecularScale`` (values, or tensors like the sampler's other parameters)."""
+    return _node_emit(DisneyNodeQueues, sampler, None, P, lights, spp_n, seed, first_index, queues, share_scratch,
+                      state=(state, depths), scales=(indirectDiffuseScale, indirectSpecularScale))
+
+
+def advance_state(ctx, queue, parent: RayState, ray_type: int, out: Optional[RayState] = None,
+                  rays: Optional[int] = None) -> RayState:
+    """The state of the hits of ``queue``'s rays (a RayQueue or ShadowQueue emitted for points in state ``parent``), which
+    leave as rays of ``ray_type`` (rls_trace_ray_state_advance): Rr and the type's counter grow by one, saturating at 255.
+    ``rays``: the queue's ray count where the caller knows it (else read from the device); ``out``: a RayState to write."""
+    rays = queue.count if rays is None else int(rays)
+    child = RayState.empty(ctx, rays) if out is None else out
+    if child.n < rays:
+        raise ValueError("advance_state: out holds fewer planes than the queue has rays")
+    check(load().rls_trace_ray_state_advance(ctx.handle, rays, queue._point.data_ptr(), C.byref(parent.struct(queue.n)),
+                                             int(ray_type), C.byref(child.struct(rays))))
+    return child
 
 
 class SkinNodeQueues(_NodeQueues):

@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast]
+    python tools/trace_bench.py [--closure ggx|disney|sss|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -33,6 +33,12 @@ light loop's share of it (the same kernels through the light-loop emit), the nod
 resolves on the same queues (the light-loop resolve plus one glossy / refraction resolve per ray queue: they write one sum
 per queue and leave the composition to the caller), and rls_ggx_shade / rls_disney_shade.  Uniform random radiance and
 visibility.  The queues share one scratch block.
+--closure ggx-bounce / disney-bounce: the node at the hits of secondary rays (trace.ggx_bounce_rays / disney_bounce_rays) on the
+ggx-node / disney-node batch, under --state: `camera` (every point a camera ray at depth 0: the node call's rays, so the
+difference to it is what the per-point switches cost), `secondary` (every point a glossy ray's hit at depth 1: no indirect
+rays) or `half` (the two alternating point by point: neighbouring lanes differ); GI depths total 8, diffuse 2, glossy 2,
+refraction 4.  The node call's emit and resolve are timed in the SAME process, before and after the bounce call's: the
+difference between the node call's two figures is the spread to read the bounce call's against.
 --closure skin-node: the rlSkin node (trace.skin_node_rays) with per-point parameters on the plane z = 0 (shading points in
 [0,4) x [0,4), the plane lit from +z) under --lights lights: the node emit (five queues, one call), the node resolve (one
 launch; uniform random visibility and radiance, the probe hits of the plane intersected with torch on the device),
@@ -351,6 +357,65 @@ def bench_node(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
     }
 
 
+def bench_bounce(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """the bounce call of rlGgx or rlDisney on bench_node's batch under --state, the node call beside it in the same process"""
+    import torch
+    import rlshaders_amd as R
+    from rlshaders_amd import trace as T
+    from rlshaders_amd.closures import make_light
+    disney = args.closure == "disney-bounce"
+    nl = args.lights
+    lights = [make_light(center=c, radius=r, radiance=e) for c, r, e in LIGHT_SPECS[:nl]]
+    wo, N, T_ = R.gen_frame(ctx, seed, 0, n)
+    u = lambda stream, lo=0.0, hi=1.0: R.gen_uniform(ctx, seed, 0, n, stream, lo, hi)
+    P = torch.stack([u(60, 0.0, 4.0), u(61, 0.0, 4.0), u(62)]).contiguous()
+    dev = ctx.torch_device
+    secondary = {"camera": torch.zeros(n, dtype=torch.bool, device=dev), "secondary": torch.ones(n, dtype=torch.bool, device=dev),
+                 "half": (torch.arange(n, device=dev) % 2).to(torch.bool)}[args.state]
+    depth = secondary.to(torch.uint8)
+    zero = torch.zeros(n, dtype=torch.uint8, device=dev)
+    rt = torch.where(secondary, torch.tensor(T.RLS_RT_GLOSSY, dtype=torch.uint8, device=dev),
+                     torch.tensor(T.RLS_RT_CAMERA, dtype=torch.uint8, device=dev))
+    state = T.RayState(rt, depth, zero, depth.clone(), zero.clone())
+    depths = T.gi_depths((8, 2, 2, 4))
+    if disney:
+        base = torch.stack([u(8 + j) for j in range(3)])
+        s = R.DisneySampler(ctx, wo, N, T_, base_color=base, **{k: u(32 + j) for j, k in enumerate(R._capi.DISNEY_SCALARS)})
+        kd, ks = u(50), u(51)
+        nq, bq = (T.DisneyNodeQueues(ctx, n, nl, spp_n, share_scratch=True) for _ in range(2))
+        node_emit = lambda: T.disney_node_rays(s, P, lights, spp_n, seed, queues=nq)
+        emit = lambda: T.disney_bounce_rays(s, P, lights, spp_n, seed, state, depths, queues=bq, indirectDiffuseScale=kd,
+                                            indirectSpecularScale=ks)
+    else:
+        ksc = torch.stack([u(10 + k) for k in range(3)])
+        s = R.GgxSampler(ctx, wo, N, T_, specColor=ksc, ior=u(13, 1.05, 2.55), roughness=u(14, 0.05, 1.0),
+                         anisotropic=R.gen_aniso(ctx, seed, 0, n))
+        shp = dict(KdColor=torch.stack([u(20 + k) for k in range(3)]), Kd=u(23), diffuseRoughness=u(24), Ks=u(25),
+                   KtColor=torch.stack([u(26 + k) for k in range(3)]), Kt=u(29))
+        sh = T.ggx_shader(s, **shp)
+        nq, bq = (T.GgxNodeQueues(ctx, n, nl, spp_n, share_scratch=True) for _ in range(2))
+        node_emit = lambda: T.ggx_node_rays(s, sh, P, lights, spp_n, seed, queues=nq)
+        emit = lambda: T.ggx_bounce_rays(s, sh, P, lights, spp_n, seed, state, depths, queues=bq)
+    res = {k: ctx.empty(3, n) for k in s.SHADE_AOVS + ("out",)}
+
+    def both(q, fn):
+        ms_emit = timed(fn, args.repeats, args.warmup)
+        cnt = q.counts()
+        planes = [torch.rand(3, max(cnt[r], 1), device=dev) for r in ("shadow",) + q.RAYS]
+        ms_res = timed(lambda: q.resolve(*planes, out=res, counts=cnt), args.repeats, args.warmup)
+        del planes
+        return cnt, round(ms_emit, 4), round(ms_res, 4)
+
+    _, ne0, nr0 = both(nq, node_emit)
+    cnt, be, br = both(bq, emit)
+    ncnt, ne1, nr1 = both(nq, node_emit)
+    rec["lights"], rec["state"] = nl, args.state
+    rec[args.closure] = {
+        "rays": cnt, "node_rays": ncnt, "emit_ms": be, "resolve_ms": br, "node_emit_ms": [ne0, ne1], "node_resolve_ms": [nr0, nr1],
+        "emit_over_node": round(be / min(ne0, ne1), 4), "resolve_over_node": round(br / min(nr0, nr1), 4),
+    }
+
+
 def bench_skin_node(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
     """the whole rlSkin node on the plane z = 0: emit, the one-launch resolve, the stand-alone resolves that exist, the analytic call"""
     import math
@@ -427,8 +492,10 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
-    ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node"),
-                    default="ggx")
+    ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
+                                          "ggx-bounce", "disney-bounce"), default="ggx")
+    ap.add_argument("--state", choices=("camera", "secondary", "half"), default="camera",
+                    help="ggx-bounce / disney-bounce: every point a camera ray at depth 0, a glossy ray's hit at depth 1, or the two alternating")
     ap.add_argument("--lights", type=int, default=2, help="the light loops: spherical lights, 1..8")
     ap.add_argument("--hit-spp-n", type=int, default=1, help="sss-hits: the light loop at the hits draws hit_spp_n^2 samples a light")
     args = ap.parse_args()
@@ -451,7 +518,7 @@ def main() -> None:
     if args.closure != "ggx":
         rec["closure"] = args.closure
         {"disney": bench_disney, "sss": bench_sss, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
-         "skin-node": bench_skin_node}.get(
+         "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
         print(json.dumps(rec), flush=True)
