@@ -100,7 +100,49 @@ def build_library(force: bool = False, verbose: bool = False, variant: str = "",
             list(ex.map(run, jobs))
     if force or jobs or _stale(lib, objs):
         run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(lib), *map(str, objs)])
+    if not variant:
+        build_rr_library(force=force, verbose=verbose)
     return lib
+
+
+# BASELINE config 2's kernel with one uniform-slope pass per workgroup (csrc_rr/ggx_rr.hip): a second companion, for the same
+# reason as the one below -- the product's device code stays the frozen one.  The product library looks for it next to itself
+# and hands it the streamed EXACT reflect+refract launches (csrc/ggx.hip, rr_wg_launcher), so build_library() builds it
+# right after the product and every caller of build_library() has it.  EXACT only (the kernel has no FAST flavour), the
+# same flags, a fixed -cuid; linked against librlshaders_amd.so (contexts, errors) and found next to it ($ORIGIN).
+RR_CSRC = PKG / "csrc_rr"
+RR_SOURCES = ["ggx_rr.hip"]
+RR_LIB = LIBDIR / "librls_ggx_rr.so"
+RR_HEADERS = [RR_CSRC / "rls_rr_device.hpp"]
+
+
+def build_rr_library(force: bool = False, verbose: bool = False) -> Path:
+    """Compile csrc_rr/ for gfx950 and link librls_ggx_rr.so against the product library (which must exist).  Returns its path."""
+    hipcc = _hipcc()
+    objdir = OBJDIR / "rr"
+    objdir.mkdir(parents=True, exist_ok=True)
+    objs, built = [], False
+    for name in RR_SOURCES:
+        src = RR_CSRC / name
+        obj = objdir / (src.stem + ".o")
+        objs.append(obj)
+        if force or _stale(obj, [src, *HEADERS, *RR_HEADERS, Path(__file__)]):
+            cmd = [hipcc, *HIPCC_FLAGS, f"-cuid=rls_ggx_rr.{src.stem}", "-DRLS_FAST=0", "-c", str(src), "-o", str(obj)]
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            p = subprocess.run(cmd, capture_output=True, text=True)
+            if p.returncode != 0:
+                raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
+            built = True
+    if force or built or _stale(RR_LIB, [*objs, LIB]):
+        cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(RR_LIB), *map(str, objs),
+               f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
+    return RR_LIB
 
 
 # The caller-traced integrators (include/rlshaders_amd_trace.h): a companion library beside the product, so that the product's

@@ -5,6 +5,12 @@
 // Roofline: HBM nominally (EXACT arithmetic makes the kernels VALU-issue-bound: DESIGN.md section 5).  Algorithmic bytes per point (all planes streamed): reflect triple 64 B in
 // (wo3 N3 T3 Ks3 rough ior xi2) + 32 B out (wi3 f3 pdf F) = 96 B; reflect+refract 72 B in +
 // 48 B out = 120 B; +4 B when `anisotropic` is a stream.
+#include <dlfcn.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+
 #include "rls_internal.hpp"
 
 using namespace rlsd;
@@ -152,6 +158,31 @@ __global__ RLS_GGX_ATTR(OP) void ggx_kernel_stamped(GgxIO a0, unsigned long long
 }
 #endif
 
+#if !RLS_FAST
+// The companion code object of BASELINE config 2 (csrc_rr/ggx_rr.hip, librls_ggx_rr.so: the streamed EXACT reflect+refract
+// body with one uniform-slope pass per workgroup instead of one per wavefront -- same bits).  This library's device code is
+// frozen, so the kernel lives beside it: looked for once per process, next to the file this library was loaded from, and
+// only by the product itself (an experiment flavour, librlshaders_amd_<variant>.so, launches its own kernels).  Not there, or
+// RLS_GGX_RR_WG=0 in the environment (A/B runs, the parity tests): nullptr, and ggx_kernel<5, 0, 1> runs as it always has.
+typedef rls_status (*RrWgLaunch)(rls_context *, const GgxIO *, const char *);
+RrWgLaunch rr_wg_launcher()
+{
+    static const RrWgLaunch fn = []() -> RrWgLaunch {
+        const char *e = getenv("RLS_GGX_RR_WG");
+        if (e && !strcmp(e, "0")) return nullptr;
+        Dl_info self;
+        if (!dladdr(reinterpret_cast<const void *>(&rls_ggx_reflect_refract), &self) || !self.dli_fname) return nullptr;
+        std::string path(self.dli_fname);
+        const size_t dir = path.rfind('/') == std::string::npos ? 0 : path.rfind('/') + 1;
+        if (path.compare(dir, 19, "librlshaders_amd.so") != 0) return nullptr;       // (.so, .so.0, .so.<version>)
+        path.replace(dir, std::string::npos, "librls_ggx_rr.so");
+        void *h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        return h ? reinterpret_cast<RrWgLaunch>(dlsym(h, "rls_ggx_rr_wg_launch")) : nullptr;
+    }();
+    return fn;
+}
+#endif
+
 template <int OP>
 rls_status launch_kernel(rls_context *ctx, const GgxIO &io, const char *name)
 {
@@ -161,6 +192,11 @@ rls_status launch_kernel(rls_context *ctx, const GgxIO &io, const char *name)
     if constexpr (OP == OP_REFLECT_REFRACT)        // BASELINE config 2 under rls_diag_clock_stamps_begin
         RLS_STAMPED_LAUNCH(streamed, (ggx_kernel_stamped<OP, RLS_FAST, STREAMED_ALL>),
                            rlsh::grid_for(ctx, io.n, rlsh::kBlock, RLS_CAP_MULT), io, name);
+#if !RLS_FAST
+    if constexpr (OP == OP_REFLECT_REFRACT)        // ... and without a bracket, the companion's kernel where it is installed
+        if (streamed)
+            if (const RrWgLaunch wg = rr_wg_launcher()) return wg(ctx, &io, name);
+#endif
     if (streamed)
         hipLaunchKernelGGL((ggx_kernel<OP, RLS_FAST, STREAMED_ALL>), rlsh::grid_for(ctx, io.n, rlsh::kBlock, RLS_CAP_MULT), dim3(rlsh::kBlock), 0, ctx->stream, io);
     else if (uniform)   // a thread that hoists wants many tiles to spread the hoisted work over (grid_for_hoisting)
