@@ -544,8 +544,8 @@ rls_status rls_trace_skin_resolve(rls_context *ctx, int64_t n, const rls_skin_cl
  * state (n > 0), and for whatever the node calls refuse.  Neither synchronises the host; both can be recorded into an
  * rls_graph.  The state planes are indexed by the point's index in THIS call, like P.
  *
- * Not covered: rlSkin (its Rr == 0 test changes the mean-Fresnel hand-down, and integrateScatter swaps to an Oren-Nayar light
- * loop on diffuse rays), the opacity branch and the shadow-ray branch of either node.
+ * Not covered: the opacity branch and the shadow-ray branch of any node.  rls_trace_sss_hits_emit's trace_diffuse
+ * (shouldTraceDiffuse at the probe hits) stays a per-call flag.  rlSkin's bounce calls are below, after the state's types.
  * ---------------------------------------------------------------------------------------- */
 
 /* sg->Rt */
@@ -591,6 +591,72 @@ rls_status rls_trace_disney_bounce_resolve(rls_context *ctx, int64_t n, const rl
  * rays == 0 launches nothing.  Never synchronises the host. */
 rls_status rls_trace_ray_state_advance(rls_context *ctx, int64_t rays, const uint32_t *point, const rls_ray_state *parent,
                                        int ray_type, const rls_ray_state *child);
+
+/* ------------------------------------------------------------------------------------------
+ * Secondary-ray hits: rlSkin.  rls_trace_skin_emit / _resolve with the per-point state; shader_evaluate's switches
+ * (src/rlSkin.cpp:165-256, src/rlSss.h:170-186, src/rlGgx.h:172-184) change which rays are queued AND the mean-Fresnel
+ * hand-down, so sssWeight and every AOV.  Per point i, rt = ray_type[i], d = *depths:
+ *   rt & RLS_RT_SHADOW:  the node returns before it shades (:169-172).  No ray in any queue, the probe rays written with
+ *                        maxdist = 0, the three scalars and every output plane +0.  The opacity stays with the caller.
+ *   sS = Rr_gloss[i] <= d.glossy (:185) gates both GGX lobes together.  Shut: neither lobe has a shadow ray or a glossy ray;
+ *                        sheen = specular = +0 (AI_RGB_BLACK, not 0 * weight); sheenFresnel = specularFresnel = 0, and sssWeight
+ *                        is :238 with both at 0.
+ *   first = Rr[i] == 0 (:200, :224; Rr, not the camera bit) gates each lobe's integrateGlossy.  Shut, with sS open: the lobe's
+ *                        light loop still runs, its glossy queue has no ray for the point, and the lobe's mean Fresnel is the
+ *                        running sum over the light loops' BSDF samples alone divided by their count -- 1 when nothing was
+ *                        drawn (no lights, every light RLS_MIS_LIGHT_ONLY, no valid cone): what the node call forms for a small
+ *                        lobe colour.  sheenFresnel, specularFresnel and sssWeight follow from it.
+ *   dif = rt & RLS_RT_DIFFUSE (src/rlSss.h:172-186): integrateScatter is sss_color * sum_l (irradiance_l * light diffuse), an
+ *                        Oren-Nayar MIS light loop at roughness 0 about the point's own normal, without probes.  The point's
+ *                        probe rays get maxdist = 0 and its hits are not read (as at sssWeight < AI_EPSILON); the loop's shadow
+ *                        rays go into diffuse_shadow.
+ * The AOV planes are written for every point.
+ *
+ * q.node, t.node, out, capacities and scratch are the node calls'.  diffuse_shadow (NULL if and only if n_lights == 0) needs
+ * capacity >= n * n_lights * 2 * spp_n^2; of its weight planes only weight_diffuse.r is written (weight_specular and the other two
+ * may be NULL); rls_trace_shadow_scratch_bytes(n, n_lights, spp_n) is enough scratch, and it may be the node queues' shared block.
+ * The emit fills it last, after the probe emit has written sssWeight.  At a point with dif, not a shadow ray's, and sssWeight >=
+ * AI_EPSILON it holds the diffuse-carrying rays rls_trace_ggx_direct_emit queues for a point with this P, N, T and wo, diffuseRoughness = 0, a KdColor *
+ * Kd that is not small, this first_index and the seed (seed ^ RLS_SKIN_DIFFUSE_SEED): order, kind (light | RLS_SHADOW_BSDF |
+ * RLS_SHADOW_DIFFUSE), maxdist, point and sample as in rls_shadow_queue, lights ascending, per light the light-strategy segment
+ * and then the BSDF-strategy segment; no specular segment.  sss_color does not gate it.  The seed is derived because the lobes'
+ * light loops at the same point draw from streams 6 .. 69 of hash(seed, .) already, and the diffuse loop's 6 l .. 6 l + 5 would
+ * repeat them.  Every other point has no ray in it.
+ *
+ * Resolve at a dif point:  sss_c = sssWeight < AI_EPSILON ? 0 : (sss_color_c * D_c) * sssWeight, D the light loop's diffuse sum
+ * exactly as rls_trace_sss_hits_resolve forms its direct term: per light the light-strategy and the BSDF-strategy sum of
+ * visibility_c * weight_diffuse.r in queue order, (radiance_c[l] * (their sum)) * (1 / spp_n^2), the first light assigning, the
+ * later ones adding; black when n_lights == 0.  Everything else is rls_trace_skin_resolve's arithmetic behind the switches above;
+ * out = (sheen + specular) + sss.
+ *
+ * With every point a camera ray, every counter 0 and depths >= 0 both calls write rls_trace_skin_emit / _resolve's bytes into
+ * q.node and out, and diffuse_shadow is empty.  Refused, before the context is read: what the node calls refuse; a NULL state,
+ * depths or (n > 0) state plane; diffuse_shadow not present exactly when n_lights > 0, or with a NULL offsets, required plane,
+ * too small a capacity or scratch; a NULL diffuse_visibility plane (resolve, n_lights > 0).  Neither call synchronises the host;
+ * both can be recorded into an rls_graph.
+ * ---------------------------------------------------------------------------------------- */
+
+#define RLS_SKIN_DIFFUSE_SEED 0x9E3779B9u
+
+typedef struct rls_skin_bounce_queues {
+    rls_skin_node_queues node;               /* as rls_trace_skin_emit takes them */
+    const rls_shadow_queue *diffuse_shadow;  /* integrateScatter's light loop at diffuse rays' points; NULL iff n_lights == 0 */
+} rls_skin_bounce_queues;
+
+typedef struct rls_skin_bounce_traced {
+    rls_skin_node_traced node;
+    rls_crgb diffuse_visibility;             /* not read when n_lights == 0 */
+} rls_skin_bounce_traced;
+
+rls_status rls_trace_skin_bounce_emit(rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
+                                      const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                      uint64_t first_index, const rls_ray_state *state, const rls_gi_depths *depths,
+                                      const rls_skin_bounce_queues *q);
+rls_status rls_trace_skin_bounce_resolve(rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
+                                         const rls_sphere_light *lights, int n_lights, int use_cavity_fade,
+                                         int literal_matrix, int spp_n, const rls_ray_state *state,
+                                         const rls_gi_depths *depths, const rls_skin_bounce_queues *q,
+                                         const rls_skin_bounce_traced *t, const rls_skin_integrate_out *out);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,30 @@ __device__ __forceinline__ BounceGates bounce_gates(const BounceState &b, int64_
     return g;
 }
 
+// rlSkin's shader_evaluate (src/rlSkin.cpp:165-256) reads two switches the other nodes lack, beside lit and specular (its sS,
+// :185).  They are written here, once, and not as members of BounceGates: with two more members there the rlGgx and rlDisney
+// bounce kernels that read their gates in a loop body (the light loop's emit, the refraction emit, both resolves) compile to
+// other code.
+struct SkinGates : BounceGates {
+    bool first;              // sg->Rr == 0, each lobe's integrateGlossy (:200, :224): Rr, not the camera bit
+    bool sss_diffuse;        // sg->Rt & AI_RAY_DIFFUSE off a shadow ray: integrateScatter's Oren-Nayar light loop (src/rlSss.h:172-186)
+};
+__device__ __forceinline__ SkinGates skin_gates(const BounceState &b, int64_t i)
+{
+    SkinGates g = {};
+    static_cast<BounceGates &>(g) = bounce_gates(b, i);
+    g.first = b.s.Rr[i] == 0;
+    g.sss_diffuse = g.lit && (b.s.ray_type[i] & RLS_RT_DIFFUSE);
+    return g;
+}
+// the gates at point i in a body two kernels share: STATE, the bounce call's kernel, whose argument struct carries the state
+template <bool STATE, class IO>
+__device__ __forceinline__ SkinGates state_gates(const IO &a, int64_t i)
+{
+    if constexpr (STATE) return skin_gates(a.st, i);
+    else return SkinGates{};
+}
+
 struct NoShader {};
 template <class Closure, class Shader>
 struct ShadowEmitIO {
@@ -257,6 +281,42 @@ struct SkinNodeResolveIO {
     int64_t n;
 };
 
+// rlSkin's bounce calls (rls_trace_skin_bounce_emit / _resolve): the node's argument structs with the state behind them -- the node
+// kernels keep their own structs, and with them their kernel arguments -- and the Oren-Nayar light loop that stands in for
+// integrateScatter at a diffuse ray's point (skin_diffuse_emit_kernel, rls_trace_hits.hpp): the hit list's staging (HitEmitIO)
+// over points, rays only where the point's state and its sssWeight (as the probe emit left it) open the loop.
+struct SkinBounceShadowEmitIO : SkinShadowEmitIO {
+    BounceState st;
+};
+struct SkinBounceGlossyEmitIO : SkinGlossyEmitIO {
+    BounceState st;
+};
+struct SkinBounceProbeEmitIO : SkinProbeEmitIO {
+    BounceState st;
+};
+struct SkinDiffuseEmitIO {
+    rls_cvec3 wo, N, T;      // the closure's
+    rls_cvec3 P;
+    const float *sssWeight;
+    rls_sphere_light lights[RLS_MAX_LIGHTS];
+    int nl;
+    float *dir[3];
+    float *maxdist;
+    float *wd[3];            // wd[0] only
+    uint32_t *tag;
+    int64_t *count;          // = the queue's offsets
+    int64_t n;
+    int spp;
+    uint32_t seed;
+    uint64_t first;
+    BounceState st;
+};
+// dif_s: the Oren-Nayar loop's queue (offsets, wd[0], kind, vis, rad, nl, inv; nl == 0: no queue)
+struct SkinBounceResolveIO : SkinNodeResolveIO {
+    ShadowResolveIO dif_s;
+    BounceState st;
+};
+
 // rlSss: the probe-ray emit and the scatter resolve.  Both walk tiles of `tile_points` consecutive points: ray j = i * spp + s
 // of the dense queue is ray j - p0 * spp of the tile that starts at point p0.  The emit takes up to kSssEmitRays rays per
 // tile (several per thread), the resolve up to kBlock (one per thread: its LDS holds the terms of every hit of the tile).
@@ -340,6 +400,7 @@ constexpr int kHitStagePlanes = 5;           // dir[3], maxdist, weight_diffuse.
 // whether a light-loop emit stages weight_specular (ShadowStage, rls_trace_shadow_emit.hpp): all but the hits' Oren-Nayar loop
 template <class IO> constexpr bool kStageSpecular = true;
 template <> constexpr bool kStageSpecular<HitEmitIO> = false;
+template <> constexpr bool kStageSpecular<SkinDiffuseEmitIO> = false;
 
 constexpr int kSssEmitRays = 4 * rlsh::kBlock;
 constexpr int kSssEmitPoints = rlsh::kBlock;       // (one thread per point computes the point's part)

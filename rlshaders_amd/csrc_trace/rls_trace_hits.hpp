@@ -84,9 +84,10 @@ __global__ __launch_bounds__(rlsh::kBlock) void sss_hits_list_kernel(HitListIO a
 
 // the light-sampling strategy's evaluation for the queued requests: ggx_light_eval_run's diffuse term (rls_loops.hpp; its
 // lines, to be changed together) about the closure's own normal -- AiOrenNayarMISCreateData(sg, 0) has no view to offer, and
-// at roughness 0 the lobe reads the view only to test its side.  Whole wavefront.
-template <int K>
-__device__ __forceinline__ void hit_light_eval_run(SlowLds<K> &Q, int cnt, const OrenNayar &on, float conePdf, int mode)
+// at roughness 0 the lobe reads the view only to test its side.  VIEW: the caller has a view (rlSkin's diffuse rays' points).
+// Whole wavefront.
+template <int K, bool VIEW = false>
+__device__ __forceinline__ void hit_light_eval_run(SlowLds<K> &Q, int cnt, const OrenNayar &on, V3 view, float conePdf, int mode)
 {
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
     wave_lds_fence();
@@ -99,8 +100,10 @@ __device__ __forceinline__ void hit_light_eval_run(SlowLds<K> &Q, int cnt, const
         OrenNayar o;                                            // every lane executes the fetches
         o.N = lane_fetch(on.N, src); o.A = lane_fetch(on.A, src); o.B = lane_fetch(on.B, src);
         const float cp = lane_fetch(conePdf, src);
+        V3 wo = o.N;
+        if constexpr (VIEW) wo = lane_fetch(view, src);
         if (have) {
-            const float fd = oren_nayar_brdf(o, o.N, L);
+            const float fd = oren_nayar_brdf(o, wo, L);
             const float wd = mode == RLS_MIS_LIGHT_ONLY ? 1.0f : power_heuristic(cp, oren_nayar_pdf(o, L));
             Q.q[wave][3][j] = R_DIV(fd * wd, cp);
         }
@@ -141,49 +144,11 @@ __global__ RLS_INT_ATTR void sss_hits_emit_kernel(HitEmitIO a)
         Frame fr;
         fr.N = N; fr.U = T; fr.V = cross(N, T);
         const OrenNayar on = oren_nayar_make(N, 0.0f);           // AiOrenNayarMISCreateData(sg, 0.0f), :443
+        constexpr bool kView = false;
+        const V3 view = N;
         const uint64_t index = a.first + (uint64_t)e;
         ShadowStage<G, HitEmitIO, SEGS> st = { a, i, live, sub, 0, 0 };
-        for (int l = 0; l < a.nl; l++) {
-            const LightRegs lt = light_regs(a.lights[l], P);
-            const LightCone &cone = lt.cone;
-            const int mode = lt.mode;
-            const uint32_t stream = kScrambleStream + 6 * l;
-            const uint32_t sx = hash_u32(a.seed, index, stream), sy = hash_u32(a.seed, index, stream + 1);
-            const uint32_t dx = hash_u32(a.seed, index, stream + 4), dy = hash_u32(a.seed, index, stream + 5);
-
-            // segment 0: one light sample
-            if (mode == RLS_MIS_BSDF_ONLY) st.skip(l, 0);
-            for (int s0 = sub; mode != RLS_MIS_BSDF_ONLY && s0 - sub < spp; s0 += K * G) {
-                RLS_LIGHT_SAMPLE_PUSH(slow, qn, tab, spp, s0, cone, N, sx, sy,
-                                      slow.st[0][k][tid] = L.x; slow.st[1][k][tid] = L.y; slow.st[2][k][tid] = L.z;)
-                hit_light_eval_run<K>(slow, qn, on, cone.pdf, mode);
-#pragma unroll 1
-                for (int k = 0; k < K; k++) {
-                    float t[4], ud[3] = { 0.0f, 0.0f, 0.0f };
-                    if (eval_pop<K>(slow, k, t)) ud[0] = t[3];
-                    const V3 L = mk(slow.st[0][k][tid], slow.st[1][k][tid], slow.st[2][k][tid]);
-                    st.template put<1>(cone, l, 0, s0 + k * G, s0 + k * G < spp, L, zero, ud);
-                }
-            }
-            // segment 1: one BSDF sample of the Oren-Nayar lobe (streams +4/5), where it hits the light
-            if (mode == RLS_MIS_LIGHT_ONLY) st.skip(l, 1);
-            for (int s0 = sub; mode != RLS_MIS_LIGHT_ONLY && s0 - sub < spp; s0 += G) {
-                const int s = s0;
-                float ud[3] = { 0.0f, 0.0f, 0.0f };
-                V3 Ld = mk(0.0f, 0.0f, 0.0f);
-                if (s < spp && cone.valid) {
-                    const float rx = bits_u01(tab[0][s] ^ dx), ry = bits_u01(tab[1][s] ^ dy);
-                    Ld = cosine_hemisphere(fr, rx, ry);
-                    const float pd = oren_nayar_pdf(on, Ld);
-                    if (pd > 0.0f && cone_hit(cone, Ld)) {
-                        const float fd = oren_nayar_brdf(on, N, Ld);
-                        const float wd = mode == RLS_MIS_BSDF_ONLY ? 1.0f : power_heuristic(pd, cone.pdf);
-                        ud[0] = R_DIV(fd * wd, pd);
-                    }
-                }
-                st.template put<1>(cone, l, 1, s, s < spp, Ld, zero, ud);
-            }
-        }
+#include "rls_trace_body_hit_light_loop.hpp"
         if (live && sub == 0) {
             if (a.count) a.count[i] = st.run;
             if (a.dtag) {
@@ -201,6 +166,45 @@ __global__ RLS_INT_ATTR void sss_hits_emit_kernel(HitEmitIO a)
                 a.dcount[i] = keep ? 1 : 0;
             }
         }
+    }
+}
+
+// integrateScatter at a diffuse ray's point (src/rlSss.h:172-186; rls_trace_skin_bounce_emit): the same light loop over POINTS
+// -- the closure oren_nayar_make(N, 0), the frame (N, T), the samples of hash(seed, first + i) -- at the points whose ray state
+// is a diffuse ray's (skin_gates) and whose sssWeight, as the probe emit left it, is not below AI_EPSILON, with the point's own
+// view, whose side rlGgx's Oren-Nayar lobe tests (oren_nayar_brdf): the terms are those of rls_trace_ggx_direct_emit's diffuse
+// lobe at roughness 0.  Every other point counts 0 and stages nothing, its tags included (hits_compact_kernel reads a point
+// without rays as dropped).  Most wavefronts hold no such point: the gate is read before anything is built, and a wavefront
+// without one goes on to its next round.
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void skin_diffuse_emit_kernel(SkinDiffuseEmitIO a)
+{
+    constexpr int K = RLS_SPEC_BLOCK;
+    constexpr int SEGS = kSkinShadowSegments;
+    __shared__ uint32_t tab[2][kMaxSpp];
+    __shared__ SlowLds<K> slow;
+    stage_libm_tables();
+    stage_table(tab, a.spp);
+    RLS_POINT_WALK(G, a.n)
+    const int spp = a.spp, tid = (int)threadIdx.x;
+    const float zero[3] = { 0.0f, 0.0f, 0.0f };
+    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
+        bool live = false;
+        V3 N = mk(0.0f, 0.0f, 1.0f), P = mk(0.0f, 0.0f, 0.0f), T = mk(1.0f, 0.0f, 0.0f), view = N;
+        if (i < a.n) {
+            live = skin_gates(a.st, i).sss_diffuse && !(a.sssWeight[i] < kEps);
+            if (!live && sub == 0) a.count[i] = 0;
+        }
+        if (__builtin_amdgcn_ballot_w64(live) == 0) continue;   // (wave-uniform: what follows has ballots and shuffles only)
+        if (live) { N = ld3(a.N, i); P = ld3(a.P, i); T = ld3(a.T, i); view = ld3(a.wo, i); }
+        constexpr bool kView = true;
+        Frame fr;
+        fr.N = N; fr.U = T; fr.V = cross(N, T);
+        const OrenNayar on = oren_nayar_make(N, 0.0f);           // AiOrenNayarMISCreateData(sg, 0.0f), src/rlSss.h:175
+        const uint64_t index = a.first + (uint64_t)i;
+        ShadowStage<G, SkinDiffuseEmitIO, SEGS> st = { a, i, live, sub, 0, 0 };
+#include "rls_trace_body_hit_light_loop.hpp"
+        if (live && sub == 0) a.count[i] = st.run;
     }
 }
 

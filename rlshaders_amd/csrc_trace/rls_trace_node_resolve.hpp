@@ -119,80 +119,27 @@ __global__ __launch_bounds__(rlsh::kBlock) void disney_node_compose_kernel(Disne
 // A point whose sssWeight is below AI_EPSILON has its hits left unread and sss = 0.  LDS: 37.9 KB a workgroup (the scatter
 // terms, as sss_scatter_resolve_kernel; the light loop's product planes and a ray queue's planes lie in the same store): four
 // workgroups (16 waves) a CU.
+// (the Oren-Nayar loop's queue, which the bounce call's argument struct alone has)
+template <bool STATE, class IO>
+__device__ __forceinline__ const ShadowResolveIO &skin_diffuse_loop(const IO &a)
+{
+    if constexpr (STATE) return a.dif_s;
+    else return a.sheen_s;
+}
 template <int FAST_MATH = RLS_FAST>
 __global__ __launch_bounds__(rlsh::kBlock) void skin_node_resolve_kernel(SkinNodeResolveIO a)
 {
-    __shared__ float lds[RLS_MAX_PROBE_HITS * 3 * rlsh::kBlock];
-    __shared__ uint8_t kinds[kShadowTile];
-    __shared__ float rad[RLS_MAX_LIGHTS][3];
-    __shared__ uint8_t slots[rlsh::kBlock];
-    __shared__ uint8_t shaded[rlsh::kBlock];
-    static_assert(RLS_MAX_PROBE_HITS * 3 * rlsh::kBlock >= 6 * kShadowTile, "the scatter terms' store holds the product planes");
-    float (*prod)[kShadowTile] = (float (*)[kShadowTile])lds;
-    float (*term)[3][rlsh::kBlock] = (float (*)[3][rlsh::kBlock])lds;
-    stage_libm_tables();
-    stage_radiance(rad, a.sheen_s);                              // (both lobes: the same lights)
-    const int t = (int)threadIdx.x, P = a.tile_points;
-    for (int64_t p0 = (int64_t)blockIdx.x * rlsh::kBlock; p0 < a.n; p0 += (int64_t)gridDim.x * rlsh::kBlock) {
-        const int64_t i = p0 + t;
-        float litA[3] = { 0.0f, 0.0f, 0.0f }, litB[3] = { 0.0f, 0.0f, 0.0f }, none[3], gA[3], gB[3];
-        if (a.sheen_s.nl > 0) shadow_sums<0>(prod, kinds, rad, a.sheen_s, p0, litA, none);              // :193-198
-        ray_sums_about_reference<3>(prod, a.sheen_g, p0, a.n, a.inv, gA);
-        if (a.spec_s.nl > 0) shadow_sums<0>(prod, kinds, rad, a.spec_s, p0, litB, none);                // :217-222
-        ray_sums_about_reference<3>(prod, a.spec_g, p0, a.n, a.inv, gB);
-        // integrateScatter, :244-246
-        const int bc = a.n - p0 < rlsh::kBlock ? (int)(a.n - p0) : rlsh::kBlock;
-        float sc[3] = { 0.0f, 0.0f, 0.0f };
-        for (int q0 = 0; q0 < bc; q0 += P) {
-            const int pc = bc - q0 < P ? bc - q0 : P;
-            __syncthreads();                                     // the store's previous contents are consumed
-            if (t < pc * a.spp) {
-                const int lp = t / a.spp;
-                const int64_t pi = p0 + q0 + lp, j = (p0 + q0) * a.spp + t;
-                const SkinNodeResolveIO al = RLS_INT_ARGS(a);
-                if (al.sssWeight[pi] < kEps) {
-                    slots[t] = 0; shaded[t] = 0;
-                } else {
-                    const rls_skin_closure &c = al.c;
-                    const PIndex<int64_t> pk = pindex(c.materials, pi);
-                    const float mult = ldp(c.sss_dist_multiplier, pk);
-                    const NdProfile p = nd_make<true>(ldp(c.sss_scatter_dist[0], pk) * mult, ldp(c.sss_scatter_dist[1], pk) * mult,
-                                                      ldp(c.sss_scatter_dist[2], pk) * mult);
-                    const Frame fr = sss_frame(ld3(c.N, pi), ld3(c.T, pi), true);
-                    scatter_ray_terms(term, slots, shaded, t, p, fr, ld3(al.P, pi), al.h, j, al.cavity != 0, al.literal != 0);
-                }
-            }
-            __syncthreads();
-            if (t >= q0 && t < q0 + pc) {
-                float depth;
-                scatter_point_sums(term, slots, shaded, (t - q0) * a.spp, a.spp, sc, depth);
-            }
-        }
-        if (i < a.n) {
-            const SkinNodeResolveIO al = RLS_INT_ARGS(a);
-            const rls_skin_closure &c = al.c;
-            const PIndex<int64_t> pk = pindex(c.materials, i);
-            const float sheenWeight = ldp(c.sheen_weight, pk), specWeight = ldp(c.specular_weight, pk);
-            const float sheenFresnel = al.sheenFresnel[i], specularFresnel = al.specularFresnel[i], sssWeight = al.sssWeight[i];
-            float br, bg, bb;
-            ldrgb(c.sss_color, pk, br, bg, bb);
-            const float bc3[3] = { br, bg, bb };
-            const float sw = specWeight * (1.0f - sheenFresnel);                      // :231
-            float sh[3], sp[3], ss[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                sh[k] = (sheenWeight > kEps ? litA[k] + gA[k] : 0.0f) * sheenWeight;  // :191, :207
-                sp[k] = (specWeight > kEps ? litB[k] + gB[k] : 0.0f) * sw;            // :214, :231
-                ss[k] = sssWeight < kEps ? 0.0f : bc3[k] * sc[k] * a.inv * sssWeight; // :244-246
-            }
-            const rls_skin_integrate_out &o = al.o;
-            strgb(o.sheen, i, sh[0], sh[1], sh[2]);
-            strgb(o.specular, i, sp[0], sp[1], sp[2]);
-            strgb(o.sss, i, ss[0], ss[1], ss[2]);
-            if (o.out.r) strgb(o.out, i, sh[0] + sp[0] + ss[0], sh[1] + sp[1] + ss[1], sh[2] + sp[2] + ss[2]);   // :254
-            if (o.sheenFresnel) stg(o.sheenFresnel, i, sheenFresnel);
-            if (o.specularFresnel) stg(o.specularFresnel, i, specularFresnel);
-            if (o.sssWeight) stg(o.sssWeight, i, sssWeight);
-        }
-    }
+    constexpr bool STATE = false;
+#include "rls_trace_body_skin_node_resolve.hpp"
+}
+// STATE (rls_trace_skin_bounce_resolve): a FIFTH walk, over the Oren-Nayar loop's queue (shadow_sums<1, false>, as
+// sss_hits_resolve_kernel forms its direct term) through the same store; per point the switches of shader_evaluate
+// (bounce_gates): sheen = specular = +0 where !(Rr_gloss <= GI_glossy_depth); at a diffuse ray's point the probe hits are not
+// read and sss = (sss_color * D) * sssWeight with D the loop's diffuse sum (src/rlSss.h:172-186).  integrateGlossy's Rr == 0
+// switch is the emit's: a lobe without glossy rays sums to +0.  A shadow ray's point is +0 everywhere: its sssWeight is 0.
+template <int FAST_MATH = RLS_FAST>
+__global__ __launch_bounds__(rlsh::kBlock) void skin_bounce_resolve_kernel(SkinBounceResolveIO a)
+{
+    constexpr bool STATE = true;
+#include "rls_trace_body_skin_node_resolve.hpp"
 }

@@ -88,17 +88,19 @@ __global__ __launch_bounds__(rlsh::kBlock) void sss_probe_emit_kernel(SssEmitIO 
 template <int FAST_MATH = RLS_FAST>
 __global__ __launch_bounds__(rlsh::kBlock) void skin_probe_emit_kernel(SkinProbeEmitIO a)
 {
+    constexpr bool STATE = false;
     probe_emit_tiles<4>(a, [&](int64_t i, NdProfile &p, Frame &fr) {
-        const rls_skin_closure &c = a.c;
-        const PIndex<int64_t> pk = pindex(c.materials, i);
-        const float mult = ldp(c.sss_dist_multiplier, pk);                            // :235-236
-        float sssWeight = ldp(c.sss_weight, pk);
-        sssWeight *= 1.0f - a.specularFresnel[i] * (1.0f - a.sheenFresnel[i]);        // :238
-        a.sssWeight[i] = sssWeight;
-        p = nd_make<true>(ldp(c.sss_scatter_dist[0], pk) * mult, ldp(c.sss_scatter_dist[1], pk) * mult,
-                          ldp(c.sss_scatter_dist[2], pk) * mult);
-        fr = sss_frame(ld3(c.N, i), ld3(c.T, i), true);
-        return !(sssWeight < kEps);
+#include "rls_trace_body_skin_probe_point.hpp"
+    });
+}
+// STATE (rls_trace_skin_bounce_emit): a shadow ray's point has sssWeight = +0, and neither it nor a diffuse ray's point -- where
+// integrateScatter is a light loop (src/rlSss.h:172-186; skin_diffuse_emit_kernel) -- has probe rays to trace: maxdist = 0.
+template <int FAST_MATH = RLS_FAST>
+__global__ __launch_bounds__(rlsh::kBlock) void skin_bounce_probe_emit_kernel(SkinBounceProbeEmitIO a)
+{
+    constexpr bool STATE = true;
+    probe_emit_tiles<4>(a, [&](int64_t i, NdProfile &p, Frame &fr) {
+#include "rls_trace_body_skin_probe_point.hpp"
     });
 }
 

@@ -196,67 +196,16 @@ __device__ __forceinline__ SkinLobe skin_lobe(const rls_skin_closure &c, int64_t
 template <int G, int FAST_MATH = RLS_FAST>
 __global__ RLS_INT_ATTR void skin_shadow_emit_kernel(SkinShadowEmitIO a)
 {
-    __shared__ uint32_t tab[2][kMaxSpp];
-    stage_libm_tables();
-    stage_table(tab, a.spp);
-    RLS_POINT_WALK(G, a.n)
-    const int spp = a.spp;
-    const uint32_t stream = a.lobe ? 5u : 3u;
-    for (int64_t it = 0, i = first; it < rounds; it++, i += stride) {
-        const bool live = i < a.n;
-        const int64_t ii = live ? i : a.n - 1;
-        const SkinLobe sl = skin_lobe(a.c, ii, a.lobe);
-        const Ggx &g = sl.g;
-        const V3 N = sl.N, P = ld3(a.P, ii);
-        const uint64_t index = a.first + (uint64_t)ii;
-        ShadowStage<G, SkinShadowEmitIO, kSkinShadowSegments> st = { a, i, live, sub, 0, 0 };
-        float f = 0.0f, cnt = 0.0f;
-        for (int l = 0; l < a.nl; l++) {
-            const LightRegs lt = light_regs(a.lights[l], P);
-            const LightCone &cone = lt.cone;
-            const int mode = lt.mode;
-            uint32_t scr[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) scr[k] = hash_u32(a.seed, index, kScrambleStream + 2 * (stream + 4 * l) + k);
-            const bool draw = sl.weight > kEps && cone.valid;
-            for (int s0 = 0; s0 < spp; s0 += G) {               // the same trip count in every lane (ballots, shuffles)
-                const int s = s0 + sub;
-                const bool ok = s < spp;
-                float wa[3] = { 0.0f, 0.0f, 0.0f }, wb[3] = { 0.0f, 0.0f, 0.0f }, tF = 0.0f, tC = 0.0f;
-                V3 La = mk(0.0f, 0.0f, 0.0f), Lb = mk(0.0f, 0.0f, 0.0f);
-                if (draw && ok && mode != RLS_MIS_BSDF_ONLY) {
-                    float rx = bits_u01(tab[0][s] ^ scr[0]), ry = bits_u01(tab[1][s] ^ scr[1]);
-                    La = cone_sample(cone, rx, ry);
-                    if (dot(La, N) > 0.0f) {
-                        float fr, fg, fb, pb;
-                        ggx_eval_pdf<true, true>(g, La, fr, fg, fb, pb);
-                        float wgt = mode == RLS_MIS_LIGHT_ONLY ? 1.0f : power_heuristic(cone.pdf, pb);
-                        wa[0] = R_DIV(fr * wgt, cone.pdf); wa[1] = R_DIV(fg * wgt, cone.pdf); wa[2] = R_DIV(fb * wgt, cone.pdf);
-                    }
-                }
-                if (draw && ok && mode != RLS_MIS_LIGHT_ONLY) {
-                    float rx = bits_u01(tab[0][s] ^ scr[2]), ry = bits_u01(tab[1][s] ^ scr[3]);
-                    V3 M = vndf_microfacet(sl.w, g.fr, rx, ry);
-                    Lb = reflect_direction(g.view, M);
-                    tF = ggx_fresnel(g, Lb, M);                     // mReflectWeight += ..., mMisSampleCount += 1
-                    tC = 1.0f;
-                    if (!is_zero(Lb) && dot(Lb, N) > 0.0f && cone_hit(cone, Lb)) {
-                        float fr, fg, fb, pb;
-                        ggx_eval_pdf<true, true>(g, Lb, fr, fg, fb, pb);
-                        float wgt = mode == RLS_MIS_BSDF_ONLY ? 1.0f : power_heuristic(pb, cone.pdf);
-                        wb[0] = R_DIV(fr * wgt, pb); wb[1] = R_DIV(fg * wgt, pb); wb[2] = R_DIV(fb * wgt, pb);
-                    }
-                }
-                st.put_pair(cone, l, s, ok, La, wa, Lb, wb);
-                fold<G>(f, tF);
-                cnt += G == 1 ? tC : group_sum<G>(tC);
-            }
-        }
-        if (live && sub == 0) {
-            a.count[i] = st.run;
-            a.fsum[i] = f; a.fcnt[i] = cnt;
-        }
-    }
+    constexpr bool STATE = false;
+#include "rls_trace_body_skin_shadow_emit.hpp"
+}
+// STATE (rls_trace_skin_bounce_emit): both lobes sit behind sS = Rr_gloss <= GI_glossy_depth (src/rlSkin.cpp:185) and neither
+// runs at a shadow ray's point: such a point draws nothing -- no ray, and (sum, count) = (0, 0) handed on.
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void skin_bounce_shadow_emit_kernel(SkinBounceShadowEmitIO a)
+{
+    constexpr bool STATE = true;
+#include "rls_trace_body_skin_shadow_emit.hpp"
 }
 
 // A lobe's integrateGlossy (LOBE 0 sheen: stream pair 0; 1 specular: pair 1): GgxGlossy's rays on the lobe's closure, behind
@@ -295,4 +244,27 @@ template <int G, int FAST_MATH = RLS_FAST>
 __global__ RLS_INT_ATTR void skin_specular_glossy_emit_kernel(SkinGlossyEmitIO a)
 {
     emit_points<G, SkinGlossy<G, 1>>(a);
+}
+
+// STATE (rls_trace_skin_bounce_emit): the lobe behind sS as its light loop (lobe_open: else the scalar 0 is handed down), and
+// integrateGlossy behind Rr == 0 on top of the lobe's own gates (src/rlSkin.cpp:200, 224): where that is shut the queue has no
+// ray for the point and the hand-down is the mean over the light loop's BSDF samples alone -- what a small colour gets.
+template <int G, int LOBE>
+struct SkinBounceGlossy : SkinGlossy<G, LOBE> {
+    __device__ SkinBounceGlossy(const SkinBounceGlossyEmitIO &a, int64_t ii) : SkinGlossy<G, LOBE>(a, ii)
+    {
+        const SkinGates b = skin_gates(a.st, ii);
+        this->lobe_open = this->lobe_open && b.specular;
+        this->open = this->open && b.specular && b.first;
+    }
+};
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void skin_bounce_sheen_glossy_emit_kernel(SkinBounceGlossyEmitIO a)
+{
+    emit_points<G, SkinBounceGlossy<G, 0>>(a);
+}
+template <int G, int FAST_MATH = RLS_FAST>
+__global__ RLS_INT_ATTR void skin_bounce_specular_glossy_emit_kernel(SkinBounceGlossyEmitIO a)
+{
+    emit_points<G, SkinBounceGlossy<G, 1>>(a);
 }

@@ -9,9 +9,9 @@
 // (run_shadow_emit) share the staging's carve (staging) and the scan (scan_counts); the probe emits write a dense queue.
 // Resolve: one launch per verb; a whole node's walks every queue of the node and composes the AOVs in registers.
 //
-// rlGgx's and rlDisney's whole nodes have a second pair of verbs for the hits of secondary rays (rls_trace_*_bounce_*): the
-// same checks and steps (ggx_node_emit, ggx_node_resolve, disney_node_emit, disney_node_resolve) with the per-point ray state
-// and the kernels that read it.
+// The whole nodes have a second pair of verbs for the hits of secondary rays (rls_trace_*_bounce_*): the same checks and steps
+// (ggx_node_emit, ggx_node_resolve, disney_node_emit, disney_node_resolve, skin_node_emit, skin_node_resolve) with the
+// per-point ray state and the kernels that read it; rlSkin's has a sixth queue, integrateScatter's light loop at diffuse rays.
 //
 // Built twice like the closure units of librlshaders_amd.so (rlshaders_amd/build.py, build_trace_library): RLS_FAST=0
 // carries the C ABI, the EXACT emit kernels and the mode-free scan / compact / resolve kernels; RLS_FAST=1 the FAST emit
@@ -101,6 +101,21 @@ RLS_TRACE_G_VERB(ggx_bounce_diffuse_emit, GgxBounceEmitIO)
 RLS_TRACE_G_VERB(disney_bounce_direct_emit, DisneyShadowEmitIO)
 RLS_TRACE_G_VERB(disney_bounce_diffuse_emit, DisneyBounceEmitIO)
 RLS_TRACE_G_VERB(disney_bounce_specular_emit, DisneyBounceEmitIO)
+RLS_TRACE_G_VERB(skin_bounce_shadow_emit, SkinBounceShadowEmitIO)
+RLS_TRACE_G_VERB(skin_bounce_sheen_glossy_emit, SkinBounceGlossyEmitIO)
+RLS_TRACE_G_VERB(skin_bounce_specular_glossy_emit, SkinBounceGlossyEmitIO)
+static rls_status launch_skin_bounce_probe_emit(rls_context *ctx, int, const SkinBounceProbeEmitIO &io, const char *name)
+{
+    return launch_tiles(ctx, skin_bounce_probe_emit_kernel<>, io, name);
+}
+RLS_FLAVOURS(skin_bounce_probe_emit, SkinBounceProbeEmitIO)
+RLS_TRACE_G_VERB(skin_diffuse_emit, SkinDiffuseEmitIO)
+static rls_status launch_skin_bounce_resolve(rls_context *ctx, int, const SkinBounceResolveIO &io, const char *name)
+{
+    hipLaunchKernelGGL(skin_bounce_resolve_kernel<>, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(name, RLS_FAST);
+}
+RLS_FLAVOURS(skin_bounce_resolve, SkinBounceResolveIO)
 
 #if !RLS_FAST
 
@@ -866,6 +881,167 @@ rls_status disney_node_resolve(const char *fn, rls_context *ctx, int64_t n, cons
     return rlsh::check_launch(fn);
 }
 
+// ---- rlSkin's whole node: the node calls (st == NULL) and the bounce calls (st: the per-point ray state; dq: the queue of
+// integrateScatter's light loop at diffuse rays' points, NULL without lights) ------------------------------------------------
+// the bounce calls' queue struct: the node's, and the sixth queue present exactly where there are lights
+rls_status check_skin_bounce(const char *fn, const rls_context *ctx, int64_t n, int spp_n, const rls_sphere_light *lights,
+                             int n_lights, const rls_skin_bounce_queues *q)
+{
+    if (rls_status s = check_skin_node(fn, ctx, n, spp_n, lights, n_lights, q ? &q->node : nullptr)) return s;
+    RLS_REQUIRE_IN(fn, n_lights > 0 || q->diffuse_shadow == nullptr, "queues.diffuse_shadow is set but n_lights is 0");
+    RLS_REQUIRE_IN(fn, n_lights == 0 || q->diffuse_shadow != nullptr, "queues.diffuse_shadow is NULL but n_lights > 0");
+    RLS_REQUIRE_IN(fn, n_lights == 0 || q->diffuse_shadow->offsets != nullptr, "queue.offsets is NULL");
+    return RLS_OK;
+}
+// the planes both sides need of that queue (weight_diffuse.r is its only weight plane), n > 0
+rls_status check_diffuse_shadow_queue(const char *fn, const rls_shadow_queue *q, int64_t n, int nl, int spp)
+{
+    RLS_REQUIRE_IN(fn, rlsh::has3(q->dir) && q->maxdist != nullptr, "queue.dir or queue.maxdist plane is NULL");
+    RLS_REQUIRE_IN(fn, q->weight_diffuse.r != nullptr, "queue.weight_specular or queue.weight_diffuse plane is NULL");
+    RLS_REQUIRE_IN(fn, q->kind != nullptr, "queue.kind is NULL");
+    RLS_REQUIRE_IN(fn, q->capacity >= n * nl * kSkinShadowSegments * spp, "queue.capacity < n * n_lights * 2 * spp_n^2");
+    return RLS_OK;
+}
+// its staging: the hit list's planes (dir[3], maxdist, weight_diffuse.r) and 32-bit tags of n * n_lights * 2 * spp slots
+inline Staging diffuse_shadow_staging(void *base, int64_t n, int nl, int spp)
+{
+    return staging(base, n, nl * kSkinShadowSegments * spp, kHitStagePlanes, sizeof(uint32_t));
+}
+
+rls_status skin_node_emit(const char *fn, rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
+                          const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed, uint64_t first_index,
+                          const BounceState *st, const rls_skin_node_queues *q, const rls_shadow_queue *dq)
+{
+    const rls_shadow_queue *const sq[2] = { q->sheen_shadow, q->specular_shadow };
+    const rls_ray_queue *const gq[2] = { q->sheen_glossy, q->specular_glossy };
+    float *const fresnel[2] = { q->sheenFresnel, q->specularFresnel };
+    const int spp = spp_n * spp_n;
+    if (n == 0) {
+        for (int k = 0; k < 2; k++) {
+            if (n_lights > 0)
+                if (rls_status s = empty_queue(ctx, sq[k]->offsets, fn)) return s;
+            if (rls_status s = empty_queue(ctx, gq[k]->offsets, fn)) return s;
+        }
+        if (rls_status s = empty_queue(ctx, q->probes->offsets, fn)) return s;
+        return dq ? empty_queue(ctx, dq->offsets, fn) : RLS_OK;
+    }
+    if (rls_status s = rlsh::check_closure(fn, c, &P)) return s;
+    for (int k = 0; k < 2; k++)
+        if (rls_status s = check_ray_queue(fn, gq[k], 3, n, spp_n)) return s;
+    if (rls_status s = check_probe_queue(fn, q->probes, n * spp)) return s;
+    SkinBounceShadowEmitIO sio = {};
+    if (n_lights > 0) {
+        for (int k = 0; k < 2; k++) {
+            if (rls_status s = check_shadow_queue(fn, sq[k], 0, n, n_lights, spp)) return s;
+            if (rls_status s = check_shadow_scratch(fn, sq[k], 0, n, n_lights, spp)) return s;
+        }
+        if (dq) {
+            if (rls_status s = check_diffuse_shadow_queue(fn, dq, n, n_lights, spp)) return s;
+            RLS_REQUIRE_IN(fn, dq->scratch != nullptr && dq->scratch_bytes >= diffuse_shadow_staging(nullptr, n, n_lights, spp).bytes,
+                           "queue.scratch is NULL or smaller than rls_trace_shadow_scratch_bytes");
+        }
+        if (rls_status s = copy_lights(lights, n_lights, 1, sio.lights, &sio.nl)) return s;
+        sio.c = *c; sio.P = P; sio.fcnt = q->sssWeight;
+    }
+    if (st) sio.st = *st;
+    // per lobe: the light loop, which leaves its Fresnel (sum, count) in (the lobe's Fresnel plane, sssWeight); integrateGlossy,
+    // which folds on from there and writes the lobe's hand-down into its Fresnel plane
+    for (int k = 0; k < 2; k++) {
+        if (n_lights > 0) {
+            sio.lobe = k; sio.fsum = fresnel[k];
+            SkinShadowEmitIO &pio = sio;                         // (the node call's kernels take the structs without the state)
+            if (rls_status s = st ? run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, sq[k], 0, fn, dispatch_skin_bounce_shadow_emit)
+                                  : run_shadow_emit(ctx, n, pio, spp_n, seed, first_index, sq[k], 0, fn, dispatch_skin_shadow_emit))
+                return s;
+        }
+        SkinBounceGlossyEmitIO io = {};
+        io.c = *c;
+        if (n_lights > 0) { io.fsum = fresnel[k]; io.fcnt = q->sssWeight; }
+        if (st) {
+            io.st = *st;
+            if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, gq[k], fresnel[k], 3, fn,
+                                            k == 0 ? dispatch_skin_bounce_sheen_glossy_emit : dispatch_skin_bounce_specular_glossy_emit))
+                return s;
+        } else {
+            SkinGlossyEmitIO &pio = io;
+            if (rls_status s = run_ray_emit(ctx, n, pio, spp, seed, first_index, gq[k], fresnel[k], 3, fn,
+                                            k == 0 ? dispatch_skin_sheen_glossy_emit : dispatch_skin_specular_glossy_emit)) return s;
+        }
+    }
+    // integrateScatter's probe rays; sssWeight from the two hand-downs
+    SkinBounceProbeEmitIO io = {};
+    io.c = *c; io.P = P; io.q = *q->probes;
+    io.sheenFresnel = q->sheenFresnel; io.specularFresnel = q->specularFresnel; io.sssWeight = q->sssWeight;
+    set_loop(io, n, spp_n, seed, first_index);
+    io.tile_points = sss_emit_tile_points(spp);
+    if (!st) return dispatch_skin_probe_emit(ctx, 0, io, fn);
+    io.st = *st;
+    if (rls_status s = dispatch_skin_bounce_probe_emit(ctx, 0, io, fn)) return s;
+    if (!dq) return RLS_OK;
+    // integrateScatter's light loop at the diffuse rays' points, last: it reads the sssWeight the probe emit has just written.
+    // Its streams are the lobes' light loops' at another seed.
+    SkinDiffuseEmitIO dio = {};
+    dio.wo = c->wo; dio.N = c->N; dio.T = c->T; dio.P = P; dio.sssWeight = q->sssWeight;
+    for (int l = 0; l < sio.nl; l++) dio.lights[l] = sio.lights[l];
+    dio.nl = sio.nl; dio.st = *st;
+    const Staging sg = diffuse_shadow_staging(dq->scratch, n, dio.nl, spp);
+    for (int k = 0; k < 3; k++) dio.dir[k] = sg.f[k];
+    dio.maxdist = sg.f[3]; dio.wd[0] = sg.f[4]; dio.tag = (uint32_t *)sg.tag; dio.count = dq->offsets;
+    set_loop(dio, n, spp_n, seed ^ RLS_SKIN_DIFFUSE_SEED, first_index);
+    if (rls_status s = dispatch_skin_diffuse_emit(ctx, pick_group(ctx, n, spp), dio, fn)) return s;
+    if (rls_status s = scan_counts(ctx, dq->offsets, n, sg.totals, sg.tiles)) return s;
+    ShadowCompactIO cio = {};
+    for (int k = 0; k < 4; k++) cio.src[k] = sg.f[k];
+    cio.src[7] = sg.f[4];
+    cio.tag = dio.tag; cio.offsets = dq->offsets; cio.q = *dq; cio.n = n; cio.spp = spp;
+    cio.slots = dio.nl * kSkinShadowSegments * spp;
+    cio.tile_points = compact_tile_points(kShadowMaxSlots, cio.slots);
+    hipLaunchKernelGGL(hits_compact_kernel, rlsh::grid_for(ctx, n, cio.tile_points), dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    return rlsh::check_launch("hits_compact_kernel");
+}
+
+// t, out: not NULL (the callers' check); dvis: the visibility traced for dq's rays
+rls_status skin_node_resolve(const char *fn, rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
+                             const rls_sphere_light *lights, int n_lights, int use_cavity_fade, int literal_matrix, int spp_n,
+                             const BounceState *st, const rls_skin_node_queues *q, const rls_shadow_queue *dq,
+                             const rls_skin_node_traced *t, rls_crgb dvis, const rls_skin_integrate_out *out)
+{
+    RLS_REQUIRE_IN(fn, t->hits != nullptr, "traced.hits is NULL");
+    if (rls_status s = check_max_hits(fn, t->hits)) return s;
+    if (n == 0) return RLS_OK;
+    const int spp = spp_n * spp_n;
+    if (rls_status s = rlsh::check_closure(fn, c, &P)) return s;
+    if (rls_status s = check_aov_planes(fn, { out->sheen, out->specular, out->sss }, out->out)) return s;
+    SkinBounceResolveIO io = {};
+    if (n_lights > 0) {
+        if (rls_status s = shadow_resolve_io(fn, io.sheen_s, n, 0, lights, n_lights, spp_n, q->sheen_shadow, t->sheen_visibility))
+            return s;
+        if (rls_status s = shadow_resolve_io(fn, io.spec_s, n, 0, lights, n_lights, spp_n, q->specular_shadow, t->specular_visibility))
+            return s;
+        if (dq) {
+            if (rls_status s = check_diffuse_shadow_queue(fn, dq, n, n_lights, spp)) return s;
+            RLS_REQUIRE_IN(fn, dvis.r && dvis.g && dvis.b, "visibility plane is NULL");
+            ShadowResolveIO &d = io.dif_s;
+            d = io.sheen_s;                                      // the lights' radiance, their count, 1 / spp
+            d.offsets = dq->offsets; d.kind = dq->kind; d.vis = dvis;
+            for (int k = 0; k < 3; k++) d.ws[k] = nullptr;
+            d.wd[0] = dq->weight_diffuse.r; d.wd[1] = nullptr; d.wd[2] = nullptr;
+        }
+    }
+    io.sheen_s.n = n; io.spec_s.n = n; io.dif_s.n = n;
+    if (rls_status s = node_ray_io(fn, io.sheen_g, q->sheen_glossy, 3, n, spp_n, t->sheen_glossy, out->sheen)) return s;
+    if (rls_status s = node_ray_io(fn, io.spec_g, q->specular_glossy, 3, n, spp_n, t->specular_glossy, out->specular)) return s;
+    if (rls_status s = check_probe_hits(fn, q->probes, t->hits, n * spp)) return s;
+    io.c = *c; io.P = P; io.h = *t->hits; io.o = *out;
+    io.sheenFresnel = q->sheenFresnel; io.specularFresnel = q->specularFresnel; io.sssWeight = q->sssWeight;
+    io.inv = 1.0f / (float)spp;                                  // as the loop kernels: 1 / spp
+    io.spp = spp; io.tile_points = sss_resolve_tile_points(spp);
+    io.cavity = use_cavity_fade != 0; io.literal = literal_matrix != 0; io.n = n;
+    if (!st) return dispatch_skin_node_resolve(ctx, 0, io, fn);
+    io.st = *st;
+    return dispatch_skin_bounce_resolve(ctx, 0, io, fn);
+}
+
 } // namespace
 
 extern "C" {
@@ -974,54 +1150,8 @@ rls_status rls_trace_skin_emit(rls_context *ctx, int64_t n, const rls_skin_closu
                                const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
                                uint64_t first_index, const rls_skin_node_queues *q)
 {
-    const char *fn = __func__;
-    if (rls_status s = check_skin_node(fn, ctx, n, spp_n, lights, n_lights, q)) return s;
-    const rls_shadow_queue *const sq[2] = { q->sheen_shadow, q->specular_shadow };
-    const rls_ray_queue *const gq[2] = { q->sheen_glossy, q->specular_glossy };
-    float *const fresnel[2] = { q->sheenFresnel, q->specularFresnel };
-    const int spp = spp_n * spp_n;
-    if (n == 0) {
-        for (int k = 0; k < 2; k++) {
-            if (n_lights > 0)
-                if (rls_status s = empty_queue(ctx, sq[k]->offsets, fn)) return s;
-            if (rls_status s = empty_queue(ctx, gq[k]->offsets, fn)) return s;
-        }
-        return empty_queue(ctx, q->probes->offsets, fn);
-    }
-    if (rls_status s = rlsh::check_closure(fn, c, &P)) return s;
-    for (int k = 0; k < 2; k++)
-        if (rls_status s = check_ray_queue(fn, gq[k], 3, n, spp_n)) return s;
-    if (rls_status s = check_probe_queue(fn, q->probes, n * spp)) return s;
-    SkinShadowEmitIO sio = {};
-    if (n_lights > 0) {
-        for (int k = 0; k < 2; k++) {
-            if (rls_status s = check_shadow_queue(fn, sq[k], 0, n, n_lights, spp)) return s;
-            if (rls_status s = check_shadow_scratch(fn, sq[k], 0, n, n_lights, spp)) return s;
-        }
-        if (rls_status s = copy_lights(lights, n_lights, 1, sio.lights, &sio.nl)) return s;
-        sio.c = *c; sio.P = P; sio.fcnt = q->sssWeight;
-    }
-    // per lobe: the light loop, which leaves its Fresnel (sum, count) in (the lobe's Fresnel plane, sssWeight); integrateGlossy,
-    // which folds on from there and writes the lobe's hand-down into its Fresnel plane
-    for (int k = 0; k < 2; k++) {
-        if (n_lights > 0) {
-            sio.lobe = k; sio.fsum = fresnel[k];
-            if (rls_status s = run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, sq[k], 0, fn, dispatch_skin_shadow_emit))
-                return s;
-        }
-        SkinGlossyEmitIO io = {};
-        io.c = *c;
-        if (n_lights > 0) { io.fsum = fresnel[k]; io.fcnt = q->sssWeight; }
-        if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, gq[k], fresnel[k], 3, fn,
-                                        k == 0 ? dispatch_skin_sheen_glossy_emit : dispatch_skin_specular_glossy_emit)) return s;
-    }
-    // integrateScatter's probe rays; sssWeight from the two hand-downs
-    SkinProbeEmitIO io = {};
-    io.c = *c; io.P = P; io.q = *q->probes;
-    io.sheenFresnel = q->sheenFresnel; io.specularFresnel = q->specularFresnel; io.sssWeight = q->sssWeight;
-    set_loop(io, n, spp_n, seed, first_index);
-    io.tile_points = sss_emit_tile_points(spp);
-    return dispatch_skin_probe_emit(ctx, 0, io, fn);
+    if (rls_status s = check_skin_node(__func__, ctx, n, spp_n, lights, n_lights, q)) return s;
+    return skin_node_emit(__func__, ctx, n, c, P, lights, n_lights, spp_n, seed, first_index, nullptr, q, nullptr);
 }
 
 rls_status rls_trace_skin_resolve(rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
@@ -1029,32 +1159,35 @@ rls_status rls_trace_skin_resolve(rls_context *ctx, int64_t n, const rls_skin_cl
                                   int spp_n, const rls_skin_node_queues *q, const rls_skin_node_traced *t,
                                   const rls_skin_integrate_out *out)
 {
-    const char *fn = __func__;
-    if (rls_status s = check_skin_node(fn, ctx, n, spp_n, lights, n_lights, q)) return s;
+    if (rls_status s = check_skin_node(__func__, ctx, n, spp_n, lights, n_lights, q)) return s;
     RLS_REQUIRE(t != nullptr && out != nullptr, "traced or out is NULL");
-    RLS_REQUIRE(t->hits != nullptr, "traced.hits is NULL");
-    if (rls_status s = check_max_hits(fn, t->hits)) return s;
-    if (n == 0) return RLS_OK;
-    const int spp = spp_n * spp_n;
-    if (rls_status s = rlsh::check_closure(fn, c, &P)) return s;
-    if (rls_status s = check_aov_planes(fn, { out->sheen, out->specular, out->sss }, out->out)) return s;
-    SkinNodeResolveIO io = {};
-    if (n_lights > 0) {
-        if (rls_status s = shadow_resolve_io(fn, io.sheen_s, n, 0, lights, n_lights, spp_n, q->sheen_shadow, t->sheen_visibility))
-            return s;
-        if (rls_status s = shadow_resolve_io(fn, io.spec_s, n, 0, lights, n_lights, spp_n, q->specular_shadow, t->specular_visibility))
-            return s;
-    }
-    io.sheen_s.n = n; io.spec_s.n = n;
-    if (rls_status s = node_ray_io(fn, io.sheen_g, q->sheen_glossy, 3, n, spp_n, t->sheen_glossy, out->sheen)) return s;
-    if (rls_status s = node_ray_io(fn, io.spec_g, q->specular_glossy, 3, n, spp_n, t->specular_glossy, out->specular)) return s;
-    if (rls_status s = check_probe_hits(fn, q->probes, t->hits, n * spp)) return s;
-    io.c = *c; io.P = P; io.h = *t->hits; io.o = *out;
-    io.sheenFresnel = q->sheenFresnel; io.specularFresnel = q->specularFresnel; io.sssWeight = q->sssWeight;
-    io.inv = 1.0f / (float)spp;                                  // as the loop kernels: 1 / spp
-    io.spp = spp; io.tile_points = sss_resolve_tile_points(spp);
-    io.cavity = use_cavity_fade != 0; io.literal = literal_matrix != 0; io.n = n;
-    return dispatch_skin_node_resolve(ctx, 0, io, fn);
+    return skin_node_resolve(__func__, ctx, n, c, P, lights, n_lights, use_cavity_fade, literal_matrix, spp_n, nullptr, q, nullptr,
+                             t, rls_crgb{}, out);
+}
+
+rls_status rls_trace_skin_bounce_emit(rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
+                                      const rls_sphere_light *lights, int n_lights, int spp_n, uint32_t seed,
+                                      uint64_t first_index, const rls_ray_state *state, const rls_gi_depths *depths,
+                                      const rls_skin_bounce_queues *q)
+{
+    BounceState st = {};
+    if (rls_status s = check_skin_bounce(__func__, ctx, n, spp_n, lights, n_lights, q)) return s;
+    if (rls_status s = check_state(__func__, state, depths, n > 0, st)) return s;
+    return skin_node_emit(__func__, ctx, n, c, P, lights, n_lights, spp_n, seed, first_index, &st, &q->node, q->diffuse_shadow);
+}
+
+rls_status rls_trace_skin_bounce_resolve(rls_context *ctx, int64_t n, const rls_skin_closure *c, rls_cvec3 P,
+                                         const rls_sphere_light *lights, int n_lights, int use_cavity_fade,
+                                         int literal_matrix, int spp_n, const rls_ray_state *state,
+                                         const rls_gi_depths *depths, const rls_skin_bounce_queues *q,
+                                         const rls_skin_bounce_traced *t, const rls_skin_integrate_out *out)
+{
+    BounceState st = {};
+    if (rls_status s = check_skin_bounce(__func__, ctx, n, spp_n, lights, n_lights, q)) return s;
+    if (rls_status s = check_state(__func__, state, depths, n > 0, st)) return s;
+    RLS_REQUIRE(t != nullptr && out != nullptr, "traced or out is NULL");
+    return skin_node_resolve(__func__, ctx, n, c, P, lights, n_lights, use_cavity_fade, literal_matrix, spp_n, &st, &q->node,
+                             q->diffuse_shadow, &t->node, t->diffuse_visibility, out);
 }
 
 rls_status rls_trace_sss_hits_scratch_bytes(int64_t n, int spp_n, int max_hits, int64_t hit_capacity, int n_lights,

@@ -350,15 +350,16 @@ inline void resolveHits(const Device &d, const rls_probe_hits &hits, const rls_s
 
 // The device buffers of one light-loop emit (rls_shadow_queue): per-ray planes for n * n_lights * 3 * spp_n^2 rays, offsets
 // [n + 1] and the emit's scratch.  Ggx: weight_diffuse is its .r plane alone.  Skin: a lobe's light loop of the rlSkin node --
-// no weight_diffuse, two rays a sample at most (n * n_lights * 2 * spp_n^2 rays).
+// no weight_diffuse, two rays a sample at most (n * n_lights * 2 * spp_n^2 rays).  SkinScatter: integrateScatter's Oren-Nayar
+// light loop at the diffuse rays' points of an rlSkin bounce emit -- Skin's capacity, weight_diffuse.r alone, no weight_specular.
 class ShadowQueue {
 public:
-    enum Node { Ggx, Disney, Skin };
+    enum Node { Ggx, Disney, Skin, SkinScatter };
 
     ShadowQueue(const Device &d, int64_t n, int n_lights, int spp_n, Node node)
         : dev_(&d), n_(n), n_lights_(n_lights), spp_n_(spp_n), node_(node)
     {
-        const int64_t cap = n * n_lights * (node == Skin ? 2 : 3) * spp_n * spp_n;
+        const int64_t cap = n * n_lights * (node == Skin || node == SkinScatter ? 2 : 3) * spp_n * spp_n;
         size_t scratch = 0;
         check(rls_trace_shadow_scratch_bytes(n, n_lights, spp_n, &scratch));
         try {
@@ -366,7 +367,7 @@ public:
             q_.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(n + 1)));
             q_.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
             q_.maxdist = falloc(cap);
-            q_.weight_specular = rls_rgb{falloc(cap), falloc(cap), falloc(cap)};
+            if (node != SkinScatter) q_.weight_specular = rls_rgb{falloc(cap), falloc(cap), falloc(cap)};
             if (node != Skin) q_.weight_diffuse.r = falloc(cap);
             if (node == Disney) { q_.weight_diffuse.g = falloc(cap); q_.weight_diffuse.b = falloc(cap); }
             q_.kind = static_cast<uint8_t *>(alloc((size_t)cap));
@@ -571,6 +572,34 @@ private:
     rls_skin_node_queues q_{};
 };
 
+// rls_skin_bounce_queues: the node's queues and the shadow queue of integrateScatter's light loop at the diffuse rays' points
+// (none with n_lights == 0)
+class SkinBounceQueues {
+public:
+    SkinBounceQueues(const Device &d, int64_t n, int n_lights, int spp_n)
+        : node_(d, n, n_lights, spp_n),
+          diffuse_shadow_(n_lights > 0 ? new ShadowQueue(d, n, n_lights, spp_n, ShadowQueue::SkinScatter) : nullptr)
+    {
+        q_.node = node_.c();
+        q_.diffuse_shadow = diffuse_shadow_ ? &diffuse_shadow_->c() : nullptr;
+    }
+    ~SkinBounceQueues() { delete diffuse_shadow_; }
+    SkinBounceQueues(const SkinBounceQueues &) = delete;
+    SkinBounceQueues &operator=(const SkinBounceQueues &) = delete;
+
+    const rls_skin_bounce_queues &c() const { return q_; }
+    const SkinNodeQueues &node() const { return node_; }
+    const ShadowQueue *diffuseShadow() const { return diffuse_shadow_; }      // nullptr without lights
+    int64_t points() const { return node_.points(); }
+    int lights() const { return node_.lights(); }
+    int sppN() const { return node_.sppN(); }
+
+private:
+    SkinNodeQueues node_;
+    ShadowQueue *diffuse_shadow_;
+    rls_skin_bounce_queues q_{};
+};
+
 namespace detail {
 inline rls_crgb crgb(const Planes &p) { return p.empty() ? rls_crgb{nullptr, nullptr, nullptr} : rls_crgb{p.plane(0), p.plane(1), p.plane(2)}; }
 template <class Q>
@@ -763,6 +792,32 @@ inline void resolveNode(const Device &d, const rls_skin_closure &c, const Planes
     if (out) o.out = out->rgb();
     check(rls_trace_skin_resolve(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights,
                                  cavityFade ? 1 : 0, literalMatrix ? 1 : 0, q.sppN(), &q.c(), &t, &o));
+}
+
+// rlSkin at the hits of secondary rays (rls_trace_skin_bounce_emit / _resolve): emitNode / resolveNode with the ray state per
+// point and the options' GI depths; diffuseVisibility: for q.diffuseShadow()'s rays (an empty Planes without lights)
+inline void emitBounce(const Device &d, const rls_skin_closure &c, const Planes &P, const rls_sphere_light *lights, int n_lights,
+                       int64_t n, int spp_n, uint32_t seed, const rls_ray_state &state, const rls_gi_depths &depths,
+                       SkinBounceQueues &q, uint64_t first_index = 0)
+{
+    detail::checkNodeQueues(q, n, n_lights, spp_n, "emitBounce: queues of another size or light count");
+    check(rls_trace_skin_bounce_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n, seed,
+                                     first_index, &state, &depths, &q.c()));
+}
+inline void resolveBounce(const Device &d, const rls_skin_closure &c, const Planes &P, const rls_sphere_light *lights,
+                          int n_lights, const rls_ray_state &state, const rls_gi_depths &depths, const SkinBounceQueues &q,
+                          const Planes &sheenVisibility, const Planes &specularVisibility, const Planes &sheenGlossy,
+                          const Planes &specularGlossy, const rls_probe_hits &hits, const Planes &diffuseVisibility,
+                          bool cavityFade, bool literalMatrix, Planes &aovs, Planes *out = nullptr)
+{
+    detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveBounce: queues of another light count");
+    rls_skin_bounce_traced t = {{detail::crgb(sheenVisibility), detail::crgb(specularVisibility), detail::crgb(sheenGlossy),
+                                 detail::crgb(specularGlossy), &hits}, detail::crgb(diffuseVisibility)};
+    rls_skin_integrate_out o = {};
+    o.sheen = aovs.rgb(0); o.specular = aovs.rgb(3); o.sss = aovs.rgb(6);
+    if (out) o.out = out->rgb();
+    check(rls_trace_skin_bounce_resolve(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights,
+                                        cavityFade ? 1 : 0, literalMatrix ? 1 : 0, q.sppN(), &state, &depths, &q.c(), &t, &o));
 }
 
 } // namespace rlsb

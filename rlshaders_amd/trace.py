@@ -30,6 +30,8 @@ or of one rlDisney lobe, trace them with your own tracer, resolve the radiance; 
     st = trace.RayState.camera(ctx, n)                           # sg->Rt and the sg->Rr* counters per point
     bq = trace.ggx_bounce_rays(sampler, shader, P, lights, 4, 7, st, depths=(8, 2, 2, 4))   # the node under that state
     hits = trace.advance_state(ctx, bq.glossy, st, trace.RLS_RT_GLOSSY)                     # the state of those rays' hits
+    kq = trace.skin_bounce_rays(skin, P, lights, 4, 7, st, depths=(8, 2, 2, 4))             # SkinBounceQueues: + diffuse_shadow
+    aov = kq.resolve(vis_a, vis_b, La, Lb, cnt, hP, hN, E, diffuse_visibility=vis_d)        # rlSkin under that state
 
 ``count`` is read from the device once (it synchronises); everything else stays asynchronous on the context's stream, so
 ``glossy_rays(..., queue=q)`` / ``q.resolve(L, out=...)`` with preallocated tensors can be recorded by ``ctx.capture()``.
@@ -154,6 +156,20 @@ class RayState_(C.Structure):
 
 _state, _depths = C.POINTER(RayState_), C.POINTER(GiDepths_)
 
+# rls_trace_skin_bounce_emit: the seed of integrateScatter's light loop at diffuse rays' points is seed ^ this
+RLS_SKIN_DIFFUSE_SEED = 0x9E3779B9
+
+
+class SkinBounceQueues_(C.Structure):
+    """rls_skin_bounce_queues"""
+    _fields_ = [("node", SkinNodeQueues_), ("diffuse_shadow", _sq)]
+
+
+class SkinBounceTraced_(C.Structure):
+    """rls_skin_bounce_traced"""
+    _fields_ = [("node", SkinNodeTraced_), ("diffuse_visibility", capi.CRgb)]
+
+
 PROTOTYPES = {
     "rls_trace_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
     "rls_trace_ggx_glossy_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
@@ -208,6 +224,11 @@ PROTOTYPES = {
     "rls_trace_skin_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.SkinClosure), capi.CVec3, _lights, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(SkinNodeQueues_), C.POINTER(SkinNodeTraced_),
                                          C.POINTER(capi.SkinIntegrateOut)]),
+    "rls_trace_skin_bounce_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.SkinClosure), capi.CVec3, _lights, C.c_int, C.c_int,
+                                             C.c_uint32, C.c_uint64, _state, _depths, C.POINTER(SkinBounceQueues_)]),
+    "rls_trace_skin_bounce_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.SkinClosure), capi.CVec3, _lights, C.c_int, C.c_int,
+                                                C.c_int, C.c_int, _state, _depths, C.POINTER(SkinBounceQueues_),
+                                                C.POINTER(SkinBounceTraced_), C.POINTER(capi.SkinIntegrateOut)]),
 }
 
 _lib = None
@@ -664,22 +685,25 @@ class ShadowQueue:
     properties view the first ``count`` rays.  ``disney``: an rlDisney queue (three planes of weight_diffuse; rlGgx has one).
     ``skin``: a lobe's light loop of the rlSkin node: no weight_diffuse, two rays a sample at most (capacity n * n_lights * 2 *
     spp_n^2), within a light the samples ascending and a sample's light-strategy ray before its BSDF-strategy ray; resolved by
-    ``SkinNodeQueues.resolve``."""
+    ``SkinNodeQueues.resolve``.  ``scatter`` (with ``skin``): integrateScatter's Oren-Nayar light loop at the diffuse rays' points
+    of an rlSkin bounce emit: weight_diffuse [1, count] alone, no weight_specular; rlGgx's order without the specular segment."""
 
     def __init__(self, ctx, n: int, n_lights: int, spp_n: int, disney: bool = False, scratch: Optional[torch.Tensor] = None,
-                 skin: bool = False):
+                 skin: bool = False, scatter: bool = False):
         self.ctx, self.n, self.n_lights, self.spp_n, self.disney = ctx, int(n), int(n_lights), int(spp_n), bool(disney)
-        self.skin = bool(skin)
+        self.skin, self.scatter = bool(skin), bool(scatter)
         if self.skin and self.disney:
             raise ValueError("skin and disney exclude each other")
+        if self.scatter and not self.skin:
+            raise ValueError("scatter: a queue of the rlSkin node")
         dev = ctx.torch_device
         cap = self.n * self.n_lights * (2 if skin else 3) * self.spp_n * self.spp_n
         self.capacity = cap
         self.offsets = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
         self._dir = torch.empty(3, cap, dtype=torch.float32, device=dev)
         self._maxdist = torch.empty(cap, dtype=torch.float32, device=dev)
-        self._ws = torch.empty(3, cap, dtype=torch.float32, device=dev)
-        self._wd = torch.empty(0 if skin else 3 if disney else 1, cap, dtype=torch.float32, device=dev)
+        self._ws = torch.empty(0 if scatter else 3, cap, dtype=torch.float32, device=dev)
+        self._wd = torch.empty(1 if scatter else 0 if skin else 3 if disney else 1, cap, dtype=torch.float32, device=dev)
         self._kind = torch.empty(cap, dtype=torch.uint8, device=dev)
         self._point = torch.empty(cap, dtype=torch.int32, device=dev)          # uint32 on the device; n < 2^31 here
         self._sample = torch.empty(cap, dtype=torch.uint8, device=dev)
@@ -690,9 +714,9 @@ class ShadowQueue:
         q.offsets = self.offsets.data_ptr()
         q.dir = capi.Vec3(*[self._dir[k].data_ptr() for k in range(3)])
         q.maxdist = self._maxdist.data_ptr()
-        q.weight_specular = capi.Rgb(*[self._ws[k].data_ptr() for k in range(3)])
+        q.weight_specular = capi.Rgb(*[None if scatter else self._ws[k].data_ptr() for k in range(3)])
         wd = self._wd
-        q.weight_diffuse = capi.Rgb(None if skin else wd[0].data_ptr(), wd[1].data_ptr() if disney else None,
+        q.weight_diffuse = capi.Rgb(None if skin and not scatter else wd[0].data_ptr(), wd[1].data_ptr() if disney else None,
                                     wd[2].data_ptr() if disney else None)
         q.kind, q.point, q.sample = self._kind.data_ptr(), self._point.data_ptr(), self._sample.data_ptr()
         q.scratch, q.scratch_bytes = self._scratch.data_ptr(), self._scratch.numel()
@@ -1089,10 +1113,21 @@ class SkinNodeQueues(_NodeQueues):
         visibilities are not read without lights and may be None); count, P, N, irradiance are the probe hits as
         ``ProbeQueue.resolve`` takes them.  ``counts``: the ray counts where the caller knows them (skips the reads of
         offsets[n], e.g. while recording a graph)."""
-        if self.sampler is None:
-            raise RuntimeError("resolve: no emit has filled these queues (trace.skin_node_rays)")
+        t, hits, out, o = self._traced(sheen_visibility, specular_visibility, sheen_glossy, specular_glossy, count, P, N, irradiance,
+                                       out, self.counts() if counts is None else counts)
         ctx, n = self.ctx, self.n
-        cnt = self.counts() if counts is None else counts
+        la, nl = self.lights
+        q = self._struct()
+        check(load().rls_trace_skin_resolve(ctx.handle, n, C.byref(self.sampler.c), _points(self.P, n), la, nl,
+                                            1 if use_cavity_fade else 0, 1 if literal_matrix else 0, self.spp_n, C.byref(q),
+                                            C.byref(t), C.byref(o)))
+        return out
+
+    def _traced(self, sheen_visibility, specular_visibility, sheen_glossy, specular_glossy, count, P, N, irradiance, out, cnt):
+        """the node's traced struct (and the hits it points at, to be kept alive), the output dict and its C struct"""
+        if self.sampler is None:
+            raise RuntimeError("resolve: no emit has filled these queues (trace.skin_node_rays / skin_bounce_rays)")
+        ctx, n = self.ctx, self.n
         t = SkinNodeTraced_()
         if self.n_lights > 0:
             t.sheen_visibility = _radiance(sheen_visibility, cnt["sheen_shadow"], "sheen_visibility")
@@ -1111,11 +1146,55 @@ class SkinNodeQueues(_NodeQueues):
         for k in self.SCALARS:
             if k in out:
                 setattr(o, k, plane(out[k], n, k))
+        return t, hits, out, o
+
+
+class SkinBounceQueues(SkinNodeQueues):
+    """``SkinNodeQueues`` for an rlSkin bounce emit (rls_trace_skin_bounce_emit): the node's queues and ``diffuse_shadow``, the
+    ShadowQueue of integrateScatter's Oren-Nayar light loop at the diffuse rays' points (None without lights; weight_diffuse
+    [1, count] alone)."""
+    STRUCT, EMIT, BOUNCE_EMIT = SkinBounceQueues_, "rls_trace_skin_bounce_emit", "rls_trace_skin_bounce_emit"
+
+    def __init__(self, ctx, n: int, n_lights: int, spp_n: int, share_scratch: bool = False):
+        super().__init__(ctx, n, n_lights, spp_n, share_scratch)
+        self.diffuse_shadow = ShadowQueue(ctx, self.n, self.n_lights, self.spp_n, scratch=self.scratch, skin=True, scatter=True) \
+            if self.n_lights > 0 else None
+
+    def _struct(self):
+        node = super()._struct()
+        q = SkinBounceQueues_()
+        for name, _ in SkinNodeQueues_._fields_:
+            setattr(q.node, name, getattr(node, name))
+        q.diffuse_shadow = C.pointer(self.diffuse_shadow.q) if self.diffuse_shadow is not None else None
+        return q
+
+    def counts(self) -> dict:
+        cnt = super().counts()
+        cnt["diffuse_shadow"] = self.diffuse_shadow.count if self.diffuse_shadow is not None else 0
+        return cnt
+
+    def resolve(self, sheen_visibility, specular_visibility, sheen_glossy, specular_glossy, count, P, N, irradiance,
+                diffuse_visibility=None, use_cavity_fade: bool = False, literal_matrix: bool = False, out=None,
+                counts: Optional[dict] = None) -> dict:
+        """``SkinNodeQueues.resolve`` under the emit's ray state (rls_trace_skin_bounce_resolve).  ``diffuse_visibility``:
+        [3, >= count] float32 for ``diffuse_shadow``'s rays; not read without lights and may be None."""
+        cnt = self.counts() if counts is None else counts
+        node, hits, out, o = self._traced(sheen_visibility, specular_visibility, sheen_glossy, specular_glossy, count, P, N,
+                                          irradiance, out, cnt)
+        if self.state is None:
+            raise RuntimeError("resolve: no bounce emit has filled these queues (trace.skin_bounce_rays)")
+        t = SkinBounceTraced_()
+        for name, _ in SkinNodeTraced_._fields_:
+            setattr(t.node, name, getattr(node, name))
+        if self.n_lights > 0:
+            t.diffuse_visibility = _radiance(diffuse_visibility, cnt["diffuse_shadow"], "diffuse_visibility")
+        ctx, n = self.ctx, self.n
         la, nl = self.lights
         q = self._struct()
-        check(load().rls_trace_skin_resolve(ctx.handle, n, C.byref(self.sampler.c), _points(self.P, n), la, nl,
-                                            1 if use_cavity_fade else 0, 1 if literal_matrix else 0, self.spp_n, C.byref(q),
-                                            C.byref(t), C.byref(o)))
+        state, depths = self.state
+        check(load().rls_trace_skin_bounce_resolve(ctx.handle, n, C.byref(self.sampler.c), _points(self.P, n), la, nl,
+                                                   1 if use_cavity_fade else 0, 1 if literal_matrix else 0, self.spp_n,
+                                                   C.byref(state.struct(n)), C.byref(depths), C.byref(q), C.byref(t), C.byref(o)))
         return out
 
 
@@ -1126,3 +1205,15 @@ def skin_node_rays(shader, P: torch.Tensor, lights, spp_n: int, seed: int, first
     ``shader``: a ``SkinShader``; ``lights``: None, one ``make_light`` or a sequence; P: [3, n] float32, sg->P per point.
     ``share_scratch``: the queues share one scratch block."""
     return _node_emit(SkinNodeQueues, shader, None, P, lights, spp_n, seed, first_index, queues, share_scratch)
+
+
+def skin_bounce_rays(shader, P: torch.Tensor, lights, spp_n: int, seed: int, state: RayState, depths, first_index: int = 0,
+                     queues: Optional[SkinBounceQueues] = None, share_scratch: bool = False) -> SkinBounceQueues:
+    """``skin_node_rays`` at the hits of secondary rays (rls_trace_skin_bounce_emit): per point the switches of rlSkin's
+    shader_evaluate read off ``state`` and ``depths`` (``gi_depths``) -- nothing at a shadow ray's point, both GGX lobes behind
+    Rr_gloss <= GI_glossy_depth, each lobe's integrateGlossy behind Rr == 0 (which moves the mean-Fresnel hand-down, so
+    sssWeight), and on a diffuse ray integrateScatter's probe walk replaced by one Oren-Nayar light loop, whose shadow rays go
+    into ``diffuse_shadow`` at the seed ``seed ^ RLS_SKIN_DIFFUSE_SEED``.  The queues remember the state: ``.resolve(...)`` is the
+    bounce resolve."""
+    return _node_emit(SkinBounceQueues, shader, None, P, lights, spp_n, seed, first_index, queues, share_scratch,
+                      state=(state, depths))

@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
+    python tools/trace_bench.py [--closure ggx|disney|sss|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -45,6 +45,10 @@ launch; uniform random visibility and radiance, the probe hits of the plane inte
 rls_skin_integrate on the same batch, and the existing stand-alone resolves that fit the node's queues -- one glossy resolve
 per lobe and the scatter resolve.  The lobes' shadow queues (one sum per light, no diffuse planes) have no stand-alone
 resolve, and there is no compose kernel for this node: `separate_partial_ms` is a LOWER bound on a separate-kernels path.
+--closure skin-bounce: the rlSkin node at the hits of secondary rays (trace.skin_bounce_rays) on the skin-node batch under
+--state (`camera`: the node call's rays and an empty diffuse_shadow; `secondary`: every point a glossy ray's hit at depth 1, no
+glossy rays; `half`: the two alternating; `diffuse`: every point a diffuse ray's hit, the Oren-Nayar light loop in place of the
+probe walk), the node call beside it in the same process as for the other two nodes.
 """
 from __future__ import annotations
 
@@ -416,12 +420,11 @@ def bench_bounce(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
     }
 
 
-def bench_skin_node(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
-    """the whole rlSkin node on the plane z = 0: emit, the one-launch resolve, the stand-alone resolves that exist, the analytic call"""
+def skin_batch(args, ctx, n: int, seed: int):
+    """the rlSkin batch of skin-node and skin-bounce: per-point parameters on the plane z = 0 -> (shader, P, lights, Ns, Tg, p, dist, mult)"""
     import math
     import torch
     import rlshaders_amd as R
-    from rlshaders_amd import trace as T
     from rlshaders_amd.closures import make_light
     nl = args.lights
     dev = ctx.torch_device
@@ -440,16 +443,14 @@ def bench_skin_node(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None
     p = dict(sss_color=u3(10), sss_weight=u(13, 0.2, 1.0), sss_dist_multiplier=mult, sss_scatter_dist=dist,
              specular_color=u3(14), specular_weight=u(17, 0.1, 0.9), specular_roughness=u(18, 0.05, 1.0), specular_ior=u(19, 1.05, 2.0),
              sheen_color=u3(20), sheen_weight=u(23, 0.1, 0.9), sheen_roughness=u(24, 0.05, 1.0), sheen_ior=u(25, 1.05, 2.0))
-    sk = R.SkinShader(ctx, wo, Ns, Tg, **p)
-    scene = R.make_scene("plane", light_dir=(0, 0, 1), light_color=(1.0, 1.0, 1.0))
-    keys3, keys1 = ("sheen", "specular", "sss", "out"), ("sheenFresnel", "specularFresnel", "sssWeight")
-    aov = {k: ctx.empty(3, n) for k in keys3}
-    aov.update({k: ctx.empty(n) for k in keys1})
-    ms_int = timed(lambda: sk.integrate(P, scene, spp_n, seed, env=(0.7, 0.8, 0.9), out=aov, lights=lights), args.repeats, args.warmup)
-    nq = T.SkinNodeQueues(ctx, n, nl, spp_n, share_scratch=True)
-    ms_emit = timed(lambda: T.skin_node_rays(sk, P, lights, spp_n, seed, queues=nq), args.repeats, args.warmup)
-    cnt = nq.counts()
-    O, D, md = nq.probes.origin, nq.probes.dir, nq.probes.maxdist
+    return R.SkinShader(ctx, wo, Ns, Tg, **p), P, lights, Ns, Tg, p, dist, mult
+
+
+def plane_hits(pq):
+    """the probe queue's rays intersected with the plane z = 0 on the device -> (count, P, N, E = 1 / pi, the hits found)"""
+    import math
+    import torch
+    O, D, md = pq.origin, pq.dir, pq.maxdist
     with torch.no_grad():
         t = -O[2] / D[2]
         ok = (D[2] != 0) & (t > 0) & (t <= md)
@@ -458,8 +459,69 @@ def bench_skin_node(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None
         hN[2] = 1
         E = torch.full_like(hP, 1.0 / math.pi)
         hc = ok.to(torch.uint8)
-    hits = int(hc.sum().item())
-    rnd = lambda k: torch.rand(3, max(cnt[k], 1), device=dev)
+    return hc, hP, hN, E, int(hc.sum().item())
+
+
+def bench_skin_bounce(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """the bounce call of rlSkin on the skin-node batch under --state, the node call beside it in the same process"""
+    import torch
+    from rlshaders_amd import trace as T
+    sk, P, lights, *_ = skin_batch(args, ctx, n, seed)
+    nl, dev = args.lights, ctx.torch_device
+    odd = (torch.arange(n, device=dev) % 2).to(torch.bool)
+    secondary = {"camera": torch.zeros_like(odd), "secondary": torch.ones_like(odd), "half": odd, "diffuse": torch.ones_like(odd)}[args.state]
+    depth = secondary.to(torch.uint8)
+    zero = torch.zeros(n, dtype=torch.uint8, device=dev)
+    kind = T.RLS_RT_DIFFUSE if args.state == "diffuse" else T.RLS_RT_GLOSSY
+    rt = torch.where(secondary, torch.tensor(kind, dtype=torch.uint8, device=dev), torch.tensor(T.RLS_RT_CAMERA, dtype=torch.uint8, device=dev))
+    state = T.RayState(rt, depth, depth.clone() if args.state == "diffuse" else zero, zero.clone() if args.state == "diffuse" else depth.clone(),
+                       zero.clone())
+    depths = T.gi_depths((8, 2, 2, 4))
+    nq, bq = T.SkinNodeQueues(ctx, n, nl, spp_n, share_scratch=True), T.SkinBounceQueues(ctx, n, nl, spp_n, share_scratch=True)
+    keys3, keys1 = ("sheen", "specular", "sss", "out"), ("sheenFresnel", "specularFresnel", "sssWeight")
+    res = {k: ctx.empty(3, n) for k in keys3}
+    res.update({k: ctx.empty(n) for k in keys1})
+
+    def both(q, fn, bounce):
+        ms_emit = timed(fn, args.repeats, args.warmup)
+        cnt = q.counts()
+        hc, hP, hN, E, hits = plane_hits(q.probes)
+        rnd = lambda k: torch.rand(3, max(cnt[k], 1), device=dev)
+        planes = [rnd("sheen_shadow"), rnd("specular_shadow"), rnd("sheen_glossy"), rnd("specular_glossy")]
+        kw = dict(diffuse_visibility=rnd("diffuse_shadow")) if bounce else {}
+        ms_res = timed(lambda: q.resolve(*planes, hc, hP, hN, E, out=res, counts=cnt, **kw), args.repeats, args.warmup)
+        del planes, kw, hc, hP, hN, E
+        return dict(cnt, probes=q.probes.count, probe_hits=hits), round(ms_emit, 4), round(ms_res, 4)
+
+    node_emit = lambda: T.skin_node_rays(sk, P, lights, spp_n, seed, queues=nq)
+    emit = lambda: T.skin_bounce_rays(sk, P, lights, spp_n, seed, state, depths, queues=bq)
+    _, ne0, nr0 = both(nq, node_emit, False)
+    cnt, be, br = both(bq, emit, True)
+    ncnt, ne1, nr1 = both(nq, node_emit, False)
+    rec["lights"], rec["state"] = nl, args.state
+    rec[args.closure] = {
+        "rays": cnt, "node_rays": ncnt, "emit_ms": be, "resolve_ms": br, "node_emit_ms": [ne0, ne1], "node_resolve_ms": [nr0, nr1],
+        "emit_over_node": round(be / min(ne0, ne1), 4), "resolve_over_node": round(br / min(nr0, nr1), 4),
+    }
+
+
+def bench_skin_node(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """the whole rlSkin node on the plane z = 0: emit, the one-launch resolve, the stand-alone resolves that exist, the analytic call"""
+    import torch
+    import rlshaders_amd as R
+    from rlshaders_amd import trace as T
+    nl = args.lights
+    sk, P, lights, Ns, Tg, p, dist, mult = skin_batch(args, ctx, n, seed)
+    scene = R.make_scene("plane", light_dir=(0, 0, 1), light_color=(1.0, 1.0, 1.0))
+    keys3, keys1 = ("sheen", "specular", "sss", "out"), ("sheenFresnel", "specularFresnel", "sssWeight")
+    aov = {k: ctx.empty(3, n) for k in keys3}
+    aov.update({k: ctx.empty(n) for k in keys1})
+    ms_int = timed(lambda: sk.integrate(P, scene, spp_n, seed, env=(0.7, 0.8, 0.9), out=aov, lights=lights), args.repeats, args.warmup)
+    nq = T.SkinNodeQueues(ctx, n, nl, spp_n, share_scratch=True)
+    ms_emit = timed(lambda: T.skin_node_rays(sk, P, lights, spp_n, seed, queues=nq), args.repeats, args.warmup)
+    cnt = nq.counts()
+    hc, hP, hN, E, hits = plane_hits(nq.probes)
+    rnd = lambda k: torch.rand(3, max(cnt[k], 1), device=ctx.torch_device)
     planes = [rnd("sheen_shadow"), rnd("specular_shadow"), rnd("sheen_glossy"), rnd("specular_glossy")]
     res = {k: ctx.empty(3, n) for k in keys3}
     res.update({k: ctx.empty(n) for k in keys1})
@@ -493,9 +555,10 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
     ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
-                                          "ggx-bounce", "disney-bounce"), default="ggx")
-    ap.add_argument("--state", choices=("camera", "secondary", "half"), default="camera",
-                    help="ggx-bounce / disney-bounce: every point a camera ray at depth 0, a glossy ray's hit at depth 1, or the two alternating")
+                                          "ggx-bounce", "disney-bounce", "skin-bounce"), default="ggx")
+    ap.add_argument("--state", choices=("camera", "secondary", "half", "diffuse"), default="camera",
+                    help="the bounce closures: every point a camera ray at depth 0, a glossy ray's hit at depth 1, or the two alternating; "
+                         "skin-bounce: or a diffuse ray's hit at depth 1")
     ap.add_argument("--lights", type=int, default=2, help="the light loops: spherical lights, 1..8")
     ap.add_argument("--hit-spp-n", type=int, default=1, help="sss-hits: the light loop at the hits draws hit_spp_n^2 samples a light")
     args = ap.parse_args()
@@ -518,7 +581,7 @@ def main() -> None:
     if args.closure != "ggx":
         rec["closure"] = args.closure
         {"disney": bench_disney, "sss": bench_sss, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
-         "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce}.get(
+         "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
         print(json.dumps(rec), flush=True)
