@@ -573,17 +573,17 @@ class GgxSampler:
                                     1 if traced else 0, int(spp_n), int(seed) & 0xFFFFFFFF, int(first_index), C.byref(o)))
         return out
 
-    def microfacet(self, rx, ry, kernel: int = RLS_KERNEL_VNDF):
+    def microfacet(self, rx, ry, kernel: int = RLS_KERNEL_VNDF, out=None):
         """VNDFKernel::evalSample (src/rlGgx.cpp:63-99) or NDFKernel::evalSample (src/rlGgx.h:33-41)."""
         n, ctx = self.n, self.ctx
-        m = ctx.empty(3, n)
+        m = ctx.empty(3, n) if out is None else out
         check(ctx.lib.rls_ggx_microfacet(ctx.handle, n, C.byref(self.c), kernel, plane(rx, n, "rx"),
                                          plane(ry, n, "ry"), vec3(m, n, "m")))
         return m
 
-    def ndfPdf(self, indir):
+    def ndfPdf(self, indir, out=None):
         n, ctx = self.n, self.ctx
-        pdf = ctx.empty(n)
+        pdf = ctx.empty(n) if out is None else out
         check(ctx.lib.rls_ggx_ndf_pdf(ctx.handle, n, C.byref(self.c), cvec3(indir, n, "indir"), plane(pdf, n, "pdf")))
         return pdf
 
@@ -639,23 +639,23 @@ class DisneySampler:
             raise ValueError("ray_type must be RLS_RAY_DIFFUSE or RLS_RAY_GLOSSY")
         self.mSampleType = ray_type
 
-    def evalSample(self, rx, ry):
+    def evalSample(self, rx, ry, out=None):
         n, ctx = self.n, self.ctx
-        wi = ctx.empty(3, n)
+        wi = ctx.empty(3, n) if out is None else out
         check(ctx.lib.rls_disney_sample(ctx.handle, n, C.byref(self.c), self.mSampleType, plane(rx, n, "rx"),
                                         plane(ry, n, "ry"), vec3(wi, n, "wi")))
         return wi
 
-    def evalBrdf(self, indir):
+    def evalBrdf(self, indir, out=None):
         n, ctx = self.n, self.ctx
-        f = ctx.empty(3, n)
+        f = ctx.empty(3, n) if out is None else out
         check(ctx.lib.rls_disney_eval(ctx.handle, n, C.byref(self.c), self.mSampleType, cvec3(indir, n, "indir"),
                                       rgb(f, n, "f")))
         return f
 
-    def evalPdf(self, indir):
+    def evalPdf(self, indir, out=None):
         n, ctx = self.n, self.ctx
-        pdf = ctx.empty(n)
+        pdf = ctx.empty(n) if out is None else out
         check(ctx.lib.rls_disney_pdf(ctx.handle, n, C.byref(self.c), self.mSampleType, cvec3(indir, n, "indir"),
                                      plane(pdf, n, "pdf")))
         return pdf
@@ -669,25 +669,25 @@ class DisneySampler:
         return wi, f, pdf
 
     # -- alternates the reference compiles but never selects (mSampleFromVisibleNormal = true) -------
-    def altSample(self, kind: int, rx, ry):
+    def altSample(self, kind: int, rx, ry, out=None):
         """kind 0: sampleGTR2AnisoDirection (src/rlDisney.cpp:406-414), 1: sampleGTR2Direction (504-512)."""
         n, ctx = self.n, self.ctx
-        m = ctx.empty(3, n)
+        m = ctx.empty(3, n) if out is None else out
         check(ctx.lib.rls_disney_alt_sample(ctx.handle, n, C.byref(self.c), int(kind), plane(rx, n, "rx"),
                                             plane(ry, n, "ry"), vec3(m, n, "m")))
         return m
 
-    def altPdf(self, indir):
+    def altPdf(self, indir, out=None):
         """evalSpecularPdf with mSampleFromVisibleNormal == false (src/rlDisney.cpp:541-542)."""
         n, ctx = self.n, self.ctx
-        pdf = ctx.empty(n)
+        pdf = ctx.empty(n) if out is None else out
         check(ctx.lib.rls_disney_alt_pdf(ctx.handle, n, C.byref(self.c), cvec3(indir, n, "indir"), plane(pdf, n, "pdf")))
         return pdf
 
-    def dGtr2(self, m):
+    def dGtr2(self, m, out=None):
         """D_GTR2 (src/rlDisney.cpp:553-559)."""
         n, ctx = self.n, self.ctx
-        d = ctx.empty(n)
+        d = ctx.empty(n) if out is None else out
         check(ctx.lib.rls_disney_d_gtr2(ctx.handle, n, C.byref(self.c), cvec3(m, n, "m"), plane(d, n, "d")))
         return d
 
@@ -822,15 +822,15 @@ class NDProfile:
     def getRadius(self, rx):
         return self.sample(rx)[0]
 
-    def getPdf(self, r):
+    def getPdf(self, r, out=None):
         n, ctx = self.n, self.ctx
-        pdf = ctx.empty(n)
+        pdf = ctx.empty(n) if out is None else out
         check(ctx.lib.rls_nd_pdf(ctx.handle, n, C.byref(self.c), plane(r, n, "r"), plane(pdf, n, "pdf")))
         return pdf
 
-    def evalProfile(self, r):
+    def evalProfile(self, r, out=None):
         n, ctx = self.n, self.ctx
-        prof = ctx.empty(3, n)
+        prof = ctx.empty(3, n) if out is None else out
         check(ctx.lib.rls_nd_eval(ctx.handle, n, C.byref(self.c), plane(r, n, "r"), rgb(prof, n, "profile")))
         return prof
 
@@ -844,10 +844,10 @@ class GaussianProfile:
         self._keep = dist_x
         self.p = param(dist_x, self.n, "dist_x")
 
-    def sample(self, rx):
+    def sample(self, rx, out=None):
         """getRadius(rx), getPdf(r), evalProfile(r) -> (r, pdf, profile)"""
         n, ctx = self.n, self.ctx
-        r, pdf, prof = ctx.empty(n), ctx.empty(n), ctx.empty(n)
+        r, pdf, prof = out if out is not None else (ctx.empty(n), ctx.empty(n), ctx.empty(n))
         check(ctx.lib.rls_gaussian_sample(ctx.handle, n, self.p, plane(rx, n, "rx"), plane(r, n, "r"),
                                           plane(pdf, n, "pdf"), plane(prof, n, "profile")))
         return r, pdf, prof
@@ -877,10 +877,10 @@ class SssSampler:
             plane(out["pdf"], n, "pdf"), rgb(out["profile"], n, "profile")))
         return out
 
-    def misPdf(self, disp, sampleN, literal_matrix: bool = False):
+    def misPdf(self, disp, sampleN, literal_matrix: bool = False, out=None):
         """3-axis MIS pdf of a probe hit (src/rlSss.h:246-266)."""
         n, ctx = self.n, self.ctx
-        pdf = ctx.empty(n)
+        pdf = ctx.empty(n) if out is None else out
         check(ctx.lib.rls_sss_mis_pdf(ctx.handle, n, C.byref(self.c), cvec3(disp, n, "disp"),
                                       cvec3(sampleN, n, "sampleN"), 1 if literal_matrix else 0, plane(pdf, n, "pdf")))
         return pdf
@@ -898,19 +898,19 @@ class SssSampler:
         return (result, depth) if want_depth else result
 
     @staticmethod
-    def cavityFade(ctx: Context, disp, sampleN, No):
+    def cavityFade(ctx: Context, disp, sampleN, No, out=None):
         """src/rlSss.h:401-413."""
         n = int(disp.shape[-1])
-        fade = ctx.empty(n)
+        fade = ctx.empty(n) if out is None else out
         check(ctx.lib.rls_sss_cavity_fade(ctx.handle, n, cvec3(disp, n, "disp"), cvec3(sampleN, n, "sampleN"),
                                           cvec3(No, n, "No"), plane(fade, n, "fade")))
         return fade
 
     @staticmethod
-    def sampleDiffuseDirection(ctx: Context, rx, ry, normal, T):
+    def sampleDiffuseDirection(ctx: Context, rx, ry, normal, T, out=None):
         """src/rlSss.h:536-545."""
         n = int(normal.shape[-1])
-        wi = ctx.empty(3, n)
+        wi = ctx.empty(3, n) if out is None else out
         check(ctx.lib.rls_sss_sample_diffuse_direction(ctx.handle, n, cvec3(normal, n, "normal"), cvec3(T, n, "T"),
                                                        plane(rx, n, "rx"), plane(ry, n, "ry"), vec3(wi, n, "wi")))
         return wi
@@ -1050,10 +1050,10 @@ class SkinShader:
 
 
 # ================================================================================================
-def util_reflect_luminance(ctx: Context, i, nrm, color):
+def util_reflect_luminance(ctx: Context, i, nrm, color, out=None):
     """reflectDirection(i, nrm) and colorToLuminance(color) (src/rlUtil.h:31-39) -> ([3,n], [n])"""
     n = int(i.shape[-1])
-    r, lum = ctx.empty(3, n), ctx.empty(n)
+    r, lum = out if out is not None else (ctx.empty(3, n), ctx.empty(n))
     check(ctx.lib.rls_util_reflect_luminance(ctx.handle, n, cvec3(i, n, "i"), cvec3(nrm, n, "nrm"), cvec3(color, n, "color"),
                                              vec3(r, n, "reflected"), plane(lum, n, "luminance")))
     return r, lum
@@ -1098,9 +1098,9 @@ def checksum(ctx: Context, t: torch.Tensor) -> int:
     return int(v.value)
 
 
-def util_directions(ctx: Context, a, b):
+def util_directions(ctx: Context, a, b, out=None):
     n = int(a.shape[0])
-    sph, disk = ctx.empty(3, n), ctx.empty(3, n)
+    sph, disk = out if out is not None else (ctx.empty(3, n), ctx.empty(3, n))
     check(ctx.lib.rls_util_directions(ctx.handle, n, plane(a, n, "a"), plane(b, n, "b"), vec3(sph, n, "spherical"),
                                       vec3(disk, n, "disk")))
     return sph, disk

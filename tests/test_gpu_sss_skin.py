@@ -234,7 +234,8 @@ def test_uniform_scatter_distance_is_hoisted_and_bit_identical(gpu, oracle, mult
     the tile loop and keep NDProfile in scalar registers (sss.hip, uniform_profile) -- the same values as the per-point
     evaluation: radius, pdf, profile, probe ray and MIS pdf equal the oracle's AND the streamed kernel's (the same distances as
     per-point planes) bit for bit, for distances inside, on the borders of and outside the reciprocal window, degenerate ones
-    included."""
+    included.
+    At this n every thread walks at most one tile; the carry-over across tiles is held by test_gpu_pointwise_edges.py."""
     n = 1 << 14
     _, N, T = cases.frame(11, n)
     x = np.stack([oracle.gen_uniform(11, 0, n, oracle.S_XI0 + j) for j in range(2)])
@@ -292,7 +293,8 @@ def test_skin_uniform_parameters_are_hoisted_and_bit_identical(gpu, oracle, case
     """Every parameter one value for the batch: skin_kernel<UNIFORM_ALL> evaluates the parameter-only arithmetic once per thread
     (the lobes' roughness / ior terms, NDProfile::setDistance).  Its 24 outputs equal the oracle's and those of the streamed
     kernel (the same values as per-point planes) bit for bit, with layers switched off, weights on the 1e-4 threshold,
-    degenerate ior / roughness and scatter distances outside the reciprocal window."""
+    degenerate ior / roughness and scatter distances outside the reciprocal window.
+    At this n every thread walks at most one tile; the carry-over across tiles is held by test_gpu_pointwise_edges.py."""
     n = 1 << 14
     wo, N, T = cases.frame(cases.SEED_PARITY, n)
     xi = cases.xi(cases.SEED_PARITY, n, 6)

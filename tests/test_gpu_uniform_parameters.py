@@ -3,7 +3,9 @@ the node parameters that enter parameter-only arithmetic one value for the batch
 texture is linked to it -- that arithmetic runs once per thread ahead of the tile loop and stays in scalar registers.  Colours
 (rlGgx's specColor, rlDisney's base_color) may be per-point planes beside it: the colour-map case.  The results must be the
 per-point evaluation's: every verb is compared bit for bit with the STREAMED kernel given the same values as per-point planes,
-and with the oracle under the gates of the mixed-parameter tests."""
+and with the oracle under the gates of the mixed-parameter tests.
+At these n every thread walks at most one tile: the carry-over of the hoisted values from tile to tile is held by
+test_gpu_pointwise_edges.py."""
 import numpy as np
 import pytest
 import torch
