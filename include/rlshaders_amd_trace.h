@@ -511,8 +511,8 @@ rls_status rls_trace_skin_resolve(rls_context *ctx, int64_t n, const rls_skin_cl
  * gives traced = 0).
  *
  * Per point i, with rt = ray_type[i] (tested with & as the reference tests sg->Rt) and d = *depths:
- *   a point with rt & RLS_RT_SHADOW queues nothing and every output plane is +0 there (the reference returns an opacity, which
- *   stays with the caller, like the opacity branch itself); for every other point, cam = rt & RLS_RT_CAMERA and
+ *   a point with rt & RLS_RT_SHADOW queues nothing and every output plane is +0 there (the reference returns an opacity:
+ *   rls_trace_ggx_opacity / rls_trace_disney_opacity, at the end of this header); for every other point, cam = rt & RLS_RT_CAMERA and
  *
  *   rlGgx     sD = !small(KdColor * Kd) && Rr_diff[i] <= d.diffuse            (sampleDiffuse)
  *             sS = Rr_gloss[i] <= d.glossy
@@ -544,7 +544,8 @@ rls_status rls_trace_skin_resolve(rls_context *ctx, int64_t n, const rls_skin_cl
  * state (n > 0), and for whatever the node calls refuse.  Neither synchronises the host; both can be recorded into an
  * rls_graph.  The state planes are indexed by the point's index in THIS call, like P.
  *
- * Not covered: the opacity branch and the shadow-ray branch of any node.  rls_trace_sss_hits_emit's trace_diffuse
+ * Not covered: AiShaderGlobalsApplyOpacity's own decisions (a closed service: whether a node returns early on its opacity; the
+ * opacity and shadow-ray values themselves are at the end of this header).  rls_trace_sss_hits_emit's trace_diffuse
  * (shouldTraceDiffuse at the probe hits) stays a per-call flag.  rlSkin's bounce calls are below, after the state's types.
  * ---------------------------------------------------------------------------------------- */
 
@@ -597,7 +598,7 @@ rls_status rls_trace_ray_state_advance(rls_context *ctx, int64_t rays, const uin
  * (src/rlSkin.cpp:165-256, src/rlSss.h:170-186, src/rlGgx.h:172-184) change which rays are queued AND the mean-Fresnel
  * hand-down, so sssWeight and every AOV.  Per point i, rt = ray_type[i], d = *depths:
  *   rt & RLS_RT_SHADOW:  the node returns before it shades (:169-172).  No ray in any queue, the probe rays written with
- *                        maxdist = 0, the three scalars and every output plane +0.  The opacity stays with the caller.
+ *                        maxdist = 0, the three scalars and every output plane +0.  The opacity: rls_trace_skin_opacity.
  *   sS = Rr_gloss[i] <= d.glossy (:185) gates both GGX lobes together.  Shut: neither lobe has a shadow ray or a glossy ray;
  *                        sheen = specular = +0 (AI_RGB_BLACK, not 0 * weight); sheenFresnel = specularFresnel = 0, and sssWeight
  *                        is :238 with both at 0.
@@ -657,6 +658,70 @@ rls_status rls_trace_skin_bounce_resolve(rls_context *ctx, int64_t n, const rls_
                                          int literal_matrix, int spp_n, const rls_ray_state *state,
                                          const rls_gi_depths *depths, const rls_skin_bounce_queues *q,
                                          const rls_skin_bounce_traced *t, const rls_skin_integrate_out *out);
+
+/* ------------------------------------------------------------------------------------------
+ * Shadow rays' hits: the opacity each node returns, and the visibility of a shadow ray folded from the opacities of the surfaces
+ * it crosses -- the plane every light-loop and node resolve above reads ("1 - sg->Lo in Arnold's terms").
+ *
+ * sg->out_opacity of the three shader_evaluate, per point i and channel c, every operation rounded to float32 by itself (no
+ * math-mode form: EXACT and FAST contexts write the same bytes).  o = opacity * opacity_color_c (rlGgx, rlSkin) or opacity_c
+ * (rlDisney); clamp(v) = MAX(0, MIN(v, 1)) with MIN(a, b) = a < b ? a : b and MAX(a, b) = a > b ? a : b, so a NaN gives 1 and
+ * -0 stays -0 (AiColorClamp); shadow: ray_type[i] & RLS_RT_SHADOW, ray_type the rls_ray_state.ray_type plane, NULL: no point is a
+ * shadow ray's.
+ *                 a shadow ray's point                                        any other point
+ *   rlGgx         1 - KtColor_c * Kt            (src/rlGgx.cpp:264-268)        clamp(o)   (:250, :326)
+ *   rlDisney      o, NOT clamped                (src/rlDisney.cpp:685-687)     clamp(o)   (:679, :728)
+ *   rlSkin        incoming_c * clamp(o)         (src/rlSkin.cpp:169-172)       clamp(o)   (:167, :255)
+ * rlSkin multiplies into the sg->out_opacity it finds: `incoming`, all three planes or none (none reads as 1); it may alias
+ * out_opacity plane for plane.  The parameters travel like every node parameter: per-point planes, uniform values, or columns
+ * looked up through materials (entry min(id[i], count - 1)).
+ *
+ * AiShaderGlobalsApplyOpacity (src/rlGgx.cpp:252, src/rlDisney.cpp:681) is a closed service and stays the renderer's: whether a
+ * point is skipped, made stochastically transparent or ends its shadow ray on the opacity is decided there, before any of the
+ * values above is formed.  A caller whose service ends shadow rays itself passes those hits WITHOUT the shadow bit: they then
+ * take the clamp(o) column, the opacity the service was handed.
+ *
+ * rls_trace_shadow_visibility, per shadow ray j < rays and channel c:
+ *     T = base ? base_c[j] : 1;   for k = 0 .. min(count[j], max_hits) - 1, in order:  T = T * (1 - o_c(e)),  e = k * stride + j;
+ *     visibility_c[j] = T
+ * with o_c(e) = opacity_c[e], or opacity_c[min(index[e], table_count - 1)] where index is given (a table of out_opacity values,
+ * one per distinct surface, e.g. what an opacity call wrote for table_count points).  No clamp and no early exit: a non-finite
+ * opacity propagates as IEEE arithmetic gives it, and an opacity outside [0, 1] -- rlDisney's shadow branch is not clamped, and
+ * rlGgx's 1 - KtColor * Kt leaves [0, 1] with KtColor * Kt -- gives a factor outside [0, 1]: bounding it is the renderer's job.  A
+ * ray with no hit gets base, or 1.  base: all three planes or none; it may alias visibility plane for plane.  Nothing is written
+ * at j >= rays.  The result is what rls_trace_*_direct_resolve, the node resolves and rls_trace_sss_hits_resolve take as
+ * visibility.
+ *
+ * All four: n == 0 / rays == 0 launches nothing; never synchronise the host; can be recorded into an rls_graph.  Refused with
+ * RLS_ERR_INVALID_ARGUMENT before the context is read: a NULL struct; a NULL or partly NULL output plane set; a partly NULL
+ * incoming / base / rgb parameter; materials.id set with materials.count == 0; n < 0 / rays < 0; max_hits outside 1 .. 255;
+ * stride < rays; a NULL count or opacity plane; index set with table_count == 0.
+ * ---------------------------------------------------------------------------------------- */
+
+typedef struct rls_ggx_opacity    { rls_param opacity; rls_param_rgb opacity_color, KtColor; rls_param Kt;
+                                    rls_material_index materials; } rls_ggx_opacity;
+typedef struct rls_disney_opacity { rls_param_rgb opacity; rls_material_index materials; } rls_disney_opacity;
+typedef struct rls_skin_opacity   { rls_param opacity; rls_param_rgb opacity_color;
+                                    rls_material_index materials; } rls_skin_opacity;
+
+rls_status rls_trace_ggx_opacity(rls_context *ctx, int64_t n, const rls_ggx_opacity *p, const uint8_t *ray_type,
+                                 rls_rgb out_opacity);
+rls_status rls_trace_disney_opacity(rls_context *ctx, int64_t n, const rls_disney_opacity *p, const uint8_t *ray_type,
+                                    rls_rgb out_opacity);
+rls_status rls_trace_skin_opacity(rls_context *ctx, int64_t n, const rls_skin_opacity *p, const uint8_t *ray_type,
+                                  rls_crgb incoming, rls_rgb out_opacity);
+
+typedef struct rls_shadow_hits {
+    int max_hits;            /* 1 .. 255: hit slots per shadow ray */
+    int64_t stride;          /* >= rays: hit k of ray j is element e = k * stride + j */
+    const uint8_t *count;    /* [rays], required; values above max_hits read as max_hits */
+    rls_crgb opacity;        /* required: out_opacity per element (index == NULL), or a table of table_count entries */
+    const uint32_t *index;   /* NULL-able: [max_hits * stride]; element e reads entry min(index[e], table_count - 1) */
+    uint32_t table_count;    /* read only with index; >= 1 */
+} rls_shadow_hits;
+
+rls_status rls_trace_shadow_visibility(rls_context *ctx, int64_t rays, const rls_shadow_hits *h, rls_crgb base,
+                                       rls_rgb visibility);
 
 #ifdef __cplusplus
 }

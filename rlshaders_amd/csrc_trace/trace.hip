@@ -12,6 +12,8 @@
 // The whole nodes have a second pair of verbs for the hits of secondary rays (rls_trace_*_bounce_*): the same checks and steps
 // (ggx_node_emit, ggx_node_resolve, disney_node_emit, disney_node_resolve, skin_node_emit, skin_node_resolve) with the
 // per-point ray state and the kernels that read it; rlSkin's has a sixth queue, integrateScatter's light loop at diffuse rays.
+// The visibility the light loops' resolves read has four verbs of its own at the end of this file (rls_trace_opacity.hpp): the
+// opacity each node returns at a shadow ray's hit, and the fold of a ray's hits into its visibility.
 //
 // Built twice like the closure units of librlshaders_amd.so (rlshaders_amd/build.py, build_trace_library): RLS_FAST=0
 // carries the C ABI, the EXACT emit kernels and the mode-free scan / compact / resolve kernels; RLS_FAST=1 the FAST emit
@@ -30,6 +32,7 @@ namespace {
 #include "rls_trace_queue.hpp"
 #include "rls_trace_node_resolve.hpp"
 #include "rls_trace_hits.hpp"
+#include "rls_trace_opacity.hpp"
 
 // one launch of the rlSss emit or resolve: a workgroup per tile of io.tile_points points, grid-striding past the cap
 template <class IO>
@@ -1317,6 +1320,91 @@ rls_status rls_trace_sss_hits_resolve(rls_context *ctx, const rls_probe_hits *h,
     io.E = E; io.n = hq->hit_capacity;
     hipLaunchKernelGGL(sss_hits_resolve_kernel, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
     return rlsh::check_launch(fn);
+}
+
+} // extern "C"
+
+// ---- shadow rays' hits: the nodes' opacity and the fold into a visibility (rls_trace_opacity.hpp) ---------------------------
+namespace {
+
+// what the three opacity verbs check of their arguments ahead of the n == 0 return (the struct's own members: the caller), and
+// after it
+rls_status check_opacity(const char *fn, const rls_context *ctx, int64_t n, bool have_params)
+{
+    RLS_REQUIRE_IN(fn, ctx != nullptr, "ctx is NULL");
+    if (rls_status s = check_n(fn, n)) return s;
+    RLS_REQUIRE_IN(fn, have_params, "params is NULL");
+    return RLS_OK;
+}
+rls_status check_opacity_params(const char *fn, std::initializer_list<const rls_param_rgb *> colours, const rls_material_index &m)
+{
+    for (const rls_param_rgb *c : colours) RLS_REQUIRE_IN(fn, rlsh::ok_rgb(*c), "colour planes must be all set or all NULL");
+    RLS_REQUIRE_IN(fn, rlsh::ok_materials(m), "materials.id is set but materials.count is 0");
+    return RLS_OK;
+}
+inline bool all_or_none(rls_crgb v) { return (v.r && v.g && v.b) || (!v.r && !v.g && !v.b); }
+
+template <class IO>
+rls_status launch_opacity(rls_context *ctx, void (*kernel)(IO), const IO &io, const char *name)
+{
+    hipLaunchKernelGGL(kernel, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(name);
+}
+
+} // namespace
+
+extern "C" {
+
+rls_status rls_trace_ggx_opacity(rls_context *ctx, int64_t n, const rls_ggx_opacity *p, const uint8_t *ray_type,
+                                 rls_rgb out_opacity)
+{
+    if (rls_status s = check_opacity(__func__, ctx, n, p != nullptr)) return s;
+    if (rls_status s = check_opacity_params(__func__, { &p->opacity_color, &p->KtColor }, p->materials)) return s;
+    if (n == 0) return RLS_OK;
+    RLS_REQUIRE(rlsh::has3(out_opacity), "NULL output plane");
+    const GgxOpacityIO io = { *p, ray_type, out_opacity, n };
+    return launch_opacity(ctx, ggx_opacity_kernel, io, __func__);
+}
+
+rls_status rls_trace_disney_opacity(rls_context *ctx, int64_t n, const rls_disney_opacity *p, const uint8_t *ray_type,
+                                    rls_rgb out_opacity)
+{
+    if (rls_status s = check_opacity(__func__, ctx, n, p != nullptr)) return s;
+    if (rls_status s = check_opacity_params(__func__, { &p->opacity }, p->materials)) return s;
+    if (n == 0) return RLS_OK;
+    RLS_REQUIRE(rlsh::has3(out_opacity), "NULL output plane");
+    const DisneyOpacityIO io = { *p, ray_type, out_opacity, n };
+    return launch_opacity(ctx, disney_opacity_kernel, io, __func__);
+}
+
+rls_status rls_trace_skin_opacity(rls_context *ctx, int64_t n, const rls_skin_opacity *p, const uint8_t *ray_type,
+                                  rls_crgb incoming, rls_rgb out_opacity)
+{
+    if (rls_status s = check_opacity(__func__, ctx, n, p != nullptr)) return s;
+    if (rls_status s = check_opacity_params(__func__, { &p->opacity_color }, p->materials)) return s;
+    RLS_REQUIRE(all_or_none(incoming), "incoming planes must be all set or all NULL");
+    if (n == 0) return RLS_OK;
+    RLS_REQUIRE(rlsh::has3(out_opacity), "NULL output plane");
+    const SkinOpacityIO io = { *p, ray_type, incoming, out_opacity, n };
+    return launch_opacity(ctx, skin_opacity_kernel, io, __func__);
+}
+
+rls_status rls_trace_shadow_visibility(rls_context *ctx, int64_t rays, const rls_shadow_hits *h, rls_crgb base,
+                                       rls_rgb visibility)
+{
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE(rays >= 0, "rays < 0");
+    RLS_REQUIRE(h != nullptr, "hits is NULL");
+    RLS_REQUIRE(h->max_hits >= 1 && h->max_hits <= 255, "hits.max_hits must be in [1, 255]");
+    RLS_REQUIRE(h->stride >= rays, "hits.stride < rays");
+    RLS_REQUIRE(h->index == nullptr || h->table_count > 0, "hits.index is set but hits.table_count is 0");
+    RLS_REQUIRE(all_or_none(base), "base planes must be all set or all NULL");
+    if (rays == 0) return RLS_OK;
+    RLS_REQUIRE(h->count != nullptr && h->opacity.r && h->opacity.g && h->opacity.b, "hits.count or hits.opacity plane is NULL");
+    RLS_REQUIRE(rlsh::has3(visibility), "NULL output plane");
+    const ShadowFoldIO io = { *h, base, visibility, rays };
+    hipLaunchKernelGGL(shadow_visibility_kernel, rlsh::grid_for(ctx, rays), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(__func__);
 }
 
 } // extern "C"

@@ -34,6 +34,10 @@
 //     rlsb::emitBounce(dev, ggx, shader, P, lights, n_lights, n, spp_n, seed, state.c(), depths, nq);
 //     rlsb::resolveBounce(dev, ggx, shader, lights, n_lights, state.c(), depths, nq, visibility, Lglossy, Lrefract, Ldiffuse, aovs, &out);
 //     rlsb::advanceState(dev, rays, nq.glossy().c().point, state.c(), RLS_RT_GLOSSY, child);   // the state of those rays' hits
+// The visibility of shadow rays from the opacities of the surfaces they cross (the nodes' opacity and shadow-ray branches):
+//     rlsb::ggxOpacity(dev, sheet, m, hitState.c().ray_type, table.rgb());  // sg->out_opacity of m surfaces (also disney-, skinOpacity)
+//     rlsb::ShadowHits hits(dev, rays, maxHits, rlsb::ShadowHits::Indexed); // the tracer fills hits.count() and hits.index()
+//     rlsb::foldVisibility(dev, rays, hits.c(table, m), rlsb::Planes(), visibility);   // -> resolveDirect / resolveNode
 // Nothing here synchronises the host except RayQueue::count() and ShadowQueue::count() (they read offsets[n]).
 #pragma once
 
@@ -818,6 +822,99 @@ inline void resolveBounce(const Device &d, const rls_skin_closure &c, const Plan
     if (out) o.out = out->rgb();
     check(rls_trace_skin_bounce_resolve(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights,
                                         cavityFade ? 1 : 0, literalMatrix ? 1 : 0, q.sppN(), &state, &depths, &q.c(), &t, &o));
+}
+
+// sg->out_opacity of the three nodes at n points (rls_trace_ggx_opacity / _disney_opacity / _skin_opacity): rayType: the state's
+// ray_type plane (RayState::c().ray_type) or nullptr, no point being a shadow ray's; outOpacity: 3 planes of n floats
+// (Planes::rgb(), or planes inside a longer table).  rlSkin: incoming, the sg->out_opacity the node found, an empty Planes reading
+// as 1; it may hold outOpacity's planes.
+inline void ggxOpacity(const Device &d, const rls_ggx_opacity &p, int64_t n, const uint8_t *rayType, const rls_rgb &outOpacity)
+{
+    check(rls_trace_ggx_opacity(d.ctx(), n, &p, rayType, outOpacity));
+}
+inline void disneyOpacity(const Device &d, const rls_disney_opacity &p, int64_t n, const uint8_t *rayType,
+                          const rls_rgb &outOpacity)
+{
+    check(rls_trace_disney_opacity(d.ctx(), n, &p, rayType, outOpacity));
+}
+inline void skinOpacity(const Device &d, const rls_skin_opacity &p, int64_t n, const uint8_t *rayType, const Planes &incoming,
+                        const rls_rgb &outOpacity)
+{
+    check(rls_trace_skin_opacity(d.ctx(), n, &p, rayType, detail::crgb(incoming), outOpacity));
+}
+
+// The hits of `rays` shadow rays (rls_shadow_hits) in device buffers of its own: count [rays] and, per element k * rays + j
+// (stride = rays), either the hit's out_opacity (Direct: opacity() is 3 planes of maxHits * rays floats) or the index of its
+// surface in a caller's table of out_opacity values (Indexed: index(), maxHits * rays entries; the table, 3 planes of tableCount
+// floats -- what an opacity call wrote for tableCount surfaces -- is passed to c()).  The caller's tracer fills them.
+class ShadowHits {
+public:
+    enum Form { Direct, Indexed };
+
+    ShadowHits(const Device &d, int64_t rays, int maxHits, Form form) : dev_(&d), rays_(rays), max_hits_(maxHits), form_(form)
+    {
+        const size_t elements = (size_t)rays * (size_t)maxHits;
+        try {
+            count_ = static_cast<uint8_t *>(alloc((size_t)rays));
+            if (form == Direct) opacity_ = static_cast<float *>(alloc(3 * elements * sizeof(float)));
+            else index_ = static_cast<uint32_t *>(alloc(elements * sizeof(uint32_t)));
+        } catch (...) {
+            release();
+            throw;
+        }
+    }
+    ~ShadowHits() { release(); }
+    ShadowHits(const ShadowHits &) = delete;
+    ShadowHits &operator=(const ShadowHits &) = delete;
+
+    int64_t rays() const { return rays_; }
+    int maxHits() const { return max_hits_; }
+    uint8_t *count() const { return count_; }
+    float *opacity(int channel) const { return opacity_ + (size_t)channel * (size_t)rays_ * (size_t)max_hits_; }
+    uint32_t *index() const { return index_; }
+    // Direct
+    rls_shadow_hits c() const
+    {
+        if (form_ != Direct) throw Error(RLS_ERR_INVALID_ARGUMENT, "ShadowHits::c: indexed hits need their table");
+        return rls_shadow_hits{max_hits_, rays_, count_, rls_crgb{opacity(0), opacity(1), opacity(2)}, nullptr, 0u};
+    }
+    // Indexed: table: 3 planes of tableCount floats
+    rls_shadow_hits c(const Planes &table, uint32_t tableCount) const
+    {
+        if (form_ != Indexed) throw Error(RLS_ERR_INVALID_ARGUMENT, "ShadowHits::c: direct hits take no table");
+        return rls_shadow_hits{max_hits_, rays_, count_, detail::crgb(table), index_, tableCount};
+    }
+
+private:
+    void release()
+    {
+        for (int k = 0; k < nbufs_; k++) rls_device_free(dev_->ctx(), bufs_[k]);
+        nbufs_ = 0;
+    }
+    void *alloc(size_t bytes)
+    {
+        void *p = nullptr;
+        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
+        bufs_[nbufs_++] = p;
+        return p;
+    }
+
+    const Device *dev_;
+    int64_t rays_;
+    int max_hits_;
+    Form form_;
+    uint8_t *count_ = nullptr;
+    float *opacity_ = nullptr;
+    uint32_t *index_ = nullptr;
+    void *bufs_[2] = {};
+    int nbufs_ = 0;
+};
+
+// the visibility of the shadow rays from their hits' opacities (rls_trace_shadow_visibility): base (an empty Planes: 1) times
+// (1 - opacity) of every hit, in hit order; visibility: 3 planes of >= rays floats, what resolveDirect and the node resolves take
+inline void foldVisibility(const Device &d, int64_t rays, const rls_shadow_hits &hits, const Planes &base, Planes &visibility)
+{
+    check(rls_trace_shadow_visibility(d.ctx(), rays, &hits, detail::crgb(base), visibility.rgb()));
 }
 
 } // namespace rlsb

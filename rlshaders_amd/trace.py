@@ -33,6 +33,9 @@ or of one rlDisney lobe, trace them with your own tracer, resolve the radiance; 
     kq = trace.skin_bounce_rays(skin, P, lights, 4, 7, st, depths=(8, 2, 2, 4))             # SkinBounceQueues: + diffuse_shadow
     aov = kq.resolve(vis_a, vis_b, La, Lb, cnt, hP, hN, E, diffuse_visibility=vis_d)        # rlSkin under that state
 
+    o = trace.ggx_opacity(ctx, m, KtColor=tint, Kt=0.5, ray_type=hit_state)                 # sg->out_opacity at shadow rays' hits
+    vis = trace.shadow_visibility(ctx, s.count, trace.ShadowHits(cnt, o, max_hits, index=hit_surface))   # -> s.resolve(vis)
+
 ``count`` is read from the device once (it synchronises); everything else stays asynchronous on the context's stream, so
 ``glossy_rays(..., queue=q)`` / ``q.resolve(L, out=...)`` with preallocated tensors can be recorded by ``ctx.capture()``.
 """
@@ -47,7 +50,8 @@ import torch
 
 from . import _capi as capi
 from ._capi import RLS_RAY_DIFFUSE, RLS_RAY_GLOSSY, check
-from .closures import DisneySampler, GgxSampler, SssSampler, cvec3, light_array, param, param_rgb, plane, rgb
+from .closures import (DisneySampler, GgxSampler, SssSampler, cvec3, light_array, material_index, param, param_rgb, plane,
+                       rgb)
 
 TRACE_LIB_PATH = capi._PKG / "lib" / "librls_trace.so"
 
@@ -170,6 +174,28 @@ class SkinBounceTraced_(C.Structure):
     _fields_ = [("node", SkinNodeTraced_), ("diffuse_visibility", capi.CRgb)]
 
 
+class GgxOpacity_(C.Structure):
+    """rls_ggx_opacity"""
+    _fields_ = [("opacity", capi.Param), ("opacity_color", capi.ParamRgb), ("KtColor", capi.ParamRgb), ("Kt", capi.Param),
+                ("materials", capi.MaterialIndex)]
+
+
+class DisneyOpacity_(C.Structure):
+    """rls_disney_opacity"""
+    _fields_ = [("opacity", capi.ParamRgb), ("materials", capi.MaterialIndex)]
+
+
+class SkinOpacity_(C.Structure):
+    """rls_skin_opacity"""
+    _fields_ = [("opacity", capi.Param), ("opacity_color", capi.ParamRgb), ("materials", capi.MaterialIndex)]
+
+
+class ShadowHits_(C.Structure):
+    """rls_shadow_hits"""
+    _fields_ = [("max_hits", C.c_int), ("stride", C.c_int64), ("count", C.c_void_p), ("opacity", capi.CRgb),
+                ("index", C.c_void_p), ("table_count", C.c_uint32)]
+
+
 PROTOTYPES = {
     "rls_trace_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
     "rls_trace_ggx_glossy_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
@@ -229,6 +255,10 @@ PROTOTYPES = {
     "rls_trace_skin_bounce_resolve": (C.c_int, [_ctx, _i64, C.POINTER(capi.SkinClosure), capi.CVec3, _lights, C.c_int, C.c_int,
                                                 C.c_int, C.c_int, _state, _depths, C.POINTER(SkinBounceQueues_),
                                                 C.POINTER(SkinBounceTraced_), C.POINTER(capi.SkinIntegrateOut)]),
+    "rls_trace_ggx_opacity": (C.c_int, [_ctx, _i64, C.POINTER(GgxOpacity_), _vp, capi.Rgb]),
+    "rls_trace_disney_opacity": (C.c_int, [_ctx, _i64, C.POINTER(DisneyOpacity_), _vp, capi.Rgb]),
+    "rls_trace_skin_opacity": (C.c_int, [_ctx, _i64, C.POINTER(SkinOpacity_), _vp, capi.CRgb, capi.Rgb]),
+    "rls_trace_shadow_visibility": (C.c_int, [_ctx, _i64, C.POINTER(ShadowHits_), capi.CRgb, capi.Rgb]),
 }
 
 _lib = None
@@ -1217,3 +1247,113 @@ def skin_bounce_rays(shader, P: torch.Tensor, lights, spp_n: int, seed: int, sta
     bounce resolve."""
     return _node_emit(SkinBounceQueues, shader, None, P, lights, spp_n, seed, first_index, queues, share_scratch,
                       state=(state, depths))
+
+
+# ---------------------------------------------------------------------------------------------
+# Shadow rays' hits: the opacity each node returns and the fold of the opacities along a shadow ray into a visibility
+
+
+def _ray_type(ray_type, n: int):
+    """the rls_ray_state.ray_type plane of n points: None (no point is a shadow ray's), a uint8 CUDA tensor [n] or a RayState"""
+    if ray_type is None:
+        return None
+    t = ray_type.ray_type if isinstance(ray_type, RayState) else ray_type
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 1 or t.shape[0] < n or \
+            not t.is_contiguous():
+        raise TypeError(f"ray_type: expected a contiguous uint8 CUDA tensor [>= {n}] or a RayState")
+    return t.data_ptr() if n > 0 else None
+
+
+def ggx_opacity(ctx, n: int, opacity=1.0, opacity_color=(1.0, 1.0, 1.0), KtColor=(1.0, 1.0, 1.0), Kt=0.0, ray_type=None,
+                materials=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sg->out_opacity of rlGgx at n points (rls_trace_ggx_opacity) -> [3, n]: at a shadow ray's point (``ray_type`` &
+    RLS_RT_SHADOW) 1 - KtColor * Kt (src/rlGgx.cpp:264-268), at any other clamp(opacity * opacity_color, 0, 1) (:250, :326).
+    The parameters are numbers or CUDA tensors like the samplers': per-point [n] / [3, n], or with ``materials`` = (ids, count)
+    per-material columns.  ``ray_type``: None, a uint8 tensor [n] or a ``RayState``."""
+    n = int(n)
+    m, pn = material_index(materials, n)
+    p = GgxOpacity_(param(opacity, pn, "opacity"), param_rgb(opacity_color, pn, "opacity_color"),
+                    param_rgb(KtColor, pn, "KtColor"), param(Kt, pn, "Kt"), m)
+    res = ctx.empty(3, n) if out is None else out
+    check(load().rls_trace_ggx_opacity(ctx.handle, n, C.byref(p), _ray_type(ray_type, n), rgb(res, n, "out_opacity")))
+    return res
+
+
+def disney_opacity(ctx, n: int, opacity=(1.0, 1.0, 1.0), ray_type=None, materials=None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sg->out_opacity of rlDisney (rls_trace_disney_opacity) -> [3, n]: at a shadow ray's point the opacity as it is, NOT
+    clamped (src/rlDisney.cpp:685-687), at any other clamp(opacity, 0, 1) (:728)."""
+    n = int(n)
+    m, pn = material_index(materials, n)
+    p = DisneyOpacity_(param_rgb(opacity, pn, "opacity"), m)
+    res = ctx.empty(3, n) if out is None else out
+    check(load().rls_trace_disney_opacity(ctx.handle, n, C.byref(p), _ray_type(ray_type, n), rgb(res, n, "out_opacity")))
+    return res
+
+
+def skin_opacity(ctx, n: int, opacity=1.0, opacity_color=(1.0, 1.0, 1.0), ray_type=None, materials=None,
+                 incoming: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sg->out_opacity of rlSkin (rls_trace_skin_opacity) -> [3, n]: clamp(opacity * opacity_color, 0, 1) (src/rlSkin.cpp:167,
+    :255), at a shadow ray's point multiplied into the sg->out_opacity the node found (:169-172): ``incoming`` [3, n], None
+    reading as 1; it may be ``out``."""
+    n = int(n)
+    m, pn = material_index(materials, n)
+    p = SkinOpacity_(param(opacity, pn, "opacity"), param_rgb(opacity_color, pn, "opacity_color"), m)
+    res = ctx.empty(3, n) if out is None else out
+    inc = capi.CRgb(None, None, None) if incoming is None or n == 0 else _radiance(incoming, n, "incoming")
+    check(load().rls_trace_skin_opacity(ctx.handle, n, C.byref(p), _ray_type(ray_type, n), inc, rgb(res, n, "out_opacity")))
+    return res
+
+
+class ShadowHits:
+    """The hits of shadow rays as rls_shadow_hits: hit k of ray j is element k * stride + j.
+    count: uint8 CUDA [>= rays], the hits of every ray (values above max_hits read as max_hits).
+    opacity, without ``index``: float32 CUDA [3, max_hits, stride] (or [3, max_hits * stride] with ``stride`` given), out_opacity
+    per element; with ``index``: a table [3, table_count], and index an int32 / uint32 CUDA tensor [max_hits, stride] (or
+    [max_hits * stride] with ``stride`` given) whose entries pick the table's column (clamped to the last)."""
+
+    def __init__(self, count: torch.Tensor, opacity: torch.Tensor, max_hits: int, stride: Optional[int] = None,
+                 index: Optional[torch.Tensor] = None):
+        max_hits = int(max_hits)
+        if not 1 <= max_hits <= 255:
+            raise ValueError("max_hits must be in 1 .. 255")
+        if not isinstance(count, torch.Tensor) or count.dtype != torch.uint8 or not count.is_cuda or count.dim() != 1 or \
+                not count.is_contiguous():
+            raise TypeError("count: expected a contiguous uint8 CUDA tensor [rays]")
+        elements = index if index is not None else opacity
+        lead = 0 if index is not None else 1
+        if not isinstance(elements, torch.Tensor) or not elements.is_cuda or not elements.is_contiguous():
+            raise TypeError("opacity / index: expected contiguous CUDA tensors")
+        if elements.dim() == lead + 2:
+            if elements.shape[lead] != max_hits or (stride is not None and int(stride) != elements.shape[lead + 1]):
+                raise ValueError("opacity / index: expected [.., max_hits, stride]")
+            stride = int(elements.shape[lead + 1])
+        elif elements.dim() != lead + 1 or stride is None or elements.shape[lead] < max_hits * int(stride):
+            raise ValueError("opacity / index: expected [.., max_hits, stride], or [.., >= max_hits * stride] with stride given")
+        if not isinstance(opacity, torch.Tensor) or opacity.dtype != torch.float32 or not opacity.is_cuda or \
+                opacity.shape[0] != 3 or not opacity.is_contiguous():
+            raise TypeError("opacity: expected a contiguous float32 CUDA tensor of 3 planes")
+        if index is not None and (index.dtype not in (torch.int32, torch.uint32) or opacity.dim() != 2 or opacity.shape[1] < 1):
+            raise TypeError("index: expected an int32 CUDA tensor beside an opacity table [3, table_count >= 1]")
+        self.count, self.opacity, self.index, self.max_hits, self.stride = count, opacity, index, max_hits, int(stride)
+        h = ShadowHits_()
+        h.max_hits, h.stride, h.count = self.max_hits, self.stride, count.data_ptr()
+        planes = opacity.reshape(3, -1)
+        h.opacity = capi.CRgb(*[planes[k].data_ptr() for k in range(3)])
+        if index is not None:
+            h.index, h.table_count = index.data_ptr(), int(opacity.shape[1])
+        self.h = h
+
+
+def shadow_visibility(ctx, rays: int, hits: ShadowHits, base: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The visibility of ``rays`` shadow rays from the opacities of their hits (rls_trace_shadow_visibility) -> [3, rays]: per
+    ray and channel base (None: 1) times (1 - opacity) of every hit, in hit order; no clamp.  What ``ShadowQueue.resolve``, the
+    node queues' ``.resolve`` and ``HitQueues.resolve`` take as visibility.  ``base`` [3, >= rays] may be ``out``."""
+    rays = int(rays)
+    if hits.stride < rays or hits.count.shape[0] < rays:
+        raise ValueError(f"hits: stride {hits.stride} / count [{hits.count.shape[0]}] below {rays} rays")
+    res = ctx.empty(3, rays) if out is None else out
+    b = capi.CRgb(None, None, None) if base is None or rays == 0 else _radiance(base, rays, "base")
+    check(load().rls_trace_shadow_visibility(ctx.handle, rays, C.byref(hits.h), b, rgb(res, rays, "visibility")))
+    return res

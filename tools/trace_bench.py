@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
+    python tools/trace_bench.py [--closure ggx|disney|sss|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce|shadow-fold] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -49,6 +49,10 @@ resolve, and there is no compose kernel for this node: `separate_partial_ms` is 
 --state (`camera`: the node call's rays and an empty diffuse_shadow; `secondary`: every point a glossy ray's hit at depth 1, no
 glossy rays; `half`: the two alternating; `diffuse`: every point a diffuse ray's hit, the Oren-Nayar light loop in place of the
 probe walk), the node call beside it in the same process as for the other two nodes.
+--closure shadow-fold: rls_trace_shadow_visibility (trace.shadow_visibility) over 2^log2n shadow rays at max_hits 4, counts
+uniform in 0 .. 4, stride = rays, uniform random opacities, no base: `direct` (an opacity per element) and `indexed` (an index
+per element into a table of 4096 surfaces).  Bytes, direct: 1 (count) + 12 per hit read, 12 written per ray; indexed: 1 +
+(4 (index) + 12 (the table's entry, from cache)) per hit read, 12 written per ray.  --spp-n is not read.
 """
 from __future__ import annotations
 
@@ -547,6 +551,34 @@ def bench_skin_node(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None
     }
 
 
+def bench_shadow_fold(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """the fold of the hits' opacities into the shadow rays' visibility, direct and indexed (module docstring)"""
+    import torch
+    from rlshaders_amd import trace as T
+    dev, max_hits, table_count = ctx.torch_device, 4, 4096
+    g = torch.Generator(device=dev).manual_seed(seed)
+    count = torch.randint(0, max_hits + 1, (n,), generator=g, device=dev).to(torch.uint8)
+    hits = int(count.sum(dtype=torch.int64).item())
+    out = ctx.empty(3, n)
+    rec.update({"rays": n, "max_hits": max_hits, "hits": hits, "hits_per_ray": round(hits / n, 4)})
+    for form in ("direct", "indexed"):
+        if form == "direct":
+            opacity, index = torch.rand(3, max_hits, n, generator=g, device=dev), None
+            bytes_ = n * (1 + 12) + hits * 12
+        else:
+            opacity = torch.rand(3, table_count, generator=g, device=dev)
+            index = torch.randint(0, table_count, (max_hits, n), generator=g, device=dev, dtype=torch.int32)
+            bytes_ = n * (1 + 12) + hits * (4 + 12)
+        h = T.ShadowHits(count, opacity, max_hits, index=index)
+        ms = timed(lambda: T.shadow_visibility(ctx, n, h, out=out), args.repeats, args.warmup)
+        rec[form] = {"ms": round(ms, 4), "bytes": bytes_, "rays_per_s": round(n / (ms * 1e-3), 1), "tb_per_s": rate(bytes_, ms),
+                     "frac_of_8tbps": round(rate(bytes_, ms) / HBM_TBPS, 4)}
+        if index is not None:
+            rec[form]["table_count"] = table_count
+        del h, opacity, index
+        torch.cuda.empty_cache()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=24)
@@ -555,7 +587,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
     ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
-                                          "ggx-bounce", "disney-bounce", "skin-bounce"), default="ggx")
+                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold"), default="ggx")
     ap.add_argument("--state", choices=("camera", "secondary", "half", "diffuse"), default="camera",
                     help="the bounce closures: every point a camera ray at depth 0, a glossy ray's hit at depth 1, or the two alternating; "
                          "skin-bounce: or a diffuse ray's hit at depth 1")
@@ -581,7 +613,8 @@ def main() -> None:
     if args.closure != "ggx":
         rec["closure"] = args.closure
         {"disney": bench_disney, "sss": bench_sss, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
-         "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce}.get(
+         "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce,
+         "shadow-fold": bench_shadow_fold}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
         print(json.dumps(rec), flush=True)
