@@ -7,11 +7,15 @@
 // Emit, three steps on the context's stream: the closure's emit kernel (every sample staged, the per-point counts to
 // offsets), the scan of the counts, the compaction into the queue.  The sample-ray emits (run_ray_emit) and the light loops'
 // (run_shadow_emit) share the staging's carve (staging) and the scan (scan_counts); the probe emits write a dense queue.
+// compact_rays is the sample-ray compaction, also of the hit list's diffuse queue.
 // Resolve: one launch per verb; a whole node's walks every queue of the node and composes the AOVs in registers.
 //
 // The whole nodes have a second pair of verbs for the hits of secondary rays (rls_trace_*_bounce_*): the same checks and steps
 // (ggx_node_emit, ggx_node_resolve, disney_node_emit, disney_node_resolve, skin_node_emit, skin_node_resolve) with the
-// per-point ray state and the kernels that read it; rlSkin's has a sixth queue, integrateScatter's light loop at diffuse rays.
+// per-point ray state and the kernels that read it -- an emit names each queue once, node_ray_emit / node_shadow_emit picking
+// the kernel; rlSkin's has a sixth queue, integrateScatter's light loop at diffuse rays.  That queue and the one of rlSss's
+// probe-hit shading are one shape, written once: check_hit_list_queue, set_hit_list_staging, compact_hit_list,
+// hit_list_resolve_io.
 // The visibility the light loops' resolves read has four verbs of its own at the end of this file (rls_trace_opacity.hpp): the
 // opacity each node returns at a shadow ray's hit, and the fold of a ray's hits into its visibility.
 //
@@ -42,17 +46,31 @@ rls_status launch_tiles(rls_context *ctx, void (*kernel)(IO), const IO &io, cons
     hipLaunchKernelGGL(kernel, grid, dim3(rlsh::kBlock), 0, ctx->stream, io);
     return rlsh::check_launch(name, RLS_FAST);
 }
+// one launch of a kernel that takes a lane per point of io.n
+template <class IO>
+rls_status launch_points(rls_context *ctx, void (*kernel)(IO), const IO &io, const char *name)
+{
+    hipLaunchKernelGGL(kernel, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(name, RLS_FAST);
+}
 
 } // namespace
 
 // The kernel selection of each verb (rls_internal.hpp, RLS_FLAVOURS), the verbs in the order of their first use: a code object
 // holds its kernels in that order (csrc/sss.hip).  RLS_TRACE_G_VERB: a verb whose kernels are <verb>_kernel<G>, chosen by the
-// lane group g; the probe verbs and rlSkin's resolve, chosen by nothing, are written out.
+// lane group g; RLS_TRACE_TILE_VERB, RLS_TRACE_POINT_VERB: the probe verbs and rlSkin's resolve, one kernel chosen by nothing,
+// launched by launch_tiles and launch_points.
 #define RLS_TRACE_G_VERB(verb, IO)                                                                            \
     static rls_status launch_##verb(rls_context *ctx, int g, const IO &io, const char *name)                  \
     {                                                                                                         \
         return launch_g(ctx, RLS_G_FAMILY(verb##_kernel), g, io, name);                                       \
     }                                                                                                         \
+    RLS_FLAVOURS(verb, IO)
+#define RLS_TRACE_TILE_VERB(verb, IO)                                                                         \
+    static rls_status launch_##verb(rls_context *ctx, int, const IO &io, const char *name) { return launch_tiles(ctx, verb##_kernel<>, io, name); } \
+    RLS_FLAVOURS(verb, IO)
+#define RLS_TRACE_POINT_VERB(verb, IO)                                                                        \
+    static rls_status launch_##verb(rls_context *ctx, int, const IO &io, const char *name) { return launch_points(ctx, verb##_kernel<>, io, name); } \
     RLS_FLAVOURS(verb, IO)
 using GgxShadowEmitIO = ShadowEmitIO<rls_ggx_closure, rls_ggx_shader>;
 using DisneyShadowEmitIO = ShadowEmitIO<rls_disney_closure, NoShader>;
@@ -67,35 +85,14 @@ RLS_TRACE_G_VERB(disney_node_diffuse_emit, EmitIO<rls_disney_closure>)
 RLS_TRACE_G_VERB(disney_node_specular_emit, EmitIO<rls_disney_closure>)
 RLS_TRACE_G_VERB(ggx_direct_emit, GgxShadowEmitIO)
 RLS_TRACE_G_VERB(disney_direct_emit, DisneyShadowEmitIO)
-static rls_status launch_sss_probe_emit(rls_context *ctx, int, const SssEmitIO &io, const char *name)
-{
-    return launch_tiles(ctx, sss_probe_emit_kernel<>, io, name);
-}
-RLS_FLAVOURS(sss_probe_emit, SssEmitIO)
-static rls_status launch_sss_scatter_resolve(rls_context *ctx, int, const SssResolveIO &io, const char *name)
-{
-    return launch_tiles(ctx, sss_scatter_resolve_kernel<>, io, name);
-}
-RLS_FLAVOURS(sss_scatter_resolve, SssResolveIO)
+RLS_TRACE_TILE_VERB(sss_probe_emit, SssEmitIO)
+RLS_TRACE_TILE_VERB(sss_scatter_resolve, SssResolveIO)
 RLS_TRACE_G_VERB(skin_shadow_emit, SkinShadowEmitIO)
 RLS_TRACE_G_VERB(skin_sheen_glossy_emit, SkinGlossyEmitIO)
 RLS_TRACE_G_VERB(skin_specular_glossy_emit, SkinGlossyEmitIO)
-static rls_status launch_skin_probe_emit(rls_context *ctx, int, const SkinProbeEmitIO &io, const char *name)
-{
-    return launch_tiles(ctx, skin_probe_emit_kernel<>, io, name);
-}
-RLS_FLAVOURS(skin_probe_emit, SkinProbeEmitIO)
-static rls_status launch_skin_node_resolve(rls_context *ctx, int, const SkinNodeResolveIO &io, const char *name)
-{
-    hipLaunchKernelGGL(skin_node_resolve_kernel<>, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
-    return rlsh::check_launch(name, RLS_FAST);
-}
-RLS_FLAVOURS(skin_node_resolve, SkinNodeResolveIO)
-static rls_status launch_sss_hits_gate(rls_context *ctx, int, const HitGateIO &io, const char *name)
-{
-    return launch_tiles(ctx, sss_hits_gate_kernel<>, io, name);
-}
-RLS_FLAVOURS(sss_hits_gate, HitGateIO)
+RLS_TRACE_TILE_VERB(skin_probe_emit, SkinProbeEmitIO)
+RLS_TRACE_POINT_VERB(skin_node_resolve, SkinNodeResolveIO)
+RLS_TRACE_TILE_VERB(sss_hits_gate, HitGateIO)
 RLS_TRACE_G_VERB(sss_hits_emit, HitEmitIO)
 RLS_TRACE_G_VERB(ggx_bounce_direct_emit, GgxShadowEmitIO)
 RLS_TRACE_G_VERB(ggx_bounce_glossy_emit, GgxBounceEmitIO)
@@ -107,18 +104,9 @@ RLS_TRACE_G_VERB(disney_bounce_specular_emit, DisneyBounceEmitIO)
 RLS_TRACE_G_VERB(skin_bounce_shadow_emit, SkinBounceShadowEmitIO)
 RLS_TRACE_G_VERB(skin_bounce_sheen_glossy_emit, SkinBounceGlossyEmitIO)
 RLS_TRACE_G_VERB(skin_bounce_specular_glossy_emit, SkinBounceGlossyEmitIO)
-static rls_status launch_skin_bounce_probe_emit(rls_context *ctx, int, const SkinBounceProbeEmitIO &io, const char *name)
-{
-    return launch_tiles(ctx, skin_bounce_probe_emit_kernel<>, io, name);
-}
-RLS_FLAVOURS(skin_bounce_probe_emit, SkinBounceProbeEmitIO)
+RLS_TRACE_TILE_VERB(skin_bounce_probe_emit, SkinBounceProbeEmitIO)
 RLS_TRACE_G_VERB(skin_diffuse_emit, SkinDiffuseEmitIO)
-static rls_status launch_skin_bounce_resolve(rls_context *ctx, int, const SkinBounceResolveIO &io, const char *name)
-{
-    hipLaunchKernelGGL(skin_bounce_resolve_kernel<>, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
-    return rlsh::check_launch(name, RLS_FAST);
-}
-RLS_FLAVOURS(skin_bounce_resolve, SkinBounceResolveIO)
+RLS_TRACE_POINT_VERB(skin_bounce_resolve, SkinBounceResolveIO)
 
 #if !RLS_FAST
 
@@ -292,6 +280,18 @@ rls_status check_probe_hits(const char *fn, const rls_probe_queue *q, const rls_
     return RLS_OK;
 }
 
+// The hit-list-shaped light-loop queue (weight_diffuse.r its only weight plane, two segments a light: rlSss's probe-hit shading
+// over the hit list, the rlSkin bounce's diffuse_shadow over the points): the planes both sides need of it for n entries;
+// planes false: a list of no entries has no rays
+rls_status check_hit_list_queue(const char *fn, const rls_shadow_queue *q, bool planes, int64_t n, int nl, int spp)
+{
+    RLS_REQUIRE_IN(fn, !planes || (rlsh::has3(q->dir) && q->maxdist != nullptr), "queue.dir or queue.maxdist plane is NULL");
+    RLS_REQUIRE_IN(fn, !planes || q->weight_diffuse.r != nullptr, "queue.weight_specular or queue.weight_diffuse plane is NULL");
+    RLS_REQUIRE_IN(fn, !planes || q->kind != nullptr, "queue.kind is NULL");
+    RLS_REQUIRE_IN(fn, q->capacity >= n * nl * kSkinShadowSegments * spp, "queue.capacity < n * n_lights * 2 * spp_n^2");
+    return RLS_OK;
+}
+
 // What both hit verbs check of their list, loop and queues (emit: the scratch and the staging's limits too)
 rls_status check_hit_queues(const char *fn, const rls_hit_queues *hq, int n_lights, int hit_spp_n, int trace_diffuse)
 {
@@ -304,13 +304,8 @@ rls_status check_hit_queues(const char *fn, const rls_hit_queues *hq, int n_ligh
                    "queues.hit_count or queues.hit_element is NULL");
     const bool planes = hq->hit_capacity > 0;                    // (a list of no entries has no rays: offsets[0] alone)
     if (n_lights > 0) {
-        const rls_shadow_queue &q = hq->shadow;
-        RLS_REQUIRE_IN(fn, q.offsets != nullptr, "queue or queue.offsets is NULL");
-        RLS_REQUIRE_IN(fn, !planes || (rlsh::has3(q.dir) && q.maxdist != nullptr), "queue.dir or queue.maxdist plane is NULL");
-        RLS_REQUIRE_IN(fn, !planes || q.weight_diffuse.r != nullptr, "queue.weight_specular or queue.weight_diffuse plane is NULL");
-        RLS_REQUIRE_IN(fn, !planes || q.kind != nullptr, "queue.kind is NULL");
-        RLS_REQUIRE_IN(fn, q.capacity >= hq->hit_capacity * n_lights * kSkinShadowSegments * hit_spp_n * hit_spp_n,
-                       "queue.capacity < n * n_lights * 2 * spp_n^2");
+        RLS_REQUIRE_IN(fn, hq->shadow.offsets != nullptr, "queue or queue.offsets is NULL");
+        if (rls_status s = check_hit_list_queue(fn, &hq->shadow, planes, hq->hit_capacity, n_lights, hit_spp_n * hit_spp_n)) return s;
     }
     if (trace_diffuse) {
         const rls_ray_queue &q = hq->diffuse;
@@ -390,6 +385,21 @@ rls_status scan_counts(rls_context *ctx, int64_t *offsets, int64_t n, int64_t *t
 // points per compaction tile: as many as tile_slots slots hold, a point's index in its tile being 8 bits
 inline int compact_tile_points(int tile_slots, int per_point) { return std::min(tile_slots / per_point, kCompactMaxPoints); }
 
+// the compaction of a ray emit's kept records into its queue, the counts scanned: the staged planes f (dir[3], then nw weight
+// planes) and 16-bit tags of n points at spp slots a point
+rls_status compact_rays(rls_context *ctx, float *const *f, const uint16_t *tag, const rls_ray_queue *q, int64_t n, int spp, int nw)
+{
+    TraceCompactIO cio = {};
+    for (int k = 0; k < 3; k++) cio.sdir[k] = f[k];
+    for (int k = 0; k < nw; k++) cio.sw[k] = f[3 + k];
+    cio.tag = tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp;
+    cio.tile_points = compact_tile_points(kCompactSlots, spp);
+    const dim3 cgrid = rlsh::grid_for(ctx, n, cio.tile_points);
+    if (nw == 1) hipLaunchKernelGGL(trace_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    else hipLaunchKernelGGL(trace_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    return rlsh::check_launch("trace_compact_kernel");
+}
+
 // A ray emit of n > 0 points at `spp` samples a point (a node's untraced refraction: 1) into a checked queue: the staging in
 // the queue's scratch, the closure's emit kernel (io: its closure part filled; dispatch, with G for the batch), the scan of the
 // per-point counts in place into offsets, the compaction of the kept records into the queue (nw weight planes).  side: the
@@ -405,15 +415,24 @@ rls_status run_ray_emit(rls_context *ctx, int64_t n, IO &io, int spp, uint32_t s
     io.n = n; io.spp = spp; io.seed = seed; io.first = first_index;
     if (rls_status s = dispatch(ctx, pick_group(ctx, n, spp), io, name)) return s;
     if (rls_status s = scan_counts(ctx, q->offsets, n, st.totals, st.tiles)) return s;
+    return compact_rays(ctx, st.f, io.tag, q, n, spp, nw);
+}
 
-    TraceCompactIO cio = {};
-    for (int k = 0; k < 3; k++) { cio.sdir[k] = st.f[k]; cio.sw[k] = st.f[3 + k]; }
-    cio.tag = io.tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp;
-    cio.tile_points = compact_tile_points(kCompactSlots, spp);
-    const dim3 cgrid = rlsh::grid_for(ctx, n, cio.tile_points);
-    if (nw == 1) hipLaunchKernelGGL(trace_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
-    else hipLaunchKernelGGL(trace_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
-    return rlsh::check_launch("trace_compact_kernel");
+// One ray queue of a node emit, named once for the node call and the bounce call.  io: the bounce kernels' argument struct, whose
+// base Node is the node kernels'; st: the bounce call's state, copied in ahead of the bounce kernel, or NULL: the node kernel
+// on the base.  The rest: run_ray_emit's.
+template <class Node, class Bounce>
+rls_status node_ray_emit(rls_context *ctx, int64_t n, Bounce &io, const BounceState *st, int spp, uint32_t seed, uint64_t first_index,
+                         const rls_ray_queue *q, float *side, int nw, const char *name,
+                         rls_status (*node)(rls_context *, int, const Node &, const char *),
+                         rls_status (*bounce)(rls_context *, int, const Bounce &, const char *))
+{
+    if (st) {
+        io.st = *st;
+        return run_ray_emit(ctx, n, io, spp, seed, first_index, q, side, nw, name, bounce);
+    }
+    Node &base = io;
+    return run_ray_emit(ctx, n, base, spp, seed, first_index, q, side, nw, name, node);
 }
 
 // one ray resolve: the sum of io's queue (nw weight planes; one plane: x io.scale) into io.out
@@ -456,6 +475,51 @@ rls_status run_shadow_emit(rls_context *ctx, int64_t n, IO &io, int spp_n, uint3
     else if (nwd == 1) hipLaunchKernelGGL(shadow_compact_kernel<1>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
     else hipLaunchKernelGGL(shadow_compact_kernel<3>, cgrid, dim3(rlsh::kBlock), 0, ctx->stream, cio);
     return rlsh::check_launch("shadow_compact_kernel");
+}
+// a node emit's light-loop queue, as node_ray_emit (rlGgx, rlDisney: one struct serves both kernels)
+template <class Node, class Bounce>
+rls_status node_shadow_emit(rls_context *ctx, int64_t n, Bounce &io, const BounceState *st, int spp_n, uint32_t seed,
+                            uint64_t first_index, const rls_shadow_queue *q, int nwd, const char *name,
+                            rls_status (*node)(rls_context *, int, const Node &, const char *),
+                            rls_status (*bounce)(rls_context *, int, const Bounce &, const char *))
+{
+    if (st) {
+        io.st = *st;
+        return run_shadow_emit(ctx, n, io, spp_n, seed, first_index, q, nwd, name, bounce);
+    }
+    Node &base = io;
+    return run_shadow_emit(ctx, n, base, spp_n, seed, first_index, q, nwd, name, node);
+}
+
+// The hit-list-shaped queue's emit and compaction.  f: its kHitStagePlanes staged planes -- dir[3], maxdist, weight_diffuse.r --
+// of n entries at nl * 2 * spp slots an entry; tag: their 32-bit tags; count: the queue's offsets (NULL: no light loop)
+template <class IO>
+void set_hit_list_staging(IO &io, float *const *f, uint32_t *tag, int64_t *count)
+{
+    for (int k = 0; k < 3; k++) io.dir[k] = f[k];
+    io.maxdist = f[3]; io.wd[0] = f[4]; io.tag = tag; io.count = count;
+}
+// totals: scan_tiles(n) tile sums
+rls_status compact_hit_list(rls_context *ctx, float *const *f, const uint32_t *tag, const rls_shadow_queue *q, int64_t n, int nl,
+                            int spp, int64_t *totals)
+{
+    if (rls_status s = scan_counts(ctx, q->offsets, n, totals, scan_tiles(n))) return s;
+    ShadowCompactIO cio = {};
+    for (int k = 0; k < 4; k++) cio.src[k] = f[k];
+    cio.src[7] = f[4];
+    cio.tag = tag; cio.offsets = q->offsets; cio.q = *q; cio.n = n; cio.spp = spp;
+    cio.slots = nl * kSkinShadowSegments * spp;
+    cio.tile_points = compact_tile_points(kShadowMaxSlots, cio.slots);
+    hipLaunchKernelGGL(hits_compact_kernel, rlsh::grid_for(ctx, n, cio.tile_points), dim3(rlsh::kBlock), 0, ctx->stream, cio);
+    return rlsh::check_launch("hits_compact_kernel");
+}
+// its part of a resolve's argument struct: no weight_specular, one plane of weight_diffuse (the lights' radiance, their count,
+// 1 / spp and n: the caller's)
+void hit_list_resolve_io(ShadowResolveIO &io, const rls_shadow_queue *q, rls_crgb visibility)
+{
+    io.offsets = q->offsets; io.kind = q->kind; io.vis = visibility;
+    for (int k = 0; k < 3; k++) { io.ws[k] = nullptr; io.wd[k] = nullptr; }
+    io.wd[0] = q->weight_diffuse.r;
 }
 
 // one light-loop resolve: io's queue (nwd planes of weight_diffuse: rlGgx 1, rlDisney 3) into io.dd and io.ds
@@ -732,28 +796,17 @@ rls_status ggx_node_emit(const char *fn, rls_context *ctx, int64_t n, const rls_
     }
     GgxBounceEmitIO io = {};
     io.c = *c; io.sh = *sh; io.traced = traced ? 1 : 0;
-    if (st) {
-        sio.st = *st; io.st = *st;
-        if (n_lights > 0)
-            if (rls_status s = run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, q->shadow, 1, fn, dispatch_ggx_bounce_direct_emit))
-                return s;
-        if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, q->glossy, nullptr, 3, fn, dispatch_ggx_bounce_glossy_emit))
-            return s;
-        // both branches of integrateRefract in one launch at the call's spp: an untraced point's one ray is its sample 0
-        if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, q->refract, nullptr, 1, fn,
-                                        dispatch_ggx_bounce_refract_emit)) return s;
-        return run_ray_emit(ctx, n, io, spp, seed, first_index, q->diffuse, nullptr, 1, fn, dispatch_ggx_bounce_diffuse_emit);
-    }
-    GgxNodeEmitIO &pio = io;                                     // (the node call's ray emits take the struct without the state)
     if (n_lights > 0)
-        if (rls_status s = run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, q->shadow, 1, fn, dispatch_ggx_direct_emit))
-            return s;
-    if (rls_status s = run_ray_emit(ctx, n, pio, spp, seed, first_index, q->glossy, nullptr, 3, fn, dispatch_ggx_node_glossy_emit))
-        return s;
-    // the untraced branch is one ray a point: one sample (GgxNodeRefract)
-    if (rls_status s = run_ray_emit(ctx, n, pio, traced ? spp : 1, seed, first_index, q->refract, nullptr, 1, fn,
-                                    dispatch_ggx_node_refract_emit)) return s;
-    return run_ray_emit(ctx, n, pio, spp, seed, first_index, q->diffuse, nullptr, 1, fn, dispatch_ggx_node_diffuse_emit);
+        if (rls_status s = node_shadow_emit(ctx, n, sio, st, spp_n, seed, first_index, q->shadow, 1, fn, dispatch_ggx_direct_emit,
+                                            dispatch_ggx_bounce_direct_emit)) return s;
+    if (rls_status s = node_ray_emit(ctx, n, io, st, spp, seed, first_index, q->glossy, nullptr, 3, fn, dispatch_ggx_node_glossy_emit,
+                                     dispatch_ggx_bounce_glossy_emit)) return s;
+    // the node call's untraced branch is one ray a point: one sample (GgxNodeRefract).  The bounce call (traced = 1) has both
+    // branches of integrateRefract in one launch at the call's spp: an untraced point's one ray is its sample 0
+    if (rls_status s = node_ray_emit(ctx, n, io, st, traced ? spp : 1, seed, first_index, q->refract, nullptr, 1, fn,
+                                     dispatch_ggx_node_refract_emit, dispatch_ggx_bounce_refract_emit)) return s;
+    return node_ray_emit(ctx, n, io, st, spp, seed, first_index, q->diffuse, nullptr, 1, fn, dispatch_ggx_node_diffuse_emit,
+                         dispatch_ggx_bounce_diffuse_emit);
 }
 
 rls_status ggx_node_resolve(const char *fn, rls_context *ctx, int64_t n, const rls_ggx_closure *c, const rls_ggx_shader *sh,
@@ -826,22 +879,13 @@ rls_status disney_node_emit(const char *fn, rls_context *ctx, int64_t n, const r
     }
     DisneyBounceEmitIO io = {};
     io.c = *c;
-    if (st) {
-        sio.st = *st; io.st = *st;
-        if (n_lights > 0)
-            if (rls_status s = run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, q->shadow, 3, fn,
-                                               dispatch_disney_bounce_direct_emit)) return s;
-        if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, q->diffuse, nullptr, 3, fn,
-                                        dispatch_disney_bounce_diffuse_emit)) return s;
-        return run_ray_emit(ctx, n, io, spp, seed, first_index, q->specular, nullptr, 3, fn, dispatch_disney_bounce_specular_emit);
-    }
-    EmitIO<rls_disney_closure> &pio = io;
     if (n_lights > 0)
-        if (rls_status s = run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, q->shadow, 3, fn, dispatch_disney_direct_emit))
-            return s;
-    if (rls_status s = run_ray_emit(ctx, n, pio, spp, seed, first_index, q->diffuse, nullptr, 3, fn, dispatch_disney_node_diffuse_emit))
-        return s;
-    return run_ray_emit(ctx, n, pio, spp, seed, first_index, q->specular, nullptr, 3, fn, dispatch_disney_node_specular_emit);
+        if (rls_status s = node_shadow_emit(ctx, n, sio, st, spp_n, seed, first_index, q->shadow, 3, fn, dispatch_disney_direct_emit,
+                                            dispatch_disney_bounce_direct_emit)) return s;
+    if (rls_status s = node_ray_emit(ctx, n, io, st, spp, seed, first_index, q->diffuse, nullptr, 3, fn,
+                                     dispatch_disney_node_diffuse_emit, dispatch_disney_bounce_diffuse_emit)) return s;
+    return node_ray_emit(ctx, n, io, st, spp, seed, first_index, q->specular, nullptr, 3, fn, dispatch_disney_node_specular_emit,
+                         dispatch_disney_bounce_specular_emit);
 }
 
 // sc: the bounce call's closure and scales (its materials index alone is read), checked by the caller
@@ -896,16 +940,8 @@ rls_status check_skin_bounce(const char *fn, const rls_context *ctx, int64_t n, 
     RLS_REQUIRE_IN(fn, n_lights == 0 || q->diffuse_shadow->offsets != nullptr, "queue.offsets is NULL");
     return RLS_OK;
 }
-// the planes both sides need of that queue (weight_diffuse.r is its only weight plane), n > 0
-rls_status check_diffuse_shadow_queue(const char *fn, const rls_shadow_queue *q, int64_t n, int nl, int spp)
-{
-    RLS_REQUIRE_IN(fn, rlsh::has3(q->dir) && q->maxdist != nullptr, "queue.dir or queue.maxdist plane is NULL");
-    RLS_REQUIRE_IN(fn, q->weight_diffuse.r != nullptr, "queue.weight_specular or queue.weight_diffuse plane is NULL");
-    RLS_REQUIRE_IN(fn, q->kind != nullptr, "queue.kind is NULL");
-    RLS_REQUIRE_IN(fn, q->capacity >= n * nl * kSkinShadowSegments * spp, "queue.capacity < n * n_lights * 2 * spp_n^2");
-    return RLS_OK;
-}
-// its staging: the hit list's planes (dir[3], maxdist, weight_diffuse.r) and 32-bit tags of n * n_lights * 2 * spp slots
+// that queue's staging (its planes: check_hit_list_queue): the hit list's planes (dir[3], maxdist, weight_diffuse.r) and 32-bit
+// tags of n * n_lights * 2 * spp slots
 inline Staging diffuse_shadow_staging(void *base, int64_t n, int nl, int spp)
 {
     return staging(base, n, nl * kSkinShadowSegments * spp, kHitStagePlanes, sizeof(uint32_t));
@@ -939,37 +975,28 @@ rls_status skin_node_emit(const char *fn, rls_context *ctx, int64_t n, const rls
             if (rls_status s = check_shadow_scratch(fn, sq[k], 0, n, n_lights, spp)) return s;
         }
         if (dq) {
-            if (rls_status s = check_diffuse_shadow_queue(fn, dq, n, n_lights, spp)) return s;
+            if (rls_status s = check_hit_list_queue(fn, dq, true, n, n_lights, spp)) return s;
             RLS_REQUIRE_IN(fn, dq->scratch != nullptr && dq->scratch_bytes >= diffuse_shadow_staging(nullptr, n, n_lights, spp).bytes,
                            "queue.scratch is NULL or smaller than rls_trace_shadow_scratch_bytes");
         }
         if (rls_status s = copy_lights(lights, n_lights, 1, sio.lights, &sio.nl)) return s;
         sio.c = *c; sio.P = P; sio.fcnt = q->sssWeight;
     }
-    if (st) sio.st = *st;
     // per lobe: the light loop, which leaves its Fresnel (sum, count) in (the lobe's Fresnel plane, sssWeight); integrateGlossy,
     // which folds on from there and writes the lobe's hand-down into its Fresnel plane
     for (int k = 0; k < 2; k++) {
         if (n_lights > 0) {
             sio.lobe = k; sio.fsum = fresnel[k];
-            SkinShadowEmitIO &pio = sio;                         // (the node call's kernels take the structs without the state)
-            if (rls_status s = st ? run_shadow_emit(ctx, n, sio, spp_n, seed, first_index, sq[k], 0, fn, dispatch_skin_bounce_shadow_emit)
-                                  : run_shadow_emit(ctx, n, pio, spp_n, seed, first_index, sq[k], 0, fn, dispatch_skin_shadow_emit))
-                return s;
+            if (rls_status s = node_shadow_emit(ctx, n, sio, st, spp_n, seed, first_index, sq[k], 0, fn, dispatch_skin_shadow_emit,
+                                                dispatch_skin_bounce_shadow_emit)) return s;
         }
         SkinBounceGlossyEmitIO io = {};
         io.c = *c;
         if (n_lights > 0) { io.fsum = fresnel[k]; io.fcnt = q->sssWeight; }
-        if (st) {
-            io.st = *st;
-            if (rls_status s = run_ray_emit(ctx, n, io, spp, seed, first_index, gq[k], fresnel[k], 3, fn,
-                                            k == 0 ? dispatch_skin_bounce_sheen_glossy_emit : dispatch_skin_bounce_specular_glossy_emit))
-                return s;
-        } else {
-            SkinGlossyEmitIO &pio = io;
-            if (rls_status s = run_ray_emit(ctx, n, pio, spp, seed, first_index, gq[k], fresnel[k], 3, fn,
-                                            k == 0 ? dispatch_skin_sheen_glossy_emit : dispatch_skin_specular_glossy_emit)) return s;
-        }
+        if (rls_status s = node_ray_emit(ctx, n, io, st, spp, seed, first_index, gq[k], fresnel[k], 3, fn,
+                                         k == 0 ? dispatch_skin_sheen_glossy_emit : dispatch_skin_specular_glossy_emit,
+                                         k == 0 ? dispatch_skin_bounce_sheen_glossy_emit : dispatch_skin_bounce_specular_glossy_emit))
+            return s;
     }
     // integrateScatter's probe rays; sssWeight from the two hand-downs
     SkinBounceProbeEmitIO io = {};
@@ -988,19 +1015,10 @@ rls_status skin_node_emit(const char *fn, rls_context *ctx, int64_t n, const rls
     for (int l = 0; l < sio.nl; l++) dio.lights[l] = sio.lights[l];
     dio.nl = sio.nl; dio.st = *st;
     const Staging sg = diffuse_shadow_staging(dq->scratch, n, dio.nl, spp);
-    for (int k = 0; k < 3; k++) dio.dir[k] = sg.f[k];
-    dio.maxdist = sg.f[3]; dio.wd[0] = sg.f[4]; dio.tag = (uint32_t *)sg.tag; dio.count = dq->offsets;
+    set_hit_list_staging(dio, sg.f, (uint32_t *)sg.tag, dq->offsets);
     set_loop(dio, n, spp_n, seed ^ RLS_SKIN_DIFFUSE_SEED, first_index);
     if (rls_status s = dispatch_skin_diffuse_emit(ctx, pick_group(ctx, n, spp), dio, fn)) return s;
-    if (rls_status s = scan_counts(ctx, dq->offsets, n, sg.totals, sg.tiles)) return s;
-    ShadowCompactIO cio = {};
-    for (int k = 0; k < 4; k++) cio.src[k] = sg.f[k];
-    cio.src[7] = sg.f[4];
-    cio.tag = dio.tag; cio.offsets = dq->offsets; cio.q = *dq; cio.n = n; cio.spp = spp;
-    cio.slots = dio.nl * kSkinShadowSegments * spp;
-    cio.tile_points = compact_tile_points(kShadowMaxSlots, cio.slots);
-    hipLaunchKernelGGL(hits_compact_kernel, rlsh::grid_for(ctx, n, cio.tile_points), dim3(rlsh::kBlock), 0, ctx->stream, cio);
-    return rlsh::check_launch("hits_compact_kernel");
+    return compact_hit_list(ctx, sg.f, dio.tag, dq, n, dio.nl, spp, sg.totals);
 }
 
 // t, out: not NULL (the callers' check); dvis: the visibility traced for dq's rays
@@ -1022,13 +1040,10 @@ rls_status skin_node_resolve(const char *fn, rls_context *ctx, int64_t n, const 
         if (rls_status s = shadow_resolve_io(fn, io.spec_s, n, 0, lights, n_lights, spp_n, q->specular_shadow, t->specular_visibility))
             return s;
         if (dq) {
-            if (rls_status s = check_diffuse_shadow_queue(fn, dq, n, n_lights, spp)) return s;
+            if (rls_status s = check_hit_list_queue(fn, dq, true, n, n_lights, spp)) return s;
             RLS_REQUIRE_IN(fn, dvis.r && dvis.g && dvis.b, "visibility plane is NULL");
-            ShadowResolveIO &d = io.dif_s;
-            d = io.sheen_s;                                      // the lights' radiance, their count, 1 / spp
-            d.offsets = dq->offsets; d.kind = dq->kind; d.vis = dvis;
-            for (int k = 0; k < 3; k++) d.ws[k] = nullptr;
-            d.wd[0] = dq->weight_diffuse.r; d.wd[1] = nullptr; d.wd[2] = nullptr;
+            io.dif_s = io.sheen_s;                               // the lights' radiance, their count, 1 / spp
+            hit_list_resolve_io(io.dif_s, dq, dvis);
         }
     }
     io.sheen_s.n = n; io.spec_s.n = n; io.dif_s.n = n;
@@ -1251,37 +1266,18 @@ rls_status rls_trace_sss_hits_emit(rls_context *ctx, int64_t n, const rls_sss_cl
     if (!shadow && !diffuse) return RLS_OK;
     // the two emits over the list in one kernel, then each queue's scan and compaction
     io.h = *h; io.T = hitT; io.hit_count = hq->hit_count; io.hit_element = hq->hit_element;
-    for (int k = 0; k < 3; k++) io.dir[k] = sc.f[k];
-    io.maxdist = sc.f[3]; io.wd[0] = sc.f[4]; io.tag = sc.tag;
-    io.count = shadow ? hq->shadow.offsets : nullptr;
+    set_hit_list_staging(io, sc.f, sc.tag, shadow ? hq->shadow.offsets : nullptr);
     if (diffuse) {
         for (int k = 0; k < 3; k++) io.ddir[k] = sc.df[k];
         io.dw = sc.df[3]; io.dtag = sc.dtag; io.dcount = hq->diffuse.offsets;
     }
     set_loop(io, cap, hit_spp_n, seed, hit_first_index);
     if (rls_status s = dispatch_sss_hits_emit(ctx, pick_group(ctx, cap, hit_spp), io, fn)) return s;
-    if (shadow) {
-        if (rls_status s = scan_counts(ctx, hq->shadow.offsets, cap, sc.totals, scan_tiles(cap))) return s;
-        ShadowCompactIO cio = {};
-        for (int k = 0; k < 4; k++) cio.src[k] = sc.f[k];
-        cio.src[7] = sc.f[4];
-        cio.tag = sc.tag; cio.offsets = hq->shadow.offsets; cio.q = hq->shadow; cio.n = cap; cio.spp = hit_spp;
-        cio.slots = io.nl * kSkinShadowSegments * hit_spp;
-        cio.tile_points = compact_tile_points(kShadowMaxSlots, cio.slots);
-        hipLaunchKernelGGL(hits_compact_kernel, rlsh::grid_for(ctx, cap, cio.tile_points), dim3(rlsh::kBlock), 0,
-                           ctx->stream, cio);
-        if (rls_status s = rlsh::check_launch("hits_compact_kernel")) return s;
-    }
+    if (shadow)
+        if (rls_status s = compact_hit_list(ctx, sc.f, sc.tag, &hq->shadow, cap, io.nl, hit_spp, sc.totals)) return s;
     if (diffuse) {
         if (rls_status s = scan_counts(ctx, hq->diffuse.offsets, cap, sc.totals, scan_tiles(cap))) return s;
-        TraceCompactIO cio = {};
-        for (int k = 0; k < 3; k++) cio.sdir[k] = sc.df[k];
-        cio.sw[0] = sc.df[3];
-        cio.tag = sc.dtag; cio.offsets = hq->diffuse.offsets; cio.q = hq->diffuse; cio.n = cap; cio.spp = 1;
-        cio.tile_points = compact_tile_points(kCompactSlots, 1);
-        hipLaunchKernelGGL(trace_compact_kernel<1>, rlsh::grid_for(ctx, cap, cio.tile_points), dim3(rlsh::kBlock), 0, ctx->stream,
-                           cio);
-        if (rls_status s = rlsh::check_launch("trace_compact_kernel")) return s;
+        return compact_rays(ctx, sc.df, sc.dtag, &hq->diffuse, cap, 1, 1);
     }
     return RLS_OK;
 }
@@ -1309,10 +1305,7 @@ rls_status rls_trace_sss_hits_resolve(rls_context *ctx, const rls_probe_hits *h,
     if (hq->hit_capacity == 0) return RLS_OK;
     for (int l = 0; l < io.s.nl; l++)
         for (int k = 0; k < 3; k++) io.s.rad[l][k] = lt[l].radiance[k];
-    if (io.s.nl > 0) {
-        io.s.offsets = hq->shadow.offsets; io.s.kind = hq->shadow.kind; io.s.vis = visibility;
-        io.s.wd[0] = hq->shadow.weight_diffuse.r;
-    }
+    if (io.s.nl > 0) hit_list_resolve_io(io.s, &hq->shadow, visibility);
     io.s.inv = 1.0f / (float)(hit_spp_n * hit_spp_n);                // as the loop kernels: 1 / spp
     io.s.n = hq->hit_capacity;
     io.hit_count = hq->hit_count; io.hit_element = hq->hit_element;
@@ -1344,13 +1337,6 @@ rls_status check_opacity_params(const char *fn, std::initializer_list<const rls_
 }
 inline bool all_or_none(rls_crgb v) { return (v.r && v.g && v.b) || (!v.r && !v.g && !v.b); }
 
-template <class IO>
-rls_status launch_opacity(rls_context *ctx, void (*kernel)(IO), const IO &io, const char *name)
-{
-    hipLaunchKernelGGL(kernel, rlsh::grid_for(ctx, io.n), dim3(rlsh::kBlock), 0, ctx->stream, io);
-    return rlsh::check_launch(name);
-}
-
 } // namespace
 
 extern "C" {
@@ -1363,7 +1349,7 @@ rls_status rls_trace_ggx_opacity(rls_context *ctx, int64_t n, const rls_ggx_opac
     if (n == 0) return RLS_OK;
     RLS_REQUIRE(rlsh::has3(out_opacity), "NULL output plane");
     const GgxOpacityIO io = { *p, ray_type, out_opacity, n };
-    return launch_opacity(ctx, ggx_opacity_kernel, io, __func__);
+    return launch_points(ctx, ggx_opacity_kernel, io, __func__);
 }
 
 rls_status rls_trace_disney_opacity(rls_context *ctx, int64_t n, const rls_disney_opacity *p, const uint8_t *ray_type,
@@ -1374,7 +1360,7 @@ rls_status rls_trace_disney_opacity(rls_context *ctx, int64_t n, const rls_disne
     if (n == 0) return RLS_OK;
     RLS_REQUIRE(rlsh::has3(out_opacity), "NULL output plane");
     const DisneyOpacityIO io = { *p, ray_type, out_opacity, n };
-    return launch_opacity(ctx, disney_opacity_kernel, io, __func__);
+    return launch_points(ctx, disney_opacity_kernel, io, __func__);
 }
 
 rls_status rls_trace_skin_opacity(rls_context *ctx, int64_t n, const rls_skin_opacity *p, const uint8_t *ray_type,
@@ -1386,7 +1372,7 @@ rls_status rls_trace_skin_opacity(rls_context *ctx, int64_t n, const rls_skin_op
     if (n == 0) return RLS_OK;
     RLS_REQUIRE(rlsh::has3(out_opacity), "NULL output plane");
     const SkinOpacityIO io = { *p, ray_type, incoming, out_opacity, n };
-    return launch_opacity(ctx, skin_opacity_kernel, io, __func__);
+    return launch_points(ctx, skin_opacity_kernel, io, __func__);
 }
 
 rls_status rls_trace_shadow_visibility(rls_context *ctx, int64_t rays, const rls_shadow_hits *h, rls_crgb base,

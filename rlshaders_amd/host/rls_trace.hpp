@@ -43,6 +43,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "rls_batch.hpp"
@@ -50,25 +51,70 @@
 
 namespace rlsb {
 
+namespace detail {
+// The device allocations of one queue object, freed together -- also when the object's constructor throws half way, this
+// being a member of it.
+class DeviceBuffers {
+public:
+    explicit DeviceBuffers(const Device &d) : dev_(&d) {}
+    ~DeviceBuffers() { for (void *p : bufs_) rls_device_free(dev_->ctx(), p); }
+    DeviceBuffers(const DeviceBuffers &) = delete;
+    DeviceBuffers &operator=(const DeviceBuffers &) = delete;
+
+    void *alloc(size_t bytes)
+    {
+        bufs_.reserve(bufs_.size() + 1);                    // (no throw between the allocation and its entry)
+        void *p = nullptr;
+        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
+        bufs_.push_back(p);
+        return p;
+    }
+    template <class T>
+    T *alloc(int64_t count) { return static_cast<T *>(alloc(sizeof(T) * (size_t)count)); }
+    rls_vec3 vec3(int64_t count) { return rls_vec3{alloc<float>(count), alloc<float>(count), alloc<float>(count)}; }
+    // one count of a queue, an int64_t in device memory (synchronises)
+    int64_t read(const int64_t *p) const
+    {
+        int64_t c = 0;
+        check(rls_copy_to_host(dev_->ctx(), &c, p, sizeof(c)));
+        return c;
+    }
+
+private:
+    const Device *dev_;
+    std::vector<void *> bufs_;
+};
+
+inline rls_crgb crgb(const Planes &p) { return p.empty() ? rls_crgb{nullptr, nullptr, nullptr} : rls_crgb{p.plane(0), p.plane(1), p.plane(2)}; }
+template <class Q>
+inline void checkNodeQueues(const Q &q, int64_t n, int n_lights, int spp_n, const char *who)
+{
+    if (q.points() != n || q.lights() != n_lights || q.sppN() != spp_n) throw Error(RLS_ERR_INVALID_ARGUMENT, who);
+}
+} // namespace detail
+
 // The device buffers of one emit: per-ray planes for n * spp_n^2 rays, offsets [n + 1] and the emit's scratch.
 class RayQueue {
 public:
     // NodeDiffuse: the rlGgx node's Oren-Nayar queue -- one weight plane like Refract, no kind plane
     enum Kind { Glossy, Refract, DisneyDiffuse, DisneyGlossy, NodeDiffuse };
 
-    RayQueue(const Device &d, int64_t n, int spp_n, Kind kind) : dev_(&d), n_(n), spp_n_(spp_n), kind_(kind)
+    RayQueue(const Device &d, int64_t n, int spp_n, Kind kind) : bufs_(d), n_(n), spp_n_(spp_n), kind_(kind)
     {
         const int64_t cap = n * spp_n * spp_n;
         size_t scratch = 0;
         check(rls_trace_scratch_bytes(n, spp_n, &scratch));
-        try {
-            allocate(cap, scratch);
-        } catch (...) {
-            release();
-            throw;
-        }
+        q_.capacity = cap;
+        q_.offsets = bufs_.alloc<int64_t>(n + 1);
+        q_.dir = bufs_.vec3(cap);
+        q_.weight.r = bufs_.alloc<float>(cap);
+        if (kind != Refract && kind != NodeDiffuse) { q_.weight.g = bufs_.alloc<float>(cap); q_.weight.b = bufs_.alloc<float>(cap); }
+        q_.point = bufs_.alloc<uint32_t>(cap);
+        q_.sample = bufs_.alloc<uint8_t>(cap);
+        if (kind == Refract) q_.kind = bufs_.alloc<uint8_t>(cap);
+        q_.scratch = bufs_.alloc(scratch);
+        q_.scratch_bytes = scratch;
     }
-    ~RayQueue() { release(); }
     RayQueue(const RayQueue &) = delete;
     RayQueue &operator=(const RayQueue &) = delete;
 
@@ -77,48 +123,14 @@ public:
     int sppN() const { return spp_n_; }
     Kind kind() const { return kind_; }
     // offsets[n]: the number of rays (synchronises)
-    int64_t count() const
-    {
-        int64_t c = 0;
-        check(rls_copy_to_host(dev_->ctx(), &c, q_.offsets + n_, sizeof(c)));
-        return c;
-    }
+    int64_t count() const { return bufs_.read(q_.offsets + n_); }
 
 private:
-    void allocate(int64_t cap, size_t scratch)
-    {
-        q_.capacity = cap;
-        q_.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(n_ + 1)));
-        q_.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
-        q_.weight.r = falloc(cap);
-        if (kind_ != Refract && kind_ != NodeDiffuse) { q_.weight.g = falloc(cap); q_.weight.b = falloc(cap); }
-        q_.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
-        q_.sample = static_cast<uint8_t *>(alloc((size_t)cap));
-        if (kind_ == Refract) q_.kind = static_cast<uint8_t *>(alloc((size_t)cap));
-        q_.scratch = alloc(scratch);
-        q_.scratch_bytes = scratch;
-    }
-    void release()
-    {
-        for (int k = 0; k < nbufs_; k++) rls_device_free(dev_->ctx(), bufs_[k]);
-        nbufs_ = 0;
-    }
-    void *alloc(size_t bytes)
-    {
-        void *p = nullptr;
-        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
-        bufs_[nbufs_++] = p;
-        return p;
-    }
-    float *falloc(int64_t count) { return static_cast<float *>(alloc(sizeof(float) * (size_t)count)); }
-
-    const Device *dev_;
+    detail::DeviceBuffers bufs_;
     int64_t n_;
     int spp_n_;
     Kind kind_;
     rls_ray_queue q_{};
-    void *bufs_[12] = {};
-    int nbufs_ = 0;
 };
 
 // integrateGlossy's sample rays (src/rlGgx.h:172-179); avgReflectWeight: n floats (getAvgReflectWeight, :181-184) or nullptr
@@ -155,36 +167,28 @@ inline void emitDisney(const Device &d, const rls_disney_closure &c, int lobe, i
 // n floats
 inline void resolveGlossy(const Device &d, const RayQueue &q, const Planes &radiance, Planes &sum)
 {
-    check(rls_trace_ggx_glossy_resolve(d.ctx(), q.points(), &q.c(),
-                                       rls_crgb{radiance.plane(0), radiance.plane(1), radiance.plane(2)}, sum.rgb()));
+    check(rls_trace_ggx_glossy_resolve(d.ctx(), q.points(), &q.c(), detail::crgb(radiance), sum.rgb()));
 }
 
 inline void resolveRefract(const Device &d, const RayQueue &q, const Planes &radiance, Planes &result)
 {
-    check(rls_trace_ggx_refract_resolve(d.ctx(), q.points(), &q.c(), q.sppN(),
-                                        rls_crgb{radiance.plane(0), radiance.plane(1), radiance.plane(2)}, result.rgb()));
+    check(rls_trace_ggx_refract_resolve(d.ctx(), q.points(), &q.c(), q.sppN(), detail::crgb(radiance), result.rgb()));
 }
 
 // integrateScatter's probe rays: n * spp_n^2 rays, ray j = i * spp_n^2 + s (no compaction: count() is known on the host)
 class ProbeQueue {
 public:
-    ProbeQueue(const Device &d, int64_t n, int spp_n) : dev_(&d), n_(n), spp_n_(spp_n)
+    ProbeQueue(const Device &d, int64_t n, int spp_n) : bufs_(d), n_(n), spp_n_(spp_n)
     {
         const int64_t cap = n * spp_n * spp_n;
-        try {
-            q_.capacity = cap;
-            q_.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(n + 1)));
-            q_.origin = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
-            q_.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
-            q_.maxdist = falloc(cap);
-            q_.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
-            q_.sample = static_cast<uint8_t *>(alloc((size_t)cap));
-        } catch (...) {
-            release();
-            throw;
-        }
+        q_.capacity = cap;
+        q_.offsets = bufs_.alloc<int64_t>(n + 1);
+        q_.origin = bufs_.vec3(cap);
+        q_.dir = bufs_.vec3(cap);
+        q_.maxdist = bufs_.alloc<float>(cap);
+        q_.point = bufs_.alloc<uint32_t>(cap);
+        q_.sample = bufs_.alloc<uint8_t>(cap);
     }
-    ~ProbeQueue() { release(); }
     ProbeQueue(const ProbeQueue &) = delete;
     ProbeQueue &operator=(const ProbeQueue &) = delete;
 
@@ -194,26 +198,10 @@ public:
     int64_t count() const { return q_.capacity; }
 
 private:
-    void release()
-    {
-        for (int k = 0; k < nbufs_; k++) rls_device_free(dev_->ctx(), bufs_[k]);
-        nbufs_ = 0;
-    }
-    void *alloc(size_t bytes)
-    {
-        void *p = nullptr;
-        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
-        bufs_[nbufs_++] = p;
-        return p;
-    }
-    float *falloc(int64_t count) { return static_cast<float *>(alloc(sizeof(float) * (size_t)count)); }
-
-    const Device *dev_;
+    detail::DeviceBuffers bufs_;
     int64_t n_;
     int spp_n_;
     rls_probe_queue q_{};
-    void *bufs_[10] = {};
-    int nbufs_ = 0;
 };
 
 // integrateScatter's probe rays (getProbeRay, src/rlSss.h:224-228); P: 3 planes of n floats, sg->P
@@ -221,7 +209,7 @@ inline void emitProbes(const Device &d, const rls_sss_closure &c, const Planes &
                        ProbeQueue &q, uint64_t first_index = 0)
 {
     if (q.points() != n || q.sppN() != spp_n) throw Error(RLS_ERR_INVALID_ARGUMENT, "emitProbes: a queue of another size");
-    check(rls_trace_sss_probe_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, spp_n, seed,
+    check(rls_trace_sss_probe_emit(d.ctx(), n, &c, P.cvec3(), spp_n, seed,
                                    first_index, &q.c()));
 }
 
@@ -231,7 +219,7 @@ inline void resolveScatter(const Device &d, const rls_sss_closure &c, const Plan
                            const rls_probe_hits &hits, bool cavityFade, bool literalMatrix, Planes &result,
                            float *meanDepth = nullptr)
 {
-    check(rls_trace_sss_scatter_resolve(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, q.sppN(),
+    check(rls_trace_sss_scatter_resolve(d.ctx(), q.points(), &c, P.cvec3(), q.sppN(),
                                         &q.c(), &hits, cavityFade ? 1 : 0, literalMatrix ? 1 : 0, result.rgb(),
                                         meanDepth));
 }
@@ -243,42 +231,36 @@ class HitQueues {
 public:
     HitQueues(const Device &d, int64_t n, int spp_n, int max_hits, int64_t hitCapacity, int n_lights, int hit_spp_n,
               bool traceDiffuse)
-        : dev_(&d), n_(n), spp_n_(spp_n), n_lights_(n_lights), hit_spp_n_(hit_spp_n), diffuse_(traceDiffuse)
+        : bufs_(d), n_(n), spp_n_(spp_n), n_lights_(n_lights), hit_spp_n_(hit_spp_n), diffuse_(traceDiffuse)
     {
         size_t scratch = 0;
         check(rls_trace_sss_hits_scratch_bytes(n, spp_n, max_hits, hitCapacity, n_lights, hit_spp_n, &scratch));
         const int64_t cap = hitCapacity, scap = cap * n_lights * 2 * hit_spp_n * hit_spp_n;
-        try {
-            q_.hit_capacity = cap;
-            q_.hit_count = static_cast<int64_t *>(alloc(sizeof(int64_t)));
-            q_.hit_element = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)cap));
-            if (n_lights > 0) {
-                rls_shadow_queue &s = q_.shadow;
-                s.capacity = scap;
-                s.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(cap + 1)));
-                s.dir = rls_vec3{falloc(scap), falloc(scap), falloc(scap)};
-                s.maxdist = falloc(scap);
-                s.weight_diffuse.r = falloc(scap);
-                s.kind = static_cast<uint8_t *>(alloc((size_t)scap));
-                s.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)scap));
-                s.sample = static_cast<uint8_t *>(alloc((size_t)scap));
-            }
-            if (traceDiffuse) {
-                rls_ray_queue &r = q_.diffuse;
-                r.capacity = cap;
-                r.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(cap + 1)));
-                r.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
-                r.weight.r = falloc(cap);
-                r.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
-            }
-            q_.scratch = alloc(scratch);
-            q_.scratch_bytes = scratch;
-        } catch (...) {
-            release();
-            throw;
+        q_.hit_capacity = cap;
+        q_.hit_count = bufs_.alloc<int64_t>(1);
+        q_.hit_element = bufs_.alloc<int64_t>(cap);
+        if (n_lights > 0) {
+            rls_shadow_queue &s = q_.shadow;
+            s.capacity = scap;
+            s.offsets = bufs_.alloc<int64_t>(cap + 1);
+            s.dir = bufs_.vec3(scap);
+            s.maxdist = bufs_.alloc<float>(scap);
+            s.weight_diffuse.r = bufs_.alloc<float>(scap);
+            s.kind = bufs_.alloc<uint8_t>(scap);
+            s.point = bufs_.alloc<uint32_t>(scap);
+            s.sample = bufs_.alloc<uint8_t>(scap);
         }
+        if (traceDiffuse) {
+            rls_ray_queue &r = q_.diffuse;
+            r.capacity = cap;
+            r.offsets = bufs_.alloc<int64_t>(cap + 1);
+            r.dir = bufs_.vec3(cap);
+            r.weight.r = bufs_.alloc<float>(cap);
+            r.point = bufs_.alloc<uint32_t>(cap);
+        }
+        q_.scratch = bufs_.alloc(scratch);
+        q_.scratch_bytes = scratch;
     }
-    ~HitQueues() { release(); }
     HitQueues(const HitQueues &) = delete;
     HitQueues &operator=(const HitQueues &) = delete;
 
@@ -289,39 +271,17 @@ public:
     int hitSppN() const { return hit_spp_n_; }
     bool traceDiffuse() const { return diffuse_; }
     // the TRUE number of shaded hits, the shadow rays, the diffuse rays (each synchronises)
-    int64_t hitCount() const { return read(q_.hit_count); }
+    int64_t hitCount() const { return bufs_.read(q_.hit_count); }
     int64_t listed() const { const int64_t c = hitCount(); return c < q_.hit_capacity ? c : q_.hit_capacity; }
-    int64_t shadowCount() const { return n_lights_ > 0 ? read(q_.shadow.offsets + q_.hit_capacity) : 0; }
-    int64_t diffuseCount() const { return diffuse_ ? read(q_.diffuse.offsets + q_.hit_capacity) : 0; }
+    int64_t shadowCount() const { return n_lights_ > 0 ? bufs_.read(q_.shadow.offsets + q_.hit_capacity) : 0; }
+    int64_t diffuseCount() const { return diffuse_ ? bufs_.read(q_.diffuse.offsets + q_.hit_capacity) : 0; }
 
 private:
-    int64_t read(const int64_t *p) const
-    {
-        int64_t c = 0;
-        check(rls_copy_to_host(dev_->ctx(), &c, p, sizeof(c)));
-        return c;
-    }
-    void release()
-    {
-        for (int k = 0; k < nbufs_; k++) rls_device_free(dev_->ctx(), bufs_[k]);
-        nbufs_ = 0;
-    }
-    void *alloc(size_t bytes)
-    {
-        void *p = nullptr;
-        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
-        bufs_[nbufs_++] = p;
-        return p;
-    }
-    float *falloc(int64_t count) { return static_cast<float *>(alloc(sizeof(float) * (size_t)count)); }
-
-    const Device *dev_;
+    detail::DeviceBuffers bufs_;
     int64_t n_;
     int spp_n_, n_lights_, hit_spp_n_;
     bool diffuse_;
     rls_hit_queues q_{};
-    void *bufs_[20] = {};
-    int nbufs_ = 0;
 };
 
 // shadeProbeSample's rays at the caller's hits (src/rlSss.h:415-418): c, P, q, cavityFade those of the scatter resolve the
@@ -333,8 +293,8 @@ inline void emitHits(const Device &d, const rls_sss_closure &c, const Planes &P,
 {
     if (hq.points() != q.points() || hq.sppN() != q.sppN() || hq.lights() != n_lights)
         throw Error(RLS_ERR_INVALID_ARGUMENT, "emitHits: queues of another size or light count");
-    const rls_cvec3 T = hitT ? rls_cvec3{hitT->plane(0), hitT->plane(1), hitT->plane(2)} : rls_cvec3{nullptr, nullptr, nullptr};
-    check(rls_trace_sss_hits_emit(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, q.sppN(), &q.c(), &hits,
+    const rls_cvec3 T = hitT ? hitT->cvec3() : rls_cvec3{nullptr, nullptr, nullptr};
+    check(rls_trace_sss_hits_emit(d.ctx(), q.points(), &c, P.cvec3(), q.sppN(), &q.c(), &hits,
                                   T, cavityFade ? 1 : 0, lights, n_lights, hq.hitSppN(), hq.traceDiffuse() ? 1 : 0, seed,
                                   hit_first_index, &hq.c()));
 }
@@ -346,10 +306,9 @@ inline void resolveHits(const Device &d, const rls_probe_hits &hits, const rls_s
                         const HitQueues &hq, const Planes &visibility, const Planes *radiance, Planes &E)
 {
     if (hq.lights() != n_lights) throw Error(RLS_ERR_INVALID_ARGUMENT, "resolveHits: queues of another light count");
-    const rls_crgb L = radiance ? rls_crgb{radiance->plane(0), radiance->plane(1), radiance->plane(2)}
-                                : rls_crgb{nullptr, nullptr, nullptr};
+    const rls_crgb L = radiance ? detail::crgb(*radiance) : rls_crgb{nullptr, nullptr, nullptr};
     check(rls_trace_sss_hits_resolve(d.ctx(), &hits, lights, n_lights, hq.hitSppN(), hq.traceDiffuse() ? 1 : 0, &hq.c(),
-                                     rls_crgb{visibility.plane(0), visibility.plane(1), visibility.plane(2)}, L, E.rgb()));
+                                     detail::crgb(visibility), L, E.rgb()));
 }
 
 // The device buffers of one light-loop emit (rls_shadow_queue): per-ray planes for n * n_lights * 3 * spp_n^2 rays, offsets
@@ -361,30 +320,24 @@ public:
     enum Node { Ggx, Disney, Skin, SkinScatter };
 
     ShadowQueue(const Device &d, int64_t n, int n_lights, int spp_n, Node node)
-        : dev_(&d), n_(n), n_lights_(n_lights), spp_n_(spp_n), node_(node)
+        : bufs_(d), n_(n), n_lights_(n_lights), spp_n_(spp_n), node_(node)
     {
         const int64_t cap = n * n_lights * (node == Skin || node == SkinScatter ? 2 : 3) * spp_n * spp_n;
         size_t scratch = 0;
         check(rls_trace_shadow_scratch_bytes(n, n_lights, spp_n, &scratch));
-        try {
-            q_.capacity = cap;
-            q_.offsets = static_cast<int64_t *>(alloc(sizeof(int64_t) * (size_t)(n + 1)));
-            q_.dir = rls_vec3{falloc(cap), falloc(cap), falloc(cap)};
-            q_.maxdist = falloc(cap);
-            if (node != SkinScatter) q_.weight_specular = rls_rgb{falloc(cap), falloc(cap), falloc(cap)};
-            if (node != Skin) q_.weight_diffuse.r = falloc(cap);
-            if (node == Disney) { q_.weight_diffuse.g = falloc(cap); q_.weight_diffuse.b = falloc(cap); }
-            q_.kind = static_cast<uint8_t *>(alloc((size_t)cap));
-            q_.point = static_cast<uint32_t *>(alloc(sizeof(uint32_t) * (size_t)cap));
-            q_.sample = static_cast<uint8_t *>(alloc((size_t)cap));
-            q_.scratch = alloc(scratch);
-            q_.scratch_bytes = scratch;
-        } catch (...) {
-            release();
-            throw;
-        }
+        q_.capacity = cap;
+        q_.offsets = bufs_.alloc<int64_t>(n + 1);
+        q_.dir = bufs_.vec3(cap);
+        q_.maxdist = bufs_.alloc<float>(cap);
+        if (node != SkinScatter) q_.weight_specular = rls_rgb{bufs_.alloc<float>(cap), bufs_.alloc<float>(cap), bufs_.alloc<float>(cap)};
+        if (node != Skin) q_.weight_diffuse.r = bufs_.alloc<float>(cap);
+        if (node == Disney) { q_.weight_diffuse.g = bufs_.alloc<float>(cap); q_.weight_diffuse.b = bufs_.alloc<float>(cap); }
+        q_.kind = bufs_.alloc<uint8_t>(cap);
+        q_.point = bufs_.alloc<uint32_t>(cap);
+        q_.sample = bufs_.alloc<uint8_t>(cap);
+        q_.scratch = bufs_.alloc(scratch);
+        q_.scratch_bytes = scratch;
     }
-    ~ShadowQueue() { release(); }
     ShadowQueue(const ShadowQueue &) = delete;
     ShadowQueue &operator=(const ShadowQueue &) = delete;
 
@@ -394,35 +347,14 @@ public:
     int sppN() const { return spp_n_; }
     Node node() const { return node_; }
     // offsets[n]: the number of rays (synchronises)
-    int64_t count() const
-    {
-        int64_t c = 0;
-        check(rls_copy_to_host(dev_->ctx(), &c, q_.offsets + n_, sizeof(c)));
-        return c;
-    }
+    int64_t count() const { return bufs_.read(q_.offsets + n_); }
 
 private:
-    void release()
-    {
-        for (int k = 0; k < nbufs_; k++) rls_device_free(dev_->ctx(), bufs_[k]);
-        nbufs_ = 0;
-    }
-    void *alloc(size_t bytes)
-    {
-        void *p = nullptr;
-        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
-        bufs_[nbufs_++] = p;
-        return p;
-    }
-    float *falloc(int64_t count) { return static_cast<float *>(alloc(sizeof(float) * (size_t)count)); }
-
-    const Device *dev_;
+    detail::DeviceBuffers bufs_;
     int64_t n_;
     int n_lights_, spp_n_;
     Node node_;
     rls_shadow_queue q_{};
-    void *bufs_[16] = {};
-    int nbufs_ = 0;
 };
 
 inline void checkShadowQueue(const ShadowQueue &q, ShadowQueue::Node node, int64_t n, int n_lights, int spp_n, const char *who)
@@ -438,7 +370,7 @@ inline void emitDirect(const Device &d, const rls_ggx_closure &c, const rls_ggx_
                        uint64_t first_index = 0)
 {
     checkShadowQueue(q, ShadowQueue::Ggx, n, n_lights, spp_n, "emitDirect: a queue of another node, size or light count");
-    check(rls_trace_ggx_direct_emit(d.ctx(), n, &c, &sh, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights,
+    check(rls_trace_ggx_direct_emit(d.ctx(), n, &c, &sh, P.cvec3(), lights, n_lights,
                                     spp_n, seed, first_index, &q.c()));
 }
 
@@ -447,7 +379,7 @@ inline void emitDirect(const Device &d, const rls_disney_closure &c, const Plane
                        int n_lights, int64_t n, int spp_n, uint32_t seed, ShadowQueue &q, uint64_t first_index = 0)
 {
     checkShadowQueue(q, ShadowQueue::Disney, n, n_lights, spp_n, "emitDirect: a queue of another node, size or light count");
-    check(rls_trace_disney_direct_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n,
+    check(rls_trace_disney_direct_emit(d.ctx(), n, &c, P.cvec3(), lights, n_lights, spp_n,
                                        seed, first_index, &q.c()));
 }
 
@@ -458,8 +390,7 @@ inline void resolveDirect(const Device &d, const rls_ggx_closure &c, const rls_g
                           Planes &directSpecular)
 {
     checkShadowQueue(q, ShadowQueue::Ggx, q.points(), n_lights, q.sppN(), "resolveDirect: a queue of another node or light count");
-    check(rls_trace_ggx_direct_resolve(d.ctx(), q.points(), &c, &sh, lights, n_lights, q.sppN(), &q.c(),
-                                       rls_crgb{visibility.plane(0), visibility.plane(1), visibility.plane(2)},
+    check(rls_trace_ggx_direct_resolve(d.ctx(), q.points(), &c, &sh, lights, n_lights, q.sppN(), &q.c(), detail::crgb(visibility),
                                        directDiffuse.rgb(), directSpecular.rgb()));
 }
 
@@ -467,8 +398,7 @@ inline void resolveDirect(const Device &d, const rls_sphere_light *lights, int n
                           const Planes &visibility, Planes &directDiffuse, Planes &directSpecular)
 {
     checkShadowQueue(q, ShadowQueue::Disney, q.points(), n_lights, q.sppN(), "resolveDirect: a queue of another node or light count");
-    check(rls_trace_disney_direct_resolve(d.ctx(), q.points(), lights, n_lights, q.sppN(), &q.c(),
-                                          rls_crgb{visibility.plane(0), visibility.plane(1), visibility.plane(2)},
+    check(rls_trace_disney_direct_resolve(d.ctx(), q.points(), lights, n_lights, q.sppN(), &q.c(), detail::crgb(visibility),
                                           directDiffuse.rgb(), directSpecular.rgb()));
 }
 
@@ -483,12 +413,11 @@ public:
         q_.shadow = shadow_ ? &shadow_->c() : nullptr;
         q_.glossy = &glossy_.c(); q_.refract = &refract_.c(); q_.diffuse = &diffuse_.c();
     }
-    ~GgxNodeQueues() { delete shadow_; }
     GgxNodeQueues(const GgxNodeQueues &) = delete;
     GgxNodeQueues &operator=(const GgxNodeQueues &) = delete;
 
     const rls_ggx_node_queues &c() const { return q_; }
-    const ShadowQueue *shadow() const { return shadow_; }          // nullptr without lights
+    const ShadowQueue *shadow() const { return shadow_.get(); }    // nullptr without lights
     const RayQueue &glossy() const { return glossy_; }
     const RayQueue &refract() const { return refract_; }
     const RayQueue &diffuse() const { return diffuse_; }
@@ -499,7 +428,7 @@ public:
 private:
     int64_t n_;
     int n_lights_, spp_n_;
-    ShadowQueue *shadow_;
+    std::unique_ptr<ShadowQueue> shadow_;
     RayQueue glossy_, refract_, diffuse_;
     rls_ggx_node_queues q_{};
 };
@@ -515,12 +444,11 @@ public:
         q_.shadow = shadow_ ? &shadow_->c() : nullptr;
         q_.diffuse = &diffuse_.c(); q_.specular = &specular_.c();
     }
-    ~DisneyNodeQueues() { delete shadow_; }
     DisneyNodeQueues(const DisneyNodeQueues &) = delete;
     DisneyNodeQueues &operator=(const DisneyNodeQueues &) = delete;
 
     const rls_disney_node_queues &c() const { return q_; }
-    const ShadowQueue *shadow() const { return shadow_; }
+    const ShadowQueue *shadow() const { return shadow_.get(); }
     const RayQueue &diffuse() const { return diffuse_; }
     const RayQueue &specular() const { return specular_; }
     int64_t points() const { return n_; }
@@ -530,7 +458,7 @@ public:
 private:
     int64_t n_;
     int n_lights_, spp_n_;
-    ShadowQueue *shadow_;
+    std::unique_ptr<ShadowQueue> shadow_;
     RayQueue diffuse_, specular_;
     rls_disney_node_queues q_{};
 };
@@ -551,13 +479,12 @@ public:
         q_.sheen_glossy = &sheen_glossy_.c(); q_.specular_glossy = &specular_glossy_.c(); q_.probes = &probes_.c();
         q_.sheenFresnel = scalars_.plane(0); q_.specularFresnel = scalars_.plane(1); q_.sssWeight = scalars_.plane(2);
     }
-    ~SkinNodeQueues() { delete sheen_shadow_; delete specular_shadow_; }
     SkinNodeQueues(const SkinNodeQueues &) = delete;
     SkinNodeQueues &operator=(const SkinNodeQueues &) = delete;
 
     const rls_skin_node_queues &c() const { return q_; }
-    const ShadowQueue *sheenShadow() const { return sheen_shadow_; }          // nullptr without lights
-    const ShadowQueue *specularShadow() const { return specular_shadow_; }
+    const ShadowQueue *sheenShadow() const { return sheen_shadow_.get(); }    // nullptr without lights
+    const ShadowQueue *specularShadow() const { return specular_shadow_.get(); }
     const RayQueue &sheenGlossy() const { return sheen_glossy_; }
     const RayQueue &specularGlossy() const { return specular_glossy_; }
     const ProbeQueue &probes() const { return probes_; }
@@ -569,7 +496,7 @@ public:
 private:
     int64_t n_;
     int n_lights_, spp_n_;
-    ShadowQueue *sheen_shadow_, *specular_shadow_;
+    std::unique_ptr<ShadowQueue> sheen_shadow_, specular_shadow_;
     RayQueue sheen_glossy_, specular_glossy_;
     ProbeQueue probes_;
     Planes scalars_;
@@ -587,29 +514,60 @@ public:
         q_.node = node_.c();
         q_.diffuse_shadow = diffuse_shadow_ ? &diffuse_shadow_->c() : nullptr;
     }
-    ~SkinBounceQueues() { delete diffuse_shadow_; }
     SkinBounceQueues(const SkinBounceQueues &) = delete;
     SkinBounceQueues &operator=(const SkinBounceQueues &) = delete;
 
     const rls_skin_bounce_queues &c() const { return q_; }
     const SkinNodeQueues &node() const { return node_; }
-    const ShadowQueue *diffuseShadow() const { return diffuse_shadow_; }      // nullptr without lights
+    const ShadowQueue *diffuseShadow() const { return diffuse_shadow_.get(); } // nullptr without lights
     int64_t points() const { return node_.points(); }
     int lights() const { return node_.lights(); }
     int sppN() const { return node_.sppN(); }
 
 private:
     SkinNodeQueues node_;
-    ShadowQueue *diffuse_shadow_;
+    std::unique_ptr<ShadowQueue> diffuse_shadow_;
     rls_skin_bounce_queues q_{};
 };
 
+// what resolveNode and resolveBounce of a node both fill: the traced struct from the caller's planes, the AOV struct from aovs
+// (the planes in the struct's order, 3 each) and out (sg->out.RGB or nullptr)
 namespace detail {
-inline rls_crgb crgb(const Planes &p) { return p.empty() ? rls_crgb{nullptr, nullptr, nullptr} : rls_crgb{p.plane(0), p.plane(1), p.plane(2)}; }
-template <class Q>
-inline void checkNodeQueues(const Q &q, int64_t n, int n_lights, int spp_n, const char *who)
+inline rls_ggx_node_traced ggxTraced(const Planes &visibility, const Planes &glossy, const Planes &refract, const Planes &diffuse)
 {
-    if (q.points() != n || q.lights() != n_lights || q.sppN() != spp_n) throw Error(RLS_ERR_INVALID_ARGUMENT, who);
+    return rls_ggx_node_traced{crgb(visibility), crgb(glossy), crgb(refract), crgb(diffuse)};
+}
+inline rls_ggx_shade_out ggxOut(Planes &aovs, Planes *out)
+{
+    rls_ggx_shade_out o = {};
+    o.direct_diffuse = aovs.rgb(0); o.direct_specular = aovs.rgb(3); o.refraction = aovs.rgb(6);
+    o.indirect_diffuse = aovs.rgb(9); o.indirect_specular = aovs.rgb(12);
+    if (out) o.out = out->rgb();
+    return o;
+}
+inline rls_disney_node_traced disneyTraced(const Planes &visibility, const Planes &diffuse, const Planes &specular)
+{
+    return rls_disney_node_traced{crgb(visibility), crgb(diffuse), crgb(specular)};
+}
+inline rls_disney_shade_out disneyOut(Planes &aovs, Planes *out)
+{
+    rls_disney_shade_out o = {};
+    o.direct_diffuse = aovs.rgb(0); o.direct_specular = aovs.rgb(3); o.indirect_diffuse = aovs.rgb(6);
+    o.indirect_specular = aovs.rgb(9);
+    if (out) o.out = out->rgb();
+    return o;
+}
+inline rls_skin_node_traced skinTraced(const Planes &sheenVisibility, const Planes &specularVisibility, const Planes &sheenGlossy,
+                                       const Planes &specularGlossy, const rls_probe_hits &hits)
+{
+    return rls_skin_node_traced{crgb(sheenVisibility), crgb(specularVisibility), crgb(sheenGlossy), crgb(specularGlossy), &hits};
+}
+inline rls_skin_integrate_out skinOut(Planes &aovs, Planes *out)
+{
+    rls_skin_integrate_out o = {};
+    o.sheen = aovs.rgb(0); o.specular = aovs.rgb(3); o.sss = aovs.rgb(6);
+    if (out) o.out = out->rgb();
+    return o;
 }
 } // namespace detail
 
@@ -620,7 +578,7 @@ inline void emitNode(const Device &d, const rls_ggx_closure &c, const rls_ggx_sh
                      GgxNodeQueues &q, uint64_t first_index = 0)
 {
     detail::checkNodeQueues(q, n, n_lights, spp_n, "emitNode: queues of another size or light count");
-    check(rls_trace_ggx_shade_emit(d.ctx(), n, &c, &sh, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights,
+    check(rls_trace_ggx_shade_emit(d.ctx(), n, &c, &sh, P.cvec3(), lights, n_lights,
                                    traced ? 1 : 0, spp_n, seed, first_index, &q.c()));
 }
 
@@ -629,7 +587,7 @@ inline void emitNode(const Device &d, const rls_disney_closure &c, const Planes 
                      int n_lights, int64_t n, int spp_n, uint32_t seed, DisneyNodeQueues &q, uint64_t first_index = 0)
 {
     detail::checkNodeQueues(q, n, n_lights, spp_n, "emitNode: queues of another size or light count");
-    check(rls_trace_disney_shade_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n,
+    check(rls_trace_disney_shade_emit(d.ctx(), n, &c, P.cvec3(), lights, n_lights, spp_n,
                                       seed, first_index, &q.c()));
 }
 
@@ -641,11 +599,8 @@ inline void resolveNode(const Device &d, const rls_ggx_closure &c, const rls_ggx
                         const Planes &refract, const Planes &diffuse, Planes &aovs, Planes *out = nullptr)
 {
     detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveNode: queues of another light count");
-    rls_ggx_node_traced t = {detail::crgb(visibility), detail::crgb(glossy), detail::crgb(refract), detail::crgb(diffuse)};
-    rls_ggx_shade_out o = {};
-    o.direct_diffuse = aovs.rgb(0); o.direct_specular = aovs.rgb(3); o.refraction = aovs.rgb(6);
-    o.indirect_diffuse = aovs.rgb(9); o.indirect_specular = aovs.rgb(12);
-    if (out) o.out = out->rgb();
+    const rls_ggx_node_traced t = detail::ggxTraced(visibility, glossy, refract, diffuse);
+    const rls_ggx_shade_out o = detail::ggxOut(aovs, out);
     check(rls_trace_ggx_shade_resolve(d.ctx(), q.points(), &c, &sh, lights, n_lights, traced ? 1 : 0, q.sppN(), &q.c(), &t, &o));
 }
 
@@ -655,11 +610,8 @@ inline void resolveNode(const Device &d, const rls_sphere_light *lights, int n_l
                         Planes *out = nullptr)
 {
     detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveNode: queues of another light count");
-    rls_disney_node_traced t = {detail::crgb(visibility), detail::crgb(diffuse), detail::crgb(specular)};
-    rls_disney_shade_out o = {};
-    o.direct_diffuse = aovs.rgb(0); o.direct_specular = aovs.rgb(3); o.indirect_diffuse = aovs.rgb(6);
-    o.indirect_specular = aovs.rgb(9);
-    if (out) o.out = out->rgb();
+    const rls_disney_node_traced t = detail::disneyTraced(visibility, diffuse, specular);
+    const rls_disney_shade_out o = detail::disneyOut(aovs, out);
     check(rls_trace_disney_shade_resolve(d.ctx(), q.points(), lights, n_lights, q.sppN(), &q.c(), &t, &o));
 }
 
@@ -717,7 +669,7 @@ inline void emitBounce(const Device &d, const rls_ggx_closure &c, const rls_ggx_
                        const rls_ray_state &state, const rls_gi_depths &depths, GgxNodeQueues &q, uint64_t first_index = 0)
 {
     detail::checkNodeQueues(q, n, n_lights, spp_n, "emitBounce: queues of another size or light count");
-    check(rls_trace_ggx_bounce_emit(d.ctx(), n, &c, &sh, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n,
+    check(rls_trace_ggx_bounce_emit(d.ctx(), n, &c, &sh, P.cvec3(), lights, n_lights, spp_n,
                                     seed, first_index, &state, &depths, &q.c()));
 }
 inline void emitBounce(const Device &d, const rls_disney_closure &c, const Planes &P, const rls_sphere_light *lights,
@@ -725,7 +677,7 @@ inline void emitBounce(const Device &d, const rls_disney_closure &c, const Plane
                        const rls_gi_depths &depths, DisneyNodeQueues &q, uint64_t first_index = 0)
 {
     detail::checkNodeQueues(q, n, n_lights, spp_n, "emitBounce: queues of another size or light count");
-    check(rls_trace_disney_bounce_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n,
+    check(rls_trace_disney_bounce_emit(d.ctx(), n, &c, P.cvec3(), lights, n_lights, spp_n,
                                        seed, first_index, &state, &depths, &q.c()));
 }
 
@@ -736,11 +688,8 @@ inline void resolveBounce(const Device &d, const rls_ggx_closure &c, const rls_g
                           Planes &aovs, Planes *out = nullptr)
 {
     detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveBounce: queues of another light count");
-    rls_ggx_node_traced t = {detail::crgb(visibility), detail::crgb(glossy), detail::crgb(refract), detail::crgb(diffuse)};
-    rls_ggx_shade_out o = {};
-    o.direct_diffuse = aovs.rgb(0); o.direct_specular = aovs.rgb(3); o.refraction = aovs.rgb(6);
-    o.indirect_diffuse = aovs.rgb(9); o.indirect_specular = aovs.rgb(12);
-    if (out) o.out = out->rgb();
+    const rls_ggx_node_traced t = detail::ggxTraced(visibility, glossy, refract, diffuse);
+    const rls_ggx_shade_out o = detail::ggxOut(aovs, out);
     check(rls_trace_ggx_bounce_resolve(d.ctx(), q.points(), &c, &sh, lights, n_lights, q.sppN(), &state, &depths, &q.c(), &t, &o));
 }
 // rlDisney: c as the emit took it (its materials index serves the scales), the node's indirectDiffuseScale / indirectSpecularScale
@@ -751,11 +700,8 @@ inline void resolveBounce(const Device &d, const rls_disney_closure &c, rls_para
                           Planes *out = nullptr)
 {
     detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveBounce: queues of another light count");
-    rls_disney_node_traced t = {detail::crgb(visibility), detail::crgb(diffuse), detail::crgb(specular)};
-    rls_disney_shade_out o = {};
-    o.direct_diffuse = aovs.rgb(0); o.direct_specular = aovs.rgb(3); o.indirect_diffuse = aovs.rgb(6);
-    o.indirect_specular = aovs.rgb(9);
-    if (out) o.out = out->rgb();
+    const rls_disney_node_traced t = detail::disneyTraced(visibility, diffuse, specular);
+    const rls_disney_shade_out o = detail::disneyOut(aovs, out);
     check(rls_trace_disney_bounce_resolve(d.ctx(), q.points(), &c, indirectDiffuseScale, indirectSpecularScale, lights, n_lights,
                                           q.sppN(), &state, &depths, &q.c(), &t, &o));
 }
@@ -776,7 +722,7 @@ inline void emitNode(const Device &d, const rls_skin_closure &c, const Planes &P
                      int64_t n, int spp_n, uint32_t seed, SkinNodeQueues &q, uint64_t first_index = 0)
 {
     detail::checkNodeQueues(q, n, n_lights, spp_n, "emitNode: queues of another size or light count");
-    check(rls_trace_skin_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n, seed,
+    check(rls_trace_skin_emit(d.ctx(), n, &c, P.cvec3(), lights, n_lights, spp_n, seed,
                               first_index, &q.c()));
 }
 
@@ -789,12 +735,9 @@ inline void resolveNode(const Device &d, const rls_skin_closure &c, const Planes
                         bool literalMatrix, Planes &aovs, Planes *out = nullptr)
 {
     detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveNode: queues of another light count");
-    rls_skin_node_traced t = {detail::crgb(sheenVisibility), detail::crgb(specularVisibility), detail::crgb(sheenGlossy),
-                              detail::crgb(specularGlossy), &hits};
-    rls_skin_integrate_out o = {};
-    o.sheen = aovs.rgb(0); o.specular = aovs.rgb(3); o.sss = aovs.rgb(6);
-    if (out) o.out = out->rgb();
-    check(rls_trace_skin_resolve(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights,
+    const rls_skin_node_traced t = detail::skinTraced(sheenVisibility, specularVisibility, sheenGlossy, specularGlossy, hits);
+    const rls_skin_integrate_out o = detail::skinOut(aovs, out);
+    check(rls_trace_skin_resolve(d.ctx(), q.points(), &c, P.cvec3(), lights, n_lights,
                                  cavityFade ? 1 : 0, literalMatrix ? 1 : 0, q.sppN(), &q.c(), &t, &o));
 }
 
@@ -805,7 +748,7 @@ inline void emitBounce(const Device &d, const rls_skin_closure &c, const Planes 
                        SkinBounceQueues &q, uint64_t first_index = 0)
 {
     detail::checkNodeQueues(q, n, n_lights, spp_n, "emitBounce: queues of another size or light count");
-    check(rls_trace_skin_bounce_emit(d.ctx(), n, &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights, spp_n, seed,
+    check(rls_trace_skin_bounce_emit(d.ctx(), n, &c, P.cvec3(), lights, n_lights, spp_n, seed,
                                      first_index, &state, &depths, &q.c()));
 }
 inline void resolveBounce(const Device &d, const rls_skin_closure &c, const Planes &P, const rls_sphere_light *lights,
@@ -815,12 +758,10 @@ inline void resolveBounce(const Device &d, const rls_skin_closure &c, const Plan
                           bool cavityFade, bool literalMatrix, Planes &aovs, Planes *out = nullptr)
 {
     detail::checkNodeQueues(q, q.points(), n_lights, q.sppN(), "resolveBounce: queues of another light count");
-    rls_skin_bounce_traced t = {{detail::crgb(sheenVisibility), detail::crgb(specularVisibility), detail::crgb(sheenGlossy),
-                                 detail::crgb(specularGlossy), &hits}, detail::crgb(diffuseVisibility)};
-    rls_skin_integrate_out o = {};
-    o.sheen = aovs.rgb(0); o.specular = aovs.rgb(3); o.sss = aovs.rgb(6);
-    if (out) o.out = out->rgb();
-    check(rls_trace_skin_bounce_resolve(d.ctx(), q.points(), &c, rls_cvec3{P.plane(0), P.plane(1), P.plane(2)}, lights, n_lights,
+    const rls_skin_bounce_traced t = {detail::skinTraced(sheenVisibility, specularVisibility, sheenGlossy, specularGlossy, hits),
+                                      detail::crgb(diffuseVisibility)};
+    const rls_skin_integrate_out o = detail::skinOut(aovs, out);
+    check(rls_trace_skin_bounce_resolve(d.ctx(), q.points(), &c, P.cvec3(), lights, n_lights,
                                         cavityFade ? 1 : 0, literalMatrix ? 1 : 0, q.sppN(), &state, &depths, &q.c(), &t, &o));
 }
 
@@ -851,19 +792,13 @@ class ShadowHits {
 public:
     enum Form { Direct, Indexed };
 
-    ShadowHits(const Device &d, int64_t rays, int maxHits, Form form) : dev_(&d), rays_(rays), max_hits_(maxHits), form_(form)
+    ShadowHits(const Device &d, int64_t rays, int maxHits, Form form) : bufs_(d), rays_(rays), max_hits_(maxHits), form_(form)
     {
-        const size_t elements = (size_t)rays * (size_t)maxHits;
-        try {
-            count_ = static_cast<uint8_t *>(alloc((size_t)rays));
-            if (form == Direct) opacity_ = static_cast<float *>(alloc(3 * elements * sizeof(float)));
-            else index_ = static_cast<uint32_t *>(alloc(elements * sizeof(uint32_t)));
-        } catch (...) {
-            release();
-            throw;
-        }
+        const int64_t elements = rays * maxHits;
+        count_ = bufs_.alloc<uint8_t>(rays);
+        if (form == Direct) opacity_ = bufs_.alloc<float>(3 * elements);
+        else index_ = bufs_.alloc<uint32_t>(elements);
     }
-    ~ShadowHits() { release(); }
     ShadowHits(const ShadowHits &) = delete;
     ShadowHits &operator=(const ShadowHits &) = delete;
 
@@ -886,28 +821,13 @@ public:
     }
 
 private:
-    void release()
-    {
-        for (int k = 0; k < nbufs_; k++) rls_device_free(dev_->ctx(), bufs_[k]);
-        nbufs_ = 0;
-    }
-    void *alloc(size_t bytes)
-    {
-        void *p = nullptr;
-        check(rls_device_alloc(dev_->ctx(), bytes > 0 ? bytes : 1, &p));
-        bufs_[nbufs_++] = p;
-        return p;
-    }
-
-    const Device *dev_;
+    detail::DeviceBuffers bufs_;
     int64_t rays_;
     int max_hits_;
     Form form_;
     uint8_t *count_ = nullptr;
     float *opacity_ = nullptr;
     uint32_t *index_ = nullptr;
-    void *bufs_[2] = {};
-    int nbufs_ = 0;
 };
 
 // the visibility of the shadow rays from their hits' opacities (rls_trace_shadow_visibility): base (an empty Planes: 1) times
