@@ -660,6 +660,70 @@ rls_status rls_trace_skin_bounce_resolve(rls_context *ctx, int64_t n, const rls_
                                          const rls_skin_bounce_traced *t, const rls_skin_integrate_out *out);
 
 /* ------------------------------------------------------------------------------------------
+ * Routing a queue's hits to the nodes.  A queue's rays land on surfaces that carry different nodes, or on nothing; every node
+ * call above takes a batch of points of ONE node.  The five calls below take a traced queue from "a hit per ray" to "a dense
+ * batch per node" and back:
+ *
+ *   rls_trace_route_hits     bin[k] (one byte per ray, written by the tracer: the node bin of the surface ray k hit, any value
+ *                            >= bins -- 255 by convention -- a miss) -> a STABLE partition of the ray indices by bin:
+ *                              key(k) = bin[k] < bins ? bin[k] : bins
+ *                              order  = the ray indices sorted by key, ASCENDING within a key (numpy: argsort(key, kind="stable"))
+ *                              offsets[b] = the number of rays with key < b, b = 0 .. bins + 1  (offsets[0] = 0, offsets[bins + 1] = rays)
+ *                              slot   = the inverse permutation, order[slot[k]] == k  (where asked)
+ *                            Bin b's rays are order[offsets[b] .. offsets[b + 1]); the misses are bin index `bins`.
+ *   rls_trace_route_gather   dst[j] = src[index[j]], j < m, for every plane: a bin's hit data (P, N, T, wo, material ids, the
+ *                            advanced rls_ray_state) out of the per-ray planes into the dense batch a node call takes.
+ *                            index = order + offsets[b], m = offsets[b + 1] - offsets[b].
+ *   rls_trace_route_scatter  dst[index[j]] = src[j]: a child batch's `out` back to its rays' places in the parent's radiance planes.
+ *   rls_trace_route_fill     dst[p][index[j]] = value[p]: the misses' environment radiance (or a visibility).
+ *
+ * The caller reads offsets once with rls_copy_to_host (bins + 2 values): the bin sizes are the host argument n of the node
+ * calls.  Word planes move as 32-bit patterns and byte planes as bytes: NaN payloads, -0, denormals and integer ids come through
+ * bit for bit, and EXACT and FAST contexts write the same bytes.  Every position is a function of the inputs alone (a counting
+ * sort from wavefront ballots and the queues' scan: no atomic), so a replay writes the same order.
+ *
+ * Scatter and fill write each index once where the index has no duplicate (a range of `order` has none); with duplicates which
+ * write lasts is not defined.  Nothing is written outside index's elements (scatter, fill), dst[0, m) (gather), order[0, rays),
+ * slot[0, rays) and offsets[0, bins + 2).  Finer routing than a node bin -- many instances of one node -- is rls_material_index's.
+ *
+ * All pointers are the caller's device memory except rls_trace_route_fill's dst and value, host arrays read during the call
+ * (the plane structs travel by value: nothing of the host's is read after a call returns).  Nothing is allocated, no call
+ * synchronises the host, every call can be recorded into an rls_graph.  m == 0 launches nothing; rls_trace_route_hits at
+ * rays == 0 writes offsets (all 0) and nothing else.  Refused with RLS_ERR_INVALID_ARGUMENT before the context is read: a NULL
+ * ctx, routes, offsets, scratch or planes, a NULL bin or order (rays > 0) or index (m > 0); bins outside 1 .. 16; scratch_bytes below
+ * rls_trace_route_scratch_bytes(rays, bins); rays < 0 or m < 0; n_w32 outside 0 .. RLS_ROUTE_MAX_W32, n_u8 outside 0 ..
+ * RLS_ROUTE_MAX_U8 or no plane at all; n_planes outside 1 .. RLS_ROUTE_MAX_W32; a NULL plane below its count; dst == src for
+ * the same plane of a gather or scatter (the result would depend on scheduling).  rays > 2^32 - 1: RLS_ERR_UNSUPPORTED (order
+ * is 32-bit; route in chunks).
+ * ---------------------------------------------------------------------------------------- */
+
+enum { RLS_ROUTE_MAX_BINS = 16, RLS_ROUTE_MAX_W32 = 24, RLS_ROUTE_MAX_U8 = 8 };
+
+typedef struct rls_hit_routes {
+    int bins;                /* node bins 0 .. bins - 1, 1 <= bins <= 16; bin index `bins` collects the misses */
+    int64_t *offsets;        /* [bins + 2]: bin b owns order[offsets[b], offsets[b + 1]); offsets[bins + 1] == rays */
+    uint32_t *order;         /* [rays]: ray indices grouped by bin, ascending within a bin */
+    uint32_t *slot;          /* [rays], NULL-able: the inverse, order[slot[k]] == k */
+    void *scratch;           /* >= rls_trace_route_scratch_bytes(rays, bins) */
+    size_t scratch_bytes;
+} rls_hit_routes;
+
+typedef struct rls_route_planes {
+    int n_w32, n_u8;                             /* planes of 32-bit words (float, uint32 ids) and of bytes (rls_ray_state) */
+    const void *src_w32[RLS_ROUTE_MAX_W32];
+    void *dst_w32[RLS_ROUTE_MAX_W32];
+    const uint8_t *src_u8[RLS_ROUTE_MAX_U8];
+    uint8_t *dst_u8[RLS_ROUTE_MAX_U8];
+} rls_route_planes;
+
+rls_status rls_trace_route_scratch_bytes(int64_t rays, int bins, size_t *bytes);
+rls_status rls_trace_route_hits(rls_context *ctx, int64_t rays, const uint8_t *bin, const rls_hit_routes *r);
+rls_status rls_trace_route_gather(rls_context *ctx, int64_t m, const uint32_t *index, const rls_route_planes *p);
+rls_status rls_trace_route_scatter(rls_context *ctx, int64_t m, const uint32_t *index, const rls_route_planes *p);
+rls_status rls_trace_route_fill(rls_context *ctx, int64_t m, const uint32_t *index, int n_planes, float *const *dst,
+                                const float *value);
+
+/* ------------------------------------------------------------------------------------------
  * Shadow rays' hits: the opacity each node returns, and the visibility of a shadow ray folded from the opacities of the surfaces
  * it crosses -- the plane every light-loop and node resolve above reads ("1 - sg->Lo in Arnold's terms").
  *

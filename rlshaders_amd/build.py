@@ -188,7 +188,7 @@ def build_trace_library(force: bool = False, verbose: bool = False) -> Path:
 
 
 def build_trace_example(verbose: bool = False, name: str = "example_trace") -> Path:
-    """host/example_trace.cpp (or ``name``: example_trace_bounce, example_trace_skin_bounce, example_trace_shadow) against both libraries (emit -> a host-side \"tracer\" ->
+    """host/example_trace.cpp (or ``name``: example_trace_bounce, example_trace_skin_bounce, example_trace_shadow, example_trace_path) against both libraries (emit -> a host-side \"tracer\" ->
     resolve)."""
     OBJDIR.mkdir(exist_ok=True)
     lib = build_trace_library(verbose=verbose)

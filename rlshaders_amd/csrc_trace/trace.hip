@@ -17,7 +17,8 @@
 // probe-hit shading are one shape, written once: check_hit_list_queue, set_hit_list_staging, compact_hit_list,
 // hit_list_resolve_io.
 // The visibility the light loops' resolves read has four verbs of its own at the end of this file (rls_trace_opacity.hpp): the
-// opacity each node returns at a shadow ray's hit, and the fold of a ray's hits into its visibility.
+// opacity each node returns at a shadow ray's hit, and the fold of a ray's hits into its visibility.  After them the five verbs
+// that route a traced queue's hits to the nodes (rls_trace_route.hpp): the stable partition by node bin, gather, scatter, fill.
 //
 // Built twice like the closure units of librlshaders_amd.so (rlshaders_amd/build.py, build_trace_library): RLS_FAST=0
 // carries the C ABI, the EXACT emit kernels and the mode-free scan / compact / resolve kernels; RLS_FAST=1 the FAST emit
@@ -37,6 +38,7 @@ namespace {
 #include "rls_trace_node_resolve.hpp"
 #include "rls_trace_hits.hpp"
 #include "rls_trace_opacity.hpp"
+#include "rls_trace_route.hpp"
 
 // one launch of the rlSss emit or resolve: a workgroup per tile of io.tile_points points, grid-striding past the cap
 template <class IO>
@@ -1390,6 +1392,135 @@ rls_status rls_trace_shadow_visibility(rls_context *ctx, int64_t rays, const rls
     RLS_REQUIRE(rlsh::has3(visibility), "NULL output plane");
     const ShadowFoldIO io = { *h, base, visibility, rays };
     hipLaunchKernelGGL(shadow_visibility_kernel, rlsh::grid_for(ctx, rays), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(__func__);
+}
+
+} // extern "C"
+
+// ---- routing a queue's hits to the nodes (rls_trace_route.hpp) ----------------------------------------------------------------
+namespace {
+
+// The scratch of rls_trace_route_hits, each part 256-byte aligned: the bin-major counts of (bins + 1) keys x tiles, scanned in
+// place, with the grand total behind them, then the scan's tile sums.
+struct RouteScratch {
+    int64_t *counts, *totals;
+    int64_t tiles, cells;
+    size_t bytes;
+};
+inline RouteScratch route_scratch(void *base, int64_t rays, int bins)
+{
+    RouteScratch s = {};
+    s.tiles = (rays + kRouteTile - 1) / kRouteTile;
+    s.cells = (int64_t)(bins + 1) * s.tiles;
+    char *p = (char *)base;
+    s.counts = (int64_t *)p;
+    size_t off = align256((size_t)(s.cells + 1) * sizeof(int64_t));
+    s.totals = (int64_t *)(p + off);
+    off += align256((size_t)std::max<int64_t>(scan_tiles(s.cells), 1) * sizeof(int64_t));
+    s.bytes = off;
+    return s;
+}
+rls_status check_route_size(const char *fn, int64_t rays, int bins)
+{
+    RLS_REQUIRE_IN(fn, rays >= 0, "rays < 0");
+    if (rays > (int64_t)UINT32_MAX) {
+        rlsh::set_error("%s: %s", fn, "rays > 2^32 - 1 (order is 32-bit: route in chunks)");
+        return RLS_ERR_UNSUPPORTED;
+    }
+    RLS_REQUIRE_IN(fn, bins >= 1 && bins <= RLS_ROUTE_MAX_BINS, "bins must be in [1, 16]");
+    return RLS_OK;
+}
+
+// what gather and scatter check of their arguments, ahead of the m == 0 return
+rls_status check_route_planes(const char *fn, const rls_context *ctx, int64_t m, const uint32_t *index, const rls_route_planes *p)
+{
+    RLS_REQUIRE_IN(fn, ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE_IN(fn, m >= 0, "m < 0");
+    RLS_REQUIRE_IN(fn, p != nullptr, "planes is NULL");
+    RLS_REQUIRE_IN(fn, p->n_w32 >= 0 && p->n_w32 <= RLS_ROUTE_MAX_W32, "planes.n_w32 must be in [0, 24]");
+    RLS_REQUIRE_IN(fn, p->n_u8 >= 0 && p->n_u8 <= RLS_ROUTE_MAX_U8, "planes.n_u8 must be in [0, 8]");
+    RLS_REQUIRE_IN(fn, p->n_w32 + p->n_u8 > 0, "planes holds no plane");
+    for (int k = 0; k < p->n_w32; k++) {
+        RLS_REQUIRE_IN(fn, p->src_w32[k] != nullptr && p->dst_w32[k] != nullptr, "planes.src_w32 or planes.dst_w32 plane is NULL");
+        RLS_REQUIRE_IN(fn, p->src_w32[k] != p->dst_w32[k], "a plane's dst is its src");
+    }
+    for (int k = 0; k < p->n_u8; k++) {
+        RLS_REQUIRE_IN(fn, p->src_u8[k] != nullptr && p->dst_u8[k] != nullptr, "planes.src_u8 or planes.dst_u8 plane is NULL");
+        RLS_REQUIRE_IN(fn, p->src_u8[k] != p->dst_u8[k], "a plane's dst is its src");
+    }
+    RLS_REQUIRE_IN(fn, m == 0 || index != nullptr, "index is NULL");
+    return RLS_OK;
+}
+rls_status route_move(const char *fn, rls_context *ctx, int64_t m, const uint32_t *index, const rls_route_planes *p, bool gather)
+{
+    if (rls_status s = check_route_planes(fn, ctx, m, index, p)) return s;
+    if (m == 0) return RLS_OK;
+    const RouteMoveIO io = { *p, index, m };
+    hipLaunchKernelGGL(gather ? route_gather_kernel : route_scatter_kernel, rlsh::grid_for(ctx, m), dim3(rlsh::kBlock), 0,
+                       ctx->stream, io);
+    return rlsh::check_launch(fn);
+}
+
+} // namespace
+
+extern "C" {
+
+rls_status rls_trace_route_scratch_bytes(int64_t rays, int bins, size_t *bytes)
+{
+    RLS_REQUIRE(bytes != nullptr, "bytes is NULL");
+    if (rls_status s = check_route_size(__func__, rays, bins)) return s;
+    *bytes = route_scratch(nullptr, rays, bins).bytes;
+    return RLS_OK;
+}
+
+rls_status rls_trace_route_hits(rls_context *ctx, int64_t rays, const uint8_t *bin, const rls_hit_routes *r)
+{
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE(r != nullptr, "routes is NULL");
+    if (rls_status s = check_route_size(__func__, rays, r->bins)) return s;
+    RLS_REQUIRE(r->offsets != nullptr, "routes.offsets is NULL");
+    RLS_REQUIRE(rays == 0 || (bin != nullptr && r->order != nullptr), "bin or routes.order is NULL");
+    const RouteScratch sc = route_scratch(r->scratch, rays, r->bins);
+    RLS_REQUIRE(r->scratch != nullptr && r->scratch_bytes >= sc.bytes,
+                "routes.scratch is NULL or smaller than rls_trace_route_scratch_bytes");
+    RouteIO io = {};
+    io.bin = bin; io.counts = sc.counts; io.offsets = r->offsets; io.order = r->order; io.slot = r->slot;
+    io.rays = rays; io.tiles = sc.tiles; io.bins = r->bins;
+    if (rays > 0) {
+        hipLaunchKernelGGL(route_count_kernel, rlsh::grid_for(ctx, rays, kRouteTile), dim3(rlsh::kBlock), 0, ctx->stream, io);
+        if (rls_status s = rlsh::check_launch("route_count_kernel")) return s;
+        if (rls_status s = scan_counts(ctx, sc.counts, sc.cells, sc.totals, scan_tiles(sc.cells))) return s;
+    }
+    hipLaunchKernelGGL(route_place_kernel, rlsh::grid_for(ctx, rays, kRouteTile), dim3(rlsh::kBlock), 0, ctx->stream, io);
+    return rlsh::check_launch(__func__);
+}
+
+rls_status rls_trace_route_gather(rls_context *ctx, int64_t m, const uint32_t *index, const rls_route_planes *p)
+{
+    return route_move(__func__, ctx, m, index, p, true);
+}
+
+rls_status rls_trace_route_scatter(rls_context *ctx, int64_t m, const uint32_t *index, const rls_route_planes *p)
+{
+    return route_move(__func__, ctx, m, index, p, false);
+}
+
+rls_status rls_trace_route_fill(rls_context *ctx, int64_t m, const uint32_t *index, int n_planes, float *const *dst,
+                                const float *value)
+{
+    RLS_REQUIRE(ctx != nullptr, "ctx is NULL");
+    RLS_REQUIRE(m >= 0, "m < 0");
+    RLS_REQUIRE(n_planes >= 1 && n_planes <= RLS_ROUTE_MAX_W32, "n_planes must be in [1, 24]");
+    RLS_REQUIRE(dst != nullptr && value != nullptr, "dst or value is NULL");
+    RouteFillIO io = {};
+    for (int k = 0; k < n_planes; k++) {
+        RLS_REQUIRE(dst[k] != nullptr, "dst plane is NULL");
+        io.dst[k] = dst[k]; io.value[k] = value[k];
+    }
+    RLS_REQUIRE(m == 0 || index != nullptr, "index is NULL");
+    if (m == 0) return RLS_OK;
+    io.index = index; io.m = m; io.n_planes = n_planes;
+    hipLaunchKernelGGL(route_fill_kernel, rlsh::grid_for(ctx, m), dim3(rlsh::kBlock), 0, ctx->stream, io);
     return rlsh::check_launch(__func__);
 }
 

@@ -38,7 +38,13 @@
 //     rlsb::ggxOpacity(dev, sheet, m, hitState.c().ray_type, table.rgb());  // sg->out_opacity of m surfaces (also disney-, skinOpacity)
 //     rlsb::ShadowHits hits(dev, rays, maxHits, rlsb::ShadowHits::Indexed); // the tracer fills hits.count() and hits.index()
 //     rlsb::foldVisibility(dev, rays, hits.c(table, m), rlsb::Planes(), visibility);   // -> resolveDirect / resolveNode
-// Nothing here synchronises the host except RayQueue::count() and ShadowQueue::count() (they read offsets[n]).
+// From one bounce to the next: the traced queue's hits split by the node they landed on, each node's batch gathered, its out put back:
+//     rlsb::HitRoutes routes(dev, rays, bins);  rlsb::routeHits(dev, hitBin, routes);           // hitBin: one byte per ray
+//     rlsb::gatherHits(dev, routes, b, rlsb::RoutePlanes().planes(hitP, P_b, 3).state(hitState.c(), state_b.c()));
+//     ... emitBounce / trace / resolveBounce on routes.size(b) points per bin ...
+//     rlsb::scatterToRays(dev, routes, b, rlsb::RoutePlanes().planes(out_b, radiance, 3));  rlsb::fillMisses(dev, routes, env, radiance);
+// Nothing here synchronises the host except RayQueue::count(), ShadowQueue::count() (they read offsets[n]) and
+// HitRoutes::bounds() (offsets, once per route).
 #pragma once
 
 #include <algorithm>
@@ -835,6 +841,108 @@ private:
 inline void foldVisibility(const Device &d, int64_t rays, const rls_shadow_hits &hits, const Planes &base, Planes &visibility)
 {
     check(rls_trace_shadow_visibility(d.ctx(), rays, &hits, detail::crgb(base), visibility.rgb()));
+}
+
+// The stable partition of a traced queue's `rays` rays by the node bin they hit (rls_hit_routes) in device buffers of its own:
+// offsets [bins + 2], order [rays], slot [rays] (where asked) and the scratch.  routeHits fills it; bounds() reads offsets once
+// per route (synchronises): bin b's rays are index(b) [size(b)], ascending, b == bins the misses.
+class HitRoutes {
+public:
+    HitRoutes(const Device &d, int64_t rays, int bins, bool slot = false) : bufs_(d), dev_(&d), rays_(rays)
+    {
+        size_t scratch = 0;
+        check(rls_trace_route_scratch_bytes(rays, bins, &scratch));
+        r_.bins = bins;
+        r_.offsets = bufs_.alloc<int64_t>(bins + 2);
+        r_.order = bufs_.alloc<uint32_t>(rays);
+        if (slot) r_.slot = bufs_.alloc<uint32_t>(rays);
+        r_.scratch = bufs_.alloc(scratch);
+        r_.scratch_bytes = scratch;
+    }
+    HitRoutes(const HitRoutes &) = delete;
+    HitRoutes &operator=(const HitRoutes &) = delete;
+
+    const rls_hit_routes &c() const { return r_; }
+    int64_t rays() const { return rays_; }
+    int bins() const { return r_.bins; }
+    void routed() { host_.clear(); }
+    const std::vector<int64_t> &bounds() const
+    {
+        if (host_.empty()) {
+            host_.resize((size_t)r_.bins + 2);
+            check(rls_copy_to_host(dev_->ctx(), host_.data(), r_.offsets, host_.size() * sizeof(int64_t)));
+        }
+        return host_;
+    }
+    int64_t size(int b) const { return bounds().at((size_t)b + 1) - bounds().at((size_t)b); }
+    const uint32_t *index(int b) const { return r_.order + bounds().at((size_t)b); }
+
+private:
+    detail::DeviceBuffers bufs_;
+    const Device *dev_;
+    int64_t rays_;
+    rls_hit_routes r_{};
+    mutable std::vector<int64_t> host_;
+};
+
+// bin: one byte per ray, the node bin of the surface it hit; a value >= routes.bins() (255 by convention) a miss
+inline void routeHits(const Device &d, const uint8_t *bin, HitRoutes &routes)
+{
+    routes.routed();
+    check(rls_trace_route_hits(d.ctx(), routes.rays(), bin, &routes.c()));
+}
+
+// The planes one mover call takes, pair by pair: word(src, dst) a plane of floats or 32-bit ids, byte(src, dst) a plane of
+// bytes; state(src, dst) the five planes of an rls_ray_state; planes(src, first, dst, count) `count` planes of two Planes.
+class RoutePlanes {
+public:
+    RoutePlanes &word(const void *src, void *dst)
+    {
+        if (p_.n_w32 >= RLS_ROUTE_MAX_W32) throw Error(RLS_ERR_INVALID_ARGUMENT, "RoutePlanes: more than RLS_ROUTE_MAX_W32 word planes");
+        p_.src_w32[p_.n_w32] = src; p_.dst_w32[p_.n_w32++] = dst;
+        return *this;
+    }
+    RoutePlanes &byte(const uint8_t *src, uint8_t *dst)
+    {
+        if (p_.n_u8 >= RLS_ROUTE_MAX_U8) throw Error(RLS_ERR_INVALID_ARGUMENT, "RoutePlanes: more than RLS_ROUTE_MAX_U8 byte planes");
+        p_.src_u8[p_.n_u8] = src; p_.dst_u8[p_.n_u8++] = dst;
+        return *this;
+    }
+    RoutePlanes &planes(const Planes &src, Planes &dst, int count, int srcFirst = 0, int dstFirst = 0)
+    {
+        for (int k = 0; k < count; k++) word(src.plane(srcFirst + k), dst.plane(dstFirst + k));
+        return *this;
+    }
+    RoutePlanes &state(const rls_ray_state &src, const rls_ray_state &dst)
+    {
+        return byte(src.ray_type, const_cast<uint8_t *>(dst.ray_type)).byte(src.Rr, const_cast<uint8_t *>(dst.Rr))
+            .byte(src.Rr_diff, const_cast<uint8_t *>(dst.Rr_diff)).byte(src.Rr_gloss, const_cast<uint8_t *>(dst.Rr_gloss))
+            .byte(src.Rr_refr, const_cast<uint8_t *>(dst.Rr_refr));
+    }
+    const rls_route_planes &c() const { return p_; }
+
+private:
+    rls_route_planes p_{};
+};
+
+// bin b's columns of the per-ray src planes into the dense dst planes (rls_trace_route_gather); an empty bin moves nothing
+inline void gatherHits(const Device &d, const HitRoutes &routes, int b, const RoutePlanes &planes)
+{
+    if (routes.size(b) > 0) check(rls_trace_route_gather(d.ctx(), routes.size(b), routes.index(b), &planes.c()));
+}
+// bin b's dense src planes back to its rays' places in the per-ray dst planes (rls_trace_route_scatter)
+inline void scatterToRays(const Device &d, const HitRoutes &routes, int b, const RoutePlanes &planes)
+{
+    if (routes.size(b) > 0) check(rls_trace_route_scatter(d.ctx(), routes.size(b), routes.index(b), &planes.c()));
+}
+// value[p] into the misses' places of dst's first `count` planes (rls_trace_route_fill): the environment's radiance
+inline void fillMisses(const Device &d, const HitRoutes &routes, const float *value, Planes &dst, int count = 3)
+{
+    float *planes[RLS_ROUTE_MAX_W32] = {};
+    if (count < 1 || count > RLS_ROUTE_MAX_W32) throw Error(RLS_ERR_INVALID_ARGUMENT, "fillMisses: count outside 1 .. RLS_ROUTE_MAX_W32");
+    for (int k = 0; k < count; k++) planes[k] = dst.plane(k);
+    const int misses = routes.bins();
+    if (routes.size(misses) > 0) check(rls_trace_route_fill(d.ctx(), routes.size(misses), routes.index(misses), count, planes, value));
 }
 
 } // namespace rlsb

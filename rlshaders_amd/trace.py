@@ -36,6 +36,10 @@ or of one rlDisney lobe, trace them with your own tracer, resolve the radiance; 
     o = trace.ggx_opacity(ctx, m, KtColor=tint, Kt=0.5, ray_type=hit_state)                 # sg->out_opacity at shadow rays' hits
     vis = trace.shadow_visibility(ctx, s.count, trace.ShadowHits(cnt, o, max_hits, index=hit_surface))   # -> s.resolve(vis)
 
+    r = trace.route_hits(ctx, hit_bin, bins=2)                   # HitRoutes: the queue's rays split by the node they hit
+    hP, hN, ids = r.gather(0, P_hit, N_hit, material_id)         # bin 0's hit data as a dense batch; r.gather_state(0, hits)
+    r.scatter(0, child["out"], L); r.fill_misses(env, L)         # the children's out and the environment, back in ray order
+
 ``count`` is read from the device once (it synchronises); everything else stays asynchronous on the context's stream, so
 ``glossy_rays(..., queue=q)`` / ``q.resolve(L, out=...)`` with preallocated tensors can be recorded by ``ctx.capture()``.
 """
@@ -196,6 +200,22 @@ class ShadowHits_(C.Structure):
                 ("index", C.c_void_p), ("table_count", C.c_uint32)]
 
 
+RLS_ROUTE_MAX_BINS, RLS_ROUTE_MAX_W32, RLS_ROUTE_MAX_U8 = 16, 24, 8
+
+
+class HitRoutes_(C.Structure):
+    """rls_hit_routes"""
+    _fields_ = [("bins", C.c_int), ("offsets", C.c_void_p), ("order", C.c_void_p), ("slot", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+class RoutePlanes_(C.Structure):
+    """rls_route_planes"""
+    _fields_ = [("n_w32", C.c_int), ("n_u8", C.c_int), ("src_w32", C.c_void_p * RLS_ROUTE_MAX_W32),
+                ("dst_w32", C.c_void_p * RLS_ROUTE_MAX_W32), ("src_u8", C.c_void_p * RLS_ROUTE_MAX_U8),
+                ("dst_u8", C.c_void_p * RLS_ROUTE_MAX_U8)]
+
+
 PROTOTYPES = {
     "rls_trace_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
     "rls_trace_ggx_glossy_emit": (C.c_int, [_ctx, _i64, C.POINTER(capi.GgxClosure), C.c_int, C.c_uint32, C.c_uint64, _q, _vp]),
@@ -259,6 +279,11 @@ PROTOTYPES = {
     "rls_trace_disney_opacity": (C.c_int, [_ctx, _i64, C.POINTER(DisneyOpacity_), _vp, capi.Rgb]),
     "rls_trace_skin_opacity": (C.c_int, [_ctx, _i64, C.POINTER(SkinOpacity_), _vp, capi.CRgb, capi.Rgb]),
     "rls_trace_shadow_visibility": (C.c_int, [_ctx, _i64, C.POINTER(ShadowHits_), capi.CRgb, capi.Rgb]),
+    "rls_trace_route_scratch_bytes": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_size_t)]),
+    "rls_trace_route_hits": (C.c_int, [_ctx, _i64, _vp, C.POINTER(HitRoutes_)]),
+    "rls_trace_route_gather": (C.c_int, [_ctx, _i64, _vp, C.POINTER(RoutePlanes_)]),
+    "rls_trace_route_scatter": (C.c_int, [_ctx, _i64, _vp, C.POINTER(RoutePlanes_)]),
+    "rls_trace_route_fill": (C.c_int, [_ctx, _i64, _vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_float)]),
 }
 
 _lib = None
@@ -1357,3 +1382,190 @@ def shadow_visibility(ctx, rays: int, hits: ShadowHits, base: Optional[torch.Ten
     b = capi.CRgb(None, None, None) if base is None or rays == 0 else _radiance(base, rays, "base")
     check(load().rls_trace_shadow_visibility(ctx.handle, rays, C.byref(hits.h), b, rgb(res, rays, "visibility")))
     return res
+
+
+# ---- routing a queue's hits to the nodes ------------------------------------------------------------------------------------------
+def route_scratch_bytes(rays: int, bins: int) -> int:
+    b = C.c_size_t()
+    check(load().rls_trace_route_scratch_bytes(int(rays), int(bins), C.byref(b)))
+    return int(b.value)
+
+
+_W32 = (torch.float32, torch.int32, torch.uint32)
+
+
+def _route_rows(t: torch.Tensor, what: str) -> list:
+    """the planes of one tensor: itself (1-D) or its rows ([k, count]), float32 / int32 / uint32 words or uint8 bytes"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() not in (1, 2) or t.stride(-1) != 1 or \
+            t.dtype not in _W32 + (torch.uint8,):
+        raise TypeError(f"{what}: expected a float32 / int32 / uint32 / uint8 CUDA tensor [count] or [k, count] with unit inner "
+                        f"stride")
+    return [t] if t.dim() == 1 else [t[k] for k in range(t.shape[0])]
+
+
+def _route_index(index: torch.Tensor, m: Optional[int]) -> int:
+    if not isinstance(index, torch.Tensor) or index.dtype not in (torch.int32, torch.uint32) or not index.is_cuda or \
+            index.dim() != 1 or not index.is_contiguous():
+        raise TypeError("index: expected a contiguous int32 / uint32 CUDA tensor [m]")
+    m = int(index.shape[0]) if m is None else int(m)
+    if m > index.shape[0]:
+        raise ValueError(f"index holds {index.shape[0]} entries, the call has {m}")
+    return m
+
+
+def route_planes(src, dst) -> RoutePlanes_:
+    """rls_route_planes of two equally long lists of 1-D plane tensors, pairwise of one dtype: the 32-bit planes in list order,
+    then the byte planes in list order.  The counts are passed on as they are: the library refuses what exceeds its caps."""
+    if len(src) != len(dst):
+        raise ValueError("route_planes: as many dst planes as src planes")
+    p = RoutePlanes_()
+    words, octets = [], []
+    for s, d in zip(src, dst):
+        if s.dtype != d.dtype or s.dim() != 1 or d.dim() != 1 or s.stride(0) != 1 or d.stride(0) != 1:
+            raise TypeError("route_planes: a src and its dst are 1-D planes of one dtype with unit stride")
+        (octets if s.dtype == torch.uint8 else words).append((s, d))
+    p.n_w32, p.n_u8 = len(words), len(octets)
+    for k, (s, d) in enumerate(words[:RLS_ROUTE_MAX_W32]):
+        p.src_w32[k], p.dst_w32[k] = s.data_ptr(), d.data_ptr()
+    for k, (s, d) in enumerate(octets[:RLS_ROUTE_MAX_U8]):
+        p.src_u8[k], p.dst_u8[k] = s.data_ptr(), d.data_ptr()
+    return p
+
+
+def _route_move(ctx, index: torch.Tensor, src, dst, m: Optional[int], gather: bool) -> None:
+    m = _route_index(index, m)
+    if m == 0 or not src:
+        return
+    fn = load().rls_trace_route_gather if gather else load().rls_trace_route_scatter
+    # (more planes than one call takes: several calls, words and bytes capped separately)
+    words = [(s, d) for s, d in zip(src, dst) if s.dtype != torch.uint8]
+    octets = [(s, d) for s, d in zip(src, dst) if s.dtype == torch.uint8]
+    while words or octets:
+        part = words[:RLS_ROUTE_MAX_W32] + octets[:RLS_ROUTE_MAX_U8]
+        words, octets = words[RLS_ROUTE_MAX_W32:], octets[RLS_ROUTE_MAX_U8:]
+        p = route_planes([s for s, _ in part], [d for _, d in part])
+        check(fn(ctx.handle, m, index.data_ptr(), C.byref(p)))
+
+
+def route_gather(ctx, index: torch.Tensor, src, dst, m: Optional[int] = None) -> None:
+    """dst[p][j] = src[p][index[j]], j < m (rls_trace_route_gather): ``src`` / ``dst`` lists of 1-D plane tensors, ``index`` an
+    int32 / uint32 CUDA tensor (a range of ``HitRoutes.order``)."""
+    _route_move(ctx, index, src, dst, m, True)
+
+
+def route_scatter(ctx, index: torch.Tensor, src, dst, m: Optional[int] = None) -> None:
+    """dst[p][index[j]] = src[p][j], j < m (rls_trace_route_scatter)"""
+    _route_move(ctx, index, src, dst, m, False)
+
+
+def route_fill(ctx, index: torch.Tensor, value, dst, m: Optional[int] = None) -> None:
+    """dst[p][index[j]] = value[p], j < m (rls_trace_route_fill): ``dst`` a list of 1-D float32 planes, ``value`` as many numbers"""
+    m = _route_index(index, m)
+    value = [float(v) for v in value]
+    if len(value) != len(dst):
+        raise ValueError("route_fill: one value per plane")
+    for d in dst:
+        if not isinstance(d, torch.Tensor) or d.dtype != torch.float32 or not d.is_cuda or d.dim() != 1 or d.stride(0) != 1:
+            raise TypeError("route_fill: dst planes are 1-D float32 CUDA tensors with unit stride")
+    if m == 0:
+        return
+    ptrs = (C.c_void_p * max(len(dst), 1))(*[d.data_ptr() for d in dst])
+    vals = (C.c_float * max(len(dst), 1))(*value)
+    check(load().rls_trace_route_fill(ctx.handle, m, index.data_ptr(), len(dst), ptrs, vals))
+
+
+class HitRoutes:
+    """The stable partition of ``rays`` rays by the node bin they hit (rls_hit_routes): owns ``offsets`` [bins + 2] int64,
+    ``order`` [rays] (uint32 on the device, int32 here: ray indices below 2^31 read as they are), ``slot`` (the inverse, where
+    asked) and the scratch.  Bin ``b``'s rays are ``index(b)``, ascending; ``b == bins`` gives the misses."""
+
+    def __init__(self, ctx, rays: int, bins: int, slot: bool = False):
+        self.ctx, self.rays, self.bins = ctx, int(rays), int(bins)
+        dev = ctx.torch_device
+        self.offsets = torch.empty(self.bins + 2, dtype=torch.int64, device=dev)
+        self.order = torch.empty(self.rays, dtype=torch.int32, device=dev)
+        self.slot = torch.empty(self.rays, dtype=torch.int32, device=dev) if slot else None
+        self._scratch = torch.empty(max(route_scratch_bytes(self.rays, self.bins), 1), dtype=torch.uint8, device=dev)
+        r = HitRoutes_()
+        r.bins, r.offsets = self.bins, self.offsets.data_ptr()
+        r.order = self.order.data_ptr() if self.rays > 0 else None
+        r.slot = self.slot.data_ptr() if slot and self.rays > 0 else None
+        r.scratch, r.scratch_bytes = self._scratch.data_ptr(), self._scratch.numel()
+        self.r = r
+        self._host = None
+
+    def route(self, bin: torch.Tensor) -> "HitRoutes":
+        if not isinstance(bin, torch.Tensor) or bin.dtype != torch.uint8 or not bin.is_cuda or bin.dim() != 1 or \
+                bin.shape[0] < self.rays or not bin.is_contiguous():
+            raise TypeError(f"bin: expected a contiguous uint8 CUDA tensor [>= {self.rays}]")
+        self._host = None
+        check(load().rls_trace_route_hits(self.ctx.handle, self.rays, bin.data_ptr() if self.rays > 0 else None,
+                                          C.byref(self.r)))
+        return self
+
+    def bounds(self) -> list:
+        """offsets on the host (one device-to-host copy after a route, cached: it synchronises)"""
+        if self._host is None:
+            self._host = [int(v) for v in self.offsets.tolist()]
+        return self._host
+
+    def sizes(self) -> list:
+        """the ray count of every bin 0 .. bins - 1 and of the misses (bins + 1 values)"""
+        o = self.bounds()
+        return [o[b + 1] - o[b] for b in range(self.bins + 1)]
+
+    def index(self, b: int) -> torch.Tensor:
+        """bin b's ray indices, ascending: a view into ``order`` (b == bins: the misses)"""
+        if not 0 <= int(b) <= self.bins:
+            raise ValueError(f"bin {b} outside 0 .. {self.bins}")
+        o = self.bounds()
+        return self.order[o[int(b)]:o[int(b) + 1]]
+
+    def gather(self, b: int, *tensors) -> tuple:
+        """bin b's columns of every tensor ([rays] or [k, rays]) as dense tensors ([m] / [k, m]), one per argument"""
+        idx = self.index(b)
+        m = int(idx.shape[0])
+        src, dst, out = [], [], []
+        for t in tensors:
+            rows = _route_rows(t, "gather")
+            if t.shape[-1] < self.rays:
+                raise ValueError(f"gather: a tensor of {t.shape[-1]} columns, the routes have {self.rays} rays")
+            res = torch.empty(t.shape[:-1] + (m,), dtype=t.dtype, device=t.device)
+            src += rows
+            dst += _route_rows(res, "gather")
+            out.append(res)
+        route_gather(self.ctx, idx, src, dst)
+        return tuple(out)
+
+    def gather_state(self, b: int, state: RayState) -> RayState:
+        """the RayState of bin b's rays out of the per-ray ``state``"""
+        return RayState(*self.gather(b, *[getattr(state, name) for name in RayState.PLANES]))
+
+    def scatter(self, b: int, src_rgb: torch.Tensor, dst_rgb: torch.Tensor) -> torch.Tensor:
+        """bin b's dense ``src_rgb`` [k, m] back to its rays' columns of ``dst_rgb`` [k, rays]"""
+        idx = self.index(b)
+        src, dst = _route_rows(src_rgb, "scatter"), _route_rows(dst_rgb, "scatter")
+        if src_rgb.shape[-1] < idx.shape[0] or dst_rgb.shape[-1] < self.rays or len(src) != len(dst):
+            raise ValueError("scatter: src [k, >= the bin's size] and dst [k, >= rays]")
+        route_scatter(self.ctx, idx, src, dst)
+        return dst_rgb
+
+    def fill_misses(self, value, dst_rgb: torch.Tensor) -> torch.Tensor:
+        """``value`` (one number per plane) into the misses' columns of ``dst_rgb`` [k, rays]"""
+        if dst_rgb.shape[-1] < self.rays:
+            raise ValueError("fill_misses: dst [k, >= rays]")
+        route_fill(self.ctx, self.index(self.bins), value, _route_rows(dst_rgb, "fill_misses"))
+        return dst_rgb
+
+
+def route_hits(ctx, bin: torch.Tensor, bins: int, slot: bool = False, routes: Optional[HitRoutes] = None,
+               rays: Optional[int] = None) -> HitRoutes:
+    """Route ``rays`` (default: all of ``bin``) traced rays by the node bin they hit (rls_trace_route_hits): ``bin`` uint8 CUDA
+    [rays], a value below ``bins`` that node's bin, any other (255 by convention) a miss.  ``routes``: a HitRoutes to write
+    again (no allocation: recordable by ``ctx.capture()``)."""
+    rays = int(bin.shape[0]) if rays is None else int(rays)
+    if routes is None:
+        routes = HitRoutes(ctx, rays, bins, slot)
+    elif routes.rays != rays or routes.bins != int(bins) or (slot and routes.slot is None):
+        raise ValueError("route_hits: routes was made for another ray count, bin count or without slot")
+    return routes.route(bin)

@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce|shadow-fold] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
+    python tools/trace_bench.py [--closure ggx|disney|sss|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce|shadow-fold|route] [--mix even|skewed|one] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -53,6 +53,13 @@ probe walk), the node call beside it in the same process as for the other two no
 uniform in 0 .. 4, stride = rays, uniform random opacities, no base: `direct` (an opacity per element) and `indexed` (an index
 per element into a table of 4096 surfaces).  Bytes, direct: 1 (count) + 12 per hit read, 12 written per ray; indexed: 1 +
 (4 (index) + 12 (the table's entry, from cache)) per hit read, 12 written per ray.  --spp-n is not read.
+--closure route: routing 2^log2n traced rays to 3 node bins and the misses (trace.route_hits, HitRoutes) at --mix even (a
+quarter of the rays in each bin and a quarter misses), skewed (70 / 20 / 9 % and 1 % misses) or one (every ray in bin 0):
+route_hits without and with slot, a 12-plane gather and a 3-plane scatter of bin 0, the fill of the misses' 3 planes.  Beside
+each the device-to-device copy (torch copy_) that moves the verb's algorithmic traffic, half of it read and half written --
+route: 2 B read + 4 B written per ray, + 4 B with slot; gather / scatter: 4 B of index + 8 B per word plane per element; fill:
+4 B of index + 4 B per plane per element.  Medians of at least 9 calls after at least 3 warm-up calls, device events, with the
+fastest and slowest call beside them.  --spp-n is not read.
 """
 from __future__ import annotations
 
@@ -579,6 +586,65 @@ def bench_shadow_fold(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> No
         torch.cuda.empty_cache()
 
 
+def timed_spread(fn, repeats: int, warmup: int) -> dict:
+    """timed(), with the fastest and the slowest of the measured calls beside the median"""
+    import torch
+    for _ in range(warmup):
+        fn()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    ms.sort()
+    return {"ms": round(ms[len(ms) // 2], 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}
+
+
+def bench_route(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """the routing verbs beside the copy of their algorithmic traffic (module docstring)"""
+    import torch
+    from rlshaders_amd import trace as T
+    dev, bins = ctx.torch_device, 3
+    repeats, warmup = max(args.repeats, 9), max(args.warmup, 3)
+    g = torch.Generator(device=dev).manual_seed(seed)
+    share = {"even": (0.25, 0.25, 0.25, 0.25), "skewed": (0.70, 0.20, 0.09, 0.01), "one": (1.0, 0.0, 0.0, 0.0)}[args.mix]
+    u = torch.rand(n, generator=g, device=dev)
+    edges = torch.tensor(share, device=dev).cumsum(0)
+    key = torch.bucketize(u, edges[:-1], right=True)
+    bin_ = torch.where(key < bins, key, torch.full_like(key, 255)).to(torch.uint8)
+    del u, key
+
+    def with_copy(fn, bytes_, elements):
+        """fn's time and the time of a copy of bytes_ / 2 bytes (bytes_ of traffic)"""
+        if elements == 0:
+            return None
+        r = timed_spread(fn, repeats, warmup)
+        a, b = (torch.empty(max(bytes_ // 2, 1), dtype=torch.uint8, device=dev) for _ in range(2))
+        c = timed_spread(lambda: b.copy_(a), repeats, warmup)
+        del a, b
+        r.update({"elements": elements, "bytes": bytes_, "tb_per_s": rate(bytes_, r["ms"]), "copy_ms": c["ms"],
+                  "copy_min_ms": c["min_ms"], "copy_max_ms": c["max_ms"], "copy_tb_per_s": rate(bytes_, c["ms"]),
+                  "fraction_of_copy": round(c["ms"] / r["ms"], 4)})
+        return r
+
+    rec.update({"rays": n, "bins": bins, "mix": args.mix, "repeats": repeats, "warmup": warmup})
+    plain, slotted = T.HitRoutes(ctx, n, bins), T.HitRoutes(ctx, n, bins, slot=True)
+    rec["route"] = with_copy(lambda: T.route_hits(ctx, bin_, bins, routes=plain), n * 6, n)
+    rec["route_slot"] = with_copy(lambda: T.route_hits(ctx, bin_, bins, slot=True, routes=slotted), n * 10, n)
+    del slotted
+    rec["sizes"] = plain.sizes()
+    m, misses = rec["sizes"][0], rec["sizes"][bins]
+    idx, miss_idx = plain.index(0), plain.index(bins)
+    src = torch.rand(12, n, generator=g, device=dev)
+    dense = torch.empty(12, m, device=dev)
+    rec["gather_12"] = with_copy(lambda: T.route_gather(ctx, idx, list(src), list(dense)), m * (4 + 8 * 12), m)
+    rec["scatter_3"] = with_copy(lambda: T.route_scatter(ctx, idx, list(dense[:3]), list(src[:3])), m * (4 + 8 * 3), m)
+    rec["fill_3"] = with_copy(lambda: T.route_fill(ctx, miss_idx, (0.25, 0.3, 0.4), list(src[:3])), misses * (4 + 4 * 3), misses)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=24)
@@ -587,7 +653,8 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
     ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
-                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold"), default="ggx")
+                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "route"), default="ggx")
+    ap.add_argument("--mix", choices=("even", "skewed", "one"), default="even", help="route: the rays' split over 3 bins and the misses")
     ap.add_argument("--state", choices=("camera", "secondary", "half", "diffuse"), default="camera",
                     help="the bounce closures: every point a camera ray at depth 0, a glossy ray's hit at depth 1, or the two alternating; "
                          "skin-bounce: or a diffuse ray's hit at depth 1")
@@ -614,7 +681,7 @@ def main() -> None:
         rec["closure"] = args.closure
         {"disney": bench_disney, "sss": bench_sss, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
          "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce,
-         "shadow-fold": bench_shadow_fold}.get(
+         "shadow-fold": bench_shadow_fold, "route": bench_route}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
         print(json.dumps(rec), flush=True)
