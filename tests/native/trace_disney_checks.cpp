@@ -1,5 +1,5 @@
 // trace_disney_checks.cpp -- the argument checks of rls_trace_disney_emit (librls_trace.so), driven with dummy planes and
-// no GPU (tests/test_trace_disney_abi.py builds and runs it), in the style of argument_checks.cpp.
+// no GPU (tests/test_trace_abi.py builds and runs it), in the style of argument_checks.cpp.
 //
 // Every case starts from a set of arguments that passes every check, breaks one or two of them (or none) and records what
 // the call returns.  A call whose arguments pass reaches the launch, and with no device there its hipSetDevice fails: status

@@ -1,5 +1,5 @@
 // trace_sss_checks.cpp -- the argument checks of rls_trace_sss_probe_emit and rls_trace_sss_scatter_resolve
-// (librls_trace.so), driven with dummy planes and no GPU (tests/test_trace_sss_abi.py builds and runs it), in the style of
+// (librls_trace.so), driven with dummy planes and no GPU (tests/test_trace_abi.py builds and runs it), in the style of
 // trace_disney_checks.cpp.
 //
 // Every case starts from a set of arguments that passes every check, breaks one or two of them (or none) and records what

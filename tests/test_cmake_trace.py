@@ -40,7 +40,7 @@ def built():
 
 
 def test_companion_builds_and_exports_its_header(built):
-    from test_trace_abi import declared_trace_symbols, exported_trace_symbols
+    from trace_abi_util import declared_trace_symbols, exported_trace_symbols
     lib = built / "librls_trace.so"
     assert lib.exists()
     assert exported_trace_symbols(lib) == declared_trace_symbols()

@@ -1,189 +1,82 @@
 """CPU: the secondary-ray calls of the companion library (rls_trace_ggx_bounce_emit / _resolve, rls_trace_disney_bounce_emit /
 _resolve, rls_trace_ray_state_advance; include/rlshaders_amd_trace.h, librls_trace.so).
 
-The five symbols are declared, exported and bound with matching arity; the header with the state structs compiles as C99 and
-C++14; the library still holds two code objects, each with the state-aware emit kernels at every lane-group width, the EXACT
-one with the two bounce resolve kernels and the advance kernel, and the parents' kernels keep their names; every refusal
-returns RLS_ERR_INVALID_ARGUMENT with the entry point's name in the message.  The checks run through ctypes with dummy planes
-and a dummy context (tests/test_trace_shade_abi.py's World): a refused call returns before the context is read."""
+Every refusal -- the node calls' table and the state's (tests/trace_abi_util.py) -- returns RLS_ERR_INVALID_ARGUMENT with the
+entry point's name in the message.  The checks run through ctypes with dummy planes and a dummy context: a refused call returns
+before the context is read.  The family's rows of tests/trace_abi_tables.py are checked with the whole table by
+tests/test_trace_abi.py; the three tests that repeat those checks on this family's rows alone keep their names from before the
+table."""
 import ctypes as C
-import re
-import subprocess
 
 import pytest
 
-from test_trace_shade_abi import BOTH, EMIT_ONLY, HEADER, INVALID, RESOLVE_ONLY, ROOT, World, _declarations, _last_ray, trace_lib  # noqa: F401
+from trace_abi_tables import FAMILIES
+from trace_abi_util import (INVALID, PLANES, Dummies, NodeWorld, check_absent_from_product, check_bound, check_callables,
+                            check_members, check_placement, empty_state, node_table, put, refusals, trace_lib)  # noqa: F401
 
-SYMBOLS = ("rls_trace_ggx_bounce_emit", "rls_trace_ggx_bounce_resolve", "rls_trace_disney_bounce_emit",
-           "rls_trace_disney_bounce_resolve", "rls_trace_ray_state_advance")
-ARITY = dict(rls_trace_ggx_bounce_emit=13, rls_trace_ggx_bounce_resolve=12, rls_trace_disney_bounce_emit=12,
-             rls_trace_disney_bounce_resolve=13, rls_trace_ray_state_advance=6)
-EMIT_FAMILIES = ("ggx_bounce_direct_emit_kernel", "ggx_bounce_glossy_emit_kernel", "ggx_bounce_refract_emit_kernel",
-                 "ggx_bounce_diffuse_emit_kernel", "disney_bounce_direct_emit_kernel", "disney_bounce_diffuse_emit_kernel",
-                 "disney_bounce_specular_emit_kernel")
-MODE_FREE = ("ggx_bounce_resolve_kernel", "disney_bounce_resolve_kernel", "state_advance_kernel")
+F = FAMILIES["bounce"]
 
 
 def test_declared_exported_and_bound_with_matching_arity(trace_lib):
-    from rlshaders_amd import trace
-    decl = _declarations()
-    out = subprocess.run(["nm", "-D", "--defined-only", str(trace_lib)], capture_output=True, text=True, check=True).stdout
-    lib = trace.load()
-    for name in SYMBOLS:
-        assert name in decl, name
-        assert len(decl[name].split(",")) == ARITY[name], (name, decl[name])
-        assert f" T {name}\n" in out, name
-        restype, argtypes = trace.PROTOTYPES[name]
-        assert restype is C.c_int and len(argtypes) == ARITY[name], name
-        assert getattr(lib, name).argtypes == argtypes
-    assert all(callable(getattr(trace, f)) for f in ("ggx_bounce_rays", "disney_bounce_rays", "advance_state", "RayState"))
-    # the binding structs have the header's members, in its order; the ray-type bits are the header's
-    text = HEADER.read_text()
-    for cls, c_name in ((trace.GiDepths_, "rls_gi_depths"), (trace.RayState_, "rls_ray_state")):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (c_name, c_name), text, flags=re.S).group(1)
-        members = [re.findall(r"\w+", part)[-1] for d in body.split(";") if d.strip() for part in d.split(",")]
-        assert members == [f[0] for f in cls._fields_], (c_name, members)
-    for name, value in re.findall(r"(RLS_RT_[A-Z]+) = (0x[0-9a-f]+)", text):
-        assert getattr(trace, name) == int(value, 16), name
-    assert {n for n, _ in re.findall(r"(RLS_RT_[A-Z]+) = (0x[0-9a-f]+)", text)} == \
-        {"RLS_RT_CAMERA", "RLS_RT_SHADOW", "RLS_RT_REFLECTED", "RLS_RT_REFRACTED", "RLS_RT_DIFFUSE", "RLS_RT_GLOSSY"}
-
-
-def test_header_compiles_as_c_and_cxx(tmp_path):
-    src = tmp_path / "t.c"
-    src.write_text('#include "rlshaders_amd_trace.h"\n'
-                   'int main(void){ rls_ggx_node_queues q = {0}; rls_disney_node_queues d = {0}; rls_ray_state s = {0};\n'
-                   '  rls_gi_depths g = { 8, 2, 2, 4 }; rls_param k = { 0, 1.0f }; int rt = RLS_RT_CAMERA | RLS_RT_GLOSSY;\n'
-                   '  rls_cvec3 P = { 0, 0, 0 };\n'
-                   '  return rls_trace_ggx_bounce_emit(0, 0, 0, 0, P, 0, 0, 1, 7, 0, &s, &g, &q) +\n'
-                   '         rls_trace_disney_bounce_emit(0, 0, 0, P, 0, 0, 1, 7, 0, &s, &g, &d) +\n'
-                   '         rls_trace_ggx_bounce_resolve(0, 0, 0, 0, 0, 0, 1, &s, &g, &q, 0, 0) +\n'
-                   '         rls_trace_disney_bounce_resolve(0, 0, 0, k, k, 0, 0, 1, &s, &g, &d, 0, 0) +\n'
-                   '         rls_trace_ray_state_advance(0, 0, 0, &s, rt, &s); }\n')
-    for cc, std in (("gcc", "-std=c99"), ("g++", "-std=c++14")):
-        p = subprocess.run([cc, std, "-Wall", "-Werror", "-pedantic", "-fsyntax-only", f"-I{ROOT / 'include'}",
-                            "-x", "c" if cc == "gcc" else "c++", str(src)], capture_output=True, text=True)
-        assert p.returncode == 0, (cc, p.stderr)
+    check_bound(trace_lib, F["arity"])
+    check_callables(F["callables"])
+    check_members(F["structs"])          # (the RLS_RT_* bits: tests/test_trace_abi.py::test_the_constants_are_the_headers)
 
 
 def test_still_two_code_objects_with_the_bounce_kernels(trace_lib):
-    from rlshaders_amd.codeid import DeviceCode, code_objects, fatbin
-    assert len(code_objects(fatbin(trace_lib))) == 2             # still the EXACT and the FAST unit
-    dc = DeviceCode(trace_lib)
-    units = {0: set(), 1: set()}
-    for fast in (0, 1):
-        for fam in EMIT_FAMILIES:
-            for g in (1, 4, 16, 64):
-                u = dc.unit_of_kernel(f"{fam}<{g}, {fast}>")
-                assert u is not None, (fam, g, fast)
-                units[fast].add(u)
-    assert len(units[0]) == 1 and len(units[1]) == 1 and units[0] != units[1]
-    for k in MODE_FREE:                                          # + and x and integer arithmetic only: in the EXACT unit
-        assert dc.unit_of_kernel(k) in units[0], k
-    # the parents keep their names beside them
-    for k in ("ggx_direct_emit_kernel<4, 0>", "disney_direct_emit_kernel<1, 1>", "ggx_node_refract_emit_kernel<16, 0>",
-              "disney_node_specular_emit_kernel<64, 1>", "ggx_node_resolve_kernel", "disney_node_resolve_kernel"):
-        assert dc.unit_of_kernel(k) is not None, k
+    check_placement(trace_lib, F["width"], F["mode"], F["free"])
 
 
 def test_no_bounce_kernel_in_the_product_library(trace_lib):
-    from rlshaders_amd import build
-    from rlshaders_amd.codeid import code_objects, fatbin
-    for elf in code_objects(fatbin(build.build_library())):
-        for fam in EMIT_FAMILIES + MODE_FREE:
-            assert fam.encode() not in elf, fam
-
-
-class BounceWorld(World):
-    """World with the state planes, the depths and rlDisney's scales"""
-
-    def __init__(self, node):
-        super().__init__(node)
-        from rlshaders_amd import trace
-        p = C.addressof(self.mem)
-        self.state = trace.RayState_(p, p, p, p, p)
-        self.depths = trace.GiDepths_(8, 2, 2, 4)
-        self.sp, self.dp = C.byref(self.state), C.byref(self.depths)
-        self.scale = self.capi.Param(None, 0.5)
-
-    def emit(self):
-        if self.node == "ggx":
-            return self.lib.rls_trace_ggx_bounce_emit(self.ctxp, self.n, self._c(), C.byref(self.sh), self.P, self.lights,
-                                                      self.nl, self.spp_n, 7, 0, self.sp, self.dp, self.qp)
-        return self.lib.rls_trace_disney_bounce_emit(self.ctxp, self.n, self._c(), self.P, self.lights, self.nl, self.spp_n,
-                                                     7, 0, self.sp, self.dp, self.qp)
-
-    def resolve(self):
-        if self.node == "ggx":
-            return self.lib.rls_trace_ggx_bounce_resolve(self.ctxp, self.n, self._c(), C.byref(self.sh), self.lights, self.nl,
-                                                         self.spp_n, self.sp, self.dp, self.qp, self.tp, self.op)
-        return self.lib.rls_trace_disney_bounce_resolve(self.ctxp, self.n, self._c(), self.scale, self.scale, self.lights,
-                                                        self.nl, self.spp_n, self.sp, self.dp, self.qp, self.tp, self.op)
-
-
-PLANES = "state.ray_type, state.Rr, state.Rr_diff, state.Rr_gloss or state.Rr_refr plane is NULL"
-STATE = [("state NULL", lambda w: setattr(w, "sp", None), "state is NULL"),
-         ("depths NULL", lambda w: setattr(w, "dp", None), "depths is NULL")] + \
-        [(f"state.{name} NULL", (lambda name: lambda w: setattr(w.state, name, None))(name), PLANES)
-         for name in ("ray_type", "Rr", "Rr_diff", "Rr_gloss", "Rr_refr")]
+    check_absent_from_product(F["width"] + F["free"])
 
 
 @pytest.mark.parametrize("verb", ["emit", "resolve"])
 @pytest.mark.parametrize("node", ["ggx", "disney"])
 def test_every_refusal_names_the_entry_point(trace_lib, node, verb):
-    """the node calls' table (tests/test_trace_shade_abi.py) and the state's"""
-    from rlshaders_amd import _capi as capi
-    entry = f"rls_trace_{node}_bounce_{verb}"
-    table = BOTH + STATE + (EMIT_ONLY if verb == "emit" else RESOLVE_ONLY)
-    if node == "ggx":
-        table = table + [("closure NULL", lambda w: setattr(w, "c", None), "closure or shader is NULL")]
-    else:
-        table = table + [("closure NULL", lambda w: setattr(w, "c", None), "closure is NULL")]
-    wrong = []
-    for what, breakit, text in table:
-        w = BounceWorld(node)
-        breakit(w)
-        st = getattr(w, verb)()
-        msg = capi.load().rls_last_error().decode()
-        ok = st == INVALID and msg.startswith(entry + ": ") and (text is None or msg == f"{entry}: {text}")
-        if what == "lights NULL":                                # copy_lights names itself, as in every light-loop verb
-            ok = st == INVALID and msg.endswith("lights is NULL")
-        if not ok:
-            wrong.append(f'{entry} / {what}: status {st} "{msg}", want "{text}"')
+    wrong = refusals(lambda: NodeWorld(node, bounce=True), lambda w: getattr(w, verb)(), f"rls_trace_{node}_bounce_{verb}",
+                     node_table(node, True, verb))
     assert not wrong, "\n".join(wrong)
 
 
+class AdvanceWorld(Dummies):
+    """rls_trace_ray_state_advance over 4 rays"""
+
+    def __init__(self):
+        super().__init__()
+        self.rays, self.point, self.ray_type = 4, self.p, 0x40
+        self.parent, self.child = self.ray_state(), self.ray_state()
+        self.pp, self.chp = C.byref(self.parent), C.byref(self.child)
+
+    def call(self):
+        return self.lib.rls_trace_ray_state_advance(self.ctxp, self.rays, self.point, self.pp, self.ray_type, self.chp)
+
+
+ADVANCE = [
+    ("ctx NULL", lambda w: put(w, "ctxp", None), "ctx is NULL"),
+    ("rays < 0", lambda w: put(w, "rays", -1), "rays < 0"),
+    ("parent NULL", lambda w: put(w, "pp", None), "parent or child is NULL"),
+    ("child NULL", lambda w: put(w, "chp", None), "parent or child is NULL"),
+    ("ray_type 0x100", lambda w: put(w, "ray_type", 0x100), "ray_type is not a byte of RLS_RT_* bits"),
+    ("point NULL", lambda w: put(w, "point", None), "point is NULL"),
+    ("a child plane NULL", lambda w: put(w.child, "Rr_refr", None), PLANES),
+    ("a parent plane NULL", lambda w: put(w.parent, "Rr_refr", None), PLANES),
+]
+
+
 def test_the_advance_call_refuses_by_name_and_takes_no_rays_without_a_device(trace_lib):
-    from rlshaders_amd import _capi as capi, trace
-    lib = trace.load()
-    mem = C.create_string_buffer(64)
-    ctx = C.create_string_buffer(4096)
-    p = C.addressof(mem)
-    ok_state = lambda: trace.RayState_(p, p, p, p, p)
-    entry = "rls_trace_ray_state_advance"
-    half = ok_state()
-    half.Rr_refr = None
-    cases_ = [((None, 4, p, C.byref(ok_state()), 0x40, C.byref(ok_state())), "ctx is NULL"),
-              ((C.addressof(ctx), -1, p, C.byref(ok_state()), 0x40, C.byref(ok_state())), "rays < 0"),
-              ((C.addressof(ctx), 4, p, None, 0x40, C.byref(ok_state())), "parent or child is NULL"),
-              ((C.addressof(ctx), 4, p, C.byref(ok_state()), 0x40, None), "parent or child is NULL"),
-              ((C.addressof(ctx), 4, p, C.byref(ok_state()), 0x100, C.byref(ok_state())), "ray_type is not a byte of RLS_RT_* bits"),
-              ((C.addressof(ctx), 4, None, C.byref(ok_state()), 0x40, C.byref(ok_state())), "point is NULL"),
-              ((C.addressof(ctx), 4, p, C.byref(ok_state()), 0x40, C.byref(half)), PLANES),
-              ((C.addressof(ctx), 4, p, C.byref(half), 0x40, C.byref(ok_state())), PLANES)]
-    for args, text in cases_:
-        assert lib.rls_trace_ray_state_advance(*args) == INVALID, text
-        assert capi.load().rls_last_error().decode() == f"{entry}: {text}"
-    # rays == 0 launches nothing: the dummy context is not read
-    assert lib.rls_trace_ray_state_advance(C.addressof(ctx), 0, None, C.byref(ok_state()), 0x40, C.byref(ok_state())) == 0
+    wrong = refusals(AdvanceWorld, AdvanceWorld.call, "rls_trace_ray_state_advance", ADVANCE)
+    assert not wrong, "\n".join(wrong)
+    w = AdvanceWorld()                   # rays == 0 launches nothing: the dummy context is not read
+    w.rays, w.point = 0, None
+    assert w.call() == 0
 
 
 @pytest.mark.parametrize("node", ["ggx", "disney"])
 def test_a_resolve_of_nothing_succeeds_without_a_device(trace_lib, node):
-    w = BounceWorld(node)
+    w = NodeWorld(node, bounce=True)
     w.n = 0
-    w.state = type(w.state)()                                    # an empty batch reads no plane
-    w.sp = C.byref(w.state)
+    empty_state(w)
     assert w.resolve() == 0
     w.sp = None
     assert w.resolve() == INVALID

@@ -4,7 +4,7 @@ rls_trace_route_gather, rls_trace_route_scatter, rls_trace_route_fill; librls_tr
 tests/native/trace_route_checks.cpp runs them with a hand-built context, dummy planes and no GPU: the status, the message and
 its entry-point prefix of every refusal the header lists, RLS_ERR_UNSUPPORTED past 2^32 - 1 rays, that a passing argument set
 reaches the launch (RLS_ERR_HIP), and that an empty call succeeds without one while a bad argument beside it is still refused.
-Like tests/test_trace_sss_abi.py it skips where torch sees a GPU."""
+Like tests/test_trace_abi.py's native drivers it skips where torch sees a GPU."""
 import subprocess
 from pathlib import Path
 
