@@ -204,6 +204,62 @@ def build_trace_example(verbose: bool = False, name: str = "example_trace") -> P
     return out
 
 
+# rlSss's probe walk (include/rlshaders_amd_walk.h): a third companion, so that the trace library's surface -- pinned entry point
+# by entry point, tests/test_trace_abi.py -- and the product stay what they are.  The walk is mode-free: ONE unit, compiled with
+# RLS_FAST=0 (IEEE arithmetic), the same flags, a fixed -cuid.  It includes the trace library's scan kernels from csrc_trace/, so
+# those headers are its dependencies too; linked against librlshaders_amd.so (contexts, errors, graphs), found by $ORIGIN.
+WALK_CSRC = PKG / "csrc_walk"
+WALK_SOURCES = ["walk.hip"]
+WALK_LIB = LIBDIR / "librls_walk.so"
+WALK_HEADERS = [*sorted(WALK_CSRC.glob("*.hpp")), PKG.parent / "include" / "rlshaders_amd_walk.h"]
+
+
+def build_walk_library(force: bool = False, verbose: bool = False) -> Path:
+    """Compile csrc_walk/ for gfx950 and link librls_walk.so against the product library.  Returns its path."""
+    hipcc = _hipcc()
+    main = build_library(verbose=verbose)
+    objdir = OBJDIR / "walk"
+    objdir.mkdir(parents=True, exist_ok=True)
+
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
+
+    objs, built = [], False
+    for name in WALK_SOURCES:
+        src = WALK_CSRC / name
+        obj = objdir / (src.stem + ".o")
+        objs.append(obj)
+        if force or _stale(obj, [src, *HEADERS, *TRACE_HEADERS, *WALK_HEADERS, Path(__file__)]):
+            run([hipcc, *HIPCC_FLAGS, f"-cuid=rls_walk.{src.stem}", "-DRLS_FAST=0", "-c", str(src), "-o", str(obj)])
+            built = True
+    if force or built or _stale(WALK_LIB, [*objs, main]):
+        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(WALK_LIB), *map(str, objs),
+             f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"])
+    return WALK_LIB
+
+
+def build_walk_example(verbose: bool = False, name: str = "example_walk") -> Path:
+    """host/example_walk.cpp against the three libraries (probe emit -> walk over a host-side closest-hit function -> resolve)."""
+    OBJDIR.mkdir(exist_ok=True)
+    trace, lib = build_trace_library(verbose=verbose), build_walk_library(verbose=verbose)
+    src, out = PKG / "host" / f"{name}.cpp", OBJDIR / name
+    if _stale(out, [src, PKG / "host" / "rls_walk.hpp", PKG / "host" / "rls_trace.hpp", lib, trace, LIB, *HEADERS, *TRACE_HEADERS,
+                    *WALK_HEADERS]):
+        cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{PKG / 'host'}", str(src), "-o", str(out),
+               f"-L{LIBDIR}", "-lrls_walk", "-lrls_trace", "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib",
+               "-Wl,-rpath,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
+    return out
+
+
 def build_host_examples(verbose: bool = False) -> Path:
     """Compile-check the C++ host mirror (header-only) and its example against the C ABI."""
     OBJDIR.mkdir(exist_ok=True)

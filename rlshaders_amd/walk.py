@@ -1,0 +1,233 @@
+"""rlSss's probe walk on the device (include/rlshaders_amd_walk.h, companion library ``librls_walk.so``): between
+``trace.sss_probe_rays`` and ``ProbeQueue.resolve`` the reference walks every probe ray through the object
+(SssSampler::traceProbe, src/rlSss.h:288-357).  ``ProbeWalk`` is that walk; the renderer's part is a nearest-hit query.
+
+    p = trace.sss_probe_rays(sss, P, spp_n=4, seed=7)            # the probe rays, dense
+    w = walk.ProbeWalk(ctx, p, P)                                # begin: the rays with maxdist > 0 listed
+    while w.active:                                              # at most 12 steps: the walk's trial budget
+        r = w.rays                                               # views of the list: r.ray, r.origin, r.dir, r.maxdist [.., active]
+        w.step(my_nearest_hit(r.origin, r.dir, r.maxdist))       # Found(hit, t, P, N, Ns[, object]), one entry per listed ray
+    res = p.resolve(*w.hits(E))                                  # count, P, N as the resolves read them, E the caller's
+
+    walk.run(p, P, tracer)                                       # the loop above; tracer(rays, active) -> Found
+
+``active`` reads the device (it synchronises); ``step`` does not, and with ``bound`` left at the list's capacity a whole walk
+of 12 steps can be recorded by ``ctx.capture()``: steps on an empty list do nothing.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from pathlib import Path
+from types import SimpleNamespace
+from typing import Optional
+
+import torch
+
+from . import _capi as capi
+from . import trace
+from ._capi import check
+from .closures import cvec3
+
+WALK_LIB_PATH = capi._PKG / "lib" / "librls_walk.so"
+
+RLS_WALK_TRIALS = 12
+RLS_WALK_FOREIGN_STOPS = 0
+RLS_WALK_FOREIGN_SKIPS = 1
+FOREIGN = {"stop": RLS_WALK_FOREIGN_STOPS, "skip": RLS_WALK_FOREIGN_SKIPS}
+
+
+class WalkRays_(C.Structure):
+    """rls_walk_rays"""
+    _fields_ = [("capacity", C.c_int64), ("count", C.c_void_p), ("ray", C.c_void_p), ("origin", capi.Vec3), ("dir", capi.Vec3),
+                ("maxdist", C.c_void_p), ("trials", C.c_void_p)]
+
+
+class WalkFound_(C.Structure):
+    """rls_walk_found"""
+    _fields_ = [("hit", C.c_void_p), ("t", C.c_void_p), ("P", capi.CVec3), ("N", capi.CVec3), ("Ns", capi.CVec3),
+                ("object", C.c_void_p)]
+
+
+class WalkHits_(C.Structure):
+    """rls_walk_hits"""
+    _fields_ = [("max_hits", C.c_int), ("stride", C.c_int64), ("count", C.c_void_p), ("P", capi.Vec3), ("N", capi.Vec3)]
+
+
+class Walk_(C.Structure):
+    """rls_walk"""
+    _fields_ = [("rays", C.c_int64), ("spp", C.c_int), ("point", C.c_void_p), ("P", capi.CVec3), ("own", C.c_void_p),
+                ("foreign", C.c_int), ("hits", WalkHits_), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+_ctx, _i64 = C.c_void_p, C.c_int64
+PROTOTYPES = {
+    "rls_walk_scratch_bytes": (C.c_int, [_i64, C.POINTER(C.c_size_t)]),
+    "rls_walk_begin": (C.c_int, [_ctx, C.POINTER(Walk_), C.POINTER(trace.ProbeQueue_), C.POINTER(WalkRays_)]),
+    "rls_walk_step": (C.c_int, [_ctx, C.POINTER(Walk_), C.POINTER(WalkRays_), C.POINTER(WalkFound_), _i64, C.POINTER(WalkRays_)]),
+    "rls_walk_active": (C.c_int, [_ctx, C.POINTER(WalkRays_), C.POINTER(C.c_int64)]),
+}
+
+_lib = None
+
+
+def load() -> C.CDLL:
+    """Load (once) and prototype the companion library; RLSHADERS_AMD_WALK_LIB overrides its path.  The product and the trace
+    library are loaded first (contexts, errors; the queues the walk starts on)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    trace.load()
+    path = Path(os.environ.get("RLSHADERS_AMD_WALK_LIB", str(WALK_LIB_PATH)))
+    if not path.exists():
+        raise RuntimeError(f"rlshaders_amd.walk: {path} not found. Build it with "
+                           f"`python -c 'from rlshaders_amd import build; build.build_walk_library()'` (needs hipcc).")
+    lib = C.CDLL(str(path), mode=C.RTLD_GLOBAL)
+    missing = [n for n in PROTOTYPES if not hasattr(lib, n)]
+    if missing:
+        raise RuntimeError(f"rlshaders_amd.walk: {path} lacks C-ABI symbols: {missing}")
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    _lib = lib
+    return lib
+
+
+def scratch_bytes(rays: int) -> int:
+    b = C.c_size_t()
+    check(load().rls_walk_scratch_bytes(int(rays), C.byref(b)))
+    return int(b.value)
+
+
+def _rows(t: torch.Tensor, n: int, what: str, cls):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.shape[0] != 3 or \
+            t.shape[1] < n or t.stride(1) != 1:
+        raise ValueError(f"{what}: expected a float32 CUDA tensor [3, >= {n}] with unit inner stride")
+    return cls(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+
+
+def _flat(t: torch.Tensor, n: int, what: str, dtypes) -> int:
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or not t.is_cuda or t.dim() != 1 or t.shape[0] < n or \
+            not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous CUDA tensor [>= {n}] of {' or '.join(str(d) for d in dtypes)}")
+    return t.data_ptr()
+
+
+class Found:
+    """The renderer's nearest hit of every listed ray (rls_walk_found), indexed like the list a step reads: hit uint8 (or bool),
+    t float32 (sg->Rl from the step's origin), P, N, Ns float32 [3, >= active], object int32 ids or None."""
+
+    def __init__(self, hit, t, P, N, Ns, object=None):
+        self.hit, self.t, self.P, self.N, self.Ns, self.object = hit, t, P, N, Ns, object
+
+    def struct(self, n: int) -> WalkFound_:
+        f = WalkFound_()
+        f.hit = _flat(self.hit, n, "found.hit", (torch.uint8, torch.bool))
+        f.t = _flat(self.t, n, "found.t", (torch.float32,))
+        f.P, f.N, f.Ns = (_rows(t, n, "found." + k, capi.CVec3) for k, t in (("P", self.P), ("N", self.N), ("Ns", self.Ns)))
+        f.object = None if self.object is None else _flat(self.object, n, "found.object", (torch.int32,))
+        return f
+
+
+class _List:
+    """one active list's device buffers and its struct"""
+
+    def __init__(self, alloc, cap: int):
+        self.count = alloc((1,), torch.int64)
+        self.ray = alloc((cap,), torch.int32)                        # uint32 on the device; rays < 2^31 here
+        self.origin = alloc((3, cap), torch.float32)
+        self.dir = alloc((3, cap), torch.float32)
+        self.maxdist = alloc((cap,), torch.float32)
+        self.trials = alloc((cap,), torch.uint8)
+        s = WalkRays_()
+        s.capacity, s.count, s.ray = cap, self.count.data_ptr(), self.ray.data_ptr()
+        s.origin = capi.Vec3(*[self.origin[k].data_ptr() for k in range(3)])
+        s.dir = capi.Vec3(*[self.dir[k].data_ptr() for k in range(3)])
+        s.maxdist, s.trials = self.maxdist.data_ptr(), self.trials.data_ptr()
+        self.s = s
+
+
+class ProbeWalk:
+    """The walk of a probe queue's rays (``trace.sss_probe_rays``, or ``trace.skin_node_rays(...).probe``) about the shading
+    points P [3, n]: begun on construction.  own: int32 [n], the id of each point's own object, or None for one object everywhere;
+    foreign: "stop" (the compiled reference) or "skip" (include/rlshaders_amd_walk.h).  alloc(shape, dtype) -> a contiguous device
+    tensor: where the walk's lists and hits come from (torch.empty by default); scratch: a uint8 tensor of scratch_bytes(rays);
+    point: int32 [rays], each ray's point (the queue's ``point`` plane) where it is not j // spp_n^2."""
+
+    def __init__(self, ctx, queue, P: torch.Tensor, own: Optional[torch.Tensor] = None, max_hits: int = trace.RLS_MAX_PROBE_HITS,
+                 foreign: str = "stop", scratch: Optional[torch.Tensor] = None, alloc=None, point: Optional[torch.Tensor] = None):
+        self.ctx, self.queue, self.P, self.own, self.point = ctx, queue, P, own, point
+        dev = ctx.torch_device
+        rays = self.count = int(queue.count)
+        self.max_hits = int(max_hits)
+        if alloc is None:
+            alloc = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        self.hit_count = alloc((rays,), torch.uint8)
+        self.hit_P = alloc((3, self.max_hits, rays), torch.float32)
+        self.hit_N = alloc((3, self.max_hits, rays), torch.float32)
+        need = scratch_bytes(rays)
+        self.scratch = alloc((need,), torch.uint8) if scratch is None else scratch
+        if self.scratch.dtype != torch.uint8 or not self.scratch.is_contiguous() or self.scratch.numel() < need:
+            raise ValueError(f"scratch: expected a contiguous uint8 CUDA tensor of >= {need} bytes")
+        self.lists = [_List(alloc, rays), _List(alloc, rays)]
+        self.at = 0                                                 # the list the next step reads
+        w = Walk_()
+        w.rays, w.spp = rays, queue.spp_n * queue.spp_n
+        w.point = None if point is None else _flat(point, rays, "point", (torch.int32,))
+        w.P = cvec3(P, queue.n, "P") if queue.n > 0 else capi.CVec3(None, None, None)
+        w.own = None if own is None else _flat(own, queue.n, "own", (torch.int32,))
+        if foreign not in FOREIGN:
+            raise ValueError("foreign: 'stop' or 'skip'")
+        w.foreign = FOREIGN[foreign]
+        w.hits.max_hits, w.hits.stride, w.hits.count = self.max_hits, rays, self.hit_count.data_ptr()
+        w.hits.P = capi.Vec3(*[self.hit_P[k].data_ptr() for k in range(3)])
+        w.hits.N = capi.Vec3(*[self.hit_N[k].data_ptr() for k in range(3)])
+        w.scratch, w.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel()
+        self.w = w
+        self.begin()
+
+    def begin(self) -> "ProbeWalk":
+        """(re)start the walk on the queue as it is now"""
+        self.at = 0
+        check(load().rls_walk_begin(self.ctx.handle, C.byref(self.w), C.byref(self.queue.q), C.byref(self.lists[0].s)))
+        return self
+
+    @property
+    def rays(self) -> SimpleNamespace:
+        """the list the next step reads, as tensors of its capacity: entries [0, active) are the active rays"""
+        l = self.lists[self.at]
+        return SimpleNamespace(count=l.count, ray=l.ray, origin=l.origin, dir=l.dir, maxdist=l.maxdist, trials=l.trials)
+
+    @property
+    def active(self) -> int:
+        """the active rays, read from the device (synchronises)"""
+        n = C.c_int64()
+        check(load().rls_walk_active(self.ctx.handle, C.byref(self.lists[self.at].s), C.byref(n)))
+        return int(n.value)
+
+    def step(self, found: Found, bound: Optional[int] = None) -> "ProbeWalk":
+        """one step over the nearest hits of the listed rays; bound: an upper bound on the active count (it sizes the grid and the
+        planes ``found`` must hold), by default the list's capacity"""
+        b = self.count if bound is None else min(int(bound), self.count)
+        check(load().rls_walk_step(self.ctx.handle, C.byref(self.w), C.byref(self.lists[self.at].s), C.byref(found.struct(b)),
+                                   -1 if bound is None else b, C.byref(self.lists[self.at ^ 1].s)))
+        self.at ^= 1
+        return self
+
+    def hits(self, E: Optional[torch.Tensor] = None) -> tuple:
+        """(count, P, N, E): the arguments of ``ProbeQueue.resolve`` and of ``trace.sss_hit_rays`` (E: the caller's irradiance
+        planes [3, max_hits, rays], passed through)"""
+        return self.hit_count, self.hit_P, self.hit_N, E
+
+
+def run(queue, P: torch.Tensor, tracer, own: Optional[torch.Tensor] = None, max_hits: int = trace.RLS_MAX_PROBE_HITS,
+        foreign: str = "stop", ctx=None) -> ProbeWalk:
+    """Walk the queue's rays to the end: tracer(rays, active) -> Found, the nearest hits of the first ``active`` listed rays.  At most
+    RLS_WALK_TRIALS steps, the walk's trial budget."""
+    w = ProbeWalk(queue.ctx if ctx is None else ctx, queue, P, own=own, max_hits=max_hits, foreign=foreign)
+    for _ in range(RLS_WALK_TRIALS):
+        m = w.active
+        if m == 0:
+            break
+        w.step(tracer(w.rays, m), bound=m)
+    return w

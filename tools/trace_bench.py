@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce|shadow-fold|route] [--mix even|skewed|one] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
+    python tools/trace_bench.py [--closure ggx|disney|sss|sss-walk|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce|shadow-fold|route] [--mix even|skewed|one] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -16,6 +16,12 @@ rlSss: the emit writes 12 (origin) + 12 (dir) + 4 (maxdist) + 4 (point) + 1 (sam
 dense); the resolve reads 1 B of count per ray plus 12 (P) + 12 (N) + 12 (irradiance) = 36 B per reported hit slot.  Its
 hits come from a plane intersected with torch on the device (the shading points lie on the plane z = 0, lit from +z):
 timing needs plausible hits, not the oracle's.
+--closure sss-walk: the probe walk (rlshaders_amd.walk, librls_walk.so) on --closure sss's closure with the shading points on a
+sphere of radius 0.5 about the origin (the plane ends every walk after one hit): rls_walk_begin, then step by step over a torch
+closest-hit tracer -- the active count, the nearest hits, the accepted hits, the survivors, the step's time (the tracer's is
+outside the events) and the bytes it moves -- the sum over the walk, and sss_probe_emit and sss_scatter_resolve from the same
+process.  Medians of at least 9 whole walks after at least 3 warm-up walks, device events.
+
 --closure sss-hits: the same plane and probe hits (about 0.5 a ray) shaded through the caller's tracer (trace.sss_hit_rays,
 HitQueues.resolve) under --lights lights at --hit-spp-n^2 samples a light (default 1), with the diffuse ray: the hits emit (the
 gate, the list, both queues) and the resolve, uniform random visibility and radiance; hit_capacity is the ray count (one slot a
@@ -182,6 +188,91 @@ def bench_sss(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
         "resolve_tb_per_s": rate(res_bytes, ms_res), "resolve_frac_of_8tbps": round(rate(res_bytes, ms_res) / HBM_TBPS, 4),
         "emit_over_integrate": round(ms_emit / ms_int, 4),
         "emit_plus_resolve_over_integrate": round((ms_emit + ms_res) / ms_int, 4),
+    }
+
+
+def bench_sss_walk(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """bench_sss's closure on a sphere (module docstring, --closure sss-walk): the probe walk step by step"""
+    import math
+    import torch
+    import rlshaders_amd as R
+    from rlshaders_amd import build, trace as T, walk as W
+    build.build_walk_library()
+    repeats, warmup = max(args.repeats, 9), max(args.warmup, 3)
+    dev, radius = ctx.torch_device, 0.5
+    _, Ns, Tg = R.gen_frame(ctx, seed, 0, n)
+    P = (Ns * radius).contiguous()
+    s = R.SssSampler(ctx, Ns, Tg, (0.8, 0.5, 0.3), (0.05, 0.1, 0.2))
+    q = T.ProbeQueue(ctx, n, spp_n)
+    res = ctx.empty(3, n)
+    ms_emit = timed(lambda: T.sss_probe_rays(s, P, spp_n, seed, queue=q), repeats, warmup)
+    rays = q.count
+    w = W.ProbeWalk(ctx, q, P)
+
+    def closest(r, m):
+        """the renderer: the sphere's closest hit in (0, maxdist] of the first m listed rays"""
+        o, d, md = r.origin[:, :m], r.dir[:, :m], r.maxdist[:m]
+        a, b, c = (d * d).sum(0), (o * d).sum(0), (o * o).sum(0) - radius * radius
+        sq = (b * b - a * c).clamp_min(0).sqrt()
+        t0, t1 = (-b - sq) / a, (-b + sq) / a
+        t = torch.where(t0 > 0, t0, t1)
+        hit = (b * b - a * c >= 0) & (t > 0) & (t <= md)
+        hp = (o + d * t).contiguous()
+        nrm = (hp / radius).contiguous()
+        return W.Found(hit.to(torch.uint8), t.contiguous(), hp, nrm, nrm), int(hit.sum().item())
+
+    steps, begin_ms = [], []
+    for run in range(warmup + repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        w.begin()
+        b.record()
+        b.synchronize()
+        begin_ms.append(a.elapsed_time(b))
+        for k in range(W.RLS_WALK_TRIALS):
+            m = w.active
+            if m == 0:
+                break
+            found, hits = closest(w.rays, m)
+            stored = int(w.hit_count.sum(dtype=torch.int64).item())
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            w.step(found, bound=m)
+            b.record()
+            b.synchronize()
+            if k == len(steps):
+                steps.append({"active": m, "hits": hits, "ms": []})
+            if run >= warmup:
+                steps[k]["ms"].append(a.elapsed_time(b))
+            if run == warmup:
+                steps[k]["accepted"] = int(w.hit_count.sum(dtype=torch.int64).item()) - stored
+                steps[k]["survivors"] = w.active
+    total_ms = total_bytes = 0.0
+    for st in steps:
+        ms = sorted(st.pop("ms"))
+        # per listed ray, the step kernel reads ray 4, maxdist 4, trials 1, hit 1, count 1, prev 12 and writes flag 1, left 4; the
+        # place kernel reads ray 4 and flag 1 again: 33.  A hit: t 4, P / N / Ns 36.  An accepted hit: P / N 24 and count 1
+        # written.  A survivor: found.P 12, dir 12, left 4 read, ray 4, trials 1, origin 12, dir 12, maxdist 4 written: 61.
+        bytes_ = st["active"] * 33 + st["hits"] * 40 + st["accepted"] * 25 + st["survivors"] * 61
+        st.update(ms=round(ms[len(ms) // 2], 4), min_ms=round(ms[0], 4), max_ms=round(ms[-1], 4), bytes=bytes_,
+                  tb_per_s=rate(bytes_, ms[len(ms) // 2]))
+        total_ms += st["ms"]
+        total_bytes += bytes_
+    begin_ms = sorted(begin_ms[warmup:])
+    cnt, hP, hN, _ = w.hits()
+    E = torch.full((3, w.max_hits, rays), 1.0 / math.pi, device=dev)
+    ms_res = timed(lambda: q.resolve(cnt, hP, hN, E, out=res), repeats, warmup)
+    # the copy DESIGN section 5 measures the kernels against, over as many bytes as the first step moves
+    a_, b_ = (torch.empty(max(steps[0]["bytes"] // 2, 1), dtype=torch.uint8, device=dev) for _ in range(2))
+    copy = timed_spread(lambda: b_.copy_(a_), repeats, warmup)
+    rec["sss-walk"] = {
+        "rays": rays, "repeats": repeats, "warmup": warmup, "begin_ms": round(begin_ms[len(begin_ms) // 2], 4),
+        "begin_tb_per_s": rate(rays * 7 + steps[0]["active"] * 61, begin_ms[len(begin_ms) // 2]), "steps": steps,
+        "walk_ms": round(total_ms, 4), "walk_bytes": int(total_bytes), "walk_tb_per_s": rate(total_bytes, total_ms),
+        "hits_per_ray": round(int(cnt.sum(dtype=torch.int64).item()) / max(rays, 1), 4),
+        "emit_ms": round(ms_emit, 4), "resolve_ms": round(ms_res, 4),
+        "walk_over_emit_plus_resolve": round((total_ms + begin_ms[len(begin_ms) // 2]) / (ms_emit + ms_res), 4),
+        "copy_of_first_step_bytes_ms": copy["ms"], "copy_tb_per_s": rate(steps[0]["bytes"], copy["ms"]),
     }
 
 
@@ -653,7 +744,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
     ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
-                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "route"), default="ggx")
+                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "route", "sss-walk"), default="ggx")
     ap.add_argument("--mix", choices=("even", "skewed", "one"), default="even", help="route: the rays' split over 3 bins and the misses")
     ap.add_argument("--state", choices=("camera", "secondary", "half", "diffuse"), default="camera",
                     help="the bounce closures: every point a camera ray at depth 0, a glossy ray's hit at depth 1, or the two alternating; "
@@ -679,7 +770,7 @@ def main() -> None:
            "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
     if args.closure != "ggx":
         rec["closure"] = args.closure
-        {"disney": bench_disney, "sss": bench_sss, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
+        {"disney": bench_disney, "sss": bench_sss, "sss-walk": bench_sss_walk, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
          "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce,
          "shadow-fold": bench_shadow_fold, "route": bench_route}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
