@@ -260,6 +260,63 @@ def build_walk_example(verbose: bool = False, name: str = "example_walk") -> Pat
     return out
 
 
+# ---- the shadow rays' walk (include/rlshaders_amd_shadow_walk.h): a fourth companion, built like the probe walk's -- one
+# mode-free unit with RLS_FAST=0, the same flags, a fixed -cuid, the trace library's scan kernels included from csrc_trace/ --
+# and linked against librlshaders_amd.so alone, found by $ORIGIN.
+SHADOW_WALK_CSRC = PKG / "csrc_shadow_walk"
+SHADOW_WALK_SOURCES = ["shadow_walk.hip"]
+SHADOW_WALK_LIB = LIBDIR / "librls_shadow_walk.so"
+SHADOW_WALK_HEADERS = [*sorted(SHADOW_WALK_CSRC.glob("*.hpp")), PKG.parent / "include" / "rlshaders_amd_shadow_walk.h",
+                       PKG.parent / "include" / "rlshaders_amd_walk.h"]
+
+
+def build_shadow_walk_library(force: bool = False, verbose: bool = False) -> Path:
+    """Compile csrc_shadow_walk/ for gfx950 and link librls_shadow_walk.so against the product library.  Returns its path."""
+    hipcc = _hipcc()
+    main = build_library(verbose=verbose)
+    objdir = OBJDIR / "shadow_walk"
+    objdir.mkdir(parents=True, exist_ok=True)
+
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
+
+    objs, built = [], False
+    for name in SHADOW_WALK_SOURCES:
+        src = SHADOW_WALK_CSRC / name
+        obj = objdir / (src.stem + ".o")
+        objs.append(obj)
+        if force or _stale(obj, [src, *HEADERS, *TRACE_HEADERS, *SHADOW_WALK_HEADERS, Path(__file__)]):
+            run([hipcc, *HIPCC_FLAGS, f"-cuid=rls_shadow_walk.{src.stem}", "-DRLS_FAST=0", "-c", str(src), "-o", str(obj)])
+            built = True
+    if force or built or _stale(SHADOW_WALK_LIB, [*objs, main]):
+        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(SHADOW_WALK_LIB), *map(str, objs),
+             f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"])
+    return SHADOW_WALK_LIB
+
+
+def build_shadow_walk_example(verbose: bool = False, name: str = "example_shadow_walk") -> Path:
+    """host/example_shadow_walk.cpp against the product, the trace library and the shadow walk (light-loop emit -> walk over a
+    host-side closest-hit function -> resolve)."""
+    OBJDIR.mkdir(exist_ok=True)
+    trace, lib = build_trace_library(verbose=verbose), build_shadow_walk_library(verbose=verbose)
+    src, out = PKG / "host" / f"{name}.cpp", OBJDIR / name
+    if _stale(out, [src, PKG / "host" / "rls_shadow_walk.hpp", PKG / "host" / "rls_trace.hpp", lib, trace, LIB, *HEADERS,
+                    *TRACE_HEADERS, *SHADOW_WALK_HEADERS]):
+        cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{PKG / 'host'}", str(src), "-o", str(out),
+               f"-L{LIBDIR}", "-lrls_shadow_walk", "-lrls_trace", "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib",
+               "-Wl,-rpath,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
+    return out
+
+
 def build_host_examples(verbose: bool = False) -> Path:
     """Compile-check the C++ host mirror (header-only) and its example against the C ABI."""
     OBJDIR.mkdir(exist_ok=True)

@@ -1,0 +1,225 @@
+"""Shadow rays walked on the device (include/rlshaders_amd_shadow_walk.h, companion library ``librls_shadow_walk.so``): between
+a light loop's emit and its resolve the renderer owes a visibility per shadow ray.  ``trace.shadow_visibility`` folds it from a
+finished list of all hits of every ray; ``ShadowWalk`` forms the same plane from NEAREST hits, surface by surface, and ends a
+ray at an opaque surface, at the light, or when its budget of steps is spent.
+
+    q = trace.ggx_shadow_rays(ggx, shader, P, lights, spp_n=2, seed=7)   # the light loop's shadow rays
+    w = shadow_walk.ShadowWalk(ctx, q, P, max_steps=8)                   # begin: T = 1, the rays with maxdist > 0 listed
+    while w.active:                                                      # at most max_steps steps
+        r = w.rays                                                       # views of the list: r.ray, r.origin, r.dir, r.maxdist
+        w.step(my_nearest_hit(r.origin, r.dir, r.maxdist))               # Found(hit, t, P, opacity[, index]), an entry per listed ray
+    dd, ds = q.resolve(w.visibility)                                     # T of every ray: what every resolve reads
+
+    shadow_walk.run(q, P, tracer, max_steps=8)                           # the loop above; tracer(rays, active) -> Found
+
+``active`` reads the device (it synchronises); the constructor and ``step`` do not -- the queue's ray count is read on the
+device -- and with ``bound`` left at the list's capacity a whole walk can be recorded by ``ctx.capture()``: steps on an empty
+list do nothing.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from pathlib import Path
+from types import SimpleNamespace
+from typing import Optional
+
+import torch
+
+from . import _capi as capi
+from . import trace
+from ._capi import check
+from .walk import WalkRays_, _flat, _List                 # the active list is the probe walk's (rls_walk_rays)
+
+SHADOW_WALK_LIB_PATH = capi._PKG / "lib" / "librls_shadow_walk.so"
+
+RLS_SHADOW_WALK_MAX_STEPS = 255
+
+
+class ShadowWalkFound_(C.Structure):
+    """rls_shadow_walk_found"""
+    _fields_ = [("hit", C.c_void_p), ("t", C.c_void_p), ("P", capi.CVec3), ("opacity", capi.CRgb), ("index", C.c_void_p),
+                ("table_count", C.c_uint32)]
+
+
+class ShadowWalk_(C.Structure):
+    """rls_shadow_walk"""
+    _fields_ = [("rays", C.c_int64), ("count", C.c_void_p), ("max_steps", C.c_int), ("O", capi.CVec3), ("via", C.c_void_p),
+                ("base", capi.CRgb), ("visibility", capi.Rgb), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
+_ctx, _i64 = C.c_void_p, C.c_int64
+PROTOTYPES = {
+    "rls_shadow_walk_scratch_bytes": (C.c_int, [_i64, C.POINTER(C.c_size_t)]),
+    "rls_shadow_walk_begin": (C.c_int, [_ctx, C.POINTER(ShadowWalk_), C.POINTER(trace.ShadowQueue_), C.POINTER(WalkRays_)]),
+    "rls_shadow_walk_step": (C.c_int, [_ctx, C.POINTER(ShadowWalk_), C.POINTER(WalkRays_), C.POINTER(ShadowWalkFound_), _i64,
+                                       C.POINTER(WalkRays_)]),
+    "rls_shadow_walk_active": (C.c_int, [_ctx, C.POINTER(WalkRays_), C.POINTER(C.c_int64)]),
+}
+
+_lib = None
+
+
+def load() -> C.CDLL:
+    """Load (once) and prototype the companion library; RLSHADERS_AMD_SHADOW_WALK_LIB overrides its path.  The product and the
+    trace library are loaded first (contexts, errors; the queues the walk starts on)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    trace.load()
+    path = Path(os.environ.get("RLSHADERS_AMD_SHADOW_WALK_LIB", str(SHADOW_WALK_LIB_PATH)))
+    if not path.exists():
+        raise RuntimeError(f"rlshaders_amd.shadow_walk: {path} not found. Build it with "
+                           f"`python -c 'from rlshaders_amd import build; build.build_shadow_walk_library()'` (needs hipcc).")
+    lib = C.CDLL(str(path), mode=C.RTLD_GLOBAL)
+    missing = [n for n in PROTOTYPES if not hasattr(lib, n)]
+    if missing:
+        raise RuntimeError(f"rlshaders_amd.shadow_walk: {path} lacks C-ABI symbols: {missing}")
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    _lib = lib
+    return lib
+
+
+def scratch_bytes(rays: int) -> int:
+    b = C.c_size_t()
+    check(load().rls_shadow_walk_scratch_bytes(int(rays), C.byref(b)))
+    return int(b.value)
+
+
+def _rows(t: torch.Tensor, n: int, what: str, cls):
+    """three planes of >= n floats (a plane of one element has no inner stride to speak of)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.shape[0] != 3 or \
+            t.shape[1] < n or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what}: expected a float32 CUDA tensor [3, >= {n}] with unit inner stride")
+    return cls(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+
+
+class Found:
+    """The renderer's nearest hit of every listed ray (rls_shadow_walk_found), indexed like the list a step reads: hit uint8 (or
+    bool), t float32 (the distance from the entry's origin), P float32 [3, >= active], and the hit's opacity: float32
+    [3, >= active] per entry, or with ``index`` (int32 [>= active], uint32 on the device) a table [3, table_count] of out_opacity
+    values, e.g. ``trace.ggx_opacity``'s; an index past the table reads its last entry."""
+
+    def __init__(self, hit, t, P, opacity, index=None):
+        self.hit, self.t, self.P, self.opacity, self.index = hit, t, P, opacity, index
+
+    def struct(self, n: int) -> ShadowWalkFound_:
+        f = ShadowWalkFound_()
+        f.hit = _flat(self.hit, n, "found.hit", (torch.uint8, torch.bool))
+        f.t = _flat(self.t, n, "found.t", (torch.float32,))
+        f.P = _rows(self.P, n, "found.P", capi.CVec3)
+        if self.index is None:
+            f.opacity, f.index, f.table_count = _rows(self.opacity, n, "found.opacity", capi.CRgb), None, 0
+        else:
+            f.opacity = _rows(self.opacity, 1, "found.opacity", capi.CRgb)
+            f.index, f.table_count = _flat(self.index, n, "found.index", (torch.int32,)), int(self.opacity.shape[1])
+        return f
+
+
+class RawQueue:
+    """A shadow queue over the caller's own planes, as far as the walk reads it: dir float32 [3, rays], maxdist float32 [rays],
+    point int32 [rays] (uint32 on the device), count: an int64 device tensor of one element holding the number of rays, or
+    None for all of them."""
+
+    def __init__(self, dir: torch.Tensor, maxdist: torch.Tensor, point: torch.Tensor, count: Optional[torch.Tensor] = None):
+        self.capacity = int(maxdist.shape[0])
+        self.dir, self.maxdist, self.point, self.count = dir, maxdist, point, count
+        q = trace.ShadowQueue_()
+        q.capacity = self.capacity
+        if self.capacity > 0:
+            q.dir = _rows(dir, self.capacity, "dir", capi.Vec3)
+            q.maxdist = _flat(maxdist, self.capacity, "maxdist", (torch.float32,))
+            q.point = _flat(point, self.capacity, "point", (torch.int32,))
+        self.q = q
+
+
+def _queue(queue):
+    """-> (rls_shadow_queue, capacity, the device address of its ray count or None)"""
+    if isinstance(queue, trace.HitQueues):
+        return queue.q.shadow, queue.shadow_capacity, queue.shadow_offsets[queue.hit_capacity:].data_ptr()
+    if isinstance(queue, trace.ShadowQueue):
+        return queue.q, queue.capacity, queue.offsets[queue.n:].data_ptr()
+    if isinstance(queue, RawQueue):
+        return queue.q, queue.capacity, None if queue.count is None else _flat(queue.count, 1, "count", (torch.int64,))
+    raise TypeError("queue: a trace.ShadowQueue (also the shadow queue of a node's queue set), a trace.HitQueues or a RawQueue")
+
+
+class ShadowWalk:
+    """The walk of a shadow queue's rays: begun on construction.  queue: a ``trace.ShadowQueue`` (``trace.ggx_shadow_rays``,
+    ``disney_shadow_rays``, the shadow queue of a node's queue set), a ``trace.HitQueues`` (its shadow queue, with
+    ``via=queues._hit_element`` and O the hit planes [3, max_hits * stride]) or a ``RawQueue``.  O [3, .]: the origins' table,
+    indexed by the queue's point plane (sg->P per point), or through ``via`` (int64).  base [3, >= rays]: T's start, None for
+    1; it may be ``out``.  max_steps: the surfaces a ray may cross, 1 .. 255.  out [3, >= rays]: the visibility planes;
+    scratch: a uint8 tensor of scratch_bytes(rays); alloc(shape, dtype) -> a contiguous device tensor: where the walk's lists,
+    visibility and scratch come from (torch.empty by default)."""
+
+    def __init__(self, ctx, queue, O: torch.Tensor, base: Optional[torch.Tensor] = None, via: Optional[torch.Tensor] = None,
+                 max_steps: int = 16, out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None, alloc=None):
+        self.ctx, self.queue, self.O, self.base, self.via = ctx, queue, O, base, via
+        dev = ctx.torch_device
+        self.q, rays, count = _queue(queue)
+        self.capacity, self.max_steps = rays, int(max_steps)
+        if alloc is None:
+            alloc = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        self.visibility = alloc((3, rays), torch.float32) if out is None else out
+        need = scratch_bytes(rays)
+        self.scratch = alloc((need,), torch.uint8) if scratch is None else scratch
+        if self.scratch.dtype != torch.uint8 or not self.scratch.is_contiguous() or self.scratch.numel() < need:
+            raise ValueError(f"scratch: expected a contiguous uint8 CUDA tensor of >= {need} bytes")
+        self.lists = [_List(alloc, rays), _List(alloc, rays)]
+        self.at = 0                                                 # the list the next step reads
+        w = ShadowWalk_()
+        w.rays, w.count, w.max_steps = rays, count, self.max_steps
+        if rays > 0:
+            w.O = _rows(O, 1, "O", capi.CVec3)
+            w.visibility = _rows(self.visibility, rays, "out", capi.Rgb)
+        w.via = None if via is None else _flat(via, 0, "via", (torch.int64,))
+        if base is not None and rays > 0:
+            w.base = _rows(base, rays, "base", capi.CRgb)
+        w.scratch, w.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel()
+        self.w = w
+        self.begin()
+
+    def begin(self) -> "ShadowWalk":
+        """(re)start the walk on the queue as it is now"""
+        self.at = 0
+        check(load().rls_shadow_walk_begin(self.ctx.handle, C.byref(self.w), C.byref(self.q), C.byref(self.lists[0].s)))
+        return self
+
+    @property
+    def rays(self) -> SimpleNamespace:
+        """the list the next step reads, as tensors of its capacity: entries [0, active) are the active rays; trials: the steps
+        left"""
+        l = self.lists[self.at]
+        return SimpleNamespace(count=l.count, ray=l.ray, origin=l.origin, dir=l.dir, maxdist=l.maxdist, trials=l.trials)
+
+    @property
+    def active(self) -> int:
+        """the active rays, read from the device (synchronises)"""
+        n = C.c_int64()
+        check(load().rls_shadow_walk_active(self.ctx.handle, C.byref(self.lists[self.at].s), C.byref(n)))
+        return int(n.value)
+
+    def step(self, found: Found, bound: Optional[int] = None) -> "ShadowWalk":
+        """one step over the nearest hits of the listed rays; bound: an upper bound on the active count (it sizes the grid and the
+        planes ``found`` must hold), by default the list's capacity"""
+        b = self.capacity if bound is None else min(int(bound), self.capacity)
+        check(load().rls_shadow_walk_step(self.ctx.handle, C.byref(self.w), C.byref(self.lists[self.at].s),
+                                          C.byref(found.struct(b)), -1 if bound is None else b, C.byref(self.lists[self.at ^ 1].s)))
+        self.at ^= 1
+        return self
+
+
+def run(queue, O: torch.Tensor, tracer, base: Optional[torch.Tensor] = None, via: Optional[torch.Tensor] = None,
+        max_steps: int = 16, out: Optional[torch.Tensor] = None, ctx=None) -> ShadowWalk:
+    """Walk the queue's rays to the end: tracer(rays, active) -> Found, the nearest hits of the first ``active`` listed rays.  At
+    most max_steps steps."""
+    w = ShadowWalk(queue.ctx if ctx is None else ctx, queue, O, base=base, via=via, max_steps=max_steps, out=out)
+    for _ in range(w.max_steps):
+        m = w.active
+        if m == 0:
+            break
+        w.step(tracer(w.rays, m), bound=m)
+    return w

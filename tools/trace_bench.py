@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss|sss-walk|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce|shadow-fold|route] [--mix even|skewed|one] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
+    python tools/trace_bench.py [--closure ggx|disney|sss|sss-walk|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce|shadow-fold|shadow-walk|route] [--mix even|skewed|one] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -59,6 +59,14 @@ probe walk), the node call beside it in the same process as for the other two no
 uniform in 0 .. 4, stride = rays, uniform random opacities, no base: `direct` (an opacity per element) and `indexed` (an index
 per element into a table of 4096 surfaces).  Bytes, direct: 1 (count) + 12 per hit read, 12 written per ray; indexed: 1 +
 (4 (index) + 12 (the table's entry, from cache)) per hit read, 12 written per ray.  --spp-n is not read.
+--closure shadow-walk: the shadow walk (rlshaders_amd.shadow_walk, librls_shadow_walk.so) over --closure shadow-fold's rays and
+surfaces in its indexed form: 2^log2n rays, ray j crossing count[j] (uniform in 0 .. 4) of the table's 4096 surfaces one unit of
+distance apart, no base.  Step k hands every listed ray its k-th surface (a hit while k < count[j]); the hits are prepared outside
+the timed calls.  begin, every step (median, fastest, slowest of at least 9 runs after at least 3 warm-up runs, device events) and
+their sum, beside rls_trace_shadow_visibility over the same hits given as a list, whose visibility the walk's must equal byte for
+byte.  Bytes of a step: 34 per listed ray (ray, maxdist, steps, hit, T read; state and left written; ray and state read again by
+the place kernel), 32 per hit (t, index, the table's entry from cache, T written), 61 per survivor (found.P, dir, left read; ray,
+steps, origin, dir, maxdist written).  --spp-n is not read.
 --closure route: routing 2^log2n traced rays to 3 node bins and the misses (trace.route_hits, HitRoutes) at --mix even (a
 quarter of the rays in each bin and a quarter misses), skewed (70 / 20 / 9 % and 1 % misses) or one (every ray in bin 0):
 route_hits without and with slot, a 12-plane gather and a 3-plane scatter of bin 0, the fill of the misses' 3 planes.  Beside
@@ -677,6 +685,84 @@ def bench_shadow_fold(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> No
         torch.cuda.empty_cache()
 
 
+def bench_shadow_walk(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """the shadow walk over bench_shadow_fold's indexed rays and surfaces, beside the fold of the same hits (module docstring)"""
+    import torch
+    from rlshaders_amd import build, shadow_walk as W, trace as T
+    build.build_shadow_walk_library()
+    repeats, warmup = max(args.repeats, 9), max(args.warmup, 3)
+    dev, max_hits, table_count = ctx.torch_device, 4, 4096
+    g = torch.Generator(device=dev).manual_seed(seed)
+    count = torch.randint(0, max_hits + 1, (n,), generator=g, device=dev).to(torch.uint8)
+    table = torch.rand(3, table_count, generator=g, device=dev)
+    index = torch.randint(0, table_count, (max_hits, n), generator=g, device=dev, dtype=torch.int32)
+    d = torch.randn(3, n, generator=g, device=dev)
+    d = (d / d.norm(dim=0)).contiguous()
+    O = torch.rand(3, n, generator=g, device=dev)
+    q = W.RawQueue(d, torch.full((n,), 1e3, device=dev), torch.arange(n, dtype=torch.int32, device=dev))
+    w = W.ShadowWalk(ctx, q, O, max_steps=2 * max_hits)
+    fold = ctx.empty(3, n)
+    hits = T.ShadowHits(count, table, max_hits, index=index)
+    fold_ms = timed_spread(lambda: T.shadow_visibility(ctx, n, hits, out=fold), repeats, warmup)
+
+    def found(r, m, k):
+        """the renderer: listed ray j meets its k-th surface one unit on, while it has one"""
+        j = r.ray[:m].long()
+        hit = count[j] > k
+        ix = index[min(k, max_hits - 1)][j].contiguous()
+        P = (r.origin[:, :m] + r.dir[:, :m]).contiguous()
+        return W.Found(hit.to(torch.uint8), torch.ones(m, device=dev), P, table, index=ix), int(hit.sum().item())
+
+    steps, begin_ms = [], []
+    for run in range(warmup + repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        w.begin()
+        b.record()
+        b.synchronize()
+        begin_ms.append(a.elapsed_time(b))
+        for k in range(w.max_steps):
+            m = w.active
+            if m == 0:
+                break
+            f, nhit = found(w.rays, m, k)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            w.step(f, bound=m)
+            b.record()
+            b.synchronize()
+            if k == len(steps):
+                steps.append({"active": m, "hits": nhit, "ms": []})
+            if run >= warmup:
+                steps[k]["ms"].append(a.elapsed_time(b))
+            if run == warmup:
+                steps[k]["survivors"] = w.active
+    same = bool(torch.equal(w.visibility.view(torch.int32), fold.view(torch.int32)))
+    total_ms = total_bytes = 0.0
+    for st in steps:
+        ms = sorted(st.pop("ms"))
+        bytes_ = st["active"] * 34 + st["hits"] * 32 + st["survivors"] * 61
+        st.update(ms=round(ms[len(ms) // 2], 4), min_ms=round(ms[0], 4), max_ms=round(ms[-1], 4), bytes=bytes_,
+                  bytes_per_active_ray=round(bytes_ / st["active"], 1), tb_per_s=rate(bytes_, ms[len(ms) // 2]))
+        total_ms += st["ms"]
+        total_bytes += bytes_
+    begin_ms = sorted(begin_ms[warmup:])
+    bm = begin_ms[len(begin_ms) // 2]
+    nhits = int(count.sum(dtype=torch.int64).item())
+    fold_bytes = n * (1 + 12) + nhits * (4 + 12)
+    rec["shadow-walk"] = {
+        "rays": n, "max_hits": max_hits, "table_count": table_count, "hits": nhits, "repeats": repeats, "warmup": warmup,
+        "begin_ms": round(bm, 4), "begin_min_ms": round(begin_ms[0], 4), "begin_max_ms": round(begin_ms[-1], 4),
+        # begin: per ray maxdist read, T and state written, state read again: 20; per listed ray point, O, dir, maxdist read and
+        # ray, steps, origin, dir, maxdist written: 65
+        "begin_tb_per_s": rate(n * 20 + steps[0]["active"] * 65, bm),
+        "steps": steps, "steps_ms": round(total_ms, 4), "steps_bytes": int(total_bytes), "steps_tb_per_s": rate(total_bytes, total_ms),
+        "walk_ms": round(bm + total_ms, 4), "fold_ms": fold_ms["ms"], "fold_min_ms": fold_ms["min_ms"], "fold_max_ms": fold_ms["max_ms"],
+        "fold_tb_per_s": rate(fold_bytes, fold_ms["ms"]), "walk_over_fold": round((bm + total_ms) / fold_ms["ms"], 2),
+        "walk_equals_fold": same,
+    }
+
+
 def timed_spread(fn, repeats: int, warmup: int) -> dict:
     """timed(), with the fastest and the slowest of the measured calls beside the median"""
     import torch
@@ -744,7 +830,8 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
     ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
-                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "route", "sss-walk"), default="ggx")
+                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk"),
+                    default="ggx")
     ap.add_argument("--mix", choices=("even", "skewed", "one"), default="even", help="route: the rays' split over 3 bins and the misses")
     ap.add_argument("--state", choices=("camera", "secondary", "half", "diffuse"), default="camera",
                     help="the bounce closures: every point a camera ray at depth 0, a glossy ray's hit at depth 1, or the two alternating; "
@@ -772,7 +859,7 @@ def main() -> None:
         rec["closure"] = args.closure
         {"disney": bench_disney, "sss": bench_sss, "sss-walk": bench_sss_walk, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
          "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce,
-         "shadow-fold": bench_shadow_fold, "route": bench_route}.get(
+         "shadow-fold": bench_shadow_fold, "shadow-walk": bench_shadow_walk, "route": bench_route}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
         print(json.dumps(rec), flush=True)
