@@ -317,6 +317,31 @@ def build_shadow_walk_example(verbose: bool = False, name: str = "example_shadow
     return out
 
 
+# ---- the test-only device probe of rls_libm.hpp's primitives (tests/native/libm_device_probe.hip): the product's own flags
+# and headers, one unit, a fixed -cuid, linked on its own (it calls nothing of the product) -- under tests/, so that no product
+# library gains an entry point.
+PROBE_SRC = PKG.parent / "tests" / "native" / "libm_device_probe.hip"
+PROBE_LIB = PKG.parent / "tests" / "native" / "build" / "librls_libm_probe.so"
+
+
+def build_libm_probe(force: bool = False, verbose: bool = False, include: Path = CSRC, out: Path = PROBE_LIB) -> Path:
+    """Compile tests/native/libm_device_probe.hip for gfx950 into tests/native/build/librls_libm_probe.so; rebuilt only when
+    the probe or a header is newer.  ``include`` / ``out`` build it against another copy of the headers (a mutated
+    rls_libm.hpp, to see the tests fail) next to the real one."""
+    hipcc = _hipcc()
+    out.parent.mkdir(parents=True, exist_ok=True)
+    headers = HEADERS if include == CSRC else sorted(Path(include).glob("*"))
+    if force or _stale(out, [PROBE_SRC, *headers, Path(__file__)]):
+        cmd = [hipcc, *HIPCC_FLAGS, "-cuid=rls_libm_probe.libm_device_probe", "-DRLS_FAST=0", f"-I{include}", "-shared",
+               str(PROBE_SRC), "-o", str(out)]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
+    return out
+
+
 def build_host_examples(verbose: bool = False) -> Path:
     """Compile-check the C++ host mirror (header-only) and its example against the C ABI."""
     OBJDIR.mkdir(exist_ok=True)

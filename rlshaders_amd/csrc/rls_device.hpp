@@ -357,9 +357,9 @@ RLS_DEV float slope_y_ratio(float u)
 #if RLS_FAST
     return R_DIVH(num, den);
 #else
-    // for u in [0, 1] (ry in [0, 1]) the denominator falls from 0.598 to 4.9e-4: the short division of rls_libm.hpp
-    // rounds like IEEE division for every such u (all 2^32 bit patterns of ry: tools/micro/exact1.hip); other u
-    // (random numbers outside [0, 1], NaN) take the IEEE sequence
+    // for ry in [0, 1], u = 2 |ry - 1/2| is 0 or a multiple of 2^-24 up to 1 and the denominator falls from 0.598 to 4.9e-4: the
+    // short division of rls_libm.hpp rounds like IEEE division for every such u (all 2^32 bit patterns of ry: tools/micro/exact1.hip;
+    // NOT for 0 < u < 2^-113, which no ry gives: tests/test_gpu_libm_primitives.py); u > 1 and NaN take the IEEE sequence
     if (__builtin_expect(!(u <= 1.0f), 0)) return num / den;
     return rlm::div32_m(num, den);
 #endif
