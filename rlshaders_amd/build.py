@@ -317,6 +317,81 @@ def build_shadow_walk_example(verbose: bool = False, name: str = "example_shadow
     return out
 
 
+# ---- nearest-hit queries over a triangle mesh (include/rlshaders_amd_nearest.h): a fifth companion -- one mode-free unit with
+# RLS_FAST=0, the same flags, a fixed -cuid -- linked against librlshaders_amd.so alone, found by $ORIGIN.  It includes nothing
+# of the other companions' sources; its header includes the probe walk's for the type of the walks' lists.
+NEAREST_CSRC = PKG / "csrc_nearest"
+NEAREST_SOURCES = ["nearest.hip"]
+NEAREST_LIB = LIBDIR / "librls_nearest.so"
+NEAREST_HEADERS = [NEAREST_CSRC / "rls_nearest_device.hpp", NEAREST_CSRC / "rls_nearest_bvh.hpp",
+                   PKG.parent / "include" / "rlshaders_amd_nearest.h", PKG.parent / "include" / "rlshaders_amd_walk.h",
+                   PKG.parent / "include" / "rlshaders_amd_trace.h"]
+
+
+def build_nearest_library(force: bool = False, verbose: bool = False) -> Path:
+    """Compile csrc_nearest/ for gfx950 and link librls_nearest.so against the product library.  Returns its path."""
+    hipcc = _hipcc()
+    main = build_library(verbose=verbose)
+    objdir = OBJDIR / "nearest"
+    objdir.mkdir(parents=True, exist_ok=True)
+
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
+
+    objs, built = [], False
+    for name in NEAREST_SOURCES:
+        src = NEAREST_CSRC / name
+        obj = objdir / (src.stem + ".o")
+        objs.append(obj)
+        if force or _stale(obj, [src, *HEADERS, *NEAREST_HEADERS, Path(__file__)]):
+            run([hipcc, *HIPCC_FLAGS, f"-cuid=rls_nearest.{src.stem}", "-DRLS_FAST=0", "-c", str(src), "-o", str(obj)])
+            built = True
+    if force or built or _stale(NEAREST_LIB, [*objs, main]):
+        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(NEAREST_LIB), *map(str, objs),
+             f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"])
+    return NEAREST_LIB
+
+
+def build_nearest_example(verbose: bool = False, name: str = "example_nearest") -> Path:
+    """host/example_nearest.cpp against the product, the trace library, both walks and the nearest-hit library (emit -> walk over
+    device nearest hits -> resolve: no host tracer)."""
+    OBJDIR.mkdir(exist_ok=True)
+    trace, walk, shadow = build_trace_library(verbose=verbose), build_walk_library(verbose=verbose), build_shadow_walk_library(verbose=verbose)
+    lib = build_nearest_library(verbose=verbose)
+    host = PKG / "host"
+    src, out = host / f"{name}.cpp", OBJDIR / name
+    if _stale(out, [src, host / "rls_nearest.hpp", host / "rls_shadow_walk.hpp", host / "rls_walk.hpp", host / "rls_trace.hpp", lib, trace,
+                    walk, shadow, LIB, *HEADERS, *TRACE_HEADERS, *WALK_HEADERS, *SHADOW_WALK_HEADERS, *NEAREST_HEADERS]):
+        cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{host}", str(src), "-o", str(out),
+               f"-L{LIBDIR}", "-lrls_nearest", "-lrls_shadow_walk", "-lrls_walk", "-lrls_trace", "-lrlshaders_amd",
+               f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
+    return out
+
+
+def build_nearest_stats(verbose: bool = False) -> Path:
+    """csrc_nearest/nearest_stats.cpp: the traversal source compiled for the host (g++, -ffp-contract=off, no HIP), counting the
+    nodes and triangles a ray visits (rlshaders_amd.nearest.host_stats)."""
+    OBJDIR.mkdir(exist_ok=True)
+    src, out = NEAREST_CSRC / "nearest_stats.cpp", OBJDIR / "nearest_stats"
+    if _stale(out, [src, NEAREST_CSRC / "rls_nearest_device.hpp", NEAREST_CSRC / "rls_nearest_bvh.hpp"]):
+        cmd = ["g++", "-std=c++14", "-O2", "-Wall", "-ffp-contract=off", str(src), "-o", str(out)]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"nearest_stats failed to build:\n{p.stdout}\n{p.stderr}")
+    return out
+
+
 # ---- the test-only device probe of rls_libm.hpp's primitives (tests/native/libm_device_probe.hip): the product's own flags
 # and headers, one unit, a fixed -cuid, linked on its own (it calls nothing of the product) -- under tests/, so that no product
 # library gains an entry point.

@@ -763,6 +763,170 @@ def bench_shadow_walk(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> No
     }
 
 
+def icosphere(level: int, radius: float = 1.0, center=(0.0, 0.0, 0.0)):
+    """a subdivided icosahedron, 20 * 4^level triangles -> (V float32 [nv, 3], tri uint32 [nt, 3], unit normals [nv, 3])"""
+    import numpy as np
+    g = (1 + 5 ** 0.5) / 2
+    V = np.array([(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1),
+                  (-g, 0, -1), (-g, 0, 1)], np.float64)
+    V /= np.linalg.norm(V, axis=1, keepdims=True)
+    T = np.array([(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+                  (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)], np.int64)
+    for _ in range(level):
+        e = np.sort(np.concatenate([T[:, [0, 1]], T[:, [1, 2]], T[:, [2, 0]]]), axis=1)
+        edges, inv = np.unique(e, axis=0, return_inverse=True)
+        mid = V[edges[:, 0]] + V[edges[:, 1]]
+        mid /= np.linalg.norm(mid, axis=1, keepdims=True)
+        m = (len(V) + inv.reshape(-1)).reshape(3, -1)              # the midpoints of ab, bc, ca of every triangle
+        V = np.concatenate([V, mid])
+        a, b, c = T[:, 0], T[:, 1], T[:, 2]
+        T = np.concatenate([np.stack(t, axis=1) for t in ((a, m[0], m[2]), (b, m[1], m[0]), (c, m[2], m[1]), (m[0], m[1], m[2]))])
+    return (V * radius + np.asarray(center, np.float64)).astype(np.float32), T.astype(np.uint32), V.astype(np.float32)
+
+
+def bench_nearest(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """rls_nearest_hits on an icosphere of 81 920 triangles: a camera grid's rays (coherent), then cosine-distributed rays from the
+    points they hit with `last` set (incoherent), each beside a copy_ of the bytes of its ray and found planes"""
+    import numpy as np
+    import torch
+    from rlshaders_amd import nearest
+    nearest.load()
+    repeats, warmup = max(args.repeats, 9), max(args.warmup, 3)
+    dev = ctx.torch_device
+    V, tri, normals = icosphere(args.level)
+    scene = nearest.Scene(ctx, V, tri, normals=normals)
+    side = int(round(n ** 0.5))
+    n = side * side
+    g = torch.Generator(device=dev).manual_seed(seed)
+    # a pinhole at (0, 0, -3) looking at the sphere through a side x side grid of 1.3 x 1.3 at z = -2: about half the rays hit
+    u = (torch.arange(side, device=dev, dtype=torch.float32) + 0.5) / side * 1.3 - 0.65
+    d = torch.stack([u.repeat(side), u.repeat_interleave(side), torch.ones(n, device=dev)]).contiguous()
+    o = torch.tensor([0.0, 0.0, -3.0], device=dev)[:, None].expand(3, n).contiguous()
+    planes = ("P", "N", "Ns", "surface", "prim")
+    found = nearest.Found(ctx, n, planes=planes)
+    rays = nearest.Rays(o, d)
+
+    def with_copy(fn, bytes_):
+        r = timed_spread(fn, repeats, warmup)
+        a, b = (torch.empty(max(bytes_ // 2, 1), dtype=torch.uint8, device=dev) for _ in range(2))
+        c = timed_spread(lambda: b.copy_(a), repeats, warmup)
+        del a, b
+        r.update({"bytes": bytes_, "copy_ms": c["ms"], "copy_min_ms": c["min_ms"], "copy_max_ms": c["max_ms"],
+                  "over_copy": round(r["ms"] / c["ms"], 2)})
+        return r
+
+    def account(r, hits, ray_bytes, hit_bytes, sample):
+        # read per ray: origin, dir (24) [+ last 4]; written per ray: hit (1); per hit: t, P, N, Ns, surface, prim (48) [+ last 4]
+        bytes_ = n * ray_bytes + n + hits * hit_bytes
+        out = with_copy(r, bytes_)
+        out.update({"rays": n, "hits": hits, "mrays_per_s": round(n / out["ms"] / 1e3, 1), "bytes_per_ray": round(bytes_ / n, 1)})
+        # the nodes and triangles a ray visits: the kernel's traversal source run on the host over the same tree, on every
+        # 4096 rays of the stream: one out of every run of n / 4096, at a place in the run that moves with the run (a fixed
+        # stride would pick two columns of the camera's grid)
+        o_, d_, skip_ = sample
+        run = max(n // 4096, 1)
+        k = torch.arange(min(n, 4096), device=dev)
+        pick = k * run + (k * 37) % run
+        st = nearest.host_stats(V, tri, o_[:, pick].cpu().numpy(), d_[:, pick].cpu().numpy(),
+                                skip=None if skip_ is None else skip_[pick].cpu().numpy().view(np.uint32), leaf_size=scene.leaf_size)
+        out.update({"sample_rays": st["rays"], "sample_hits": st["hits"], "nodes_per_ray": round(st["nodes"] / st["rays"], 1),
+                    "triangles_per_ray": round(st["triangles"] / st["rays"], 1)})
+        return out
+
+    scene.hits(rays, found=found)
+    hits = int(found.hit.sum(dtype=torch.int64).item())
+    rec["scene"] = {"triangles": scene.nt, "nodes": scene.nodes, "depth": scene.depth, "leaf_size": scene.leaf_size,
+                    "device_bytes": scene.device_bytes}
+    rec["coherent"] = account(lambda: scene.hits(rays, found=found), hits, 24, 48, (o, d, None))
+    # incoherent: from every hit point (the misses from points of the sphere chosen at random) a cosine-distributed direction
+    # about the inward normal, the triangle the point lies on skipped through `last`
+    hit = found.hit.bool()
+    Pn = torch.randn(3, n, generator=g, device=dev)
+    Pn = Pn / Pn.norm(dim=0)
+    O2 = torch.where(hit[None, :], found.P, Pn).contiguous()
+    inward = -(O2 / O2.norm(dim=0))
+    w = torch.randn(3, n, generator=g, device=dev)
+    w = w / w.norm(dim=0)
+    d2 = (inward + 0.999 * w).contiguous()                          # a unit vector about the normal's tip: cosine-distributed
+    last0 = torch.where(hit, found.prim, torch.full_like(found.prim, -1)).contiguous()
+    last = last0.clone()
+    rays2 = nearest.Rays(O2, d2)
+    found2 = nearest.Found(ctx, n, planes=planes)
+
+    def incoherent():
+        last.copy_(last0)
+        scene.hits(rays2, last=last, found=found2)
+
+    incoherent()
+    hits2 = int(found2.hit.sum(dtype=torch.int64).item())
+    reset = timed_spread(lambda: last.copy_(last0), repeats, warmup)
+    rec["incoherent"] = account(incoherent, hits2, 28, 52, (O2, d2, last0))
+    rec["incoherent"]["last_reset_ms"] = reset["ms"]               # inside the timed call: the copy that sets `last` again
+    scene.close()
+
+
+def bench_shadow_walk_nearest(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """a whole shadow walk with its queries inside the events: n rays from the unit cube through three nested tinted icospheres
+    (3 x 5 120 triangles, radii 2, 3, 4), every step = rls_nearest_walk_hits + rls_shadow_walk_step"""
+    import numpy as np
+    import torch
+    from rlshaders_amd import nearest, shadow_walk as W
+    W.load(), nearest.load()
+    repeats, warmup = max(args.repeats, 9), max(args.warmup, 3)
+    dev = ctx.torch_device
+    Vs, Ts, Ss = [], [], []
+    for k, radius in enumerate((2.0, 3.0, 4.0)):
+        V, tri, _ = icosphere(4, radius, (0.5, 0.5, 0.5))
+        Ts.append(tri + sum(len(v) for v in Vs))
+        Vs.append(V)
+        Ss.append(np.full(len(tri), k, np.uint32))
+    scene = nearest.Scene(ctx, np.concatenate(Vs), np.concatenate(Ts), surface=np.concatenate(Ss))
+    g = torch.Generator(device=dev).manual_seed(seed)
+    table = (torch.rand(3, 3, generator=g, device=dev) * 0.9).contiguous()
+    d = torch.randn(3, n, generator=g, device=dev)
+    d = (d / d.norm(dim=0)).contiguous()
+    O = torch.rand(3, n, generator=g, device=dev)
+    q = W.RawQueue(d, torch.full((n,), 1e3, device=dev), torch.arange(n, dtype=torch.int32, device=dev))
+    w = W.ShadowWalk(ctx, q, O, max_steps=8)
+    found = nearest.Found(ctx, n, planes=("P", "surface"))
+    last = torch.empty(n, dtype=torch.int32, device=dev)
+    steps, begin_ms = [], []
+    for run in range(warmup + repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        w.begin()
+        last.fill_(-1)
+        b.record()
+        b.synchronize()
+        begin_ms.append(a.elapsed_time(b))
+        for k in range(w.max_steps):
+            m = w.active
+            if m == 0:
+                break
+            a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            a.record()
+            scene.hits(w.rays, active=m, last=last, found=found)
+            b.record()
+            w.step(found.shadow_found(table), bound=m)
+            c.record()
+            c.synchronize()
+            if k == len(steps):
+                steps.append({"active": m, "hits": int(found.hit[:m].sum(dtype=torch.int64).item()), "trace_ms": [], "step_ms": []})
+            if run >= warmup:
+                steps[k]["trace_ms"].append(a.elapsed_time(b))
+                steps[k]["step_ms"].append(b.elapsed_time(c))
+    med = lambda v: round(sorted(v)[len(v) // 2], 4)
+    for st in steps:
+        st["trace_ms"], st["step_ms"] = med(st["trace_ms"]), med(st["step_ms"])
+    bm = med(begin_ms[warmup:])
+    trace_ms, step_ms = sum(st["trace_ms"] for st in steps), sum(st["step_ms"] for st in steps)
+    rec["shadow-walk"] = {"tracer": "nearest", "rays": n, "triangles": scene.nt, "nodes": scene.nodes, "repeats": repeats, "warmup": warmup,
+                          "begin_ms": bm, "steps": steps, "trace_ms": round(trace_ms, 4), "step_ms": round(step_ms, 4),
+                          "walk_ms": round(bm + trace_ms + step_ms, 4), "walk_only_ms": round(bm + step_ms, 4),
+                          "mean_visibility": float(w.visibility.mean().item())}
+    scene.close()
+
+
 def timed_spread(fn, repeats: int, warmup: int) -> dict:
     """timed(), with the fastest and the slowest of the measured calls beside the median"""
     import torch
@@ -830,7 +994,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
     ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
-                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk"),
+                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk", "nearest"),
                     default="ggx")
     ap.add_argument("--mix", choices=("even", "skewed", "one"), default="even", help="route: the rays' split over 3 bins and the misses")
     ap.add_argument("--state", choices=("camera", "secondary", "half", "diffuse"), default="camera",
@@ -838,6 +1002,9 @@ def main() -> None:
                          "skin-bounce: or a diffuse ray's hit at depth 1")
     ap.add_argument("--lights", type=int, default=2, help="the light loops: spherical lights, 1..8")
     ap.add_argument("--hit-spp-n", type=int, default=1, help="sss-hits: the light loop at the hits draws hit_spp_n^2 samples a light")
+    ap.add_argument("--tracer", choices=("synthetic", "nearest"), default="synthetic",
+                    help="shadow-walk: the hits prepared outside the events, or traced by rls_nearest_walk_hits inside them")
+    ap.add_argument("--level", type=int, default=6, help="nearest: the icosphere's subdivisions (6: 81 920 triangles)")
     args = ap.parse_args()
     if args.repeats < 3:
         ap.error("--repeats must be at least 3")
@@ -859,7 +1026,8 @@ def main() -> None:
         rec["closure"] = args.closure
         {"disney": bench_disney, "sss": bench_sss, "sss-walk": bench_sss_walk, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
          "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce,
-         "shadow-fold": bench_shadow_fold, "shadow-walk": bench_shadow_walk, "route": bench_route}.get(
+         "shadow-fold": bench_shadow_fold, "route": bench_route, "nearest": bench_nearest,
+         "shadow-walk": bench_shadow_walk_nearest if args.tracer == "nearest" else bench_shadow_walk}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
         print(json.dumps(rec), flush=True)
