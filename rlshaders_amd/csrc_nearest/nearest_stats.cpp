@@ -1,12 +1,12 @@
-// nearest_stats.cpp -- the nodes and triangles a ray visits, counted on the CPU by the traversal source the kernel compiles
+// nearest_stats.cpp -- the nodes and triangles a ray visits and the most stack entries it holds, counted on the CPU by the traversal source the kernel compiles
 // (rls_nearest_device.hpp through NearestStats) over the tree the library builds (rls_nearest_bvh.hpp).  A stand-alone host
 // program, no HIP (rlshaders_amd/build.py, build_nearest_stats; -ffp-contract=off): rlshaders_amd.nearest.host_stats writes its
 // input and reads its output; tools/trace_bench.py --closure nearest runs it on a sample of the rays it times.
 //
 // usage: nearest_stats <file> [--per-ray]
 // file: int64 nv, nt, leaf_size, rays; float V[nv * 3]; uint32 T[nt * 3]; per ray 8 words: o.xyz, d.xyz, maxdist (float), skip
-// (uint32).  Prints one JSON line: rays, hits, nodes and triangles visited in all, the tree's nodes and depth; with --per-ray
-// also "per_ray": [[hit, prim, nodes, triangles], ...].
+// (uint32).  Prints one JSON line: rays, hits, nodes and triangles visited in all, max_stack (the most stack entries any ray
+// held), the tree's nodes and depth; with --per-ray also "per_ray": [[hit, prim, nodes, triangles, max_stack], ...].
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -52,9 +52,13 @@ int main(int argc, char **argv)
         const bool hit = best.prim != kNearestNoPrim;
         hits += hit;
         all.nodes += st.nodes; all.tris += st.tris;
-        if (per_ray) printf("%s[%d, %u, %lld, %lld]", k ? ", " : "", hit ? 1 : 0, hit ? best.prim : 0u, (long long)st.nodes, (long long)st.tris);
+        nearest_count_push(all, st.max_stack);
+        if (per_ray)
+            printf("%s[%d, %u, %lld, %lld, %d]", k ? ", " : "", hit ? 1 : 0, hit ? best.prim : 0u, (long long)st.nodes, (long long)st.tris,
+                   st.max_stack);
     }
     if (per_ray) printf("], ");
-    printf("\"hits\": %lld, \"nodes\": %lld, \"triangles\": %lld}\n", (long long)hits, (long long)all.nodes, (long long)all.tris);
+    printf("\"hits\": %lld, \"nodes\": %lld, \"triangles\": %lld, \"max_stack\": %d}\n", (long long)hits, (long long)all.nodes,
+           (long long)all.tris, all.max_stack);
     return 0;
 }

@@ -2,7 +2,8 @@
 // triangle test, the traversal and a hit's frame, each written once as host + device functions, and (under hipcc) the kernel
 // around them.  tests/native/nearest_host_check.cpp compiles the same functions for the CPU and holds the traversal to a brute
 // force over the statement, bit for bit; nearest_stats.cpp beside this file counts the nodes and triangles a ray visits through
-// NearestStats (rlshaders_amd.nearest.host_stats; tools/trace_bench.py --closure nearest and tests/test_gpu_nearest_edges.py use it).
+// NearestStats, and the most stack entries it holds (rlshaders_amd.nearest.host_stats; tools/trace_bench.py --closure nearest,
+// tests/test_gpu_nearest_edges.py and tests/test_nearest_deep.py use it).
 //
 // float32 throughout, every operation by itself (-ffp-contract=off), / and sqrt correctly rounded; min and max are compares
 // written out, so a NaN never replaces the other operand.
@@ -32,12 +33,14 @@ struct NearestBest {
     uint32_t prim;                                // kNearestNoPrim: no candidate yet
     uint32_t slot;                                // the winner's triangle record
 };
-struct NearestStats { int64_t nodes = 0, tris = 0; };
+struct NearestStats { int64_t nodes = 0, tris = 0; int max_stack = 0; };   // max_stack: the most entries the ray held at once
 struct NearestNoStats {};
 RLS_NEAREST_HD void nearest_count_node(NearestStats &s) { s.nodes++; }
 RLS_NEAREST_HD void nearest_count_tri(NearestStats &s) { s.tris++; }
+RLS_NEAREST_HD void nearest_count_push(NearestStats &s, int held) { if (held > s.max_stack) s.max_stack = held; }
 RLS_NEAREST_HD void nearest_count_node(NearestNoStats &) {}
 RLS_NEAREST_HD void nearest_count_tri(NearestNoStats &) {}
+RLS_NEAREST_HD void nearest_count_push(NearestNoStats &, int) {}
 
 RLS_NEAREST_HD bool nearest_sign(float f)
 {
@@ -169,7 +172,10 @@ RLS_NEAREST_HD NearestBest nearest_traverse(const NearestNode *nodes, int64_t no
                 const uint32_t axis = n.meta >> kNearestAxisShift;
                 const float da = axis == 0 ? r.d[0] : axis == 1 ? r.d[1] : r.d[2];
                 const uint32_t near = nearest_sign(da) ? 1u : 0u;      // the left child holds the smaller centroids
-                if (sp < kNearestStack) stack(sp++) = n.first + (1u - near);
+                if (sp < kNearestStack) {
+                    stack(sp++) = n.first + (1u - near);
+                    nearest_count_push(stats, sp);
+                }
                 node = n.first + near;
                 continue;
             }

@@ -326,11 +326,11 @@ class tracer:
 
 
 def host_stats(vertices, triangles, origin, dir, maxdist=None, skip=None, leaf_size: int = 0, per_ray: bool = False) -> dict:
-    """The nodes and triangles the traversal visits for the given rays, counted on the CPU by the kernel's own traversal source
+    """The nodes and triangles the traversal visits for the given rays and the most stack entries a ray holds, counted on the CPU by the kernel's own traversal source
     over the library's own tree (csrc_nearest/nearest_stats.cpp, a stand-alone host program; no device).  vertices [nv, 3],
     triangles [nt, 3], origin / dir float32 [3, M] (numpy), maxdist [M] or None (+inf), skip [M] triangle ids or None.
-    -> {"rays", "hits", "nodes", "triangles" (totals), "tree_nodes", "depth"} and, with per_ray, "per_ray": a row
-    [hit, prim, nodes, triangles] per ray."""
+    -> {"rays", "hits", "nodes", "triangles" (totals), "max_stack" (the largest of the rays'; at most depth - 1), "tree_nodes",
+    "depth"} and, with per_ray, "per_ray": a row [hit, prim, nodes, triangles, max_stack] per ray."""
     import json
     import subprocess
     import tempfile

@@ -11,8 +11,19 @@
 //                                         triangles, for every leaf_size: random rays, rays at vertices and edges, axis-parallel
 //                                         rays with signed zeros, origins on box planes, NaN / inf components, hostile reaches,
 //                                         skipped triangles
-// Prints "ok ..." lines and exits 0, or the first differences and exits 1.  tests/test_nearest_bvh.py and
-// tests/test_nearest_host_traversal.py drive it, the latter once more under -fsanitize=address,undefined.
+//   nearest_host_check file <mesh.bin> <rays.bin> <out.bin> [leaf]
+//                                         the brute force over a mesh and a ray stream that tests/nearest_host_check_util.py
+//                                         wrote (a reference that scales to 2^22 triangles), on min(hardware threads, 16)
+//                                         threads.  mesh.bin: int64 nv, nt; float V[nv * 3]; uint32 T[nt * 3].  rays.bin: int64
+//                                         rays; 8 words a ray: o.xyz, d.xyz, maxdist (float), skip (uint32).  out.bin, a ray:
+//                                         the brute force's prim (0xFFFFFFFF: none), t (float).  With leaf the tree is built,
+//                                         its invariants are checked (exit 1 where one fails) and the traversal runs too: out.bin
+//                                         then holds 7 words a ray, the two above and the traversal's prim, t, nodes, triangles,
+//                                         max_stack (the most stack entries held).  Prints one line: the tree's depth and nodes,
+//                                         the hits and how many rays differ; the caller compares the words.
+// Prints "ok ..." lines and exits 0, or the first differences and exits 1.  tests/test_nearest_bvh.py,
+// tests/test_nearest_host_traversal.py and tests/test_nearest_deep.py drive it, the latter two once more under
+// -fsanitize=address,undefined.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -121,10 +132,8 @@ Mesh soup(int nt, uint64_t seed)
 int fails = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { if (fails++ < 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
 
-void check_tree(const Mesh &m, int leaf, const char *what)
+void check_built(const Mesh &m, const NearestBvh &b, int leaf, const char *what)
 {
-    NearestBvh b;
-    nearest_build(m.V.data(), m.T.data(), m.nt(), leaf, b);
     const int64_t nt = m.nt();
     CHECK(b.depth <= nearest_depth_bound(nt, leaf), "%s leaf %d: depth %d > bound %d", what, leaf, b.depth, nearest_depth_bound(nt, leaf));
     CHECK(b.depth - 1 <= kNearestStack, "%s: depth %d past the stack", what, b.depth);
@@ -171,6 +180,15 @@ void check_tree(const Mesh &m, int leaf, const char *what)
     for (int64_t i = 0; i < nt; i++) CHECK(seen[(size_t)i] == 1, "%s leaf %d: triangle %lld in %d leaves", what, leaf, (long long)i, seen[(size_t)i]);
     for (size_t i = 0; i < b.nodes.size(); i++) CHECK(reached[i] == 1, "%s: node %zu reached %d times", what, i, reached[i]);
     CHECK(deepest == b.depth, "%s: depth %d reported, %d found", what, b.depth, deepest);
+}
+
+void check_tree(const Mesh &m, int leaf, const char *what)
+{
+    NearestBvh b;
+    const int64_t nt = m.nt();
+    nearest_build(m.V.data(), m.T.data(), nt, leaf, b);
+    check_built(m, b, leaf, what);
+    if (nt == 0) return;
     // the same inputs give the same tree
     NearestBvh again;
     nearest_build(m.V.data(), m.T.data(), nt, leaf, again);
@@ -194,7 +212,8 @@ int run_bvh()
         for (size_t i = 0; i < same.T.size(); i++) same.T[i] = (uint32_t)i;
         check_tree(same, leaf, "coincident");
     }
-    // the depth bound at the limit's end of the range, without building: 2^22 triangles at leaf 1 need 23 levels, 22 entries
+    // the depth bound at the limit's end of the range (such a tree is built by the file mode, tests/test_nearest_deep.py): 2^22
+    // triangles at leaf 1 need 23 levels, 22 entries
     CHECK(nearest_depth_bound((int64_t)1 << 22, 1) - 1 <= kNearestStack, "the triangle limit does not fit the stack");
     if (fails) return 1;
     printf("ok bvh\n");
@@ -299,6 +318,12 @@ Ray make_ray(const Mesh &m, uint64_t k, uint64_t seed)
     return q;
 }
 
+unsigned pool_size(unsigned cap)
+{
+    const unsigned threads = std::thread::hardware_concurrency();
+    return threads < 1 ? 1 : threads > cap ? cap : threads;
+}
+
 struct Tally { int64_t rays = 0, hits = 0, nodes = 0, tris = 0, bad = 0; };
 
 void run_range(const Mesh &m, const NearestBvh &b, uint64_t seed, uint64_t begin, uint64_t end, Tally *out)
@@ -326,8 +351,7 @@ int run_traverse(int64_t total)
     struct Case { const char *name; Mesh m; double share; } cases[3] = {
         { "icosphere", icosphere(2), 0.6 }, { "quad grid", quad_grid(33), 0.1 }, { "soup", soup(1025, 1032), 0.3 } };
     const int leaves[4] = { 1, 2, 4, 8 };
-    unsigned threads = std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : threads > 8 ? 8 : threads;
+    const unsigned threads = pool_size(8);
     int64_t bad = 0, done = 0;
     for (int ci = 0; ci < 3; ci++) {
         const Case &c = cases[ci];
@@ -362,12 +386,97 @@ int run_traverse(int64_t total)
     return bad ? 1 : 0;
 }
 
+// ---- a mesh and a ray stream from files ------------------------------------------------------------------------------------------
+template <class T>
+bool read_all(FILE *f, std::vector<T> &v) { return v.empty() || fread(v.data(), sizeof(T), v.size(), f) == v.size(); }
+
+constexpr int kBruteWords = 2, kFileWords = 7;
+
+void file_range(const Mesh &m, const NearestBvh *b, const uint32_t *rays, uint32_t *out, int words, int64_t begin, int64_t end,
+                Tally *tally)
+{
+    Tally t;
+    for (int64_t k = begin; k < end; k++) {
+        Ray q;
+        memcpy(&q, rays + 8 * k, sizeof q);
+        uint32_t *w = out + (size_t)words * (size_t)k;
+        const Result want = brute(m, q.o, q.d, q.m, q.skip);
+        w[0] = want.prim;
+        memcpy(&w[1], &want.t, 4);
+        t.rays++; t.hits += want.prim != 0xFFFFFFFFu;
+        if (!b) continue;
+        const NearestRay r = nearest_ray(q.o, q.d, q.m, q.skip);
+        uint32_t stack[kNearestStack];
+        NearestStats st;
+        const NearestBest got = nearest_traverse(b->nodes.data(), (int64_t)b->nodes.size(), b->tris.data(), r,
+                                                 [&](int i) -> uint32_t & { return stack[i]; }, st);
+        w[2] = got.prim;
+        memcpy(&w[3], &got.t, 4);
+        w[4] = (uint32_t)st.nodes; w[5] = (uint32_t)st.tris; w[6] = (uint32_t)st.max_stack;
+        t.nodes += st.nodes; t.tris += st.tris;
+        t.bad += !(got.prim == want.prim && (want.prim == 0xFFFFFFFFu || !memcmp(&got.t, &want.t, 4)));
+    }
+    *tally = t;
+}
+
+int run_file(const char *mesh_path, const char *rays_path, const char *out_path, int leaf)
+{
+    static_assert(sizeof(Ray) == 32, "a ray record is 8 words");
+    Mesh m;
+    std::vector<uint32_t> rays;
+    int64_t head[2] = { 0, 0 }, count = 0;
+    FILE *f = fopen(mesh_path, "rb");
+    bool ok = f && fread(head, sizeof(int64_t), 2, f) == 2 && head[0] >= 0 && head[1] >= 0 && head[1] <= ((int64_t)1 << 22) &&
+              head[0] <= 3 * head[1] + 3;
+    if (ok) {
+        m.V.resize(3 * (size_t)head[0]); m.T.resize(3 * (size_t)head[1]);
+        ok = read_all(f, m.V) && read_all(f, m.T);
+        for (uint32_t i : m.T) ok = ok && (int64_t)i < head[0];
+    }
+    if (f) fclose(f);
+    if (!ok) { fprintf(stderr, "nearest_host_check: %s is missing, short or malformed\n", mesh_path); return 2; }
+    f = fopen(rays_path, "rb");
+    ok = f && fread(&count, sizeof(int64_t), 1, f) == 1 && count >= 0 && count <= ((int64_t)1 << 24);
+    if (ok) {
+        rays.resize(8 * (size_t)count);
+        ok = read_all(f, rays);
+    }
+    if (f) fclose(f);
+    if (!ok) { fprintf(stderr, "nearest_host_check: %s is missing, short or malformed\n", rays_path); return 2; }
+    if (leaf < 0 || leaf > 8) { fprintf(stderr, "nearest_host_check: leaf 1 .. 8\n"); return 2; }
+    NearestBvh b;
+    if (leaf) {
+        nearest_build(m.V.data(), m.T.data(), m.nt(), leaf, b);
+        check_built(m, b, leaf, "file");
+    }
+    const int words = leaf ? kFileWords : kBruteWords;
+    std::vector<uint32_t> out((size_t)words * (size_t)count);
+    const unsigned threads = pool_size(16);
+    std::vector<Tally> t(threads);
+    std::vector<std::thread> pool;
+    for (unsigned w = 0; w < threads; w++)
+        pool.emplace_back(file_range, std::cref(m), leaf ? &b : nullptr, rays.data(), out.data(), words, count * w / threads,
+                          count * (w + 1) / threads, &t[w]);
+    for (auto &th : pool) th.join();
+    Tally sum;
+    for (const Tally &x : t) { sum.rays += x.rays; sum.hits += x.hits; sum.nodes += x.nodes; sum.tris += x.tris; sum.bad += x.bad; }
+    f = fopen(out_path, "wb");
+    ok = f && (out.empty() || fwrite(out.data(), 4, out.size(), f) == out.size());
+    if (f) ok = fclose(f) == 0 && ok;
+    if (!ok) { fprintf(stderr, "nearest_host_check: cannot write %s\n", out_path); return 2; }
+    if (fails) return 1;
+    printf("ok file: nt %lld leaf %d depth %d nodes %lld rays %lld hits %lld differ %lld\n", (long long)m.nt(), leaf, b.depth,
+           (long long)b.nodes.size(), (long long)sum.rays, (long long)sum.hits, (long long)sum.bad);
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
     if (argc >= 2 && !strcmp(argv[1], "bvh")) return run_bvh();
     if (argc >= 2 && !strcmp(argv[1], "traverse")) return run_traverse(argc >= 3 ? atoll(argv[2]) : 1000000);
-    fprintf(stderr, "usage: nearest_host_check bvh | traverse [rays]\n");
+    if (argc >= 5 && !strcmp(argv[1], "file")) return run_file(argv[2], argv[3], argv[4], argc >= 6 ? atoi(argv[5]) : 0);
+    fprintf(stderr, "usage: nearest_host_check bvh | traverse [rays] | file <mesh.bin> <rays.bin> <out.bin> [leaf]\n");
     return 2;
 }

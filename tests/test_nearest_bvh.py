@@ -1,8 +1,9 @@
 """CPU: the tree of librls_nearest.so (rlshaders_amd/csrc_nearest/rls_nearest_bvh.hpp) built by the stand-alone host program
 tests/native/nearest_host_check.cpp -- no HIP, no library: for leaf_size 1, 2, 4, 8 and nt = 0, 1, 2, 3, 1025, the icosphere, the
 quad grid and 64 coincident triangles, every triangle is in exactly one leaf, every node's box contains its children's and its
-triangles', the depth is within ceil(log2(nt / leaf)) + 1, a second build gives the same bytes; and the header compiles without
-HIP, which the program's build shows."""
+triangles', the depth is within ceil(log2(nt / leaf)) + 1, a second build gives the same bytes; the header compiles without
+HIP, which the program's build shows; and the triangle limit fits the stack as arithmetic over the header's constants (a tree of
+that size, and the deep trees that fill the stack, are built by test_nearest_deep.py)."""
 import math
 import re
 

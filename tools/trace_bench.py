@@ -830,7 +830,7 @@ def bench_nearest(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
         st = nearest.host_stats(V, tri, o_[:, pick].cpu().numpy(), d_[:, pick].cpu().numpy(),
                                 skip=None if skip_ is None else skip_[pick].cpu().numpy().view(np.uint32), leaf_size=scene.leaf_size)
         out.update({"sample_rays": st["rays"], "sample_hits": st["hits"], "nodes_per_ray": round(st["nodes"] / st["rays"], 1),
-                    "triangles_per_ray": round(st["triangles"] / st["rays"], 1)})
+                    "triangles_per_ray": round(st["triangles"] / st["rays"], 1), "max_stack": st["max_stack"]})
         return out
 
     scene.hits(rays, found=found)
