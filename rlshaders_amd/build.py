@@ -323,7 +323,7 @@ def build_shadow_walk_example(verbose: bool = False, name: str = "example_shadow
 NEAREST_CSRC = PKG / "csrc_nearest"
 NEAREST_SOURCES = ["nearest.hip"]
 NEAREST_LIB = LIBDIR / "librls_nearest.so"
-NEAREST_HEADERS = [NEAREST_CSRC / "rls_nearest_device.hpp", NEAREST_CSRC / "rls_nearest_bvh.hpp",
+NEAREST_HEADERS = [NEAREST_CSRC / "rls_nearest_device.hpp", NEAREST_CSRC / "rls_nearest_bvh.hpp", NEAREST_CSRC / "rls_nearest_scene.hpp",
                    PKG.parent / "include" / "rlshaders_amd_nearest.h", PKG.parent / "include" / "rlshaders_amd_walk.h",
                    PKG.parent / "include" / "rlshaders_amd_trace.h"]
 
@@ -389,6 +389,65 @@ def build_nearest_stats(verbose: bool = False) -> Path:
         p = subprocess.run(cmd, capture_output=True, text=True)
         if p.returncode != 0:
             raise RuntimeError(f"nearest_stats failed to build:\n{p.stdout}\n{p.stderr}")
+    return out
+
+
+# ---- moving meshes (include/rlshaders_amd_nearest_refit.h): a sixth companion, librls_nearest_refit.so -- csrc_nearest/refit.hip,
+# one mode-free unit with RLS_FAST=0, the same flags, a fixed -cuid -- linked against librlshaders_amd.so alone, found by
+# $ORIGIN.  It reads a scene of librls_nearest.so through the private header csrc_nearest/rls_nearest_scene.hpp and calls
+# nothing of that library.
+NEAREST_REFIT_SOURCES = ["refit.hip"]
+NEAREST_REFIT_LIB = LIBDIR / "librls_nearest_refit.so"
+NEAREST_REFIT_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", PKG.parent / "include" / "rlshaders_amd_nearest_refit.h"]
+
+
+def build_nearest_refit_library(force: bool = False, verbose: bool = False) -> Path:
+    """Compile csrc_nearest/refit.hip for gfx950 and link librls_nearest_refit.so against the product library.  Returns its path."""
+    hipcc = _hipcc()
+    main = build_library(verbose=verbose)
+    objdir = OBJDIR / "nearest_refit"
+    objdir.mkdir(parents=True, exist_ok=True)
+
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
+
+    objs, built = [], False
+    for name in NEAREST_REFIT_SOURCES:
+        src = NEAREST_CSRC / name
+        obj = objdir / (src.stem + ".o")
+        objs.append(obj)
+        if force or _stale(obj, [src, *HEADERS, *NEAREST_HEADERS, *NEAREST_REFIT_HEADERS, Path(__file__)]):
+            run([hipcc, *HIPCC_FLAGS, f"-cuid=rls_nearest_refit.{src.stem}", "-DRLS_FAST=0", "-c", str(src), "-o", str(obj)])
+            built = True
+    if force or built or _stale(NEAREST_REFIT_LIB, [*objs, main]):
+        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(NEAREST_REFIT_LIB), *map(str, objs),
+             f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"])
+    return NEAREST_REFIT_LIB
+
+
+def build_nearest_refit_example(verbose: bool = False, name: str = "example_nearest_refit") -> Path:
+    """host/example_nearest_refit.cpp against the product, the trace library, both walks, the nearest-hit library and its
+    refit (a sphere squashed and moved over three frames, walked on the refit scene and on a fresh one)."""
+    OBJDIR.mkdir(exist_ok=True)
+    trace, walk, shadow = build_trace_library(verbose=verbose), build_walk_library(verbose=verbose), build_shadow_walk_library(verbose=verbose)
+    near, lib = build_nearest_library(verbose=verbose), build_nearest_refit_library(verbose=verbose)
+    host = PKG / "host"
+    src, out = host / f"{name}.cpp", OBJDIR / name
+    if _stale(out, [src, host / "rls_nearest_refit.hpp", host / "rls_nearest.hpp", host / "rls_shadow_walk.hpp", host / "rls_walk.hpp",
+                    host / "rls_trace.hpp", lib, near, trace, walk, shadow, LIB, *HEADERS, *TRACE_HEADERS, *WALK_HEADERS,
+                    *SHADOW_WALK_HEADERS, *NEAREST_HEADERS, *NEAREST_REFIT_HEADERS]):
+        cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{host}", str(src), "-o", str(out),
+               f"-L{LIBDIR}", "-lrls_nearest_refit", "-lrls_nearest", "-lrls_shadow_walk", "-lrls_walk", "-lrls_trace", "-lrlshaders_amd",
+               f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
     return out
 
 

@@ -25,15 +25,7 @@ static_assert(RLS_NEAREST_STACK == 24, "the header's stack size is the kernel's"
 
 static_assert(kNearestStack == RLS_NEAREST_STACK, "the header's stack size is the kernel's");
 
-struct rls_nearest_scene {
-    int device;
-    void *blob;                   // the one device allocation
-    const NearestNode *nodes;
-    const NearestTri *tris;
-    const uint32_t *index, *surface;
-    const float *normals;
-    rls_nearest_scene_info info;
-};
+#include "rls_nearest_scene.hpp"                    // struct rls_nearest_scene: the layout the refit library shares
 
 namespace {
 
@@ -119,7 +111,9 @@ rls_status rls_nearest_scene_create(rls_context *ctx, const rls_nearest_mesh *me
         rlsh::set_error("%s: the tree is deeper than its bound", __func__);
         return RLS_ERR_UNSUPPORTED;
     }
+    sc->layout = kNearestSceneLayout;
     sc->device = ctx->device;
+    sc->o_nodes = o_nodes; sc->o_tris = o_tris; sc->o_index = o_index; sc->o_surface = o_surface; sc->o_normals = o_normals;
     sc->info.nv = nv; sc->info.nt = nt; sc->info.nodes = (int64_t)bvh.nodes.size();
     sc->info.leaf_size = leaf; sc->info.depth = bvh.depth; sc->info.device_bytes = bytes;
     if (bytes) {

@@ -1,0 +1,204 @@
+"""helpers of the refit library's tests (test_nearest_refit_*.py, test_gpu_nearest_refit*.py): what
+include/rlshaders_amd_nearest_refit.h declares and librls_nearest_refit.so exports, valid arguments over dummy memory for the
+refusal table, the build and the pair files of tests/native/nearest_refit_host_check.cpp, the moved meshes, and the numpy
+bottom-up union a read tree is held to.  pytest does not collect this module."""
+import ctypes as C
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import nearest_util as U
+from nearest_util import F
+from trace_abi_util import ROOT, Dummies, code_text, dynamic_symbols
+
+HEADER = ROOT / "include" / "rlshaders_amd_nearest_refit.h"
+SCENE_HEADER = ROOT / "rlshaders_amd" / "csrc_nearest" / "rls_nearest_scene.hpp"
+SOURCE = ROOT / "tests" / "native" / "nearest_refit_host_check.cpp"
+FLAGS = ["-std=c++14", "-Wall", "-Werror", "-ffp-contract=off", "-pthread"]
+COUNT_MASK = 0xFF
+
+
+@pytest.fixture(scope="module")
+def refit_lib():
+    from rlshaders_amd import build
+    return build.build_nearest_refit_library()
+
+
+# ---- the header --------------------------------------------------------------------------------------------------------------------
+def declared_symbols():
+    return sorted(set(re.findall(r"\b(rls_[a-z0-9_]+)\s*\(", code_text(HEADER))))
+
+
+def declarations():
+    """entry point -> its parameter list"""
+    return {m.group(1): m.group(2)
+            for m in re.finditer(r"rls_status\s+(rls_nearest_refit_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", code_text(HEADER), flags=re.S)}
+
+
+def exported_symbols(lib):
+    return sorted(l.split()[-1] for l in dynamic_symbols(lib).splitlines() if l.split() and l.split()[-1].startswith("rls_"))
+
+
+def structs():
+    return re.findall(r"typedef struct (\w+)\s*\{", code_text(HEADER))
+
+
+def struct_members(c_name):
+    body = re.search(r"typedef struct %s\s*\{(.*?)\}\s*%s;" % (c_name, c_name), code_text(HEADER), flags=re.S).group(1)
+    return [re.search(r"(\w+)\s*$", part.strip()).group(1) for d in body.split(";") if d.strip() for part in d.split(",")]
+
+
+def scene_layout_tag():
+    """kNearestSceneLayout, from the private header"""
+    return int(re.search(r"kNearestSceneLayout\s*=\s*(0x[0-9a-fA-F]+)ull", SCENE_HEADER.read_text()).group(1), 16)
+
+
+class RefitWorld(Dummies):
+    """valid arguments of every entry point over dummy memory.  The scene is 4 KiB that start with this build's layout tag and
+    device 0 (the dummy context's); the refit is 4 KiB that start with a public info struct of 3 vertices with normals and
+    device 0 -- the two structs lead with just these members (csrc_nearest/rls_nearest_scene.hpp, refit.hip), so every check
+    is reached; a refused call reads nothing else."""
+
+    def __init__(self):
+        super().__init__()
+        from rlshaders_amd import nearest_refit
+        self.mod, self.rlib = nearest_refit, nearest_refit.load()
+        self.scene = C.create_string_buffer(4096)
+        C.c_uint64.from_buffer(self.scene, 0).value = scene_layout_tag()
+        self.refit = C.create_string_buffer(4096)
+        self.refit_info = nearest_refit.NearestRefitInfo_.from_buffer(self.refit, 0)
+        self.refit_info.nv, self.refit_info.nt, self.refit_info.has_normals = 3, 1, 1
+        self.mesh = nearest_refit.NearestRefitMesh_(3, self.p, self.p, self.p)
+        self.out = C.c_void_p()
+        self.info = nearest_refit.NearestRefitInfo_()
+        self.scenep, self.refitp = C.addressof(self.scene), C.addressof(self.refit)
+        self.meshp, self.outp, self.infop = C.byref(self.mesh), C.byref(self.out), C.byref(self.info)
+
+    def scene_device(self, device):
+        C.c_int.from_buffer(self.scene, 8).value = device
+
+    def refit_device(self, device):
+        C.c_int.from_buffer(self.refit, C.sizeof(self.mod.NearestRefitInfo_)).value = device
+
+    def create(self):
+        return self.rlib.rls_nearest_refit_create(self.ctxp, self.scenep, self.outp)
+
+    def update(self):
+        return self.rlib.rls_nearest_refit_update(self.ctxp, self.refitp, self.meshp)
+
+    def get_info(self):
+        return self.rlib.rls_nearest_refit_get_info(self.refitp, self.infop)
+
+    def read_tree(self):
+        return self.rlib.rls_nearest_refit_read_tree(self.ctxp, self.refitp, self.p, self.p, self.p)
+
+
+# ---- the host check ------------------------------------------------------------------------------------------------------------------
+def build(directory, sanitize=False):
+    exe = Path(directory) / ("nearest_refit_host_check_san" if sanitize else "nearest_refit_host_check")
+    extra = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
+    p = subprocess.run(["g++", *FLAGS, *extra, str(SOURCE), "-o", str(exe)], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout + p.stderr
+    return exe
+
+
+def write_pair(path, A, B, tri):
+    """int64 nv, nt; float32 A[nv * 3]; float32 B[nv * 3]; uint32 T[nt * 3]"""
+    A, B, tri = np.ascontiguousarray(A, "<f4"), np.ascontiguousarray(B, "<f4"), np.ascontiguousarray(tri, "<u4")
+    assert A.shape == B.shape
+    with open(path, "wb") as f:
+        f.write(np.array([A.shape[0], tri.shape[0]], "<i8").tobytes())
+        f.write(A.tobytes() + B.tobytes() + tri.tobytes())
+    return Path(path)
+
+
+PAIR_LINE = re.compile(r"ok pair: nt (\d+) leaf (\d+) depth (\d+) nodes (\d+) parked (\d+) rays (\d+) hits (\d+) differ (\d+) "
+                       r"refit ([\d.]+) nodes ([\d.]+) triangles a ray rebuilt ([\d.]+) nodes ([\d.]+) triangles a ray")
+
+
+def run_pair(exe, path, rays, leaf):
+    p = subprocess.run([str(exe), str(path), str(rays), str(leaf)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-4000:] + p.stderr[-4000:]
+    m = PAIR_LINE.fullmatch(p.stdout.strip().splitlines()[-1])
+    assert m, p.stdout
+    keys = ("nt", "leaf", "depth", "nodes", "parked", "rays", "hits", "differ")
+    out = {k: int(v) for k, v in zip(keys, m.groups())}
+    out.update(refit_nodes=float(m.group(9)), refit_tris=float(m.group(10)), rebuilt_nodes=float(m.group(11)), rebuilt_tris=float(m.group(12)))
+    return out
+
+
+# ---- moved meshes --------------------------------------------------------------------------------------------------------------------
+def jittered(mesh, seed, amount=0.15):
+    rng = np.random.default_rng(seed)
+    return (mesh.V + rng.uniform(-amount, amount, mesh.V.shape)).astype(F)
+
+
+def squashed(mesh, seed):
+    """scaled per axis, sheared and moved: every triangle moves, most rays change their hit"""
+    rng = np.random.default_rng(seed)
+    V = mesh.V.astype(np.float64) * np.array([1.3, 0.55, 0.9])
+    V[:, 0] += 0.35 * V[:, 1]
+    return (V + np.array([0.21, -0.17, 0.12]) + rng.uniform(-0.02, 0.02, V.shape)).astype(F)
+
+
+def twisted(V, radians):
+    """about y, by `radians` end to end over the mesh's height"""
+    V = np.asarray(V, np.float64)
+    y = V[:, 1]
+    a = radians * (y - y.min()) / max(float(np.ptp(y)), 1e-30)
+    c, s = np.cos(a), np.sin(a)
+    return np.stack([c * V[:, 0] + s * V[:, 2], y, -s * V[:, 0] + c * V[:, 2]], 1).astype(F)
+
+
+def moved(mesh, V):
+    return U.Mesh(V, mesh.tri, surface=mesh.surface, normals=mesh.normals)
+
+
+def without(mesh, V, gone):
+    """the mesh on V with the triangles `gone` (a bool mask) made degenerate at the origin: they never hit, ids stay"""
+    V = np.concatenate([np.asarray(V, F), np.zeros((1, 3), F)])
+    tri = mesh.tri.copy()
+    tri[gone] = V.shape[0] - 1
+    V = np.where(np.isfinite(V), V, F(0))
+    normals = None if mesh.normals is None else np.concatenate([mesh.normals, np.zeros((1, 3), F)])
+    return U.Mesh(V, tri, surface=mesh.surface, normals=normals)
+
+
+def levels_np(links):
+    """the level of every node (the root: 1) from the links; a child's index is past its parent's"""
+    level = np.zeros(links.shape[0], np.int64)
+    if links.shape[0]:
+        level[0] = 1
+    inner = np.flatnonzero((links[:, 1] & COUNT_MASK) == 0)
+    for n in inner:
+        level[links[n, 0]] = level[links[n, 0] + 1] = level[n] + 1
+    return level
+
+
+def union_np(boxes, links, prims, V, tri):
+    """the bottom-up union over a read tree: a leaf from its triangles' vertices (a triangle with a non-finite coordinate: the
+    origin), an inner node from its children, level by level -> boxes [nodes, 6]"""
+    V, tri = np.asarray(V, F), np.asarray(tri).astype(np.int64)
+    nodes = links.shape[0]
+    want = np.zeros((nodes, 6), F)
+    if nodes == 0:
+        return want
+    P = V[tri[prims.astype(np.int64)]]                               # [nt, 3, 3] in leaf order
+    P = np.where(np.isfinite(P).all(axis=(1, 2))[:, None, None], P, F(0))
+    lo, hi = P.min(axis=1), P.max(axis=1)
+    count = (links[:, 1] & COUNT_MASK).astype(np.int64)
+    leaves = np.flatnonzero(count)
+    leaves = leaves[np.argsort(links[leaves, 0], kind="stable")]
+    first = links[leaves, 0].astype(np.int64)
+    assert first[0] == 0 and np.array_equal(first[1:], (first + count[leaves])[:-1]) and first[-1] + count[leaves[-1]] == len(prims)
+    want[leaves, :3], want[leaves, 3:] = np.minimum.reduceat(lo, first), np.maximum.reduceat(hi, first)
+    level = levels_np(links)
+    assert (level > 0).all()
+    for l in range(int(level.max()), 0, -1):
+        n = np.flatnonzero((level == l) & (count == 0))
+        a, b = links[n, 0].astype(np.int64), links[n, 0].astype(np.int64) + 1
+        want[n, :3], want[n, 3:] = np.minimum(want[a, :3], want[b, :3]), np.maximum(want[a, 3:], want[b, 3:])
+    return want

@@ -74,6 +74,14 @@ each the device-to-device copy (torch copy_) that moves the verb's algorithmic t
 route: 2 B read + 4 B written per ray, + 4 B with slot; gather / scatter: 4 B of index + 8 B per word plane per element; fill:
 4 B of index + 4 B per plane per element.  Medians of at least 9 calls after at least 3 warm-up calls, device events, with the
 fastest and slowest call beside them.  --spp-n is not read.
+--closure nearest-refit: moving meshes (rlshaders_amd.nearest_refit, librls_nearest_refit.so).  "update": Refit.update on device
+vertices (the mesh twisted about y by 0.5 radians) against nearest.Scene(...) creation on the same vertices -- a host clock around
+the build, the upload and a synchronise, the median of 3 -- at the --level icosphere (6: 81 920 triangles) and at a grid of
+2 * 724^2 triangles; the update with the tree's top folded into one single-workgroup launch and with one launch per level
+(RLS_NEAREST_REFIT_FOLD=0), the two alternating twice, each the median, fastest and slowest of at least 9 calls after 3 warm-up
+calls, device events.  "queries": --closure nearest's coherent and incoherent streams of 2^log2n rays on the tree refit to the
+icosphere twisted by 0.5 and by 2 radians and on a tree rebuilt from the twisted vertices, and their ratio; same_as_refit: the two
+trees' hit and t planes are the same bytes.  --spp-n is not read.
 """
 from __future__ import annotations
 
@@ -865,6 +873,128 @@ def bench_nearest(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
     scene.close()
 
 
+def bench_nearest_refit(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """rls_nearest_refit_update against nearest.Scene(...) creation on the same vertices (a host build and an upload), at the
+    81 920-triangle icosphere and at a 2^20-triangle grid, with the single-workgroup launch of the tree's top (the default) and
+    with one launch per level (RLS_NEAREST_REFIT_FOLD=0); then --closure nearest's two streams on the refit tree and on a rebuilt
+    tree, for the icosphere twisted about y by 0.5 and by 2 radians end to end"""
+    import os
+    import time
+
+    import numpy as np
+    import torch
+    from rlshaders_amd import nearest, nearest_refit
+    nearest_refit.load()
+    repeats, warmup = max(args.repeats, 9), max(args.warmup, 3)
+    dev = ctx.torch_device
+
+    def twisted(V, radians):
+        V = np.asarray(V, np.float64)
+        a = radians * (V[:, 1] - V[:, 1].min()) / np.ptp(V[:, 1])
+        c, s = np.cos(a), np.sin(a)
+        return np.stack([c * V[:, 0] + s * V[:, 2], V[:, 1], -s * V[:, 0] + c * V[:, 2]], 1).astype(np.float32)
+
+    def grid(side):
+        g = np.linspace(-1.0, 1.0, side + 1)
+        x, y = np.meshgrid(g, g, indexing="xy")
+        V = np.stack([x, y, 0.1 * np.sin(3.0 * x) * np.cos(2.0 * y)], axis=-1).reshape(-1, 3).astype(np.float32)
+        j, i = np.divmod(np.arange(side * side, dtype=np.int64), side)
+        a = j * (side + 1) + i
+        return V, np.stack([a, a + 1, a + side + 2, a, a + side + 2, a + side + 1], axis=1).reshape(-1, 3).astype(np.uint32)
+
+    def make_refit(scene, fold):
+        old = os.environ.get("RLS_NEAREST_REFIT_FOLD")
+        os.environ["RLS_NEAREST_REFIT_FOLD"] = "1" if fold else "0"      # read when the refit is made
+        try:
+            return nearest_refit.Refit(scene)
+        finally:
+            if old is None:
+                del os.environ["RLS_NEAREST_REFIT_FOLD"]
+            else:
+                os.environ["RLS_NEAREST_REFIT_FOLD"] = old
+
+    V6, tri6, _ = icosphere(args.level)
+    Vg, trig = grid(724)                                             # 2 * 724^2 = 1 048 352 triangles
+    rec["update"] = {}
+    for name, V, tri in (("icosphere", V6, tri6), ("grid", Vg, trig)):
+        moved = twisted(V, 0.5)
+        scene = nearest.Scene(ctx, V, tri)
+        dv = torch.from_numpy(moved).to(dev)
+        out = {"triangles": scene.nt, "nodes": scene.nodes, "depth": scene.depth}
+        # the two versions alternate, twice: the spread between the passes is beside the difference
+        for fold in (True, False, True, False):
+            r = make_refit(scene, fold)
+            t = timed_spread(lambda: r.update(dv), repeats, warmup)
+            key = "update_folded" if fold else "update_per_level"
+            out.setdefault(key, []).append(t)
+            r.close()
+        # the bytes an update moves at least: a record read (prim) and written, 36 bytes of vertices, 12 of indices a triangle;
+        # a node read and its box written
+        bytes_ = scene.nt * (4 + 48 + 36 + 12) + scene.nodes * (32 + 24)
+        out["bytes"] = bytes_
+        out["update_tb_per_s"] = rate(bytes_, out["update_folded"][0]["ms"])
+        create = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            s2 = nearest.Scene(ctx, moved, tri)
+            torch.cuda.synchronize()
+            create.append((time.perf_counter() - t0) * 1e3)
+            s2.close()
+        create.sort()
+        out["create_ms"] = {"ms": round(create[1], 2), "min_ms": round(create[0], 2), "max_ms": round(create[2], 2)}
+        out["create_over_update"] = round(create[1] / out["update_folded"][0]["ms"], 1)
+        rec["update"][name] = out
+        scene.close()
+
+    # query cost: the drift of a refit tree against a rebuilt one
+    side = int(round(n ** 0.5))
+    n = side * side
+    g = torch.Generator(device=dev).manual_seed(seed)
+    u = (torch.arange(side, device=dev, dtype=torch.float32) + 0.5) / side * 1.3 - 0.65
+    d = torch.stack([u.repeat(side), u.repeat_interleave(side), torch.ones(n, device=dev)]).contiguous()
+    o = torch.tensor([0.0, 0.0, -3.0], device=dev)[:, None].expand(3, n).contiguous()
+    planes = ("P", "N", "Ns", "surface", "prim")
+    rec["queries"] = {"rays": n}
+    for radians in (0.5, 2.0):
+        moved = twisted(V6, radians)
+        kept = nearest.Scene(ctx, V6, tri6)
+        r = nearest_refit.Refit(kept)
+        r.update(torch.from_numpy(moved).to(dev))
+        rebuilt = nearest.Scene(ctx, moved, tri6)
+        out = {}
+        streams = None
+        for name, scene in (("refit", kept), ("rebuilt", rebuilt)):
+            found = nearest.Found(ctx, n, planes=planes)
+            rays = nearest.Rays(o, d)
+            scene.hits(rays, found=found)
+            if streams is None:                                      # the incoherent stream: from the hits, as --closure nearest
+                hit = found.hit.bool()
+                Pn = torch.randn(3, n, generator=g, device=dev)
+                Pn = Pn / Pn.norm(dim=0)
+                O2 = torch.where(hit[None, :], found.P, Pn).contiguous()
+                w = torch.randn(3, n, generator=g, device=dev)
+                d2 = (-(O2 / O2.norm(dim=0)) + 0.999 * w / w.norm(dim=0)).contiguous()
+                last0 = torch.where(hit, found.prim, torch.full_like(found.prim, -1)).contiguous()
+                streams = (O2, d2, last0, found.hit.clone(), found.t.clone())
+            O2, d2, last0, hit0, t0 = streams
+            same = bool(torch.equal(found.hit, hit0) and torch.equal(found.t[hit0.bool()].view(torch.int32), t0[hit0.bool()].view(torch.int32)))
+            last = last0.clone()
+            rays2, found2 = nearest.Rays(O2, d2), nearest.Found(ctx, n, planes=planes)
+
+            def incoherent():
+                last.copy_(last0)
+                scene.hits(rays2, last=last, found=found2)
+
+            out[name] = {"coherent": timed_spread(lambda: scene.hits(rays, found=found), repeats, warmup),
+                         "incoherent": timed_spread(incoherent, repeats, warmup), "hits": int(found.hit.sum(dtype=torch.int64).item()),
+                         "same_as_refit": same}
+        out["coherent_refit_over_rebuilt"] = round(out["refit"]["coherent"]["ms"] / out["rebuilt"]["coherent"]["ms"], 3)
+        out["incoherent_refit_over_rebuilt"] = round(out["refit"]["incoherent"]["ms"] / out["rebuilt"]["incoherent"]["ms"], 3)
+        rec["queries"][f"twist_{radians}"] = out
+        r.close(), kept.close(), rebuilt.close()
+
+
 def bench_shadow_walk_nearest(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
     """a whole shadow walk with its queries inside the events: n rays from the unit cube through three nested tinted icospheres
     (3 x 5 120 triangles, radii 2, 3, 4), every step = rls_nearest_walk_hits + rls_shadow_walk_step"""
@@ -994,7 +1124,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
     ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
-                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk", "nearest"),
+                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk", "nearest", "nearest-refit"),
                     default="ggx")
     ap.add_argument("--mix", choices=("even", "skewed", "one"), default="even", help="route: the rays' split over 3 bins and the misses")
     ap.add_argument("--state", choices=("camera", "secondary", "half", "diffuse"), default="camera",
@@ -1026,7 +1156,7 @@ def main() -> None:
         rec["closure"] = args.closure
         {"disney": bench_disney, "sss": bench_sss, "sss-walk": bench_sss_walk, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
          "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce,
-         "shadow-fold": bench_shadow_fold, "route": bench_route, "nearest": bench_nearest,
+         "shadow-fold": bench_shadow_fold, "route": bench_route, "nearest": bench_nearest, "nearest-refit": bench_nearest_refit,
          "shadow-walk": bench_shadow_walk_nearest if args.tracer == "nearest" else bench_shadow_walk}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
