@@ -320,6 +320,28 @@ def load() -> C.CDLL:
 _lib_path = None
 
 
+def load_companion(module: str, default: Path, env: str, prototypes: dict, build_fn: str, first=()) -> C.CDLL:
+    """Load and prototype a companion library for ``module``: the path in the environment variable ``env``, else ``default``.
+    first: the ``load`` callables of what it needs in the process before it (the product for its contexts and errors, other
+    companions for the structs it takes).  build_fn: the function of rlshaders_amd.build that makes it, for the message when
+    it is not there.  The caller keeps the result (its module's ``_lib``): its ``load()`` is on the path of every call into
+    the library, where a look at the environment costs more than the call's own checks."""
+    for load_first in first:
+        load_first()
+    path = Path(os.environ.get(env, str(default)))
+    if not path.exists():
+        raise RuntimeError(f"{module}: {path} not found. Build it with "
+                           f"`python -c 'from rlshaders_amd import build; build.{build_fn}()'` (needs hipcc).")
+    lib = C.CDLL(str(path), mode=C.RTLD_GLOBAL)
+    missing = [n for n in prototypes if not hasattr(lib, n)]
+    if missing:
+        raise RuntimeError(f"{module}: {path} lacks C-ABI symbols: {missing}")
+    for name, (restype, argtypes) in prototypes.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
 def loaded_path() -> Path:
     """the file the C ABI was loaded from (RLSHADERS_AMD_LIB or the in-tree build) -- what rlshaders_amd.codeid identifies"""
     load()

@@ -5,6 +5,9 @@ snapshot to the GPU box).  hipcc cross-compiles without a GPU present.
 Parity build flags: ``-ffp-contract=off`` and no fast-math (FMA contraction alone moves ~5 % of
 chained GGX values past 1e-5 relative).  fp32 divide / sqrt stay correctly
 rounded (hipcc default ``-fhip-fp32-correctly-rounded-divide-sqrt``).
+
+The companion libraries beside the product (``librls_*.so``) are described once each in COMPANIONS and built by one function;
+tests/test_build_commands.py holds every command line of this file to a recording.
 """
 from __future__ import annotations
 
@@ -14,9 +17,12 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
+from typing import NamedTuple
 
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
+HOST = PKG / "host"
+INCLUDE = PKG.parent / "include"
 LIBDIR = PKG / "lib"
 OBJDIR = PKG / "build"
 LIB = LIBDIR / "librlshaders_amd.so"
@@ -27,7 +33,9 @@ SOURCES = ["shade.hip", "integrate.hip", "lights.hip", "scatter.hip", "skin.hip"
            "libm_check.hip"]
 FAST_UNITS = {"ggx.hip", "disney.hip", "sss.hip", "skin.hip", "integrate.hip", "lights.hip", "scatter.hip", "shade.hip", "alternates.hip"}
 HEADERS = [CSRC / "rls_device.hpp", CSRC / "rls_libm.hpp", CSRC / "rls_libm_tables.inc", CSRC / "rls_libm_flavour_args.inc", CSRC / "rls_internal.hpp", CSRC / "rls_loops.hpp",
-           PKG.parent / "include" / "rlshaders_amd.h", PKG.parent / "include" / "rlshaders_amd_diag.h"]
+           INCLUDE / "rlshaders_amd.h", INCLUDE / "rlshaders_amd_diag.h"]
+# a unit's flavours: EXACT (carries the C ABI), FAST (kernels behind a hidden symbol)
+EXACT, FAST = ("", "RLS_FAST=0"), ("_fast", "RLS_FAST=1")
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
@@ -40,6 +48,7 @@ HIPCC_FLAGS = [
     "-fno-gpu-rdc",
     "-Wall", "-Wno-unused-function",
 ]
+HOST_CXX = ["g++", "-std=c++14", "-O2", "-Wall"]
 
 
 def _hipcc() -> str:
@@ -56,6 +65,25 @@ def _stale(target: Path, deps) -> bool:
     return any(Path(d).stat().st_mtime > t for d in deps)
 
 
+def _run(cmd, verbose: bool, what: str = "hipcc failed"):
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    if p.returncode != 0:
+        raise RuntimeError(f"{what}:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
+    return p
+
+
+def _compile_and_link(jobs, lib: Path, objs, link_deps, link_flags, force: bool, verbose: bool) -> Path:
+    """the stale objects compiled (in parallel), then the library linked if anything was, or if it is older than a dependency"""
+    if jobs:
+        with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
+            list(ex.map(lambda cmd: _run(cmd, verbose), jobs))
+    if force or jobs or _stale(lib, link_deps):
+        _run([_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(lib), *map(str, objs), *link_flags], verbose)
+    return lib
+
+
 def sources():
     return [CSRC / s for s in SOURCES if (CSRC / s).exists()]
 
@@ -70,13 +98,11 @@ def build_library(force: bool = False, verbose: bool = False, variant: str = "",
     objdir = OBJDIR if not variant else PKG / f"build_{variant}"
     lib = LIB if not variant else LIBDIR / f"librlshaders_amd_{variant}.so"
     objdir.mkdir(exist_ok=True)
-    srcs = sources()
     jobs = []
     objs = []
-    for src in srcs:
-        # every closure unit twice: EXACT (carries the C ABI) and FAST (kernels behind a hidden symbol)
-        flavours = [("", "RLS_FAST=0")] + ([("_fast", "RLS_FAST=1")] if src.name in FAST_UNITS else [])
-        for suffix, flag in flavours:
+    for src in sources():
+        # every closure unit twice
+        for suffix, flag in [EXACT] + ([FAST] if src.name in FAST_UNITS else []):
             obj = objdir / (src.stem + suffix + ".o")
             objs.append(obj)
             if force or _stale(obj, [src, *HEADERS, Path(__file__)]):
@@ -86,295 +112,152 @@ def build_library(force: bool = False, verbose: bool = False, variant: str = "",
                 # unit makes the device code a function of sources and flags alone.
                 jobs.append([hipcc, *HIPCC_FLAGS, *extra, f"-cuid=rlshaders_amd.{src.stem}{suffix}", f"-D{flag}",
                              *[f"-D{d}" for d in defines], "-c", str(src), "-o", str(obj)])
-
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
-        return p
-
-    if jobs:
-        with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
-            list(ex.map(run, jobs))
-    if force or jobs or _stale(lib, objs):
-        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(lib), *map(str, objs)])
+    _compile_and_link(jobs, lib, objs, objs, [], force, verbose)
     if not variant:
         build_rr_library(force=force, verbose=verbose)
     return lib
 
 
-# BASELINE config 2's kernel with one uniform-slope pass per workgroup (csrc_rr/ggx_rr.hip): a second companion, for the same
-# reason as the one below -- the product's device code stays the frozen one.  The product library looks for it next to itself
-# and hands it the streamed EXACT reflect+refract launches (csrc/ggx.hip, rr_wg_launcher), so build_library() builds it
-# right after the product and every caller of build_library() has it.  EXACT only (the kernel has no FAST flavour), the
-# same flags, a fixed -cuid; linked against librlshaders_amd.so (contexts, errors) and found next to it ($ORIGIN).
-RR_CSRC = PKG / "csrc_rr"
-RR_SOURCES = ["ggx_rr.hip"]
-RR_LIB = LIBDIR / "librls_ggx_rr.so"
+# ---- the companion libraries: librls_<name>.so beside the product, so that the product's device code -- frozen,
+# tests/test_profile_binding.py -- and each other's pinned surfaces stay what they are.  All are built alike: the product's
+# flags, a fixed -cuid per unit and flavour (rls_<name>.<unit>[_fast]), objects under build/<objdir>/, linked against
+# librlshaders_amd.so alone (contexts, errors, graphs) and found next to it ($ORIGIN) -- a name no build_library(variant=...)
+# output can take.  What differs is one Companion each:
+#   headers: what its units include beyond HEADERS -- an object is stale against its source, these and this file;
+#   flavours: EXACT alone (a mode-free library: IEEE arithmetic) or EXACT and FAST;
+#   after_product: build_library() is its prerequisite.  Not so for rr, which build_library() itself builds right after the
+#     product (the product looks for it next to itself, so every caller of build_library() has it): it links the product as
+#     it finds it.
+class Companion(NamedTuple):
+    name: str
+    objdir: str
+    csrc: Path
+    units: list
+    headers: list
+    flavours: tuple = (EXACT,)
+    after_product: bool = True
+
+    @property
+    def lib(self) -> Path:
+        return LIBDIR / f"librls_{self.name}.so"
+
+
+RR_CSRC, TRACE_CSRC, WALK_CSRC = PKG / "csrc_rr", PKG / "csrc_trace", PKG / "csrc_walk"
+SHADOW_WALK_CSRC, NEAREST_CSRC = PKG / "csrc_shadow_walk", PKG / "csrc_nearest"
 RR_HEADERS = [RR_CSRC / "rls_rr_device.hpp"]
+TRACE_HEADERS = [*sorted(TRACE_CSRC.glob("*.hpp")), INCLUDE / "rlshaders_amd_trace.h"]
+WALK_HEADERS = [*sorted(WALK_CSRC.glob("*.hpp")), INCLUDE / "rlshaders_amd_walk.h"]
+SHADOW_WALK_HEADERS = [*sorted(SHADOW_WALK_CSRC.glob("*.hpp")), INCLUDE / "rlshaders_amd_shadow_walk.h", INCLUDE / "rlshaders_amd_walk.h"]
+NEAREST_HEADERS = [NEAREST_CSRC / "rls_nearest_device.hpp", NEAREST_CSRC / "rls_nearest_bvh.hpp", NEAREST_CSRC / "rls_nearest_scene.hpp",
+                   INCLUDE / "rlshaders_amd_nearest.h", INCLUDE / "rlshaders_amd_walk.h", INCLUDE / "rlshaders_amd_trace.h"]
+NEAREST_REFIT_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", INCLUDE / "rlshaders_amd_nearest_refit.h"]
+
+COMPANIONS = {c.name: c for c in (
+    # BASELINE config 2's kernel with one uniform-slope pass per workgroup, handed the streamed EXACT reflect+refract launches
+    # by the product (csrc/ggx.hip, rr_wg_launcher); the kernel has no FAST flavour
+    Companion("ggx_rr", "rr", RR_CSRC, ["ggx_rr.hip"], RR_HEADERS, after_product=False),
+    # the caller-traced integrators (include/rlshaders_amd_trace.h): the two flavours of the product's closure units
+    Companion("trace", "trace", TRACE_CSRC, ["trace.hip"], TRACE_HEADERS, flavours=(EXACT, FAST)),
+    # rlSss's probe walk (include/rlshaders_amd_walk.h); it includes the trace library's scan kernels from csrc_trace/
+    Companion("walk", "walk", WALK_CSRC, ["walk.hip"], TRACE_HEADERS + WALK_HEADERS),
+    # the shadow rays' walk (include/rlshaders_amd_shadow_walk.h): the scan from csrc_trace/, the list machinery it shares
+    # with the probe walk from csrc_walk/
+    Companion("shadow_walk", "shadow_walk", SHADOW_WALK_CSRC, ["shadow_walk.hip"],
+              TRACE_HEADERS + SHADOW_WALK_HEADERS + [WALK_CSRC / "rls_walk_list.hpp"]),
+    # nearest-hit queries over a triangle mesh (include/rlshaders_amd_nearest.h): nothing of the other companions' sources; its
+    # header includes the probe walk's for the type of the walks' lists
+    Companion("nearest", "nearest", NEAREST_CSRC, ["nearest.hip"], NEAREST_HEADERS),
+    # moving meshes (include/rlshaders_amd_nearest_refit.h): it reads a scene of librls_nearest.so through the private header
+    # csrc_nearest/rls_nearest_scene.hpp and calls nothing of that library
+    Companion("nearest_refit", "nearest_refit", NEAREST_CSRC, ["refit.hip"], NEAREST_HEADERS + NEAREST_REFIT_HEADERS),
+)}
+RR_LIB, TRACE_LIB, WALK_LIB = COMPANIONS["ggx_rr"].lib, COMPANIONS["trace"].lib, COMPANIONS["walk"].lib
+SHADOW_WALK_LIB, NEAREST_LIB, NEAREST_REFIT_LIB = COMPANIONS["shadow_walk"].lib, COMPANIONS["nearest"].lib, COMPANIONS["nearest_refit"].lib
+
+
+def build_companion(name: str, force: bool = False, verbose: bool = False) -> Path:
+    """Compile a companion's units for gfx950 and link librls_<name>.so against the product library.  Returns its path."""
+    c = COMPANIONS[name]
+    hipcc = _hipcc()
+    main = build_library(verbose=verbose) if c.after_product else LIB
+    objdir = OBJDIR / c.objdir
+    objdir.mkdir(parents=True, exist_ok=True)
+    jobs, objs = [], []
+    for unit in c.units:
+        src = c.csrc / unit
+        for suffix, flag in c.flavours:
+            obj = objdir / (src.stem + suffix + ".o")
+            objs.append(obj)
+            if force or _stale(obj, [src, *HEADERS, *c.headers, Path(__file__)]):
+                jobs.append([hipcc, *HIPCC_FLAGS, f"-cuid=rls_{c.name}.{src.stem}{suffix}", f"-D{flag}", "-c", str(src), "-o", str(obj)])
+    return _compile_and_link(jobs, c.lib, objs, [*objs, main], [f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"], force, verbose)
 
 
 def build_rr_library(force: bool = False, verbose: bool = False) -> Path:
-    """Compile csrc_rr/ for gfx950 and link librls_ggx_rr.so against the product library (which must exist).  Returns its path."""
-    hipcc = _hipcc()
-    objdir = OBJDIR / "rr"
-    objdir.mkdir(parents=True, exist_ok=True)
-    objs, built = [], False
-    for name in RR_SOURCES:
-        src = RR_CSRC / name
-        obj = objdir / (src.stem + ".o")
-        objs.append(obj)
-        if force or _stale(obj, [src, *HEADERS, *RR_HEADERS, Path(__file__)]):
-            cmd = [hipcc, *HIPCC_FLAGS, f"-cuid=rls_ggx_rr.{src.stem}", "-DRLS_FAST=0", "-c", str(src), "-o", str(obj)]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            p = subprocess.run(cmd, capture_output=True, text=True)
-            if p.returncode != 0:
-                raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
-            built = True
-    if force or built or _stale(RR_LIB, [*objs, LIB]):
-        cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(RR_LIB), *map(str, objs),
-               f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
-    return RR_LIB
-
-
-# The caller-traced integrators (include/rlshaders_amd_trace.h): a companion library beside the product, so that the product's
-# device code -- frozen, tests/test_profile_binding.py -- stays what it is.  Same flags, the same two flavours per unit (EXACT
-# with the C ABI, FAST behind hidden symbols), fixed -cuid per unit; linked against librlshaders_amd.so (context, errors) and
-# found next to it ($ORIGIN).  A name no build_library(variant=...) output can take.
-TRACE_CSRC = PKG / "csrc_trace"
-TRACE_SOURCES = ["trace.hip"]
-TRACE_LIB = LIBDIR / "librls_trace.so"
-TRACE_HEADERS = [*sorted(TRACE_CSRC.glob("*.hpp")), PKG.parent / "include" / "rlshaders_amd_trace.h"]
+    return build_companion("ggx_rr", force, verbose)
 
 
 def build_trace_library(force: bool = False, verbose: bool = False) -> Path:
-    """Compile csrc_trace/ for gfx950 and link librls_trace.so against the product library.  Returns its path."""
-    hipcc = _hipcc()
-    main = build_library(verbose=verbose)
-    objdir = OBJDIR / "trace"
-    objdir.mkdir(parents=True, exist_ok=True)
-    jobs, objs = [], []
-    for name in TRACE_SOURCES:
-        src = TRACE_CSRC / name
-        for suffix, flag in (("", "RLS_FAST=0"), ("_fast", "RLS_FAST=1")):
-            obj = objdir / (src.stem + suffix + ".o")
-            objs.append(obj)
-            if force or _stale(obj, [src, *HEADERS, *TRACE_HEADERS, Path(__file__)]):
-                jobs.append([hipcc, *HIPCC_FLAGS, f"-cuid=rls_trace.{src.stem}{suffix}", f"-D{flag}", "-c", str(src),
-                             "-o", str(obj)])
-
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
-
-    if jobs:
-        with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
-            list(ex.map(run, jobs))
-    if force or jobs or _stale(TRACE_LIB, [*objs, main]):
-        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(TRACE_LIB), *map(str, objs),
-             f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"])
-    return TRACE_LIB
-
-
-def build_trace_example(verbose: bool = False, name: str = "example_trace") -> Path:
-    """host/example_trace.cpp (or ``name``: example_trace_bounce, example_trace_skin_bounce, example_trace_shadow, example_trace_path) against both libraries (emit -> a host-side \"tracer\" ->
-    resolve)."""
-    OBJDIR.mkdir(exist_ok=True)
-    lib = build_trace_library(verbose=verbose)
-    src, out = PKG / "host" / f"{name}.cpp", OBJDIR / name
-    if _stale(out, [src, PKG / "host" / "rls_trace.hpp", lib, LIB, *HEADERS, *TRACE_HEADERS]):
-        cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{PKG / 'host'}", str(src), "-o", str(out),
-               f"-L{LIBDIR}", "-lrls_trace", "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
-    return out
-
-
-# rlSss's probe walk (include/rlshaders_amd_walk.h): a third companion, so that the trace library's surface -- pinned entry point
-# by entry point, tests/test_trace_abi.py -- and the product stay what they are.  The walk is mode-free: ONE unit, compiled with
-# RLS_FAST=0 (IEEE arithmetic), the same flags, a fixed -cuid.  It includes the trace library's scan kernels from csrc_trace/, so
-# those headers are its dependencies too; linked against librlshaders_amd.so (contexts, errors, graphs), found by $ORIGIN.
-WALK_CSRC = PKG / "csrc_walk"
-WALK_SOURCES = ["walk.hip"]
-WALK_LIB = LIBDIR / "librls_walk.so"
-WALK_HEADERS = [*sorted(WALK_CSRC.glob("*.hpp")), PKG.parent / "include" / "rlshaders_amd_walk.h"]
+    return build_companion("trace", force, verbose)
 
 
 def build_walk_library(force: bool = False, verbose: bool = False) -> Path:
-    """Compile csrc_walk/ for gfx950 and link librls_walk.so against the product library.  Returns its path."""
-    hipcc = _hipcc()
-    main = build_library(verbose=verbose)
-    objdir = OBJDIR / "walk"
-    objdir.mkdir(parents=True, exist_ok=True)
-
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
-
-    objs, built = [], False
-    for name in WALK_SOURCES:
-        src = WALK_CSRC / name
-        obj = objdir / (src.stem + ".o")
-        objs.append(obj)
-        if force or _stale(obj, [src, *HEADERS, *TRACE_HEADERS, *WALK_HEADERS, Path(__file__)]):
-            run([hipcc, *HIPCC_FLAGS, f"-cuid=rls_walk.{src.stem}", "-DRLS_FAST=0", "-c", str(src), "-o", str(obj)])
-            built = True
-    if force or built or _stale(WALK_LIB, [*objs, main]):
-        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(WALK_LIB), *map(str, objs),
-             f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"])
-    return WALK_LIB
-
-
-def build_walk_example(verbose: bool = False, name: str = "example_walk") -> Path:
-    """host/example_walk.cpp against the three libraries (probe emit -> walk over a host-side closest-hit function -> resolve)."""
-    OBJDIR.mkdir(exist_ok=True)
-    trace, lib = build_trace_library(verbose=verbose), build_walk_library(verbose=verbose)
-    src, out = PKG / "host" / f"{name}.cpp", OBJDIR / name
-    if _stale(out, [src, PKG / "host" / "rls_walk.hpp", PKG / "host" / "rls_trace.hpp", lib, trace, LIB, *HEADERS, *TRACE_HEADERS,
-                    *WALK_HEADERS]):
-        cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{PKG / 'host'}", str(src), "-o", str(out),
-               f"-L{LIBDIR}", "-lrls_walk", "-lrls_trace", "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib",
-               "-Wl,-rpath,/opt/rocm/lib"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
-    return out
-
-
-# ---- the shadow rays' walk (include/rlshaders_amd_shadow_walk.h): a fourth companion, built like the probe walk's -- one
-# mode-free unit with RLS_FAST=0, the same flags, a fixed -cuid, the trace library's scan kernels included from csrc_trace/ --
-# and linked against librlshaders_amd.so alone, found by $ORIGIN.
-SHADOW_WALK_CSRC = PKG / "csrc_shadow_walk"
-SHADOW_WALK_SOURCES = ["shadow_walk.hip"]
-SHADOW_WALK_LIB = LIBDIR / "librls_shadow_walk.so"
-SHADOW_WALK_HEADERS = [*sorted(SHADOW_WALK_CSRC.glob("*.hpp")), PKG.parent / "include" / "rlshaders_amd_shadow_walk.h",
-                       PKG.parent / "include" / "rlshaders_amd_walk.h"]
+    return build_companion("walk", force, verbose)
 
 
 def build_shadow_walk_library(force: bool = False, verbose: bool = False) -> Path:
-    """Compile csrc_shadow_walk/ for gfx950 and link librls_shadow_walk.so against the product library.  Returns its path."""
-    hipcc = _hipcc()
-    main = build_library(verbose=verbose)
-    objdir = OBJDIR / "shadow_walk"
-    objdir.mkdir(parents=True, exist_ok=True)
-
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
-
-    objs, built = [], False
-    for name in SHADOW_WALK_SOURCES:
-        src = SHADOW_WALK_CSRC / name
-        obj = objdir / (src.stem + ".o")
-        objs.append(obj)
-        if force or _stale(obj, [src, *HEADERS, *TRACE_HEADERS, *SHADOW_WALK_HEADERS, Path(__file__)]):
-            run([hipcc, *HIPCC_FLAGS, f"-cuid=rls_shadow_walk.{src.stem}", "-DRLS_FAST=0", "-c", str(src), "-o", str(obj)])
-            built = True
-    if force or built or _stale(SHADOW_WALK_LIB, [*objs, main]):
-        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(SHADOW_WALK_LIB), *map(str, objs),
-             f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"])
-    return SHADOW_WALK_LIB
-
-
-def build_shadow_walk_example(verbose: bool = False, name: str = "example_shadow_walk") -> Path:
-    """host/example_shadow_walk.cpp against the product, the trace library and the shadow walk (light-loop emit -> walk over a
-    host-side closest-hit function -> resolve)."""
-    OBJDIR.mkdir(exist_ok=True)
-    trace, lib = build_trace_library(verbose=verbose), build_shadow_walk_library(verbose=verbose)
-    src, out = PKG / "host" / f"{name}.cpp", OBJDIR / name
-    if _stale(out, [src, PKG / "host" / "rls_shadow_walk.hpp", PKG / "host" / "rls_trace.hpp", lib, trace, LIB, *HEADERS,
-                    *TRACE_HEADERS, *SHADOW_WALK_HEADERS]):
-        cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{PKG / 'host'}", str(src), "-o", str(out),
-               f"-L{LIBDIR}", "-lrls_shadow_walk", "-lrls_trace", "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib",
-               "-Wl,-rpath,/opt/rocm/lib"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
-    return out
-
-
-# ---- nearest-hit queries over a triangle mesh (include/rlshaders_amd_nearest.h): a fifth companion -- one mode-free unit with
-# RLS_FAST=0, the same flags, a fixed -cuid -- linked against librlshaders_amd.so alone, found by $ORIGIN.  It includes nothing
-# of the other companions' sources; its header includes the probe walk's for the type of the walks' lists.
-NEAREST_CSRC = PKG / "csrc_nearest"
-NEAREST_SOURCES = ["nearest.hip"]
-NEAREST_LIB = LIBDIR / "librls_nearest.so"
-NEAREST_HEADERS = [NEAREST_CSRC / "rls_nearest_device.hpp", NEAREST_CSRC / "rls_nearest_bvh.hpp", NEAREST_CSRC / "rls_nearest_scene.hpp",
-                   PKG.parent / "include" / "rlshaders_amd_nearest.h", PKG.parent / "include" / "rlshaders_amd_walk.h",
-                   PKG.parent / "include" / "rlshaders_amd_trace.h"]
+    return build_companion("shadow_walk", force, verbose)
 
 
 def build_nearest_library(force: bool = False, verbose: bool = False) -> Path:
-    """Compile csrc_nearest/ for gfx950 and link librls_nearest.so against the product library.  Returns its path."""
-    hipcc = _hipcc()
-    main = build_library(verbose=verbose)
-    objdir = OBJDIR / "nearest"
-    objdir.mkdir(parents=True, exist_ok=True)
+    return build_companion("nearest", force, verbose)
 
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
 
-    objs, built = [], False
-    for name in NEAREST_SOURCES:
-        src = NEAREST_CSRC / name
-        obj = objdir / (src.stem + ".o")
-        objs.append(obj)
-        if force or _stale(obj, [src, *HEADERS, *NEAREST_HEADERS, Path(__file__)]):
-            run([hipcc, *HIPCC_FLAGS, f"-cuid=rls_nearest.{src.stem}", "-DRLS_FAST=0", "-c", str(src), "-o", str(obj)])
-            built = True
-    if force or built or _stale(NEAREST_LIB, [*objs, main]):
-        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(NEAREST_LIB), *map(str, objs),
-             f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"])
-    return NEAREST_LIB
+def build_nearest_refit_library(force: bool = False, verbose: bool = False) -> Path:
+    return build_companion("nearest_refit", force, verbose)
+
+
+def _link_flags(libs) -> list:
+    return [f"-L{LIBDIR}", *[f"-l{l}" for l in libs], "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
+
+
+def build_example(name: str, companions, verbose: bool = False) -> Path:
+    """host/<name>.cpp against the product and the companions named, in link order (a library ahead of what it uses); each is
+    built first, and the example is stale against them, their headers and their host mirrors host/rls_<companion>.hpp"""
+    deps = [LIB, *HEADERS]
+    for c in reversed(companions):
+        deps += [build_companion(c, verbose=verbose), HOST / f"rls_{c}.hpp", *COMPANIONS[c].headers]
+    src, out = HOST / f"{name}.cpp", OBJDIR / name
+    if _stale(out, [src, *deps]):
+        _run([*HOST_CXX, f"-I{INCLUDE}", f"-I{HOST}", str(src), "-o", str(out), *_link_flags(f"rls_{c}" for c in companions)], verbose,
+             f"host example {name} failed to build")
+    return out
+
+
+def build_trace_example(verbose: bool = False, name: str = "example_trace") -> Path:
+    """host/example_trace.cpp (or ``name``: example_trace_bounce, example_trace_skin_bounce, example_trace_shadow,
+    example_trace_path): emit -> a host-side "tracer" -> resolve"""
+    return build_example(name, ["trace"], verbose)
+
+
+def build_walk_example(verbose: bool = False, name: str = "example_walk") -> Path:
+    """probe emit -> walk over a host-side closest-hit function -> resolve"""
+    return build_example(name, ["walk", "trace"], verbose)
+
+
+def build_shadow_walk_example(verbose: bool = False, name: str = "example_shadow_walk") -> Path:
+    """light-loop emit -> walk over a host-side closest-hit function -> resolve"""
+    return build_example(name, ["shadow_walk", "trace"], verbose)
 
 
 def build_nearest_example(verbose: bool = False, name: str = "example_nearest") -> Path:
-    """host/example_nearest.cpp against the product, the trace library, both walks and the nearest-hit library (emit -> walk over
-    device nearest hits -> resolve: no host tracer)."""
-    OBJDIR.mkdir(exist_ok=True)
-    trace, walk, shadow = build_trace_library(verbose=verbose), build_walk_library(verbose=verbose), build_shadow_walk_library(verbose=verbose)
-    lib = build_nearest_library(verbose=verbose)
-    host = PKG / "host"
-    src, out = host / f"{name}.cpp", OBJDIR / name
-    if _stale(out, [src, host / "rls_nearest.hpp", host / "rls_shadow_walk.hpp", host / "rls_walk.hpp", host / "rls_trace.hpp", lib, trace,
-                    walk, shadow, LIB, *HEADERS, *TRACE_HEADERS, *WALK_HEADERS, *SHADOW_WALK_HEADERS, *NEAREST_HEADERS]):
-        cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{host}", str(src), "-o", str(out),
-               f"-L{LIBDIR}", "-lrls_nearest", "-lrls_shadow_walk", "-lrls_walk", "-lrls_trace", "-lrlshaders_amd",
-               f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
-    return out
+    """emit -> walk over device nearest hits -> resolve: no host tracer"""
+    return build_example(name, ["nearest", "shadow_walk", "walk", "trace"], verbose)
+
+
+def build_nearest_refit_example(verbose: bool = False, name: str = "example_nearest_refit") -> Path:
+    """a sphere squashed and moved over three frames, walked on the refit scene and on a fresh one"""
+    return build_example(name, ["nearest_refit", "nearest", "shadow_walk", "walk", "trace"], verbose)
 
 
 def build_nearest_stats(verbose: bool = False) -> Path:
@@ -383,71 +266,7 @@ def build_nearest_stats(verbose: bool = False) -> Path:
     OBJDIR.mkdir(exist_ok=True)
     src, out = NEAREST_CSRC / "nearest_stats.cpp", OBJDIR / "nearest_stats"
     if _stale(out, [src, NEAREST_CSRC / "rls_nearest_device.hpp", NEAREST_CSRC / "rls_nearest_bvh.hpp"]):
-        cmd = ["g++", "-std=c++14", "-O2", "-Wall", "-ffp-contract=off", str(src), "-o", str(out)]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"nearest_stats failed to build:\n{p.stdout}\n{p.stderr}")
-    return out
-
-
-# ---- moving meshes (include/rlshaders_amd_nearest_refit.h): a sixth companion, librls_nearest_refit.so -- csrc_nearest/refit.hip,
-# one mode-free unit with RLS_FAST=0, the same flags, a fixed -cuid -- linked against librlshaders_amd.so alone, found by
-# $ORIGIN.  It reads a scene of librls_nearest.so through the private header csrc_nearest/rls_nearest_scene.hpp and calls
-# nothing of that library.
-NEAREST_REFIT_SOURCES = ["refit.hip"]
-NEAREST_REFIT_LIB = LIBDIR / "librls_nearest_refit.so"
-NEAREST_REFIT_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", PKG.parent / "include" / "rlshaders_amd_nearest_refit.h"]
-
-
-def build_nearest_refit_library(force: bool = False, verbose: bool = False) -> Path:
-    """Compile csrc_nearest/refit.hip for gfx950 and link librls_nearest_refit.so against the product library.  Returns its path."""
-    hipcc = _hipcc()
-    main = build_library(verbose=verbose)
-    objdir = OBJDIR / "nearest_refit"
-    objdir.mkdir(parents=True, exist_ok=True)
-
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
-
-    objs, built = [], False
-    for name in NEAREST_REFIT_SOURCES:
-        src = NEAREST_CSRC / name
-        obj = objdir / (src.stem + ".o")
-        objs.append(obj)
-        if force or _stale(obj, [src, *HEADERS, *NEAREST_HEADERS, *NEAREST_REFIT_HEADERS, Path(__file__)]):
-            run([hipcc, *HIPCC_FLAGS, f"-cuid=rls_nearest_refit.{src.stem}", "-DRLS_FAST=0", "-c", str(src), "-o", str(obj)])
-            built = True
-    if force or built or _stale(NEAREST_REFIT_LIB, [*objs, main]):
-        run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(NEAREST_REFIT_LIB), *map(str, objs),
-             f"-L{LIBDIR}", "-lrlshaders_amd", "-Wl,-rpath,$ORIGIN"])
-    return NEAREST_REFIT_LIB
-
-
-def build_nearest_refit_example(verbose: bool = False, name: str = "example_nearest_refit") -> Path:
-    """host/example_nearest_refit.cpp against the product, the trace library, both walks, the nearest-hit library and its
-    refit (a sphere squashed and moved over three frames, walked on the refit scene and on a fresh one)."""
-    OBJDIR.mkdir(exist_ok=True)
-    trace, walk, shadow = build_trace_library(verbose=verbose), build_walk_library(verbose=verbose), build_shadow_walk_library(verbose=verbose)
-    near, lib = build_nearest_library(verbose=verbose), build_nearest_refit_library(verbose=verbose)
-    host = PKG / "host"
-    src, out = host / f"{name}.cpp", OBJDIR / name
-    if _stale(out, [src, host / "rls_nearest_refit.hpp", host / "rls_nearest.hpp", host / "rls_shadow_walk.hpp", host / "rls_walk.hpp",
-                    host / "rls_trace.hpp", lib, near, trace, walk, shadow, LIB, *HEADERS, *TRACE_HEADERS, *WALK_HEADERS,
-                    *SHADOW_WALK_HEADERS, *NEAREST_HEADERS, *NEAREST_REFIT_HEADERS]):
-        cmd = ["g++", "-std=c++14", "-O2", "-Wall", f"-I{PKG.parent / 'include'}", f"-I{host}", str(src), "-o", str(out),
-               f"-L{LIBDIR}", "-lrls_nearest_refit", "-lrls_nearest", "-lrls_shadow_walk", "-lrls_walk", "-lrls_trace", "-lrlshaders_amd",
-               f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
+        _run([*HOST_CXX, "-ffp-contract=off", str(src), "-o", str(out)], verbose, "nearest_stats failed to build")
     return out
 
 
@@ -466,13 +285,8 @@ def build_libm_probe(force: bool = False, verbose: bool = False, include: Path =
     out.parent.mkdir(parents=True, exist_ok=True)
     headers = HEADERS if include == CSRC else sorted(Path(include).glob("*"))
     if force or _stale(out, [PROBE_SRC, *headers, Path(__file__)]):
-        cmd = [hipcc, *HIPCC_FLAGS, "-cuid=rls_libm_probe.libm_device_probe", "-DRLS_FAST=0", f"-I{include}", "-shared",
-               str(PROBE_SRC), "-o", str(out)]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{p.stdout}\n{p.stderr}")
+        _run([hipcc, *HIPCC_FLAGS, "-cuid=rls_libm_probe.libm_device_probe", "-DRLS_FAST=0", f"-I{include}", "-shared",
+              str(PROBE_SRC), "-o", str(out)], verbose)
     return out
 
 
@@ -481,19 +295,10 @@ def build_host_examples(verbose: bool = False) -> Path:
     OBJDIR.mkdir(exist_ok=True)
     first = OBJDIR / "example_arnold_stub"
     for name in ("example_arnold_stub", "example_multi_gpu", "example_host_pipeline", "test_arnold_stub"):
-        src = PKG / "host" / f"{name}.cpp"
-        out = OBJDIR / name
-        if not src.exists():
-            continue
-        if _stale(out, [src, PKG / "host" / "rls_batch.hpp", PKG / "host" / "rl_arnold_stub.hpp", LIB, *HEADERS]):
-            cmd = ["g++", "-std=c++14", "-O2", "-Wall", "-pthread", f"-I{PKG.parent / 'include'}", f"-I{PKG / 'host'}",
-                   str(src), "-o", str(out), f"-L{LIBDIR}", "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}",
-                   "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            p = subprocess.run(cmd, capture_output=True, text=True)
-            if p.returncode != 0:
-                raise RuntimeError(f"host example {name} failed to build:\n{p.stdout}\n{p.stderr}")
+        src, out = HOST / f"{name}.cpp", OBJDIR / name
+        if src.exists() and _stale(out, [src, HOST / "rls_batch.hpp", HOST / "rl_arnold_stub.hpp", LIB, *HEADERS]):
+            _run([*HOST_CXX, "-pthread", f"-I{INCLUDE}", f"-I{HOST}", str(src), "-o", str(out), *_link_flags([])], verbose,
+                 f"host example {name} failed to build")
     return first
 
 

@@ -6,7 +6,7 @@
 // A step on the context's stream:
 //   1. shadow_step_kernel: per entry of the input list the decision, T updated in the caller's visibility planes, and for the
 //      entry its state (survives | steps left << 1, 16 bits: a budget of 255 does not fit the probe walk's flag byte) and the new
-//      maxdist; per tile of kShadowWalkTile entries the survivors counted from wavefront ballots.
+//      maxdist; per tile of kWalkTile entries the survivors counted from wavefront ballots.
 //   2. the trace library's scan (trace_scan_{block,totals,add}_kernel, csrc_trace/rls_trace_queue.hpp) over the tile counts:
 //      every tile's first position in the output list; the grand total is the output list's count, written where it lives.
 //   3. shadow_place_kernel: the stable compaction of the probe walk's walk_place_kernel (csrc_walk/rls_walk_device.hpp) -- a
@@ -15,11 +15,11 @@
 // rls_shadow_walk_begin is steps 2 and 3 behind shadow_begin_kernel, which writes T = base or 1 and flags the rays with
 // maxdist > 0.  No atomic, no workgroup waits on another; every position is a function of the inputs alone.
 //
-// A tile is kBlock entries, one per lane.  The counts live on the device: every kernel is launched over the caller's bound and
+// A tile is kBlock entries, one per lane: kWalkTile, kWalkWaves and the tile's survivor count, tile_count, are the probe walk's
+// (csrc_walk/rls_walk_list.hpp, included ahead of this file and compiled into this code object: a header both units include
+// changes neither library's machine code).  The counts live on the device: every kernel is launched over the caller's bound and
 // reads the count itself, lanes past it idle, tiles past it count 0 survivors.
 
-constexpr int kShadowWalkTile = rlsh::kBlock;
-constexpr int kShadowWalkWaves = rlsh::kBlock / 64;
 constexpr int kShadowSurvives = 1;           // bit 0 of an entry's state; the steps left above it
 
 struct ShadowVerdict { bool survives; float T[3], left; int steps; };
@@ -59,32 +59,12 @@ __device__ __forceinline__ int64_t shadow_entries(const int64_t *count, int64_t 
     return m < 0 ? 0 : m < bound ? m : bound;
 }
 
-// the survivors of this workgroup's tile, from one ballot a wavefront; whole workgroup.  below: those on the lanes and
-// wavefronts before this lane.  (walk_tile_count of csrc_walk/rls_walk_device.hpp, restated: that file belongs to another
-// library's pinned code object.)
-__device__ __forceinline__ int shadow_tile_count(int (&wtot)[kShadowWalkWaves], bool survives, int &below)
-{
-    const int wave = (int)(threadIdx.x >> 6);
-    const uint64_t m = __builtin_amdgcn_ballot_w64(survives);
-    below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    __syncthreads();                                             // the previous tile's sums are read
-    if ((threadIdx.x & 63u) == 0) wtot[wave] = __builtin_popcountll(m);
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for (int w = 0; w < kShadowWalkWaves; w++) {
-        if (w < wave) below += wtot[w];
-        total += wtot[w];
-    }
-    return total;
-}
-
 __global__ __launch_bounds__(rlsh::kBlock) void shadow_begin_kernel(ShadowWalkIO a)
 {
-    __shared__ int wtot[kShadowWalkWaves];
+    __shared__ int wtot[kWalkWaves];
     const int64_t m = shadow_entries(a.w.count, a.bound);
     for (int64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-        const int64_t j = tile * kShadowWalkTile + threadIdx.x;
+        const int64_t j = tile * kWalkTile + threadIdx.x;
         bool active = false;
         if (j < m) {
             active = a.q.maxdist[j] > 0.0f;                      // (a NaN is not active)
@@ -94,18 +74,18 @@ __global__ __launch_bounds__(rlsh::kBlock) void shadow_begin_kernel(ShadowWalkIO
             a.state[j] = (uint16_t)(active ? kShadowSurvives | a.w.max_steps << 1 : 0);
         }
         int below;
-        const int total = shadow_tile_count(wtot, active, below);
+        const int total = tile_count(wtot, active, below);
         if (threadIdx.x == 0) a.counts[tile] = total;
     }
 }
 
 __global__ __launch_bounds__(rlsh::kBlock) void shadow_step_kernel(ShadowWalkIO a)
 {
-    __shared__ int wtot[kShadowWalkWaves];
+    __shared__ int wtot[kWalkWaves];
     const int64_t m = shadow_entries(a.in.count, a.bound);
     const rls_rgb &vis = a.w.visibility;
     for (int64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-        const int64_t k = tile * kShadowWalkTile + threadIdx.x;
+        const int64_t k = tile * kWalkTile + threadIdx.x;
         bool survives = false;
         const int64_t j = k < m ? (int64_t)a.in.ray[k] : a.w.rays;
         if (j < a.w.rays) {                                      // (an index past the queue is no ray of this walk)
@@ -128,7 +108,7 @@ __global__ __launch_bounds__(rlsh::kBlock) void shadow_step_kernel(ShadowWalkIO 
             a.left[k] = v.left;
         }
         int below;
-        const int total = shadow_tile_count(wtot, survives, below);
+        const int total = tile_count(wtot, survives, below);
         if (threadIdx.x == 0) a.counts[tile] = total;
     }
 }
@@ -137,16 +117,16 @@ __global__ __launch_bounds__(rlsh::kBlock) void shadow_step_kernel(ShadowWalkIO 
 template <bool BEGIN>
 __global__ __launch_bounds__(rlsh::kBlock) void shadow_place_kernel(ShadowWalkIO a)
 {
-    __shared__ int wtot[kShadowWalkWaves];
+    __shared__ int wtot[kWalkWaves];
     const int64_t m = shadow_entries(BEGIN ? a.w.count : a.in.count, a.bound);
     for (int64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-        const int64_t k = tile * kShadowWalkTile + threadIdx.x;
+        const int64_t k = tile * kWalkTile + threadIdx.x;
         const int64_t j = BEGIN ? k : k < m ? (int64_t)a.in.ray[k] : a.w.rays;
         const bool live = BEGIN ? k < m : j < a.w.rays;
         const int st = live ? a.state[k] : 0;
         const bool survives = (st & kShadowSurvives) != 0;
         int below;
-        shadow_tile_count(wtot, survives, below);
+        tile_count(wtot, survives, below);
         if (!survives) continue;
         const int64_t at = a.counts[tile] + below;
         a.out.ray[at] = (uint32_t)j;

@@ -14,15 +14,14 @@
 // rls_walk_begin is steps 2 and 3 behind walk_begin_kernel, which zeroes the hit counts and flags the rays with maxdist > 0.
 // No atomic, no workgroup waits on another; every position is a function of the inputs alone.
 //
-// A tile is kBlock entries, one per lane.  The lists' count lives on the device: every kernel is launched over the caller's
+// A tile is kBlock entries, one per lane (kWalkTile, kWalkWaves and the tile's survivor count, tile_count, are in
+// rls_walk_list.hpp, which walk.hip includes ahead of this file and the shadow rays' walk shares).  The lists' count lives on the device: every kernel is launched over the caller's
 // bound on it and reads the count itself, lanes past it idle, tiles past it count 0 survivors.
 //
 // What a ray carries from step to step: trials (a plane of the list) and maxdist = msgData->maxDist (the list's own plane:
 // ray.maxdist is reset to it after every hit, :346).  prev -- sg->P, the last accepted position -- is the hit the walk stored
 // last, or the shading point: it is read back from the hits, not carried.
 
-constexpr int kWalkTile = rlsh::kBlock;
-constexpr int kWalkWaves = rlsh::kBlock / 64;
 constexpr int kWalkSurvives = 1;             // bit 0 of an entry's flag; the trials left above it
 
 struct WalkRay { V3 prev; float left; int trials, count; };
@@ -68,25 +67,6 @@ __device__ __forceinline__ int64_t walk_entries(const WalkIO &a)
     return m < 0 ? 0 : m < a.bound ? m : a.bound;
 }
 
-// the survivors of this workgroup's tile, from one ballot a wavefront; whole workgroup.  below: those on the lanes and
-// wavefronts before this lane.
-__device__ __forceinline__ int walk_tile_count(int (&wtot)[kWalkWaves], bool survives, int &below)
-{
-    const int wave = (int)(threadIdx.x >> 6);
-    const uint64_t m = __builtin_amdgcn_ballot_w64(survives);
-    below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    __syncthreads();                                             // the previous tile's sums are read
-    if ((threadIdx.x & 63u) == 0) wtot[wave] = __builtin_popcountll(m);
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for (int w = 0; w < kWalkWaves; w++) {
-        if (w < wave) below += wtot[w];
-        total += wtot[w];
-    }
-    return total;
-}
-
 __global__ __launch_bounds__(rlsh::kBlock) void walk_begin_kernel(WalkIO a)
 {
     __shared__ int wtot[kWalkWaves];
@@ -99,7 +79,7 @@ __global__ __launch_bounds__(rlsh::kBlock) void walk_begin_kernel(WalkIO a)
             a.flag[j] = (uint8_t)(active ? kWalkSurvives | RLS_WALK_TRIALS << 1 : 0);
         }
         int below;
-        const int total = walk_tile_count(wtot, active, below);
+        const int total = tile_count(wtot, active, below);
         if (threadIdx.x == 0) a.counts[tile] = total;
     }
 }
@@ -141,7 +121,7 @@ __global__ __launch_bounds__(rlsh::kBlock) void walk_step_kernel(WalkIO a)
             a.left[k] = v.left;
         }
         int below;
-        const int total = walk_tile_count(wtot, survives, below);
+        const int total = tile_count(wtot, survives, below);
         if (threadIdx.x == 0) a.counts[tile] = total;
     }
 }
@@ -159,7 +139,7 @@ __global__ __launch_bounds__(rlsh::kBlock) void walk_place_kernel(WalkIO a)
         const int fl = live ? a.flag[k] : 0;
         const bool survives = (fl & kWalkSurvives) != 0;
         int below;
-        walk_tile_count(wtot, survives, below);
+        tile_count(wtot, survives, below);
         if (!survives) continue;
         const int64_t at = a.counts[tile] + below;
         a.out.ray[at] = (uint32_t)j;

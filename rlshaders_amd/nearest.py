@@ -15,7 +15,6 @@ numpy): the tree, its leaf size and the math mode of the context do not change a
 from __future__ import annotations
 
 import ctypes as C
-import os
 from pathlib import Path
 from typing import Optional
 
@@ -25,7 +24,7 @@ import torch
 from . import _capi as capi
 from . import shadow_walk, trace, walk
 from ._capi import check
-from .walk import WalkRays_, _flat
+from .walk import WalkRays_, _flat, _rows
 
 NEAREST_LIB_PATH = capi._PKG / "lib" / "librls_nearest.so"
 
@@ -77,30 +76,10 @@ def load() -> C.CDLL:
     """Load (once) and prototype the companion library; RLSHADERS_AMD_NEAREST_LIB overrides its path.  The product library is
     loaded first (contexts, errors)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    capi.load()
-    path = Path(os.environ.get("RLSHADERS_AMD_NEAREST_LIB", str(NEAREST_LIB_PATH)))
-    if not path.exists():
-        raise RuntimeError(f"rlshaders_amd.nearest: {path} not found. Build it with "
-                           f"`python -c 'from rlshaders_amd import build; build.build_nearest_library()'` (needs hipcc).")
-    lib = C.CDLL(str(path), mode=C.RTLD_GLOBAL)
-    missing = [n for n in PROTOTYPES if not hasattr(lib, n)]
-    if missing:
-        raise RuntimeError(f"rlshaders_amd.nearest: {path} lacks C-ABI symbols: {missing}")
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib = lib
-    return lib
-
-
-def _rows(t: torch.Tensor, n: int, what: str, cls):
-    """three planes of >= n floats"""
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.shape[0] != 3 or \
-            t.shape[1] < n or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise ValueError(f"{what}: expected a float32 CUDA tensor [3, >= {n}] with unit inner stride")
-    return cls(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+    if _lib is None:
+        _lib = capi.load_companion("rlshaders_amd.nearest", NEAREST_LIB_PATH, "RLSHADERS_AMD_NEAREST_LIB", PROTOTYPES,
+                                   "build_nearest_library", first=(capi.load,))
+    return _lib
 
 
 _IDS = (torch.int32, torch.uint32)

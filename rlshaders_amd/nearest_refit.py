@@ -14,8 +14,6 @@ cost can drift.  A triangle with a NaN or an infinity among its coordinates is p
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
 from typing import Optional
 
 import numpy as np
@@ -55,22 +53,10 @@ def load() -> C.CDLL:
     """Load (once) and prototype the companion library; RLSHADERS_AMD_NEAREST_REFIT_LIB overrides its path.  The product
     library and the nearest-hit library (whose scenes it reads) are loaded first."""
     global _lib
-    if _lib is not None:
-        return _lib
-    nearest.load()
-    path = Path(os.environ.get("RLSHADERS_AMD_NEAREST_REFIT_LIB", str(NEAREST_REFIT_LIB_PATH)))
-    if not path.exists():
-        raise RuntimeError(f"rlshaders_amd.nearest_refit: {path} not found. Build it with "
-                           f"`python -c 'from rlshaders_amd import build; build.build_nearest_refit_library()'` (needs hipcc).")
-    lib = C.CDLL(str(path), mode=C.RTLD_GLOBAL)
-    missing = [n for n in PROTOTYPES if not hasattr(lib, n)]
-    if missing:
-        raise RuntimeError(f"rlshaders_amd.nearest_refit: {path} lacks C-ABI symbols: {missing}")
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = capi.load_companion("rlshaders_amd.nearest_refit", NEAREST_REFIT_LIB_PATH, "RLSHADERS_AMD_NEAREST_REFIT_LIB",
+                                   PROTOTYPES, "build_nearest_refit_library", first=(nearest.load,))
+    return _lib
 
 
 class Refit:

@@ -19,8 +19,6 @@ list do nothing.
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
 from types import SimpleNamespace
 from typing import Optional
 
@@ -29,7 +27,7 @@ import torch
 from . import _capi as capi
 from . import trace
 from ._capi import check
-from .walk import WalkRays_, _flat, _List                 # the active list is the probe walk's (rls_walk_rays)
+from .walk import WalkRays_, _flat, _List, _rows          # the active list is the probe walk's (rls_walk_rays)
 
 SHADOW_WALK_LIB_PATH = capi._PKG / "lib" / "librls_shadow_walk.so"
 
@@ -64,36 +62,16 @@ def load() -> C.CDLL:
     """Load (once) and prototype the companion library; RLSHADERS_AMD_SHADOW_WALK_LIB overrides its path.  The product and the
     trace library are loaded first (contexts, errors; the queues the walk starts on)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    trace.load()
-    path = Path(os.environ.get("RLSHADERS_AMD_SHADOW_WALK_LIB", str(SHADOW_WALK_LIB_PATH)))
-    if not path.exists():
-        raise RuntimeError(f"rlshaders_amd.shadow_walk: {path} not found. Build it with "
-                           f"`python -c 'from rlshaders_amd import build; build.build_shadow_walk_library()'` (needs hipcc).")
-    lib = C.CDLL(str(path), mode=C.RTLD_GLOBAL)
-    missing = [n for n in PROTOTYPES if not hasattr(lib, n)]
-    if missing:
-        raise RuntimeError(f"rlshaders_amd.shadow_walk: {path} lacks C-ABI symbols: {missing}")
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = capi.load_companion("rlshaders_amd.shadow_walk", SHADOW_WALK_LIB_PATH, "RLSHADERS_AMD_SHADOW_WALK_LIB", PROTOTYPES,
+                                   "build_shadow_walk_library", first=(trace.load,))
+    return _lib
 
 
 def scratch_bytes(rays: int) -> int:
     b = C.c_size_t()
     check(load().rls_shadow_walk_scratch_bytes(int(rays), C.byref(b)))
     return int(b.value)
-
-
-def _rows(t: torch.Tensor, n: int, what: str, cls):
-    """three planes of >= n floats (a plane of one element has no inner stride to speak of)"""
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.shape[0] != 3 or \
-            t.shape[1] < n or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise ValueError(f"{what}: expected a float32 CUDA tensor [3, >= {n}] with unit inner stride")
-    return cls(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
 
 
 class Found:

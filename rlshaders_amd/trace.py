@@ -46,8 +46,6 @@ or of one rlDisney lobe, trace them with your own tracer, resolve the radiance; 
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
 from typing import Optional
 
 import torch
@@ -293,22 +291,10 @@ def load() -> C.CDLL:
     """Load (once) and prototype the companion library; RLSHADERS_AMD_TRACE_LIB overrides its path.  The product library is
     loaded first (the companion takes its contexts and error state from it)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    capi.load()
-    path = Path(os.environ.get("RLSHADERS_AMD_TRACE_LIB", str(TRACE_LIB_PATH)))
-    if not path.exists():
-        raise RuntimeError(f"rlshaders_amd.trace: {path} not found. Build it with "
-                           f"`python -c 'from rlshaders_amd import build; build.build_trace_library()'` (needs hipcc).")
-    lib = C.CDLL(str(path), mode=C.RTLD_GLOBAL)
-    missing = [n for n in PROTOTYPES if not hasattr(lib, n)]
-    if missing:
-        raise RuntimeError(f"rlshaders_amd.trace: {path} lacks C-ABI symbols: {missing}")
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = capi.load_companion("rlshaders_amd.trace", TRACE_LIB_PATH, "RLSHADERS_AMD_TRACE_LIB", PROTOTYPES,
+                                   "build_trace_library", first=(capi.load,))
+    return _lib
 
 
 def _radiance(t: torch.Tensor, count: int, what: str) -> "capi.CRgb":

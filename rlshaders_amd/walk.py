@@ -17,8 +17,6 @@ of 12 steps can be recorded by ``ctx.capture()``: steps on an empty list do noth
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
 from types import SimpleNamespace
 from typing import Optional
 
@@ -75,22 +73,10 @@ def load() -> C.CDLL:
     """Load (once) and prototype the companion library; RLSHADERS_AMD_WALK_LIB overrides its path.  The product and the trace
     library are loaded first (contexts, errors; the queues the walk starts on)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    trace.load()
-    path = Path(os.environ.get("RLSHADERS_AMD_WALK_LIB", str(WALK_LIB_PATH)))
-    if not path.exists():
-        raise RuntimeError(f"rlshaders_amd.walk: {path} not found. Build it with "
-                           f"`python -c 'from rlshaders_amd import build; build.build_walk_library()'` (needs hipcc).")
-    lib = C.CDLL(str(path), mode=C.RTLD_GLOBAL)
-    missing = [n for n in PROTOTYPES if not hasattr(lib, n)]
-    if missing:
-        raise RuntimeError(f"rlshaders_amd.walk: {path} lacks C-ABI symbols: {missing}")
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = capi.load_companion("rlshaders_amd.walk", WALK_LIB_PATH, "RLSHADERS_AMD_WALK_LIB", PROTOTYPES, "build_walk_library",
+                                   first=(trace.load,))
+    return _lib
 
 
 def scratch_bytes(rays: int) -> int:
@@ -99,9 +85,11 @@ def scratch_bytes(rays: int) -> int:
     return int(b.value)
 
 
+# ---- the checks of a caller's tensor, for this module and for the others whose libraries take planes and lists of this one's
 def _rows(t: torch.Tensor, n: int, what: str, cls):
+    """three planes of >= n floats (a plane of one element has no inner stride to speak of)"""
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.shape[0] != 3 or \
-            t.shape[1] < n or t.stride(1) != 1:
+            t.shape[1] < n or (t.shape[1] > 1 and t.stride(1) != 1):
         raise ValueError(f"{what}: expected a float32 CUDA tensor [3, >= {n}] with unit inner stride")
     return cls(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
 

@@ -23,6 +23,7 @@ CONSTANTS = ("RLS_SHADOW_WALK_MAX_STEPS",)
 KERNELS = ("shadow_begin_kernel", "shadow_step_kernel", "shadow_place_kernel", "trace_scan_block_kernel",
            "trace_scan_totals_kernel", "trace_scan_add_kernel")
 HIP = ROOT / "rlshaders_amd" / "csrc_shadow_walk" / "shadow_walk.hip"
+SHARED = ROOT / "rlshaders_amd" / "csrc_walk" / "rls_walk_list.hpp"
 
 
 def mirrors():
@@ -227,10 +228,15 @@ def test_scratch_bytes_refuses_by_name(shadow_walk_lib):
 
 
 def test_the_checks_are_written_once():
-    """every message of the host layer appears once in shadow_walk.hip, apart from the in / out pair of one check, and every
-    message the tables above ask for is one of them"""
-    text = HIP.read_text()
-    messages = re.findall(r'RLS_REQUIRE(?:_IN)?\([^;]*?"([^"]+)"\s*\)\s*;', text, flags=re.S)
+    """every message of the host layer appears once in shadow_walk.hip and the list machinery it shares with the probe walk
+    (csrc_walk/rls_walk_list.hpp) taken together, apart from the in / out pair of one check, and every message the tables above
+    ask for is one of them; what the shared header says, shadow_walk.hip does not say again"""
+    hip, shared = HIP.read_text(), SHARED.read_text()
+    pattern = r'RLS_REQUIRE(?:_IN)?\([^;]*?"([^"]+)"\s*\)\s*;'
+    text = hip + shared
+    messages = re.findall(pattern, text, flags=re.S)
     assert len(messages) >= 20 and len(messages) == len(set(messages)), sorted(m for m in set(messages) if messages.count(m) > 1)
     for _, _, want in WALK + BEGIN + STEP + ACTIVE:
         assert text.count(f'"{want}"') == 1, want
+    in_shared = re.findall(pattern, shared, flags=re.S)
+    assert in_shared and not [m for m in in_shared if f'"{m}"' in hip]

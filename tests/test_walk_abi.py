@@ -210,8 +210,14 @@ def test_every_argument_check_refuses_by_name(walk_lib, entry, call, table):
 
 
 def test_the_checks_are_written_once():
-    """every message of the host layer appears once in walk.hip, apart from the in / out pair of one check"""
+    """every message of the host layer appears once in walk.hip and the list machinery it shares with the shadow walk
+    (rls_walk_list.hpp) taken together, apart from the in / out pair of one check; what the shared header says, walk.hip does
+    not say again"""
     import re
-    text = (ROOT / "rlshaders_amd" / "csrc_walk" / "walk.hip").read_text()
-    messages = re.findall(r'RLS_REQUIRE(?:_IN)?\([^;]*?"([^"]+)"\s*\)\s*;', text, flags=re.S)
+    hip = (ROOT / "rlshaders_amd" / "csrc_walk" / "walk.hip").read_text()
+    shared = (ROOT / "rlshaders_amd" / "csrc_walk" / "rls_walk_list.hpp").read_text()
+    pattern = r'RLS_REQUIRE(?:_IN)?\([^;]*?"([^"]+)"\s*\)\s*;'
+    messages = re.findall(pattern, hip + shared, flags=re.S)
     assert len(messages) >= 20 and len(messages) == len(set(messages)), sorted(m for m in set(messages) if messages.count(m) > 1)
+    in_shared = re.findall(pattern, shared, flags=re.S)
+    assert in_shared and not [m for m in in_shared if f'"{m}"' in hip]
