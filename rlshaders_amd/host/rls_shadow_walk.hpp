@@ -17,7 +17,7 @@
 // walks the list's capacity, so a whole walk can be recorded into a Graph.
 #pragma once
 
-#include "rls_trace.hpp"
+#include "rls_walk.hpp"                                   // detail::WalkLists: the active lists are the probe walk's, as in C
 #include "rlshaders_amd_shadow_walk.h"
 
 namespace rlsb {
@@ -32,15 +32,7 @@ public:
         w_.rays = rays;
         size_t scratch = 0;
         check(rls_shadow_walk_scratch_bytes(rays, &scratch));
-        for (rls_walk_rays &l : lists_) {
-            l.capacity = rays;
-            l.count = bufs_.alloc<int64_t>(1);
-            l.ray = bufs_.alloc<uint32_t>(rays);
-            l.origin = bufs_.vec3(rays);
-            l.dir = bufs_.vec3(rays);
-            l.maxdist = bufs_.alloc<float>(rays);
-            l.trials = bufs_.alloc<uint8_t>(rays);
-        }
+        lists_.alloc(bufs_, rays);
         w_.scratch = bufs_.alloc(scratch);
         w_.scratch_bytes = scratch;
         vis_ = Planes(d, rays > 0 ? rays : 1, 3);
@@ -65,23 +57,22 @@ public:
         w_.O = O;
         w_.via = via;
         w_.base = base;
-        at_ = 0;
-        check(rls_shadow_walk_begin(dev_->ctx(), &w_, &q, &lists_[0]));
+        check(rls_shadow_walk_begin(dev_->ctx(), &w_, &q, &lists_.first()));
     }
     // the list the next step reads
-    const rls_walk_rays &rays() const { return lists_[at_]; }
+    const rls_walk_rays &rays() const { return lists_.in(); }
     // its count (synchronises)
     int64_t active() const
     {
         int64_t m = 0;
-        check(rls_shadow_walk_active(dev_->ctx(), &lists_[at_], &m));
+        check(rls_shadow_walk_active(dev_->ctx(), &lists_.in(), &m));
         return m;
     }
     // found: the nearest hits of the listed rays and their opacity; bound: an upper bound on active(), < 0 for the capacity
     void step(const rls_shadow_walk_found &found, int64_t bound = -1)
     {
-        check(rls_shadow_walk_step(dev_->ctx(), &w_, &lists_[at_], &found, bound, &lists_[at_ ^ 1]));
-        at_ ^= 1;
+        check(rls_shadow_walk_step(dev_->ctx(), &w_, &lists_.in(), &found, bound, &lists_.out()));
+        lists_.flip();
     }
     // T of every ray, valid after begin and after every step: what resolveDirect and the node resolves take as visibility
     const Planes &visibility() const { return vis_; }
@@ -90,10 +81,9 @@ public:
 private:
     const Device *dev_;
     detail::DeviceBuffers bufs_;
+    detail::WalkLists lists_;
     Planes vis_;
     rls_shadow_walk w_{};
-    rls_walk_rays lists_[2] = {};
-    int at_ = 0;
 };
 
 } // namespace rlsb

@@ -21,6 +21,31 @@
 
 namespace rlsb {
 
+namespace detail {
+// The two active lists of a walk (rls_walk_rays: the probe walk's and the shadow walk's alike), stated once: the ten buffers of
+// each out of the walk's own DeviceBuffers, the list the next step reads, and the flip after a step.
+struct WalkLists {
+    rls_walk_rays lists[2] = {};
+    int at = 0;
+    void alloc(DeviceBuffers &bufs, int64_t rays)
+    {
+        for (rls_walk_rays &l : lists) {
+            l.capacity = rays;
+            l.count = bufs.alloc<int64_t>(1);
+            l.ray = bufs.alloc<uint32_t>(rays);
+            l.origin = bufs.vec3(rays);
+            l.dir = bufs.vec3(rays);
+            l.maxdist = bufs.alloc<float>(rays);
+            l.trials = bufs.alloc<uint8_t>(rays);
+        }
+    }
+    const rls_walk_rays &first() { at = 0; return lists[0]; }     // what begin writes
+    const rls_walk_rays &in() const { return lists[at]; }          // what a step reads
+    const rls_walk_rays &out() const { return lists[at ^ 1]; }     // ... and writes, before the flip
+    void flip() { at ^= 1; }
+};
+} // namespace detail
+
 // One walk's device buffers -- the two active lists, the hits, the scratch -- owned here and nowhere else: allocated through one
 // DeviceBuffers member, so a constructor that throws half way frees what it had.
 class ProbeWalk {
@@ -32,15 +57,7 @@ public:
         w_.hits.stride = rays;
         size_t scratch = 0;
         check(rls_walk_scratch_bytes(rays, &scratch));
-        for (rls_walk_rays &l : lists_) {
-            l.capacity = rays;
-            l.count = bufs_.alloc<int64_t>(1);
-            l.ray = bufs_.alloc<uint32_t>(rays);
-            l.origin = bufs_.vec3(rays);
-            l.dir = bufs_.vec3(rays);
-            l.maxdist = bufs_.alloc<float>(rays);
-            l.trials = bufs_.alloc<uint8_t>(rays);
-        }
+        lists_.alloc(bufs_, rays);
         w_.hits.count = bufs_.alloc<uint8_t>(rays);
         w_.hits.P = bufs_.vec3(rays * maxHits);
         w_.hits.N = bufs_.vec3(rays * maxHits);
@@ -58,23 +75,22 @@ public:
         w_.P = P.cvec3();
         w_.own = own;
         w_.foreign = foreign;
-        at_ = 0;
-        check(rls_walk_begin(dev_->ctx(), &w_, &q.c(), &lists_[0]));
+        check(rls_walk_begin(dev_->ctx(), &w_, &q.c(), &lists_.first()));
     }
     // the list the next step reads
-    const rls_walk_rays &rays() const { return lists_[at_]; }
+    const rls_walk_rays &rays() const { return lists_.in(); }
     // its count (synchronises)
     int64_t active() const
     {
         int64_t m = 0;
-        check(rls_walk_active(dev_->ctx(), &lists_[at_], &m));
+        check(rls_walk_active(dev_->ctx(), &lists_.in(), &m));
         return m;
     }
     // found: the nearest hits of the listed rays; bound: an upper bound on active(), < 0 for the capacity
     void step(const rls_walk_found &found, int64_t bound = -1)
     {
-        check(rls_walk_step(dev_->ctx(), &w_, &lists_[at_], &found, bound, &lists_[at_ ^ 1]));
-        at_ ^= 1;
+        check(rls_walk_step(dev_->ctx(), &w_, &lists_.in(), &found, bound, &lists_.out()));
+        lists_.flip();
     }
     // what the resolves and emitHits read: the walk's count, P, N and the caller's irradiance planes (max_hits * rays floats each)
     rls_probe_hits hits(rls_crgb irradiance = rls_crgb{nullptr, nullptr, nullptr}) const
@@ -91,9 +107,8 @@ public:
 private:
     const Device *dev_;
     detail::DeviceBuffers bufs_;
+    detail::WalkLists lists_;
     rls_walk w_{};
-    rls_walk_rays lists_[2] = {};
-    int at_ = 0;
 };
 
 } // namespace rlsb

@@ -24,7 +24,7 @@ import torch
 from . import _capi as capi
 from . import shadow_walk, trace, walk
 from ._capi import check
-from .walk import WalkRays_, _flat, _rows
+from .walk import _IDS, WalkRays_, _flat, _rows, rays_struct
 
 NEAREST_LIB_PATH = capi._PKG / "lib" / "librls_nearest.so"
 
@@ -82,7 +82,6 @@ def load() -> C.CDLL:
     return _lib
 
 
-_IDS = (torch.int32, torch.uint32)
 VECTORS = ("P", "N", "Ns", "T", "wo")
 SCALARS = (("prim", torch.int32), ("surface", torch.int32), ("u", torch.float32), ("v", torch.float32))
 ALL_PLANES = VECTORS + tuple(k for k, _ in SCALARS)
@@ -252,12 +251,7 @@ class Scene:
         else:
             cap = int(rays.maxdist.shape[0])
             n = cap if active is None else min(int(active), cap)
-            r = WalkRays_()
-            r.capacity, r.count = cap, _flat(rays.count, 1, "list.count", (torch.int64,))
-            if cap > 0:
-                r.ray = _flat(rays.ray, cap, "list.ray", _IDS)
-                r.origin, r.dir = _rows(rays.origin, cap, "list.origin", capi.Vec3), _rows(rays.dir, cap, "list.dir", capi.Vec3)
-                r.maxdist = _flat(rays.maxdist, cap, "list.maxdist", (torch.float32,))
+            r = rays_struct(rays, cap, trials=False)
         if found is None:
             found = Found(ctx, n, planes=planes, bin=bin_of_surface is not None)
         elif found.rays < n:

@@ -19,7 +19,6 @@ list do nothing.
 from __future__ import annotations
 
 import ctypes as C
-from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -27,7 +26,7 @@ import torch
 from . import _capi as capi
 from . import trace
 from ._capi import check
-from .walk import WalkRays_, _flat, _List, _rows          # the active list is the probe walk's (rls_walk_rays)
+from .walk import ListWalk, WalkRays_, _flat, _rows       # the active list (rls_walk_rays) and its host layer are the probe walk's
 
 SHADOW_WALK_LIB_PATH = capi._PKG / "lib" / "librls_shadow_walk.so"
 
@@ -124,7 +123,7 @@ def _queue(queue):
     raise TypeError("queue: a trace.ShadowQueue (also the shadow queue of a node's queue set), a trace.HitQueues or a RawQueue")
 
 
-class ShadowWalk:
+class ShadowWalk(ListWalk):
     """The walk of a shadow queue's rays: begun on construction.  queue: a ``trace.ShadowQueue`` (``trace.ggx_shadow_rays``,
     ``disney_shadow_rays``, the shadow queue of a node's queue set), a ``trace.HitQueues`` (its shadow queue, with
     ``via=queues._hit_element`` and O the hit planes [3, max_hits * stride]) or a ``RawQueue``.  O [3, .]: the origins' table,
@@ -135,19 +134,11 @@ class ShadowWalk:
 
     def __init__(self, ctx, queue, O: torch.Tensor, base: Optional[torch.Tensor] = None, via: Optional[torch.Tensor] = None,
                  max_steps: int = 16, out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None, alloc=None):
-        self.ctx, self.queue, self.O, self.base, self.via = ctx, queue, O, base, via
-        dev = ctx.torch_device
+        self.queue, self.O, self.base, self.via = queue, O, base, via
         self.q, rays, count = _queue(queue)
         self.capacity, self.max_steps = rays, int(max_steps)
-        if alloc is None:
-            alloc = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        alloc = self._alloc(ctx, alloc)
         self.visibility = alloc((3, rays), torch.float32) if out is None else out
-        need = scratch_bytes(rays)
-        self.scratch = alloc((need,), torch.uint8) if scratch is None else scratch
-        if self.scratch.dtype != torch.uint8 or not self.scratch.is_contiguous() or self.scratch.numel() < need:
-            raise ValueError(f"scratch: expected a contiguous uint8 CUDA tensor of >= {need} bytes")
-        self.lists = [_List(alloc, rays), _List(alloc, rays)]
-        self.at = 0                                                 # the list the next step reads
         w = ShadowWalk_()
         w.rays, w.count, w.max_steps = rays, count, self.max_steps
         if rays > 0:
@@ -156,38 +147,9 @@ class ShadowWalk:
         w.via = None if via is None else _flat(via, 0, "via", (torch.int64,))
         if base is not None and rays > 0:
             w.base = _rows(base, rays, "base", capi.CRgb)
-        w.scratch, w.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel()
-        self.w = w
-        self.begin()
-
-    def begin(self) -> "ShadowWalk":
-        """(re)start the walk on the queue as it is now"""
-        self.at = 0
-        check(load().rls_shadow_walk_begin(self.ctx.handle, C.byref(self.w), C.byref(self.q), C.byref(self.lists[0].s)))
-        return self
-
-    @property
-    def rays(self) -> SimpleNamespace:
-        """the list the next step reads, as tensors of its capacity: entries [0, active) are the active rays; trials: the steps
-        left"""
-        l = self.lists[self.at]
-        return SimpleNamespace(count=l.count, ray=l.ray, origin=l.origin, dir=l.dir, maxdist=l.maxdist, trials=l.trials)
-
-    @property
-    def active(self) -> int:
-        """the active rays, read from the device (synchronises)"""
-        n = C.c_int64()
-        check(load().rls_shadow_walk_active(self.ctx.handle, C.byref(self.lists[self.at].s), C.byref(n)))
-        return int(n.value)
-
-    def step(self, found: Found, bound: Optional[int] = None) -> "ShadowWalk":
-        """one step over the nearest hits of the listed rays; bound: an upper bound on the active count (it sizes the grid and the
-        planes ``found`` must hold), by default the list's capacity"""
-        b = self.capacity if bound is None else min(int(bound), self.capacity)
-        check(load().rls_shadow_walk_step(self.ctx.handle, C.byref(self.w), C.byref(self.lists[self.at].s),
-                                          C.byref(found.struct(b)), -1 if bound is None else b, C.byref(self.lists[self.at ^ 1].s)))
-        self.at ^= 1
-        return self
+        lib = load()
+        self._start(ctx, w, self.q, rays, scratch_bytes(rays), scratch, alloc, lib.rls_shadow_walk_begin, lib.rls_shadow_walk_step,
+                    lib.rls_shadow_walk_active)
 
 
 def run(queue, O: torch.Tensor, tracer, base: Optional[torch.Tensor] = None, via: Optional[torch.Tensor] = None,
@@ -195,9 +157,4 @@ def run(queue, O: torch.Tensor, tracer, base: Optional[torch.Tensor] = None, via
     """Walk the queue's rays to the end: tracer(rays, active) -> Found, the nearest hits of the first ``active`` listed rays.  At
     most max_steps steps."""
     w = ShadowWalk(queue.ctx if ctx is None else ctx, queue, O, base=base, via=via, max_steps=max_steps, out=out)
-    for _ in range(w.max_steps):
-        m = w.active
-        if m == 0:
-            break
-        w.step(tracer(w.rays, m), bound=m)
-    return w
+    return w.drive(tracer, w.max_steps)

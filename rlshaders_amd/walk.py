@@ -117,8 +117,25 @@ class Found:
         return f
 
 
+_IDS = (torch.int32, torch.uint32)
+
+
+def rays_struct(l, cap: int, trials: bool = True) -> WalkRays_:
+    """rls_walk_rays over the tensors of l (count, ray, origin, dir, maxdist and, with ``trials``, trials), each checked to hold
+    cap entries"""
+    s = WalkRays_()
+    s.capacity, s.count = cap, _flat(l.count, 1, "list.count", (torch.int64,))
+    if cap > 0:
+        s.ray = _flat(l.ray, cap, "list.ray", _IDS)
+        s.origin, s.dir = _rows(l.origin, cap, "list.origin", capi.Vec3), _rows(l.dir, cap, "list.dir", capi.Vec3)
+        s.maxdist = _flat(l.maxdist, cap, "list.maxdist", (torch.float32,))
+        if trials:
+            s.trials = _flat(l.trials, cap, "list.trials", (torch.uint8,))
+    return s
+
+
 class _List:
-    """one active list's device buffers and its struct"""
+    """one active list's device buffers, its struct and the reference a call passes"""
 
     def __init__(self, alloc, cap: int):
         self.count = alloc((1,), torch.int64)
@@ -127,15 +144,74 @@ class _List:
         self.dir = alloc((3, cap), torch.float32)
         self.maxdist = alloc((cap,), torch.float32)
         self.trials = alloc((cap,), torch.uint8)
-        s = WalkRays_()
-        s.capacity, s.count, s.ray = cap, self.count.data_ptr(), self.ray.data_ptr()
-        s.origin = capi.Vec3(*[self.origin[k].data_ptr() for k in range(3)])
-        s.dir = capi.Vec3(*[self.dir[k].data_ptr() for k in range(3)])
-        s.maxdist, s.trials = self.maxdist.data_ptr(), self.trials.data_ptr()
-        self.s = s
+        self.s = rays_struct(self, cap)
+        self.p = C.byref(self.s)
 
 
-class ProbeWalk:
+class ListWalk:
+    """What a walk over two lists of rls_walk_rays is, whichever rays it walks: alloc's default, the scratch, the two lists a step
+    swaps, and begin / rays / active / step over the three entry points its subclass names.  A subclass allocates what is its
+    own through ``_alloc``, fills its struct but for the scratch, and calls ``_start``."""
+
+    @staticmethod
+    def _alloc(ctx, alloc):
+        if alloc is not None:
+            return alloc
+        dev = ctx.torch_device
+        return lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+
+    def _start(self, ctx, w, q, rays: int, need: int, scratch, alloc, begin, step, active):
+        """w: the walk's struct, q: its queue's; need: the scratch's bytes; begin, step, active: the library's functions"""
+        self.scratch = alloc((need,), torch.uint8) if scratch is None else scratch
+        if self.scratch.dtype != torch.uint8 or not self.scratch.is_contiguous() or self.scratch.numel() < need:
+            raise ValueError(f"scratch: expected a contiguous uint8 CUDA tensor of >= {need} bytes")
+        self.lists = [_List(alloc, rays), _List(alloc, rays)]
+        w.scratch, w.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel()
+        self.ctx, self.w, self._rays = ctx, w, rays
+        self._wp, self._qp, self._begin, self._step, self._active = C.byref(w), C.byref(q), begin, step, active
+        self.begin()
+
+    def begin(self):
+        """(re)start the walk on the queue as it is now"""
+        self.at = 0                                                 # the list the next step reads
+        check(self._begin(self.ctx.handle, self._wp, self._qp, self.lists[0].p))
+        return self
+
+    @property
+    def rays(self) -> SimpleNamespace:
+        """the list the next step reads, as tensors of its capacity: entries [0, active) are the active rays; trials: the steps
+        left"""
+        l = self.lists[self.at]
+        return SimpleNamespace(count=l.count, ray=l.ray, origin=l.origin, dir=l.dir, maxdist=l.maxdist, trials=l.trials)
+
+    @property
+    def active(self) -> int:
+        """the active rays, read from the device (synchronises)"""
+        n = C.c_int64()
+        check(self._active(self.ctx.handle, self.lists[self.at].p, C.byref(n)))
+        return int(n.value)
+
+    def step(self, found, bound: Optional[int] = None):
+        """one step over the nearest hits of the listed rays (the module's ``Found``); bound: an upper bound on the active count
+        (it sizes the grid and the planes ``found`` must hold), by default the list's capacity"""
+        b = self._rays if bound is None else min(int(bound), self._rays)
+        check(self._step(self.ctx.handle, self._wp, self.lists[self.at].p, C.byref(found.struct(b)), -1 if bound is None else b,
+                         self.lists[self.at ^ 1].p))
+        self.at ^= 1
+        return self
+
+    def drive(self, tracer, steps: int):
+        """to the end, in at most ``steps`` steps: tracer(rays, active) -> Found, the nearest hits of the first ``active`` listed
+        rays"""
+        for _ in range(steps):
+            m = self.active
+            if m == 0:
+                break
+            self.step(tracer(self.rays, m), bound=m)
+        return self
+
+
+class ProbeWalk(ListWalk):
     """The walk of a probe queue's rays (``trace.sss_probe_rays``, or ``trace.skin_node_rays(...).probe``) about the shading
     points P [3, n]: begun on construction.  own: int32 [n], the id of each point's own object, or None for one object everywhere;
     foreign: "stop" (the compiled reference) or "skip" (include/rlshaders_amd_walk.h).  alloc(shape, dtype) -> a contiguous device
@@ -144,21 +220,13 @@ class ProbeWalk:
 
     def __init__(self, ctx, queue, P: torch.Tensor, own: Optional[torch.Tensor] = None, max_hits: int = trace.RLS_MAX_PROBE_HITS,
                  foreign: str = "stop", scratch: Optional[torch.Tensor] = None, alloc=None, point: Optional[torch.Tensor] = None):
-        self.ctx, self.queue, self.P, self.own, self.point = ctx, queue, P, own, point
-        dev = ctx.torch_device
+        self.queue, self.P, self.own, self.point = queue, P, own, point
         rays = self.count = int(queue.count)
         self.max_hits = int(max_hits)
-        if alloc is None:
-            alloc = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        alloc = self._alloc(ctx, alloc)
         self.hit_count = alloc((rays,), torch.uint8)
         self.hit_P = alloc((3, self.max_hits, rays), torch.float32)
         self.hit_N = alloc((3, self.max_hits, rays), torch.float32)
-        need = scratch_bytes(rays)
-        self.scratch = alloc((need,), torch.uint8) if scratch is None else scratch
-        if self.scratch.dtype != torch.uint8 or not self.scratch.is_contiguous() or self.scratch.numel() < need:
-            raise ValueError(f"scratch: expected a contiguous uint8 CUDA tensor of >= {need} bytes")
-        self.lists = [_List(alloc, rays), _List(alloc, rays)]
-        self.at = 0                                                 # the list the next step reads
         w = Walk_()
         w.rays, w.spp = rays, queue.spp_n * queue.spp_n
         w.point = None if point is None else _flat(point, rays, "point", (torch.int32,))
@@ -170,37 +238,9 @@ class ProbeWalk:
         w.hits.max_hits, w.hits.stride, w.hits.count = self.max_hits, rays, self.hit_count.data_ptr()
         w.hits.P = capi.Vec3(*[self.hit_P[k].data_ptr() for k in range(3)])
         w.hits.N = capi.Vec3(*[self.hit_N[k].data_ptr() for k in range(3)])
-        w.scratch, w.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel()
-        self.w = w
-        self.begin()
-
-    def begin(self) -> "ProbeWalk":
-        """(re)start the walk on the queue as it is now"""
-        self.at = 0
-        check(load().rls_walk_begin(self.ctx.handle, C.byref(self.w), C.byref(self.queue.q), C.byref(self.lists[0].s)))
-        return self
-
-    @property
-    def rays(self) -> SimpleNamespace:
-        """the list the next step reads, as tensors of its capacity: entries [0, active) are the active rays"""
-        l = self.lists[self.at]
-        return SimpleNamespace(count=l.count, ray=l.ray, origin=l.origin, dir=l.dir, maxdist=l.maxdist, trials=l.trials)
-
-    @property
-    def active(self) -> int:
-        """the active rays, read from the device (synchronises)"""
-        n = C.c_int64()
-        check(load().rls_walk_active(self.ctx.handle, C.byref(self.lists[self.at].s), C.byref(n)))
-        return int(n.value)
-
-    def step(self, found: Found, bound: Optional[int] = None) -> "ProbeWalk":
-        """one step over the nearest hits of the listed rays; bound: an upper bound on the active count (it sizes the grid and the
-        planes ``found`` must hold), by default the list's capacity"""
-        b = self.count if bound is None else min(int(bound), self.count)
-        check(load().rls_walk_step(self.ctx.handle, C.byref(self.w), C.byref(self.lists[self.at].s), C.byref(found.struct(b)),
-                                   -1 if bound is None else b, C.byref(self.lists[self.at ^ 1].s)))
-        self.at ^= 1
-        return self
+        lib = load()
+        self._start(ctx, w, queue.q, rays, scratch_bytes(rays), scratch, alloc, lib.rls_walk_begin, lib.rls_walk_step,
+                    lib.rls_walk_active)
 
     def hits(self, E: Optional[torch.Tensor] = None) -> tuple:
         """(count, P, N, E): the arguments of ``ProbeQueue.resolve`` and of ``trace.sss_hit_rays`` (E: the caller's irradiance
@@ -213,9 +253,4 @@ def run(queue, P: torch.Tensor, tracer, own: Optional[torch.Tensor] = None, max_
     """Walk the queue's rays to the end: tracer(rays, active) -> Found, the nearest hits of the first ``active`` listed rays.  At most
     RLS_WALK_TRIALS steps, the walk's trial budget."""
     w = ProbeWalk(queue.ctx if ctx is None else ctx, queue, P, own=own, max_hits=max_hits, foreign=foreign)
-    for _ in range(RLS_WALK_TRIALS):
-        m = w.active
-        if m == 0:
-            break
-        w.step(tracer(w.rays, m), bound=m)
-    return w
+    return w.drive(tracer, RLS_WALK_TRIALS)

@@ -1,12 +1,12 @@
 """helpers of the shadow walk's CPU tests (test_shadow_walk_abi.py, test_cmake_shadow_walk.py): what
 include/rlshaders_amd_shadow_walk.h declares and librls_shadow_walk.so exports, and valid arguments over dummy memory for the
 refusal table, after trace_abi_util.Dummies.  pytest does not collect this module."""
-import ctypes as C
 import re
 
 import pytest
 
-from trace_abi_util import ROOT, Dummies, code_text, dynamic_symbols
+from trace_abi_util import ROOT, code_text, dynamic_symbols
+from walk_abi_util import ListWalkWorld
 
 HEADER = ROOT / "include" / "rlshaders_amd_shadow_walk.h"
 
@@ -42,42 +42,17 @@ def struct_members(c_name):
     return [re.search(r"(\w+)\s*$", part.strip()).group(1) for d in body.split(";") if d.strip() for part in d.split(",")]
 
 
-class ShadowWalkWorld(Dummies):
+class ShadowWalkWorld(ListWalkWorld):
     """a valid walk of 192 rays (the capacity of a node's light loop over 8 points, 2 lights, spp_n = 2) over dummy memory: the
     walk, the queue, two lists, the found hits"""
 
     def __init__(self):
-        super().__init__()
         from rlshaders_amd import shadow_walk
-        capi = self.capi
-        self.sw, self.wlib = shadow_walk, shadow_walk.load()
-        self.q = self.shadow_queue(3)
-        self.q.point = self.p
-        rays = self.rays = self.q.capacity
-        self.w = shadow_walk.ShadowWalk_()
-        self.w.rays, self.w.count, self.w.max_steps, self.w.O = rays, self.p, 8, self.v3(capi.CVec3)
-        self.w.visibility = self.v3(capi.Rgb)
-        self.w.scratch, self.w.scratch_bytes = self.p, self._scratch(self.wlib.rls_shadow_walk_scratch_bytes, rays)
-        self.lists = [self.list_at(0), self.list_at(4096)]
-        self.f = shadow_walk.ShadowWalkFound_(self.p, self.p, self.v3(capi.CVec3), self.v3(capi.CRgb), None, 0)
-        self.wp, self.qp, self.fp = C.byref(self.w), C.byref(self.q), C.byref(self.f)
-        self.inp, self.outp = C.byref(self.lists[0]), C.byref(self.lists[1])
-        self.bound = -1
-        self.host = C.c_int64()
-        self.hostp = C.byref(self.host)
-
-    def list_at(self, off):
-        """a list whose planes start `off` bytes into the dummy block (two lists must not share planes)"""
-        capi, l, p = self.capi, self.sw.WalkRays_(), self.p + off
-        l.capacity, l.count, l.ray, l.maxdist, l.trials = self.rays, p, p, p, p
-        l.origin, l.dir = capi.Vec3(p, p, p), capi.Vec3(p, p, p)
-        return l
-
-    def begin(self):
-        return self.wlib.rls_shadow_walk_begin(self.ctxp, self.wp, self.qp, self.outp)
-
-    def step(self):
-        return self.wlib.rls_shadow_walk_step(self.ctxp, self.wp, self.inp, self.fp, self.bound, self.outp)
-
-    def active(self):
-        return self.wlib.rls_shadow_walk_active(self.ctxp, self.inp, self.hostp)
+        super().__init__(shadow_walk.load(), "rls_shadow_walk")
+        capi, q, w = self.capi, self.shadow_queue(3), shadow_walk.ShadowWalk_()
+        q.point = self.p
+        rays = self.rays = q.capacity
+        w.rays, w.count, w.max_steps, w.O = rays, self.p, 8, self.v3(capi.CVec3)
+        w.visibility = self.v3(capi.Rgb)
+        w.scratch, w.scratch_bytes = self.p, self._scratch(self.wlib.rls_shadow_walk_scratch_bytes, rays)
+        self.over(w, q, shadow_walk.ShadowWalkFound_(self.p, self.p, self.v3(capi.CVec3), self.v3(capi.CRgb), None, 0))

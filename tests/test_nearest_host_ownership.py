@@ -2,36 +2,19 @@
 every allocation, also when one of them fails.
 
 tests/native/nearest_ownership.cpp is built as an integrator builds against the header (g++ -std=c++14 -Wall, here with the
-address and undefined-behaviour sanitizers: a stand-alone host program) but links no library: it defines rls_device_alloc /
-rls_device_free and the scene's create / destroy over the heap, counting live blocks and failing the k-th call.  Every form is
-constructed once unhindered -- N allocations, none live after destruction -- and once per k in 1..N with the k-th failing -- an
-rlsb::Error, none live (what leaks for real is the sanitizer's to report: the program's blocks are not freed behind its back)."""
+address and undefined-behaviour sanitizers: a stand-alone host program) but links no library: with ownership_harness.hpp it
+defines rls_device_alloc / rls_device_free and the scene's create / destroy over the heap, counting live blocks and failing
+the k-th call.  Every form is constructed once unhindered -- N allocations, none live after destruction -- and once per k in
+1..N with the k-th failing -- an rlsb::Error, none live (what a k leaves live is reported in its row, then given back the way
+it was made: free for a block, delete for a scene)."""
 import re
-import subprocess
-from pathlib import Path
 
-import pytest
+from ownership_util import (HOST, rows_of, test_a_failing_allocation_throws_and_leaves_nothing_live,  # noqa: F401
+                            test_nothing_is_live_after_destruction)
 
-ROOT = Path(__file__).resolve().parent.parent
-DRIVER = ROOT / "tests" / "native" / "nearest_ownership.cpp"
-HEADER = ROOT / "rlshaders_amd" / "host" / "rls_nearest.hpp"
+HEADER = HOST / "rls_nearest.hpp"
 
-
-@pytest.fixture(scope="module")
-def rows(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("nearest_ownership") / "nearest_ownership"
-    cmd = ["g++", "-std=c++14", "-Wall", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{ROOT / 'include'}",
-           f"-I{ROOT / 'rlshaders_amd' / 'host'}", str(DRIVER), "-o", str(exe)]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout + p.stderr
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, p.stdout + p.stderr
-    out = {}
-    for line in p.stdout.splitlines():
-        name, n, live, leaked, silent = line.split("\t")
-        out[name] = dict(n=int(n), live=int(live), leaked=[int(k) for k in leaked.split(",") if k],
-                         silent=[int(k) for k in silent.split(",") if k])
-    return out
+rows = rows_of("nearest_ownership", sanitize=True)
 
 
 def test_every_form_is_constructed(rows):
@@ -43,15 +26,6 @@ def test_every_form_is_constructed(rows):
         want[f"NearestFound shadow rays {r}"] = 2 + 3 + 1 + 1
         want[f"NearestFound bare rays {r}"] = 2
     assert {k: v["n"] for k, v in rows.items()} == want
-
-
-def test_nothing_is_live_after_destruction(rows):
-    assert {k: r["live"] for k, r in rows.items() if r["live"]} == {}
-
-
-def test_a_failing_allocation_throws_and_leaves_nothing_live(rows):
-    assert {k: r["silent"] for k, r in rows.items() if r["silent"]} == {}
-    assert {k: r["leaked"] for k, r in rows.items() if r["leaked"]} == {}
 
 
 def test_one_owner_in_the_header():

@@ -17,6 +17,7 @@ import pytest
 from shadow_walk_abi_util import (HEADER, ShadowWalkWorld, declarations, declared_symbols, exported_symbols,  # noqa: F401
                                   shadow_walk_lib, struct_members, structs)
 from trace_abi_util import INVALID, ROOT, dynamic_symbols, put, refusals
+from walk_abi_util import ACTIVE, LIST_IN, LIST_OUT
 
 ARITY = dict(rls_shadow_walk_scratch_bytes=2, rls_shadow_walk_begin=4, rls_shadow_walk_step=6, rls_shadow_walk_active=3)
 CONSTANTS = ("RLS_SHADOW_WALK_MAX_STEPS",)
@@ -58,7 +59,7 @@ def probe(tmp_path_factory):
 
 # ---- the surface ---------------------------------------------------------------------------------------------------------------
 def test_exports_exactly_the_header_and_the_bindings(shadow_walk_lib):
-    from rlshaders_amd import shadow_walk
+    from rlshaders_amd import shadow_walk, walk
     declared, decl = declared_symbols(), declarations()
     assert declared and all(s.startswith("rls_shadow_walk_") for s in declared), declared
     assert exported_symbols(shadow_walk_lib) == declared
@@ -77,6 +78,9 @@ def test_exports_exactly_the_header_and_the_bindings(shadow_walk_lib):
     assert list(sig.parameters)[:4] == ["self", "ctx", "queue", "O"]
     assert all(sig.parameters[k].default is None for k in ("base", "via", "out", "scratch", "alloc")) and "max_steps" in sig.parameters
     assert list(inspect.signature(shadow_walk.Found.__init__).parameters) == ["self", "hit", "t", "P", "opacity", "index"]
+    # the list walk's host layer is written once, in walk.ListWalk: neither walk states it again
+    for cls in (shadow_walk.ShadowWalk, walk.ProbeWalk):
+        assert issubclass(cls, walk.ListWalk) and not {"begin", "step", "active", "rays"} & set(vars(cls)), cls
 
 
 def test_other_libraries_know_nothing_of_the_shadow_walk(shadow_walk_lib):
@@ -163,7 +167,6 @@ def test_scratch_size():
     assert lib.rls_shadow_walk_scratch_bytes(1, None) == INVALID
 
 
-LIST = "out.ray, out.origin, out.dir, out.maxdist or out.trials plane is NULL"
 WALK = [
     ("ctx NULL", lambda w: put(w, "ctxp", None), "ctx is NULL"),
     ("walk NULL", lambda w: put(w, "wp", None), "walk is NULL"),
@@ -177,13 +180,8 @@ WALK = [
     ("scratch NULL", lambda w: put(w.w, "scratch", None), "walk.scratch is NULL or smaller than rls_shadow_walk_scratch_bytes"),
     ("scratch short", lambda w: put(w.w, "scratch_bytes", w.w.scratch_bytes - 1),
      "walk.scratch is NULL or smaller than rls_shadow_walk_scratch_bytes"),
-    ("out NULL", lambda w: put(w, "outp", None), "out is NULL"),
-    ("out.count NULL", lambda w: put(w.lists[1], "count", None), "out.count is NULL"),
-    ("out.capacity short", lambda w: put(w.lists[1], "capacity", w.w.rays - 1), "out.capacity < walk.rays"),
-    ("out.trials NULL", lambda w: put(w.lists[1], "trials", None), LIST),
-    ("out.dir NULL", lambda w: put(w.lists[1], "dir", w.half3(w.capi.Vec3)), LIST),
 ]
-BEGIN = WALK + [
+BEGIN = WALK + LIST_OUT + [
     ("O NULL", lambda w: put(w.w, "O", w.half3(w.capi.CVec3)), "walk.O plane is NULL"),
     ("queue NULL", lambda w: put(w, "qp", None), "queue is NULL"),
     ("queue.capacity short", lambda w: put(w.q, "capacity", w.w.rays - 1), "queue.capacity < walk.rays"),
@@ -191,22 +189,11 @@ BEGIN = WALK + [
     ("queue.dir NULL", lambda w: put(w.q, "dir", w.half3(w.capi.Vec3)), "queue.dir or queue.maxdist plane is NULL"),
     ("queue.point NULL", lambda w: put(w.q, "point", None), "queue.point is NULL: the walk reads every ray's origin through it"),
 ]
-STEP = WALK + [
-    ("in NULL", lambda w: put(w, "inp", None), "in is NULL"),
-    ("in.count NULL", lambda w: put(w.lists[0], "count", None), "in.count is NULL"),
-    ("in.capacity short", lambda w: put(w.lists[0], "capacity", w.w.rays - 1), "in.capacity < walk.rays"),
-    ("in.ray NULL", lambda w: put(w.lists[0], "ray", None), LIST.replace("out", "in")),
-    ("out is in", lambda w: put(w, "outp", w.inp), "out is in: a step reads one list and writes the other"),
+STEP = WALK + LIST_OUT + LIST_IN + [
     ("found NULL", lambda w: put(w, "fp", None), "found is NULL"),
     ("found.hit NULL", lambda w: put(w.f, "hit", None), "found.hit, found.t, found.P or found.opacity plane is NULL"),
     ("found.opacity half", lambda w: put(w.f, "opacity", w.half3(w.capi.CRgb)), "found.hit, found.t, found.P or found.opacity plane is NULL"),
     ("index, empty table", lambda w: put(w.f, "index", w.p), "found.index is set with found.table_count == 0"),
-]
-ACTIVE = [
-    ("ctx NULL", lambda w: put(w, "ctxp", None), "ctx is NULL"),
-    ("rays NULL", lambda w: put(w, "inp", None), "rays or rays.count is NULL"),
-    ("rays.count NULL", lambda w: put(w.lists[0], "count", None), "rays or rays.count is NULL"),
-    ("host_count NULL", lambda w: put(w, "hostp", None), "host_count is NULL"),
 ]
 
 

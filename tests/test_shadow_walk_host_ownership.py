@@ -2,36 +2,18 @@
 also when one of them fails.
 
 tests/native/shadow_walk_ownership.cpp is built as an integrator builds against the header (g++ -std=c++14 -Wall, here with the
-address and undefined-behaviour sanitizers: a stand-alone host program) but links no library: it defines rls_device_alloc /
-rls_device_free over malloc, counting live blocks and failing the k-th call.  It constructs the walk with and without rays: once
-unhindered -- N allocations, none live after destruction -- and once per k in 1..N with the k-th allocation failing -- an
-rlsb::Error, none live."""
+address and undefined-behaviour sanitizers: a stand-alone host program) but links no library: with ownership_harness.hpp it
+defines rls_device_alloc / rls_device_free over malloc, counting live blocks and failing the k-th call.  It constructs the walk
+with and without rays: once unhindered -- N allocations, none live after destruction -- and once per k in 1..N with the k-th
+allocation failing -- an rlsb::Error, none live."""
 import re
-import subprocess
-from pathlib import Path
 
-import pytest
+from ownership_util import (HOST, rows_of, test_a_failing_allocation_throws_and_leaves_nothing_live,  # noqa: F401
+                            test_nothing_is_live_after_destruction)
 
-ROOT = Path(__file__).resolve().parent.parent
-DRIVER = ROOT / "tests" / "native" / "shadow_walk_ownership.cpp"
-HEADER = ROOT / "rlshaders_amd" / "host" / "rls_shadow_walk.hpp"
+HEADER = HOST / "rls_shadow_walk.hpp"
 
-
-@pytest.fixture(scope="module")
-def rows(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("shadow_walk_ownership") / "shadow_walk_ownership"
-    cmd = ["g++", "-std=c++14", "-Wall", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{ROOT / 'include'}",
-           f"-I{ROOT / 'rlshaders_amd' / 'host'}", str(DRIVER), "-o", str(exe)]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout + p.stderr
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, p.stdout + p.stderr
-    out = {}
-    for line in p.stdout.splitlines():
-        name, n, live, leaked, silent = line.split("\t")
-        out[name] = dict(n=int(n), live=int(live), leaked=[int(k) for k in leaked.split(",") if k],
-                         silent=[int(k) for k in silent.split(",") if k])
-    return out
+rows = rows_of("shadow_walk_ownership", sanitize=True)
 
 
 def test_the_walk_is_constructed_in_every_form(rows):
@@ -40,19 +22,11 @@ def test_the_walk_is_constructed_in_every_form(rows):
     assert {r["n"] for r in rows.values()} == {2 * 10 + 1 + 1}
 
 
-def test_nothing_is_live_after_destruction(rows):
-    assert {k: r["live"] for k, r in rows.items() if r["live"]} == {}
-
-
-def test_a_failing_allocation_throws_and_leaves_nothing_live(rows):
-    assert {k: r["silent"] for k, r in rows.items() if r["silent"]} == {}
-    assert {k: r["leaked"] for k, r in rows.items() if r["leaked"]} == {}
-
-
 def test_one_owner_in_the_header():
     """the lists and the scratch go through the class's one DeviceBuffers member, the visibility is one Planes member; the header
     frees and allocates nothing by itself, and the class cannot be copied"""
     text = HEADER.read_text()
     assert not re.search(r"\brls_device_(alloc|free)\b", text)
     assert text.count("detail::DeviceBuffers bufs_;") == 1 and text.count("Planes vis_;") == 1
+    assert "bufs_.alloc<uint32_t>" not in text                   # the lists' buffers are rls_walk.hpp's to state, once
     assert "ShadowWalk(const ShadowWalk &) = delete;" in text and "ShadowWalk &operator=(const ShadowWalk &) = delete;" in text

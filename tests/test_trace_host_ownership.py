@@ -1,35 +1,23 @@
 """CPU: the buffer-owning classes of host/rls_trace.hpp give back every device allocation, also when one of them fails.
 
 tests/native/trace_queue_ownership.cpp is built as an integrator builds against the header (g++ -std=c++14 -Wall) but links
-neither library: it defines rls_device_alloc / rls_device_free over malloc, counting live blocks and failing the k-th call.
-It constructs RayQueue of every kind, ProbeQueue, HitQueues with and without lights and diffuse, ShadowQueue of every node,
-ShadowHits in both forms and the four node queue sets with and without lights (n = 5, spp_n = 2, 2 lights, max_hits 3): once
-unhindered -- N allocations, none live after destruction -- and once per k in 1..N with the k-th allocation failing -- an
-rlsb::Error, none live."""
-import subprocess
-from pathlib import Path
+neither library: with ownership_harness.hpp it defines rls_device_alloc / rls_device_free over malloc, counting live blocks and
+failing the k-th call.  It constructs RayQueue of every kind, ProbeQueue, HitQueues with and without lights and diffuse,
+ShadowQueue of every node, ShadowHits in both forms and the four node queue sets with and without lights (n = 5, spp_n = 2,
+2 lights, max_hits 3): once unhindered -- N allocations, none live after destruction -- and once per k in 1..N with the k-th
+allocation failing -- an rlsb::Error, none live."""
+from ownership_util import (ROOT, rows_of, test_a_failing_allocation_throws_and_leaves_nothing_live,  # noqa: F401
+                            test_nothing_is_live_after_destruction)
 
-import pytest
-
-ROOT = Path(__file__).resolve().parent.parent
-DRIVER = ROOT / "tests" / "native" / "trace_queue_ownership.cpp"
+rows = rows_of("trace_queue_ownership", sanitize=False)
 
 
-@pytest.fixture(scope="module")
-def rows(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("trace_queue_ownership") / "trace_queue_ownership"
-    cmd = ["g++", "-std=c++14", "-Wall",f"-I{ROOT / 'include'}", f"-I{ROOT / 'rlshaders_amd' / 'host'}", str(DRIVER),
-           "-o", str(exe)]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout + p.stderr
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, p.stdout + p.stderr
-    out = {}
-    for line in p.stdout.splitlines():
-        name, n, live, leaked, silent = line.split("\t")
-        out[name] = dict(n=int(n), live=int(live), leaked=[int(k) for k in leaked.split(",") if k],
-                         silent=[int(k) for k in silent.split(",") if k])
-    return out
+def test_the_counting_allocator_is_written_once():
+    """in ownership_harness.hpp, for this program and the four after its pattern"""
+    programs = sorted((ROOT / "tests" / "native").glob("*_ownership.cpp"))
+    assert len(programs) == 5
+    for p in programs:
+        assert "rls_device_alloc" not in p.read_text() and '#include "ownership_harness.hpp"' in p.read_text(), p.name
 
 
 def test_every_owning_class_is_constructed(rows):
@@ -50,12 +38,3 @@ def test_every_owning_class_is_constructed(rows):
         skin = 2 * shadows * rows["ShadowQueue Skin"]["n"] + 2 * ray + rows["ProbeQueue"]["n"] + 1
         assert rows[f"SkinNodeQueues lights {l}"]["n"] == skin
         assert rows[f"SkinBounceQueues lights {l}"]["n"] == skin + shadows * rows["ShadowQueue SkinScatter"]["n"]
-
-
-def test_nothing_is_live_after_destruction(rows):
-    assert {k: r["live"] for k, r in rows.items() if r["live"]} == {}
-
-
-def test_a_failing_allocation_throws_and_leaves_nothing_live(rows):
-    assert {k: r["silent"] for k, r in rows.items() if r["silent"]} == {}
-    assert {k: r["leaked"] for k, r in rows.items() if r["leaked"]} == {}

@@ -13,8 +13,8 @@ import subprocess
 import pytest
 
 from trace_abi_util import INVALID, ROOT, dynamic_symbols, put, refusals
-from walk_abi_util import (HEADER, WalkWorld, declared_walk_symbols, exported_walk_symbols, walk_declarations, walk_lib,  # noqa: F401
-                           walk_struct_members, walk_structs)
+from walk_abi_util import (ACTIVE, HEADER, LIST_IN, LIST_OUT, WalkWorld, declared_walk_symbols, exported_walk_symbols,  # noqa: F401
+                           walk_declarations, walk_lib, walk_struct_members, walk_structs)
 
 ARITY = dict(rls_walk_scratch_bytes=2, rls_walk_begin=4, rls_walk_step=6, rls_walk_active=3)
 CONSTANTS = ("RLS_WALK_TRIALS", "RLS_WALK_FOREIGN_STOPS", "RLS_WALK_FOREIGN_SKIPS")
@@ -170,35 +170,19 @@ WALK = [
     ("hits.N NULL", lambda w: put(w.w.hits, "N", w.half3(w.capi.Vec3)), "walk.hits.count, walk.hits.P or walk.hits.N plane is NULL"),
     ("scratch NULL", lambda w: put(w.w, "scratch", None), "walk.scratch is NULL or smaller than rls_walk_scratch_bytes"),
     ("scratch short", lambda w: put(w.w, "scratch_bytes", w.w.scratch_bytes - 1), "walk.scratch is NULL or smaller than rls_walk_scratch_bytes"),
-    ("out NULL", lambda w: put(w, "outp", None), "out is NULL"),
-    ("out.count NULL", lambda w: put(w.lists[1], "count", None), "out.count is NULL"),
-    ("out.capacity short", lambda w: put(w.lists[1], "capacity", w.w.rays - 1), "out.capacity < walk.rays"),
-    ("out.trials NULL", lambda w: put(w.lists[1], "trials", None), "out.ray, out.origin, out.dir, out.maxdist or out.trials plane is NULL"),
-    ("out.dir NULL", lambda w: put(w.lists[1], "dir", w.half3(w.capi.Vec3)), "out.ray, out.origin, out.dir, out.maxdist or out.trials plane is NULL"),
 ]
-BEGIN = WALK + [
+BEGIN = WALK + LIST_OUT + [
     ("queue NULL", lambda w: put(w, "qp", None), "queue is NULL"),
     ("queue.capacity short", lambda w: put(w.q, "capacity", w.w.rays - 1), "queue.capacity < walk.rays"),
     ("queue.maxdist NULL", lambda w: put(w.q, "maxdist", None), "queue.origin, queue.dir or queue.maxdist plane is NULL"),
     ("queue.origin NULL", lambda w: put(w.q, "origin", w.half3(w.capi.Vec3)), "queue.origin, queue.dir or queue.maxdist plane is NULL"),
 ]
-STEP = WALK + [
-    ("in NULL", lambda w: put(w, "inp", None), "in is NULL"),
-    ("in.count NULL", lambda w: put(w.lists[0], "count", None), "in.count is NULL"),
-    ("in.capacity short", lambda w: put(w.lists[0], "capacity", w.w.rays - 1), "in.capacity < walk.rays"),
-    ("in.ray NULL", lambda w: put(w.lists[0], "ray", None), "in.ray, in.origin, in.dir, in.maxdist or in.trials plane is NULL"),
-    ("out is in", lambda w: put(w, "outp", w.inp), "out is in: a step reads one list and writes the other"),
+STEP = WALK + LIST_OUT + LIST_IN + [
     ("found NULL", lambda w: put(w, "fp", None), "found is NULL"),
     ("found.hit NULL", lambda w: put(w.f, "hit", None), "found.hit, found.t, found.P, found.N or found.Ns plane is NULL"),
     ("found.Ns NULL", lambda w: put(w.f, "Ns", w.half3(w.capi.CVec3)), "found.hit, found.t, found.P, found.N or found.Ns plane is NULL"),
     ("own without object", lambda w: put(w.w, "own", w.p), "walk.own and found.object must be both set or both NULL"),
     ("object without own", lambda w: put(w.f, "object", w.p), "walk.own and found.object must be both set or both NULL"),
-]
-ACTIVE = [
-    ("ctx NULL", lambda w: put(w, "ctxp", None), "ctx is NULL"),
-    ("rays NULL", lambda w: put(w, "inp", None), "rays or rays.count is NULL"),
-    ("rays.count NULL", lambda w: put(w.lists[0], "count", None), "rays or rays.count is NULL"),
-    ("host_count NULL", lambda w: put(w, "hostp", None), "host_count is NULL"),
 ]
 
 

@@ -2,51 +2,24 @@
 one of them fails.
 
 tests/native/walk_ownership.cpp is built as an integrator builds against the header (g++ -std=c++14 -Wall, here with the address
-and undefined-behaviour sanitizers: a stand-alone host program) but links no library: it defines rls_device_alloc / rls_device_free
-over malloc, counting live blocks and failing the k-th call.  It constructs the walk with and without rays and at two max_hits:
-once unhindered -- N allocations, none live after destruction -- and once per k in 1..N with the k-th allocation failing -- an
-rlsb::Error, none live."""
+and undefined-behaviour sanitizers: a stand-alone host program) but links no library: with ownership_harness.hpp it defines
+rls_device_alloc / rls_device_free over malloc, counting live blocks and failing the k-th call.  It constructs the walk with and
+without rays and at two max_hits: once unhindered -- N allocations, none live after destruction -- and once per k in 1..N with
+the k-th allocation failing -- an rlsb::Error, none live."""
 import re
-import subprocess
-from pathlib import Path
 
-import pytest
+from ownership_util import (HOST, rows_of, test_a_failing_allocation_throws_and_leaves_nothing_live,  # noqa: F401
+                            test_nothing_is_live_after_destruction)
 
-ROOT = Path(__file__).resolve().parent.parent
-DRIVER = ROOT / "tests" / "native" / "walk_ownership.cpp"
-HEADER = ROOT / "rlshaders_amd" / "host" / "rls_walk.hpp"
+HEADER = HOST / "rls_walk.hpp"
 
-
-@pytest.fixture(scope="module")
-def rows(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("walk_ownership") / "walk_ownership"
-    cmd = ["g++", "-std=c++14", "-Wall", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{ROOT / 'include'}",
-           f"-I{ROOT / 'rlshaders_amd' / 'host'}", str(DRIVER), "-o", str(exe)]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout + p.stderr
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, p.stdout + p.stderr
-    out = {}
-    for line in p.stdout.splitlines():
-        name, n, live, leaked, silent = line.split("\t")
-        out[name] = dict(n=int(n), live=int(live), leaked=[int(k) for k in leaked.split(",") if k],
-                         silent=[int(k) for k in silent.split(",") if k])
-    return out
+rows = rows_of("walk_ownership", sanitize=True)
 
 
 def test_the_walk_is_constructed_in_every_form(rows):
     assert set(rows) == {f"ProbeWalk rays {r} max_hits {m}" for r in (20, 0) for m in (12, 1)}
     # two lists of 10 buffers (count, ray, origin[3], dir[3], maxdist, trials), the hits' count and 6 planes, the scratch
     assert {r["n"] for r in rows.values()} == {2 * 10 + 7 + 1}
-
-
-def test_nothing_is_live_after_destruction(rows):
-    assert {k: r["live"] for k, r in rows.items() if r["live"]} == {}
-
-
-def test_a_failing_allocation_throws_and_leaves_nothing_live(rows):
-    assert {k: r["silent"] for k, r in rows.items() if r["silent"]} == {}
-    assert {k: r["leaked"] for k, r in rows.items() if r["leaked"]} == {}
 
 
 def test_one_owner_in_the_header():
