@@ -16,6 +16,11 @@
 // It also counts the nodes and triangles a ray visits on the refit tree and, where B is finite, on a tree rebuilt from B.
 // Prints one "ok pair: ..." line and exits 0, or the first differences and exits 1.  tests/test_nearest_refit_host.py drives
 // it, once more under -fsanitize=address,undefined.
+//
+//   nearest_refit_host_check tree <pair.bin> <leaf> <out.bin>
+//
+// writes the tree the builder makes on A -- the tree a scene on A holds: int64 nodes, nt; uint32 (first, meta)[nodes];
+// uint32 prim[nt] in leaf order; float (lo xyz, hi xyz)[nodes] -- what rls_nearest_refit_read_tree returns, without a device.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -328,11 +333,40 @@ int run_pair(const char *path, int64_t rays, int leaf)
     return 0;
 }
 
+// the tree the product's builder makes on A -- the tree a scene on A holds -- for the tests that need its links without a device
+int write_tree(const char *path, int leaf, const char *out)
+{
+    Pair p;
+    if (!read_pair(path, p)) { fprintf(stderr, "nearest_refit_host_check: %s is missing, short or malformed (A must be finite)\n", path); return 2; }
+    if (leaf < 1 || leaf > 8) { fprintf(stderr, "nearest_refit_host_check: leaf 1 .. 8\n"); return 2; }
+    NearestBvh built;
+    nearest_build(p.A.data(), p.T.data(), p.nt, leaf, built);
+    const int64_t head[2] = { (int64_t)built.nodes.size(), (int64_t)built.tris.size() };
+    std::vector<uint32_t> links, prims;
+    std::vector<float> boxes;
+    for (const NearestNode &n : built.nodes) {
+        links.push_back(n.first); links.push_back(n.meta);
+        for (int c = 0; c < 3; c++) boxes.push_back(n.lo[c]);
+        for (int c = 0; c < 3; c++) boxes.push_back(n.hi[c]);
+    }
+    for (const NearestTri &t : built.tris) prims.push_back(t.prim);
+    FILE *f = fopen(out, "wb");
+    bool ok = f && fwrite(head, sizeof(int64_t), 2, f) == 2;
+    ok = ok && fwrite(links.data(), sizeof(uint32_t), links.size(), f) == links.size();
+    ok = ok && fwrite(prims.data(), sizeof(uint32_t), prims.size(), f) == prims.size();
+    ok = ok && fwrite(boxes.data(), sizeof(float), boxes.size(), f) == boxes.size();
+    if (f) ok = fclose(f) == 0 && ok;
+    if (!ok) { fprintf(stderr, "nearest_refit_host_check: cannot write %s\n", out); return 2; }
+    printf("ok tree: nt %lld leaf %d depth %d nodes %lld\n", (long long)p.nt, leaf, built.depth, (long long)built.nodes.size());
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
+    if (argc == 5 && !strcmp(argv[1], "tree")) return write_tree(argv[2], atoi(argv[3]), argv[4]);
     if (argc == 4) return run_pair(argv[1], atoll(argv[2]), atoi(argv[3]));
-    fprintf(stderr, "usage: nearest_refit_host_check <pair.bin> <rays> <leaf>\n");
+    fprintf(stderr, "usage: nearest_refit_host_check <pair.bin> <rays> <leaf>\n       nearest_refit_host_check tree <pair.bin> <leaf> <out.bin>\n");
     return 2;
 }

@@ -106,8 +106,10 @@ def test_moved_meshes(ctx, name, leaf):
 @pytest.mark.parametrize("nt,leaf", [(0, 4), (1, 4), (1, 1), (5, 4), (9, 8), (2, 1), (5, 1), (6, 1), (7, 1), (9, 1), (257, 1), (600, 1)])
 def test_small_trees(ctx, nt, leaf):
     """nt = 0 and 1: the root is a leaf (or absent); nt = leaf + 1: one split; nt = 5, 6, 7, 9 at leaf 1: leaves on two levels;
-    nt = 257 at leaf 1: a level of exactly one workgroup's 256 nodes below the folded top; nt = 600 at leaf 1: a level list of
-    more than one workgroup's nodes"""
+    nt = 257 at leaf 1: levels of 1, 2, 4 .. 256 and 2 nodes, none above one workgroup's 256, so the whole tree is the folded
+    top and the single-workgroup launch meets a full level of 256 lanes with a level of 2 below it (the per-level kernel at
+    such levels: test_gpu_nearest_refit_edges.py, test_both_launch_plans); nt = 600 at leaf 1: a level list of more than one
+    workgroup's nodes"""
     from rlshaders_amd import nearest_refit
     s = U.soup(max(nt, 1), seed=100 + nt)
     a = U.Mesh(s.V, s.tri[:nt], surface=s.surface[:nt], normals=s.normals)

@@ -2,7 +2,12 @@
 capped at one workgroup per CU (RLS_BLOCKS_PER_CU=1) a grid mesh of 2.5 x compute_units x 256 + 77 triangles -- two and a half
 rounds of the record kernel and of the widest levels, a partial last tile -- at leaf 1 and leaf 4 gives the bytes of the default
 context and of a fresh scene, on a few thousand rays aimed at the moved mesh; `surface` and `bin` are intact (the update writes
-nothing outside the records and the boxes); a second update in the same stream, nothing synchronised between the two, lands."""
+nothing outside the records and the boxes); a second update in the same stream, nothing synchronised between the two, lands.
+
+Both launch plans of the update (refit.hip): a refit made under RLS_NEAREST_REFIT_FOLD=0 launches refit_level_kernel once per
+level up to the root, one made with the variable unset hands the top of the tree to refit_top_kernel.  On the trees of
+nearest_refit_util.PLAN_TREES -- level sizes asserted from the links read back -- the two give the same read tree == the numpy
+union and the same query bytes == nearest_np, after an update and after the update back."""
 import numpy as np
 import pytest
 import torch
@@ -10,8 +15,8 @@ import torch
 import rlshaders_amd as R
 import nearest_util as U
 from nearest_util import F
-from nearest_refit_util import levels_np, union_np
-from test_gpu_nearest import SCALAR, VEC, _bytes, _dev, _host, query
+from nearest_refit_util import PLAN_GRIDS, PLAN_TREES, levels_fast, levels_np, moved, profile_np, squashed, union_fast, union_np
+from test_gpu_nearest import SCALAR, VEC, _bytes, _dev, _host, check_found, query
 
 pytestmark = pytest.mark.gpu
 
@@ -129,3 +134,62 @@ def test_two_and_a_half_rounds_and_a_partial_last_tile(gpu_ctx, one_block_per_cu
     for s in (capped, plain, fresh_b, fresh_c):
         s.close()
 
+
+
+# ---- both launch plans -----------------------------------------------------------------------------------------------------------------
+def refit_under(scene, fold):
+    """a refit created with RLS_NEAREST_REFIT_FOLD set to `fold`, or unset (None): the variable is read at creation"""
+    from rlshaders_amd import nearest_refit
+    mp = pytest.MonkeyPatch()
+    if fold is None:
+        mp.delenv("RLS_NEAREST_REFIT_FOLD", raising=False)
+    else:
+        mp.setenv("RLS_NEAREST_REFIT_FOLD", fold)
+    try:
+        return nearest_refit.Refit(scene)
+    finally:
+        mp.undo()
+
+
+@pytest.mark.parametrize("nt,leaf", [(nt, 1) for nt in PLAN_TREES] + [(0, leaf) for leaf in PLAN_GRIDS])
+def test_both_launch_plans(gpu_ctx, nt, leaf):
+    """nt = 0: U.quad_grid(33).  The level sizes each tree was chosen for (PLAN_TREES) are the builder's, on the device as in
+    the CPU test of the host program's tree: no nt had to be changed."""
+    from rlshaders_amd import nearest
+    from test_gpu_nearest_refit import rays_for
+    a = U.soup(nt) if nt else U.quad_grid(33)
+    b = moved(a, squashed(a, 3))
+    rays = rays_for(a, b, 96, 1000 + nt)
+    ha, hb = U.nearest_np(a, *rays), U.nearest_np(b, *rays)
+    n = rays[1].shape[1]
+    # (triangle 0 of a soup is degenerate: of 1 triangle next to nothing hits, of 2 a fifth of the rays)
+    assert hb.hit.mean() >= (0.0 if nt == 1 else 0.1 if nt == 2 else 0.25), hb.hit.mean()
+    make = lambda: nearest.Scene(gpu_ctx, a.V, a.tri, surface=a.surface, normals=a.normals, leaf_size=leaf)
+    level_scene, top_scene = make(), make()
+    by_level, by_top = refit_under(level_scene, "0"), refit_under(top_scene, None)
+    boxes0, links0, prims0 = by_level.read_tree()
+    assert profile_np(links0) == (PLAN_TREES[nt] if nt else PLAN_GRIDS[leaf])
+    assert np.array_equal(levels_fast(links0), levels_np(links0))
+    assert np.array_equal(boxes0, union_np(boxes0, links0, prims0, a.V, a.tri))
+
+    def bytes_of(scene, h, what):
+        f, last, _ = query(gpu_ctx, scene, *rays, bin_table=BINS)
+        check_found(f, h, n, (nt, leaf, what), bin_table=BINS)
+        return _bytes(f, NAMES) + [_host(last)]
+
+    for V, h, what in ((b.V, hb, "updated"), (a.V, ha, "back")):
+        parked = torch.full((2,), 77, dtype=torch.int64, device="cuda")
+        by_level.update(_dev(V), parked=parked[:1])
+        by_top.update(_dev(V), parked=parked[1:])
+        trees = by_level.read_tree(), by_top.read_tree()
+        for x, y in zip(*trees):
+            assert np.array_equal(x, y), (nt, leaf, what, "the two plans' trees differ")
+        boxes, links, prims = trees[0]
+        assert np.array_equal(links, links0) and np.array_equal(prims, prims0)
+        want = union_np(boxes, links, prims, V, a.tri)
+        assert np.array_equal(boxes, want) and np.array_equal(union_fast(boxes, links, prims, V, a.tri), want), (nt, leaf, what)
+        assert _host(parked).tolist() == [0, 0]
+        for x, y in zip(bytes_of(level_scene, h, what + ", a launch a level"), bytes_of(top_scene, h, what + ", the top folded")):
+            assert np.array_equal(x, y), (nt, leaf, what, "the two plans' bytes differ")
+    assert np.array_equal(boxes, boxes0)
+    by_level.close(), by_top.close(), level_scene.close(), top_scene.close()

@@ -13,9 +13,9 @@ rows = rows_of("trace_queue_ownership", sanitize=False)
 
 
 def test_the_counting_allocator_is_written_once():
-    """in ownership_harness.hpp, for this program and the four after its pattern"""
+    """in ownership_harness.hpp, for this program and the five after its pattern"""
     programs = sorted((ROOT / "tests" / "native").glob("*_ownership.cpp"))
-    assert len(programs) == 5
+    assert len(programs) == 6
     for p in programs:
         assert "rls_device_alloc" not in p.read_text() and '#include "ownership_harness.hpp"' in p.read_text(), p.name
 
