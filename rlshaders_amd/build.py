@@ -151,6 +151,7 @@ SHADOW_WALK_HEADERS = [*sorted(SHADOW_WALK_CSRC.glob("*.hpp")), INCLUDE / "rlsha
 NEAREST_HEADERS = [NEAREST_CSRC / "rls_nearest_device.hpp", NEAREST_CSRC / "rls_nearest_bvh.hpp", NEAREST_CSRC / "rls_nearest_scene.hpp",
                    INCLUDE / "rlshaders_amd_nearest.h", INCLUDE / "rlshaders_amd_walk.h", INCLUDE / "rlshaders_amd_trace.h"]
 NEAREST_REFIT_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", INCLUDE / "rlshaders_amd_nearest_refit.h"]
+NEAREST_REBUILD_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", NEAREST_CSRC / "rls_nearest_rebuild.hpp", INCLUDE / "rlshaders_amd_nearest_rebuild.h"]
 
 COMPANIONS = {c.name: c for c in (
     # BASELINE config 2's kernel with one uniform-slope pass per workgroup, handed the streamed EXACT reflect+refract launches
@@ -170,9 +171,13 @@ COMPANIONS = {c.name: c for c in (
     # moving meshes (include/rlshaders_amd_nearest_refit.h): it reads a scene of librls_nearest.so through the private header
     # csrc_nearest/rls_nearest_scene.hpp and calls nothing of that library
     Companion("nearest_refit", "nearest_refit", NEAREST_CSRC, ["refit.hip"], NEAREST_HEADERS + NEAREST_REFIT_HEADERS),
+    # rebuilding a scene's tree for a moved mesh (include/rlshaders_amd_nearest_rebuild.h): the scene through the same private
+    # header, the records and boxes through the refit's kernel header; it calls nothing of either library
+    Companion("nearest_rebuild", "nearest_rebuild", NEAREST_CSRC, ["rebuild.hip"], NEAREST_HEADERS + NEAREST_REBUILD_HEADERS),
 )}
 RR_LIB, TRACE_LIB, WALK_LIB = COMPANIONS["ggx_rr"].lib, COMPANIONS["trace"].lib, COMPANIONS["walk"].lib
 SHADOW_WALK_LIB, NEAREST_LIB, NEAREST_REFIT_LIB = COMPANIONS["shadow_walk"].lib, COMPANIONS["nearest"].lib, COMPANIONS["nearest_refit"].lib
+NEAREST_REBUILD_LIB = COMPANIONS["nearest_rebuild"].lib
 
 
 def build_companion(name: str, force: bool = False, verbose: bool = False) -> Path:
@@ -217,6 +222,10 @@ def build_nearest_refit_library(force: bool = False, verbose: bool = False) -> P
     return build_companion("nearest_refit", force, verbose)
 
 
+def build_nearest_rebuild_library(force: bool = False, verbose: bool = False) -> Path:
+    return build_companion("nearest_rebuild", force, verbose)
+
+
 def _link_flags(libs) -> list:
     return [f"-L{LIBDIR}", *[f"-l{l}" for l in libs], "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
 
@@ -258,6 +267,11 @@ def build_nearest_example(verbose: bool = False, name: str = "example_nearest") 
 def build_nearest_refit_example(verbose: bool = False, name: str = "example_nearest_refit") -> Path:
     """a sphere squashed and moved over three frames, walked on the refit scene and on a fresh one"""
     return build_example(name, ["nearest_refit", "nearest", "shadow_walk", "walk", "trace"], verbose)
+
+
+def build_nearest_rebuild_example(verbose: bool = False, name: str = "example_nearest_rebuild") -> Path:
+    """a sphere twisted, its tree rebuilt on the device, walked on the rebuilt scene and on a fresh one"""
+    return build_example(name, ["nearest_rebuild", "nearest", "shadow_walk", "walk", "trace"], verbose)
 
 
 def build_nearest_stats(verbose: bool = False) -> Path:

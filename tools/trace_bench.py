@@ -82,6 +82,14 @@ the build, the upload and a synchronise, the median of 3 -- at the --level icosp
 calls, device events.  "queries": --closure nearest's coherent and incoherent streams of 2^log2n rays on the tree refit to the
 icosphere twisted by 0.5 and by 2 radians and on a tree rebuilt from the twisted vertices, and their ratio; same_as_refit: the two
 trees' hit and t planes are the same bytes.  --spp-n is not read.
+--closure nearest-rebuild: the tree rebuilt on the device (rlshaders_amd.nearest_rebuild, librls_nearest_rebuild.so), on the two
+meshes of --closure nearest-refit.  "update": Rebuild.update on device vertices (the mesh twisted by 0.5 radians) beside
+Refit.update on the same vertices, each the median, fastest and slowest of at least 9 calls after 3 warm-up calls, device events,
+and beside nearest.Scene(...) creation on them (the only rebuild there was: a host clock around the build, the upload and a
+synchronise, the median of 9 after 3); the launches of an update and the bytes of its working set.  "queries": --closure
+nearest's two streams after the 0.5 and the 2 radian twist on the refit tree, on the device-rebuilt tree and on a host-rebuilt
+one (a fresh scene); same_as_host_rebuilt: every found plane of the device-rebuilt tree's queries is the fresh scene's bytes.
+--spp-n is not read.
 """
 from __future__ import annotations
 
@@ -995,6 +1003,119 @@ def bench_nearest_refit(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> 
         r.close(), kept.close(), rebuilt.close()
 
 
+def bench_nearest_rebuild(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """rls_nearest_rebuild_update beside rls_nearest_refit_update and nearest.Scene(...) creation on the same vertices, at the
+    81 920-triangle icosphere and at a 2^20-triangle grid; then --closure nearest's two streams on the refit, the device-rebuilt
+    and the host-rebuilt tree, for the icosphere twisted about y by 0.5 and by 2 radians end to end"""
+    import time
+
+    import numpy as np
+    import torch
+    from rlshaders_amd import nearest, nearest_rebuild, nearest_refit
+    nearest_refit.load(), nearest_rebuild.load()
+    repeats, warmup = max(args.repeats, 9), max(args.warmup, 3)
+    dev = ctx.torch_device
+
+    def twisted(V, radians):
+        V = np.asarray(V, np.float64)
+        a = radians * (V[:, 1] - V[:, 1].min()) / np.ptp(V[:, 1])
+        c, s = np.cos(a), np.sin(a)
+        return np.stack([c * V[:, 0] + s * V[:, 2], V[:, 1], -s * V[:, 0] + c * V[:, 2]], 1).astype(np.float32)
+
+    def grid(side):
+        g = np.linspace(-1.0, 1.0, side + 1)
+        x, y = np.meshgrid(g, g, indexing="xy")
+        V = np.stack([x, y, 0.1 * np.sin(3.0 * x) * np.cos(2.0 * y)], axis=-1).reshape(-1, 3).astype(np.float32)
+        j, i = np.divmod(np.arange(side * side, dtype=np.int64), side)
+        a = j * (side + 1) + i
+        return V, np.stack([a, a + 1, a + side + 2, a, a + side + 2, a + side + 1], axis=1).reshape(-1, 3).astype(np.uint32)
+
+    V6, tri6, _ = icosphere(args.level)
+    Vg, trig = grid(724)                                             # 2 * 724^2 = 1 048 352 triangles
+    rec["update"] = {}
+    for name, V, tri in (("icosphere", V6, tri6), ("grid", Vg, trig)):
+        moved = twisted(V, 0.5)
+        scene = nearest.Scene(ctx, V, tri)
+        dv = torch.from_numpy(moved).to(dev)
+        rb, rf = nearest_rebuild.Rebuild(scene), nearest_refit.Refit(scene)
+        levels = rb.levels
+        out = {"triangles": scene.nt, "nodes": scene.nodes, "depth": scene.depth, "device_bytes": rb.device_bytes,
+               "device_bytes_per_triangle": round(rb.device_bytes / max(scene.nt, 1), 1),
+               # init; a pass of the sort: count, three of the scan, scatter; a round: mark, three of the scan, partition;
+               # the leaves; the records; a level of boxes each
+               "launches": 1 + (8 * 5 + (levels - 1) * 5 if levels > 1 else 0) + 2 + levels}
+        # the two updates alternate, twice: the spread between the passes is beside the difference
+        for _ in range(2):
+            out.setdefault("rebuild", []).append(timed_spread(lambda: rb.update(dv), repeats, warmup))
+            out.setdefault("refit", []).append(timed_spread(lambda: rf.update(dv), repeats, warmup))
+        create = []
+        for k in range(repeats + warmup):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            s2 = nearest.Scene(ctx, moved, tri)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                create.append((time.perf_counter() - t0) * 1e3)
+            s2.close()
+        create.sort()
+        out["create_ms"] = {"ms": round(create[len(create) // 2], 2), "min_ms": round(create[0], 2), "max_ms": round(create[-1], 2)}
+        out["create_over_rebuild"] = round(out["create_ms"]["ms"] / out["rebuild"][0]["ms"], 1)
+        out["rebuild_over_refit"] = round(out["rebuild"][0]["ms"] / out["refit"][0]["ms"], 1)
+        rec["update"][name] = out
+        rb.close(), rf.close(), scene.close()
+
+    # query cost: the refit tree, the device-rebuilt tree, the host-rebuilt tree
+    side = int(round(n ** 0.5))
+    n = side * side
+    g = torch.Generator(device=dev).manual_seed(seed)
+    u = (torch.arange(side, device=dev, dtype=torch.float32) + 0.5) / side * 1.3 - 0.65
+    d = torch.stack([u.repeat(side), u.repeat_interleave(side), torch.ones(n, device=dev)]).contiguous()
+    o = torch.tensor([0.0, 0.0, -3.0], device=dev)[:, None].expand(3, n).contiguous()
+    planes = ("P", "N", "Ns", "surface", "prim")
+    rec["queries"] = {"rays": n}
+    for radians in (0.5, 2.0):
+        moved = twisted(V6, radians)
+        dv = torch.from_numpy(moved).to(dev)
+        kept, turned = nearest.Scene(ctx, V6, tri6), nearest.Scene(ctx, V6, tri6)
+        rf, rb = nearest_refit.Refit(kept), nearest_rebuild.Rebuild(turned)
+        rf.update(dv)
+        rb.update(dv)
+        fresh = nearest.Scene(ctx, moved, tri6)
+        out, streams, results = {}, None, {}
+        for name, scene in (("refit", kept), ("device_rebuilt", turned), ("host_rebuilt", fresh)):
+            found = nearest.Found(ctx, n, planes=planes, alloc=lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev))
+            rays = nearest.Rays(o, d)
+            scene.hits(rays, found=found)
+            if streams is None:                                      # the incoherent stream: from the hits, as --closure nearest
+                hit = found.hit.bool()
+                Pn = torch.randn(3, n, generator=g, device=dev)
+                Pn = Pn / Pn.norm(dim=0)
+                O2 = torch.where(hit[None, :], found.P, Pn).contiguous()
+                w = torch.randn(3, n, generator=g, device=dev)
+                d2 = (-(O2 / O2.norm(dim=0)) + 0.999 * w / w.norm(dim=0)).contiguous()
+                last0 = torch.where(hit, found.prim, torch.full_like(found.prim, -1)).contiguous()
+                streams = (O2, d2, last0)
+            O2, d2, last0 = streams
+            last = last0.clone()
+            rays2 = nearest.Rays(O2, d2)
+            found2 = nearest.Found(ctx, n, planes=planes, alloc=lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev))
+
+            def incoherent():
+                last.copy_(last0)
+                scene.hits(rays2, last=last, found=found2)
+
+            out[name] = {"coherent": timed_spread(lambda: scene.hits(rays, found=found), repeats, warmup),
+                         "incoherent": timed_spread(incoherent, repeats, warmup), "hits": int(found.hit.sum(dtype=torch.int64).item())}
+            results[name] = [getattr(f, k).clone() for f in (found, found2) for k in ("hit", "t") + planes] + [last.clone()]
+        out["device_rebuilt"]["same_as_host_rebuilt"] = all(
+            torch.equal(x.view(torch.uint8), y.view(torch.uint8)) for x, y in zip(results["device_rebuilt"], results["host_rebuilt"]))
+        for stream in ("coherent", "incoherent"):
+            out[f"{stream}_refit_over_device_rebuilt"] = round(out["refit"][stream]["ms"] / out["device_rebuilt"][stream]["ms"], 3)
+            out[f"{stream}_device_over_host_rebuilt"] = round(out["device_rebuilt"][stream]["ms"] / out["host_rebuilt"][stream]["ms"], 3)
+        rec["queries"][f"twist_{radians}"] = out
+        rf.close(), rb.close(), kept.close(), turned.close(), fresh.close()
+
+
 def bench_shadow_walk_nearest(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
     """a whole shadow walk with its queries inside the events: n rays from the unit cube through three nested tinted icospheres
     (3 x 5 120 triangles, radii 2, 3, 4), every step = rls_nearest_walk_hits + rls_shadow_walk_step"""
@@ -1124,7 +1245,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
     ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
-                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk", "nearest", "nearest-refit"),
+                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk", "nearest", "nearest-refit", "nearest-rebuild"),
                     default="ggx")
     ap.add_argument("--mix", choices=("even", "skewed", "one"), default="even", help="route: the rays' split over 3 bins and the misses")
     ap.add_argument("--state", choices=("camera", "secondary", "half", "diffuse"), default="camera",
@@ -1156,7 +1277,7 @@ def main() -> None:
         rec["closure"] = args.closure
         {"disney": bench_disney, "sss": bench_sss, "sss-walk": bench_sss_walk, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
          "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce,
-         "shadow-fold": bench_shadow_fold, "route": bench_route, "nearest": bench_nearest, "nearest-refit": bench_nearest_refit,
+         "shadow-fold": bench_shadow_fold, "route": bench_route, "nearest": bench_nearest, "nearest-refit": bench_nearest_refit, "nearest-rebuild": bench_nearest_rebuild,
          "shadow-walk": bench_shadow_walk_nearest if args.tracer == "nearest" else bench_shadow_walk}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
