@@ -150,8 +150,9 @@ WALK_HEADERS = [*sorted(WALK_CSRC.glob("*.hpp")), INCLUDE / "rlshaders_amd_walk.
 SHADOW_WALK_HEADERS = [*sorted(SHADOW_WALK_CSRC.glob("*.hpp")), INCLUDE / "rlshaders_amd_shadow_walk.h", INCLUDE / "rlshaders_amd_walk.h"]
 NEAREST_HEADERS = [NEAREST_CSRC / "rls_nearest_device.hpp", NEAREST_CSRC / "rls_nearest_bvh.hpp", NEAREST_CSRC / "rls_nearest_scene.hpp",
                    INCLUDE / "rlshaders_amd_nearest.h", INCLUDE / "rlshaders_amd_walk.h", INCLUDE / "rlshaders_amd_trace.h"]
-NEAREST_REFIT_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", INCLUDE / "rlshaders_amd_nearest_refit.h"]
-NEAREST_REBUILD_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", NEAREST_CSRC / "rls_nearest_rebuild.hpp", INCLUDE / "rlshaders_amd_nearest_rebuild.h"]
+NEAREST_REFIT_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", NEAREST_CSRC / "rls_nearest_update.hpp", INCLUDE / "rlshaders_amd_nearest_refit.h"]
+NEAREST_REBUILD_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", NEAREST_CSRC / "rls_nearest_update.hpp", NEAREST_CSRC / "rls_nearest_rebuild.hpp",
+                           INCLUDE / "rlshaders_amd_nearest_rebuild.h"]
 
 COMPANIONS = {c.name: c for c in (
     # BASELINE config 2's kernel with one uniform-slope pass per workgroup, handed the streamed EXACT reflect+refract launches
@@ -169,10 +170,10 @@ COMPANIONS = {c.name: c for c in (
     # header includes the probe walk's for the type of the walks' lists
     Companion("nearest", "nearest", NEAREST_CSRC, ["nearest.hip"], NEAREST_HEADERS),
     # moving meshes (include/rlshaders_amd_nearest_refit.h): it reads a scene of librls_nearest.so through the private header
-    # csrc_nearest/rls_nearest_scene.hpp and calls nothing of that library
+    # csrc_nearest/rls_nearest_scene.hpp and calls nothing of that library; its host layer is csrc_nearest/rls_nearest_update.hpp
     Companion("nearest_refit", "nearest_refit", NEAREST_CSRC, ["refit.hip"], NEAREST_HEADERS + NEAREST_REFIT_HEADERS),
     # rebuilding a scene's tree for a moved mesh (include/rlshaders_amd_nearest_rebuild.h): the scene through the same private
-    # header, the records and boxes through the refit's kernel header; it calls nothing of either library
+    # header, the records and boxes through the refit's kernel header, the same host layer; it calls nothing of either library
     Companion("nearest_rebuild", "nearest_rebuild", NEAREST_CSRC, ["rebuild.hip"], NEAREST_HEADERS + NEAREST_REBUILD_HEADERS),
 )}
 RR_LIB, TRACE_LIB, WALK_LIB = COMPANIONS["ggx_rr"].lib, COMPANIONS["trace"].lib, COMPANIONS["walk"].lib

@@ -266,6 +266,83 @@ class Scene:
         return found
 
 
+class MovingMesh:
+    """What the handles of the two moving-mesh libraries share (the box-only update's and the tree rebuild's module each subclass
+    it): the handle borrows a ``Scene`` and keeps a reference to it.  A subclass sets PREFIX (its entry points are PREFIX +
+    create, destroy, get_info, update, read_tree), load (its module's, a staticmethod) and Info and Mesh (its module's mirrors);
+    every field of Info but ``updates`` becomes an attribute."""
+    PREFIX = load = Info = Mesh = None
+
+    def __init__(self, scene: "Scene"):
+        self.scene, self.ctx = scene, scene.ctx
+        lib = self.load()                                            # the entry points looked up once: update is a hot call
+        self._entry = {verb: getattr(lib, self.PREFIX + verb) for verb in ("create", "destroy", "get_info", "update", "read_tree")}
+        h = C.c_void_p()
+        check(self._entry["create"](self.ctx.handle, scene.handle, C.byref(h)))
+        self.handle = h
+        self._held = ()
+        for k, v in self.info().items():
+            if k != "updates":
+                setattr(self, k, v)
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            h, self.handle = self.handle, None
+            check(self._entry["destroy"](h))
+        self.scene = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        i = self.Info()
+        check(self._entry["get_info"](self.handle, C.byref(i)))
+        return {k: bool(getattr(i, k)) if k == "has_normals" else getattr(i, k) for k, _ in self.Info._fields_}
+
+    def _plane(self, a, what: str) -> torch.Tensor:
+        """a device float32 [nv, 3], contiguous; a host array is uploaded (a copy: that path synchronises)"""
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 3)))
+        if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3 or a.shape[0] != self.nv:
+            raise ValueError(f"{what}: expected float32 [{self.nv}, 3]")
+        if not a.is_cuda:
+            a = a.to(self.ctx.torch_device)
+        if not a.is_contiguous():
+            raise ValueError(f"{what}: expected a contiguous tensor")
+        return a
+
+    def update(self, vertices, normals=None, parked: Optional[torch.Tensor] = None, ctx=None) -> Optional[torch.Tensor]:
+        """Move the scene to ``vertices`` on the context's stream (the subclass says what that does to the tree): device float32
+        tensors [nv, 3] (host arrays are uploaded first).  normals: None keeps the scene's; refused where the scene was made
+        without normals.  parked: an int64 device tensor of one element, written with the number of triangles parked, and
+        returned.  Neither synchronises nor allocates with device tensors, so it is recordable by ``ctx.capture()``; a replay
+        reads the tensors as they are then."""
+        ctx = self.ctx if ctx is None else ctx
+        V = self._plane(vertices, "vertices")
+        Nn = None if normals is None else self._plane(normals, "normals")
+        m = self.Mesh()
+        m.nv = self.nv
+        m.vertices = V.data_ptr() if self.nv else None
+        m.normals = None if Nn is None else (Nn.data_ptr() if self.nv else None)
+        if parked is not None:
+            m.parked = _flat(parked, 1, "parked", (torch.int64,))
+        check(self._entry["update"](ctx.handle, self.handle, C.byref(m)))
+        self._held = (V, Nn, parked)                                 # alive until the next update: the stream may still read them
+        return parked
+
+    def read_tree(self, ctx=None):
+        """-> (boxes float32 [nodes, 6] lo xyz hi xyz, links uint32 [nodes, 2] first, meta, prims uint32 [nt] the triangle ids
+        in leaf order), host arrays; synchronises."""
+        ctx = self.ctx if ctx is None else ctx
+        boxes, links = np.zeros((self.nodes, 6), np.float32), np.zeros((self.nodes, 2), np.uint32)
+        prims = np.zeros((self.nt,), np.uint32)
+        check(self._entry["read_tree"](ctx.handle, self.handle, boxes.ctypes.data, links.ctypes.data, prims.ctypes.data))
+        return boxes, links, prims
+
+
 class tracer:
     """A callable of the shape ``walk.run`` and ``shadow_walk.run`` take, ``tracer(rays, active) -> Found``, over a scene: the
     nearest hits of the listed rays, with ``last`` (one triangle id per queue ray, carried across the steps of a walk: a ray

@@ -14,14 +14,9 @@ cost can drift.  A triangle with a NaN or an infinity among its coordinates is p
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
-
-import numpy as np
-import torch
 
 from . import _capi as capi
 from . import nearest
-from ._capi import check
 
 NEAREST_REFIT_LIB_PATH = capi._PKG / "lib" / "librls_nearest_refit.so"
 
@@ -59,73 +54,7 @@ def load() -> C.CDLL:
     return _lib
 
 
-class Refit:
+class Refit(nearest.MovingMesh):
     """The refit of a ``nearest.Scene`` (rls_nearest_refit): it borrows the scene and keeps a reference to it.  Creation reads
-    the scene's tree once (it may synchronise)."""
-
-    def __init__(self, scene: "nearest.Scene"):
-        self.scene, self.ctx = scene, scene.ctx
-        h = C.c_void_p()
-        check(load().rls_nearest_refit_create(self.ctx.handle, scene.handle, C.byref(h)))
-        self.handle = h
-        self._held = ()
-        i = self.info()
-        self.nv, self.nt, self.nodes, self.levels, self.has_normals = i["nv"], i["nt"], i["nodes"], i["levels"], i["has_normals"]
-        self.device_bytes = i["device_bytes"]
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            h, self.handle = self.handle, None
-            check(load().rls_nearest_refit_destroy(h))
-        self.scene = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def info(self) -> dict:
-        i = NearestRefitInfo_()
-        check(load().rls_nearest_refit_get_info(self.handle, C.byref(i)))
-        return dict(nv=i.nv, nt=i.nt, nodes=i.nodes, levels=i.levels, has_normals=bool(i.has_normals), device_bytes=i.device_bytes,
-                    updates=i.updates)
-
-    def _plane(self, a, what: str) -> torch.Tensor:
-        """a device float32 [nv, 3], contiguous; a host array is uploaded (a copy: that path synchronises)"""
-        if not isinstance(a, torch.Tensor):
-            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 3)))
-        if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3 or a.shape[0] != self.nv:
-            raise ValueError(f"{what}: expected float32 [{self.nv}, 3]")
-        if not a.is_cuda:
-            a = a.to(self.ctx.torch_device)
-        if not a.is_contiguous():
-            raise ValueError(f"{what}: expected a contiguous tensor")
-        return a
-
-    def update(self, vertices, normals=None, parked: Optional[torch.Tensor] = None, ctx=None) -> Optional[torch.Tensor]:
-        """Move the scene to ``vertices`` on the context's stream: device float32 tensors [nv, 3] (host arrays are uploaded
-        first).  normals: None keeps the scene's; refused where the scene was made without normals.  parked: an int64 device
-        tensor of one element, written with the number of triangles parked, and returned.  Neither synchronises nor allocates
-        with device tensors, so it is recordable by ``ctx.capture()``; a replay reads the tensors as they are then."""
-        ctx = self.ctx if ctx is None else ctx
-        V = self._plane(vertices, "vertices")
-        Nn = None if normals is None else self._plane(normals, "normals")
-        m = NearestRefitMesh_()
-        m.nv = self.nv
-        m.vertices = V.data_ptr() if self.nv else None
-        m.normals = None if Nn is None else (Nn.data_ptr() if self.nv else None)
-        if parked is not None:
-            m.parked = nearest._flat(parked, 1, "parked", (torch.int64,))
-        check(load().rls_nearest_refit_update(ctx.handle, self.handle, C.byref(m)))
-        self._held = (V, Nn, parked)                                 # alive until the next update: the stream may still read them
-        return parked
-
-    def read_tree(self, ctx=None):
-        """-> (boxes float32 [nodes, 6] lo xyz hi xyz, links uint32 [nodes, 2] first, meta, prims uint32 [nt] the triangle ids
-        in leaf order), host arrays; synchronises."""
-        ctx = self.ctx if ctx is None else ctx
-        boxes, links = np.zeros((self.nodes, 6), np.float32), np.zeros((self.nodes, 2), np.uint32)
-        prims = np.zeros((self.nt,), np.uint32)
-        check(load().rls_nearest_refit_read_tree(ctx.handle, self.handle, boxes.ctypes.data, links.ctypes.data, prims.ctypes.data))
-        return boxes, links, prims
+    the scene's tree once (it may synchronise).  ``update`` rewrites the boxes of the tree that is there."""
+    PREFIX, Info, Mesh, load = "rls_nearest_refit_", NearestRefitInfo_, NearestRefitMesh_, staticmethod(load)

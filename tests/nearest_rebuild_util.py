@@ -2,7 +2,6 @@
 what include/rlshaders_amd_nearest_rebuild.h declares and librls_nearest_rebuild.so exports, valid arguments over dummy memory for
 the refusal table, the build and the runs of tests/native/nearest_rebuild_host_check.cpp, and the meshes of exactly nt triangles
 both the CPU and the GPU tests rebuild.  pytest does not collect this module."""
-import ctypes as C
 import re
 import subprocess
 from pathlib import Path
@@ -11,9 +10,10 @@ import numpy as np
 import pytest
 
 import nearest_util as U
+from nearest_abi_util import MovingWorld, exported_symbols, header_abi, scene_layout_tag  # noqa: F401
 from nearest_util import F
-from nearest_refit_util import run_tree, scene_layout_tag, write_pair  # noqa: F401
-from trace_abi_util import ROOT, Dummies, code_text, dynamic_symbols
+from nearest_refit_util import run_tree, write_pair  # noqa: F401
+from trace_abi_util import ROOT
 
 HEADER = ROOT / "include" / "rlshaders_amd_nearest_rebuild.h"
 SOURCE = ROOT / "tests" / "native" / "nearest_rebuild_host_check.cpp"
@@ -34,68 +34,12 @@ def rebuild_lib():
     return build.build_nearest_rebuild_library()
 
 
-# ---- the header --------------------------------------------------------------------------------------------------------------------
-def declared_symbols():
-    return sorted(set(re.findall(r"\b(rls_[a-z0-9_]+)\s*\(", code_text(HEADER))))
+# ---- the header, the dummy-memory world (nearest_abi_util.py) ----------------------------------------------------------------------
+declared_symbols, declarations, structs, struct_members = header_abi(HEADER, "rls_nearest_rebuild_")
 
 
-def declarations():
-    """entry point -> its parameter list"""
-    return {m.group(1): m.group(2)
-            for m in re.finditer(r"rls_status\s+(rls_nearest_rebuild_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", code_text(HEADER), flags=re.S)}
-
-
-def exported_symbols(lib):
-    return sorted(l.split()[-1] for l in dynamic_symbols(lib).splitlines() if l.split() and l.split()[-1].startswith("rls_"))
-
-
-def structs():
-    return re.findall(r"typedef struct (\w+)\s*\{", code_text(HEADER))
-
-
-def struct_members(c_name):
-    body = re.search(r"typedef struct %s\s*\{(.*?)\}\s*%s;" % (c_name, c_name), code_text(HEADER), flags=re.S).group(1)
-    return [re.search(r"(\w+)\s*$", part.strip()).group(1) for d in body.split(";") if d.strip() for part in d.split(",")]
-
-
-class RebuildWorld(Dummies):
-    """valid arguments of every entry point over dummy memory.  The scene is 4 KiB that start with this build's layout tag and
-    device 0 (the dummy context's); the rebuild is 4 KiB that start with a public info struct of 3 vertices with normals and
-    device 0 -- the two structs lead with just these members (csrc_nearest/rls_nearest_scene.hpp, rebuild.hip), so every check
-    is reached; a refused call reads nothing else."""
-
-    def __init__(self):
-        super().__init__()
-        from rlshaders_amd import nearest_rebuild
-        self.mod, self.rlib = nearest_rebuild, nearest_rebuild.load()
-        self.scene = C.create_string_buffer(4096)
-        C.c_uint64.from_buffer(self.scene, 0).value = scene_layout_tag()
-        self.rebuild = C.create_string_buffer(4096)
-        self.rebuild_info = nearest_rebuild.NearestRebuildInfo_.from_buffer(self.rebuild, 0)
-        self.rebuild_info.nv, self.rebuild_info.nt, self.rebuild_info.has_normals = 3, 1, 1
-        self.mesh = nearest_rebuild.NearestRebuildMesh_(3, self.p, self.p, self.p)
-        self.out = C.c_void_p()
-        self.info = nearest_rebuild.NearestRebuildInfo_()
-        self.scenep, self.rebuildp = C.addressof(self.scene), C.addressof(self.rebuild)
-        self.meshp, self.outp, self.infop = C.byref(self.mesh), C.byref(self.out), C.byref(self.info)
-
-    def scene_device(self, device):
-        C.c_int.from_buffer(self.scene, 8).value = device
-
-    def rebuild_device(self, device):
-        C.c_int.from_buffer(self.rebuild, C.sizeof(self.mod.NearestRebuildInfo_)).value = device
-
-    def create(self):
-        return self.rlib.rls_nearest_rebuild_create(self.ctxp, self.scenep, self.outp)
-
-    def update(self):
-        return self.rlib.rls_nearest_rebuild_update(self.ctxp, self.rebuildp, self.meshp)
-
-    def get_info(self):
-        return self.rlib.rls_nearest_rebuild_get_info(self.rebuildp, self.infop)
-
-    def read_tree(self):
-        return self.rlib.rls_nearest_rebuild_read_tree(self.ctxp, self.rebuildp, self.p, self.p, self.p)
+class RebuildWorld(MovingWorld):
+    NOUN = "rebuild"
 
 
 # ---- the host check ------------------------------------------------------------------------------------------------------------------

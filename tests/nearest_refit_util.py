@@ -3,7 +3,6 @@ include/rlshaders_amd_nearest_refit.h declares and librls_nearest_refit.so expor
 refusal table, the build and the pair files of tests/native/nearest_refit_host_check.cpp, the moved meshes, and the numpy
 bottom-up union a read tree is held to (node by node, and a frontier a level for trees of millions of nodes).  pytest does not
 collect this module."""
-import ctypes as C
 import re
 import subprocess
 from pathlib import Path
@@ -12,11 +11,11 @@ import numpy as np
 import pytest
 
 import nearest_util as U
+from nearest_abi_util import SCENE_HEADER, MovingWorld, exported_symbols, header_abi, scene_layout_tag  # noqa: F401
 from nearest_util import F
-from trace_abi_util import ROOT, Dummies, code_text, dynamic_symbols
+from trace_abi_util import ROOT
 
 HEADER = ROOT / "include" / "rlshaders_amd_nearest_refit.h"
-SCENE_HEADER = ROOT / "rlshaders_amd" / "csrc_nearest" / "rls_nearest_scene.hpp"
 SOURCE = ROOT / "tests" / "native" / "nearest_refit_host_check.cpp"
 FLAGS = ["-std=c++14", "-Wall", "-Werror", "-ffp-contract=off", "-pthread"]
 COUNT_MASK = 0xFF
@@ -28,73 +27,12 @@ def refit_lib():
     return build.build_nearest_refit_library()
 
 
-# ---- the header --------------------------------------------------------------------------------------------------------------------
-def declared_symbols():
-    return sorted(set(re.findall(r"\b(rls_[a-z0-9_]+)\s*\(", code_text(HEADER))))
+# ---- the header, the dummy-memory world (nearest_abi_util.py) ----------------------------------------------------------------------
+declared_symbols, declarations, structs, struct_members = header_abi(HEADER, "rls_nearest_refit_")
 
 
-def declarations():
-    """entry point -> its parameter list"""
-    return {m.group(1): m.group(2)
-            for m in re.finditer(r"rls_status\s+(rls_nearest_refit_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", code_text(HEADER), flags=re.S)}
-
-
-def exported_symbols(lib):
-    return sorted(l.split()[-1] for l in dynamic_symbols(lib).splitlines() if l.split() and l.split()[-1].startswith("rls_"))
-
-
-def structs():
-    return re.findall(r"typedef struct (\w+)\s*\{", code_text(HEADER))
-
-
-def struct_members(c_name):
-    body = re.search(r"typedef struct %s\s*\{(.*?)\}\s*%s;" % (c_name, c_name), code_text(HEADER), flags=re.S).group(1)
-    return [re.search(r"(\w+)\s*$", part.strip()).group(1) for d in body.split(";") if d.strip() for part in d.split(",")]
-
-
-def scene_layout_tag():
-    """kNearestSceneLayout, from the private header"""
-    return int(re.search(r"kNearestSceneLayout\s*=\s*(0x[0-9a-fA-F]+)ull", SCENE_HEADER.read_text()).group(1), 16)
-
-
-class RefitWorld(Dummies):
-    """valid arguments of every entry point over dummy memory.  The scene is 4 KiB that start with this build's layout tag and
-    device 0 (the dummy context's); the refit is 4 KiB that start with a public info struct of 3 vertices with normals and
-    device 0 -- the two structs lead with just these members (csrc_nearest/rls_nearest_scene.hpp, refit.hip), so every check
-    is reached; a refused call reads nothing else."""
-
-    def __init__(self):
-        super().__init__()
-        from rlshaders_amd import nearest_refit
-        self.mod, self.rlib = nearest_refit, nearest_refit.load()
-        self.scene = C.create_string_buffer(4096)
-        C.c_uint64.from_buffer(self.scene, 0).value = scene_layout_tag()
-        self.refit = C.create_string_buffer(4096)
-        self.refit_info = nearest_refit.NearestRefitInfo_.from_buffer(self.refit, 0)
-        self.refit_info.nv, self.refit_info.nt, self.refit_info.has_normals = 3, 1, 1
-        self.mesh = nearest_refit.NearestRefitMesh_(3, self.p, self.p, self.p)
-        self.out = C.c_void_p()
-        self.info = nearest_refit.NearestRefitInfo_()
-        self.scenep, self.refitp = C.addressof(self.scene), C.addressof(self.refit)
-        self.meshp, self.outp, self.infop = C.byref(self.mesh), C.byref(self.out), C.byref(self.info)
-
-    def scene_device(self, device):
-        C.c_int.from_buffer(self.scene, 8).value = device
-
-    def refit_device(self, device):
-        C.c_int.from_buffer(self.refit, C.sizeof(self.mod.NearestRefitInfo_)).value = device
-
-    def create(self):
-        return self.rlib.rls_nearest_refit_create(self.ctxp, self.scenep, self.outp)
-
-    def update(self):
-        return self.rlib.rls_nearest_refit_update(self.ctxp, self.refitp, self.meshp)
-
-    def get_info(self):
-        return self.rlib.rls_nearest_refit_get_info(self.refitp, self.infop)
-
-    def read_tree(self):
-        return self.rlib.rls_nearest_refit_read_tree(self.ctxp, self.refitp, self.p, self.p, self.p)
+class RefitWorld(MovingWorld):
+    NOUN = "refit"
 
 
 # ---- the host check ------------------------------------------------------------------------------------------------------------------

@@ -15,9 +15,10 @@ import subprocess
 
 import pytest
 
+from nearest_abi_util import UPDATE_LAYER, compiled_layout, host_layer, refusal_tables
 from nearest_rebuild_util import (HEADER, RebuildWorld, declarations, declared_symbols, exported_symbols, rebuild_lib,  # noqa: F401
-                                  scene_layout_tag, struct_members, structs)
-from trace_abi_util import ROOT, dynamic_symbols, put, refusals
+                                  struct_members, structs)
+from trace_abi_util import ROOT, dynamic_symbols, refusals
 
 ARITY = dict(rls_nearest_rebuild_create=3, rls_nearest_rebuild_destroy=1, rls_nearest_rebuild_get_info=2, rls_nearest_rebuild_update=3,
              rls_nearest_rebuild_read_tree=5)
@@ -39,20 +40,7 @@ def mirrors():
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory):
     """what the C compiler says: sizeof of every struct of the header, offsetof of every member"""
-    tmp = tmp_path_factory.mktemp("probe")
-    lines = []
-    for c_name in structs():
-        lines.append(f'  printf("sizeof {c_name} %zu\\n", sizeof({c_name}));')
-        lines += [f'  printf("{c_name}.{m} %zu\\n", offsetof({c_name}, {m}));' for m in struct_members(c_name)]
-    src, exe = tmp / "probe.c", tmp / "probe"
-    src.write_text("\n".join(['#include <stddef.h>', '#include <stdio.h>', '#include "rlshaders_amd_nearest_rebuild.h"',
-                              'int main(void) {', *lines, '  return 0; }']) + "\n")
-    p = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(src), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
-    out = [l for l in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split("\n") if l]
-    assert len(out) == len(lines)
-    return {k: int(v) for k, v in (l.rsplit(" ", 1) for l in out)}
+    return compiled_layout(tmp_path_factory.mktemp("probe"), HEADER, structs, struct_members)
 
 
 # ---- the surface ---------------------------------------------------------------------------------------------------------------
@@ -99,7 +87,7 @@ def test_no_other_library_header_or_module_knows_the_rebuild(rebuild_lib):
     assert DeviceCode(build.NEAREST_LIB).library_id == NEAREST_DEVICE_CODE
     # the rebuild reads a scene through the private header alone, and takes the records and boxes from the refit's kernel header:
     # it includes neither library's unit nor the traversal
-    text = re.sub(r"//[^\n]*", "", HIP.read_text() + (CSRC / "rls_nearest_rebuild.hpp").read_text())
+    text = re.sub(r"//[^\n]*", "", host_layer(HIP)[0] + (CSRC / "rls_nearest_rebuild.hpp").read_text())
     assert '#include "rls_nearest_scene.hpp"' in text and '#include "rls_nearest_refit.hpp"' in text
     assert "nearest.hip" not in text and "refit.hip" not in text and "rls_nearest_device.hpp" not in text
     for own in ("refit_records_kernel", "refit_level_kernel", "refit_node", "refit_record("):
@@ -164,43 +152,13 @@ def test_one_gfx950_code_object_no_scratch_no_spill(rebuild_lib, tmp_path):
 
 
 # ---- the refusals: no device needed ------------------------------------------------------------------------------------------------
-LAYOUT = "scene is not a scene of this build's layout (librls_nearest.so and librls_nearest_rebuild.so must be of one build)"
-CREATE = [
-    ("ctx NULL", lambda w: put(w, "ctxp", None), "ctx is NULL"),
-    ("out NULL", lambda w: put(w, "outp", None), "out is NULL"),
-    ("scene NULL", lambda w: put(w, "scenep", None), "scene is NULL"),
-    ("a zeroed scene", lambda w: put(w, "scenep", w.p), LAYOUT),
-    ("another layout", lambda w: C.c_uint64.from_buffer(w.scene, 0).__setattr__("value", scene_layout_tag() - 1), LAYOUT),
-    ("another device", lambda w: w.scene_device(1), "the scene lives on another device than ctx"),
-]
-UPDATE = [
-    ("ctx NULL", lambda w: put(w, "ctxp", None), "ctx is NULL"),
-    ("rebuild NULL", lambda w: put(w, "rebuildp", None), "rebuild is NULL"),
-    ("mesh NULL", lambda w: put(w, "meshp", None), "mesh is NULL"),
-    ("nv more", lambda w: put(w.mesh, "nv", 4), "mesh.nv is not the scene's"),
-    ("nv less", lambda w: put(w.mesh, "nv", 2), "mesh.nv is not the scene's"),
-    ("vertices NULL", lambda w: put(w.mesh, "vertices", None), "mesh.vertices is NULL"),
-    ("normals without", lambda w: put(w.rebuild_info, "has_normals", 0), "mesh.normals is set but the scene was made without normals"),
-    ("another device", lambda w: w.rebuild_device(1), "the rebuild's scene lives on another device than ctx"),
-]
-INFO = [
-    ("rebuild NULL", lambda w: put(w, "rebuildp", None), "rebuild is NULL"),
-    ("info NULL", lambda w: put(w, "infop", None), "info is NULL"),
-]
-READ = [
-    ("ctx NULL", lambda w: put(w, "ctxp", None), "ctx is NULL"),
-    ("rebuild NULL", lambda w: put(w, "rebuildp", None), "rebuild is NULL"),
-    ("another device", lambda w: w.rebuild_device(1), "the rebuild's scene lives on another device than ctx"),
-]
+TABLES = refusal_tables("rebuild")                                 # the rows of create, update, get_info and read_tree
+assert [len(TABLES[verb]) for verb in ("create", "update", "get_info", "read_tree")] == [6, 8, 2, 3]
 
 
-@pytest.mark.parametrize("entry,call,table", [("rls_nearest_rebuild_create", RebuildWorld.create, CREATE),
-                                              ("rls_nearest_rebuild_update", RebuildWorld.update, UPDATE),
-                                              ("rls_nearest_rebuild_get_info", RebuildWorld.get_info, INFO),
-                                              ("rls_nearest_rebuild_read_tree", RebuildWorld.read_tree, READ)],
-                         ids=["create", "update", "get_info", "read_tree"])
-def test_every_argument_check_refuses_by_name(rebuild_lib, entry, call, table):
-    wrong = refusals(RebuildWorld, call, entry, table)
+@pytest.mark.parametrize("verb", ["create", "update", "get_info", "read_tree"])
+def test_every_argument_check_refuses_by_name(rebuild_lib, verb):
+    wrong = refusals(RebuildWorld, getattr(RebuildWorld, verb), "rls_nearest_rebuild_" + verb, TABLES[verb])
     assert not wrong, "\n".join(wrong)
 
 
@@ -212,12 +170,23 @@ def test_info_of_dummy_memory_and_destroy_of_null(rebuild_lib):
 
 
 def test_the_checks_are_written_once():
-    """every message of the host layer appears once in rebuild.hip, and every message the tables above ask for is one of them"""
-    text = HIP.read_text()
-    messages = re.findall(r'RLS_REQUIRE(?:_IN)?\([^;]*?"([^"]+)"\s*\)\s*;', text, flags=re.S)
+    """every message of the host layer appears once in rebuild.hip and the shared layer it includes, and every message the
+    tables above ask for is one of them"""
+    text, messages = host_layer(HIP)
     assert len(messages) >= 12, len(messages)
     twice = sorted(m for m in set(messages) if messages.count(m) > 1)
     # the entry points' own first lines, ahead of the shared paths
     assert twice == ["ctx is NULL", "rebuild is NULL", "the rebuild's scene lives on another device than ctx"], twice
-    for _, _, want in CREATE + UPDATE + INFO + READ:
+    for _, _, want in sum(TABLES.values(), []):
         assert text.count(f'"{want}"') >= 1, want
+
+
+def test_the_shared_host_layer_names_neither_library():
+    """csrc_nearest/rls_nearest_update.hpp holds neither library's noun as a word, so no message of it can leak into the other
+    library; the mesh checks are written in it alone"""
+    shared = UPDATE_LAYER.read_text()
+    for noun in ("refit is", "rebuild is", "refit's", "rebuild's", "librls_nearest_re"):
+        assert noun not in shared, noun
+    everything = shared + HIP.read_text() + (CSRC / "refit.hip").read_text()
+    for _, _, want in TABLES["update"][2:7]:                        # mesh NULL .. normals without: four messages
+        assert everything.count(f'"{want}"') == 1 and shared.count(f'"{want}"') == 1, want
