@@ -153,6 +153,7 @@ NEAREST_HEADERS = [NEAREST_CSRC / "rls_nearest_device.hpp", NEAREST_CSRC / "rls_
 NEAREST_REFIT_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", NEAREST_CSRC / "rls_nearest_update.hpp", INCLUDE / "rlshaders_amd_nearest_refit.h"]
 NEAREST_REBUILD_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", NEAREST_CSRC / "rls_nearest_update.hpp", NEAREST_CSRC / "rls_nearest_rebuild.hpp",
                            INCLUDE / "rlshaders_amd_nearest_rebuild.h"]
+NEAREST_GROUP_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", NEAREST_CSRC / "rls_nearest_group.hpp", INCLUDE / "rlshaders_amd_nearest_group.h"]
 
 COMPANIONS = {c.name: c for c in (
     # BASELINE config 2's kernel with one uniform-slope pass per workgroup, handed the streamed EXACT reflect+refract launches
@@ -175,10 +176,14 @@ COMPANIONS = {c.name: c for c in (
     # rebuilding a scene's tree for a moved mesh (include/rlshaders_amd_nearest_rebuild.h): the scene through the same private
     # header, the records and boxes through the refit's kernel header, the same host layer; it calls nothing of either library
     Companion("nearest_rebuild", "nearest_rebuild", NEAREST_CSRC, ["rebuild.hip"], NEAREST_HEADERS + NEAREST_REBUILD_HEADERS),
+    # instanced scenes (include/rlshaders_amd_nearest_group.h): many placed scenes under a top-level tree, both levels walked in
+    # one launch; the scenes through the same private header, the query's functions from the nearest-hit library's kernel header
+    # (without its kernel); it calls nothing of the other libraries
+    Companion("nearest_group", "nearest_group", NEAREST_CSRC, ["group.hip"], NEAREST_HEADERS + NEAREST_GROUP_HEADERS),
 )}
 RR_LIB, TRACE_LIB, WALK_LIB = COMPANIONS["ggx_rr"].lib, COMPANIONS["trace"].lib, COMPANIONS["walk"].lib
 SHADOW_WALK_LIB, NEAREST_LIB, NEAREST_REFIT_LIB = COMPANIONS["shadow_walk"].lib, COMPANIONS["nearest"].lib, COMPANIONS["nearest_refit"].lib
-NEAREST_REBUILD_LIB = COMPANIONS["nearest_rebuild"].lib
+NEAREST_REBUILD_LIB, NEAREST_GROUP_LIB = COMPANIONS["nearest_rebuild"].lib, COMPANIONS["nearest_group"].lib
 
 
 def build_companion(name: str, force: bool = False, verbose: bool = False) -> Path:
@@ -227,6 +232,10 @@ def build_nearest_rebuild_library(force: bool = False, verbose: bool = False) ->
     return build_companion("nearest_rebuild", force, verbose)
 
 
+def build_nearest_group_library(force: bool = False, verbose: bool = False) -> Path:
+    return build_companion("nearest_group", force, verbose)
+
+
 def _link_flags(libs) -> list:
     return [f"-L{LIBDIR}", *[f"-l{l}" for l in libs], "-lrlshaders_amd", f"-Wl,-rpath,{LIBDIR}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
 
@@ -273,6 +282,11 @@ def build_nearest_refit_example(verbose: bool = False, name: str = "example_near
 def build_nearest_rebuild_example(verbose: bool = False, name: str = "example_nearest_rebuild") -> Path:
     """a sphere twisted, its tree rebuilt on the device, walked on the rebuilt scene and on a fresh one"""
     return build_example(name, ["nearest_rebuild", "nearest", "shadow_walk", "walk", "trace"], verbose)
+
+
+def build_nearest_group_example(verbose: bool = False, name: str = "example_nearest_group") -> Path:
+    """three instances of one mesh under a group: a shadow walk and a routed glossy queue through them, one instance moved"""
+    return build_example(name, ["nearest_group", "nearest", "shadow_walk", "walk", "trace"], verbose)
 
 
 def build_nearest_stats(verbose: bool = False) -> Path:

@@ -215,7 +215,7 @@ RLS_NEAREST_HD void nearest_frame(const NearestTri &tr, float u, float v, const 
     }
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(RLS_NEAREST_DEVICE_NO_KERNEL)   // (the group library takes the functions above alone)
 // ---- the kernel: one ray per lane over the companions' tile skeleton -----------------------------------------------------------
 struct NearestIO {
     const NearestNode *nodes;

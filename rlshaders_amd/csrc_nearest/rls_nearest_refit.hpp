@@ -138,7 +138,7 @@ inline int64_t refit_host(NearestNode *nodes, NearestTri *tris, int64_t nt, cons
     return parked;
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(RLS_NEAREST_REFIT_NO_KERNELS)   // (the group library takes the functions above alone)
 // ---- the kernels: one lane per triangle slot, then one lane per node of a level, over the companions' tile skeleton ------------
 struct RefitRecordsIO {
     NearestTri *tris;

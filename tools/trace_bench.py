@@ -90,6 +90,14 @@ synchronise, the median of 9 after 3); the launches of an update and the bytes o
 nearest's two streams after the 0.5 and the 2 radian twist on the refit tree, on the device-rebuilt tree and on a host-rebuilt
 one (a fresh scene); same_as_host_rebuilt: every found plane of the device-rebuilt tree's queries is the fresh scene's bytes.
 --spp-n is not read.
+--closure nearest-group: instanced scenes (rlshaders_amd.nearest_group, librls_nearest_group.so).  --instances copies of the
+--level icosphere (rigidly turned, on a cubic grid 2.5 radii apart) under one Group, queried by a camera grid's rays (coherent)
+and by uniformly distributed rays from the points they hit with the pair last / last_instance set (incoherent), 2^log2n each.
+Beside each (a) "flat": the same geometry baked into ONE nearest.Scene (where it fits 2^22 triangles), the same rays, and the
+share of rays whose hit flag agrees; (b) "alone": --closure nearest's camera on one instance, through a Group of one and through
+the plain Scene -- what the second level costs a ray.  "update": Group.update with both matrix planes against baking the
+vertices on the device (a batched matrix product) + Rebuild.update of the flat scene; the device bytes of the group and of the
+flat scene.  Medians, fastest and slowest of at least 9 calls after 3 warm-up calls, device events.  --spp-n is not read.
 """
 from __future__ import annotations
 
@@ -1178,6 +1186,113 @@ def bench_shadow_walk_nearest(args, ctx, n: int, spp_n: int, seed: int, rec: dic
     scene.close()
 
 
+def bench_nearest_group(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """a grid of instances of one icosphere under a group, beside the flat scene of the same geometry (module docstring)"""
+    import numpy as np
+    import torch
+    from rlshaders_amd import build, codeid, nearest, nearest_group, nearest_rebuild
+    nearest_group.load()
+    repeats, warmup = max(args.repeats, 9), max(args.warmup, 3)
+    dev = ctx.torch_device
+    V, tri, normals = icosphere(args.level)
+    nv, nt, count = V.shape[0], tri.shape[0], args.instances
+    side3 = int(np.ceil(count ** (1.0 / 3.0)))
+    rng = np.random.default_rng(seed)
+    B = np.zeros((count, 3, 4))
+    for j in range(count):
+        q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+        q = q * np.sign(np.diag(r))
+        B[j, :, :3] = q if np.linalg.det(q) > 0 else -q
+        B[j, :, 3] = 2.5 * (np.array([j % side3, (j // side3) % side3, j // (side3 * side3)]) - (side3 - 1) / 2.0)
+    half = 1.25 * side3                                               # the grid's half-width
+    scene = nearest.Scene(ctx, V, tri, normals=normals)
+    instances = [nearest_group.Instance(scene, B[j], surface_base=j) for j in range(count)]
+    group = nearest_group.Group(ctx, instances)
+    rec["group"] = dict(group.info(), triangles_a_scene=nt, scene_device_bytes=scene.device_bytes,
+                        library_id=codeid.DeviceCode(build.NEAREST_GROUP_LIB).library_id)
+    flat = None
+    if count * nt <= nearest.RLS_NEAREST_MAX_TRIANGLES:
+        Vf = np.concatenate([(V.astype(np.float64) @ B[j, :, :3].T + B[j, :, 3]).astype(np.float32) for j in range(count)])
+        Tf = np.concatenate([tri.astype(np.int64) + j * nv for j in range(count)])
+        flat = nearest.Scene(ctx, Vf, Tf, normals=np.concatenate([normals @ B[j, :, :3].T.astype(np.float32) for j in range(count)]))
+        rec["flat"] = {"triangles": flat.nt, "depth": flat.depth, "device_bytes": flat.device_bytes}
+    side = int(round(n ** 0.5))
+    n = side * side
+    g = torch.Generator(device=dev).manual_seed(seed)
+    planes = ("P", "N", "Ns", "surface", "prim")
+    u = (torch.arange(side, device=dev, dtype=torch.float32) + 0.5) / side * 2.6 - 1.3
+
+    def camera(scale):
+        d = torch.stack([u.repeat(side) * scale, u.repeat_interleave(side) * scale, torch.full((n,), 2.0 * scale, device=dev)]).contiguous()
+        o = torch.tensor([0.0, 0.0, -3.0 * scale], device=dev)[:, None].expand(3, n).contiguous()
+        return nearest.Rays(o, d)
+
+    def run(fn, found):
+        fn()
+        r = timed_spread(fn, repeats, warmup)
+        r.update({"rays": n, "hits": int(found.hit.sum(dtype=torch.int64).item()), "mrays_per_s": round(n / r["ms"] / 1e3, 1)})
+        return r
+
+    rays = camera(half)
+    fg = nearest_group.Found(ctx, n, planes=planes + ("instance",))
+    rec["coherent"] = {"group": run(lambda: group.hits(rays, found=fg), fg)}
+    ff = nearest.Found(ctx, n, planes=planes)
+    if flat is not None:
+        rec["coherent"]["flat"] = run(lambda: flat.hits(rays, found=ff), ff)
+        rec["coherent"]["same_hit_flag"] = round(float((fg.hit == ff.hit).float().mean().item()), 6)
+        rec["coherent"]["group_over_flat"] = round(rec["coherent"]["group"]["ms"] / rec["coherent"]["flat"]["ms"], 2)
+    # incoherent: from every hit point (the misses from points of the grid's box) a uniformly distributed direction, the
+    # (instance, triangle) the point lies on skipped
+    hit = fg.hit.bool()
+    O2 = torch.where(hit[None, :], fg.P, (torch.rand(3, n, generator=g, device=dev) * 2 - 1) * half).contiguous()
+    w = torch.randn(3, n, generator=g, device=dev)
+    d2 = (w / w.norm(dim=0)).contiguous()
+    none = torch.full_like(fg.prim, -1)
+    last0, inst0 = torch.where(hit, fg.prim, none).contiguous(), torch.where(hit, fg.instance, none).contiguous()
+    flat0 = torch.where(hit, fg.instance * nt + fg.prim, none).contiguous()
+    last, inst, rays2 = last0.clone(), inst0.clone(), nearest.Rays(O2, d2)
+    fg2, ff2 = nearest_group.Found(ctx, n, planes=planes + ("instance",)), nearest.Found(ctx, n, planes=planes)
+
+    def incoherent_group():
+        last.copy_(last0)
+        inst.copy_(inst0)
+        group.hits(rays2, last=last, last_instance=inst, found=fg2)
+
+    def incoherent_flat():
+        last.copy_(flat0)
+        flat.hits(rays2, last=last, found=ff2)
+
+    rec["incoherent"] = {"group": run(incoherent_group, fg2)}
+    if flat is not None:
+        rec["incoherent"]["flat"] = run(incoherent_flat, ff2)
+        rec["incoherent"]["same_hit_flag"] = round(float((fg2.hit == ff2.hit).float().mean().item()), 6)
+        rec["incoherent"]["group_over_flat"] = round(rec["incoherent"]["group"]["ms"] / rec["incoherent"]["flat"]["ms"], 2)
+    # one instance alone: the second level's cost a ray
+    one = nearest_group.Group(ctx, [nearest_group.Instance(scene, np.eye(4)[:3])])
+    rays1 = camera(0.5)
+    rec["alone"] = {"group": run(lambda: one.hits(rays1, found=fg), fg), "scene": run(lambda: scene.hits(rays1, found=ff), ff)}
+    rec["alone"]["group_over_scene"] = round(rec["alone"]["group"]["ms"] / rec["alone"]["scene"]["ms"], 2)
+    one.close()
+    # the update: two matrix planes against baking + a rebuild of the flat scene
+    A_, B_ = (torch.from_numpy(np.stack([getattr(i, k).reshape(12) for i in instances])).to(dev) for k in ("to_object", "to_world"))
+    rec["update"] = {"group": timed_spread(lambda: group.update(A_, B_), repeats, warmup), "launches": 1 + group.info()["top_depth"]}
+    if flat is not None:
+        rebuild = nearest_rebuild.Rebuild(flat)
+        Vd, L, t = torch.from_numpy(V).to(dev), B_.view(count, 3, 4)[:, :, :3].contiguous(), B_.view(count, 3, 4)[:, :, 3].contiguous()
+        out = torch.empty(count, nv, 3, device=dev)
+
+        def bake_and_rebuild():
+            torch.baddbmm(t[:, None, :], Vd[None].expand(count, nv, 3), L.transpose(1, 2), out=out)
+            rebuild.update(out.view(-1, 3))
+
+        rec["update"]["bake_and_rebuild_flat"] = timed_spread(bake_and_rebuild, repeats, warmup)
+        rec["update"]["flat_over_group"] = round(rec["update"]["bake_and_rebuild_flat"]["ms"] / rec["update"]["group"]["ms"], 1)
+        rebuild.close()
+        flat.close()
+    group.close()
+    scene.close()
+
+
 def timed_spread(fn, repeats: int, warmup: int) -> dict:
     """timed(), with the fastest and the slowest of the measured calls beside the median"""
     import torch
@@ -1245,7 +1360,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
     ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
-                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk", "nearest", "nearest-refit", "nearest-rebuild"),
+                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk", "nearest", "nearest-refit", "nearest-rebuild", "nearest-group"),
                     default="ggx")
     ap.add_argument("--mix", choices=("even", "skewed", "one"), default="even", help="route: the rays' split over 3 bins and the misses")
     ap.add_argument("--state", choices=("camera", "secondary", "half", "diffuse"), default="camera",
@@ -1255,6 +1370,7 @@ def main() -> None:
     ap.add_argument("--hit-spp-n", type=int, default=1, help="sss-hits: the light loop at the hits draws hit_spp_n^2 samples a light")
     ap.add_argument("--tracer", choices=("synthetic", "nearest"), default="synthetic",
                     help="shadow-walk: the hits prepared outside the events, or traced by rls_nearest_walk_hits inside them")
+    ap.add_argument("--instances", type=int, default=64, help="nearest-group: the placed copies of the icosphere")
     ap.add_argument("--level", type=int, default=6, help="nearest: the icosphere's subdivisions (6: 81 920 triangles)")
     args = ap.parse_args()
     if args.repeats < 3:
@@ -1278,6 +1394,7 @@ def main() -> None:
         {"disney": bench_disney, "sss": bench_sss, "sss-walk": bench_sss_walk, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
          "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce,
          "shadow-fold": bench_shadow_fold, "route": bench_route, "nearest": bench_nearest, "nearest-refit": bench_nearest_refit, "nearest-rebuild": bench_nearest_rebuild,
+         "nearest-group": bench_nearest_group,
          "shadow-walk": bench_shadow_walk_nearest if args.tracer == "nearest" else bench_shadow_walk}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
