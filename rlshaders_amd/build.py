@@ -154,6 +154,7 @@ NEAREST_REFIT_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", NEAREST_CSRC / 
 NEAREST_REBUILD_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", NEAREST_CSRC / "rls_nearest_update.hpp", NEAREST_CSRC / "rls_nearest_rebuild.hpp",
                            INCLUDE / "rlshaders_amd_nearest_rebuild.h"]
 NEAREST_GROUP_HEADERS = [NEAREST_CSRC / "rls_nearest_refit.hpp", NEAREST_CSRC / "rls_nearest_group.hpp", INCLUDE / "rlshaders_amd_nearest_group.h"]
+NEAREST_ANY_HEADERS = [NEAREST_CSRC / "rls_nearest_any.hpp", INCLUDE / "rlshaders_amd_nearest_any.h"]
 
 COMPANIONS = {c.name: c for c in (
     # BASELINE config 2's kernel with one uniform-slope pass per workgroup, handed the streamed EXACT reflect+refract launches
@@ -180,10 +181,14 @@ COMPANIONS = {c.name: c for c in (
     # one launch; the scenes through the same private header, the query's functions from the nearest-hit library's kernel header
     # (without its kernel); it calls nothing of the other libraries
     Companion("nearest_group", "nearest_group", NEAREST_CSRC, ["group.hip"], NEAREST_HEADERS + NEAREST_GROUP_HEADERS),
+    # any-hit shadow queries (include/rlshaders_amd_nearest_any.h): a one-mesh scene through the same private header, the slab and
+    # triangle tests from the nearest-hit library's kernel header (without its kernel); it calls nothing of the other libraries
+    Companion("nearest_any", "nearest_any", NEAREST_CSRC, ["any.hip"], NEAREST_HEADERS + NEAREST_ANY_HEADERS),
 )}
 RR_LIB, TRACE_LIB, WALK_LIB = COMPANIONS["ggx_rr"].lib, COMPANIONS["trace"].lib, COMPANIONS["walk"].lib
 SHADOW_WALK_LIB, NEAREST_LIB, NEAREST_REFIT_LIB = COMPANIONS["shadow_walk"].lib, COMPANIONS["nearest"].lib, COMPANIONS["nearest_refit"].lib
 NEAREST_REBUILD_LIB, NEAREST_GROUP_LIB = COMPANIONS["nearest_rebuild"].lib, COMPANIONS["nearest_group"].lib
+NEAREST_ANY_LIB = COMPANIONS["nearest_any"].lib
 
 
 def build_companion(name: str, force: bool = False, verbose: bool = False) -> Path:
@@ -234,6 +239,10 @@ def build_nearest_rebuild_library(force: bool = False, verbose: bool = False) ->
 
 def build_nearest_group_library(force: bool = False, verbose: bool = False) -> Path:
     return build_companion("nearest_group", force, verbose)
+
+
+def build_nearest_any_library(force: bool = False, verbose: bool = False) -> Path:
+    return build_companion("nearest_any", force, verbose)
 
 
 def _link_flags(libs) -> list:
@@ -287,6 +296,11 @@ def build_nearest_rebuild_example(verbose: bool = False, name: str = "example_ne
 def build_nearest_group_example(verbose: bool = False, name: str = "example_nearest_group") -> Path:
     """three instances of one mesh under a group: a shadow walk and a routed glossy queue through them, one instance moved"""
     return build_example(name, ["nearest_group", "nearest", "shadow_walk", "walk", "trace"], verbose)
+
+
+def build_nearest_any_example(verbose: bool = False, name: str = "example_nearest_any") -> Path:
+    """a light loop's shadow queue under an opaque occluder in one launch, and under a mixed table through the two-phase route"""
+    return build_example(name, ["nearest_any", "nearest", "shadow_walk", "walk", "trace"], verbose)
 
 
 def build_nearest_stats(verbose: bool = False) -> Path:

@@ -3,7 +3,7 @@ integrateRefract, with rls_ggx_integrate / rls_ggx_integrate_refract on the same
 --closure disney those of rlDisney's two lobes, with rls_disney_integrate (reduced, both lobes) on the same batch; with
 --closure sss rlSss's probe-ray emit and scatter resolve, with rls_sss_integrate_scatter on the same batch.
 
-    python tools/trace_bench.py [--closure ggx|disney|sss|sss-walk|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce|shadow-fold|shadow-walk|route] [--mix even|skewed|one] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
+    python tools/trace_bench.py [--closure ggx|disney|sss|sss-walk|sss-hits|ggx-lights|disney-lights|ggx-node|disney-node|skin-node|ggx-bounce|disney-bounce|skin-bounce|shadow-fold|shadow-walk|route|nearest|nearest-refit|nearest-rebuild|nearest-group|nearest-any] [--mix even|skewed|one] [--log2n 24] [--spp-n 4] [--repeats 5] [--warmup 2] [--fast] [--state camera|secondary|half]
 
 Prints one JSON line: ms per call (median over the repeats, device events, after the warm-up), rays per second, the
 algorithmic bytes of each call over its time and as a fraction of 8 TB/s, and emit time / integrate time.  Byte accounting:
@@ -98,6 +98,18 @@ share of rays whose hit flag agrees; (b) "alone": --closure nearest's camera on 
 the plain Scene -- what the second level costs a ray.  "update": Group.update with both matrix planes against baking the
 vertices on the device (a batched matrix product) + Rebuild.update of the flat scene; the device bytes of the group and of the
 flat scene.  Medians, fastest and slowest of at least 9 calls after 3 warm-up calls, device events.  --spp-n is not read.
+--closure nearest-any: any-hit shadow queries (rlshaders_amd.nearest_any, librls_nearest_any.so).  (a) "streams": --closure
+nearest's coherent and incoherent streams of 2^log2n rays on the --level icosphere, given finite reaches, through rls_nearest_hits
+(hit, t, P, surface: what the shadow walk's tracer asks for) and through rls_nearest_any_hits (state, visibility, reach), and their
+ratio.  (b) "opaque": a --closure ggx-lights shadow queue (--lights, --spp-n) through an opaque icosphere above the points: ONE
+any-hit launch against shadow_walk.run over nearest.tracer with an all-ones table (its rounds, and the host's reads of the active
+count, inside the events); same_visibility: the two planes are the same bytes.  (c) "mixed": a translucent shell about the opaque
+sphere: nearest_any.shadow (the launch, the flags, the walk on the veiled rays) against the full walk, the share of rays walked,
+same_open_rays: the clear and veiled rays' visibility is the same bytes; blocked_not_zero / walk_blocked_not_zero: the blocked rays
+whose visibility is not all zero after the two-phase route (none, by construction) and after the full walk (a ray that grazes the
+opaque surface may miss it from its moved origin); "any" / "nearest": one any-hit and one nearest-hit launch
+over the queue's rays on that scene.  Medians, fastest and slowest of at least 9 calls
+after 3 warm-up calls, device events.
 """
 from __future__ import annotations
 
@@ -1293,6 +1305,133 @@ def bench_nearest_group(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> 
     scene.close()
 
 
+def bench_nearest_any(args, ctx, n: int, spp_n: int, seed: int, rec: dict) -> None:
+    """the any-hit query beside the nearest-hit query and beside the shadow walk it shortens (module docstring)"""
+    import numpy as np
+    import torch
+    import rlshaders_amd as R
+    from rlshaders_amd import build, codeid, nearest, nearest_any, shadow_walk, trace as T
+    from rlshaders_amd.closures import make_light
+    nearest_any.load(), shadow_walk.load()
+    repeats, warmup = max(args.repeats, 9), max(args.warmup, 3)
+    dev = ctx.torch_device
+    rec["library_id"] = codeid.DeviceCode(build.NEAREST_ANY_LIB).library_id
+    rec["nearest_library_id"] = codeid.DeviceCode(build.NEAREST_LIB).library_id
+    # ---- (a) the two streams of --closure nearest with finite reaches
+    V, tri, normals = icosphere(args.level)
+    scene = nearest.Scene(ctx, V, tri, normals=normals)
+    rec["scene"] = {"triangles": scene.nt, "nodes": scene.nodes, "depth": scene.depth, "leaf_size": scene.leaf_size}
+    side = int(round(n ** 0.5))
+    m = side * side
+    g = torch.Generator(device=dev).manual_seed(seed)
+    u = (torch.arange(side, device=dev, dtype=torch.float32) + 0.5) / side * 1.3 - 0.65
+    d = torch.stack([u.repeat(side), u.repeat_interleave(side), torch.ones(m, device=dev)]).contiguous()
+    o = torch.tensor([0.0, 0.0, -3.0], device=dev)[:, None].expand(3, m).contiguous()
+    found = nearest.Found(ctx, m, planes=("P", "surface"))
+    state, vis, reach = (torch.empty(m, dtype=torch.uint8, device=dev), torch.empty(3, m, device=dev), torch.empty(m, device=dev))
+
+    def pair(rays, last0):
+        last = None if last0 is None else last0.clone()
+
+        def near():
+            if last is not None:
+                last.copy_(last0)                                    # rls_nearest_hits writes `last`; the any-hit query never does
+            scene.hits(rays, last=last, found=found)
+
+        def any_():
+            nearest_any.hits(scene, rays, last=last0, state=state, visibility=vis, reach=reach)
+
+        near(), any_()
+        out = {"rays": m, "hits": int(found.hit.sum(dtype=torch.int64).item()), "blocked": int((state == 1).sum().item()),
+               "nearest": timed_spread(near, repeats, warmup), "any": timed_spread(any_, repeats, warmup)}
+        if last is not None:
+            out["last_reset_ms"] = timed_spread(lambda: last.copy_(last0), repeats, warmup)["ms"]
+        out["same_hit_flag"] = bool(torch.equal(found.hit, state))
+        out["any_over_nearest"] = round(out["any"]["ms"] / out["nearest"]["ms"], 3)
+        return out
+
+    rec["streams"] = {"coherent": pair(nearest.Rays(o, d, maxdist=torch.full((m,), 3.0, device=dev)), None)}
+    first = nearest.Found(ctx, m, planes=("P", "prim"))
+    scene.hits(nearest.Rays(o, d), found=first)
+    hit = first.hit.bool()
+    Pn = torch.randn(3, m, generator=g, device=dev)
+    Pn = Pn / Pn.norm(dim=0)
+    O2 = torch.where(hit[None, :], first.P, Pn).contiguous()
+    w = torch.randn(3, m, generator=g, device=dev)
+    d2 = (-(O2 / O2.norm(dim=0)) + 0.999 * w / w.norm(dim=0)).contiguous()
+    last0 = torch.where(hit, first.prim, torch.full_like(first.prim, -1)).contiguous()
+    rec["streams"]["incoherent"] = pair(nearest.Rays(O2, d2, maxdist=torch.full((m,), 1.5, device=dev)), last0)
+    del found, first, state, vis, reach, O2, d2, w, Pn, o, d
+    scene.close()
+    # ---- (b), (c) a light loop's shadow queue under an occluder
+    nl = args.lights
+    lights = [make_light(center=c, radius=r, radiance=e) for c, r, e in LIGHT_SPECS[:nl]]
+    points = max(n // (nl * 3 * spp_n * spp_n), 1)                   # about n shadow rays
+    wo, N, T_ = R.gen_frame(ctx, seed, 0, points)
+    uu = lambda stream, lo=0.0, hi=1.0: R.gen_uniform(ctx, seed, 0, points, stream, lo, hi)
+    P = torch.stack([uu(60, 0.0, 4.0), uu(61, 0.0, 4.0), uu(62)]).contiguous()
+    s = R.GgxSampler(ctx, wo, N, T_, specColor=torch.stack([uu(10 + k) for k in range(3)]), ior=uu(13, 1.05, 2.55),
+                     roughness=uu(14, 0.05, 1.0), anisotropic=R.gen_aniso(ctx, seed, 0, points))
+    sh = T.ggx_shader(s, KdColor=torch.stack([uu(20 + k) for k in range(3)]), Kd=uu(23), diffuseRoughness=uu(24), Ks=uu(25))
+    q = T.ggx_shadow_rays(s, sh, P, lights, spp_n, seed)
+    count, cap = q.count, q.capacity
+    centre = (2.0, 2.0, 2.0)
+    Vi, Ti, _ = icosphere(args.level, 0.7, centre)
+    Vo, To, _ = icosphere(max(args.level - 1, 0), 1.0, centre)
+    rays = nearest.Rays(P, q._dir, maxdist=q._maxdist, via=q._point, count=q.offsets[q.n:], rays=cap)
+    state, vis, reach = (torch.empty(max(cap, 1), dtype=torch.uint8, device=dev), torch.empty(3, max(cap, 1), device=dev),
+                         torch.empty(max(cap, 1), device=dev))
+
+    def states():
+        st = state[:count]
+        return {k: int((st == v).sum().item()) for k, v in (("clear", 0), ("blocked", 1), ("veiled", 2))}
+
+    found = nearest.Found(ctx, cap, planes=("P", "surface"))
+    opaque = nearest.Scene(ctx, Vi, Ti)
+    ones = torch.ones(3, 1, device=dev)
+    one_launch = lambda: nearest_any.hits(opaque, rays, state=state, visibility=vis, reach=reach)
+    kept = {}                                                        # the last result of each route, for the comparisons
+
+    def full(sc, table):
+        def run():
+            kept["walk"] = shadow_walk.run(q, P, nearest.tracer(sc, opacity=table), max_steps=16)
+        return run
+
+    walk = full(opaque, ones)
+    one_launch(), walk()
+    rec["opaque"] = {"points": points, "lights": nl, "spp_n": spp_n, "rays": count, "triangles": opaque.nt, **states(),
+                     "same_visibility": bool(torch.equal(vis[:, :count].view(torch.int32), kept["walk"].visibility[:, :count].view(torch.int32))),
+                     "any": timed_spread(one_launch, repeats, warmup), "walk": timed_spread(walk, repeats, warmup),
+                     "nearest": timed_spread(lambda: opaque.hits(rays, found=found), repeats, warmup)}
+    rec["opaque"]["walk_over_any"] = round(rec["opaque"]["walk"]["ms"] / rec["opaque"]["any"]["ms"], 2)
+    opaque.close()
+    # (c) the translucent shell about the opaque sphere: surfaces 0 (the shell) and 1
+    mixed = nearest.Scene(ctx, np.concatenate([Vo, Vi]), np.concatenate([To, Ti + len(Vo)]),
+                          surface=np.concatenate([np.zeros(len(To), np.uint32), np.ones(len(Ti), np.uint32)]))
+    table = torch.tensor([[0.3, 1.0], [0.5, 1.0], [0.7, 1.0]], device=dev)
+
+    def two():
+        kept["two"] = nearest_any.shadow(q, P, mixed, table, max_steps=16)
+
+    full2 = full(mixed, table)
+    two(), full2()
+    st = kept["two"].state[:count]
+    open_ = st != 1
+    a, b = kept["two"].visibility[:, :count].view(torch.int32), kept["walk"].visibility[:, :count].view(torch.int32)
+    rec["mixed"] = {"rays": count, "triangles": mixed.nt, "clear": int((st == 0).sum().item()), "blocked": int((st == 1).sum().item()),
+                    "veiled": int((st == 2).sum().item()), "walked": kept["two"].walked, "walked_share": round(kept["two"].walked / max(count, 1), 4),
+                    "same_open_rays": bool(torch.equal(a[:, open_], b[:, open_])),
+                    "blocked_not_zero": int((a[:, ~open_] != 0).any(dim=0).sum().item()),
+                    "walk_blocked_not_zero": int((b[:, ~open_] != 0).any(dim=0).sum().item()),
+                    "two_phase": timed_spread(two, repeats, warmup), "walk": timed_spread(full2, repeats, warmup)}
+    # the launch alone, inside the two-phase route's time: every translucent candidate on the ray is met, there is no best t to cull by
+    flags = kept["two"].flags
+    rec["mixed"]["any"] = timed_spread(lambda: nearest_any.hits(mixed, rays, opaque=flags, state=state, visibility=vis, reach=reach), repeats, warmup)
+    rec["mixed"]["nearest"] = timed_spread(lambda: mixed.hits(rays, found=found), repeats, warmup)
+    rec["mixed"]["walk_over_two_phase"] = round(rec["mixed"]["walk"]["ms"] / rec["mixed"]["two_phase"]["ms"], 2)
+    mixed.close()
+
+
 def timed_spread(fn, repeats: int, warmup: int) -> dict:
     """timed(), with the fastest and the slowest of the measured calls beside the median"""
     import torch
@@ -1360,7 +1499,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--fast", action="store_true", help="RLS_MATH_FAST (default EXACT)")
     ap.add_argument("--closure", choices=("ggx", "disney", "sss", "sss-hits", "ggx-lights", "disney-lights", "ggx-node", "disney-node", "skin-node",
-                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk", "nearest", "nearest-refit", "nearest-rebuild", "nearest-group"),
+                                          "ggx-bounce", "disney-bounce", "skin-bounce", "shadow-fold", "shadow-walk", "route", "sss-walk", "nearest", "nearest-refit", "nearest-rebuild", "nearest-group", "nearest-any"),
                     default="ggx")
     ap.add_argument("--mix", choices=("even", "skewed", "one"), default="even", help="route: the rays' split over 3 bins and the misses")
     ap.add_argument("--state", choices=("camera", "secondary", "half", "diffuse"), default="camera",
@@ -1394,7 +1533,7 @@ def main() -> None:
         {"disney": bench_disney, "sss": bench_sss, "sss-walk": bench_sss_walk, "sss-hits": bench_sss_hits, "ggx-node": bench_node, "disney-node": bench_node,
          "skin-node": bench_skin_node, "ggx-bounce": bench_bounce, "disney-bounce": bench_bounce, "skin-bounce": bench_skin_bounce,
          "shadow-fold": bench_shadow_fold, "route": bench_route, "nearest": bench_nearest, "nearest-refit": bench_nearest_refit, "nearest-rebuild": bench_nearest_rebuild,
-         "nearest-group": bench_nearest_group,
+         "nearest-group": bench_nearest_group, "nearest-any": bench_nearest_any,
          "shadow-walk": bench_shadow_walk_nearest if args.tracer == "nearest" else bench_shadow_walk}.get(
             args.closure, bench_lights)(args, ctx, n, spp_n, seed, rec)
         ctx.close()
