@@ -13,21 +13,25 @@
 //   - a second group_build over the same boxes gives the same tree (the builder is deterministic);
 //   - for every ray the traversal (group_traverse, both stacks in one array of 16 + 24 words) equals the brute force
 //     (group_brute: every instance that takes part, every triangle) bit for bit in (instance, prim, t).
-// out.bin: 10 words a ray: the brute force's instance, prim, t; the traversal's instance, prim, t; top nodes visited, instances
-// entered, the most top-stack entries held, the most object-stack entries held.  Prints one "ok group: ..." line and exits 0, or
-// the first differences and exits 1.  tests/test_nearest_group_host.py drives it, once more under -fsanitize=address,undefined.
+// The rays are shared out over min(hardware threads, 16) threads where the brute force is large (a ray's result depends on
+// nothing but the ray).  out.bin: 10 words a ray: the brute force's instance, prim, t; the traversal's instance, prim, t; top
+// nodes visited, instances entered, the most top-stack entries held, the most object-stack entries held.  Prints "levels: ..." (the top tree's node count
+// level by level, the root's first: what rls_nearest_group_update's launch plan is made from) and one "ok group: ..." line and
+// exits 0, or the first differences and exits 1.  tests/test_nearest_group_host.py drives it, once more under -fsanitize=address,undefined.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
+#include <thread>
 #include <vector>
 
 #include "../../rlshaders_amd/csrc_nearest/rls_nearest_group.hpp"
 
 namespace {
 
-int fails = 0;
+std::atomic<int> fails(0);
 #define CHECK(cond, ...) do { if (!(cond)) { if (fails++ < 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
 
 struct Mesh {
@@ -62,6 +66,7 @@ int main(int argc, char **argv)
     }
     const int64_t count = ok ? head[1] : 0;
     std::vector<GroupPlacement> place((size_t)count);
+    int64_t placed_tris = 0;                                             // the triangles a ray meets in the brute force, at most
     for (int64_t j = 0; ok && j < count; j++) {
         uint32_t w[25];
         ok = fread(w, 4, 25, f) == 25 && w[0] < meshes.size();
@@ -73,6 +78,7 @@ int main(int argc, char **argv)
         const Mesh &m = meshes[w[0]];
         p.nodes = m.bvh.nodes.data(); p.tris = m.bvh.tris.data(); p.index = m.T.data();
         p.node_count = (uint32_t)m.bvh.nodes.size();
+        placed_tris += (int64_t)(m.T.size() / 3);
     }
     fclose(f);
     if (!ok) { fprintf(stderr, "bad group file\n"); return 2; }
@@ -125,42 +131,67 @@ int main(int argc, char **argv)
     if (f) fclose(f);
     if (!ok) { fprintf(stderr, "bad rays file\n"); return 2; }
     std::vector<uint32_t> out(10 * (size_t)M);
+    struct Tally { int64_t hits = 0, differ = 0; int max_top = 0, max_stack = 0; };
+    auto work = [&](int64_t k0, int64_t k1, Tally *tally) {
+        int64_t hits = 0, differ = 0;
+        int max_top = 0, max_stack = 0;
+        for (int64_t k = k0; k < k1; k++) {
+            float w[7];
+            memcpy(w, &rays[9 * (size_t)k], 28);
+            const float o[3] = { w[0], w[1], w[2] }, d[3] = { w[3], w[4], w[5] };
+            GroupRay g;
+            g.w = nearest_ray(o, d, w[6], rays[9 * (size_t)k + 8]);
+            g.skip_instance = rays[9 * (size_t)k + 7];
+            const GroupBest want = group_brute(by_instance.data(), count, g);
+            uint32_t stack[kGroupStack + kNearestStack];
+            GroupStats st;
+            const GroupBest got = group_traverse(top.nodes.data(), (int64_t)top.nodes.size(), recs.data(), g,
+                                                 [&](int i) -> uint32_t & { return stack[i]; }, st);
+            const bool hit = want.instance != kGroupNoInstance;
+            hits += hit;
+            const bool same = want.instance == got.instance && (!hit || (want.prim == got.prim && bits(want.t) == bits(got.t) &&
+                                                                          bits(want.u) == bits(got.u) && bits(want.v) == bits(got.v)));
+            if (!same) {
+                differ++;
+                CHECK(false, "ray %lld: brute (%u, %u, %a) traversal (%u, %u, %a)", (long long)k, want.instance, want.prim, want.t, got.instance, got.prim, got.t);
+            }
+            CHECK(st.max_top <= kGroupStack && st.max_top <= (top.depth > 0 ? top.depth - 1 : 0), "ray %lld: %d top entries", (long long)k, st.max_top);
+            CHECK(st.max_stack <= kNearestStack, "ray %lld: %d object entries", (long long)k, st.max_stack);
+            if (st.max_top > max_top) max_top = st.max_top;
+            if (st.max_stack > max_stack) max_stack = st.max_stack;
+            uint32_t *r = &out[10 * (size_t)k];
+            r[0] = want.instance; r[1] = hit ? want.prim : kNearestNoPrim; r[2] = bits(hit ? want.t : 0.0f);
+            r[3] = got.instance; r[4] = got.instance != kGroupNoInstance ? got.prim : kNearestNoPrim; r[5] = bits(got.instance != kGroupNoInstance ? got.t : 0.0f);
+            r[6] = (uint32_t)st.top_nodes; r[7] = (uint32_t)st.instances; r[8] = (uint32_t)st.max_top; r[9] = (uint32_t)st.max_stack;
+        }
+        tally->hits = hits; tally->differ = differ; tally->max_top = max_top; tally->max_stack = max_stack;
+    };
+    int threads = (int)std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : threads > 16 ? 16 : threads;
+    if (M * (placed_tris + count + 1) < 4000000) threads = 1;
+    std::vector<Tally> tallies((size_t)threads);
+    if (threads == 1) {
+        work(0, M, &tallies[0]);
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < threads; t++) pool.emplace_back(work, M * t / threads, M * (t + 1) / threads, &tallies[(size_t)t]);
+        for (std::thread &t : pool) t.join();
+    }
     int64_t hits = 0, differ = 0;
     int max_top = 0, max_stack = 0;
-    for (int64_t k = 0; k < M; k++) {
-        float w[7];
-        memcpy(w, &rays[9 * (size_t)k], 28);
-        const float o[3] = { w[0], w[1], w[2] }, d[3] = { w[3], w[4], w[5] };
-        GroupRay g;
-        g.w = nearest_ray(o, d, w[6], rays[9 * (size_t)k + 8]);
-        g.skip_instance = rays[9 * (size_t)k + 7];
-        const GroupBest want = group_brute(by_instance.data(), count, g);
-        uint32_t stack[kGroupStack + kNearestStack];
-        GroupStats st;
-        const GroupBest got = group_traverse(top.nodes.data(), (int64_t)top.nodes.size(), recs.data(), g,
-                                             [&](int i) -> uint32_t & { return stack[i]; }, st);
-        const bool hit = want.instance != kGroupNoInstance;
-        hits += hit;
-        const bool same = want.instance == got.instance && (!hit || (want.prim == got.prim && bits(want.t) == bits(got.t) &&
-                                                                      bits(want.u) == bits(got.u) && bits(want.v) == bits(got.v)));
-        if (!same) {
-            differ++;
-            CHECK(false, "ray %lld: brute (%u, %u, %a) traversal (%u, %u, %a)", (long long)k, want.instance, want.prim, want.t, got.instance, got.prim, got.t);
-        }
-        CHECK(st.max_top <= kGroupStack && st.max_top <= (top.depth > 0 ? top.depth - 1 : 0), "ray %lld: %d top entries", (long long)k, st.max_top);
-        CHECK(st.max_stack <= kNearestStack, "ray %lld: %d object entries", (long long)k, st.max_stack);
-        if (st.max_top > max_top) max_top = st.max_top;
-        if (st.max_stack > max_stack) max_stack = st.max_stack;
-        uint32_t *r = &out[10 * (size_t)k];
-        r[0] = want.instance; r[1] = hit ? want.prim : kNearestNoPrim; r[2] = bits(hit ? want.t : 0.0f);
-        r[3] = got.instance; r[4] = got.instance != kGroupNoInstance ? got.prim : kNearestNoPrim; r[5] = bits(got.instance != kGroupNoInstance ? got.t : 0.0f);
-        r[6] = (uint32_t)st.top_nodes; r[7] = (uint32_t)st.instances; r[8] = (uint32_t)st.max_top; r[9] = (uint32_t)st.max_stack;
+    for (const Tally &t : tallies) {
+        hits += t.hits; differ += t.differ;
+        if (t.max_top > max_top) max_top = t.max_top;
+        if (t.max_stack > max_stack) max_stack = t.max_stack;
     }
     f = fopen(argv[3], "wb");
     ok = f && (out.empty() || fwrite(out.data(), 4, out.size(), f) == out.size());
     if (f) fclose(f);
     if (!ok) { fprintf(stderr, "cannot write %s\n", argv[3]); return 2; }
-    if (fails) { printf("%d checks failed\n", fails); return 1; }
+    if (fails) { printf("%d checks failed\n", (int)fails); return 1; }
+    printf("levels:");                                                   // the root's level first: what the update's plan is made from
+    for (size_t l = offset.size() - 1; l >= 1; l--) printf(" %lld", (long long)(offset[l] - offset[l - 1]));
+    printf("\n");
     printf("ok group: instances %lld parked %lld top_leaf %d scene_leaf %d depth %d top_nodes %zu rays %lld hits %lld differ %lld max_top %d max_stack %d\n",
            (long long)count, (long long)parked, top_leaf, scene_leaf, top.depth, top.nodes.size(), (long long)M, (long long)hits,
            (long long)differ, max_top, max_stack);

@@ -1,7 +1,8 @@
-"""builds and drives tests/native/nearest_group_host_check.cpp for test_nearest_group_host.py and test_gpu_nearest_group_edges.py: a
-stand-alone host program (g++, -ffp-contract=off, no HIP), plain or under the address and undefined-behaviour sanitizers.  A
-group (nearest_group_util.Inst's over shared meshes) and a ray stream go in as raw little-endian files; the program's brute force
-and the library's two-level traversal come back as arrays.  pytest does not collect this module."""
+"""builds and drives tests/native/nearest_group_host_check.cpp for test_nearest_group_host.py, test_gpu_nearest_group_edges.py and
+test_gpu_nearest_group_update_edges.py: a stand-alone host program (g++, -ffp-contract=off, no HIP), plain or under the address and
+undefined-behaviour sanitizers.  A group (nearest_group_util.Inst's over shared meshes) and a ray stream go in as raw
+little-endian files; the program's brute force and the library's two-level traversal come back as arrays.  pytest does not
+collect this module."""
 import re
 import subprocess
 from pathlib import Path
@@ -11,7 +12,7 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 SOURCE = ROOT / "tests" / "native" / "nearest_group_host_check.cpp"
-FLAGS = ["-std=c++14", "-Wall", "-Werror", "-ffp-contract=off"]
+FLAGS = ["-std=c++14", "-Wall", "-Werror", "-ffp-contract=off", "-pthread"]
 NO_PRIM = NO_INSTANCE = 0xFFFFFFFF
 
 
@@ -49,7 +50,8 @@ LINE = re.compile(r"ok group: instances (\d+) parked (\d+) top_leaf (\d+) scene_
 
 def run(exe, group_path, o, d, m=None, skip=None, top_leaf=2, scene_leaf=4):
     """-> instance, prim uint32 [M] (NO_INSTANCE / NO_PRIM: no hit), t float32 [M]: the program's brute force; tree_instance,
-    tree_prim, tree_t: the traversal; ray_top_nodes, entered, ray_max_top, ray_max_stack [M]; and the fields of its last line"""
+    tree_prim, tree_t: the traversal; ray_top_nodes, entered, ray_max_top, ray_max_stack [M]; levels: the top tree's node counts,
+    the root's level first; and the fields of its last line"""
     group_path = Path(group_path)
     _runs[0] += 1
     rays, out = group_path.with_name(f"grays{_runs[0]}.bin"), group_path.with_name(f"gout{_runs[0]}.bin")
@@ -71,6 +73,9 @@ def run(exe, group_path, o, d, m=None, skip=None, top_leaf=2, scene_leaf=4):
     assert head, p.stdout
     names = ("instances", "parked", "top_leaf", "scene_leaf", "depth", "top_nodes", "rays", "hits", "differ", "max_top", "max_stack")
     r = SimpleNamespace(**{k: int(v) for k, v in zip(names, head.groups())})
+    levels = p.stdout.splitlines()[-2].split()
+    assert levels[0] == "levels:", p.stdout
+    r.levels = [int(v) for v in levels[1:]]                          # the top tree's nodes level by level, the root's first
     r.instance, r.prim, r.t = w[:, 0].copy(), w[:, 1].copy(), w[:, 2].copy().view("<f4")
     r.tree_instance, r.tree_prim, r.tree_t = w[:, 3].copy(), w[:, 4].copy(), w[:, 5].copy().view("<f4")
     r.ray_top_nodes, r.entered, r.ray_max_top, r.ray_max_stack = (w[:, k].astype(np.int64) for k in (6, 7, 8, 9))

@@ -269,9 +269,13 @@ def exact_instances(mesh, n=6, seed=3):
     return out
 
 
+def line_triangle():
+    return U.Mesh([(0, -1, -1), (0, 1, -1), (0, 0, 1)], [(0, 1, 2)], surface=[1])
+
+
 def line_instances(n, step=1.0):
     """n one-triangle instances along x, the triangle facing -x... +x rays: instance j's triangle in the plane x = j * step"""
-    tri = U.Mesh([(0, -1, -1), (0, 1, -1), (0, 0, 1)], [(0, 1, 2)], surface=[1])
+    tri = line_triangle()
     if n == 0:
         return []
     B = np.tile(IDENTITY, (n, 1, 1))
@@ -280,6 +284,124 @@ def line_instances(n, step=1.0):
     A[:, 0, 3] = -B[:, 0, 3]
     wlo, whi = world_box(B, *mesh_box(tri))
     return [Inst(tri, B[j], A[j], base=j, world=(wlo[j], whi[j])) for j in range(n)]
+
+
+def placed(mesh, A, B, bases=None):
+    """n placements of ONE mesh at once: A, B float32 [n, 3, 4], the world boxes by world_box over all of them (a NaN or an inf
+    among the matrices, or a box that overflows, parks its instance as the statement says); surface bases j unless given"""
+    A, B = np.asarray(A, F).reshape(-1, 3, 4), np.asarray(B, F).reshape(-1, 3, 4)
+    wlo, whi = world_box(B, *mesh_box(mesh))
+    return [Inst(mesh, B[j], A[j], base=j if bases is None else bases[j], world=(wlo[j], whi[j])) for j in range(B.shape[0])]
+
+
+def coincident():
+    """three general placements of the icosphere with instance 0 again as 2 and 5 and instance 1 again as 4, under bases of their
+    own: every hit of 0 or 1 ties with its copies at the same t bits, and the smaller j wins"""
+    i = general_instances(U.icosphere(1), 3, seed=8)
+    return [i[0], i[1], Inst(i[0].mesh, i[0].B, i[0].A, base=50), i[2], Inst(i[1].mesh, i[1].B, i[1].A, base=60),
+            Inst(i[0].mesh, i[0].B, i[0].A, base=70)]
+
+
+# ---- the update's launch plan, read from a top tree's links (rls_nearest_group_update in group.hip) ----------------------------------
+BLOCK = 256
+
+
+def level_sizes(links):
+    """links uint32 [top_nodes, 2] (first, meta) of read_tree -> the node count of every level, the root's first"""
+    first, count = links[:, 0].astype(np.int64), links[:, 1].astype(np.int64) & 0xFF
+    sizes, level = [], np.zeros(1, np.int64)
+    while level.size:
+        sizes.append(int(level.size))
+        inner = first[level[count[level] == 0]]
+        level = np.concatenate([inner, inner + 1])
+    assert sum(sizes) == links.shape[0]
+    return sizes
+
+
+def update_plan(sizes):
+    """-> (wide, folded): the levels from the root down of at most BLOCK nodes each run in ONE single-workgroup launch where there
+    are two or more of them (`folded`); every deeper level, and a lone level, is a launch of its own (`wide`)"""
+    trailing = 0
+    while trailing < len(sizes) and sizes[trailing] <= BLOCK:
+        trailing += 1
+    folded = trailing if trailing >= 2 else 0
+    return len(sizes) - folded, folded
+
+
+# the update's edge cases (test_gpu_nearest_group_update_edges.py; the plans are pinned on the CPU by test_nearest_group_host.py):
+# instances, top leaf -> the node count of every level of the top tree over line_instances(n), the root's first.  Levels of more
+# than BLOCK nodes are launched one by one, and so is every level below one; the rest is the single-workgroup launch.
+_POWERS = [1, 2, 4, 8, 16, 32, 64, 128, 256]
+PLANS = {
+    (1, 1): [1],                                                     # depth 1: nothing folded, one level launch
+    (2, 1): [1, 2],                                                  # everything folded
+    (256, 1): _POWERS,                                               # a deepest level of exactly BLOCK nodes: everything folded
+    (257, 1): _POWERS + [2],                                         # one leaf more: a tenth level of two nodes, still all folded
+    (384, 1): _POWERS + [256],                                       # two levels of exactly BLOCK nodes: the last all-folded plan
+    (385, 1): _POWERS + [258],                                       # the first plan with a wide level (a level grows by two nodes)
+    (600, 1): _POWERS + [512, 176],                                  # a wide level of two tiles beside a narrow deepest level
+    (1500, 4): _POWERS + [512],                                      # leaves of 2 and 3 records, a wide level of them
+    (MAX_INSTANCES, 1): _POWERS + [512 << k for k in range(8)],      # 17 levels, 8 of them wide
+}
+
+
+def line_moves(n, kind):
+    """new matrices for line_instances(n), exact in float32 -> A, B float32 [n, 3, 4].  shift: a non-uniform scale and a step of
+    3/4; reverse: the line backwards, so that the tree built over the old line holds the instances the wrong way round; point:
+    every placement shrunk onto the one point (3, 0, 0) -- every box of the old tree then holds the same box"""
+    L, t = np.eye(3), np.zeros((n, 3))
+    j = np.arange(n, dtype=np.float64)
+    if kind == "shift":
+        L = np.diag([1.0, 2.0, 0.5])
+        t[:, 0], t[:, 1], t[:, 2] = 0.75 * j + 0.5, 0.25, -0.125
+    elif kind == "reverse":
+        t[:, 0] = (n - 1) - j
+    elif kind == "point":
+        L = np.eye(3) * 0.5
+        t[:, 0] = 3.0
+    else:
+        raise ValueError(kind)
+    B = np.tile(affine(L), (n, 1, 1))
+    B[:, :, 3] = t
+    A = np.tile(affine(np.linalg.inv(L)), (n, 1, 1))
+    A[:, :, 3] = -t @ np.linalg.inv(L).T
+    return A.astype(F), B.astype(F)
+
+
+def park(A, B, which):
+    """in place: the instances `which` (indices) parked three ways in turn -- a NaN in A, an inf in B, and a B of finite entries
+    under which the line's triangle (y and z in [-1, 1]) has a world box that overflows"""
+    for k, j in enumerate(which):
+        r = k // 3
+        if k % 3 == 0:
+            A[j, r % 3, (r // 3) % 4] = np.nan
+        elif k % 3 == 1:
+            B[j, r % 3, (r // 3) % 4] = np.inf if r % 2 else -np.inf
+        else:
+            B[j, 1, 1] = B[j, 1, 2] = F(3e38)
+    return A, B
+
+
+def parked_pattern(n):
+    """about one instance in seven, by tile of BLOCK instances: tile 0, 3, 6, .. park none; tile 1, 4, .. every fourth instance
+    (16 in each of the tile's four waves); tile 2, 5, .. every other instance of its second wave alone -- and the same goes for
+    a last partial tile"""
+    j = np.arange(n)
+    tile, lane = j // BLOCK, j % BLOCK
+    return np.flatnonzero(((tile % 3 == 1) & (lane % 4 == 0)) | ((tile % 3 == 2) & (lane // 64 == 1) & (lane % 2 == 1)))
+
+
+def line_stream(x_lo, x_hi, K=512, seed=1):
+    """K rays along a line of placed triangles between x_lo and x_hi: from points near the axis along +-x with a small drift (they
+    cross the next triangle's plane inside it), a tenth of them well off the axis; reaches +inf or about the step
+    -> o, d float32 [3, K], m [K]"""
+    rng = np.random.default_rng(seed)
+    o = np.stack([rng.uniform(x_lo - 1.0, x_hi + 1.0, K), rng.uniform(-0.25, 0.45, K), rng.uniform(-0.4, -0.15, K)])
+    d = np.stack([rng.choice([-1.0, 1.0], K), rng.uniform(-0.02, 0.02, K), rng.uniform(-0.02, 0.02, K)]) * rng.uniform(0.5, 2.0, K)
+    off = rng.random(K) < 0.1
+    o[1, off] += 5.0
+    m = np.where(rng.random(K) < 0.4, np.inf, rng.uniform(0.2, 3.0, K))
+    return o.astype(F), d.astype(F), m.astype(F)
 
 
 def bake(insts):

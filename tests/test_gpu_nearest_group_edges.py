@@ -5,7 +5,9 @@
      lane 37 alone crosses every instance's box without hitting a triangle (it opens all 131071 top nodes) among 63 lanes that miss
      the root; a wavefront of 64 identical stack-filling rays (the ray along the line holds 16 top entries on its way to instance 0);
      the rays of the CPU test.  Every result equals the CPU program's (tests/native/nearest_group_host_check.cpp: the same
-     traversal source, held to its brute force there), and the stack-filling ray's is instance 0 at t = 1."""
+     traversal source, held to its brute force there), and the stack-filling ray's is instance 0 at t = 1;
+  C. both stacks live in one lane: three exact translations of the deep grid (23 levels at leaf 1) under its stack-filling stream,
+     where a ray fills the object rows of the kernel's stack array while it holds entries in the top rows."""
 import numpy as np
 import pytest
 import torch
@@ -21,6 +23,8 @@ from test_gpu_nearest_group import SCALAR, VEC, DeviceGroup, all_bytes, mesh_of,
 
 pytestmark = pytest.mark.gpu
 TILE = 256
+DEEP_BOTH = 106                                                      # rays at 22 object entries while a top entry is held
+DEEP_HITS = 394
 
 
 @pytest.fixture(scope="module")
@@ -106,3 +110,43 @@ def test_the_deepest_top_tree_once(gpu_ctx, tmp_path):
     assert (_host(f.instance)[64:128] == 0).all() and (_host(f.t)[64:128] == 1.0).all()
     assert np.array_equal(_host(f.instance).view(np.uint32)[128:][hit[128:]], want[hit[128:]]) and np.array_equal(hit[128:], want != G.NO_INSTANCE)
     assert np.array_equal(_host(f.surface).view(np.uint32)[hit], r.tree_instance[hit] + 1)      # base j + the mesh's surface id 1
+
+
+def deep_three():
+    """three exact translations of the deep grid (2^21 + 20 triangles; 23 levels and an object stack of 22 at leaf 1) and its
+    577-ray stack-filling stream, ray k mapped to the world of instance k % 3 and skipping its triangle there"""
+    mesh = U.deep_grid()
+    shifts = ((-1.25, 0.5, 0.0), (1.0, -0.25, 0.75), (0.25, 1.5, -0.5))
+    insts = [G.Inst(mesh, G.affine(t=t), G.affine(t=[-x for x in t]), base=5000 * j) for j, t in enumerate(shifts)]
+    o, d, m, skip, _ = U.deep_stream(mesh)
+    j = np.arange(d.shape[1]) % len(insts)
+    o = (o + np.array(shifts, F)[j].T).astype(F)
+    return mesh, insts, o, d, m, (np.where(skip == U.NO_PRIM, G.NO_INSTANCE, j).astype(np.uint32), skip)
+
+
+def test_both_stacks_live_in_one_lane(gpu_ctx, tmp_path):
+    """The kernel keeps a lane's top stack in rows 0 .. 15 of one LDS array and its object stack in rows 16 .. 39.  Over one-triangle
+    scenes the object rows stay empty; here a corner ray holds a top entry (the sibling of the instance it is in) while it fills
+    all 22 object entries its tree has use for, and must find that top entry again afterwards.  Expected: the CPU program's brute
+    force over the statement; the device equals it bit for bit on every ray."""
+    mesh, insts, o, d, m, skip = deep_three()
+    r = H.run(H.build(tmp_path), H.write_group(tmp_path / "deep.bin", insts), o, d, m, skip, top_leaf=1, scene_leaf=1)
+    both = (r.ray_max_stack == 22) & (r.ray_max_top >= 1)
+    print("rays at full object stack holding a top entry:", int(both.sum()), "max_top", r.max_top, "hits", r.hits)
+    assert r.differ == 0 and r.depth == 3 and r.max_stack == 22 and both.sum() == DEEP_BOTH and r.hits == DEEP_HITS
+    assert 0.2 < r.hit.mean() < 0.98
+    g = DeviceGroup(gpu_ctx, insts, leaf=1, scene_leaf=1)
+    try:
+        f, last, last_instance = query(gpu_ctx, g.group, o, d, m, skip)
+    finally:
+        g.close()
+    hit = _host(f.hit) != 0
+    assert np.array_equal(hit, r.hit)
+    assert np.array_equal(_host(f.instance).view(np.uint32)[hit], r.instance[hit])
+    assert np.array_equal(_host(f.prim).view(np.uint32)[hit], r.prim[hit])
+    assert np.array_equal(_host(f.t).view(np.uint32)[hit], r.t.view(np.uint32)[hit])
+    base = np.array([i.base for i in insts], np.uint32)
+    assert np.array_equal(_host(f.surface).view(np.uint32)[hit], base[r.instance[hit]] + mesh.surface[r.prim[hit]])
+    assert np.array_equal(_host(last_instance).view(np.uint32), np.where(hit, r.instance, skip[0]))
+    assert np.array_equal(_host(last).view(np.uint32), np.where(hit, r.prim, skip[1]))
+

@@ -6,7 +6,8 @@ prim, t): the C++ restatement and the numpy one are the same function.  The grou
 smaller j wins every tie); a skip pair; parked instances (a NaN matrix, an inf matrix, an empty scene); a singular to_object;
 hostile rays (NaN / inf / zero / -0 components, NaN reach, reach 0) in every stream.  The program also checks the top builder
 (deterministic, the depth bound, every instance in one leaf) and that the update's union restated on the host gives the
-builder's boxes by value (a zero's sign may differ: rls_nearest_refit.hpp) -- at 1, 2, 3, 5 and 2^16 instances too.  The same
+builder's boxes by value (a zero's sign may differ: rls_nearest_refit.hpp) -- at 1, 2, 3, 5 and 2^16 instances too -- and it prints
+the top tree's level sizes, from which the update's launch plans of test_gpu_nearest_group_update_edges.py are pinned here.  The same
 program runs once more under the address and undefined-behaviour sanitizers, on fewer rays; nothing is loaded into Python.
 
 At 2^16 one-triangle instances on a line (top leaf 1: 17 levels) no ray holds more than 16 top entries and the ray along the
@@ -51,12 +52,6 @@ def _two_meshes():
     return [v for pair in zip(x, y) for v in pair]
 
 
-def _coincident():
-    i = G.general_instances(U.icosphere(1), 3, seed=8)
-    return [i[0], i[1], G.Inst(i[0].mesh, i[0].B, i[0].A, base=50), i[2], G.Inst(i[1].mesh, i[1].B, i[1].A, base=60),
-            G.Inst(i[0].mesh, i[0].B, i[0].A, base=70)]
-
-
 def _parked():
     mesh = U.icosphere(1)
     live = G.general_instances(mesh, 4, seed=12)
@@ -69,7 +64,7 @@ def _parked():
 
 
 GROUPS = {"one": lambda: _general(1), "two": lambda: _general(2), "three": lambda: _general(3), "five": lambda: _general(5),
-          "sixty_four": lambda: _general(64, U.icosphere(1)), "two_meshes": _two_meshes, "coincident": _coincident, "parked": _parked}
+          "sixty_four": lambda: _general(64, U.icosphere(1)), "two_meshes": _two_meshes, "coincident": G.coincident, "parked": _parked}
 
 
 @pytest.mark.parametrize("name", list(GROUPS))
@@ -112,6 +107,26 @@ def test_small_top_trees(programs, n):
             assert r.instance[0] == 0 and r.prim[0] == 0 and r.t[0] == 1.0
 
 
+@pytest.mark.parametrize("n,leaf", [k for k in G.PLANS if k[0] < G.MAX_INSTANCES])
+def test_the_update_plans_of_the_edge_cases(programs, n, leaf):
+    """the level sizes the update's launch plan is made from, for the instance counts of test_gpu_nearest_group_update_edges.py:
+    a change of the builder that changes a plan fails here, without a GPU.  The parked pattern's instances are parked by the
+    program's group_record as by the numpy statement."""
+    d, plain, _ = programs
+    A, B = G.line_moves(n, "shift")
+    which = G.parked_pattern(n)
+    insts = G.placed(G.line_triangle(), *G.park(A, B, which))
+    o, d_, m = G.line_stream(0.0, 0.75 * n, K=64)
+    for new in (G.line_instances(n), insts):
+        r = H.run(plain, H.write_group(d / f"plan{n}.bin", new), o, d_, m, top_leaf=leaf, scene_leaf=1)
+        assert r.differ == 0 and r.parked == sum(i.parked for i in new)
+        if new is not insts:
+            assert r.levels == G.PLANS[n, leaf] and len(r.levels) == r.depth and sum(r.levels) == r.top_nodes
+    assert sum(i.parked for i in insts) == which.size and np.array_equal(np.flatnonzero([i.parked for i in insts]), which)
+    wide, folded = G.update_plan(G.PLANS[n, leaf])
+    assert (wide, folded) == {1: (1, 0), 2: (0, 2), 256: (0, 9), 257: (0, 10), 384: (0, 10), 385: (1, 9), 600: (2, 9), 1500: (1, 9)}[n]
+
+
 def test_the_deepest_top_tree_fills_the_top_stack(programs):
     d, plain, san = programs
     n = G.MAX_INSTANCES
@@ -119,7 +134,7 @@ def test_the_deepest_top_tree_fills_the_top_stack(programs):
     o, dd, want = line_rays(n)
     for exe in (plain, san):
         r = H.run(exe, path, o, dd, top_leaf=1, scene_leaf=1)
-        assert r.differ == 0 and r.depth == 17 and r.top_nodes == 2 * n - 1
+        assert r.differ == 0 and r.depth == 17 and r.top_nodes == 2 * n - 1 and r.levels == G.PLANS[n, 1]
         assert r.max_top == G.GROUP_STACK and r.ray_max_top[0] == r.depth - 1 and (r.ray_max_top <= G.GROUP_STACK).all()
         assert np.array_equal(r.instance, want)
         assert r.t[0] == 1.0 and r.prim[0] == 0
