@@ -136,7 +136,24 @@ def hostile_pair(nt, seed=9):
     return a.V, B, a.tri
 
 
-PAIRS = dict(random=random_pair, identical=identical_pair, flat=flat_pair, huge=huge_pair)
+def subnormal_pair(nt):
+    """B: a soup scaled by 2^-128: every non-zero coordinate is denormal, and so is every centroid sum lo + hi and every extent
+    kmax - kmin.  An add or a subtract that flushed denormals would make every key tie and every extent zero: axis 0 everywhere,
+    the order the ids' -- the tree of the identical mesh, not the builder's"""
+    a, b = _soup(nt, 5), _soup(nt, 6)
+    assert np.array_equal(a.tri, b.tri)
+    B = (b.V.astype(np.float64) * 2.0 ** -128).astype(F)
+    if nt >= 1000:
+        assert (np.abs(B[B != 0]) < 1.1754944e-38).all() and (B != 0).mean() > 0.99
+        P = B[a.tri.astype(np.int64)]
+        ctr = P.min(axis=1) + P.max(axis=1)
+        assert (np.abs(ctr) < 1.2e-38).all()
+        for c in range(3):
+            assert np.unique(ctr[:, c]).size > nt - 4, (c, np.unique(ctr[:, c]).size)
+    return a.V, B, a.tri
+
+
+PAIRS = dict(random=random_pair, identical=identical_pair, flat=flat_pair, huge=huge_pair, subnormal=subnormal_pair)
 
 
 def parked_of(B, tri):

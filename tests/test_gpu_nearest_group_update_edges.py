@@ -21,7 +21,9 @@ a sentinel) equal the inputs'; about 512 rays return, in every plane, the bytes 
 group_np (2^16: the host program's brute force).  From 384 instances on about one instance in seven is parked -- a NaN in A, an
 inf in B, a finite B whose box overflows -- so that some workgroups park none, some in all four waves, some in one wave, and the
 last partial tile some.  Also: the line reversed and every placement shrunk onto one point (the old tree is then as bad as it
-can be); update(None, None) after a member scene's refit at 600; two updates in a row without a query between."""
+can be); update(None, None) after a member scene's refit at 600, and after a member scene's REBUILD (600 placements of the
+icosphere, twisted and carried out of its old box: records permuted and axes rewritten under the group), twice more with no
+query between; two updates in a row without a query between."""
 import numpy as np
 import pytest
 import torch
@@ -30,6 +32,7 @@ import rlshaders_amd as R
 import nearest_group_host_util as H
 import nearest_group_util as G
 import nearest_util as U
+from nearest_refit_util import twisted
 from nearest_util import F
 from test_gpu_nearest import _dev, _host
 from test_gpu_nearest_group import DeviceGroup, all_bytes, check_found, query
@@ -40,8 +43,8 @@ SENTINEL = -0x5A5A5A5A5A5A5A5B
 
 @pytest.fixture(scope="module")
 def ctx():
-    from rlshaders_amd import nearest_group, nearest_refit
-    nearest_group.load(), nearest_refit.load()                       # (a missing library is an error, not a build)
+    from rlshaders_amd import nearest_group, nearest_rebuild, nearest_refit
+    nearest_group.load(), nearest_refit.load(), nearest_rebuild.load()          # (a missing library is an error, not a build)
     c = R.Context(0)
     yield c
     c.close()
@@ -205,6 +208,62 @@ def test_the_matrices_stay_after_a_refit_of_the_member_scene(ctx):
         assert 0.2 < (h.hit != 0).mean() < 0.98 and not np.array_equal(h.t, G.group_np(old, o, d, m).t)
         check_found(f, h, d.shape[1], "refit")
         refit.close()
+    finally:
+        g.close()
+
+
+def test_the_matrices_stay_after_a_rebuild_of_the_member_scene(ctx):
+    """the rebuild's twin of the test above, on a mesh whose tree a move can change: 600 placements of the 80-triangle icosphere
+    along the line.  The member scene is rebuilt for the mesh twisted by 2 rad and carried outside its old root box -- the
+    records under the group are permuted and split axes rewritten, which no refit does -- then update(None, None)"""
+    from rlshaders_amd import nearest_rebuild
+    n = 600
+    line = G.line_instances(n)
+    mesh = U.icosphere(1)
+    old = G.placed(mesh, *G.matrices(line), bases=[i.base for i in line])
+    g = DeviceGroup(ctx, old, leaf=1, scene_leaf=1)
+    try:
+        assert check_plan(g.group, n, 1) == (2, 9)
+        rb = nearest_rebuild.Rebuild(g.scenes[id(mesh)])
+        _, links0, prims0 = rb.read_tree()
+        V = (twisted(mesh.V, 2.0).astype(np.float64) + np.array([3.0, 0.5, 0.0])).astype(F)
+        lo0, hi0 = G.mesh_box(mesh)
+        assert V[:, 0].min() > hi0[0] + 1.0                           # well outside the old root box
+        rb.update(_dev(V))
+        _, links, prims = rb.read_tree()
+        assert np.array_equal(np.sort(prims), np.arange(mesh.nt)) and links.shape == links0.shape
+        assert not np.array_equal(prims, prims0) or not np.array_equal(links, links0)       # another order or other axes: no refit's tree
+        parked = sentinel()
+        g.group.update(None, None, parked=parked)
+        moved = U.Mesh(V, mesh.tri, surface=mesh.surface, normals=mesh.normals)
+        new = G.placed(moved, *G.matrices(old), bases=[i.base for i in old])
+        o, d, m = G.line_stream(0.0, float(n), seed=9)
+        h, still = G.group_np(new, o, d, m), G.group_np(old, o, d, m)
+        assert 0.2 < (h.hit != 0).mean() < 0.98 and not np.array_equal(h.hit, still.hit)
+        fresh = DeviceGroup(ctx, new, leaf=1, scene_leaf=1)
+        try:
+            want = all_bytes(query(ctx, fresh.group, o, d, m)[0])
+
+            def check():
+                f, _, _ = query(ctx, g.group, o, d, m)
+                check_tree(g.group, new, fresh.group, parked, np.zeros(0, np.int64))
+                for x, y in zip(all_bytes(f), want):
+                    assert np.array_equal(x, y)
+                check_found(f, h, d.shape[1], "rebuild")
+                assert not np.array_equal(_host(f.hit), still.hit)
+                return g.group.read_tree()
+
+            once = check()
+            # twice more with no query between the two: nothing changes
+            parked.fill_(SENTINEL)
+            g.group.update(None, None)
+            g.group.update(None, None, parked=parked)
+            for x, y in zip(check(), once):
+                assert np.array_equal(x.view(np.uint8), y.view(np.uint8))
+            assert g.group.info()["updates"] == 3
+        finally:
+            fresh.close()
+        rb.close()
     finally:
         g.close()
 

@@ -4,7 +4,8 @@ throughout, its tree read through a nearest_refit.Refit(fresh).read_tree(): link
 in leaf order exactly, the boxes by value.
 
 The shapes of the CPU check (nt in {0, 1, leaf, leaf + 1, 2 leaf + 1, 11, 1000, 4099} x leaf in {1, 3, 4, 8} on the random, the
-identical, the flat and the huge mesh); nt about the sort's and the scan's tile of 256 elements (255, 256, 257, 769: the three
+identical, the flat, the huge and the subnormal mesh -- five meshes; on the last the device's key add and extent subtract must
+keep denormals, or every key ties); nt about the sort's and the scan's tile of 256 elements (255, 256, 257, 769: the three
 lists are one array of 3 nt positions, so the scan's tiles end at other places than the sort's, which are a list's own) and a
 deep tree, nt = 65 539 at leaf 1 (17 rounds, a scan whose tile sums take more than one run of the single workgroup).  Queries of
 both entry points after a 2 rad twist, `last` set before the rebuild; the traversal's cost; hostile vertices; the interplay with
@@ -84,7 +85,7 @@ def test_the_rebuilt_tree_is_a_fresh_scenes(ctx, name, leaf):
 @pytest.mark.parametrize("leaf", [1, 4])
 @pytest.mark.parametrize("nt", [TILE - 1, TILE, TILE + 1, 3 * TILE + 1])
 def test_sizes_at_the_tile_edges(ctx, nt, leaf):
-    for name in ("random", "flat"):
+    for name in ("random", "flat", "subnormal"):
         A, B, tri = PAIRS[name](nt)
         got, want = rebuilt_tree(ctx, A, B, tri, leaf), fresh_tree(ctx, B, tri, leaf)
         assert same_tree(got, want) is None, (name, leaf, nt, same_tree(got, want))

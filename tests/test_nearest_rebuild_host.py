@@ -5,9 +5,10 @@ sort, the axis from the list ends, a stable partition a level, the leaves' ids s
 nearest_build on B: first, meta (the axis bits included) and the order of the triangle ids exactly, the boxes by value, the
 records bit for bit; a rebuild back to A gives the tree built on A; a tree of another shape is refused.
 
-nt in {0, 1, leaf, leaf + 1, 2 leaf + 1, 11, 1000, 4099} x leaf in {1, 3, 4, 8}, on four meshes: random; every triangle the same
+nt in {0, 1, leaf, leaf + 1, 2 leaf + 1, 11, 1000, 4099} x leaf in {1, 3, 4, 8}, on five meshes: random; every triangle the same
 (every key ties: the order is the ids'); a flat grid in z = 0 with zeros of both signs and negative coordinates; coordinates
-near +-3e38 (a centroid sum of +-inf, an extent of NaN).  And vertices with NaN and infinities: the parked triangles stand at the
+near +-3e38 (a centroid sum of +-inf, an extent of NaN); a soup scaled by 2^-128 (every coordinate, centroid sum and extent is
+denormal: the tree still splits along all three axes).  And vertices with NaN and infinities: the parked triangles stand at the
 origin.  The same stand-alone program runs once more under the address and undefined-behaviour sanitizers; nothing is loaded
 into Python."""
 import numpy as np
@@ -38,6 +39,8 @@ def test_rebuild_on_the_host_is_the_builders_tree(programs, name, leaf):
             assert r["axes"][2] == 0 and r["axes"][0] and r["axes"][1], r      # no extent in z: never the longest
         if name == "identical" and nt > leaf:
             assert r["axes"] == [r["nodes"] // 2, 0, 0], r                      # every extent is zero: axis 0 everywhere
+        if name == "subnormal" and nt >= 1000:
+            assert all(r["axes"]), r                                            # a flushed key or extent: the identical mesh's axes
 
 
 @pytest.mark.parametrize("leaf", LEAVES)
